@@ -11,7 +11,10 @@ exactly as one rank of the reference sweeps it (--ssor-blocks 1).  The same oper
 solved with the reference's smoother as 20 ranks apply it (block SSOR, the cluster runs), with
 Jacobi and with Chebyshev: `config.smoothers`.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2 [--workload atoms64000|atoms8000|atoms1000|atoms8|stress201]
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--workload atoms64000|atoms8000|atoms1000|atoms8|stress201] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step computed (DIR/solution.npy, DIR/iterations.npy; float64, at most 64 MB)
+for an output-for-output comparison of two builds: the inputs are generated, so the same arguments give the same problem.
 
 --gpus N > 1 started plainly (no RANK in the environment) starts its own N rank processes (torch.distributed.run as a
 child process, before this process touches torch or HIP) and relays rank 0's line.  When the box shows fewer GPUs than
@@ -82,7 +85,7 @@ def git_head():
     return None, f"STALE .bench_commit {' '.join(parts)}: the shipped sources hash to {live}"
 
 
-def spawn_ranks(n):
+def spawn_ranks(n, dump_outputs=None):
     """--gpus N > 1 without RANK in the environment: this process has not imported torch or touched HIP; it starts N rank
     processes as children (never replaces itself), relays rank 0's JSON line and returns the launcher's exit code."""
     import socket
@@ -94,6 +97,8 @@ def spawn_ranks(n):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    if dump_outputs:
+        cmd += ["--dump-outputs", dump_outputs]  # absolute: the ranks run in ROOT (the last occurrence wins)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, env=env, cwd=ROOT)
     line = None
     for raw in proc.stdout:
@@ -162,12 +167,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-every", type=int, default=8)
     ap.add_argument("--source-hash", action="store_true", help="print the hash of the measured sources and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the solution vector and the "
+                         "iteration counts) to DIR/<name>.npy, so that two builds can be compared output for output")
     args = ap.parse_args()
     if args.source_hash:
         print(source_hash())
         return 0
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # the rank processes start in ROOT
     if args.gpus > 1 and "RANK" not in os.environ:
-        return spawn_ranks(args.gpus)  # (nothing of torch / HIP has been touched in this process)
+        return spawn_ranks(args.gpus, args.dump_outputs)  # (nothing of torch / HIP has been touched in this process)
 
     # stdout carries exactly one line (the JSON of rank 0): whatever libraries print while the job runs
     # (RCCL prints a version banner at communicator creation) goes to stderr
@@ -337,6 +349,9 @@ def main():
         return dt, r, st
 
     dt, rep_t, st = timed_solves(p, ctx, args.steps, args.warmup, args.profile_every)
+    if args.dump_outputs and rank == 0:  # before the smoother table's solves overwrite the solution
+        names = dump_outputs(args.dump_outputs, p.vector("solution"), rep_t)
+        print(f"[bench] last timed step's outputs: {', '.join(n + '.npy' for n in names)} in {args.dump_outputs}", file=sys.stderr)
     hbm_read, hbm_copy = ctx.calibrate_hbm(1 << 30, 10) if rank == 0 else (0.0, 0.0)
 
     ms_per_step = dt / args.steps * 1e3
@@ -526,6 +541,30 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(d, solution, report):
+    """--dump-outputs: what the last timed step hands its caller, as DIR/<name>.npy (float64): `solution` (the whole
+    solution vector, or, beyond the size limit, a fixed seeded sample of it with the sampled indices in `solution_index`)
+    and `iterations` (outer CG iterations, coarse CG iterations)."""
+    import numpy as np
+
+    x = np.ascontiguousarray(solution, dtype=np.float64)
+    arrays = {"iterations": np.array([report["cg_iterations"], report["coarse_iterations"]], dtype=np.float64)}
+    budget = DUMP_LIMIT_BYTES - 4096  # (the .npy headers)
+    if x.nbytes <= budget:
+        arrays["solution"] = x
+    else:  # values and their indices, 8 bytes each
+        idx = np.sort(np.random.default_rng(0).choice(x.size, size=budget // 16, replace=False))
+        arrays["solution"] = x[idx]
+        arrays["solution_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def coarse_iteration_rate(ctx, n0, spmv_moved, fused):

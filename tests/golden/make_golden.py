@@ -36,7 +36,7 @@ LOGS = {
     "cluster/without_opti": "Cluster runs output and postprocessing/without_opti.o875054",
 }
 
-ATOM_FILES = ["tests/atom_n1_2.data", "tests/atom_2.data", "atom/atom_n1_8.data", "atom/atom_n3_216.data",
+ATOM_FILES = ["tests/atom_n1_2.data", "tests/atom_2.data", "atom/atom_n1_8.data", "atom/atom_n3_216.data", "atom/atom_n5_1000.data",
               # expected output of the reference's current regression test, compared line by line with ./step50_mi355x
               "tests/gaussian-charges.mpirun=1.output",
               # |rhs norm with cutoff lists - without| per cutoff (the setup of tests_rhs_rc_variation: 2 atoms, 16^3 cells)

@@ -27,6 +27,31 @@ def test_source_hash_is_stable_and_cheap():
     assert a == b and len(a) == 16 and int(a, 16) >= 0
 
 
+def test_dump_outputs_is_whole_when_small_and_a_fixed_sample_within_64_mb_when_large(tmp_path):
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rep = {"cg_iterations": 7, "coarse_iterations": 412}
+    x = np.arange(1000, dtype=np.float64) * 0.5
+    assert bench.dump_outputs(str(tmp_path / "small"), x, rep) == ["iterations", "solution"]
+    assert np.array_equal(np.load(tmp_path / "small" / "solution.npy"), x)
+    assert np.load(tmp_path / "small" / "iterations.npy").tolist() == [7.0, 412.0]
+
+    big = np.random.default_rng(3).standard_normal(10_000_000)  # 80 MB
+    for d in ("big1", "big2"):
+        assert bench.dump_outputs(str(tmp_path / d), big, rep) == ["iterations", "solution", "solution_index"]
+        files = list((tmp_path / d).iterdir())
+        assert sum(f.stat().st_size for f in files) <= 64_000_000
+        assert all(np.load(f).dtype == np.float64 for f in files)
+    s, i = np.load(tmp_path / "big1" / "solution.npy"), np.load(tmp_path / "big1" / "solution_index.npy")
+    assert np.array_equal(s, big[i.astype(np.int64)])
+    assert np.array_equal(i, np.load(tmp_path / "big2" / "solution_index.npy"))  # the same sample every run
+
+
 def test_plain_start_with_two_gpus_spawns_two_ranks_and_reports_their_failure():
     if _has_gpu():
         pytest.skip("GPU present: covered by test_two_and_three_ranks_share_the_gpu")
