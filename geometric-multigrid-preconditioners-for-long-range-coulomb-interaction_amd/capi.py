@@ -16,6 +16,7 @@ OK, ERR_INVALID, ERR_OUTER_NOCONV, ERR_COARSE_NOCONV, ERR_HIP, ERR_COMM, ERR_UNS
 SYSTEM = -1
 JACOBI, SSOR, CHEBYSHEV = 0, 1, 2
 PRECOND_GMG, PRECOND_JACOBI, PRECOND_IDENTITY = 0, 1, 2
+SSOR_PARTITION_ROWS, SSOR_PARTITION_BALANCED = 0, 1
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/gmg_coulomb.h declares (checked by tests/test_abi.py)
@@ -29,7 +30,8 @@ SYMBOLS = [
     "gmg_prolongate", "gmg_restrict_and_add", "gmg_cg_solve",
     "gmg_comm_unique_id", "gmg_comm_init", "gmg_comm_barrier", "gmg_comm_info", "gmg_set_halo_plan", "gmg_set_global_sizes", "gmg_partition_range",
     "gmg_vec_allgather",
-    "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
+    "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks",
+    "gmg_set_ssor_block_rows", "gmg_set_ssor_partition", "gmg_get_ssor_partition", "gmg_ssor_balance_rows", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
 ]
 
 
@@ -337,3 +339,32 @@ class Context:
     def set_option(self, key: str, value: float = 1.0):
         """Diagnostic / measurement options by name (include/gmg_coulomb.h: gmg_set_option)."""
         self._chk(self.L.gmg_set_option(self.h, key.encode(), C.c_double(value)))
+
+    def set_ssor_block_rows(self, level, block_row):
+        """Explicit SSOR block boundaries of one level (n_blocks + 1 entries; an empty list clears them)."""
+        b = np.ascontiguousarray(block_row, dtype=np.int64)
+        n_blocks = max(len(b) - 1, 0)
+        self._chk(self.L.gmg_set_ssor_block_rows(self.h, C.c_int(level), C.c_int(n_blocks), _p(b, C.c_int64) if len(b) else None))
+
+    def set_ssor_partition(self, kind):
+        self._chk(self.L.gmg_set_ssor_partition(self.h, C.c_int(kind)))
+
+    def get_ssor_partition(self, level):
+        """(block_row, block_steps) of the level's SSOR plan."""
+        nb = C.c_int(0)
+        self._chk(self.L.gmg_get_ssor_partition(self.h, C.c_int(level), C.byref(nb), None, None))
+        br, st = np.zeros(nb.value + 1, dtype=np.int64), np.zeros(max(nb.value, 1), dtype=np.int64)
+        self._chk(self.L.gmg_get_ssor_partition(self.h, C.c_int(level), C.byref(nb), _p(br, C.c_int64), _p(st, C.c_int64)))
+        return br, st[:nb.value]
+
+
+def ssor_balance_rows(m, n_blocks, use_values=True):
+    """gmg_ssor_balance_rows on a host CSR (needs no device): (block_row, modelled cost per block in us)."""
+    rp, col, val = _csr(m)
+    n = len(rp) - 1
+    br, cost = np.zeros(n_blocks + 1, dtype=np.int64), np.zeros(n_blocks)
+    rc = load().gmg_ssor_balance_rows(C.c_int64(n), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double) if use_values else None,
+                                      C.c_int(n_blocks), _p(br, C.c_int64), _p(cost, C.c_double))
+    if rc != OK:
+        raise GMGError(rc, "gmg_ssor_balance_rows")
+    return br, cost

@@ -93,6 +93,9 @@ struct SgsPlan {
   int w_y_slots = 0, w_lds_bytes = 0, w_n_ranges = 0;
   int64_t w_n_coupled = 0, w_stream_bytes = 0, w_steps = 0, w_stages = 0;
   std::vector<int32_t> host_block_row;  // n_blocks + 1 (several ranks: who sweeps which rows)
+  std::vector<int64_t> host_block_steps;  // n_blocks: sub-steps of each block's chain (both directions; gmg_get_ssor_partition)
+  std::vector<int64_t> host_block_bytes;  // n_blocks: record-stream bytes of each block (plan log)
+  std::vector<int32_t> host_block_rng;    // n_blocks + 1: ranges of each block (sgs_phase_profile: cycles per block)
   double *w_stage = nullptr;            // staging of the all-gather of the swept pieces
   int64_t w_stage_len = 0;
   // four-wave variant (gmg_sgs_phase.hpp): same lists, its own ranges and record stream
@@ -177,6 +180,8 @@ struct gmg_context {
   int sellp_rr = 0;         // round-robin slice order of the fast waves: 0 by size, 1 on, 2 off
   double sellp_cost = 4.0;  // cost of a streamed slice in pattern slices (wave balancing of spmv_sellp_kernel)
   int ssor_blocks = 1;  // 1 = exact sequential SGS; B > 1 = block Jacobi of SGS (the reference on B ranks)
+  int ssor_partition = GMG_SSOR_PARTITION_ROWS;          // where the B blocks' boundaries come from (setup_sgs)
+  std::map<int, std::vector<int64_t>> ssor_block_rows;   // explicit boundaries per level (gmg_set_ssor_block_rows): these win
   int cg_variant = 0;  // 0 auto, 1 fused 2-kernel iteration, 2 unfused 3-kernel iteration
   int last_coarse_iters = 0;
   int prof_every = 0;
@@ -1119,6 +1124,20 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
                            h[12 * i + 8] / turns, h[12 * i + 9] / turns);
             }
           }
+          if (L.sgs.w_steps > 1000 && nbl > 1) {  // several blocks, one per CU: the cycles of each block's ranges
+            double c_max = 0, c_sum = 0;
+            for (int b = 0; b < nbl; ++b) {
+              unsigned long long cyc = 0, xfer = 0;
+              int steps = 0;
+              for (int i = L.sgs.host_block_rng[(size_t)b]; i < L.sgs.host_block_rng[(size_t)b + 1]; ++i) {
+                cyc += h[12 * (size_t)i]; xfer += h[12 * (size_t)i + 2] + h[12 * (size_t)i + 3]; steps += L.sgs.host_pranges[(size_t)i].n_steps;
+              }
+              std::fprintf(stderr, "[gmg]   block %3d: rows [%d, %d), %d ranges, %d steps, %llu cycles in the steps, %llu load + write-back\n", b, L.sgs.host_block_row[(size_t)b],
+                           L.sgs.host_block_row[(size_t)b + 1], L.sgs.host_block_rng[(size_t)b + 1] - L.sgs.host_block_rng[(size_t)b], steps, cyc, xfer);
+              c_max = std::max(c_max, (double)(cyc + xfer)); c_sum += (double)(cyc + xfer);
+            }
+            std::fprintf(stderr, "[gmg] four-wave sweep, %lld rows, %d blocks: longest / mean block (steps + transfers) %.2f\n", (long long)L.n, nbl, c_sum > 0 ? c_max * nbl / c_sum : 1.0);
+          }
         } else
         if (L.sgs.dep) {
           if (ctx->timed_start) {  // (two kernel arguments: the one-argument launch_timed does not fit)
@@ -1488,6 +1507,134 @@ void free_sgs(SgsPlan &g) {
   g = SgsPlan();
 }
 
+// ---- where the SSOR blocks are cut ("Block boundaries").  Modelled sweep time of a block of consecutive rows:
+//   cost = kSsorStepNs * sub-steps + stream bytes / kSsorBytesPerNs
+// sub-steps: both directions walk the stages of the block's recurrence stage(i) = 1 + max stage(j) over the coupled j in
+// [rb, i), at most kPhMaxRows rows of one stage per step -- the count setup_sgs_wave makes for the four-wave sweep.  Stream:
+// the records scale with rows x width, kSsorRowBytes per coupled row plus kSsorEntryBytes per in-block entry of it (both
+// directions; 73 MB for the 92 164 coupled rows of the 64 k-atom level 1).  Uncoupled rows (the prepass) cost nothing.
+constexpr double kSsorStepNs = 240.0;     // one dependent step of the four-wave sweep
+constexpr double kSsorBytesPerNs = 48.0;  // one CU streams ~20 B per clock at 2.4 GHz
+constexpr int64_t kSsorRowBytes = 64, kSsorEntryBytes = 28;
+
+// Pattern of the entries that couple (stored value != 0, or every stored entry without values) and its transpose.
+struct SsorPattern {
+  int64_t n = 0;
+  std::vector<int64_t> rp, trp;
+  std::vector<int32_t> col, tcol;
+  SsorPattern(int64_t n_, const int64_t *rp_, const int32_t *col_, const double *val) : n(n_) {
+    rp.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+      for (int64_t k = rp_[i]; k < rp_[i + 1]; ++k)
+        if (!val || val[k] != 0.0) col.push_back(col_[k]);
+      rp[(size_t)i + 1] = (int64_t)col.size();
+    }
+    std::vector<double> ones(col.size(), 1.0), tval;
+    transpose_host(n, n, rp.data(), col.data(), ones.data(), trp, tcol, tval);
+  }
+};
+
+// The model of one block, grown a row at a time (add() never lowers the cost: the greedy cut below relies on it).
+struct SsorBlockModel {
+  const SsorPattern &P;
+  std::vector<int32_t> stage, ent;  // per row of the block: stage, in-block entries so far
+  std::vector<char> coupled;
+  std::vector<int64_t> cnt;          // coupled rows per stage
+  int64_t rb = 0, steps = 0, bytes = 0;
+  explicit SsorBlockModel(const SsorPattern &p) : P(p), stage((size_t)p.n, 0), ent((size_t)p.n, 0), coupled((size_t)p.n, 0) {}
+  void reset(int64_t r) { rb = r; steps = bytes = 0; cnt.clear(); }
+  double cost_ns() const { return kSsorStepNs * (double)steps + (double)bytes / kSsorBytesPerNs; }
+  void put(int32_t s) {
+    if ((size_t)s >= cnt.size()) cnt.resize((size_t)s + 1, 0);
+    if (cnt[(size_t)s]++ % kPhMaxRows == 0) steps += 2;
+  }
+  void add(int64_t i) {
+    int32_t st = 0;
+    bool low = false;
+    auto touch = [&](int64_t j) {  // j in [rb, i) coupled to i
+      low = true;
+      if (!coupled[(size_t)j]) {  // coupled only to rows after it: stage 0
+        coupled[(size_t)j] = 1; stage[(size_t)j] = 0; put(0);
+        bytes += kSsorRowBytes + kSsorEntryBytes * ent[(size_t)j];
+      }
+      st = std::max(st, stage[(size_t)j] + 1);
+    };
+    int32_t e = 0;
+    for (int64_t k = P.rp[(size_t)i]; k < P.rp[(size_t)i + 1]; ++k) {
+      const int64_t c = P.col[(size_t)k];
+      if (c < rb || c > i) continue;
+      ++e;
+      if (c < i) touch(c);
+    }
+    for (int64_t k = P.trp[(size_t)i]; k < P.trp[(size_t)i + 1]; ++k) {  // entries (j, i) of the earlier rows
+      const int64_t j = P.tcol[(size_t)k];
+      if (j < rb || j >= i) continue;
+      ent[(size_t)j]++;
+      if (coupled[(size_t)j]) bytes += kSsorEntryBytes;
+      touch(j);
+    }
+    ent[(size_t)i] = e;
+    coupled[(size_t)i] = low;
+    stage[(size_t)i] = low ? st : 0;
+    if (low) { put(st); bytes += kSsorRowBytes + kSsorEntryBytes * e; }
+  }
+};
+
+// B - 1 cuts that make the blocks' modelled costs about equal: the greedy pass fills each block up to a target T (the
+// fewest blocks for that T), a bisection finds the smallest T that needs at most B of them.  O(nnz) per pass, the same
+// arithmetic in the same order on every rank.  B is clamped to (n + 63) / 64 like the equal runs; the boundaries behind
+// the last block used are n (empty blocks).  cost_us: each block's modelled time.
+void ssor_balance(const SsorPattern &P, int n_blocks, std::vector<int64_t> &block_row, std::vector<double> &cost_us) {
+  const int64_t n = P.n;
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(n_blocks, (n + 63) / 64));
+  SsorBlockModel M(P);
+  auto greedy = [&](double T, std::vector<int64_t> *cuts) {
+    int count = 1;
+    M.reset(0);
+    for (int64_t i = 0; i < n; ++i) {
+      M.add(i);
+      if (M.cost_ns() > T && i > M.rb) {
+        if (++count > nb) return count;
+        if (cuts) cuts->push_back(i);
+        M.reset(i);
+        M.add(i);
+      }
+    }
+    return count;
+  };
+  M.reset(0);
+  for (int64_t i = 0; i < n; ++i) M.add(i);
+  double lo = 0.0, hi = M.cost_ns();
+  while (hi - lo > 1e-4 * hi) {
+    const double mid = 0.5 * (lo + hi);
+    if (greedy(mid, nullptr) <= nb) hi = mid;
+    else lo = mid;
+  }
+  std::vector<int64_t> cuts;
+  greedy(hi, &cuts);
+  block_row.assign((size_t)n_blocks + 1, n);
+  block_row[0] = 0;
+  for (size_t c = 0; c < cuts.size(); ++c) block_row[c + 1] = cuts[c];
+  cost_us.assign((size_t)n_blocks, 0.0);
+  for (int b = 0; b < n_blocks; ++b) {
+    M.reset(block_row[(size_t)b]);
+    for (int64_t i = block_row[(size_t)b]; i < block_row[(size_t)b + 1]; ++i) M.add(i);
+    cost_us[(size_t)b] = M.cost_ns() * 1e-3;
+  }
+}
+
+// modelled cost (us) of every block of a partition (the plan log prints it beside what the plan really holds)
+std::vector<double> ssor_block_costs(const SsorPattern &P, const std::vector<int32_t> &block_row) {
+  SsorBlockModel M(P);
+  std::vector<double> c(block_row.size() - 1, 0.0);
+  for (size_t b = 0; b + 1 < block_row.size(); ++b) {
+    M.reset(block_row[b]);
+    for (int64_t i = block_row[b]; i < block_row[b + 1]; ++i) M.add(i);
+    c[b] = M.cost_ns() * 1e-3;
+  }
+  return c;
+}
+
 // Plan of the wavefront sweep (gmg_sgs.hpp): per block the pruned rows, the dependency stages, the steps of both
 // sweep directions, their grouping into LDS-sized ranges, and the record stream in consumption order.
 int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val, int n_blocks,
@@ -1520,10 +1667,12 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   // stream) and the LDS byte addresses of y slots.  Their maxima are checked against the allocation / the LDS budget
   // before the plan is accepted (the one fault this code ever produced was a store through an aux field).
   uint64_t max_aux = 0, max_lds_addr = 0;
+  std::vector<int64_t> blk_steps0((size_t)n_blocks + 1, 0), blk_bytes0((size_t)n_blocks + 1, 0);  // tallies at each block's start
   for (int b = 0; b < n_blocks; ++b) {
     const int64_t rb = block_row[(size_t)b], re = block_row[(size_t)b + 1];
     const int m = (int)(re - rb);
     block_rng[(size_t)b] = (int32_t)(ph ? pranges.size() : ranges.size());
+    blk_steps0[(size_t)b] = total_steps; blk_bytes0[(size_t)b] = (int64_t)stream.size();
     if (m == 0) continue;
     // ---- in-block nonzero entries of every row (local column numbers), 1 / a_ii as in setup_diag
     std::vector<int32_t> prp((size_t)m + 1, 0), pcol;
@@ -1987,6 +2136,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
     for (int dir = 0; dir < 2; ++dir) pranges.insert(pranges.end(), dir_pranges[dir].begin(), dir_pranges[dir].end());
   }
   block_rng[(size_t)n_blocks] = (int32_t)(ph ? pranges.size() : ranges.size());
+  blk_steps0[(size_t)n_blocks] = total_steps; blk_bytes0[(size_t)n_blocks] = (int64_t)stream.size();
   const int y_slots = std::max(2, (max_ws + 1) & ~1);
   // ---- the plan is memory-safe by construction, and checked: every address a record carries lies inside what is allocated
   if (!stream.empty() && (max_aux * 8 + 8 > stream.size() || max_lds_addr + 8 > (uint64_t)y_slots * 8))
@@ -2015,6 +2165,13 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   HIPC(hipMalloc(&G.w_ycur, sizeof(double) * std::max<size_t>(ci_row.size(), 1)));
   HIPC(hipStreamSynchronize(ctx->stream));
   G.host_block_row = block_row;
+  G.host_block_rng = block_rng;
+  G.host_block_steps.assign((size_t)n_blocks, 0);
+  G.host_block_bytes.assign((size_t)n_blocks, 0);
+  for (int b = 0; b < n_blocks; ++b) {
+    G.host_block_steps[(size_t)b] = blk_steps0[(size_t)b + 1] - blk_steps0[(size_t)b];
+    G.host_block_bytes[(size_t)b] = blk_bytes0[(size_t)b + 1] - blk_bytes0[(size_t)b];
+  }
   {
     const int n_ranks = ctx->dist ? ctx->comm.n_ranks : 1;
     if (n_ranks > 1 && n_blocks % n_ranks == 0) {
@@ -2075,14 +2232,29 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
 
 // SGS level schedule on the symmetrised pattern, per block of consecutive rows:
 // stage(i) = 1 + max stage(j) over the coupled j < i of the same block.
-int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val) {
+// The boundaries: the caller's (explicit_rows, checked by gmg_set_level_matrix), else the balanced cuts if that mode is on,
+// else equal runs of rows.
+int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val,
+              const std::vector<int64_t> *explicit_rows) {
   std::vector<int64_t> trp;
   std::vector<int32_t> tcol;
   std::vector<double> tval, ones((size_t)rp[n], 1.0);
   transpose_host(n, n, rp, col, ones.data(), trp, tcol, tval);
-  const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64));
-  std::vector<int32_t> block_row((size_t)n_blocks + 1), block_stage((size_t)n_blocks + 1, 0);
-  for (int b = 0; b <= n_blocks; ++b) block_row[(size_t)b] = (int32_t)(n * b / n_blocks);
+  std::vector<int32_t> block_row;
+  if (explicit_rows) {
+    block_row.assign(explicit_rows->begin(), explicit_rows->end());
+  } else if (ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED) {
+    std::vector<int64_t> br;
+    std::vector<double> cost;
+    ssor_balance(SsorPattern(n, rp, col, val), (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64)), br, cost);
+    block_row.assign(br.begin(), br.end());
+  } else {
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64));
+    block_row.resize((size_t)nb + 1);
+    for (int b = 0; b <= nb; ++b) block_row[(size_t)b] = (int32_t)(n * b / nb);
+  }
+  const int n_blocks = (int)block_row.size() - 1;
+  std::vector<int32_t> block_stage((size_t)n_blocks + 1, 0);
   std::vector<int32_t> stage((size_t)std::max<int64_t>(n, 1), 0), sp, rows((size_t)std::max<int64_t>(n, 1));
   int n_stages_max = 0;
   for (int b = 0; b < n_blocks; ++b) {
@@ -2119,7 +2291,34 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
   HIPC(hipMemcpyAsync(L.sgs.block_row, block_row.data(), sizeof(int32_t) * block_row.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(L.sgs.block_stage, block_stage.data(), sizeof(int32_t) * block_stage.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
-  return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row);
+  // (the generic sweep: one step per stage and direction; the wavefront plan replaces these with its own counts)
+  L.sgs.host_block_row = block_row;
+  L.sgs.host_block_steps.assign((size_t)n_blocks, 0);
+  for (int b = 0; b < n_blocks; ++b) L.sgs.host_block_steps[(size_t)b] = 2 * (int64_t)(block_stage[(size_t)b + 1] - block_stage[(size_t)b]);
+  L.sgs.host_block_bytes.assign((size_t)n_blocks, 0);
+  CHK(setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row));
+  if (ctx->debug_upload) {
+    // the partition: per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
+    const std::vector<double> cost = ssor_block_costs(SsorPattern(n, rp, col, val), block_row);
+    double c_max = 0, c_sum = 0;
+    int64_t s_max = 0, s_sum = 0;
+    for (int b = 0; b < n_blocks; ++b) {
+      std::fprintf(stderr, "[gmg]   SSOR block %3d: rows [%lld, %lld) %lld, sub-steps %lld, stream %.2f MB, model %.1f us\n", b, (long long)block_row[(size_t)b],
+                   (long long)block_row[(size_t)b + 1], (long long)(block_row[(size_t)b + 1] - block_row[(size_t)b]), (long long)L.sgs.host_block_steps[(size_t)b],
+                   (double)L.sgs.host_block_bytes[(size_t)b] / 1e6, cost[(size_t)b]);
+      c_max = std::max(c_max, cost[(size_t)b]); c_sum += cost[(size_t)b];
+      s_max = std::max(s_max, L.sgs.host_block_steps[(size_t)b]); s_sum += L.sgs.host_block_steps[(size_t)b];
+    }
+    std::fprintf(stderr, "[gmg]   SSOR partition (%s): %d blocks, longest / mean: model %.2f, sub-steps %.2f\n",
+                 explicit_rows ? "caller's" : ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED ? "balanced" : "equal rows", n_blocks,
+                 c_sum > 0 ? c_max * n_blocks / c_sum : 1.0, s_sum > 0 ? (double)s_max * n_blocks / (double)s_sum : 1.0);
+    if (L.sgs.w_stage) {
+      const int n_ranks = ctx->comm.n_ranks;
+      std::fprintf(stderr, "[gmg]   SSOR all-gather: %d ranks x %lld doubles (largest piece) = %.2f MB moved per sweep for %.2f MB of y\n", n_ranks,
+                   (long long)L.sgs.w_stage_len, 8e-6 * (double)L.sgs.w_stage_len * n_ranks, 8e-6 * (double)n);
+    }
+  }
+  return GMG_OK;
 }
 
 // frees every operator / work vector but keeps the stream, the reduction scratch and the communicator
@@ -2341,13 +2540,17 @@ static int finish_level(gmg_context *ctx, int level, int64_t n_rows, int64_t n_c
 int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_cols, const int64_t *rowptr,
                          const int32_t *col, const double *val) {
   if (!ctx || level < 0 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const auto ex = level > 0 ? ctx->ssor_block_rows.find(level) : ctx->ssor_block_rows.end();
+  const std::vector<int64_t> *explicit_rows = ex == ctx->ssor_block_rows.end() ? nullptr : &ex->second;
+  if (explicit_rows && explicit_rows->back() != n_rows)  // (before anything is uploaded)
+    return fail(ctx, GMG_ERR_INVALID, "gmg_set_level_matrix: the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_rows");
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
   CHK(upload_csr(ctx, L.A, n_rows, n_cols, rowptr, col, val, level > 0));
   CHK(setup_diag(ctx, n_rows, rowptr, col, val, &L.invd, &L.cheb_lmax));
   if (level > 0) {
     L.n = n_rows;  // (the SGS plan reads it)
-    CHK(setup_sgs(ctx, L, n_rows, rowptr, col, val));
+    CHK(setup_sgs(ctx, L, n_rows, rowptr, col, val, explicit_rows));
   }
   return finish_level(ctx, level, n_rows, n_cols, rowptr[n_rows]);
 }
@@ -3198,6 +3401,7 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "sellp_rr") ctx->sellp_rr = (int)value;
   else if (k == "cg_variant") ctx->cg_variant = (int)value;
   else if (k == "coarse_chunk") ctx->coarse_chunk = (int)value;
+  else if (k == "ssor_balanced") ctx->ssor_partition = on ? GMG_SSOR_PARTITION_BALANCED : GMG_SSOR_PARTITION_ROWS;
   else if (k == "sgs_y_slots") ctx->sgs_y_slots = (int)value;
   else if (k == "sgs_disable_wave") ctx->sgs_disable_wave = on;
   else if (k == "sgs_disable_phase") ctx->sgs_disable_phase = on;
@@ -3242,6 +3446,60 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant) {
 int gmg_set_ssor_blocks(gmg_context *ctx, int n_blocks) {
   if (!ctx || n_blocks < 1) return GMG_ERR_INVALID;
   ctx->ssor_blocks = n_blocks;
+  return GMG_OK;
+}
+
+int gmg_set_ssor_block_rows(gmg_context *ctx, int level, int n_blocks, const int64_t *block_row) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (level < 1 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_block_rows: levels 1 .. n_levels - 1 (level 0 is the coarse CG)");
+  if (n_blocks < 0 || (n_blocks > 0 && !block_row)) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_block_rows: n_blocks >= 0 boundaries expected");
+  if (n_blocks == 0) {
+    ctx->ssor_block_rows.erase(level);
+    return GMG_OK;
+  }
+  if (block_row[0] != 0) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_block_rows: the first boundary must be 0");
+  for (int b = 0; b < n_blocks; ++b)
+    if (block_row[b + 1] < block_row[b]) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_block_rows: boundaries must not decrease");
+  if (block_row[n_blocks] > INT32_MAX) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_block_rows: rows beyond the 32-bit range");
+  ctx->ssor_block_rows[level].assign(block_row, block_row + n_blocks + 1);
+  return GMG_OK;
+}
+
+int gmg_set_ssor_partition(gmg_context *ctx, int kind) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (kind != GMG_SSOR_PARTITION_ROWS && kind != GMG_SSOR_PARTITION_BALANCED) return fail(ctx, GMG_ERR_INVALID, "gmg_set_ssor_partition: unknown kind");
+  ctx->ssor_partition = kind;
+  return GMG_OK;
+}
+
+int gmg_get_ssor_partition(gmg_context *ctx, int level, int *n_blocks, int64_t *block_row, int64_t *block_steps) {
+  if (!ctx || !n_blocks || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const SgsPlan &G = ctx->lv[(size_t)level].sgs;
+  if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_partition: the level matrix has not been set");
+  *n_blocks = (int)G.host_block_row.size() - 1;
+  if (block_row) std::copy(G.host_block_row.begin(), G.host_block_row.end(), block_row);
+  if (block_steps) std::copy(G.host_block_steps.begin(), G.host_block_steps.end(), block_steps);
+  return GMG_OK;
+}
+
+int gmg_ssor_balance_rows(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int n_blocks, int64_t *block_row,
+                          double *block_cost) {
+  if (n < 0 || n > INT32_MAX || n_blocks < 1 || !block_row || (n > 0 && (!rowptr || !col)) || (n > 0 && rowptr[0] != 0)) return GMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; ++i) {
+    if (rowptr[i + 1] < rowptr[i]) return GMG_ERR_INVALID;
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+      if (col[k] < 0 || col[k] >= n) return GMG_ERR_INVALID;
+  }
+  std::vector<int64_t> br;
+  std::vector<double> cost;
+  if (n == 0) {
+    br.assign((size_t)n_blocks + 1, 0);
+    cost.assign((size_t)n_blocks, 0.0);
+  } else {
+    ssor_balance(SsorPattern(n, rowptr, col, val), n_blocks, br, cost);
+  }
+  std::copy(br.begin(), br.end(), block_row);
+  if (block_cost) std::copy(cost.begin(), cost.end(), block_cost);
   return GMG_OK;
 }
 

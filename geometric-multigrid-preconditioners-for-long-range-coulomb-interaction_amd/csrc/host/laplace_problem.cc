@@ -211,7 +211,7 @@ void ParameterReader::declare_parameters() {
             {"Polynomial degree", "1"}, {"Preconditioner", "GMG"}, {"Lammps input file", "atom_8.data"},
             // additions of this build (the reference selects the smoother by editing :969-970)
             {"Smoother", "SSOR"}, {"Smoother damping", "0.5"}, {"Smoother steps", "2"}, {"Chebyshev degree", "2"},
-            {"Device resident outer CG", "false"}, {"SSOR blocks", "1"}, {"Charge densities on device", "true"},
+            {"Device resident outer CG", "false"}, {"SSOR blocks", "1"}, {"SSOR block partition", "equal rows"}, {"Charge densities on device", "true"},
             {"Partition level 0", "auto"},
             // HEAD marks with Kelly + the cell residual (:1040-1089); the cluster logs (January 2018) are reproduced by
             // the Kelly indicator alone (tools/marking_rule_scan.py)
@@ -290,6 +290,9 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.chebyshev_degree = (int)prm.get_integer("Chebyshev degree");
   p.device_resident_outer_cg = prm.get_bool("Device resident outer CG");
   p.ssor_blocks = (int)prm.get_integer("SSOR blocks");
+  p.ssor_partition = prm.get("SSOR block partition");
+  if (p.ssor_partition != "equal rows" && p.ssor_partition != "balanced")
+    throw std::runtime_error("SSOR block partition must be <equal rows> or <balanced>");
   p.densities_on_device = prm.get_bool("Charge densities on device");
   p.partition_level0 = prm.get("Partition level 0");
   p.refinement_estimator = prm.get("Refinement estimator");
@@ -1268,6 +1271,8 @@ int LaplaceProblem<dim>::upload() {
   build_matrices_ms = 0.0;
   // before the level matrices: sizes the SGS schedule.  0 = one block per rank: the reference's smoother on that many ranks
   GMGC(gmg_set_ssor_blocks(gmg, par.ssor_blocks > 0 ? par.ssor_blocks : std::max(1, distributed ? n_ranks : 1)));
+  // (the default leaves the context's own setting: GMG_OPTIONS=ssor_balanced=1 measures the unchanged driver)
+  if (par.ssor_partition == "balanced") GMGC(gmg_set_ssor_partition(gmg, GMG_SSOR_PARTITION_BALANCED));
   const CSRMatrix &S = system_matrix;
   if (distributed) {
     // system matrix + outer-CG vectors and level 0 are row-partitioned (canonical equal chunks),
@@ -1460,7 +1465,8 @@ int LaplaceProblem<dim>::solve_again() {
 }
 
 // bench: the operators of the current cycle with another smoother ("Jacobi" | "SSOR" | "Chebyshev"; SSOR in
-// `ssor_blocks` blocks = the reference's smoother on that many ranks).  The SGS schedule is built at upload.
+// `ssor_blocks` blocks = the reference's smoother on that many ranks, cut as "SSOR block partition" says).  The SGS schedule
+// is built at upload.
 template <int dim>
 int LaplaceProblem<dim>::set_smoother(const std::string &smoother, int ssor_blocks) {
   if (smoother != "Jacobi" && smoother != "SSOR" && smoother != "Chebyshev") { last_error = "unknown smoother " + smoother; return GMG_ERR_INVALID; }

@@ -64,6 +64,7 @@ struct Parameters {
   int smoother_steps = 2, chebyshev_degree = 2;
   bool densities_on_device = true;  // compute_charge_densities() through gmg_charge_density when a device is in use
   int ssor_blocks = 1;  // 1: exact sequential SGS (mpirun=1); B: rank-local SGS on B blocks (mpirun=B)
+  std::string ssor_partition = "equal rows";  // where the B blocks are cut: "equal rows" | "balanced" (modelled sweep time)
   bool device_resident_outer_cg = false;  // true: gmg_cg_solve instead of the host SolverCG
   std::string partition_level0 = "auto";  // one process per GPU: auto | always | never
   std::string refinement_estimator = "Kelly + residual";  // HEAD (:1040-1089) | "Kelly": the indicator of the older cluster runs

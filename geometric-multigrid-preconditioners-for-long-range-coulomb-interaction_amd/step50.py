@@ -74,6 +74,7 @@ def prm_text(**kw) -> str:
         "steps": ("Solver input data", "Smoother steps"), "cheb_degree": ("Solver input data", "Chebyshev degree"),
         "device_cg": ("Solver input data", "Device resident outer CG"),
         "ssor_blocks": ("Solver input data", "SSOR blocks"),
+        "ssor_partition": ("Solver input data", "SSOR block partition"),
         "densities_on_device": ("Misc", "Charge densities on device"),
         "partition_level0": ("Solver input data", "Partition level 0"),
         "refinement_estimator": ("Misc", "Refinement estimator"),

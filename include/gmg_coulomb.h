@@ -265,6 +265,33 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value);
  * consecutive rows, couplings between blocks dropped (Ifpack's rank-local matrix).  Call before
  * the level matrices are set.                                                              */
 int gmg_set_ssor_blocks(gmg_context *ctx, int n_blocks);
+/* Where the SSOR blocks of a level start and end.  The reference's ranks each sweep the rows they own on that level
+ * (mg_matrices[level] over locally_owned_mg_dofs(level), src/step-50.cc:722-723, smoothed by the rank-local
+ * PreconditionSSOR of :970-973) -- p4est's cell-balanced chunks (:120-122), not equal runs of rows.  A level's boundaries
+ * come from the first source that applies: the explicit ones of gmg_set_ssor_block_rows, the balanced cuts if
+ * gmg_set_ssor_partition chose them, equal runs of rows (the default).
+ *   gmg_set_ssor_block_rows: block_row[0..n_blocks], 0 first, never decreasing, empty blocks allowed (a rank may own no
+ *     row of a level); levels >= 1 only (level 0 is the coarse CG).  Kept until cleared with n_blocks = 0 (also across
+ *     gmg_reset).  Call before the level's matrix is set; a last entry that is not that matrix's n_rows makes
+ *     gmg_set_level_matrix fail with GMG_ERR_INVALID before anything is uploaded.  n_blocks replaces gmg_set_ssor_blocks
+ *     for that level (several ranks: n_blocks = n_ranks, or a multiple, block b swept by rank b / (n_blocks / n_ranks)).
+ *   gmg_set_ssor_partition: GMG_SSOR_PARTITION_ROWS (default) or _BALANCED: B - 1 cuts, with B of gmg_set_ssor_blocks
+ *     (clamped to (n_rows + 63) / 64 as the equal runs are), that equalise the modelled sweep time of the blocks
+ *     (DESIGN.md 4).  Also the gmg_set_option / GMG_OPTIONS key ssor_balanced.
+ *   gmg_get_ssor_partition: the boundaries the level's plan uses (block_row: n_blocks + 1 entries, may be NULL) and each
+ *     block's dependent sub-steps, both sweep directions (block_steps: n_blocks entries, may be NULL).                  */
+#define GMG_SSOR_PARTITION_ROWS 0
+#define GMG_SSOR_PARTITION_BALANCED 1
+int gmg_set_ssor_block_rows(gmg_context *ctx, int level, int n_blocks, const int64_t *block_row);
+int gmg_set_ssor_partition(gmg_context *ctx, int kind);
+int gmg_get_ssor_partition(gmg_context *ctx, int level, int *n_blocks, int64_t *block_row, int64_t *block_steps);
+/* The balanced cuts of gmg_set_ssor_partition for one level matrix (host CSR, ascending columns), without a context or a
+ * device: the same routine, deterministic (every rank computes the same cuts from the replicated level matrix).  val may
+ * be NULL (every stored entry couples; else stored zeros do not, as in the sweep's plan).  block_row: n_blocks + 1
+ * entries, those behind min(n_blocks, (n + 63) / 64) blocks equal n; block_cost (may be NULL): each block's modelled
+ * sweep time in microseconds.                                                                                         */
+int gmg_ssor_balance_rows(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int n_blocks,
+                          int64_t *block_row, double *block_cost);
 
 #ifdef __cplusplus
 }
