@@ -32,6 +32,7 @@ SYMBOLS = [
     "gmg_vec_allgather",
     "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks",
     "gmg_set_ssor_block_rows", "gmg_set_ssor_partition", "gmg_get_ssor_partition", "gmg_ssor_balance_rows", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
+    "gmg_set_point_locator", "gmg_atom_forces", "gmg_direct_coulomb",
 ]
 
 
@@ -276,6 +277,39 @@ class Context:
         rc = self.L.gmg_cg_solve(self.h, x.ptr, b.ptr, C.c_double(rel_tol), C.c_int(max_it), C.c_int(precond),
                                  C.byref(it), C.byref(r0), C.byref(r))
         return {"iterations": it.value, "starting_value": r0.value, "convergence_value": r.value, "status": rc}
+
+    # ---- forces on the atoms (gmg_forces.hpp)
+    def set_point_locator(self, n0, origin, h0, node, active_dofs):
+        """The forest flattened level by level (node[k] >= 0: child 0, < 0: active cell -node[k]-1) and the DoFs of the
+        active cells' vertices [n_active, 8]."""
+        n0 = np.ascontiguousarray(n0, dtype=np.int32)
+        org = np.ascontiguousarray(origin, dtype=np.float64)
+        node = np.ascontiguousarray(node, dtype=np.int32)
+        dofs = np.ascontiguousarray(active_dofs, dtype=np.int32).reshape(-1)
+        self._chk(self.L.gmg_set_point_locator(self.h, _p(n0, C.c_int32), _p(org, C.c_double), C.c_double(h0), C.c_int64(node.size),
+                                               _p(node, C.c_int32), C.c_int64(dofs.size // 8), _p(dofs, C.c_int32)))
+
+    def atom_forces(self, xyz, q, u, r_c, cutoff=0.0):
+        """u: DeviceVector of the constraint-distributed solution -> dict phi [n], field [n, 3], force [n, 3],
+        force_short [n, 3], e_short [n]."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        n = len(q)
+        out = dict(phi=np.zeros(n), field=np.zeros((n, 3)), force=np.zeros((n, 3)), force_short=np.zeros((n, 3)), e_short=np.zeros(n))
+        D = lambda k: _p(out[k], C.c_double)
+        self._chk(self.L.gmg_atom_forces(self.h, C.c_int64(n), _p(xyz, C.c_double), _p(q, C.c_double), u.ptr, C.c_int64(u.n),
+                                         C.c_double(r_c), C.c_double(cutoff), D("phi"), D("field"), D("force"), D("force_short"),
+                                         D("e_short")))
+        return out
+
+    def direct_coulomb(self, xyz, q):
+        """Exact all-pairs Coulomb forces [n, 3] and per-atom energies [n]."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        F, e = np.zeros((len(q), 3)), np.zeros(len(q))
+        self._chk(self.L.gmg_direct_coulomb(self.h, C.c_int64(len(q)), _p(xyz, C.c_double), _p(q, C.c_double), _p(F, C.c_double),
+                                            _p(e, C.c_double)))
+        return F, e
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

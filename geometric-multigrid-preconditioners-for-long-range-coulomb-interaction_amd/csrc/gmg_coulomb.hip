@@ -17,6 +17,7 @@
 #endif
 #include "gmg_lattice.hpp"
 #include "gmg_transfer.hpp"
+#include "gmg_forces.hpp"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -196,6 +197,11 @@ struct gmg_context {
   double *dens_dev = nullptr;  // charge densities kept on the device (gmg_charge_density with dens == NULL): [cells][nq]
   int64_t dens_cells = 0;
   int dens_nq = 0;
+  // point location for the atom forces (gmg_set_point_locator; kept until gmg_reset)
+  gmg_forces::Locator loc{};
+  int32_t *loc_node = nullptr, *loc_dofs = nullptr;
+  int64_t loc_max_dof = -1;  // -1: no locator set
+  int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
   int64_t sys_global = 0, l0_global = 0;  // l0_global == 0 on a communicator: level 0 is replicated, only the outer CG is partitioned
@@ -2332,6 +2338,14 @@ void free_cg_ring(gmg_context *ctx) {
   ctx->cg_ring_len = 0;
 }
 
+void free_locator(gmg_context *ctx) {
+  for (int32_t *p : {ctx->loc_node, ctx->loc_dofs})
+    if (p) (void)hipFree(p);
+  ctx->loc_node = ctx->loc_dofs = nullptr;
+  ctx->loc = gmg_forces::Locator{};
+  ctx->loc_max_dof = -1;
+}
+
 void release_operators(gmg_context *ctx) {
   for (auto &L : ctx->lv) {
     free_csr(L.A); free_csr(L.I); free_csr(L.It); free_csr(L.P); free_csr(L.Pt);
@@ -2433,6 +2447,7 @@ int gmg_destroy(gmg_context *ctx) {
   release_operators(ctx);  // (before the communicator: the shared direction vectors are unmapped collectively)
   if (ctx->peer_push_cnt) (void)hipFree(ctx->peer_push_cnt);
   if (ctx->dens_dev) (void)hipFree(ctx->dens_dev);
+  free_locator(ctx);
   comm_destroy(ctx->comm);
   for (double *p : {ctx->part_a, ctx->part_b, ctx->scal_dev})
     if (p) (void)hipFree(p);
@@ -2454,6 +2469,7 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   (void)hipSetDevice(ctx->device);
   HIPC(hipStreamSynchronize(ctx->stream));
   release_operators(ctx);
+  free_locator(ctx);
   ctx->n_levels = n_levels;
   ctx->lv.assign((size_t)n_levels, Level());
   ctx->last_coarse_iters = 0;
@@ -3088,28 +3104,12 @@ int gmg_charge_density(gmg_context *ctx, int64_t n_cells, const double *cell_lo,
   (void)hipSetDevice(ctx->device);
   // bins of edge `cutoff` over the atoms' bounding box (host; 64 k atoms: microseconds)
   DensityArgs a{};
-  double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-  for (int d = 0; d < 3; ++d) { lo[d] = 1e300; hi[d] = -1e300; }
-  for (int64_t i = 0; i < n_atoms; ++i)
-    for (int d = 0; d < 3; ++d) { lo[d] = std::min(lo[d], atom_xyz[3 * i + d]); hi[d] = std::max(hi[d], atom_xyz[3 * i + d]); }
-  if (n_atoms == 0) { for (int d = 0; d < 3; ++d) lo[d] = hi[d] = 0; }
   const double bs = std::max(cutoff, 1e-12);
-  int bn[3];
-  int64_t total = 1;
-  for (int d = 0; d < 3; ++d) { bn[d] = std::max(1, (int)std::floor((hi[d] - lo[d]) / bs) + 1); total *= bn[d]; }
-  if (total > ((int64_t)1 << 28)) return fail(ctx, GMG_ERR_UNSUPPORTED, "atom bin grid too large");
-  std::vector<int32_t> bptr((size_t)total + 1, 0), bitems((size_t)std::max<int64_t>(n_atoms, 1));
-  auto bin_of = [&](int64_t i) {
-    int b[3];
-    for (int d = 0; d < 3; ++d) b[d] = std::min(bn[d] - 1, std::max(0, (int)std::floor((atom_xyz[3 * i + d] - lo[d]) / bs)));
-    return (int64_t)b[0] + bn[0] * ((int64_t)b[1] + (int64_t)bn[1] * b[2]);
-  };
-  for (int64_t i = 0; i < n_atoms; ++i) bptr[(size_t)bin_of(i) + 1]++;
-  for (int64_t b = 0; b < total; ++b) bptr[(size_t)b + 1] += bptr[(size_t)b];
-  {
-    std::vector<int32_t> pos(bptr.begin(), bptr.end() - 1);
-    for (int64_t i = 0; i < n_atoms; ++i) bitems[(size_t)pos[(size_t)bin_of(i)]++] = (int32_t)i;
-  }
+  gmg_forces::Bins B;
+  if (!gmg_forces::bin_atoms(n_atoms, atom_xyz, bs, (int64_t)1 << 28, B)) return fail(ctx, GMG_ERR_UNSUPPORTED, "atom bin grid too large");
+  const double *lo = B.lo;
+  const int *bn = B.n;
+  const std::vector<int32_t> &bptr = B.ptr, &bitems = B.items;
   double *d_lo = nullptr, *d_h = nullptr, *d_root = nullptr, *d_xyz = nullptr, *d_q = nullptr, *d_qp = nullptr, *d_dens = nullptr;
   int32_t *d_bptr = nullptr, *d_bitems = nullptr;
   auto cleanup = [&]() {
@@ -3160,6 +3160,181 @@ int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *de
   if (!ctx->dens_dev || ctx->dens_cells != n_cells || ctx->dens_nq != nq) return fail(ctx, GMG_ERR_INVALID, "gmg_get_charge_density: no densities of this shape on the device");
   HIPC(hipMemcpyAsync(dens, ctx->dens_dev, sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+// ---- atom forces (gmg_forces.hpp) ----
+
+}  // extern "C"
+
+namespace {
+// device buffers of one force call, freed on every way out
+struct DevBufs {
+  std::vector<void *> p;
+  ~DevBufs() { for (void *q : p) (void)hipFree(q); }
+  template <class T>
+  T *alloc(size_t n) {
+    void *q = nullptr;
+    if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 8)) != hipSuccess) return nullptr;
+    p.push_back(q);
+    return (T *)q;
+  }
+};
+bool atoms_ok(int64_t n_atoms, const double *xyz, const double *q) {
+  return n_atoms >= 0 && n_atoms < ((int64_t)1 << 31) && (n_atoms == 0 || (xyz && q));
+}
+std::vector<double> pack_xq(int64_t n, const double *xyz, const double *q) {
+  std::vector<double> xq((size_t)std::max<int64_t>(n, 1) * 4);
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) xq[(size_t)(4 * i + d)] = xyz[3 * i + d];
+    xq[(size_t)(4 * i + 3)] = q[i];
+  }
+  return xq;
+}
+// per-atom (F, e) of a pair law into out_dev [n][4]: all pairs (rcut = inf, N-body tiles) or the pairs closer than rcut
+// through the bins of gmg_forces::force_bins
+template <class Law>
+int launch_pairs(gmg_context *ctx, DevBufs &m, const Law &law, double rcut, int64_t n, const double *xyz, const double *xq_host,
+                 const double *xq_dev, double *out_dev) {
+  const int bs = ctx->force_block;
+  const size_t lds = sizeof(double) * 4 * (size_t)bs;
+  if (!(rcut < INFINITY)) {
+    hipLaunchKernelGGL(gmg_forces::pair_all_kernel<Law>, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), lds, ctx->stream, law, rcut,
+                       xq_dev, (int)n, out_dev);
+    return GMG_OK;
+  }
+  gmg_forces::Bins B;
+  gmg_forces::force_bins(n, xyz, rcut, B);
+  std::vector<double> sorted((size_t)n * 4);
+  for (int64_t k = 0; k < n; ++k)
+    for (int c = 0; c < 4; ++c) sorted[(size_t)(4 * k + c)] = xq_host[4 * (size_t)B.items[(size_t)k] + c];
+  std::vector<int32_t> ubin, ustart;
+  for (size_t b = 0; b + 1 < B.ptr.size(); ++b)
+    for (int32_t s = 0; s < B.ptr[b + 1] - B.ptr[b]; s += bs) { ubin.push_back((int32_t)b); ustart.push_back(s); }
+  double *d_sorted = m.alloc<double>(sorted.size());
+  int32_t *d_items = m.alloc<int32_t>(B.items.size()), *d_ptr = m.alloc<int32_t>(B.ptr.size());
+  int32_t *d_ubin = m.alloc<int32_t>(ubin.size()), *d_ustart = m.alloc<int32_t>(ustart.size());
+  if (!d_sorted || !d_items || !d_ptr || !d_ubin || !d_ustart) return fail(ctx, GMG_ERR_HIP, "atom forces: out of memory");
+  HIPC(hipMemcpyAsync(d_sorted, sorted.data(), sizeof(double) * sorted.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_items, B.items.data(), sizeof(int32_t) * B.items.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ptr, B.ptr.data(), sizeof(int32_t) * B.ptr.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ubin, ubin.data(), sizeof(int32_t) * ubin.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ustart, ustart.data(), sizeof(int32_t) * ustart.size(), hipMemcpyHostToDevice, ctx->stream));
+  gmg_forces::BinnedArgs a{d_sorted, d_items, d_ptr, d_ubin, d_ustart, {B.n[0], B.n[1], B.n[2]}, out_dev};
+  hipLaunchKernelGGL(gmg_forces::pair_binned_kernel<Law>, dim3((unsigned)ubin.size()), dim3(bs), lds, ctx->stream, law, rcut, a);
+  HIPC(hipStreamSynchronize(ctx->stream));  // (the host arrays above are the sources of the copies)
+  return GMG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int gmg_set_point_locator(gmg_context *ctx, const int32_t n0[3], const double origin[3], double h0, int64_t n_nodes,
+                          const int32_t *node, int64_t n_active, const int32_t *active_dofs) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  free_locator(ctx);
+  if (!n0 || !origin || !node || !active_dofs || !(h0 > 0.0) || n_active < 1 || n_nodes < 1 || n_nodes >= ((int64_t)1 << 31) ||
+      n_active >= ((int64_t)1 << 28))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: bad sizes");
+  int64_t n_roots = 1;
+  for (int d = 0; d < 3; ++d) {
+    if (n0[d] < 1) return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: bad root lattice");
+    n_roots *= n0[d];
+  }
+  if (n_roots > n_nodes) return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: fewer nodes than roots");
+  // every walk ends: children lie after their parent, inside the array, and at most 20 levels below a root
+  std::vector<int8_t> depth((size_t)n_nodes, 0);
+  for (int64_t k = 0; k < n_nodes; ++k) {
+    const int32_t v = node[k];
+    if (v >= 0) {
+      if (v <= k || (int64_t)v + 7 >= n_nodes || depth[(size_t)k] >= 20) return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: node index out of range");
+      for (int a = 0; a < 8; ++a) depth[(size_t)v + a] = (int8_t)std::max<int>(depth[(size_t)v + a], depth[(size_t)k] + 1);
+    } else if (-(int64_t)v - 1 >= n_active) {
+      return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: active cell index out of range");
+    }
+  }
+  int64_t max_dof = -1;
+  for (int64_t i = 0; i < 8 * n_active; ++i) {
+    if (active_dofs[i] < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: negative DoF");
+    max_dof = std::max<int64_t>(max_dof, active_dofs[i]);
+  }
+  int32_t *d_node = nullptr, *d_dofs = nullptr;
+  if (hipMalloc(&d_node, sizeof(int32_t) * (size_t)n_nodes) != hipSuccess) return fail(ctx, GMG_ERR_HIP, "gmg_set_point_locator: out of memory");
+  if (hipMalloc(&d_dofs, sizeof(int32_t) * 8 * (size_t)n_active) != hipSuccess) {
+    (void)hipFree(d_node);
+    return fail(ctx, GMG_ERR_HIP, "gmg_set_point_locator: out of memory");
+  }
+  ctx->loc_node = d_node;
+  ctx->loc_dofs = d_dofs;
+  HIPC(hipMemcpyAsync(d_node, node, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_dofs, active_dofs, sizeof(int32_t) * 8 * (size_t)n_active, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  ctx->loc = gmg_forces::Locator{{n0[0], n0[1], n0[2]}, {origin[0], origin[1], origin[2]}, h0, d_node, d_dofs};
+  ctx->loc_max_dof = max_dof;
+  return GMG_OK;
+}
+
+int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u, int64_t n_u,
+                    double r_c, double cutoff, double *phi, double *field, double *force, double *force_short, double *e_short) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (!atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || !(cutoff >= 0.0)) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: bad arguments");
+  if (ctx->loc_max_dof < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: call gmg_set_point_locator first");
+  if (!u || n_u <= ctx->loc_max_dof) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: u is shorter than the locator's DoFs");
+  if (n_atoms == 0) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  const int64_t n = n_atoms;
+  const bool want_field = phi || field || force, want_pairs = force || force_short || e_short;
+  const std::vector<double> xq = pack_xq(n, atom_xyz, atom_q);
+  DevBufs m;
+  double *d_xq = m.alloc<double>((size_t)n * 4), *d_phi = m.alloc<double>((size_t)n), *d_E = m.alloc<double>((size_t)n * 3);
+  double *d_pair = m.alloc<double>((size_t)n * 4);
+  if (!d_xq || !d_phi || !d_E || !d_pair) return fail(ctx, GMG_ERR_HIP, "gmg_atom_forces: out of memory");
+  HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  const int bs = ctx->force_block;
+  if (want_field)
+    hipLaunchKernelGGL(gmg_forces::atom_field_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, ctx->stream, ctx->loc, u, d_xq, (int)n,
+                       d_phi, d_E);
+  if (want_pairs) CHK(launch_pairs(ctx, m, gmg_forces::ShortLaw::make(r_c), cutoff > 0.0 ? cutoff * r_c : INFINITY, n, atom_xyz,
+                                   xq.data(), d_xq, d_pair));
+  HIPC(hipGetLastError());
+  std::vector<double> E((size_t)n * 3), pair((size_t)n * 4);
+  if (phi) HIPC(hipMemcpyAsync(phi, d_phi, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (want_field) HIPC(hipMemcpyAsync(E.data(), d_E, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  if (want_pairs) HIPC(hipMemcpyAsync(pair.data(), d_pair, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) {
+      if (field) field[3 * i + d] = E[(size_t)(3 * i + d)];
+      if (force_short) force_short[3 * i + d] = pair[(size_t)(4 * i + d)];
+      if (force) force[3 * i + d] = atom_q[i] * E[(size_t)(3 * i + d)] + pair[(size_t)(4 * i + d)];
+    }
+    if (e_short) e_short[i] = pair[(size_t)(4 * i + 3)];
+  }
+  return GMG_OK;
+}
+
+int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double *force, double *energy) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (!atoms_ok(n_atoms, atom_xyz, atom_q)) return fail(ctx, GMG_ERR_INVALID, "gmg_direct_coulomb: bad arguments");
+  if (n_atoms == 0 || (!force && !energy)) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  const int64_t n = n_atoms;
+  const std::vector<double> xq = pack_xq(n, atom_xyz, atom_q);
+  DevBufs m;
+  double *d_xq = m.alloc<double>((size_t)n * 4), *d_pair = m.alloc<double>((size_t)n * 4);
+  if (!d_xq || !d_pair) return fail(ctx, GMG_ERR_HIP, "gmg_direct_coulomb: out of memory");
+  HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  CHK(launch_pairs(ctx, m, gmg_forces::DirectLaw{}, INFINITY, n, atom_xyz, xq.data(), d_xq, d_pair));
+  HIPC(hipGetLastError());
+  std::vector<double> pair((size_t)n * 4);
+  HIPC(hipMemcpyAsync(pair.data(), d_pair, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int64_t i = 0; i < n; ++i) {
+    if (force)
+      for (int d = 0; d < 3; ++d) force[3 * i + d] = pair[(size_t)(4 * i + d)];
+    if (energy) energy[i] = pair[(size_t)(4 * i + 3)];
+  }
   return GMG_OK;
 }
 
@@ -3421,6 +3596,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "sgs_phase_nosplit") ctx->sgs_phase_nosplit = on;
   else if (k == "sgs_phase_nocascade") ctx->sgs_phase_nocascade = on;
   else if (k == "sgs_phase_chunk") ctx->sgs_phase_chunk = (int)value;
+  else if (k == "force_block") {
+    if (value != 64 && value != 128 && value != 256) return fail(ctx, GMG_ERR_INVALID, "force_block: 64, 128 or 256");
+    ctx->force_block = (int)value;
+  }
   else if (k == "sgs_groups") ctx->sgs_groups = (int)value;
   else if (k == "sgs_lds_bytes_override") ctx->sgs_lds_bytes_override = (int)value;
   else if (k == "sgs_profile") {

@@ -154,6 +154,8 @@ struct step50_report {
   double energy_analytical, energy_short, energy_fe_long, energy_self, energy_total, energy_abs_error;
   double solve_seconds, energy_norm_error;
   double build_matrices_ms;  // device time of MGTransferPrebuilt::build_matrices (gmg_build_transfer) for this cycle; 0: built on the host
+  int32_t has_forces, pad2;  // "Compute forces": net force, largest |F_i|, relative RMS error against the direct sum (0: not checked)
+  double force_net[3], force_max, force_rel_error;
 };
 int step50_get_report(step50_problem *h, int i, step50_report *out) {
   const auto &reps = DISPATCH(h, reports);
@@ -174,7 +176,57 @@ int step50_get_report(step50_problem *h, int i, step50_report *out) {
   out->solve_seconds = r.solve_seconds;
   out->energy_norm_error = r.energy_norm_error;
   out->build_matrices_ms = r.build_matrices_ms;
+  out->has_forces = r.has_forces;
+  for (int d = 0; d < 3; ++d) out->force_net[d] = r.force_net[d];
+  out->force_max = r.force_max; out->force_rel_error = r.force_rel_error;
   return 0;
+}
+
+// ---- forces on the atoms of the current solution: phi_h [n], E_h [3n], F = q E_h + F^s [3n]; any
+// output may be null.  On the device when the cycle's solve ran there, else by the host mirror; cutoff = the prm's
+// "Short-range cutoff in smoothing lengths".
+namespace {
+int copy_out(const std::vector<double> &v, double *out) {
+  if (out) std::memcpy(out, v.data(), sizeof(double) * v.size());
+  return 0;
+}
+int atom_forces_impl(step50_problem *h, int where, double cutoff, double *phi, double *field, double *force, double *force_short,
+                     double *e_short) {
+  if (h->dim != 3) { h->err = "atom forces: 3D only"; return GMG_ERR_UNSUPPORTED; }
+  auto &P = *h->p3;
+  const bool dev = where < 0 ? P.forces_on_device() : where != 0;
+  std::vector<double> a, b, c, d, e;
+  const int rc = P.atom_forces(dev, cutoff < 0 ? P.par.short_range_cutoff : cutoff, phi ? &a : nullptr, field ? &b : nullptr,
+                               force ? &c : nullptr, force_short ? &d : nullptr, e_short ? &e : nullptr);
+  if (rc != GMG_OK) return rc;
+  copy_out(a, phi); copy_out(b, field); copy_out(c, force); copy_out(d, force_short); copy_out(e, e_short);
+  return 0;
+}
+int direct_coulomb_impl(step50_problem *h, int where, double *force, double *energy) {
+  if (h->dim != 3) { h->err = "direct Coulomb sum: 3D only"; return GMG_ERR_UNSUPPORTED; }
+  auto &P = *h->p3;
+  std::vector<double> f, e;
+  const int rc = P.direct_coulomb(where < 0 ? P.forces_on_device() : where != 0, force ? &f : nullptr, energy ? &e : nullptr);
+  if (rc != GMG_OK) return rc;
+  copy_out(f, force); copy_out(e, energy);
+  return 0;
+}
+}  // namespace
+int step50_atom_forces(step50_problem *h, double *phi, double *field, double *force) {
+  return guarded(h, [&] { return atom_forces_impl(h, -1, -1.0, phi, field, force, nullptr, nullptr); });
+}
+// exact all-pairs Coulomb forces [3n] and per-atom energies [n] (either may be null)
+int step50_direct_coulomb(step50_problem *h, double *force, double *energy) {
+  return guarded(h, [&] { return direct_coulomb_impl(h, -1, force, energy); });
+}
+// the same with the backend chosen (where: -1 as the cycle ran, 0 host mirror, 1 device), the cutoff given (< 0: the
+// prm's), and the pair part F^s and the per-atom short-range energies (tests compare the two backends on one solution)
+int step50_atom_forces_ex(step50_problem *h, int where, double cutoff, double *phi, double *field, double *force, double *force_short,
+                          double *e_short) {
+  return guarded(h, [&] { return atom_forces_impl(h, where, cutoff, phi, field, force, force_short, e_short); });
+}
+int step50_direct_coulomb_ex(step50_problem *h, int where, double *force, double *energy) {
+  return guarded(h, [&] { return direct_coulomb_impl(h, where, force, energy); });
 }
 
 // ---- access to what solve() consumes, so tests can hand the same inputs to the oracle

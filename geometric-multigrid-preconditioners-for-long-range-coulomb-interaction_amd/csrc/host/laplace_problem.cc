@@ -5,6 +5,7 @@
 #include <omp.h>
 #endif
 #include "partition.h"
+#include "../gmg_forces.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -229,7 +230,10 @@ void ParameterReader::declare_parameters() {
             // the short-ranged pair sum over the pairs closer than this many smoothing lengths, found through
             // cell bins (erfc(6) = 2e-17: beyond 6 r_c a pair contributes nothing in double precision); 0 = all pairs as the
             // reference (:1325-1332).  With it the energy is also evaluated for the large systems the reference skips (:1554).
-            {"Short-range cutoff in smoothing lengths", "0"}, {"Energy for large systems", "false"}};
+            {"Short-range cutoff in smoothing lengths", "0"}, {"Energy for large systems", "false"},
+            // forces on the atoms after the energy (LAMMPS input, 3D), and with them the exact all-pairs
+            // Coulomb forces and the relative RMS error against them
+            {"Compute forces", "false"}, {"Direct Coulomb check", "false"}};
 }
 void ParameterReader::parse_input_from_string(const std::string &text) {
   std::istringstream in(text);
@@ -303,6 +307,8 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
+  p.compute_forces = prm.get_bool("Compute forces");
+  p.direct_coulomb_check = prm.get_bool("Direct Coulomb check");
   p.level0_numbering = prm.get("Level 0 numbering");
   if (p.level0_numbering != "lexicographic" && p.level0_numbering != "cell-wise")
     throw std::runtime_error("Level 0 numbering must be <lexicographic> or <cell-wise>");
@@ -1607,6 +1613,157 @@ void LaplaceProblem<dim>::postprocess_electrostatic_energy() {
 }
 
 template <int dim>
+void LaplaceProblem<dim>::point_locator(std::vector<int32_t> &node) const {
+  const int L = triangulation.n_levels();
+  std::vector<int64_t> off((size_t)L + 1, 0);
+  for (int l = 0; l < L; ++l) off[(size_t)l + 1] = off[(size_t)l] + (int64_t)triangulation.levels[(size_t)l].size();
+  node.resize((size_t)off[(size_t)L]);
+  for (int l = 0; l < L; ++l)
+    for (size_t c = 0; c < triangulation.levels[(size_t)l].size(); ++c) {
+      const Cell &cell = triangulation.levels[(size_t)l][c];
+      node[(size_t)off[(size_t)l] + c] = cell.first_child >= 0 ? (int32_t)(off[(size_t)l + 1] + cell.first_child)
+                                                                : -active_index_of_cell[(size_t)l][c] - 1;
+    }
+}
+
+template <int dim>
+int LaplaceProblem<dim>::atom_forces(bool on_device, double cutoff, std::vector<double> *phi, std::vector<double> *field,
+                                     std::vector<double> *force, std::vector<double> *force_short, std::vector<double> *e_short) {
+  if (dim != 3) { last_error = "atom forces: 3D only"; return GMG_ERR_UNSUPPORTED; }
+  if (solution.size() != vertex_of_dof.size() || active_cells.empty()) { last_error = "atom forces: no solution of this mesh"; return GMG_ERR_INVALID; }
+  const int64_t n = number_of_atoms;
+  for (std::vector<double> *v : {phi, e_short})
+    if (v) v->assign((size_t)n, 0.0);
+  for (std::vector<double> *v : {field, force, force_short})
+    if (v) v->assign((size_t)n * 3, 0.0);
+  std::vector<int32_t> node;
+  point_locator(node);
+  const int32_t n0[3] = {triangulation.n0, triangulation.n0, triangulation.n0};
+  const double origin[3] = {triangulation.origin, triangulation.origin, triangulation.origin};
+  auto data = [](std::vector<double> *v) { return v ? v->data() : nullptr; };
+  if (on_device) {
+    GMGC(ensure_context());
+    GMGC(gmg_set_point_locator(gmg, n0, origin, triangulation.h0, (int64_t)node.size(), node.data(), (int64_t)active_cells.size(),
+                               active_cell_dof_table.data()));
+    double *d_u = nullptr;
+    GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
+    int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (rc == GMG_OK)
+      rc = gmg_atom_forces(gmg, n, atom_positions.data(), charges.data(), d_u, (int64_t)solution.size(), par.r_c, cutoff, data(phi),
+                           data(field), data(force), data(force_short), data(e_short));
+    if (rc != GMG_OK) last_error = std::string("gmg_atom_forces: ") + gmg_last_error(gmg);
+    gmg_vec_free(gmg, d_u);
+    return rc;
+  }
+  // host mirror: the same per-atom functions (gmg_forces.hpp), one atom per iteration
+  const gmg_forces::Locator L{{n0[0], n0[1], n0[2]}, {origin[0], origin[1], origin[2]}, triangulation.h0, node.data(),
+                              active_cell_dof_table.data()};
+  std::vector<double> E((size_t)n * 3), pair((size_t)n * 4, 0.0), xq((size_t)n * 4);
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) xq[(size_t)(4 * i + d)] = atom_positions[(size_t)(3 * i + d)];
+    xq[(size_t)(4 * i + 3)] = charges[(size_t)i];
+  }
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n; ++i) {
+    double p;
+    gmg_forces::atom_field(L, solution.data(), &atom_positions[(size_t)(3 * i)], p, &E[(size_t)(3 * i)]);
+    if (phi) (*phi)[(size_t)i] = p;
+  }
+  const gmg_forces::ShortLaw law = gmg_forces::ShortLaw::make(par.r_c);
+  if (cutoff > 0.0) {
+    gmg_forces::Bins B;
+    gmg_forces::force_bins(n, atom_positions.data(), cutoff * par.r_c, B);
+    std::vector<double> sorted((size_t)n * 4);
+    for (int64_t k = 0; k < n; ++k)
+      for (int c = 0; c < 4; ++c) sorted[(size_t)(4 * k + c)] = xq[4 * (size_t)B.items[(size_t)k] + c];
+    const int64_t n_bins = (int64_t)B.ptr.size() - 1;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t b = 0; b < n_bins; ++b)
+      for (int64_t k = B.ptr[(size_t)b]; k < B.ptr[(size_t)b + 1]; ++k) {
+        double acc[4] = {0, 0, 0, 0};
+        gmg_forces::for_each_row(B.n, B.ptr.data(), b, [&](int64_t ks, int64_t ke) {
+          for (int64_t kj = ks; kj < ke; ++kj)
+            if (kj != k) gmg_forces::pair_add(law, cutoff * par.r_c, &sorted[(size_t)(4 * k)], &sorted[(size_t)(4 * kj)], acc);
+        });
+        double *o = &pair[4 * (size_t)B.items[(size_t)k]];
+        for (int c = 0; c < 3; ++c) o[c] = acc[c];
+        o[3] = 0.5 * acc[3];
+      }
+  } else {
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t i = 0; i < n; ++i) {
+      double acc[4] = {0, 0, 0, 0};
+      for (int64_t j = 0; j < n; ++j)
+        if (j != i) gmg_forces::pair_add(law, INFINITY, &xq[(size_t)(4 * i)], &xq[(size_t)(4 * j)], acc);
+      for (int c = 0; c < 3; ++c) pair[(size_t)(4 * i + c)] = acc[c];
+      pair[(size_t)(4 * i + 3)] = 0.5 * acc[3];
+    }
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) {
+      if (field) (*field)[(size_t)(3 * i + d)] = E[(size_t)(3 * i + d)];
+      if (force_short) (*force_short)[(size_t)(3 * i + d)] = pair[(size_t)(4 * i + d)];
+      if (force) (*force)[(size_t)(3 * i + d)] = charges[(size_t)i] * E[(size_t)(3 * i + d)] + pair[(size_t)(4 * i + d)];
+    }
+    if (e_short) (*e_short)[(size_t)i] = pair[(size_t)(4 * i + 3)];
+  }
+  return GMG_OK;
+}
+
+template <int dim>
+int LaplaceProblem<dim>::direct_coulomb(bool on_device, std::vector<double> *force, std::vector<double> *energy) {
+  const int64_t n = number_of_atoms;
+  if (force) force->assign((size_t)n * 3, 0.0);
+  if (energy) energy->assign((size_t)n, 0.0);
+  if (on_device) {
+    GMGC(ensure_context());
+    GMGC(gmg_direct_coulomb(gmg, n, atom_positions.data(), charges.data(), force ? force->data() : nullptr, energy ? energy->data() : nullptr));
+    return GMG_OK;
+  }
+  std::vector<double> xq((size_t)n * 4);
+  for (int64_t i = 0; i < n; ++i) {
+    for (int d = 0; d < 3; ++d) xq[(size_t)(4 * i + d)] = atom_positions[(size_t)(3 * i + d)];
+    xq[(size_t)(4 * i + 3)] = charges[(size_t)i];
+  }
+  const gmg_forces::DirectLaw law;
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int64_t i = 0; i < n; ++i) {
+    double acc[4] = {0, 0, 0, 0};
+    for (int64_t j = 0; j < n; ++j)
+      if (j != i) gmg_forces::pair_add(law, INFINITY, &xq[(size_t)(4 * i)], &xq[(size_t)(4 * j)], acc);
+    if (force)
+      for (int c = 0; c < 3; ++c) (*force)[(size_t)(3 * i + c)] = acc[c];
+    if (energy) (*energy)[(size_t)i] = 0.5 * acc[3];
+  }
+  return GMG_OK;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::postprocess_forces() {
+  CycleReport &rep = reports.back();
+  const bool dev = forces_on_device();
+  std::vector<double> F, Fd;
+  if (atom_forces(dev, par.short_range_cutoff, nullptr, nullptr, &F, nullptr, nullptr) != GMG_OK) throw std::runtime_error(last_error);
+  double net[3] = {0, 0, 0}, fmax = 0;
+  for (unsigned i = 0; i < number_of_atoms; ++i) {
+    double f2 = 0;
+    for (int d = 0; d < 3; ++d) { net[d] += F[3 * i + (size_t)d]; f2 += F[3 * i + (size_t)d] * F[3 * i + (size_t)d]; }
+    fmax = std::max(fmax, std::sqrt(f2));
+  }
+  rep.has_forces = true;
+  for (int d = 0; d < 3; ++d) rep.force_net[d] = net[d];
+  rep.force_max = fmax;
+  pcout("Net force on the atoms : (" + fmt("%.10e", net[0]) + ", " + fmt("%.10e", net[1]) + ", " + fmt("%.10e", net[2]) + ")");
+  pcout("Largest force on an atom :  " + fmt("%.10e", fmax));
+  if (!par.direct_coulomb_check) return;
+  if (direct_coulomb(dev, &Fd, nullptr) != GMG_OK) throw std::runtime_error(last_error);
+  double num = 0, den = 0;
+  for (size_t k = 0; k < F.size(); ++k) { num += (F[k] - Fd[k]) * (F[k] - Fd[k]); den += Fd[k] * Fd[k]; }
+  rep.force_rel_error = den > 0 ? std::sqrt(num) / std::sqrt(den) : 0.0;
+  pcout("Relative RMS error of the forces against the direct Coulomb sum :  " + fmt("%.10e", rep.force_rel_error));
+}
+
+template <int dim>
 void LaplaceProblem<dim>::postprocess_error_in_energy_norm() {
   // :1423-1461 -- || grad phi_h - grad phi_exact ||_L2 with QGauss(degree+1) per cell and the
   // analytical gradient of include/step_50.h:355-369 (GaussianCharges only; the reference
@@ -1735,6 +1892,7 @@ void LaplaceProblem<dim>::finish_cycle() {
     postprocess_electrostatic_energy();     // :1554-1555
     if (number_of_atoms < 300) postprocess_error_in_energy_norm();  // :1556 (O(cells x atoms): under the reference's small-system gate only)
   }
+  if (lammpsinput && dim == 3 && par.compute_forces) postprocess_forces();  // (3D atoms exist only with LAMMPS input)
 }
 
 // Test hook: a solution computed elsewhere (the CPU oracle in tests/) takes the place of solve();

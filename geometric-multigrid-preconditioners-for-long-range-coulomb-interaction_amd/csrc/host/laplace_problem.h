@@ -69,7 +69,9 @@ struct Parameters {
   std::string partition_level0 = "auto";  // one process per GPU: auto | always | never
   std::string refinement_estimator = "Kelly + residual";  // HEAD (:1040-1089) | "Kelly": the indicator of the older cluster runs
   double short_range_cutoff = 0.0;        // in smoothing lengths; 0: all pairs (the reference)
-  bool energy_for_large_systems = false;  // evaluate the energy also for >= 300 atoms (needs the cutoff; the reference skips it, :1554)
+  bool energy_for_large_systems = false;
+  bool compute_forces = false;        // forces on the atoms after the energy (LAMMPS input, 3D), DESIGN.md section 9
+  bool direct_coulomb_check = false;  // with them the exact all-pairs Coulomb forces and the relative RMS error against them  // evaluate the energy also for >= 300 atoms (needs the cutoff; the reference skips it, :1554)
   bool rhs_on_device = true;            // gmg_rhs_assemble: F integrated on the device from densities that stay there
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
@@ -92,6 +94,8 @@ struct CycleReport {  // the values the reference prints per cycle (src/step-50.
   double solve_seconds = 0;  // first residual to convergence, excluding upload / build_matrices
   double build_matrices_ms = 0;  // device time of mg_transfer.build_matrices (:957-958) when the device builds the transfers
   int status = 0;
+  bool has_forces = false;  // "Compute forces": sum_i F_i, max_i |F_i|, ||F - F^d|| / ||F^d|| ("Direct Coulomb check", else 0)
+  double force_net[3] = {0, 0, 0}, force_max = 0, force_rel_error = 0;
 };
 
 template <int dim>
@@ -126,6 +130,14 @@ class LaplaceProblem {
   void refine_grid(unsigned int cycle);                                  // :1095-1121
   void postprocess_electrostatic_energy();                               // :1310-1420
   void postprocess_error_in_energy_norm();                               // :1423-1461
+  void postprocess_forces();                                             // forces on the atoms (no counterpart in the reference)
+  // Per-atom phi_h, E_h, F = q E_h + F^s, F^s, e_short (any output may be null) of the current solution, cutoff in units of
+  // r_c (0: all pairs); on the device through gmg_atom_forces, or by the host mirror of the same definitions (gmg_forces.hpp).
+  int atom_forces(bool on_device, double cutoff, std::vector<double> *phi, std::vector<double> *field, std::vector<double> *force,
+                  std::vector<double> *force_short, std::vector<double> *e_short);
+  int direct_coulomb(bool on_device, std::vector<double> *force, std::vector<double> *energy);  // exact all-pairs sum
+  bool forces_on_device() const { return solve_on_device_requested && gmg != nullptr; }  // where the cycle's solve ran
+  void point_locator(std::vector<int32_t> &node) const;  // the forest flattened for gmg_set_point_locator
   std::vector<double> total_charge_density_vector() const;               // tests_rhs_rc_variation/rc_variation.cc:110-215
   int run_cycle(unsigned int cycle, bool on_device = true);              // one iteration of the loop in run()
   void finish_cycle();                                   // estimator + energy, the tail of the loop body

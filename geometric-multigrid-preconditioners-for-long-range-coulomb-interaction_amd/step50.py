@@ -25,11 +25,14 @@ class Report(C.Structure):
                 ("sol_l1", C.c_double), ("sol_l2", C.c_double), ("sol_linf", C.c_double), ("refine_threshold", C.c_double),
                 ("energy_analytical", C.c_double), ("energy_short", C.c_double), ("energy_fe_long", C.c_double),
                 ("energy_self", C.c_double), ("energy_total", C.c_double), ("energy_abs_error", C.c_double),
-                ("solve_seconds", C.c_double), ("energy_norm_error", C.c_double), ("build_matrices_ms", C.c_double)]
+                ("solve_seconds", C.c_double), ("energy_norm_error", C.c_double), ("build_matrices_ms", C.c_double),
+                ("has_forces", C.c_int32), ("pad2", C.c_int32),
+                ("force_net", C.c_double * 3), ("force_max", C.c_double), ("force_rel_error", C.c_double)]
 
     def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("dofs_by_level", "pad")}
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("dofs_by_level", "pad", "pad2", "force_net")}
         d["dofs_by_level"] = [int(self.dofs_by_level[i]) for i in range(self.n_levels)]
+        d["force_net"] = [float(v) for v in self.force_net]
         return d
 
 
@@ -84,6 +87,8 @@ def prm_text(**kw) -> str:
         "rhs_on_device": ("Misc", "RHS on device"),
         "short_range_cutoff": ("Misc", "Short-range cutoff in smoothing lengths"),
         "energy_for_large_systems": ("Misc", "Energy for large systems"),
+        "compute_forces": ("Misc", "Compute forces"),
+        "direct_coulomb_check": ("Misc", "Direct Coulomb check"),
     }
     sections = {}
     for k, v in kw.items():
@@ -150,6 +155,28 @@ class Problem:
     def solve_again(self):
         self._chk(self.L.step50_solve_again(self.h), "solve")
         return self.report(-1)
+
+    def atom_forces(self, on_device=None, cutoff=None, parts=False):
+        """Forces on the atoms from the current solution: (phi_h, E_h, F) with F = q E_h + F^s, as numpy arrays [n], [n, 3],
+        [n, 3].  on_device None: where the cycle's solve ran; False: the host mirror; True: the device.  cutoff in units of
+        r_c (None: the prm's short-range cutoff, 0: all pairs).  parts=True adds F^s [n, 3] and the per-atom short-range
+        energies e_short [n]."""
+        n = self.L.step50_n_atoms(self.h)
+        phi, E, F, Fs, es = np.zeros(n), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n)
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        where = -1 if on_device is None else int(bool(on_device))
+        self._chk(self.L.step50_atom_forces_ex(self.h, C.c_int(where), C.c_double(-1.0 if cutoff is None else cutoff), P(phi), P(E), P(F),
+                                               P(Fs), P(es)), "atom_forces")
+        return (phi, E, F, Fs, es) if parts else (phi, E, F)
+
+    def direct_coulomb(self, on_device=None):
+        """Exact all-pairs Coulomb forces [n, 3] and per-atom energies [n] (on_device as in atom_forces)."""
+        n = self.L.step50_n_atoms(self.h)
+        F, e = np.zeros((n, 3)), np.zeros(n)
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        where = -1 if on_device is None else int(bool(on_device))
+        self._chk(self.L.step50_direct_coulomb_ex(self.h, C.c_int(where), P(F), P(e)), "direct_coulomb")
+        return F, e
 
     def estimator_components(self):
         """Per active cell of the cycle just estimated: (Kelly face sum eta_K^2, residual term, level, centre)."""

@@ -162,6 +162,35 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
                      const double *term_value, int64_t n_dofs, const int64_t *dof_ptr, const int32_t *entry_slot,
                      const uint8_t *entry_coef, const double *coef_table /* [256] */, double *rhs);
 
+/* ---- forces on the atoms ------------------------------------------- */
+/* The field E = -grad phi_h that GradientPostprocessor writes (src/step-50.cc:1124-1161), taken at the atoms, plus the
+ * short-range pair forces of the erfc split (:1325-1332): F_i = q_i E_h(x_i) + F^s_i.  Definitions (gmg_forces.hpp):
+ *   E_h(x) = -(1/n) sum over the octants s = 0..7 that stay in the lattice of grad u_K(s)(x), K(s) the active cell around x
+ *            with coordinates on a cell boundary sent to the upper side in the directions of the bits of s (root lattice and
+ *            every child split), u_K the trilinear interpolant; octant 7 is the cell of the energy's phi_h(x_i) (:1354-1363)
+ *   F^s_i  = sum_{j != i, r < cutoff r_c} q_i q_j [erfc(r/r_c)/r^2 + 2/(sqrt(pi) r_c) exp(-r^2/r_c^2)/r] (x_i - x_j)/r
+ *   e_i    = 1/2 sum_{j != i, r < cutoff r_c} q_i q_j erfc(r/r_c)/r
+ * Every per-atom value is one sequential sum (atom / bin order): deterministic, independent of the launch shape.
+ *
+ * Point location (kept until gmg_reset): root lattice n0[3] at origin with cell size h0; the forest flattened level by
+ * level, roots first in lexicographic order (x fastest); node[k] >= 0: flat index of child 0 (children contiguous, child
+ * a = bx + 2 by + 4 bz), node[k] < 0: active cell -node[k]-1; active_dofs[8 * a + v]: DoF of vertex v of active cell a.
+ * 3D only (there is no 2D entry).  GMG_ERR_INVALID for bad sizes, a node index out of range or behind its parent, or more
+ * than 20 levels.                                                                                                         */
+int gmg_set_point_locator(gmg_context *ctx, const int32_t n0[3], const double origin[3], double h0, int64_t n_nodes,
+                          const int32_t *node, int64_t n_active, const int32_t *active_dofs);
+/* phi/field/force/force_short (host arrays [n], [3n], [3n], [3n]) and the per-atom short-range energy e_short [n] (any may
+ * be NULL) from the constraint-distributed solution u (device vector of n_u entries, all DoFs); cutoff in units of r_c,
+ * 0 = all pairs (N-body tiles), > 0 = the pairs of the 27 neighbouring cell bins.  Two additions to the plain form:
+ * n_u, so that a DoF of the locator beyond the end of u is refused (GMG_ERR_INVALID) instead of read, and force_short,
+ * the pair part alone, which F - q E would return only up to cancellation.  GMG_ERR_INVALID before gmg_set_point_locator. */
+int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u, int64_t n_u,
+                    double r_c, double cutoff, double *phi, double *field, double *force, double *force_short, double *e_short);
+/* exact all-pairs Coulomb forces F^d_i = sum_{j != i} q_i q_j (x_i - x_j)/r^3 and per-atom energies 1/2 sum_{j != i}
+ * q_i q_j / r (either may be NULL).                                                                                     */
+int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double *force,
+                       double *energy);
+
 /* ---- distributed (one process per GPU, RCCL over xGMI) ------------------------------ */
 #define GMG_UNIQUE_ID_BYTES 128
 int gmg_comm_unique_id(void *out_id);                       /* rank 0, then broadcast by the host.  Default: an RCCL id.  With
@@ -256,7 +285,8 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * several LDS ranges), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
  * sgs_phase_profile (cycle counters of the four-wave sweep: same results, one rank only), sgs_profile (instrumented
  * one-wave sweep; its wrong-result timing modes exist only in a -DGMG_EXPERIMENTS build, tools/build_experiments.sh),
- * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP).  Options that shape a device
+ * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
+ * 256: workgroup size of the force kernels; the results do not depend on it).  Options that shape a device
  * layout take effect at the next gmg_set_*_matrix.  The same keys are read once from the environment
  * variable GMG_OPTIONS="key=value,..." at gmg_create (for profiling scripts around bench.py).        */
 int gmg_set_option(gmg_context *ctx, const char *key, double value);
