@@ -33,6 +33,7 @@ SYMBOLS = [
     "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks",
     "gmg_set_ssor_block_rows", "gmg_set_ssor_partition", "gmg_get_ssor_partition", "gmg_ssor_balance_rows", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
     "gmg_set_point_locator", "gmg_atom_forces", "gmg_direct_coulomb",
+    "gmg_gaussian_potential", "gmg_energy_norm_error",
 ]
 
 
@@ -310,6 +311,36 @@ class Context:
         self._chk(self.L.gmg_direct_coulomb(self.h, C.c_int64(len(q)), _p(xyz, C.c_double), _p(q, C.c_double), _p(F, C.c_double),
                                             _p(e, C.c_double)))
         return F, e
+
+    # ---- exact free-space potential of the Gaussian charges (gmg_exact.hpp)
+    def gaussian_potential(self, atom_xyz, atom_q, r_c, points, want_phi=True, want_grad=True):
+        """phi [n] and grad [n, 3] (None when not wanted) of all atoms at the points [n, 3]."""
+        xyz = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(atom_q, dtype=np.float64)
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        phi = np.zeros(len(pts)) if want_phi else None
+        grad = np.zeros((len(pts), 3)) if want_grad else None
+        D = lambda a: _p(a, C.c_double) if a is not None else None
+        self._chk(self.L.gmg_gaussian_potential(self.h, C.c_int64(len(q)), D(xyz), D(q), C.c_double(r_c), C.c_int64(len(pts)), D(pts),
+                                                D(phi), D(grad)))
+        return phi, grad
+
+    def energy_norm_error(self, cell_lo, cell_h, cell_dofs, u, atom_xyz, atom_q, r_c, quadrature_points, weights, shape_grad):
+        """u: DeviceVector of the constraint-distributed solution -> (error, cell_err2 [n_cells])."""
+        lo = np.ascontiguousarray(cell_lo, dtype=np.float64).reshape(-1, 3)
+        hh = np.ascontiguousarray(cell_h, dtype=np.float64)
+        dofs = np.ascontiguousarray(cell_dofs, dtype=np.int32).reshape(-1, 8)
+        xyz = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(atom_q, dtype=np.float64)
+        qp = np.ascontiguousarray(quadrature_points, dtype=np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        sg = np.ascontiguousarray(shape_grad, dtype=np.float64).reshape(len(w), 8, 3)
+        err, ce = C.c_double(0), np.zeros(len(hh))
+        D = lambda a: _p(a, C.c_double)
+        self._chk(self.L.gmg_energy_norm_error(self.h, C.c_int64(len(hh)), D(lo), D(hh), _p(dofs, C.c_int32), u.ptr, C.c_int64(u.n),
+                                               C.c_int64(len(q)), D(xyz), D(q), C.c_double(r_c), C.c_int(len(w)), D(qp), D(w), D(sg),
+                                               C.byref(err), D(ce)))
+        return err.value, ce
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

@@ -18,6 +18,7 @@
 #include "gmg_lattice.hpp"
 #include "gmg_transfer.hpp"
 #include "gmg_forces.hpp"
+#include "gmg_exact.hpp"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -202,6 +203,7 @@ struct gmg_context {
   int32_t *loc_node = nullptr, *loc_dofs = nullptr;
   int64_t loc_max_dof = -1;  // -1: no locator set
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
+  int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
   int64_t sys_global = 0, l0_global = 0;  // l0_global == 0 on a communicator: level 0 is replicated, only the outer CG is partitioned
@@ -3338,6 +3340,96 @@ int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz
   return GMG_OK;
 }
 
+// ---- exact free-space potential of the Gaussian charges (gmg_exact.hpp) ----
+// Both calls cut their points into launches of at most 2^exact_chunk_log2 point-atom evaluations (at least one point or cell
+// per launch): a launch stays short whatever the sizes.  Every value is one lane's sequential sum, so the cuts change no bit.
+
+int gmg_gaussian_potential(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, int64_t n_points,
+                           const double *point_xyz, double *phi, double *grad) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (!atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || n_points < 0 || (n_points > 0 && !point_xyz))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_gaussian_potential: bad arguments");
+  if (n_points == 0 || (!phi && !grad)) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  const std::vector<double> xq = pack_xq(n_atoms, atom_xyz, atom_q);
+  DevBufs m;
+  double *d_xq = m.alloc<double>(xq.size()), *d_pts = m.alloc<double>(3 * (size_t)n_points);
+  double *d_phi = phi ? m.alloc<double>((size_t)n_points) : nullptr, *d_grad = grad ? m.alloc<double>(3 * (size_t)n_points) : nullptr;
+  if (!d_xq || !d_pts || (phi && !d_phi) || (grad && !d_grad)) return fail(ctx, GMG_ERR_HIP, "gmg_gaussian_potential: out of memory");
+  HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * xq.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_pts, point_xyz, sizeof(double) * 3 * (size_t)n_points, hipMemcpyHostToDevice, ctx->stream));
+  const int bs = ctx->force_block;
+  const size_t lds = sizeof(double) * 4 * (size_t)bs;
+  const gmg_exact::Gauss g = gmg_exact::Gauss::make(r_c);
+  const int64_t per_launch = std::max<int64_t>(1, ((int64_t)1 << ctx->exact_chunk_log2) / std::max<int64_t>(n_atoms, 1));
+  for (int64_t p0 = 0; p0 < n_points; p0 += per_launch) {
+    const int64_t p1 = std::min(n_points, p0 + per_launch);
+    const dim3 grid((unsigned)((p1 - p0 + bs - 1) / bs));
+    if (phi && grad)
+      hipLaunchKernelGGL((gmg_exact::gauss_potential_kernel<true, true>), grid, dim3(bs), lds, ctx->stream, g, d_xq, (int)n_atoms, d_pts, p0, p1, d_phi, d_grad);
+    else if (phi)
+      hipLaunchKernelGGL((gmg_exact::gauss_potential_kernel<true, false>), grid, dim3(bs), lds, ctx->stream, g, d_xq, (int)n_atoms, d_pts, p0, p1, d_phi, d_grad);
+    else
+      hipLaunchKernelGGL((gmg_exact::gauss_potential_kernel<false, true>), grid, dim3(bs), lds, ctx->stream, g, d_xq, (int)n_atoms, d_pts, p0, p1, d_phi, d_grad);
+  }
+  HIPC(hipGetLastError());
+  if (phi) HIPC(hipMemcpyAsync(phi, d_phi, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost, ctx->stream));
+  if (grad) HIPC(hipMemcpyAsync(grad, d_grad, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_lo, const double *cell_h, const int32_t *cell_dofs,
+                          const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, int nq,
+                          const double *quadrature_points, const double *weights, const double *shape_grad, double *error,
+                          double *cell_err2) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (n_cells < 0 || n_cells >= ((int64_t)1 << 28) || n_u < 0 || !atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || nq < 1 ||
+      (n_cells > 0 && (!cell_lo || !cell_h || !cell_dofs || !u || !quadrature_points || !weights || !shape_grad)))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_energy_norm_error: bad arguments");
+  if (nq > 64) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_energy_norm_error: more than 64 quadrature points per cell");
+  for (int64_t i = 0; i < 8 * n_cells; ++i)
+    if (cell_dofs[i] < 0 || cell_dofs[i] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_energy_norm_error: a DoF of a cell lies beyond the end of u");
+  if (n_cells == 0) {
+    if (error) *error = 0.0;
+    return GMG_OK;
+  }
+  (void)hipSetDevice(ctx->device);
+  const std::vector<double> xq = pack_xq(n_atoms, atom_xyz, atom_q);
+  const size_t nc = (size_t)n_cells;
+  DevBufs m;
+  double *d_xq = m.alloc<double>(xq.size()), *d_lo = m.alloc<double>(3 * nc), *d_h = m.alloc<double>(nc), *d_err = m.alloc<double>(nc);
+  double *d_qp = m.alloc<double>(3 * (size_t)nq), *d_w = m.alloc<double>((size_t)nq), *d_sg = m.alloc<double>(24 * (size_t)nq);
+  int32_t *d_dofs = m.alloc<int32_t>(8 * nc);
+  if (!d_xq || !d_lo || !d_h || !d_err || !d_qp || !d_w || !d_sg || !d_dofs) return fail(ctx, GMG_ERR_HIP, "gmg_energy_norm_error: out of memory");
+  HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * xq.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_lo, cell_lo, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_h, cell_h, sizeof(double) * nc, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_dofs, cell_dofs, sizeof(int32_t) * 8 * nc, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_qp, quadrature_points, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_w, weights, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_sg, shape_grad, sizeof(double) * 24 * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
+  const int bs = ctx->force_block, per_block = bs / nq;
+  const size_t lds = sizeof(double) * 5 * (size_t)bs;  // the atom tile and one value per lane
+  gmg_exact::ErrorArgs a{gmg_exact::Gauss::make(r_c), d_xq, (int)n_atoms, nq, d_lo, d_h, d_dofs, u, d_qp, d_w, d_sg, 0, 0, d_err};
+  const int64_t points = std::max<int64_t>(1, ((int64_t)1 << ctx->exact_chunk_log2) / std::max<int64_t>(n_atoms, 1));
+  const int64_t per_launch = std::max<int64_t>(1, points / nq);
+  for (int64_t c0 = 0; c0 < n_cells; c0 += per_launch) {
+    a.c0 = c0;
+    a.c1 = std::min(n_cells, c0 + per_launch);
+    hipLaunchKernelGGL(gmg_exact::energy_error_kernel, dim3((unsigned)((a.c1 - a.c0 + per_block - 1) / per_block)), dim3(bs), lds, ctx->stream, a);
+  }
+  // sum over the cells: partials per workgroup, then one workgroup (the grid depends on n_cells alone)
+  const int grid = grid_for(n_cells);
+  hipLaunchKernelGGL(sum_partial_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, (const double *)d_err, n_cells, ctx->part_a);
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a, grid, 1, 0u, ctx->scal_dev);
+  HIPC(hipGetLastError());
+  if (cell_err2) HIPC(hipMemcpyAsync(cell_err2, d_err, sizeof(double) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  CHK(fetch_scalars(ctx, 1));
+  if (error) *error = std::sqrt(ctx->scal_host[0]);
+  return GMG_OK;
+}
+
 // assemble_system's right-hand side (src/step-50.cc:813-828) from densities that never left the device: per cell
 // F_i = sum_q phi_i(x_q) rho(x_q) w_q JxW (:813-820), the Dirichlet terms -K_ij g_j (:825-828) as a list of subtractions, and
 // the scatter into the DoFs as a per-DoF gather over the (cell, vertex) slots in the reference's cell order with the
@@ -3599,6 +3691,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "force_block") {
     if (value != 64 && value != 128 && value != 256) return fail(ctx, GMG_ERR_INVALID, "force_block: 64, 128 or 256");
     ctx->force_block = (int)value;
+  }
+  else if (k == "exact_chunk_log2") {
+    if (!(value >= 0 && value <= 35) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "exact_chunk_log2: an integer in 0 .. 35");
+    ctx->exact_chunk_log2 = (int)value;
   }
   else if (k == "sgs_groups") ctx->sgs_groups = (int)value;
   else if (k == "sgs_lds_bytes_override") ctx->sgs_lds_bytes_override = (int)value;

@@ -1177,6 +1177,14 @@ __global__ __launch_bounds__(kThreads) void dot_partial_kernel(const double *x, 
   const double s = block_sum(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
+// partial sum of x (the per-cell errors of gmg_energy_norm_error): out[blockIdx]
+__global__ __launch_bounds__(kThreads) void sum_partial_kernel(const double *x, int64_t n, double *part) {
+  __shared__ double red[4];
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) acc += x[i];
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
 // partials of (sum |x|, sum x^2, max |x|, count of nonzeros) -> part[4 * grid]
 __global__ __launch_bounds__(kThreads) void norms_partial_kernel(const double *x, int64_t n, double *part) {
   __shared__ double red[4];

@@ -229,6 +229,38 @@ int step50_direct_coulomb_ex(step50_problem *h, int where, double *force, double
   return guarded(h, [&] { return direct_coulomb_impl(h, where, force, energy); });
 }
 
+// ---- the exact free-space potential of the atoms; where: -1 as the cycle ran, 0 host mirror, 1 device.
+// phi [n] and grad [3n] at n points [3n] (either output may be null)
+int step50_gaussian_potential(step50_problem *h, int where, int64_t n, const double *points, double *phi, double *grad) {
+  return guarded(h, [&] {
+    if (h->dim != 3) { h->err = "exact potential: 3D only"; return (int)GMG_ERR_UNSUPPORTED; }
+    auto &P = *h->p3;
+    return P.gaussian_potential(where < 0 ? P.exact_on_device() : where != 0, n, points, phi, grad);
+  });
+}
+// error of the current solution in the energy norm and its per-cell squares [step50_n_cells] (either may be null)
+int64_t step50_n_cells(step50_problem *h) { return (int64_t)DISPATCH(h, active_cells.size()); }
+int step50_cell_errors(step50_problem *h, int where, double *error, double *cell_err2) {
+  return guarded(h, [&] {
+    if (h->dim != 3) { h->err = "energy norm error: 3D only"; return (int)GMG_ERR_UNSUPPORTED; }
+    auto &P = *h->p3;
+    std::vector<double> ce;
+    const int rc = P.energy_norm_error(where < 0 ? P.exact_on_device() : where != 0, error, cell_err2 ? &ce : nullptr);
+    if (rc == GMG_OK) copy_out(ce, cell_err2);
+    return rc;
+  });
+}
+// the inhomogeneity of every DoF's constraint line (0 for unconstrained DoFs): Dirichlet values, and what close() folded
+// into the hanging-node lines
+int step50_constraint_inhomogeneities(step50_problem *h, double *out) {
+  const auto &c = DISPATCH(h, constraint_of_dof);
+  auto fill = [&](auto &P) {
+    for (size_t i = 0; i < c.size(); ++i) out[i] = c[i] >= 0 ? P.constraint_lines[(size_t)c[i]].inhomogeneity : 0.0;
+  };
+  if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+  return 0;
+}
+
 // ---- access to what solve() consumes, so tests can hand the same inputs to the oracle
 int step50_n_levels(step50_problem *h) { return h->dim == 2 ? h->p2->triangulation.n_levels() : h->p3->triangulation.n_levels(); }
 int step50_matrix_shape(step50_problem *h, int kind, int level, int64_t *n_rows, int64_t *n_cols, int64_t *nnz) {

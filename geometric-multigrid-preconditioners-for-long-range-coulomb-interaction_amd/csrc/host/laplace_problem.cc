@@ -6,6 +6,7 @@
 #endif
 #include "partition.h"
 #include "../gmg_forces.hpp"
+#include "../gmg_exact.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -233,7 +234,11 @@ void ParameterReader::declare_parameters() {
             {"Short-range cutoff in smoothing lengths", "0"}, {"Energy for large systems", "false"},
             // forces on the atoms after the energy (LAMMPS input, 3D), and with them the exact all-pairs
             // Coulomb forces and the relative RMS error against them
-            {"Compute forces", "false"}, {"Direct Coulomb check", "false"}};
+            {"Compute forces", "false"}, {"Direct Coulomb check", "false"},
+            // the exact free-space potential summed over all atoms in batches (gmg_exact.hpp): the
+            // Exact boundary values and the error norm on the device (or by its host mirror), and with it the error norm
+            // beyond the reference's 300-atom gate (:1554-1556)
+            {"Analytical solution on device", "false"}, {"Error norm for large systems", "false"}};
 }
 void ParameterReader::parse_input_from_string(const std::string &text) {
   std::istringstream in(text);
@@ -309,6 +314,8 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
   p.compute_forces = prm.get_bool("Compute forces");
   p.direct_coulomb_check = prm.get_bool("Direct Coulomb check");
+  p.analytical_on_device = prm.get_bool("Analytical solution on device");
+  p.error_norm_for_large_systems = prm.get_bool("Error norm for large systems");
   p.level0_numbering = prm.get("Level 0 numbering");
   if (p.level0_numbering != "lexicographic" && p.level0_numbering != "cell-wise")
     throw std::runtime_error("Level 0 numbering must be <lexicographic> or <cell-wise>");
@@ -692,14 +699,30 @@ void LaplaceProblem<dim>::make_constraints() {
   (void)shift0;
   // Dirichlet lines for boundary DoFs that are not already (hanging-node) constrained
   if (lammpsinput) compute_moments();
+  // "Analytical solution on device": the Exact values of all boundary DoFs in one batch (gmg_exact.hpp) instead of one
+  // sequential sum over the atoms per DoF; the lines are created in the same DoF order either way
+  const bool batch = par.analytical_on_device && dim == 3 && par.Boundary_conditions == "Exact" && par.Problemtype == "GaussianCharges";
+  std::vector<int32_t> batch_line;
+  std::vector<double> batch_x;
   for (int64_t i = 0; i < n; ++i) {
     if (!triangulation.vertex_on_boundary(vertex_of_dof[(size_t)i]) || constraint_of_dof[(size_t)i] >= 0) continue;
     double x[3];
     triangulation.vertex_coords(vertex_of_dof[(size_t)i], x);
     ConstraintLine line;
-    line.inhomogeneity = boundary_value(x);
+    if (batch) {
+      batch_line.push_back((int32_t)constraint_lines.size());
+      batch_x.insert(batch_x.end(), x, x + 3);
+    } else {
+      line.inhomogeneity = boundary_value(x);
+    }
     constraint_of_dof[(size_t)i] = (int32_t)constraint_lines.size();
     constraint_lines.push_back(line);
+  }
+  if (!batch_line.empty()) {
+    std::vector<double> v(batch_line.size());
+    if (gaussian_potential(exact_on_device(), (int64_t)v.size(), batch_x.data(), v.data(), nullptr) != GMG_OK)
+      throw std::runtime_error("exact boundary values: " + last_error);
+    for (size_t k = 0; k < v.size(); ++k) constraint_lines[(size_t)batch_line[k]].inhomogeneity = v[k];
   }
   // close(): masters that are themselves (Dirichlet) constrained fold into the inhomogeneity
   for (ConstraintLine &line : constraint_lines) {
@@ -1739,6 +1762,94 @@ int LaplaceProblem<dim>::direct_coulomb(bool on_device, std::vector<double> *for
 }
 
 template <int dim>
+int LaplaceProblem<dim>::gaussian_potential(bool on_device, int64_t n_points, const double *points, double *phi, double *grad) {
+  if (dim != 3) { last_error = "exact potential: 3D only"; return GMG_ERR_UNSUPPORTED; }
+  const int64_t n = number_of_atoms;
+  if (on_device) {
+    // (a context is enough: the call uses no level data, so it also works before the cycle's operators exist)
+    GMGC(ensure_context());
+    GMGC(gmg_gaussian_potential(gmg, n, atom_positions.data(), charges.data(), par.r_c, n_points, points, phi, grad));
+    return GMG_OK;
+  }
+  // host mirror: the same per-pair functions (gmg_exact.hpp), one point per iteration, atoms in ascending order
+  const gmg_exact::Gauss g = gmg_exact::Gauss::make(par.r_c);
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int64_t p = 0; p < n_points; ++p) {
+    double v = 0.0, ga[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = 0; i < n; ++i) {
+      double dir[3];
+      const double r = gmg_exact::distance(points + 3 * p, &atom_positions[(size_t)(3 * i)], dir);
+      if (phi) v += gmg_exact::value(g, r, charges[(size_t)i]);
+      if (grad) gmg_exact::gradient_add(g, r, charges[(size_t)i], dir, ga);
+    }
+    if (phi) phi[p] = v;
+    if (grad)
+      for (int d = 0; d < 3; ++d) grad[3 * p + d] = ga[d];
+  }
+  return GMG_OK;
+}
+
+template <int dim>
+int LaplaceProblem<dim>::energy_norm_error(bool on_device, double *error, std::vector<double> *cell_err2) {
+  if (dim != 3) { last_error = "energy norm error: 3D only"; return GMG_ERR_UNSUPPORTED; }
+  if (solution.size() != vertex_of_dof.size() || active_cells.empty()) { last_error = "energy norm error: no solution of this mesh"; return GMG_ERR_INVALID; }
+  constexpr int nv = 1 << dim;
+  const Quadrature<dim> quad((int)par.degree + 1);  // QGauss(degree + 1), :1427
+  const int nq = (int)quad.p.size();
+  const int64_t nc = (int64_t)active_cells.size(), n = number_of_atoms;
+  std::vector<double> lo((size_t)(3 * nc)), hh((size_t)nc), qp((size_t)(3 * nq)), sg((size_t)(24 * nq), 0.0), ce((size_t)nc, 0.0);
+  for (int64_t ci = 0; ci < nc; ++ci) {
+    const ActiveCell &ac = active_cells[(size_t)ci];
+    double x0[3];
+    triangulation.cell_origin(ac.level, triangulation.levels[(size_t)ac.level][(size_t)ac.index], x0);
+    for (int d = 0; d < 3; ++d) lo[(size_t)(3 * ci + d)] = x0[d];
+    hh[(size_t)ci] = triangulation.cell_size(ac.level);
+  }
+  for (int q = 0; q < nq; ++q)
+    for (int d = 0; d < 3; ++d) {
+      qp[(size_t)(3 * q + d)] = quad.p[(size_t)q][(size_t)d];
+      for (int a = 0; a < nv; ++a) sg[(size_t)(24 * q + 3 * a + d)] = quad.grad[(size_t)q][(size_t)a][(size_t)d];
+    }
+  if (on_device) {
+    GMGC(ensure_context());
+    double *d_u = nullptr;
+    GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
+    int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (rc == GMG_OK)
+      rc = gmg_energy_norm_error(gmg, nc, lo.data(), hh.data(), active_cell_dof_table.data(), d_u, (int64_t)solution.size(), n,
+                                 atom_positions.data(), charges.data(), par.r_c, nq, qp.data(), quad.w.data(), sg.data(), error,
+                                 cell_err2 ? ce.data() : nullptr);
+    if (rc != GMG_OK) last_error = std::string("gmg_energy_norm_error: ") + gmg_last_error(gmg);
+    gmg_vec_free(gmg, d_u);
+    if (rc == GMG_OK && cell_err2) cell_err2->swap(ce);
+    return rc;
+  }
+  // host mirror: one cell per iteration, its quadrature points in ascending order, then the cells in ascending order
+  const gmg_exact::Gauss g = gmg_exact::Gauss::make(par.r_c);
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t ci = 0; ci < nc; ++ci) {
+    const double h = hh[(size_t)ci];
+    double s = 0.0;
+    for (int q = 0; q < nq; ++q) {
+      double x[3], ga[3] = {0.0, 0.0, 0.0};
+      for (int d = 0; d < 3; ++d) x[d] = lo[(size_t)(3 * ci + d)] + h * qp[(size_t)(3 * q + d)];
+      for (int64_t i = 0; i < n; ++i) {
+        double dir[3];
+        const double r = gmg_exact::distance(x, &atom_positions[(size_t)(3 * i)], dir);
+        gmg_exact::gradient_add(g, r, charges[(size_t)i], dir, ga);
+      }
+      s += gmg_exact::point_err2(solution.data(), &active_cell_dof_table[(size_t)(8 * ci)], &sg[(size_t)(24 * q)], h, quad.w[(size_t)q], ga);
+    }
+    ce[(size_t)ci] = s;
+  }
+  double total = 0.0;
+  for (int64_t ci = 0; ci < nc; ++ci) total += ce[(size_t)ci];
+  if (error) *error = std::sqrt(total);
+  if (cell_err2) cell_err2->swap(ce);
+  return GMG_OK;
+}
+
+template <int dim>
 void LaplaceProblem<dim>::postprocess_forces() {
   CycleReport &rep = reports.back();
   const bool dev = forces_on_device();
@@ -1769,6 +1880,13 @@ void LaplaceProblem<dim>::postprocess_error_in_energy_norm() {
   // analytical gradient of include/step_50.h:355-369 (GaussianCharges only; the reference
   // dereferences a null exact_solution for Step16).
   if (par.Problemtype != "GaussianCharges") return;
+  if (par.analytical_on_device && dim == 3) {  // the same norm through gmg_exact.hpp: the device, or its host mirror
+    double e = 0.0;
+    if (energy_norm_error(exact_on_device(), &e, nullptr) != GMG_OK) throw std::runtime_error(last_error);
+    reports.back().energy_norm_error = e;
+    pcout("Error in FE solution in energy norm:  " + fmt("%.10e", e));
+    return;
+  }
   constexpr int nv = 1 << dim;
   const Quadrature<dim> quad((int)par.degree + 1);
   const double inv_constant = 1.0 / (std::sqrt(M_PI) * par.r_c);
@@ -1892,6 +2010,9 @@ void LaplaceProblem<dim>::finish_cycle() {
     postprocess_electrostatic_energy();     // :1554-1555
     if (number_of_atoms < 300) postprocess_error_in_energy_norm();  // :1556 (O(cells x atoms): under the reference's small-system gate only)
   }
+  // "Error norm for large systems": past that gate only through gmg_exact.hpp (the legacy host loop stays gated)
+  if (lammpsinput && number_of_atoms >= 300 && par.error_norm_for_large_systems && par.analytical_on_device && dim == 3)
+    postprocess_error_in_energy_norm();
   if (lammpsinput && dim == 3 && par.compute_forces) postprocess_forces();  // (3D atoms exist only with LAMMPS input)
 }
 

@@ -72,6 +72,9 @@ struct Parameters {
   bool energy_for_large_systems = false;
   bool compute_forces = false;        // forces on the atoms after the energy (LAMMPS input, 3D), DESIGN.md section 9
   bool direct_coulomb_check = false;  // with them the exact all-pairs Coulomb forces and the relative RMS error against them  // evaluate the energy also for >= 300 atoms (needs the cutoff; the reference skips it, :1554)
+  // the Exact boundary values in one batch and the error norm through gmg_exact.hpp (device or host
+  // mirror); with it the error norm may also be evaluated beyond the reference's 300-atom gate
+  bool analytical_on_device = false, error_norm_for_large_systems = false;
   bool rhs_on_device = true;            // gmg_rhs_assemble: F integrated on the device from densities that stay there
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
@@ -138,6 +141,14 @@ class LaplaceProblem {
   int direct_coulomb(bool on_device, std::vector<double> *force, std::vector<double> *energy);  // exact all-pairs sum
   bool forces_on_device() const { return solve_on_device_requested && gmg != nullptr; }  // where the cycle's solve ran
   void point_locator(std::vector<int32_t> &node) const;  // the forest flattened for gmg_set_point_locator
+  // The exact free-space potential of all atoms (Analytical_Solution, include/step_50.h:338-369) and / or its gradient at
+  // n_points points [3 n] (3D): through gmg_gaussian_potential, or by the host mirror of the same text (gmg_exact.hpp).
+  int gaussian_potential(bool on_device, int64_t n_points, const double *points, double *phi, double *grad);
+  // || grad phi_h - grad phi ||_L2 of the current solution and the per-cell squares [active cells] (either may be null):
+  // through gmg_energy_norm_error, or by the host mirror
+  int energy_norm_error(bool on_device, double *error, std::vector<double> *cell_err2);
+  // where "Analytical solution on device" evaluates: on the device when the cycle runs there, 3D Gaussian charges from atoms
+  bool exact_on_device() const { return solve_on_device_requested && dim == 3 && par.Problemtype == "GaussianCharges" && lammpsinput; }
   std::vector<double> total_charge_density_vector() const;               // tests_rhs_rc_variation/rc_variation.cc:110-215
   int run_cycle(unsigned int cycle, bool on_device = true);              // one iteration of the loop in run()
   void finish_cycle();                                   // estimator + energy, the tail of the loop body

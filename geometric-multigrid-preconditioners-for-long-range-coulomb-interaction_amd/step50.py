@@ -89,6 +89,8 @@ def prm_text(**kw) -> str:
         "energy_for_large_systems": ("Misc", "Energy for large systems"),
         "compute_forces": ("Misc", "Compute forces"),
         "direct_coulomb_check": ("Misc", "Direct Coulomb check"),
+        "analytical_on_device": ("Misc", "Analytical solution on device"),
+        "error_norm_for_large_systems": ("Misc", "Error norm for large systems"),
     }
     sections = {}
     for k, v in kw.items():
@@ -177,6 +179,35 @@ class Problem:
         where = -1 if on_device is None else int(bool(on_device))
         self._chk(self.L.step50_direct_coulomb_ex(self.h, C.c_int(where), P(F), P(e)), "direct_coulomb")
         return F, e
+
+    def gaussian_potential(self, points, on_device=None, grad=False, phi=True):
+        """The exact free-space potential of all atoms at the points [n, 3]: phi [n], with grad=True
+        (phi, grad [n, 3]); phi=False leaves the values out of the sums (they come back 0).  on_device None: the device when
+        the cycle runs there; False: the host mirror; True: the device."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        want_phi, phi, g = phi, np.zeros(len(pts)), np.zeros((len(pts), 3))
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        where = -1 if on_device is None else int(bool(on_device))
+        self._chk(self.L.step50_gaussian_potential(self.h, C.c_int(where), C.c_int64(len(pts)), P(pts), P(phi) if want_phi else None,
+                                                   P(g) if grad else None), "gaussian_potential")
+        return (phi, g) if grad else phi
+
+    def cell_errors(self, on_device=None, norm=False):
+        """Per active cell, the square of the error of the current solution in the energy norm, int_K |grad phi_h - grad phi|^2
+        (the true local error beside the Kelly indicator); norm=True adds the norm itself, the square root of their sum:
+        (cell_err2, error).  on_device as in gaussian_potential."""
+        self.L.step50_n_cells.restype = C.c_int64
+        ce, err = np.zeros(self.L.step50_n_cells(self.h)), C.c_double(0)
+        where = -1 if on_device is None else int(bool(on_device))
+        self._chk(self.L.step50_cell_errors(self.h, C.c_int(where), C.byref(err), ce.ctypes.data_as(C.POINTER(C.c_double))), "cell_errors")
+        return (ce, err.value) if norm else ce
+
+    def constraint_inhomogeneities(self):
+        """Per DoF, the inhomogeneity of its constraint line (Dirichlet values and what the hanging-node lines inherit; 0 for
+        unconstrained DoFs)."""
+        out = np.zeros(self.n_dofs())
+        self.L.step50_constraint_inhomogeneities(self.h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
 
     def estimator_components(self):
         """Per active cell of the cycle just estimated: (Kelly face sum eta_K^2, residual term, level, centre)."""

@@ -191,6 +191,32 @@ int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, c
 int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double *force,
                        double *energy);
 
+/* ---- exact free-space potential of the Gaussian charges ----------- */
+/* Analytical_Solution::value / ::gradient (include/step_50.h:338-369) summed over ALL atoms at n_points points at once:
+ *   phi(x)  = sum_i (r < 1e-10 ? 2 q_i / (sqrt(pi) r_c) : q_i erf(r / r_c) / r),                      r = |x - x_i|
+ *   grad(x) = sum_i q_i (2 r exp(-(r/r_c)^2) / (sqrt(pi) r_c) - erf(r / r_c)) / r^2 * (x - x_i) / r   (0 for r < 1e-10)
+ * It stands where VectorTools::interpolate_boundary_values calls the function once per boundary DoF for
+ * `Boundary conditions selection = Exact` (src/step-50.cc:661-696).  Host arrays in and out: point_xyz [3 n], phi [n] or
+ * NULL, grad [3 n] or NULL.  3D only.  Every value is one sequential sum over the atoms in ascending index (definitions:
+ * gmg_exact.hpp): deterministic, independent of the workgroup size (option force_block) and of how the points are cut into
+ * launches (option exact_chunk_log2).  GMG_ERR_INVALID for negative sizes, r_c <= 0 or a NULL input of nonzero size; zero
+ * atoms (phi = grad = 0) or zero points are valid calls.                                                              */
+int gmg_gaussian_potential(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c,
+                           int64_t n_points, const double *point_xyz, double *phi, double *grad);
+/* postprocess_error_in_energy_norm (src/step-50.cc:1423-1461): error = || grad phi_h - grad phi ||_L2 with grad phi as
+ * above, over n_cells cubes (lower corner cell_lo [3 n_cells], edge cell_h [n_cells], as gmg_charge_density takes them) with
+ * nq quadrature points each (quadrature_points [nq][3] on the unit cell, weights [nq]).  grad phi_h at a point is formed
+ * from the cell's 8 DoFs cell_dofs [8 n_cells] (vertex a = bx + 2 by + 4 bz) of the constraint-distributed solution u
+ * (device vector of n_u entries) with the unit-cell shape gradients shape_grad [nq][8][3] divided by the cell's edge.  Per
+ * cell, cell_err2 = sum_q |grad phi_h - grad phi|^2 w_q h^3 in ascending q (host array [n_cells] or NULL: the true local
+ * error beside the Kelly indicator); error (may be NULL) = sqrt of their sum, formed by the two-stage partial reduction
+ * (no atomics).  GMG_ERR_INVALID as above and for a DoF outside [0, n_u); GMG_ERR_UNSUPPORTED for nq > 64; zero cells
+ * give error = 0.                                                                                                      */
+int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_lo, const double *cell_h,
+                          const int32_t *cell_dofs, const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz,
+                          const double *atom_q, double r_c, int nq, const double *quadrature_points, const double *weights,
+                          const double *shape_grad, double *error, double *cell_err2);
+
 /* ---- distributed (one process per GPU, RCCL over xGMI) ------------------------------ */
 #define GMG_UNIQUE_ID_BYTES 128
 int gmg_comm_unique_id(void *out_id);                       /* rank 0, then broadcast by the host.  Default: an RCCL id.  With
@@ -286,7 +312,9 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * sgs_phase_profile (cycle counters of the four-wave sweep: same results, one rank only), sgs_profile (instrumented
  * one-wave sweep; its wrong-result timing modes exist only in a -DGMG_EXPERIMENTS build, tools/build_experiments.sh),
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
- * 256: workgroup size of the force kernels; the results do not depend on it).  Options that shape a device
+ * 256: workgroup size of the force kernels and of the exact-potential kernels; the results do not depend on it),
+ * exact_chunk_log2 (0 .. 35, default 35: gmg_gaussian_potential and gmg_energy_norm_error do at most 2^k point-atom
+ * evaluations per launch; tests force many launches on small inputs, the results do not depend on it).  Options that shape a device
  * layout take effect at the next gmg_set_*_matrix.  The same keys are read once from the environment
  * variable GMG_OPTIONS="key=value,..." at gmg_create (for profiling scripts around bench.py).        */
 int gmg_set_option(gmg_context *ctx, const char *key, double value);
