@@ -194,7 +194,8 @@ int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz
 /* ---- exact free-space potential of the Gaussian charges ----------- */
 /* Analytical_Solution::value / ::gradient (include/step_50.h:338-369) summed over ALL atoms at n_points points at once:
  *   phi(x)  = sum_i (r < 1e-10 ? 2 q_i / (sqrt(pi) r_c) : q_i erf(r / r_c) / r),                      r = |x - x_i|
- *   grad(x) = sum_i q_i (2 r exp(-(r/r_c)^2) / (sqrt(pi) r_c) - erf(r / r_c)) / r^2 * (x - x_i) / r   (0 for r < 1e-10)
+ *   grad(x) = sum_i q_i (2 r exp(-(r/r_c)^2) / (sqrt(pi) r_c) - erf(r / r_c)) / r^2 * (x - x_i) / r   (0 for r = 0; for
+ *             r < 0.25 r_c the factor is evaluated by its series in r / r_c, which does not cancel)
  * It stands where VectorTools::interpolate_boundary_values calls the function once per boundary DoF for
  * `Boundary conditions selection = Exact` (src/step-50.cc:661-696).  Host arrays in and out: point_xyz [3 n], phi [n] or
  * NULL, grad [3 n] or NULL.  3D only.  Every value is one sequential sum over the atoms in ascending index (definitions:
