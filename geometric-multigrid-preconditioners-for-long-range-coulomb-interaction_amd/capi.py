@@ -342,6 +342,49 @@ class Context:
                                                C.byref(err), D(ce)))
         return err.value, ce
 
+    # ---- charge densities and the right-hand side integrated from them
+    def charge_density(self, cell_lo, cell_h, root_lo, root_h, atom_xyz, atom_q, r_c, cutoff, use_lists, quadrature_points, dens=True):
+        """rho [n_cells, nq] at the points cell_lo + cell_h * quadrature_points of every cell (cutoff: a distance).
+        dens=None keeps the densities on the device for rhs_assemble / get_charge_density and returns None."""
+        lo = np.ascontiguousarray(cell_lo, dtype=np.float64).reshape(-1, 3)
+        hh = np.ascontiguousarray(cell_h, dtype=np.float64)
+        rlo = np.ascontiguousarray(root_lo, dtype=np.float64).reshape(-1, 3)
+        xyz = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(atom_q, dtype=np.float64)
+        qp = np.ascontiguousarray(quadrature_points, dtype=np.float64).reshape(-1, 3)
+        assert len(lo) == len(hh) == len(rlo) and len(xyz) == len(q)
+        out = None if dens is None else np.zeros((len(hh), len(qp)))
+        D = lambda a: _p(a, C.c_double)
+        self._chk(self.L.gmg_charge_density(self.h, C.c_int64(len(hh)), D(lo), D(hh), D(rlo), C.c_double(root_h), C.c_int64(len(q)),
+                                            D(xyz), D(q), C.c_double(r_c), C.c_double(cutoff), C.c_int(1 if use_lists else 0),
+                                            C.c_int(len(qp)), D(qp), None if out is None else D(out)))
+        return out
+
+    def get_charge_density(self, n_cells, nq):
+        """the densities charge_density(..., dens=None) left on the device: [n_cells, nq]"""
+        out = np.zeros((int(n_cells), int(nq)))
+        self._chk(self.L.gmg_get_charge_density(self.h, C.c_int64(n_cells), C.c_int(nq), _p(out, C.c_double)))
+        return out
+
+    def rhs_assemble(self, n_cells, dim, shape, weight, cell_level, jxw_of_level, term_slot, term_value, dof_ptr, entry_slot,
+                     entry_coef, coef_table, rhs):
+        """rhs (DeviceVector of len(dof_ptr) - 1 entries) from the densities kept on the device; shape [nq, 2^dim]."""
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        sh = np.ascontiguousarray(shape, dtype=np.float64).reshape(len(w), 1 << dim)
+        lv = np.ascontiguousarray(cell_level, dtype=np.uint8)
+        jxw = np.ascontiguousarray(jxw_of_level, dtype=np.float64)
+        ts = np.ascontiguousarray(term_slot, dtype=np.int32)
+        tv = np.ascontiguousarray(term_value, dtype=np.float64)
+        ptr = np.ascontiguousarray(dof_ptr, dtype=np.int64)
+        es = np.ascontiguousarray(entry_slot, dtype=np.int32)
+        ec = np.ascontiguousarray(entry_coef, dtype=np.uint8)
+        ct = np.ascontiguousarray(coef_table, dtype=np.float64)
+        assert len(jxw) == 16 and len(ct) == 256 and len(ts) == len(tv) and len(es) == len(ec) and len(ptr) >= 1
+        D = lambda a: _p(a, C.c_double)
+        self._chk(self.L.gmg_rhs_assemble(self.h, C.c_int64(n_cells), C.c_int(len(w)), C.c_int(dim), D(sh), D(w), _p(lv, C.c_uint8), D(jxw),
+                                          C.c_int64(len(ts)), _p(ts, C.c_int32), D(tv), C.c_int64(len(ptr) - 1), _p(ptr, C.c_int64),
+                                          _p(es, C.c_int32), _p(ec, C.c_uint8), D(ct), rhs.ptr))
+
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))
 

@@ -3444,6 +3444,9 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
     return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: call gmg_charge_density(..., dens = NULL) for these cells first");
   const int nv = 1 << dim;
   const int64_t n_slots = n_cells * nv, n_ent = dof_ptr[n_dofs];
+  if (dof_ptr[0] < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: dof_ptr starts below 0");
+  if ((n_ent > 0 && (!entry_slot || !entry_coef)) || (n_terms > 0 && (!term_slot || !term_value)))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: a list of nonzero length is NULL");
   if (n_slots >= ((int64_t)1 << 31) || n_ent >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_rhs_assemble: more than 2^31 slots");
   (void)hipSetDevice(ctx->device);
   double *d_F = nullptr, *d_tv = nullptr;
@@ -3460,6 +3463,8 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
     if (i && dof_ptr[i] < dof_ptr[i - 1]) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: dof_ptr not monotone");
     ptr32[(size_t)i] = (int32_t)dof_ptr[i];
   }
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: cell level above 15");
   for (int64_t e = 0; e < n_ent; ++e)
     if (entry_slot[e] < 0 || entry_slot[e] >= n_slots) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: slot out of range");
   for (int64_t t = 0; t < n_terms; ++t)

@@ -1265,9 +1265,9 @@ __global__ __launch_bounds__(kThreads) void charge_density_kernel(DensityArgs a)
   const double blo[3] = {a.bin_lo0, a.bin_lo1, a.bin_lo2};
   const int bn[3] = {a.bin_n0, a.bin_n1, a.bin_n2};
   if (a.use_lists) {
-    for (int d = 0; d < 3; ++d) {
-      b0[d] = max((int)floor((rlo[d] - a.cutoff - blo[d]) / a.bin_size), 0);
-      b1[d] = min((int)floor((rhi[d] + a.cutoff - blo[d]) / a.bin_size), bn[d] - 1);
+    for (int d = 0; d < 3; ++d) {  // clamped as doubles: a cell far from the atoms has a bin index no int holds
+      b0[d] = (int)fmin(fmax(floor((rlo[d] - a.cutoff - blo[d]) / a.bin_size), 0.0), (double)bn[d]);
+      b1[d] = (int)fmin(fmax(floor((rhi[d] + a.cutoff - blo[d]) / a.bin_size), -1.0), (double)(bn[d] - 1));
     }
   }
   for (int qb = 0; qb < a.nq; qb += 8) {

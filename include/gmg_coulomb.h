@@ -141,7 +141,15 @@ int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, i
  * rhs_assembly_optimization() (:260-306) evaluated on the fly: for every cell, rho at its nq
  * quadrature points, summed over the atoms closer than `cutoff` to any vertex of the cell's
  * ROOT cell (use_lists != 0; children inherit the parent's list, :441-450) or over all atoms.
- * Host arrays in, host array out (dens[n_cells * nq], incl. the factor 4 pi of :522).       */
+ * Host arrays in, host array out (dens[n_cells * nq], incl. the factor 4 pi of :522).
+ *   rho(x) = 4 pi / (r_c^3 pi^1.5) * sum_k q_k exp(-|x - x_k|^2 / r_c^2)
+ *   x      = cell_lo + cell_h * quadrature_points[q] per coordinate, as fp64 evaluates it (quadrature_points: [nq][3] on the
+ *            unit cell); cell_lo, root_lo: [3 n_cells], cell_h: [n_cells]; a child's root_lo is its root cell's corner
+ *   list   : atom k counts for a cell when its distance to the nearest of the 8 vertices root_lo + {0, root_h}^3 is below
+ *            `cutoff` -- a distance, not a multiple of r_c; an atom at exactly `cutoff` does not count.  In fp64: per
+ *            direction the nearer of root_lo and root_lo + root_h (the lower one on a tie), sqrt(mx^2 + my^2 + mz^2) < cutoff
+ * The order in which a point's atoms are summed is not specified (a wavefront shares them).  A point with no atom on its
+ * list, or n_atoms = 0, gives exactly +0.0.                                                                           */
 /* dens == NULL keeps the densities on the device for gmg_rhs_assemble (gmg_get_charge_density copies them out on demand).   */
 int gmg_charge_density(gmg_context *ctx, int64_t n_cells, const double *cell_lo, const double *cell_h,
                        const double *root_lo, double root_h, int64_t n_atoms, const double *atom_xyz,
@@ -156,7 +164,15 @@ int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *de
  *   per DoF d  rhs[d] = sum over e in [dof_ptr[d], dof_ptr[d+1]) of (entry_coef[e] == 0 ? F[slot] : coef_table[code] * F[slot])
  * with slot = cell * 2^dim + vertex, the entries of a DoF in the order the reference's cell loop adds them
  * (distribute_local_to_global: hanging-node rows contribute to their masters with the constraint weight).  Every output
- * value is one sequential sum: deterministic, no atomics.  shape: [nq][2^dim]; cell_level: [n_cells]; rhs: device vector.  */
+ * value is one sequential sum: deterministic, no atomics.  shape: [nq][2^dim]; cell_level: [n_cells]; rhs: device vector.
+ * The arithmetic, exactly (fp64, no contraction into fused multiply-adds), so that a restatement gives the same bits:
+ *   F_i starts at +0.0 and adds ((shape[q][i] * rho_q) * weight[q]) * jxw_of_level[cell_level[cell]] for q = 0 .. nq - 1;
+ *   then F[term_slot[t]] = F[term_slot[t]] - term_value[t] for t = 0 .. n_terms - 1;
+ *   rhs[d] starts at +0.0 and adds, e ascending, F[entry_slot[e]] (entry_coef[e] == 0) or coef_table[entry_coef[e]] *
+ *   F[entry_slot[e]] (codes 1 .. 255); a DoF without entries gets +0.0.
+ * 1 <= nq <= 512, dim 2 or 3, cell_level < 16.  GMG_ERR_INVALID -- found on the host, before anything is launched -- for
+ * other values, without densities of n_cells x nq on the device, for a slot outside [0, n_cells 2^dim), term slots that do
+ * not ascend, a dof_ptr that starts below 0 or decreases, or a NULL list of nonzero length.                              */
 int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const double *shape, const double *weight,
                      const uint8_t *cell_level, const double *jxw_of_level /* [16] */, int64_t n_terms, const int32_t *term_slot,
                      const double *term_value, int64_t n_dofs, const int64_t *dof_ptr, const int32_t *entry_slot,

@@ -509,6 +509,13 @@ static void precond_jacobi(void *ctx, double *dst, const double *src) { /* :996-
   for (int64_t i = 0; i < mg->S.n_rows; ++i) dst[i] = (0.6 * src[i]) * mg->S_invdiag[i];
 }
 
+/* one application of the Jacobi preconditioner of the outer solve, on its own (tests) */
+int oracle_precondition_jacobi(oracle_mg *mg, double *dst, const double *src) {
+  if (!mg->has_S) return ORACLE_ERR_ARG;
+  precond_jacobi(mg, dst, src);
+  return ORACLE_OK;
+}
+
 /* The outer solve of LaplaceProblem::solve(): tol = rel_tol * |b|_2 (:942), max 500. */
 int oracle_solve(oracle_mg *mg, double *x, const double *b, double rel_tol, int max_it, int precond_kind, int *iters,
                  double *res0, double *res, int64_t *coarse_iters) {

@@ -122,6 +122,14 @@ class OracleMG:
         rc = lib().oracle_vcycle(self.h, _p(dst, C.c_double), _p(src, C.c_double))
         return dst, rc
 
+    def precondition_jacobi(self, src):
+        """PreconditionJacobi(0.6).vmult on the system matrix, as the outer solve applies it"""
+        src = np.ascontiguousarray(src, dtype=np.float64)
+        dst = np.zeros(self.n)
+        rc = lib().oracle_precondition_jacobi(self.h, _p(dst, C.c_double), _p(src, C.c_double))
+        assert rc == OK
+        return dst
+
     def solve(self, b, x0=None, rel_tol=1e-8, max_it=500, precond=PRECOND_GMG):
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.zeros(self.n) if x0 is None else np.array(x0, dtype=np.float64)
