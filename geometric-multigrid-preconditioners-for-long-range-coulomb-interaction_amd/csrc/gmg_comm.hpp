@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "gmg_device.hpp"
+#include "gmg_mem.hpp"
 
 namespace gmg {
 
@@ -67,12 +68,13 @@ struct Comm {
   bool peer = false;
   PeerBoot *boot = nullptr;
   char boot_name[96] = {};
-  char *box[kPeerMaxRanks] = {};  // device: my mailbox (box[rank]) and the peers' (IPC-mapped)
+  char *box[kPeerMaxRanks] = {};  // device: my mailbox (box[rank]) and the peers' (IPC-mapped).  Not an owner (gmg_mem.hpp): the peers map
+                                  // it, so it is unmapped and freed at one collective point, comm_destroy
   int64_t cap = 0;                // bytes per (parity, source)
   unsigned long long seq = 0;     // collective rounds so far (the same on every rank: collectives are called in the same order)
   unsigned long long last_sent[kPeerMaxRanks][2] = {};  // round of my last message to a peer, per parity
-  unsigned int *cnt = nullptr;    // device: workgroups done, per peer (last one publishes)
-  int *abort_host = nullptr;      // pinned: set by a kernel that gave up waiting
+  DevPtr<unsigned int> cnt;       // device: workgroups done, per peer (last one publishes)
+  HostPtr<int> abort_host;        // pinned: set by a kernel that gave up waiting
   bool box_fine = false;          // my mailbox is fine-grained memory
   int ring_fine = -1;             // the shared direction ring: -1 not allocated, 0 plain hipMalloc, 1 fine-grained
   int n_devices = 1;              // distinct GPUs under the ranks
@@ -113,15 +115,9 @@ struct HaloPlan {
   int n_neighbors = 0;
   std::vector<int> rank, send_count, recv_count;
   int64_t total_send = 0, total_recv = 0;
-  int32_t *send_idx = nullptr;  // device: owned local rows to pack, neighbour after neighbour
-  double *send_buf = nullptr;   // device
+  DevPtr<int32_t> send_idx;  // device: owned local rows to pack, neighbour after neighbour
+  DevPtr<double> send_buf;   // device
 };
-
-inline void free_halo(HaloPlan &h) {
-  if (h.send_idx) (void)hipFree(h.send_idx);
-  if (h.send_buf) (void)hipFree(h.send_buf);
-  h = HaloPlan();
-}
 
 inline int build_halo(HaloPlan &h, int n_neighbors, const int32_t *neighbor_rank, const int32_t *send_count,
                       const int32_t *send_idx, const int32_t *recv_count, hipStream_t stream) {
@@ -136,9 +132,9 @@ inline int build_halo(HaloPlan &h, int n_neighbors, const int32_t *neighbor_rank
     h.total_recv += recv_count[i];
   }
   if (h.total_send > 0) {
-    if (hipMalloc(&h.send_idx, sizeof(int32_t) * (size_t)h.total_send) != hipSuccess) return 1;
-    if (hipMalloc(&h.send_buf, sizeof(double) * (size_t)h.total_send) != hipSuccess) return 1;
-    if (hipMemcpyAsync(h.send_idx, send_idx, sizeof(int32_t) * (size_t)h.total_send, hipMemcpyHostToDevice, stream) != hipSuccess)
+    if (h.send_idx.alloc((size_t)h.total_send) != hipSuccess) return 1;
+    if (h.send_buf.alloc((size_t)h.total_send) != hipSuccess) return 1;
+    if (hipMemcpyAsync(h.send_idx.get(), send_idx, sizeof(int32_t) * (size_t)h.total_send, hipMemcpyHostToDevice, stream) != hipSuccess)
       return 1;
     if (hipStreamSynchronize(stream) != hipSuccess) return 1;
   }
@@ -198,10 +194,10 @@ inline int comm_init(Comm &c, int rank, int n_ranks, const void *id_bytes) {
       c.boot->fine[rank] = c.box_fine ? 1 : 0;
     }
     if (hipMemset(c.box[rank], 0, (size_t)kPeerFlagBytes) != hipSuccess) return 1;
-    if (hipMalloc((void **)&c.cnt, sizeof(unsigned int) * 2 * kPeerMaxRanks) != hipSuccess) return 1;
-    if (hipMemset(c.cnt, 0, sizeof(unsigned int) * 2 * kPeerMaxRanks) != hipSuccess) return 1;
-    if (hipHostMalloc((void **)&c.abort_host, sizeof(int), hipHostMallocDefault) != hipSuccess) return 1;
-    *c.abort_host = 0;
+    if (c.cnt.alloc(2 * kPeerMaxRanks) != hipSuccess) return 1;
+    if (hipMemset(c.cnt.get(), 0, sizeof(unsigned int) * 2 * kPeerMaxRanks) != hipSuccess) return 1;
+    if (c.abort_host.alloc(1) != hipSuccess) return 1;
+    *c.abort_host.get() = 0;
     if (hipDeviceSynchronize() != hipSuccess) return 1;
     if (hipIpcGetMemHandle(&c.boot->handle[rank], c.box[rank]) != hipSuccess) return 1;
     if (boot_barrier(c.boot, n_ranks)) return 1;
@@ -246,8 +242,6 @@ inline void comm_destroy(Comm &c) {
       if (r != c.rank && c.box[r]) (void)hipIpcCloseMemHandle(c.box[r]);
     (void)boot_barrier(c.boot, c.n_ranks);
     if (c.box[c.rank]) (void)hipFree(c.box[c.rank]);
-    if (c.cnt) (void)hipFree(c.cnt);
-    if (c.abort_host) (void)hipHostFree(c.abort_host);
     if (c.rank == 0) (void)shm_unlink(c.boot_name);
     (void)munmap(c.boot, sizeof(PeerBoot));
   } else if (c.ready && c.comm) {
@@ -401,7 +395,7 @@ inline int peer_exchange(Comm &c, const std::vector<PeerMsg> &msgs, hipStream_t 
     }
   }
   s.me = r.me = c.rank; s.n_ranks = r.n_ranks = c.n_ranks; s.seq = r.seq = seq; s.cap = r.cap = c.cap;
-  s.my_box = r.my_box = c.box[c.rank]; s.cnt = r.cnt = c.cnt; s.abort_flag = r.abort_flag = c.abort_host;
+  s.my_box = r.my_box = c.box[c.rank]; s.cnt = r.cnt = c.cnt.get(); s.abort_flag = r.abort_flag = c.abort_host.get();
   if (s.n) hipLaunchKernelGGL(peer_send_kernel, dim3(max_send_grid, s.n), dim3(kThreads), 0, stream, s);
   if (r.n && unpack) hipLaunchKernelGGL(peer_recv_kernel, dim3(max_recv_grid, r.n), dim3(kThreads), 0, stream, r);
   return hipGetLastError() != hipSuccess;
@@ -415,7 +409,7 @@ inline int peer_allreduce(Comm &c, double *dev, int count, bool max_op, hipStrea
   if (peer_exchange(c, msgs, stream, false)) return 1;  // sends only; the reduce kernel below receives
   PeerRecvArgs r{};
   for (const PeerMsg &m : msgs) { const int i = r.n++; r.peer_box[i] = c.box[m.peer]; r.src_rank[i] = m.peer; }
-  r.me = c.rank; r.n_ranks = c.n_ranks; r.seq = c.seq; r.cap = c.cap; r.my_box = c.box[c.rank]; r.cnt = c.cnt; r.abort_flag = c.abort_host;
+  r.me = c.rank; r.n_ranks = c.n_ranks; r.seq = c.seq; r.cap = c.cap; r.my_box = c.box[c.rank]; r.cnt = c.cnt.get(); r.abort_flag = c.abort_host.get();
   // the peers' copies of MY value leave from dev before the reduce kernel overwrites it: same stream, in order
   hipLaunchKernelGGL(peer_allreduce_kernel, dim3(1), dim3(kThreads), 0, stream, r, dev, count, max_op ? 1 : 0);
   return hipGetLastError() != hipSuccess;
@@ -430,14 +424,14 @@ inline int halo_exchange(Comm &c, const HaloPlan &h, double *x, int64_t n_owned,
   if (h.total_send > 0) {
     int64_t g = (h.total_send + kThreads - 1) / kThreads;
     if (g > kMaxPartials) g = kMaxPartials;
-    hipLaunchKernelGGL(gather_scatter_kernel, dim3((unsigned)g), dim3(kThreads), 0, stream, h.send_buf, (const int32_t *)nullptr,
-                       (const double *)x, (const int32_t *)h.send_idx, h.total_send);
+    hipLaunchKernelGGL(gather_scatter_kernel, dim3((unsigned)g), dim3(kThreads), 0, stream, h.send_buf.get(), (const int32_t *)nullptr,
+                       (const double *)x, (const int32_t *)h.send_idx.get(), h.total_send);
   }
   if (c.peer) {  // (a rank without neighbours still takes part in the round: the round numbers stay in step)
     std::vector<PeerMsg> msgs;
     int64_t so = 0, ro = 0;
     for (int i = 0; i < h.n_neighbors; ++i) {
-      msgs.push_back(PeerMsg{h.rank[(size_t)i], h.send_buf + so, x + n_owned + ro, h.send_count[(size_t)i], h.recv_count[(size_t)i]});
+      msgs.push_back(PeerMsg{h.rank[(size_t)i], h.send_buf.get() + so, x + n_owned + ro, h.send_count[(size_t)i], h.recv_count[(size_t)i]});
       so += h.send_count[(size_t)i];
       ro += h.recv_count[(size_t)i];
     }
@@ -448,7 +442,7 @@ inline int halo_exchange(Comm &c, const HaloPlan &h, double *x, int64_t n_owned,
   bool failed = false;
   for (int i = 0; i < h.n_neighbors && !failed; ++i) {
     if (h.send_count[(size_t)i] > 0)
-      failed = ncclSend(h.send_buf + so, (size_t)h.send_count[(size_t)i], ncclDouble, h.rank[(size_t)i], c.comm, stream) != ncclSuccess;
+      failed = ncclSend(h.send_buf.get() + so, (size_t)h.send_count[(size_t)i], ncclDouble, h.rank[(size_t)i], c.comm, stream) != ncclSuccess;
     if (!failed && h.recv_count[(size_t)i] > 0)
       failed = ncclRecv(x + n_owned + ro, (size_t)h.recv_count[(size_t)i], ncclDouble, h.rank[(size_t)i], c.comm, stream) != ncclSuccess;
     so += h.send_count[(size_t)i];
@@ -483,6 +477,7 @@ inline int allgather_chunks(Comm &c, double *full, int64_t chunk, hipStream_t st
 
 // Collective: every rank allocates `bytes` of device memory and maps everybody else's allocation (the coarse CG keeps
 // its direction vectors there: the neighbours write their halo entries straight into them).  local[rank] is the own one.
+// Like the mailbox these stay raw pointers, freed by hand: comm_share_free is collective and must run on every rank at the same point.
 inline int comm_share_alloc(Comm &c, size_t bytes, char *ptrs[kPeerMaxRanks]) {
   if (!c.peer) return 1;
   for (int r = 0; r < kPeerMaxRanks; ++r) ptrs[r] = nullptr;
@@ -531,6 +526,6 @@ inline int comm_host_barrier(Comm &c) {
   return boot_barrier(c.boot, c.n_ranks);
 }
 
-inline bool comm_aborted(const Comm &c) { return c.peer && c.abort_host && *c.abort_host != 0; }
+inline bool comm_aborted(const Comm &c) { return c.peer && c.abort_host.get() && *c.abort_host.get() != 0; }
 
 }  // namespace gmg

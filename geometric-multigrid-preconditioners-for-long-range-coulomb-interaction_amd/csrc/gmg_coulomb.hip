@@ -19,6 +19,7 @@
 #include "gmg_transfer.hpp"
 #include "gmg_forces.hpp"
 #include "gmg_exact.hpp"
+#include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -43,27 +44,27 @@ namespace {
 
 struct DevCSR {
   int64_t n_rows = 0, n_cols = 0, nnz = 0;
-  int32_t *rowptr = nullptr, *col = nullptr;
-  double *val = nullptr;
-  int32_t *tile_row = nullptr;
+  DevPtr<int32_t> rowptr, col;
+  DevPtr<double> val;
+  DevPtr<int32_t> tile_row;
   int n_tiles = 0, tiles_per_xcd = 0, grid = 0;
   bool valid = false;
   HaloPlan halo;
   // SELL-64 copy (regular-width operators only), see gmg_device.hpp
   bool sell = false;
-  int32_t *slice_ptr = nullptr;  // in quads
-  int32_t *slice_base = nullptr; // COL16: smallest column per slice
-  void *sell_vals = nullptr;     // uchar4 codes (VAL8) or double2 pairs
-  void *sell_cols = nullptr;     // ushort4 offsets (COL16) or int4 columns
-  double *sell_dict = nullptr;   // VAL8: 256 doubles
-  int32_t *sell_spat = nullptr, *sell_pat = nullptr;  // column-pattern ids per slice / pattern table
+  DevPtr<int32_t> slice_ptr;   // in quads
+  DevPtr<int32_t> slice_base;  // COL16: smallest column per slice
+  DevPtr<void> sell_vals;      // uchar4 codes (VAL8) or double2 pairs
+  DevPtr<void> sell_cols;      // ushort4 offsets (COL16) or int4 columns
+  DevPtr<double> sell_dict;    // VAL8: 256 doubles
+  DevPtr<int32_t> sell_spat, sell_pat;  // column-pattern ids per slice / pattern table
   int sellp_pid = -1, sellp_centre[9] = {};  // the nine-runs-of-three pattern served by spmv_sellp_kernel
-  int32_t *sellp_wave_ptr = nullptr;          // slice range of every wave of spmv_sellp_kernel
-  int4 *sellp_wave_rr = nullptr;              // strided fast waves: {first slice, stride, pairs, one more slice or -1}
+  DevPtr<int32_t> sellp_wave_ptr;             // slice range of every wave of spmv_sellp_kernel
+  DevPtr<int4> sellp_wave_rr;                 // strided fast waves: {first slice, stride, pairs, one more slice or -1}
   bool use_sellp = false;
   bool rowclass = false;  // run-pattern slices take their coefficients from a per-row class table (N4)
-  uint8_t *sellp_rowcls = nullptr;
-  double *sellp_ctab = nullptr;
+  DevPtr<uint8_t> sellp_rowcls;
+  DevPtr<double> sellp_ctab;
   int n_classes = 0;
   int n_patterns = 0, n_pattern_slices = 0;
   bool val8 = false, col16 = false;
@@ -71,9 +72,9 @@ struct DevCSR {
   int64_t sell_quads = 0;
   // lattice interior walked plane by plane (gmg_lattice.hpp): rows [lat_R0, lat_R1) by class table, the other slices from the SELL streams
   bool lattice = false;
-  uint8_t *lat_rowcls = nullptr;
-  double *lat_ctab = nullptr;
-  int32_t *lat_gen = nullptr;
+  DevPtr<uint8_t> lat_rowcls;
+  DevPtr<double> lat_ctab;
+  DevPtr<int32_t> lat_gen;
   bool lat_only = false;       // made by gmg_set_level_matrix_lattice: class table + row classes, no CSR / SELL copy
   int lat_W = 0;               // rows of the window that repeats with the plane stride (== lat_nxy: one contiguous interior)
   int64_t lat_fast_rows = 0;
@@ -83,29 +84,29 @@ struct DevCSR {
 
 struct SgsPlan {
   // generic level-scheduled sweep straight from the CSR copy (fallback: rows with unsorted columns)
-  int32_t *stage_ptr = nullptr, *stage_rows = nullptr, *block_row = nullptr, *block_stage = nullptr;
+  DevPtr<int32_t> stage_ptr, stage_rows, block_row, block_stage;
   int n_blocks = 0;
   int n_stages_max = 0;
   // wavefront sweep with y in LDS (gmg_sgs.hpp)
   bool wave = false;
-  SwRange *w_ranges = nullptr;
-  int32_t *w_block_rng = nullptr, *w_ws_ci = nullptr, *w_ci_row = nullptr, *w_row_ci = nullptr, *w_rpos_f = nullptr, *w_rpos_b = nullptr;
-  char *w_stream = nullptr;
-  double *w_ycur = nullptr, *w_iso_diag = nullptr, *w_iso_invd = nullptr;
+  DevPtr<SwRange> w_ranges;
+  DevPtr<int32_t> w_block_rng, w_ws_ci, w_ci_row, w_row_ci, w_rpos_f, w_rpos_b;
+  DevPtr<char> w_stream;
+  DevPtr<double> w_ycur, w_iso_diag, w_iso_invd;
   int w_y_slots = 0, w_lds_bytes = 0, w_n_ranges = 0;
   int64_t w_n_coupled = 0, w_stream_bytes = 0, w_steps = 0, w_stages = 0;
   std::vector<int32_t> host_block_row;  // n_blocks + 1 (several ranks: who sweeps which rows)
   std::vector<int64_t> host_block_steps;  // n_blocks: sub-steps of each block's chain (both directions; gmg_get_ssor_partition)
   std::vector<int64_t> host_block_bytes;  // n_blocks: record-stream bytes of each block (plan log)
   std::vector<int32_t> host_block_rng;    // n_blocks + 1: ranges of each block (sgs_phase_profile: cycles per block)
-  double *w_stage = nullptr;            // staging of the all-gather of the swept pieces
+  DevPtr<double> w_stage;               // staging of the all-gather of the swept pieces
   int64_t w_stage_len = 0;
   // four-wave variant (gmg_sgs_phase.hpp): same lists, its own ranges and record stream
   bool phased = false;
   bool dep = false;  // records laid out for gmg_sgs_dep.hpp (field-major, late = updated within the last three steps)
   bool reg = false;  // records laid out for gmg_sgs_reg.hpp (field-major, loaded straight into registers; no staging regions in LDS)
-  PhRange *p_ranges = nullptr;
-  uint4 *p_blk_tab = nullptr;
+  DevPtr<PhRange> p_ranges;
+  DevPtr<uint4> p_blk_tab;
   std::vector<PhRange> host_pranges;
 };
 
@@ -115,12 +116,14 @@ struct Level {
   int64_t n = 0;       // owned rows
   int64_t n_vec = 0;   // owned + ghost entries of a level vector
   int64_t n_copy = 0;
-  int32_t *copy_g = nullptr, *copy_l = nullptr;
-  double *sol = nullptr, *def = nullptr, *t = nullptr, *w1 = nullptr, *w2 = nullptr, *w3 = nullptr;
+  DevPtr<int32_t> copy_g, copy_l;
+  DevPtr<double> sol, def, t, w1, w2, w3;
   // distributed runs keep levels >= 1 replicated and level 0 row-partitioned: the V-cycle sees
-  // level 0 through these full-length replicas (aliases of sol/def on a single GPU)
+  // level 0 through these full-length replicas: views of sol/def on a single GPU, of the two owners below when
+  // level 0 is partitioned (the only case in which those are allocated)
   double *sol_full = nullptr, *def_full = nullptr;
-  double *invd = nullptr;
+  DevPtr<double> sol_full_own, def_full_own;
+  DevPtr<double> invd;
   double cheb_lmax = 0.0;
   SgsPlan sgs;
 };
@@ -133,8 +136,8 @@ struct gmg_context {
   int n_levels = 0;
   std::vector<Level> lv;
   DevCSR S;
-  double *S_invd = nullptr;
-  double *S_tmp = nullptr;  // system-sized scratch with ghost tail (halo import of src)
+  DevPtr<double> S_invd;
+  DevPtr<double> S_tmp;  // system-sized scratch with ghost tail (halo import of src)
   // smoother / coarse parameters (src/step-50.cc:962, 970-973)
   int smoother = GMG_SMOOTHER_SSOR;
   double omega = 0.5;
@@ -145,23 +148,27 @@ struct gmg_context {
   int coarse_maxit = 1000;
   // coarse CG work space (level-0 sized)
   int64_t cg_n = 0;
-  double *cg_g = nullptr, *cg_d0 = nullptr, *cg_d1 = nullptr, *cg_h = nullptr;
-  double *cg_ring[kXRing] = {};  // direction vectors of the last kXRing iterations (three-kernel coarse CG), allocated on first use
+  DevPtr<double> cg_g, cg_d0, cg_d1, cg_h;
+  // direction vectors of the last kXRing iterations (three-kernel coarse CG), allocated on first use: views of cg_ring_own, or
+  // of ring_shared on the peer transport.  ring_shared is mapped by every rank and freed collectively (free_cg_ring): it stays
+  // manual, like Comm::box and what comm_share_alloc returns
+  double *cg_ring[kXRing] = {};
+  DevPtr<double> cg_ring_own[kXRing];
   int64_t cg_ring_len = 0;
   // peer transport, partitioned level 0: the ring is one shared allocation the neighbours write their halo entries into
   char *ring_shared[kPeerMaxRanks] = {};
   int64_t ring_stride = 0;                      // doubles between my ring slots
   int64_t peer_meta[kPeerMaxRanks][4 + kPeerMaxRanks] = {};  // per rank: ring stride, owned rows, ghost offset of every source
   unsigned long long peer_tag0 = 1;             // tags of the next coarse solve start here
-  unsigned int *peer_push_cnt = nullptr;
-  CGState *st = nullptr;       // device
-  CGState *st_host = nullptr;  // pinned, 2 slots (the chunk being checked / the speculative one)
+  DevPtr<unsigned int> peer_push_cnt;
+  DevPtr<CGState> st;        // device
+  HostPtr<CGState> st_host;  // pinned, 2 slots (the chunk being checked / the speculative one)
   CGState st_final{};
-  hipEvent_t ev_chunk[2] = {nullptr, nullptr};
-  double *part_a = nullptr, *part_b = nullptr;  // reduction partials (4 * kMaxPartials each)
-  double *scal_dev = nullptr;                   // 8 doubles
-  double *scal_host = nullptr;                  // pinned, 8 doubles
-  int *sgs_abort = nullptr;                     // pinned, device-visible: set by the SSOR sweep if its wave protocol broke
+  Event ev_chunk[2];
+  DevPtr<double> part_a, part_b;  // reduction partials (4 * kMaxPartials each)
+  DevPtr<double> scal_dev;        // 8 doubles
+  HostPtr<double> scal_host;      // pinned, 8 doubles
+  HostPtr<int> sgs_abort;         // pinned, device-visible: set by the SSOR sweep if its wave protocol broke
   // tuning / measurement
   int coarse_chunk = 0;
   // diagnostic options (gmg_set_option / GMG_OPTIONS); the defaults are the fast paths
@@ -187,27 +194,27 @@ struct gmg_context {
   int cg_variant = 0;  // 0 auto, 1 fused 2-kernel iteration, 2 unfused 3-kernel iteration
   int last_coarse_iters = 0;
   int prof_every = 0;
-  std::vector<hipEvent_t> ev_a, ev_b;  // sampled level-0 SpMV launches
-  std::vector<hipEvent_t> ev_c, ev_d;  // sampled update-kernel launches
-  std::vector<hipEvent_t> ev_e, ev_f;  // SSOR sweep launches
+  std::vector<Event> ev_a, ev_b;  // sampled level-0 SpMV launches
+  std::vector<Event> ev_c, ev_d;  // sampled update-kernel launches
+  std::vector<Event> ev_e, ev_f;  // SSOR sweep launches
   bool launch_refused = false;  // launch_op met an operator / mode combination it has no kernel for (reported by launch_status)
   int ev_used = 0, ev2_used = 0, ev3_used = 0;
   long long sgs_launch_no = 0;
   hipEvent_t timed_start = nullptr, timed_stop = nullptr;  // next launch carries these as its dispatch start / stop events
   gmg_stats stats{};
-  double *dens_dev = nullptr;  // charge densities kept on the device (gmg_charge_density with dens == NULL): [cells][nq]
+  DevPtr<double> dens_dev;  // charge densities kept on the device (gmg_charge_density with dens == NULL): [cells][nq]
   int64_t dens_cells = 0;
   int dens_nq = 0;
   // point location for the atom forces (gmg_set_point_locator; kept until gmg_reset)
   gmg_forces::Locator loc{};
-  int32_t *loc_node = nullptr, *loc_dofs = nullptr;
+  DevPtr<int32_t> loc_node, loc_dofs;
   int64_t loc_max_dof = -1;  // -1: no locator set
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
   int64_t sys_global = 0, l0_global = 0;  // l0_global == 0 on a communicator: level 0 is replicated, only the outer CG is partitioned
-  double *sys_full_a = nullptr, *sys_full_b = nullptr;  // replicated src / dst of the V-cycle
+  DevPtr<double> sys_full_a, sys_full_b;  // replicated src / dst of the V-cycle
   std::string err;
 };
 
@@ -272,28 +279,11 @@ inline int grid_for(int64_t n) {
   return (int)g;
 }
 
-void free_csr(DevCSR &m) {
-  if (m.rowptr) (void)hipFree(m.rowptr);
-  if (m.col) (void)hipFree(m.col);
-  if (m.val) (void)hipFree(m.val);
-  if (m.tile_row) (void)hipFree(m.tile_row);
-  if (m.slice_ptr) (void)hipFree(m.slice_ptr);
-  if (m.sellp_wave_ptr) (void)hipFree(m.sellp_wave_ptr);
-  if (m.sellp_wave_rr) (void)hipFree(m.sellp_wave_rr);
-  if (m.sellp_rowcls) (void)hipFree(m.sellp_rowcls);
-  if (m.sellp_ctab) (void)hipFree(m.sellp_ctab);
-  if (m.lat_rowcls) (void)hipFree(m.lat_rowcls);
-  if (m.lat_ctab) (void)hipFree(m.lat_ctab);
-  if (m.lat_gen) (void)hipFree(m.lat_gen);
-  if (m.slice_base) (void)hipFree(m.slice_base);
-  if (m.sell_vals) (void)hipFree(m.sell_vals);
-  if (m.sell_cols) (void)hipFree(m.sell_cols);
-  if (m.sell_dict) (void)hipFree(m.sell_dict);
-  if (m.sell_spat) (void)hipFree(m.sell_spat);
-  if (m.sell_pat) (void)hipFree(m.sell_pat);
-
-  free_halo(m.halo);
+// a fresh operator that keeps its halo plan (set before the matrix, once per operator)
+void reset_keep_halo(DevCSR &m) {
+  HaloPlan keep = std::move(m.halo);
   m = DevCSR();
+  m.halo = std::move(keep);
 }
 
 // Host CSR -> device CSR + LDS-window tiling.
@@ -345,10 +335,7 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
   const int64_t nnz = rowptr[n_rows];
   if (nnz >= (int64_t)1 << 31 || n_rows >= (int64_t)1 << 31 || n_cols >= (int64_t)1 << 31)
     return fail(ctx, GMG_ERR_UNSUPPORTED, "operator needs 64-bit device indices (nnz >= 2^31)");
-  HaloPlan keep = m.halo;
-  m.halo = HaloPlan();
-  free_csr(m);
-  m.halo = keep;
+  reset_keep_halo(m);
   m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
   const bool dbg_upload = ctx->debug_upload;
   auto t_phase = std::chrono::steady_clock::now();
@@ -384,18 +371,18 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
   int per_xcd = std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
   m.grid = 8 * per_xcd;
   const size_t pad = 8;
-  HIPC(hipMalloc(&m.rowptr, sizeof(int32_t) * ((size_t)n_rows + 1)));
-  HIPC(hipMalloc(&m.col, sizeof(int32_t) * ((size_t)nnz + pad)));
-  HIPC(hipMalloc(&m.val, sizeof(double) * ((size_t)nnz + pad)));
-  HIPC(hipMalloc(&m.tile_row, sizeof(int32_t) * tiles.size()));
-  HIPC(hipMemsetAsync(m.col + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
-  HIPC(hipMemsetAsync(m.val + nnz, 0, sizeof(double) * pad, ctx->stream));
-  HIPC(hipMemcpyAsync(m.rowptr, rp.data(), sizeof(int32_t) * rp.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(m.rowptr.alloc(((size_t)n_rows + 1)));
+  HIPC(m.col.alloc(((size_t)nnz + pad)));
+  HIPC(m.val.alloc(((size_t)nnz + pad)));
+  HIPC(m.tile_row.alloc(tiles.size()));
+  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
+  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
+  HIPC(hipMemcpyAsync(m.rowptr.get(), rp.data(), sizeof(int32_t) * rp.size(), hipMemcpyHostToDevice, ctx->stream));
   if (nnz) {
-    HIPC(hipMemcpyAsync(m.col, col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipMemcpyAsync(m.val, val, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(m.col.get(), col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(m.val.get(), val, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
   }
-  HIPC(hipMemcpyAsync(m.tile_row, tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.tile_row.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));  // host staging buffers die here
   m.valid = true;
   phase("csr copy");
@@ -566,27 +553,27 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
       }
       });
       dict.resize(256, 0.0);
-      HIPC(hipMalloc(&m.slice_ptr, sizeof(int32_t) * sp.size()));
-      HIPC(hipMalloc(&m.slice_base, sizeof(int32_t) * sbase.size()));
-      HIPC(hipMalloc(&m.sell_dict, sizeof(double) * 256));
+      HIPC(m.slice_ptr.alloc(sp.size()));
+      HIPC(m.slice_base.alloc(sbase.size()));
+      HIPC(m.sell_dict.alloc(256));
       const size_t vbytes = val8 ? v1.size() : v2.size() * 8, cbytes = col16 ? c2.size() * 2 : c4.size() * 4;
-      HIPC(hipMalloc(&m.sell_vals, vbytes + 64));
-      HIPC(hipMalloc(&m.sell_cols, cbytes + 64));
-      HIPC(hipMemcpyAsync(m.slice_ptr, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.slice_base, sbase.data(), sizeof(int32_t) * sbase.size(), hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_dict, dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_vals, val8 ? (const void *)v1.data() : (const void *)v2.data(), vbytes, hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_cols, col16 ? (const void *)c2.data() : (const void *)c4.data(), cbytes, hipMemcpyHostToDevice, ctx->stream));
+      HIPC(m.sell_vals.alloc_bytes(vbytes + 64));
+      HIPC(m.sell_cols.alloc_bytes(cbytes + 64));
+      HIPC(hipMemcpyAsync(m.slice_ptr.get(), sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
+      HIPC(hipMemcpyAsync(m.slice_base.get(), sbase.data(), sizeof(int32_t) * sbase.size(), hipMemcpyHostToDevice, ctx->stream));
+      HIPC(hipMemcpyAsync(m.sell_dict.get(), dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, ctx->stream));
+      HIPC(hipMemcpyAsync(m.sell_vals.get(), val8 ? (const void *)v1.data() : (const void *)v2.data(), vbytes, hipMemcpyHostToDevice, ctx->stream));
+      HIPC(hipMemcpyAsync(m.sell_cols.get(), col16 ? (const void *)c2.data() : (const void *)c4.data(), cbytes, hipMemcpyHostToDevice, ctx->stream));
       HIPC(hipStreamSynchronize(ctx->stream));
       m.val8 = val8; m.col16 = col16;
       if (n_pattern_slices > 0) {
         std::vector<int32_t> table(patterns.size() * 32, 0);
         for (size_t pi = 0; pi < patterns.size(); ++pi)
           for (size_t j = 0; j < 32; ++j) table[pi * 32 + j] = j < patterns[pi].size() ? patterns[pi][j] : 0;  // padding: own row, value +0.0
-        HIPC(hipMalloc(&m.sell_spat, sizeof(int32_t) * spat.size()));
-        HIPC(hipMalloc(&m.sell_pat, sizeof(int32_t) * table.size()));
-        HIPC(hipMemcpyAsync(m.sell_spat, spat.data(), sizeof(int32_t) * spat.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPC(hipMemcpyAsync(m.sell_pat, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPC(m.sell_spat.alloc(spat.size()));
+        HIPC(m.sell_pat.alloc(table.size()));
+        HIPC(hipMemcpyAsync(m.sell_spat.get(), spat.data(), sizeof(int32_t) * spat.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIPC(hipMemcpyAsync(m.sell_pat.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));
         m.n_patterns = (int)patterns.size();
         m.n_pattern_slices = n_pattern_slices;
@@ -660,10 +647,10 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
               }
             }
             if (ok && !cls_of.empty()) {
-              HIPC(hipMalloc(&m.sellp_rowcls, rowcls.size()));
-              HIPC(hipMalloc(&m.sellp_ctab, sizeof(double) * ctab.size()));
-              HIPC(hipMemcpyAsync(m.sellp_rowcls, rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
-              HIPC(hipMemcpyAsync(m.sellp_ctab, ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
+              HIPC(m.sellp_rowcls.alloc_bytes(rowcls.size()));
+              HIPC(m.sellp_ctab.alloc(ctab.size()));
+              HIPC(hipMemcpyAsync(m.sellp_rowcls.get(), rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
+              HIPC(hipMemcpyAsync(m.sellp_ctab.get(), ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
               HIPC(hipStreamSynchronize(ctx->stream));
               m.rowclass = true;
               m.n_classes = (int)cls_of.size();
@@ -702,13 +689,13 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
                     a0 = b0 + 1;
                   }
                 }
-                HIPC(hipMalloc(&m.sellp_wave_rr, sizeof(int4) * desc.size()));
-                HIPC(hipMemcpyAsync(m.sellp_wave_rr, desc.data(), sizeof(int4) * desc.size(), hipMemcpyHostToDevice, ctx->stream));
+                HIPC(m.sellp_wave_rr.alloc(desc.size()));
+                HIPC(hipMemcpyAsync(m.sellp_wave_rr.get(), desc.data(), sizeof(int4) * desc.size(), hipMemcpyHostToDevice, ctx->stream));
               }
             }
           }
-          HIPC(hipMalloc(&m.sellp_wave_ptr, sizeof(int32_t) * wp.size()));
-          HIPC(hipMemcpyAsync(m.sellp_wave_ptr, wp.data(), sizeof(int32_t) * wp.size(), hipMemcpyHostToDevice, ctx->stream));
+          HIPC(m.sellp_wave_ptr.alloc(wp.size()));
+          HIPC(hipMemcpyAsync(m.sellp_wave_ptr.get(), wp.data(), sizeof(int32_t) * wp.size(), hipMemcpyHostToDevice, ctx->stream));
           HIPC(hipStreamSynchronize(ctx->stream));
         }
       }
@@ -836,12 +823,12 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
               m.lat_gen_bytes = gen_bytes;
               m.lat_classes = (int)cls_of.size();
               if (m.lat_grid <= kMaxPartials) {
-                HIPC(hipMalloc(&m.lat_rowcls, rowcls.size() + 64));
-                HIPC(hipMalloc(&m.lat_ctab, sizeof(double) * ctab.size()));
-                HIPC(hipMalloc(&m.lat_gen, sizeof(int32_t) * std::max<size_t>(gen.size(), 1)));
-                HIPC(hipMemcpyAsync(m.lat_rowcls, rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
-                HIPC(hipMemcpyAsync(m.lat_ctab, ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
-                if (!gen.empty()) HIPC(hipMemcpyAsync(m.lat_gen, gen.data(), sizeof(int32_t) * gen.size(), hipMemcpyHostToDevice, ctx->stream));
+                HIPC(m.lat_rowcls.alloc_bytes(rowcls.size() + 64));
+                HIPC(m.lat_ctab.alloc(ctab.size()));
+                HIPC(m.lat_gen.alloc(std::max<size_t>(gen.size(), 1)));
+                HIPC(hipMemcpyAsync(m.lat_rowcls.get(), rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
+                HIPC(hipMemcpyAsync(m.lat_ctab.get(), ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
+                if (!gen.empty()) HIPC(hipMemcpyAsync(m.lat_gen.get(), gen.data(), sizeof(int32_t) * gen.size(), hipMemcpyHostToDevice, ctx->stream));
                 HIPC(hipStreamSynchronize(ctx->stream));
                 m.lattice = true;
                 if (ctx->debug_upload)
@@ -857,8 +844,7 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
         phase("lattice plan");
       }
       if (!keep_csr) {  // the CSR copy is only kept where the SGS sweeps need it (levels >= 1)
-        (void)hipFree(m.col); (void)hipFree(m.val); (void)hipFree(m.tile_row);
-        m.col = nullptr; m.val = nullptr; m.tile_row = nullptr;
+        m.col.reset(); m.val.reset(); m.tile_row.reset();
       }
     }
   }
@@ -889,10 +875,9 @@ void transpose_host(int64_t n_rows, int64_t n_cols, const int64_t *rp, const int
     }
 }
 
-int alloc_vec(gmg_context *ctx, double **p, int64_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIPC(hipMalloc(p, sizeof(double) * (size_t)std::max<int64_t>(n + 2, 2)));
-  HIPC(hipMemsetAsync(*p, 0, sizeof(double) * (size_t)std::max<int64_t>(n + 2, 2), ctx->stream));
+int alloc_vec(gmg_context *ctx, DevPtr<double> &p, int64_t n) {
+  HIPC(p.alloc((size_t)std::max<int64_t>(n + 2, 2)));
+  HIPC(hipMemsetAsync(p.get(), 0, sizeof(double) * (size_t)std::max<int64_t>(n + 2, 2), ctx->stream));
   return GMG_OK;
 }
 
@@ -916,14 +901,14 @@ inline void launch_timed(gmg_context *ctx, K kernel, dim3 grid, dim3 block, size
 template <int MODE, int CG>
 int launch_op(gmg_context *ctx, const DevCSR &m, const SpmvArgs &a) {
   if (m.sell || m.lat_only) {
-    SellArgs sa{m.slice_ptr, m.slice_base, m.sell_vals, m.sell_cols, m.sell_dict, m.sell_spat, m.sell_pat, m.n_slices, (int)m.n_rows, a};
+    SellArgs sa{m.slice_ptr.get(), m.slice_base.get(), m.sell_vals.get(), m.sell_cols.get(), m.sell_dict.get(), m.sell_spat.get(), m.sell_pat.get(), m.n_slices, (int)m.n_rows, a};
     if constexpr (MODE == kStore && (CG == 0 || CG == 2)) {
       if (m.lattice && !a.init) {
         LatArgs la{};
         la.pa.sa = sa; la.pa.col16 = m.col16 ? 1 : 0;
-        la.rowcls = m.lat_rowcls; la.ctab = m.lat_ctab; la.n_classes = m.lat_classes;
+        la.rowcls = m.lat_rowcls.get(); la.ctab = m.lat_ctab.get(); la.n_classes = m.lat_classes;
         la.nx = m.lat_nx; la.nxy = m.lat_nxy; la.W = m.lat_W; la.R0 = m.lat_R0; la.R1 = m.lat_R1; la.C = m.lat_C; la.K = m.lat_K; la.S = m.lat_S;
-        la.fast_blocks = m.lat_fast_blocks; la.gen_slices = m.lat_gen; la.n_gen = m.lat_n_gen;
+        la.fast_blocks = m.lat_fast_blocks; la.gen_slices = m.lat_gen.get(); la.n_gen = m.lat_n_gen;
         la.edge_mode = m.lat_only ? 1 : 0; la.n_rows = (int)m.n_rows;
         if (m.lat_S * m.lat_C > (m.lat_fast_blocks / 8) * 4) launch_timed(ctx, spmv_lattice_kernel<CG, true>, dim3(m.lat_grid), dim3(kThreads), 0, la);
         else launch_timed(ctx, spmv_lattice_kernel<CG, false>, dim3(m.lat_grid), dim3(kThreads), 0, la);
@@ -937,9 +922,9 @@ int launch_op(gmg_context *ctx, const DevCSR &m, const SpmvArgs &a) {
     }
     if (m.use_sellp) {
       SellPatArgs pa{};
-      pa.sa = sa; pa.wave_ptr = m.sellp_wave_ptr; pa.wave_rr = m.sellp_wave_rr; pa.pid0 = m.sellp_pid; pa.col16 = m.col16 ? 1 : 0;
+      pa.sa = sa; pa.wave_ptr = m.sellp_wave_ptr.get(); pa.wave_rr = m.sellp_wave_rr.get(); pa.pid0 = m.sellp_pid; pa.col16 = m.col16 ? 1 : 0;
       for (int u = 0; u < 9; ++u) pa.centre[u] = m.sellp_centre[u];
-      pa.rowcls = m.sellp_rowcls; pa.ctab = m.sellp_ctab; pa.n_classes = m.n_classes;
+      pa.rowcls = m.sellp_rowcls.get(); pa.ctab = m.sellp_ctab.get(); pa.n_classes = m.n_classes;
       if (m.rowclass) launch_timed(ctx, spmv_sellp_kernel<MODE, CG, true>, dim3(m.sell_grid), dim3(kThreads), 0, pa);
       else launch_timed(ctx, spmv_sellp_kernel<MODE, CG, false>, dim3(m.sell_grid), dim3(kThreads), 0, pa);
       return m.sell_grid;
@@ -960,7 +945,7 @@ void launch_spmv_mode(gmg_context *ctx, const DevCSR &m, const SpmvArgs &a) {
 
 SpmvArgs base_args(const DevCSR &m, const double *x, double *y) {
   SpmvArgs a{};
-  a.rowptr = m.rowptr; a.col = m.col; a.val = m.val; a.tile_row = m.tile_row;
+  a.rowptr = m.rowptr.get(); a.col = m.col.get(); a.val = m.val.get(); a.tile_row = m.tile_row.get();
   a.n_tiles = m.n_tiles; a.tiles_per_xcd = m.tiles_per_xcd;
   a.x = x; a.y = y;
   return a;
@@ -992,9 +977,9 @@ int spmv(gmg_context *ctx, const DevCSR &m, int mode, const double *x, double *y
 // ---- reductions to the host -------------------------------------------------------------
 
 int fetch_scalars(gmg_context *ctx, int n) {
-  HIPC(hipMemcpyAsync(ctx->scal_host, ctx->scal_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(ctx->scal_host.get(), ctx->scal_dev.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(stream_wait(ctx->stream));
-  if (*ctx->sgs_abort) return fail(ctx, GMG_ERR_HIP, "SSOR sweep: a wave gave up waiting for its partner (internal protocol error)");
+  if (*ctx->sgs_abort.get()) return fail(ctx, GMG_ERR_HIP, "SSOR sweep: a wave gave up waiting for its partner (internal protocol error)");
   if (comm_aborted(ctx->comm)) return fail(ctx, GMG_ERR_COMM, "peer transport: a rank gave up waiting for a message or an acknowledgement");
   if (ctx->comm.n_ranks > 1) {
     // sums: slots flagged by the caller; handled in the callers below
@@ -1004,15 +989,15 @@ int fetch_scalars(gmg_context *ctx, int n) {
 
 int dot_host(gmg_context *ctx, const double *x, const double *y, int64_t n, double *out) {
   const int g = grid_for(n);
-  hipLaunchKernelGGL(dot_partial_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, x, y, n, ctx->part_a);
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a, g, 1, 0u,
-                     ctx->scal_dev);
+  hipLaunchKernelGGL(dot_partial_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, x, y, n, ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), g, 1, 0u,
+                     ctx->scal_dev.get());
   if (ctx->comm.n_ranks > 1) {
-    if (allreduce_sum(ctx->comm, ctx->scal_dev, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
+    if (allreduce_sum(ctx->comm, ctx->scal_dev.get(), 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
   }
   CHK(launch_status(ctx));
   CHK(fetch_scalars(ctx, 1));
-  *out = ctx->scal_host[0];
+  *out = ctx->scal_host.get()[0];
   return GMG_OK;
 }
 
@@ -1024,7 +1009,7 @@ void collect_sgs_samples(gmg_context *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   for (int i = 0; i < ctx->ev3_used; ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev_e[(size_t)i], ctx->ev_f[(size_t)i]) != hipSuccess) continue;
+    if (hipEventElapsedTime(&ms, ctx->ev_e[(size_t)i].get(), ctx->ev_f[(size_t)i].get()) != hipSuccess) continue;
     ctx->stats.sgs_ms_total += ms;
     ctx->stats.sgs_samples++;
   }
@@ -1034,15 +1019,14 @@ void collect_sgs_samples(gmg_context *ctx) {
 // option sgs_profile: the instrumented variant of the sweep; prints where each range of the first blocks spent its cycles
 int sgs_profile_launch(gmg_context *ctx, Level &L, SgsWaveArgs p) {
   const size_t nr = (size_t)L.sgs.w_n_ranges;
-  unsigned long long *d = nullptr;
+  DevPtr<unsigned long long> d;
   std::vector<unsigned long long> h(4 * nr, 0);
-  HIPC(hipMalloc(&d, sizeof(unsigned long long) * 4 * nr));
-  p.prof = d;
+  HIPC(d.alloc(4 * nr));
+  p.prof = d.get();
   p.prof_mode = ctx->sgs_profile_mode;
   hipLaunchKernelGGL(sgs_wave_kernel<true>, dim3(L.sgs.n_blocks), dim3(kSwThreads), (size_t)L.sgs.w_lds_bytes, ctx->stream, p);
-  HIPC(hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * 4 * nr, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(h.data(), d.get(), sizeof(unsigned long long) * 4 * nr, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d);
   if (L.sgs.w_steps > 1000) {
     std::fprintf(stderr, "[gmg] SGS sweep profile mode %d (%lld rows, %d ranges; shader cycles: sweep / of it waiting for the ring / load / write-back):", ctx->sgs_profile_mode, (long long)L.n, (int)nr);
     for (size_t i = 0; i < std::min<size_t>(nr, 10); ++i)
@@ -1055,10 +1039,10 @@ int sgs_profile_launch(gmg_context *ctx, Level &L, SgsWaveArgs p) {
 int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
   if (L.sgs.wave) {
     SgsWaveArgs p{};
-    p.ranges = L.sgs.w_ranges; p.block_rng = L.sgs.w_block_rng; p.stream = L.sgs.w_stream; p.ws_ci = L.sgs.w_ws_ci;
-    p.ci_row = L.sgs.w_ci_row; p.ycur = L.sgs.w_ycur; p.y = y; p.omega = ctx->omega; p.y_slots = L.sgs.w_y_slots;
-    p.row_ci = L.sgs.w_row_ci; p.rpos_f = L.sgs.w_rpos_f; p.rpos_b = L.sgs.w_rpos_b; p.iso_diag = L.sgs.w_iso_diag;
-    p.iso_invd = L.sgs.w_iso_invd; p.r = r; p.n_rows = L.n; p.abort_flag = ctx->sgs_abort;
+    p.ranges = L.sgs.w_ranges.get(); p.block_rng = L.sgs.w_block_rng.get(); p.stream = L.sgs.w_stream.get(); p.ws_ci = L.sgs.w_ws_ci.get();
+    p.ci_row = L.sgs.w_ci_row.get(); p.ycur = L.sgs.w_ycur.get(); p.y = y; p.omega = ctx->omega; p.y_slots = L.sgs.w_y_slots;
+    p.row_ci = L.sgs.w_row_ci.get(); p.rpos_f = L.sgs.w_rpos_f.get(); p.rpos_b = L.sgs.w_rpos_b.get(); p.iso_diag = L.sgs.w_iso_diag.get();
+    p.iso_invd = L.sgs.w_iso_invd.get(); p.r = r; p.n_rows = L.n; p.abort_flag = ctx->sgs_abort.get();
     hipLaunchKernelGGL(sgs_wave_prepass_kernel, dim3(grid_for(L.n)), dim3(256), 0, ctx->stream, p);
     // one process per GPU: the blocks are what the reference's ranks sweep -- each rank sweeps its share of them and
     // the pieces of y are all-gathered (levels >= 1 are replicated: every rank needs the whole vector)
@@ -1073,7 +1057,7 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
       if (ctx->prof_every > 0 && !ctx->ev_e.empty()) {
         ctx->stats.sgs_launches++;
         if ((ctx->sgs_launch_no++ % (ctx->prof_every | 1)) == 0 && ctx->ev3_used < (int)ctx->ev_e.size()) {  // (odd stride: a V-cycle launches 4 sweeps per level, a stride of 8 would always hit the same one)
-          ctx->timed_start = ctx->ev_e[(size_t)ctx->ev3_used]; ctx->timed_stop = ctx->ev_f[(size_t)ctx->ev3_used++];
+          ctx->timed_start = ctx->ev_e[(size_t)ctx->ev3_used].get(); ctx->timed_stop = ctx->ev_f[(size_t)ctx->ev3_used++].get();
           ctx->stats.sgs_substeps += L.sgs.w_steps;
           ctx->stats.sgs_stream_bytes += L.sgs.w_stream_bytes;
         }
@@ -1081,19 +1065,18 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
       const size_t lds = ctx->sgs_lds_bytes_override > 0 ? (size_t)ctx->sgs_lds_bytes_override : (size_t)L.sgs.w_lds_bytes;
       if (L.sgs.phased) {
         SgsPhaseArgs q{};
-        q.ranges = L.sgs.p_ranges; q.blk_tab = L.sgs.p_blk_tab; q.block_rng = p.block_rng; q.block0 = p.block0; q.stream = p.stream; q.ws_ci = p.ws_ci; q.ci_row = p.ci_row;
+        q.ranges = L.sgs.p_ranges.get(); q.blk_tab = L.sgs.p_blk_tab.get(); q.block_rng = p.block_rng; q.block0 = p.block0; q.stream = p.stream; q.ws_ci = p.ws_ci; q.ci_row = p.ci_row;
         q.ycur = p.ycur; q.y = p.y; q.omega = p.omega; q.y_slots = p.y_slots; q.prof = nullptr;
         if (ctx->sgs_phase_profile > 0 && n_ranks == 1 && L.sgs.dep) {
           // diagnostics of the one-dependent-wave sweep: per range, cycles of every wave and how many of them it waited
           const size_t nr = (size_t)L.sgs.w_n_ranges;
-          unsigned long long *d = nullptr;
+          DevPtr<unsigned long long> d;
           std::vector<unsigned long long> h(12 * nr, 0);
-          HIPC(hipMalloc(&d, sizeof(unsigned long long) * 12 * nr));
-          q.prof = d;
-          hipLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), lds, ctx->stream, q, ctx->sgs_abort);
-          hipError_t e = hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * 12 * nr, hipMemcpyDeviceToHost, ctx->stream);
+          HIPC(d.alloc(12 * nr));
+          q.prof = d.get();
+          hipLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), lds, ctx->stream, q, ctx->sgs_abort.get());
+          hipError_t e = hipMemcpyAsync(h.data(), d.get(), sizeof(unsigned long long) * 12 * nr, hipMemcpyDeviceToHost, ctx->stream);
           if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-          (void)hipFree(d);
           if (e != hipSuccess) { ctx->err = std::string("SSOR sweep profile: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
           if (L.sgs.w_steps > 1000 && nbl == 1)
             for (size_t i = 0; i < nr; ++i) {
@@ -1107,19 +1090,18 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
           // the instrumented variant of the sweep (same arithmetic, same results, s_memtime around every phase); the
           // launch falls through to the common tail like the production one
           const size_t nr = (size_t)L.sgs.w_n_ranges;
-          unsigned long long *d = nullptr;
+          DevPtr<unsigned long long> d;
           std::vector<unsigned long long> h(12 * nr, 0);
-          HIPC(hipMalloc(&d, sizeof(unsigned long long) * 12 * nr));
-          q.prof = d;
+          HIPC(d.alloc(12 * nr));
+          q.prof = d.get();
 #ifdef GMG_EXPERIMENTS
-          if (ctx->sgs_chain) hipLaunchKernelGGL(sgs_chain_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q, ctx->sgs_abort);
+          if (ctx->sgs_chain) hipLaunchKernelGGL(sgs_chain_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q, ctx->sgs_abort.get());
           else
 #endif
           if (L.sgs.reg) hipLaunchKernelGGL(sgs_regs_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q);
           else hipLaunchKernelGGL(sgs_phase_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q);
-          hipError_t e = hipMemcpyAsync(h.data(), d, sizeof(unsigned long long) * 12 * nr, hipMemcpyDeviceToHost, ctx->stream);
+          hipError_t e = hipMemcpyAsync(h.data(), d.get(), sizeof(unsigned long long) * 12 * nr, hipMemcpyDeviceToHost, ctx->stream);
           if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-          (void)hipFree(d);
           if (e != hipSuccess) { ctx->err = std::string("SSOR sweep profile: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
           if (L.sgs.w_steps > 1000 && nbl == 1) {
             std::fprintf(stderr, "[gmg] four-wave sweep (%s), %lld rows: per range dir steps | cycles/step | load+write-back cycles\n",
@@ -1149,14 +1131,14 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
         } else
         if (L.sgs.dep) {
           if (ctx->timed_start) {  // (two kernel arguments: the one-argument launch_timed does not fit)
-            hipExtLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), (std::uint32_t)lds, ctx->stream, ctx->timed_start, ctx->timed_stop, 0u, q, ctx->sgs_abort);
+            hipExtLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), (std::uint32_t)lds, ctx->stream, ctx->timed_start, ctx->timed_stop, 0u, q, ctx->sgs_abort.get());
             ctx->timed_start = ctx->timed_stop = nullptr;
           } else {
-            hipLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), lds, ctx->stream, q, ctx->sgs_abort);
+            hipLaunchKernelGGL(sgs_dep_kernel, dim3(nbl), dim3(kDpThreads), lds, ctx->stream, q, ctx->sgs_abort.get());
           }
         } else
 #ifdef GMG_EXPERIMENTS
-        if (ctx->sgs_chain) hipLaunchKernelGGL(sgs_chain_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q, ctx->sgs_abort);
+        if (ctx->sgs_chain) hipLaunchKernelGGL(sgs_chain_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q, ctx->sgs_abort.get());
         else
 #endif
         if (L.sgs.reg) launch_timed(ctx, sgs_regs_kernel, dim3(nbl), dim3(kPhThreads), lds, q);
@@ -1171,13 +1153,13 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
       auto piece = [&](int r, int64_t *b, int64_t *e) { *b = br[(size_t)(r * nbl)]; *e = br[(size_t)((r + 1) * nbl)]; };
       int64_t b, e;
       piece(ctx->comm.rank, &b, &e);
-      double *mine = L.sgs.w_stage + (int64_t)ctx->comm.rank * len;
+      double *mine = L.sgs.w_stage.get() + (int64_t)ctx->comm.rank * len;
       if (e > b) HIPC(hipMemcpyAsync(mine, y + b, sizeof(double) * (size_t)(e - b), hipMemcpyDeviceToDevice, ctx->stream));
-      if (allgather_chunks(ctx->comm, L.sgs.w_stage, len, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "SSOR: all-gather failed");
+      if (allgather_chunks(ctx->comm, L.sgs.w_stage.get(), len, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "SSOR: all-gather failed");
       for (int r = 0; r < n_ranks; ++r) {
         if (r == ctx->comm.rank) continue;
         piece(r, &b, &e);
-        if (e > b) HIPC(hipMemcpyAsync(y + b, L.sgs.w_stage + (int64_t)r * len, sizeof(double) * (size_t)(e - b), hipMemcpyDeviceToDevice, ctx->stream));
+        if (e > b) HIPC(hipMemcpyAsync(y + b, L.sgs.w_stage.get() + (int64_t)r * len, sizeof(double) * (size_t)(e - b), hipMemcpyDeviceToDevice, ctx->stream));
       }
     }
     HIPC(hipGetLastError());
@@ -1185,9 +1167,9 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
   }
   HIPC(hipMemsetAsync(y, 0, sizeof(double) * (size_t)L.n, ctx->stream));
   SgsArgs a{};
-  a.rowptr = L.A.rowptr; a.col = L.A.col; a.val = L.A.val; a.invd = L.invd;
-  a.block_row = L.sgs.block_row; a.block_stage = L.sgs.block_stage;
-  a.stage_ptr = L.sgs.stage_ptr; a.stage_rows = L.sgs.stage_rows;
+  a.rowptr = L.A.rowptr.get(); a.col = L.A.col.get(); a.val = L.A.val.get(); a.invd = L.invd.get();
+  a.block_row = L.sgs.block_row.get(); a.block_stage = L.sgs.block_stage.get();
+  a.stage_ptr = L.sgs.stage_ptr.get(); a.stage_rows = L.sgs.stage_rows.get();
   a.omega = ctx->omega; a.r = r; a.y = y;
   hipLaunchKernelGGL(sgs_sweep_kernel<false>, dim3(L.sgs.n_blocks), dim3(1024), 0, ctx->stream, a);
   hipLaunchKernelGGL(sgs_sweep_kernel<true>, dim3(L.sgs.n_blocks), dim3(1024), 0, ctx->stream, a);
@@ -1202,8 +1184,8 @@ int cheb_apply(gmg_context *ctx, Level &L, const double *r, double **out) {
   const double alpha = lmax / ctx->cheb_ratio, beta = lmax;
   const double delta = 2.0 / (beta - alpha), theta = 0.5 * (beta + alpha), s1 = theta * delta;
   double rhok = 1.0 / s1;
-  double *y = L.w1, *yn = L.w3, *w = L.w2;
-  hipLaunchKernelGGL(cheb_first_kernel, dim3(grid_for(L.n)), dim3(kThreads), 0, ctx->stream, y, w, r, (const double *)L.invd,
+  double *y = L.w1.get(), *yn = L.w3.get(), *w = L.w2.get();
+  hipLaunchKernelGGL(cheb_first_kernel, dim3(grid_for(L.n)), dim3(kThreads), 0, ctx->stream, y, w, r, (const double *)L.invd.get(),
                      theta, L.n);
   for (int deg = 1; deg < ctx->cheb_degree; ++deg) {
     const double rhokp1 = 1.0 / (2.0 * s1 - rhok);
@@ -1211,7 +1193,7 @@ int cheb_apply(gmg_context *ctx, Level &L, const double *r, double **out) {
     rhok = rhokp1;
     CHK(import_ghosts(ctx, L.A, y));
     SpmvArgs a = base_args(L.A, y, yn);
-    a.b = r; a.invd = L.invd; a.w = w; a.omega = d2; a.c1 = d1;
+    a.b = r; a.invd = L.invd.get(); a.w = w; a.omega = d2; a.c1 = d1;
     launch_spmv_mode<kCheb>(ctx, L.A, a);
     std::swap(y, yn);
   }
@@ -1220,17 +1202,17 @@ int cheb_apply(gmg_context *ctx, Level &L, const double *r, double **out) {
 }
 
 // MGSmootherPrecondition::apply (from_zero) / ::smooth on level l; u and rhs are level vectors.
-// Jacobi steps run out of place; *u_io may come back pointing at the level's spare buffer.
-int smooth_level(gmg_context *ctx, int l, double **u_io, const double *rhs, bool from_zero, double **spare) {
+// Jacobi steps run out of place; u_io may come back holding the level's spare buffer (and spare_io what u_io held).
+int smooth_level(gmg_context *ctx, int l, DevPtr<double> &u_io, const double *rhs, bool from_zero, DevPtr<double> &spare_io) {
   Level &L = ctx->lv[(size_t)l];
-  double *u = *u_io;
+  double *u = u_io.get(), *spare = spare_io.get();
   const int g = grid_for(L.n);
   int first = 0;
   if (from_zero && ctx->steps > 0) {
     first = 1;
     if (ctx->smoother == GMG_SMOOTHER_JACOBI) {
       hipLaunchKernelGGL(vec_scale_mul_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, u, ctx->omega, rhs,
-                         (const double *)L.invd, L.n);
+                         (const double *)L.invd.get(), L.n);
     } else if (ctx->smoother == GMG_SMOOTHER_SSOR) {
       CHK(sgs_apply(ctx, L, u, rhs));
     } else {
@@ -1242,23 +1224,23 @@ int smooth_level(gmg_context *ctx, int l, double **u_io, const double *rhs, bool
   for (int s = first; s < ctx->steps; ++s) {
     CHK(import_ghosts(ctx, L.A, u));
     if (ctx->smoother == GMG_SMOOTHER_JACOBI) {
-      SpmvArgs a = base_args(L.A, u, *spare);
-      a.b = rhs; a.invd = L.invd; a.omega = ctx->omega;
+      SpmvArgs a = base_args(L.A, u, spare);
+      a.b = rhs; a.invd = L.invd.get(); a.omega = ctx->omega;
       launch_spmv_mode<kJacobi>(ctx, L.A, a);
-      std::swap(u, *spare);
+      std::swap(u, spare);
     } else {
-      CHK(spmv(ctx, L.A, kResid, u, L.t, nullptr, rhs));  // r = rhs - A u
+      CHK(spmv(ctx, L.A, kResid, u, L.t.get(), nullptr, rhs));  // r = rhs - A u
       if (ctx->smoother == GMG_SMOOTHER_SSOR) {
-        CHK(sgs_apply(ctx, L, L.w1, L.t));
-        hipLaunchKernelGGL(vec_add_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, u, 1.0, (const double *)L.w1, L.n);
+        CHK(sgs_apply(ctx, L, L.w1.get(), L.t.get()));
+        hipLaunchKernelGGL(vec_add_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, u, 1.0, (const double *)L.w1.get(), L.n);
       } else {
         double *y = nullptr;
-        CHK(cheb_apply(ctx, L, L.t, &y));
+        CHK(cheb_apply(ctx, L, L.t.get(), &y));
         hipLaunchKernelGGL(vec_add_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, u, 1.0, (const double *)y, L.n);
       }
     }
   }
-  *u_io = u;
+  if (u != u_io.get()) std::swap(u_io, spare_io);
   return launch_status(ctx);
 }
 
@@ -1269,7 +1251,7 @@ void collect_profile_samples(gmg_context *ctx) {
   const int iters = ctx->st_final.iters;
   for (int i = 0; i < ctx->ev_used; ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev_a[(size_t)i], ctx->ev_b[(size_t)i]) != hipSuccess) continue;
+    if (hipEventElapsedTime(&ms, ctx->ev_a[(size_t)i].get(), ctx->ev_b[(size_t)i].get()) != hipSuccess) continue;
     if (i * ctx->prof_every < iters) {
       ctx->stats.spmv0_ms_total += ms;
       ctx->stats.spmv0_samples++;
@@ -1280,7 +1262,7 @@ void collect_profile_samples(gmg_context *ctx) {
   }
   for (int i = 0; i < ctx->ev2_used; ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev_c[(size_t)i], ctx->ev_d[(size_t)i]) != hipSuccess) continue;
+    if (hipEventElapsedTime(&ms, ctx->ev_c[(size_t)i].get(), ctx->ev_d[(size_t)i].get()) != hipSuccess) continue;
     if (i * ctx->prof_every < iters) {
       ctx->stats.cgupd_ms_total += ms;
       ctx->stats.cgupd_samples++;
@@ -1310,8 +1292,8 @@ int run_cg_chunks(gmg_context *ctx, int later_default, EnqueueOne enqueue_one) {
       if (rc != GMG_OK) return rc;
     }
     CHK(launch_status(ctx));
-    HIPC(hipMemcpyAsync(&ctx->st_host[slot], ctx->st, sizeof(CGState), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(hipEventRecord(ctx->ev_chunk[slot], ctx->stream));
+    HIPC(hipMemcpyAsync(&ctx->st_host.get()[slot], ctx->st.get(), sizeof(CGState), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipEventRecord(ctx->ev_chunk[slot].get(), ctx->stream));
     return GMG_OK;
   };
   int slot = 0;
@@ -1322,11 +1304,11 @@ int run_cg_chunks(gmg_context *ctx, int later_default, EnqueueOne enqueue_one) {
   for (;;) {
     if (speculate) CHK(launch_chunk(later, slot ^ 1));
     for (;;) {
-      const hipError_t e = hipEventQuery(ctx->ev_chunk[slot]);
+      const hipError_t e = hipEventQuery(ctx->ev_chunk[slot].get());
       if (e == hipSuccess) break;
       if (e != hipErrorNotReady) { ctx->err = std::string("hipEventQuery: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
     }
-    if (ctx->st_host[slot].done) { ctx->st_final = ctx->st_host[slot]; ctx->stats.coarse_enqueued += launched; break; }
+    if (ctx->st_host.get()[slot].done) { ctx->st_final = ctx->st_host.get()[slot]; ctx->stats.coarse_enqueued += launched; break; }
     if (launched > maxit + 2 * later + 2) return fail(ctx, GMG_ERR_HIP, "coarse CG state machine did not terminate");
     if (!speculate) CHK(launch_chunk(later, slot ^ 1));
     slot ^= 1;
@@ -1353,26 +1335,26 @@ int coarse_solve(gmg_context *ctx, double *x, const double *b, int *iters_out, d
   const int64_t n = L0.n;
   const int g_upd = grid_for((n / 2 + 0));
   const int g_init = grid_for(n);
-  CGInitArgs ia{b, x, ctx->cg_g, ctx->cg_d0, ctx->cg_d1, n, ctx->st, ctx->part_b};
+  CGInitArgs ia{b, x, ctx->cg_g.get(), ctx->cg_d0.get(), ctx->cg_d1.get(), n, ctx->st.get(), ctx->part_b.get()};
   hipLaunchKernelGGL(cg_init_kernel, dim3(g_init), dim3(kThreads), 0, ctx->stream, ia);
   int n_part_gg = g_init;
   const int maxit = ctx->coarse_maxit;
   ctx->ev_used = 0; ctx->ev2_used = 0;
   CHK(run_cg_chunks(ctx, 6, [&](int launched) -> int {
     const bool odd = launched & 1;
-    SpmvArgs a = base_args(A, odd ? ctx->cg_d1 : ctx->cg_d0, ctx->cg_h);
-    a.g = ctx->cg_g;
-    a.dnew = odd ? ctx->cg_d0 : ctx->cg_d1;
-    a.st = ctx->st;
-    a.part_in = ctx->part_b; a.n_part_in = n_part_gg;
-    a.part_out = ctx->part_a;
+    SpmvArgs a = base_args(A, odd ? ctx->cg_d1.get() : ctx->cg_d0.get(), ctx->cg_h.get());
+    a.g = ctx->cg_g.get();
+    a.dnew = odd ? ctx->cg_d0.get() : ctx->cg_d1.get();
+    a.st = ctx->st.get();
+    a.part_in = ctx->part_b.get(); a.n_part_in = n_part_gg;
+    a.part_out = ctx->part_a.get();
     a.tol = ctx->coarse_tol; a.maxit = maxit;
     const bool sample = ctx->prof_every > 0 && (launched % ctx->prof_every) == 0 && ctx->ev_used < (int)ctx->ev_a.size();
-    if (sample) { ctx->timed_start = ctx->ev_a[(size_t)ctx->ev_used]; ctx->timed_stop = ctx->ev_b[(size_t)ctx->ev_used++]; }
+    if (sample) { ctx->timed_start = ctx->ev_a[(size_t)ctx->ev_used].get(); ctx->timed_stop = ctx->ev_b[(size_t)ctx->ev_used++].get(); }
     const int n_part_dh = launch_op<kStore, 1>(ctx, A, a);
-    CGUpdateArgs ua{x, ctx->cg_g, a.dnew, ctx->cg_h, n, ctx->st, ctx->part_a, n_part_dh, ctx->part_b};
+    CGUpdateArgs ua{x, ctx->cg_g.get(), a.dnew, ctx->cg_h.get(), n, ctx->st.get(), ctx->part_a.get(), n_part_dh, ctx->part_b.get()};
     const bool sample2 = sample && ctx->ev2_used < (int)ctx->ev_c.size();
-    if (sample2) { ctx->timed_start = ctx->ev_c[(size_t)ctx->ev2_used]; ctx->timed_stop = ctx->ev_d[(size_t)ctx->ev2_used++]; }
+    if (sample2) { ctx->timed_start = ctx->ev_c[(size_t)ctx->ev2_used].get(); ctx->timed_stop = ctx->ev_d[(size_t)ctx->ev2_used++].get(); }
     launch_timed(ctx, cg_update_kernel, dim3(g_upd), dim3(kThreads), 0, ua);
     n_part_gg = g_upd;
     return GMG_OK;
@@ -1411,12 +1393,12 @@ int allgather_full(gmg_context *ctx, double *full, const double *local, int64_t 
 // MGCoarseGridBase::operator() as the V-cycle sees it: replicated defect in, replicated solution out
 int coarse_level_solve(gmg_context *ctx) {
   Level &L0 = ctx->lv[0];
-  if (!l0_partitioned(ctx)) return coarse_solve(ctx, L0.sol, L0.def, nullptr, nullptr);
+  if (!l0_partitioned(ctx)) return coarse_solve(ctx, L0.sol.get(), L0.def.get(), nullptr, nullptr);
   int64_t b, e;
   part_range(ctx->l0_global, ctx->comm.rank, ctx->comm.n_ranks, &b, &e);
-  if (e > b) HIPC(hipMemcpyAsync(L0.def, L0.def_full + b, sizeof(double) * (size_t)(e - b), hipMemcpyDeviceToDevice, ctx->stream));
-  CHK(coarse_solve(ctx, L0.sol, L0.def, nullptr, nullptr));
-  return allgather_full(ctx, L0.sol_full, L0.sol, ctx->l0_global);
+  if (e > b) HIPC(hipMemcpyAsync(L0.def.get(), L0.def_full + b, sizeof(double) * (size_t)(e - b), hipMemcpyDeviceToDevice, ctx->stream));
+  CHK(coarse_solve(ctx, L0.sol.get(), L0.def.get(), nullptr, nullptr));
+  return allgather_full(ctx, L0.sol_full, L0.sol.get(), ctx->l0_global);
 }
 
 // ---- V-cycle (A5, A6, A8) -----------------------------------------------------------------
@@ -1425,24 +1407,24 @@ int level_v_step(gmg_context *ctx, int l) {
   Level &L = ctx->lv[(size_t)l];
   if (l == 0) return coarse_level_solve(ctx);
   Level &C = ctx->lv[(size_t)l - 1];
-  double *c_def = (l == 1) ? C.def_full : C.def;
+  double *c_def = (l == 1) ? C.def_full : C.def.get();
   const int g = grid_for(L.n);
-  CHK(smooth_level(ctx, l, &L.sol, L.def, true, &L.w1));  // pre_smooth->apply (Jacobi may swap sol <-> w1)
+  CHK(smooth_level(ctx, l, L.sol, L.def.get(), true, L.w1));  // pre_smooth->apply (Jacobi may swap sol <-> w1)
   if (L.has_I) {
-    CHK(spmv(ctx, L.A, kStore, L.sol, L.t));                 // t = A u
-    CHK(spmv(ctx, L.I, kStore, L.sol, L.t, L.t));            // edge_out->vmult_add
-    hipLaunchKernelGGL(vec_sadd_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, L.t, -1.0, 1.0, (const double *)L.def, L.n);
+    CHK(spmv(ctx, L.A, kStore, L.sol.get(), L.t.get()));                 // t = A u
+    CHK(spmv(ctx, L.I, kStore, L.sol.get(), L.t.get(), L.t.get()));            // edge_out->vmult_add
+    hipLaunchKernelGGL(vec_sadd_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, L.t.get(), -1.0, 1.0, (const double *)L.def.get(), L.n);
   } else {
-    CHK(spmv(ctx, L.A, kResid, L.sol, L.t, nullptr, L.def));  // t = defect - A u
+    CHK(spmv(ctx, L.A, kResid, L.sol.get(), L.t.get(), nullptr, L.def.get()));  // t = defect - A u
   }
-  CHK(spmv(ctx, C.Pt, kStore, L.t, c_def, c_def));            // restrict_and_add
+  CHK(spmv(ctx, C.Pt, kStore, L.t.get(), c_def, c_def));            // restrict_and_add
   CHK(level_v_step(ctx, l - 1));
-  const double *c_sol = (l == 1) ? C.sol_full : C.sol;        // read AFTER the recursion: Jacobi swaps C.sol
-  CHK(spmv(ctx, C.P, kAddTo, c_sol, L.sol, nullptr, L.sol));  // u += P u_c
+  const double *c_sol = (l == 1) ? C.sol_full : C.sol.get();        // read AFTER the recursion: Jacobi swaps C.sol
+  CHK(spmv(ctx, C.P, kAddTo, c_sol, L.sol.get(), nullptr, L.sol.get()));  // u += P u_c
   if (L.has_I) {
-    CHK(spmv(ctx, L.It, kResid, L.sol, L.def, nullptr, L.def));  // defect -= I^T u
+    CHK(spmv(ctx, L.It, kResid, L.sol.get(), L.def.get(), nullptr, L.def.get()));  // defect -= I^T u
   }
-  CHK(smooth_level(ctx, l, &L.sol, L.def, false, &L.w1));     // post_smooth->smooth
+  CHK(smooth_level(ctx, l, L.sol, L.def.get(), false, L.w1));     // post_smooth->smooth
   return GMG_OK;
 }
 
@@ -1452,30 +1434,30 @@ int vcycle(gmg_context *ctx, double *dst, const double *src) {
   double *dst_v = dst;
   int64_t n_sys = ctx->S.n_rows;
   if (ctx->dist) {  // PreconditionMG sees replicas of the outer vectors; only level 0 stays partitioned
-    CHK(allgather_full(ctx, ctx->sys_full_a, src, ctx->sys_global));
-    src_v = ctx->sys_full_a;
-    dst_v = ctx->sys_full_b;
+    CHK(allgather_full(ctx, ctx->sys_full_a.get(), src, ctx->sys_global));
+    src_v = ctx->sys_full_a.get();
+    dst_v = ctx->sys_full_b.get();
     n_sys = ctx->sys_global;
   }
   for (int l = 0; l < ctx->n_levels; ++l) {  // copy_to_mg
     Level &L = ctx->lv[(size_t)l];
     if (!L.A.valid) return fail(ctx, GMG_ERR_INVALID, "level matrix not set");
-    double *def = (l == 0) ? L.def_full : L.def;
+    double *def = (l == 0) ? L.def_full : L.def.get();
     const int64_t nl = (l == 0 && l0_partitioned(ctx)) ? ctx->l0_global : L.n_vec;
     HIPC(hipMemsetAsync(def, 0, sizeof(double) * (size_t)nl, ctx->stream));
-    if (l > 0) HIPC(hipMemsetAsync(L.sol, 0, sizeof(double) * (size_t)L.n_vec, ctx->stream));
+    if (l > 0) HIPC(hipMemsetAsync(L.sol.get(), 0, sizeof(double) * (size_t)L.n_vec, ctx->stream));
     if (L.n_copy)
       hipLaunchKernelGGL(gather_scatter_kernel, dim3(grid_for(L.n_copy)), dim3(kThreads), 0, ctx->stream, def,
-                         (const int32_t *)L.copy_l, src_v, (const int32_t *)L.copy_g, L.n_copy);
+                         (const int32_t *)L.copy_l.get(), src_v, (const int32_t *)L.copy_g.get(), L.n_copy);
   }
   CHK(level_v_step(ctx, ctx->n_levels - 1));
   HIPC(hipMemsetAsync(dst_v, 0, sizeof(double) * (size_t)n_sys, ctx->stream));  // copy_from_mg: dst = 0
   for (int l = 0; l < ctx->n_levels; ++l) {
     Level &L = ctx->lv[(size_t)l];
-    const double *sol = (l == 0) ? L.sol_full : L.sol;
+    const double *sol = (l == 0) ? L.sol_full : L.sol.get();
     if (L.n_copy)
       hipLaunchKernelGGL(gather_scatter_kernel, dim3(grid_for(L.n_copy)), dim3(kThreads), 0, ctx->stream, dst_v,
-                         (const int32_t *)L.copy_g, sol, (const int32_t *)L.copy_l, L.n_copy);
+                         (const int32_t *)L.copy_g.get(), sol, (const int32_t *)L.copy_l.get(), L.n_copy);
   }
   if (ctx->dist) {
     int64_t b, e;
@@ -1487,7 +1469,7 @@ int vcycle(gmg_context *ctx, double *dst, const double *src) {
 }
 
 // inverse diagonal + Gershgorin bound of D^-1 A (host), upload
-int setup_diag(gmg_context *ctx, int64_t n, const int64_t *rp, const int32_t *col, const double *val, double **invd_dev,
+int setup_diag(gmg_context *ctx, int64_t n, const int64_t *rp, const int32_t *col, const double *val, DevPtr<double> &invd_dev,
                double *lmax_out) {
   std::vector<double> invd((size_t)std::max<int64_t>(n, 1));
   double lmax = 0.0;
@@ -1502,17 +1484,9 @@ int setup_diag(gmg_context *ctx, int64_t n, const int64_t *rp, const int32_t *co
   }
   if (lmax_out) *lmax_out = lmax;
   CHK(alloc_vec(ctx, invd_dev, n));
-  if (n) HIPC(hipMemcpyAsync(*invd_dev, invd.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  if (n) HIPC(hipMemcpyAsync(invd_dev.get(), invd.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   return GMG_OK;
-}
-
-void free_sgs(SgsPlan &g) {
-  for (void *p : {(void *)g.stage_ptr, (void *)g.stage_rows, (void *)g.block_row, (void *)g.block_stage, (void *)g.w_ranges,
-                  (void *)g.w_block_rng, (void *)g.w_ws_ci, (void *)g.w_ci_row, (void *)g.w_row_ci, (void *)g.w_rpos_f, (void *)g.w_rpos_b,
-                  (void *)g.w_stream, (void *)g.w_ycur, (void *)g.w_iso_diag, (void *)g.w_iso_invd, (void *)g.w_stage, (void *)g.p_ranges, (void *)g.p_blk_tab})
-    if (p) (void)hipFree(p);
-  g = SgsPlan();
 }
 
 // ---- where the SSOR blocks are cut ("Block boundaries").  Modelled sweep time of a block of consecutive rows:
@@ -2154,23 +2128,19 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   for (size_t q = 0; q < rpos_f.size(); ++q)
     if ((uint64_t)rpos_f[q] * 8 + 8 > stream.size() || (uint64_t)rpos_b[q] * 8 + 8 > stream.size())
       return fail(ctx, GMG_ERR_INVALID, "SSOR plan: rhs position outside the stream (internal error)");
-#define SW_UP(dst, vec, T)                                                                                          \
-  HIPC(hipMalloc(&dst, sizeof(T) * std::max<size_t>((vec).size(), 1)));                                              \
-  if (!(vec).empty()) HIPC(hipMemcpyAsync(dst, (vec).data(), sizeof(T) * (vec).size(), hipMemcpyHostToDevice, ctx->stream));
-  SW_UP(G.w_ranges, ranges, SwRange)
-  SW_UP(G.p_ranges, pranges, PhRange)
-  SW_UP(G.p_blk_tab, blk_tab, uint4)
-  SW_UP(G.w_block_rng, block_rng, int32_t)
-  SW_UP(G.w_ws_ci, ws_ci, int32_t)
-  SW_UP(G.w_ci_row, ci_row, int32_t)
-  SW_UP(G.w_row_ci, row_ci, int32_t)
-  SW_UP(G.w_rpos_f, rpos_f, int32_t)
-  SW_UP(G.w_rpos_b, rpos_b, int32_t)
-  SW_UP(G.w_stream, stream, char)
-  SW_UP(G.w_iso_diag, iso_diag, double)
-  SW_UP(G.w_iso_invd, iso_invd, double)
-#undef SW_UP
-  HIPC(hipMalloc(&G.w_ycur, sizeof(double) * std::max<size_t>(ci_row.size(), 1)));
+  HIPC(upload(G.w_ranges, ranges, ctx->stream));
+  HIPC(upload(G.p_ranges, pranges, ctx->stream));
+  HIPC(upload(G.p_blk_tab, blk_tab, ctx->stream));
+  HIPC(upload(G.w_block_rng, block_rng, ctx->stream));
+  HIPC(upload(G.w_ws_ci, ws_ci, ctx->stream));
+  HIPC(upload(G.w_ci_row, ci_row, ctx->stream));
+  HIPC(upload(G.w_row_ci, row_ci, ctx->stream));
+  HIPC(upload(G.w_rpos_f, rpos_f, ctx->stream));
+  HIPC(upload(G.w_rpos_b, rpos_b, ctx->stream));
+  HIPC(upload(G.w_stream, stream, ctx->stream));
+  HIPC(upload(G.w_iso_diag, iso_diag, ctx->stream));
+  HIPC(upload(G.w_iso_invd, iso_invd, ctx->stream));
+  HIPC(G.w_ycur.alloc(std::max<size_t>(ci_row.size(), 1)));
   HIPC(hipStreamSynchronize(ctx->stream));
   G.host_block_row = block_row;
   G.host_block_rng = block_rng;
@@ -2187,7 +2157,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
       int64_t len = 1;
       for (int r = 0; r < n_ranks; ++r) len = std::max<int64_t>(len, block_row[(size_t)((r + 1) * nbl)] - block_row[(size_t)(r * nbl)]);
       G.w_stage_len = len;
-      HIPC(hipMalloc(&G.w_stage, sizeof(double) * (size_t)(len * n_ranks)));
+      HIPC(G.w_stage.alloc((size_t)(len * n_ranks)));
     }
   }
   G.w_y_slots = y_slots;
@@ -2288,16 +2258,16 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
     block_stage[(size_t)b + 1] = block_stage[(size_t)b] + ns;
     n_stages_max = std::max(n_stages_max, ns);
   }
-  free_sgs(L.sgs);
+  L.sgs = SgsPlan();
   L.sgs.n_blocks = n_blocks; L.sgs.n_stages_max = n_stages_max;
-  HIPC(hipMalloc(&L.sgs.stage_ptr, sizeof(int32_t) * std::max<size_t>(sp.size(), 1)));
-  HIPC(hipMalloc(&L.sgs.stage_rows, sizeof(int32_t) * rows.size()));
-  HIPC(hipMalloc(&L.sgs.block_row, sizeof(int32_t) * block_row.size()));
-  HIPC(hipMalloc(&L.sgs.block_stage, sizeof(int32_t) * block_stage.size()));
-  HIPC(hipMemcpyAsync(L.sgs.stage_ptr, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.stage_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.block_row, block_row.data(), sizeof(int32_t) * block_row.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.block_stage, block_stage.data(), sizeof(int32_t) * block_stage.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(L.sgs.stage_ptr.alloc(std::max<size_t>(sp.size(), 1)));
+  HIPC(L.sgs.stage_rows.alloc(rows.size()));
+  HIPC(L.sgs.block_row.alloc(block_row.size()));
+  HIPC(L.sgs.block_stage.alloc(block_stage.size()));
+  HIPC(hipMemcpyAsync(L.sgs.stage_ptr.get(), sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.sgs.stage_rows.get(), rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.sgs.block_row.get(), block_row.data(), sizeof(int32_t) * block_row.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.sgs.block_stage.get(), block_stage.data(), sizeof(int32_t) * block_stage.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   // (the generic sweep: one step per stage and direction; the wavefront plan replaces these with its own counts)
   L.sgs.host_block_row = block_row;
@@ -2320,7 +2290,7 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
     std::fprintf(stderr, "[gmg]   SSOR partition (%s): %d blocks, longest / mean: model %.2f, sub-steps %.2f\n",
                  explicit_rows ? "caller's" : ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED ? "balanced" : "equal rows", n_blocks,
                  c_sum > 0 ? c_max * n_blocks / c_sum : 1.0, s_sum > 0 ? (double)s_max * n_blocks / (double)s_sum : 1.0);
-    if (L.sgs.w_stage) {
+    if (L.sgs.w_stage.get()) {
       const int n_ranks = ctx->comm.n_ranks;
       std::fprintf(stderr, "[gmg]   SSOR all-gather: %d ranks x %lld doubles (largest piece) = %.2f MB moved per sweep for %.2f MB of y\n", n_ranks,
                    (long long)L.sgs.w_stage_len, 8e-6 * (double)L.sgs.w_stage_len * n_ranks, 8e-6 * (double)n);
@@ -2331,38 +2301,22 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
 
 // frees every operator / work vector but keeps the stream, the reduction scratch and the communicator
 void free_cg_ring(gmg_context *ctx) {
-  if (ctx->ring_shared[ctx->comm.rank]) {  // (collective: every rank frees its ring at the same point, gmg_set_level_matrix / gmg_reset / gmg_destroy)
-    comm_share_free(ctx->comm, ctx->ring_shared);
-    for (double *&p : ctx->cg_ring) p = nullptr;
-  }
-  for (double *&p : ctx->cg_ring)
-    if (p) { (void)hipFree(p); p = nullptr; }
+  // (collective: every rank frees its shared ring at the same point, gmg_set_level_matrix / gmg_reset / gmg_destroy)
+  if (ctx->ring_shared[ctx->comm.rank]) comm_share_free(ctx->comm, ctx->ring_shared);
+  for (int r = 0; r < kXRing; ++r) { ctx->cg_ring[r] = nullptr; ctx->cg_ring_own[r].reset(); }
   ctx->cg_ring_len = 0;
 }
 
 void free_locator(gmg_context *ctx) {
-  for (int32_t *p : {ctx->loc_node, ctx->loc_dofs})
-    if (p) (void)hipFree(p);
-  ctx->loc_node = ctx->loc_dofs = nullptr;
+  ctx->loc_node.reset(); ctx->loc_dofs.reset();
   ctx->loc = gmg_forces::Locator{};
   ctx->loc_max_dof = -1;
 }
 
 void release_operators(gmg_context *ctx) {
-  for (auto &L : ctx->lv) {
-    free_csr(L.A); free_csr(L.I); free_csr(L.It); free_csr(L.P); free_csr(L.Pt);
-    if (L.sol_full && L.sol_full != L.sol) (void)hipFree(L.sol_full);
-    if (L.def_full && L.def_full != L.def) (void)hipFree(L.def_full);
-    for (double *p : {L.sol, L.def, L.t, L.w1, L.w2, L.w3, L.invd})
-      if (p) (void)hipFree(p);
-    if (L.copy_g) (void)hipFree(L.copy_g);
-    if (L.copy_l) (void)hipFree(L.copy_l);
-    free_sgs(L.sgs);
-    L = Level();
-  }
-  free_csr(ctx->S);
-  for (double **p : {&ctx->sys_full_a, &ctx->sys_full_b, &ctx->S_invd, &ctx->S_tmp, &ctx->cg_g, &ctx->cg_d0, &ctx->cg_d1, &ctx->cg_h})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  for (auto &L : ctx->lv) L = Level();
+  ctx->S = DevCSR();
+  for (DevPtr<double> *p : {&ctx->sys_full_a, &ctx->sys_full_b, &ctx->S_invd, &ctx->S_tmp, &ctx->cg_g, &ctx->cg_d0, &ctx->cg_d1, &ctx->cg_h}) p->reset();
   free_cg_ring(ctx);
 }
 
@@ -2410,17 +2364,17 @@ int gmg_create(gmg_context **out, int device_id, int n_levels) {
   ctx->lv.resize((size_t)n_levels);
   auto bail = [&](int code) { gmg_destroy(ctx); return code; };
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipMalloc(&ctx->st, sizeof(CGState)) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipHostMalloc((void **)&ctx->st_host, 2 * sizeof(CGState), hipHostMallocDefault) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->st.alloc(1) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->st_host.alloc(2) != hipSuccess) return bail(GMG_ERR_HIP);
   for (auto &e : ctx->ev_chunk)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipMalloc(&ctx->part_a, sizeof(double) * 4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipMalloc(&ctx->part_b, sizeof(double) * 4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipMalloc(&ctx->scal_dev, sizeof(double) * 8) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipHostMalloc((void **)&ctx->scal_host, sizeof(double) * 8, hipHostMallocDefault) != hipSuccess) return bail(GMG_ERR_HIP);
-  if (hipHostMalloc((void **)&ctx->sgs_abort, sizeof(int), hipHostMallocDefault) != hipSuccess) return bail(GMG_ERR_HIP);
-  *ctx->sgs_abort = 0;
-  (void)hipMemsetAsync(ctx->st, 0, sizeof(CGState), ctx->stream);
+    if (e.create(hipEventDisableTiming) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->part_a.alloc(4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->part_b.alloc(4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->scal_dev.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->scal_host.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->sgs_abort.alloc(1) != hipSuccess) return bail(GMG_ERR_HIP);
+  *ctx->sgs_abort.get() = 0;
+  (void)hipMemsetAsync(ctx->st.get(), 0, sizeof(CGState), ctx->stream);
   // measurement scripts reach the diagnostic options of a context they do not create themselves through
   // GMG_OPTIONS="key=value,key=value" (same keys as gmg_set_option); unknown keys fail the creation
   if (const char *env = std::getenv("GMG_OPTIONS")) {
@@ -2447,22 +2401,10 @@ int gmg_destroy(gmg_context *ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   release_operators(ctx);  // (before the communicator: the shared direction vectors are unmapped collectively)
-  if (ctx->peer_push_cnt) (void)hipFree(ctx->peer_push_cnt);
-  if (ctx->dens_dev) (void)hipFree(ctx->dens_dev);
-  free_locator(ctx);
   comm_destroy(ctx->comm);
-  for (double *p : {ctx->part_a, ctx->part_b, ctx->scal_dev})
-    if (p) (void)hipFree(p);
-  if (ctx->st) (void)hipFree(ctx->st);
-  if (ctx->st_host) (void)hipHostFree(ctx->st_host);
-  for (auto &e : ctx->ev_chunk)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->scal_host) (void)hipHostFree(ctx->scal_host);
-  if (ctx->sgs_abort) (void)hipHostFree(ctx->sgs_abort);
-  for (auto *v : {&ctx->ev_a, &ctx->ev_b, &ctx->ev_c, &ctx->ev_d, &ctx->ev_e, &ctx->ev_f})
-    for (hipEvent_t e : *v) (void)hipEventDestroy(e);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  const hipStream_t stream = ctx->stream;
+  delete ctx;  // every other allocation and event: by its owner
+  if (stream) (void)hipStreamDestroy(stream);
   return GMG_OK;
 }
 
@@ -2473,7 +2415,8 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   release_operators(ctx);
   free_locator(ctx);
   ctx->n_levels = n_levels;
-  ctx->lv.assign((size_t)n_levels, Level());
+  ctx->lv.clear();
+  ctx->lv.resize((size_t)n_levels);
   ctx->last_coarse_iters = 0;
   ctx->stats = gmg_stats{};
   ctx->ev3_used = 0;
@@ -2493,12 +2436,12 @@ int gmg_set_system_matrix(gmg_context *ctx, int64_t n_rows, int64_t n_cols, cons
   if (!ctx) return GMG_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
   CHK(upload_csr(ctx, ctx->S, n_rows, n_cols, rowptr, col, val));
-  CHK(setup_diag(ctx, n_rows, rowptr, col, val, &ctx->S_invd, nullptr));
-  CHK(alloc_vec(ctx, &ctx->S_tmp, n_cols));
+  CHK(setup_diag(ctx, n_rows, rowptr, col, val, ctx->S_invd, nullptr));
+  CHK(alloc_vec(ctx, ctx->S_tmp, n_cols));
   if (ctx->dist) {
     const int64_t padded = part_chunk(ctx->sys_global, ctx->comm.n_ranks) * ctx->comm.n_ranks;
-    CHK(alloc_vec(ctx, &ctx->sys_full_a, padded));
-    CHK(alloc_vec(ctx, &ctx->sys_full_b, padded));
+    CHK(alloc_vec(ctx, ctx->sys_full_a, padded));
+    CHK(alloc_vec(ctx, ctx->sys_full_b, padded));
     int64_t b, e;
     part_range(ctx->sys_global, ctx->comm.rank, ctx->comm.n_ranks, &b, &e);
     if (e - b != n_rows) return fail(ctx, GMG_ERR_INVALID, "system matrix rows do not match the canonical partition");
@@ -2511,21 +2454,21 @@ static int finish_level(gmg_context *ctx, int level, int64_t n_rows, int64_t n_c
   Level &L = ctx->lv[(size_t)level];
   L.n = n_rows;
   L.n_vec = n_cols;
-  for (double **p : {&L.sol, &L.def, &L.t, &L.w1, &L.w2, &L.w3}) CHK(alloc_vec(ctx, p, n_cols));
+  for (DevPtr<double> *p : {&L.sol, &L.def, &L.t, &L.w1, &L.w2, &L.w3}) CHK(alloc_vec(ctx, *p, n_cols));
   if (level == 0) {
     if (l0_partitioned(ctx)) {
       const int64_t padded = part_chunk(ctx->l0_global, ctx->comm.n_ranks) * ctx->comm.n_ranks;
-      if (L.sol_full && L.sol_full != L.sol) (void)hipFree(L.sol_full);
-      if (L.def_full && L.def_full != L.def) (void)hipFree(L.def_full);
-      L.sol_full = L.def_full = nullptr;
-      CHK(alloc_vec(ctx, &L.sol_full, padded));
-      CHK(alloc_vec(ctx, &L.def_full, padded));
+      CHK(alloc_vec(ctx, L.sol_full_own, padded));
+      CHK(alloc_vec(ctx, L.def_full_own, padded));
+      L.sol_full = L.sol_full_own.get();
+      L.def_full = L.def_full_own.get();
     } else {
-      L.sol_full = L.sol;
-      L.def_full = L.def;
+      L.sol_full_own.reset(); L.def_full_own.reset();
+      L.sol_full = L.sol.get();
+      L.def_full = L.def.get();
     }
     ctx->cg_n = n_cols;
-    for (double **p : {&ctx->cg_g, &ctx->cg_d0, &ctx->cg_d1, &ctx->cg_h}) CHK(alloc_vec(ctx, p, n_cols));
+    for (DevPtr<double> *p : {&ctx->cg_g, &ctx->cg_d0, &ctx->cg_d1, &ctx->cg_h}) CHK(alloc_vec(ctx, *p, n_cols));
     free_cg_ring(ctx);  // sized for the previous level 0
     ctx->stats.spmv0_rows = n_rows;
     ctx->stats.spmv0_nnz = nnz;
@@ -2565,7 +2508,7 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
   CHK(upload_csr(ctx, L.A, n_rows, n_cols, rowptr, col, val, level > 0));
-  CHK(setup_diag(ctx, n_rows, rowptr, col, val, &L.invd, &L.cheb_lmax));
+  CHK(setup_diag(ctx, n_rows, rowptr, col, val, L.invd, &L.cheb_lmax));
   if (level > 0) {
     L.n = n_rows;  // (the SGS plan reads it)
     CHK(setup_sgs(ctx, L, n_rows, rowptr, col, val, explicit_rows));
@@ -2593,10 +2536,7 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[0];
   DevCSR &m = L.A;
-  HaloPlan keep = m.halo;
-  m.halo = HaloPlan();
-  free_csr(m);
-  m.halo = keep;
+  reset_keep_halo(m);
   // ---- class table
   const int64_t dims[3] = {nx, ny, nz};
   auto rep = [&](int t, int64_t mdim) -> int64_t { return t == 0 ? 0 : t == 1 ? 1 : t == 2 ? 2 : t == 3 ? mdim - 2 : mdim - 1; };
@@ -2649,18 +2589,16 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
     }
     cmap.cls[cls] = (uint8_t)found;
   }
-  HIPC(hipMalloc(&m.lat_rowcls, (size_t)n + 64));
-  HIPC(hipMalloc(&m.lat_ctab, sizeof(double) * utab.size()));
-  HIPC(hipMemcpyAsync(m.lat_ctab, utab.data(), sizeof(double) * utab.size(), hipMemcpyHostToDevice, ctx->stream));
-  CHK(alloc_vec(ctx, &L.invd, n));
-  hipLaunchKernelGGL(lattice_rowclass_kernel, dim3(grid_for(n)), dim3(kThreads), 0, ctx->stream, m.lat_rowcls, L.invd, (const double *)m.lat_ctab, cmap, (int)nx, (int)ny, (int)nz);
+  HIPC(m.lat_rowcls.alloc_bytes((size_t)n + 64));
+  HIPC(m.lat_ctab.alloc(utab.size()));
+  HIPC(hipMemcpyAsync(m.lat_ctab.get(), utab.data(), sizeof(double) * utab.size(), hipMemcpyHostToDevice, ctx->stream));
+  CHK(alloc_vec(ctx, L.invd, n));
+  hipLaunchKernelGGL(lattice_rowclass_kernel, dim3(grid_for(n)), dim3(kThreads), 0, ctx->stream, m.lat_rowcls.get(), L.invd.get(), (const double *)m.lat_ctab.get(), cmap, (int)nx, (int)ny, (int)nz);
   CHK(launch_status(ctx));
   HIPC(hipStreamSynchronize(ctx->stream));  // (utab dies with this scope)
   L.cheb_lmax = lmax;
   m.n_rows = m.n_cols = n;
   m.nnz = (3 * nx - 2) * (3 * ny - 2) * (3 * nz - 2);
-  m.valid = true;
-  m.lattice = m.lat_only = true;
   m.lat_classes = n_unique;
   m.lat_nx = (int)nx; m.lat_nxy = (int)nxy; m.lat_W = (int)nxy;
   m.lat_R0 = (int)(reach + 2); m.lat_R1 = (int)(n - reach);
@@ -2673,6 +2611,8 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   m.lat_grid = lattice_grid(ctx, m, (size_t)m.lat_n_gen);
   m.lat_grid += m.lat_fast_blocks;
   if (m.lat_grid > kMaxPartials) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_set_level_matrix_lattice: grid exceeds the reduction partials");
+  m.valid = true;
+  m.lattice = m.lat_only = true;
   if (ctx->debug_upload)
     std::fprintf(stderr, "[gmg] lattice operator %lld x %lld x %lld formed on the device: %d columns x %d steps, %d segments per XCD slab, grid %d, %d edge chunks\n", (long long)nx,
                  (long long)ny, (long long)nz, m.lat_C, m.lat_K, m.lat_S, m.lat_grid, m.lat_n_gen);
@@ -2694,7 +2634,7 @@ int gmg_set_edge_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_c
     rp[(size_t)i + 1] = (int64_t)c.size();
   }
   L.has_I = !c.empty();
-  if (!L.has_I) { free_csr(L.I); free_csr(L.It); return GMG_OK; }
+  if (!L.has_I) { L.I = DevCSR(); L.It = DevCSR(); return GMG_OK; }
   CHK(upload_csr(ctx, L.I, n_rows, n_cols, rp.data(), c.data(), v.data()));
   std::vector<int64_t> trp;
   std::vector<int32_t> tcol;
@@ -2729,60 +2669,50 @@ int gmg_build_transfer(gmg_context *ctx, int level, int dim, int64_t n_coarse, c
   if (n_coarse >= ((int64_t)1 << 30) || n_fine >= ((int64_t)1 << 28)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_build_transfer: level too large for 32-bit row pointers");
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
-  for (DevCSR *m : {&L.P, &L.Pt}) {
-    HaloPlan keep = m->halo;
-    m->halo = HaloPlan();
-    free_csr(*m);
-    m->halo = keep;
-  }
-  unsigned long long *d_fv = nullptr, *d_cv = nullptr, *d_fk = nullptr, *d_ck = nullptr;
-  uint8_t *d_cb = nullptr;
-  int32_t *d_fd = nullptr, *d_cd = nullptr;
-  auto cleanup = [&]() {
-    for (void *q : {(void *)d_fv, (void *)d_cv, (void *)d_fk, (void *)d_ck, (void *)d_cb, (void *)d_fd, (void *)d_cd})
-      if (q) (void)hipFree(q);
-  };
+  for (DevCSR *m : {&L.P, &L.Pt}) reset_keep_halo(*m);
+  DevPtr<unsigned long long> d_fv, d_cv, d_fk, d_ck;
+  DevPtr<uint8_t> d_cb;
+  DevPtr<int32_t> d_fd, d_cd;
+  Event e0, e1;
   auto table_size = [](int64_t n) { unsigned long long t = 1024; while ((int64_t)t < 2 * n) t <<= 1; return t; };
   const unsigned long long ft = table_size(n_fine), ct = table_size(n_coarse);
-#define TRC(call) do { if ((call) != hipSuccess) { cleanup(); return fail(ctx, GMG_ERR_HIP, "gmg_build_transfer: " #call " failed"); } } while (0)
-  TRC(hipMalloc(&d_fv, sizeof(uint64_t) * (size_t)n_fine));
-  TRC(hipMalloc(&d_cv, sizeof(uint64_t) * (size_t)n_coarse));
-  TRC(hipMalloc(&d_cb, (size_t)n_coarse));
-  TRC(hipMalloc(&d_fk, sizeof(uint64_t) * ft));
-  TRC(hipMalloc(&d_ck, sizeof(uint64_t) * ct));
-  TRC(hipMalloc(&d_fd, sizeof(int32_t) * ft));
-  TRC(hipMalloc(&d_cd, sizeof(int32_t) * ct));
-  TRC(hipMemcpyAsync(d_fv, fine_vertex, sizeof(uint64_t) * (size_t)n_fine, hipMemcpyHostToDevice, ctx->stream));
-  TRC(hipMemcpyAsync(d_cv, coarse_vertex, sizeof(uint64_t) * (size_t)n_coarse, hipMemcpyHostToDevice, ctx->stream));
-  TRC(hipMemcpyAsync(d_cb, coarse_boundary, (size_t)n_coarse, hipMemcpyHostToDevice, ctx->stream));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  TRC(hipEventCreate(&e0));
-  TRC(hipEventCreate(&e1));
-  TRC(hipEventRecord(e0, ctx->stream));
-  TRC(hipMemsetAsync(d_fk, 0xff, sizeof(uint64_t) * ft, ctx->stream));
-  TRC(hipMemsetAsync(d_ck, 0xff, sizeof(uint64_t) * ct, ctx->stream));
-  hipLaunchKernelGGL(tr_table_build_kernel, dim3(grid_for(n_fine)), dim3(kThreads), 0, ctx->stream, (const unsigned long long *)d_fv, n_fine, d_fk, d_fd, ft - 1);
-  hipLaunchKernelGGL(tr_table_build_kernel, dim3(grid_for(n_coarse)), dim3(kThreads), 0, ctx->stream, (const unsigned long long *)d_cv, n_coarse, d_ck, d_cd, ct - 1);
+  HIPC(d_fv.alloc((size_t)n_fine));
+  HIPC(d_cv.alloc((size_t)n_coarse));
+  HIPC(d_cb.alloc((size_t)n_coarse));
+  HIPC(d_fk.alloc(ft));
+  HIPC(d_ck.alloc(ct));
+  HIPC(d_fd.alloc(ft));
+  HIPC(d_cd.alloc(ct));
+  HIPC(hipMemcpyAsync(d_fv.get(), fine_vertex, sizeof(uint64_t) * (size_t)n_fine, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_cv.get(), coarse_vertex, sizeof(uint64_t) * (size_t)n_coarse, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_cb.get(), coarse_boundary, (size_t)n_coarse, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(hipMemsetAsync(d_fk.get(), 0xff, sizeof(uint64_t) * ft, ctx->stream));
+  HIPC(hipMemsetAsync(d_ck.get(), 0xff, sizeof(uint64_t) * ct, ctx->stream));
+  hipLaunchKernelGGL(tr_table_build_kernel, dim3(grid_for(n_fine)), dim3(kThreads), 0, ctx->stream, (const unsigned long long *)d_fv.get(), n_fine, d_fk.get(), d_fd.get(), ft - 1);
+  hipLaunchKernelGGL(tr_table_build_kernel, dim3(grid_for(n_coarse)), dim3(kThreads), 0, ctx->stream, (const unsigned long long *)d_cv.get(), n_coarse, d_ck.get(), d_cd.get(), ct - 1);
   TransferArgs a{};
-  a.fine_vertex = d_fv; a.coarse_vertex = d_cv; a.coarse_boundary = d_cb; a.n_fine = n_fine; a.n_coarse = n_coarse;
-  a.fkeys = d_fk; a.ckeys = d_ck; a.fdof = d_fd; a.cdof = d_cd; a.fmask = ft - 1; a.cmask = ct - 1; a.dim = dim; a.half = fine_spacing;
+  a.fine_vertex = d_fv.get(); a.coarse_vertex = d_cv.get(); a.coarse_boundary = d_cb.get(); a.n_fine = n_fine; a.n_coarse = n_coarse;
+  a.fkeys = d_fk.get(); a.ckeys = d_ck.get(); a.fdof = d_fd.get(); a.cdof = d_cd.get(); a.fmask = ft - 1; a.cmask = ct - 1; a.dim = dim; a.half = fine_spacing;
   // one operator after the other: count, scan, allocate, fill
   auto build = [&](DevCSR &m, bool transposed) -> int {
     const int64_t nr = transposed ? n_coarse : n_fine, nc = transposed ? n_fine : n_coarse;
-    HIPC(hipMalloc(&m.rowptr, sizeof(int32_t) * ((size_t)nr + 1)));
-    a.rowptr = m.rowptr;
+    HIPC(m.rowptr.alloc(((size_t)nr + 1)));
+    a.rowptr = m.rowptr.get();
     if (transposed) hipLaunchKernelGGL(tr_restriction_kernel<false>, dim3(grid_for(nr)), dim3(kThreads), 0, ctx->stream, a);
     else hipLaunchKernelGGL(tr_prolongation_kernel<false>, dim3(grid_for(nr)), dim3(kThreads), 0, ctx->stream, a);
-    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr, nr);
+    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr.get(), nr);
     int32_t nnz = 0;
-    HIPC(hipMemcpyAsync(&nnz, m.rowptr + nr, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(&nnz, m.rowptr.get() + nr, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     const size_t pad = 8;
-    HIPC(hipMalloc(&m.col, sizeof(int32_t) * ((size_t)nnz + pad)));
-    HIPC(hipMalloc(&m.val, sizeof(double) * ((size_t)nnz + pad)));
-    HIPC(hipMemsetAsync(m.col + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
-    HIPC(hipMemsetAsync(m.val + nnz, 0, sizeof(double) * pad, ctx->stream));
-    a.col = m.col; a.val = m.val;
+    HIPC(m.col.alloc(((size_t)nnz + pad)));
+    HIPC(m.val.alloc(((size_t)nnz + pad)));
+    HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
+    HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
+    a.col = m.col.get(); a.val = m.val.get();
     if (transposed) hipLaunchKernelGGL(tr_restriction_kernel<true>, dim3(grid_for(nr)), dim3(kThreads), 0, ctx->stream, a);
     else hipLaunchKernelGGL(tr_prolongation_kernel<true>, dim3(grid_for(nr)), dim3(kThreads), 0, ctx->stream, a);
     m.n_rows = nr; m.n_cols = nc; m.nnz = nnz;
@@ -2790,27 +2720,24 @@ int gmg_build_transfer(gmg_context *ctx, int level, int dim, int64_t n_coarse, c
   };
   int rc = build(L.P, false);
   if (rc == GMG_OK) rc = build(L.Pt, true);
-  if (rc == GMG_OK && hipEventRecord(e1, ctx->stream) != hipSuccess) rc = GMG_ERR_HIP;
+  if (rc == GMG_OK && hipEventRecord(e1.get(), ctx->stream) != hipSuccess) rc = GMG_ERR_HIP;
   // the row-window tiling of the two operators (host: a pass over the row pointers)
   for (DevCSR *m : {&L.P, &L.Pt}) {
     if (rc != GMG_OK) break;
     std::vector<int32_t> rp((size_t)m->n_rows + 1);
-    if (hipMemcpyAsync(rp.data(), m->rowptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+    if (hipMemcpyAsync(rp.data(), m->rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = GMG_ERR_HIP; break; }
     const std::vector<int32_t> tiles = window_tiles(rp.data(), m->n_rows);
     m->n_tiles = (int)tiles.size() - 1;
     m->tiles_per_xcd = (m->n_tiles + 7) / 8;
     m->grid = 8 * std::min(kMaxPartials / 8, std::max(1, m->tiles_per_xcd));
-    if (hipMalloc(&m->tile_row, sizeof(int32_t) * tiles.size()) != hipSuccess ||
-        hipMemcpyAsync(m->tile_row, tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+    if (m->tile_row.alloc(tiles.size()) != hipSuccess ||
+        hipMemcpyAsync(m->tile_row.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = GMG_ERR_HIP; break; }
     m->valid = true;
   }
   float ms = 0.f;
-  if (rc == GMG_OK && hipEventElapsedTime(&ms, e0, e1) != hipSuccess) ms = 0.f;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-#undef TRC
-  cleanup();
+  if (rc == GMG_OK && hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
   if (rc != GMG_OK) { if (ctx->err.empty()) ctx->err = "gmg_build_transfer failed"; return rc; }
   L.has_P = true;
   ctx->stats.build_matrices_ms += ms;
@@ -2825,16 +2752,16 @@ int gmg_build_transfer(gmg_context *ctx, int level, int dim, int64_t n_coarse, c
 int gmg_get_transfer(gmg_context *ctx, int level, int transposed, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
   if (!ctx || level < 0 || level >= ctx->n_levels - 1) return GMG_ERR_INVALID;
   const DevCSR &m = transposed ? ctx->lv[(size_t)level].Pt : ctx->lv[(size_t)level].P;
-  if (!m.valid || !m.rowptr || !m.col || !m.val) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_transfer: no CSR copy of this operator on the device");
+  if (!m.valid || !m.rowptr.get() || !m.col.get() || !m.val.get()) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_transfer: no CSR copy of this operator on the device");
   if (n_rows) *n_rows = m.n_rows;
   if (n_cols) *n_cols = m.n_cols;
   if (nnz) *nnz = m.nnz;
   if (!rowptr) return GMG_OK;
   std::vector<int32_t> rp((size_t)m.n_rows + 1);
-  HIPC(hipMemcpyAsync(rp.data(), m.rowptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
   if (m.nnz) {
-    HIPC(hipMemcpyAsync(col, m.col, sizeof(int32_t) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(hipMemcpyAsync(val, m.val, sizeof(double) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(col, m.col.get(), sizeof(int32_t) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(val, m.val.get(), sizeof(double) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPC(hipStreamSynchronize(ctx->stream));
   for (size_t i = 0; i < rp.size(); ++i) rowptr[i] = rp[i];
@@ -2845,14 +2772,13 @@ int gmg_set_copy_indices(gmg_context *ctx, int level, int64_t n, const int32_t *
   if (!ctx || level < 0 || level >= ctx->n_levels || n < 0) return GMG_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
-  if (L.copy_g) { (void)hipFree(L.copy_g); L.copy_g = nullptr; }
-  if (L.copy_l) { (void)hipFree(L.copy_l); L.copy_l = nullptr; }
+  L.copy_g.reset(); L.copy_l.reset();
   L.n_copy = n;
   if (n == 0) return GMG_OK;
-  HIPC(hipMalloc(&L.copy_g, sizeof(int32_t) * (size_t)n));
-  HIPC(hipMalloc(&L.copy_l, sizeof(int32_t) * (size_t)n));
-  HIPC(hipMemcpyAsync(L.copy_g, global_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.copy_l, level_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(L.copy_g.alloc((size_t)n));
+  HIPC(L.copy_l.alloc((size_t)n));
+  HIPC(hipMemcpyAsync(L.copy_g.get(), global_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.copy_l.get(), level_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   return GMG_OK;
 }
@@ -2874,12 +2800,16 @@ int gmg_set_coarse(gmg_context *ctx, double abs_tol, int max_it) {
 }
 
 // ---- vectors ----
+// (gmg_vec_alloc hands the allocation to the caller over the C ABI, gmg_vec_free takes it back: no owner in between)
 
 int gmg_vec_alloc(gmg_context *ctx, int64_t n, double **dptr) {
   if (!ctx || !dptr || n < 0) return GMG_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
   *dptr = nullptr;
-  return alloc_vec(ctx, dptr, n);
+  DevPtr<double> v;
+  CHK(alloc_vec(ctx, v, n));
+  *dptr = v.release();  // (the caller's from here on, until gmg_vec_free)
+  return GMG_OK;
 }
 int gmg_vec_free(gmg_context *ctx, double *dptr) {
   if (!ctx) return GMG_ERR_INVALID;
@@ -2925,26 +2855,26 @@ int gmg_vec_dot(gmg_context *ctx, const double *x, const double *y, int64_t n, d
 int gmg_vec_norms(gmg_context *ctx, const double *x, int64_t n, double *l1, double *l2, double *linf) {
   if (!ctx || n < 0) return GMG_ERR_INVALID;
   const int g = grid_for(n);
-  hipLaunchKernelGGL(norms_partial_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, x, n, ctx->part_a);
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a, g, 4, 4u,
-                     ctx->scal_dev);
+  hipLaunchKernelGGL(norms_partial_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, x, n, ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), g, 4, 4u,
+                     ctx->scal_dev.get());
   if (ctx->comm.n_ranks > 1) {
-    if (allreduce_sum(ctx->comm, ctx->scal_dev, 2, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
-    if (allreduce_max(ctx->comm, ctx->scal_dev + 2, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
-    if (allreduce_sum(ctx->comm, ctx->scal_dev + 3, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
+    if (allreduce_sum(ctx->comm, ctx->scal_dev.get(), 2, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
+    if (allreduce_max(ctx->comm, ctx->scal_dev.get() + 2, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
+    if (allreduce_sum(ctx->comm, ctx->scal_dev.get() + 3, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
   }
   CHK(launch_status(ctx));
   CHK(fetch_scalars(ctx, 4));
-  if (l1) *l1 = ctx->scal_host[0];
-  if (l2) *l2 = std::sqrt(ctx->scal_host[1]);
-  if (linf) *linf = ctx->scal_host[2];
+  if (l1) *l1 = ctx->scal_host.get()[0];
+  if (l2) *l2 = std::sqrt(ctx->scal_host.get()[1]);
+  if (linf) *linf = ctx->scal_host.get()[2];
   return GMG_OK;
 }
 int gmg_vec_all_zero(gmg_context *ctx, const double *x, int64_t n, int *out) {
   if (!ctx || !out) return GMG_ERR_INVALID;
   double a, b, c;
   CHK(gmg_vec_norms(ctx, x, n, &a, &b, &c));
-  *out = (ctx->scal_host[3] == 0.0) ? 1 : 0;
+  *out = (ctx->scal_host.get()[3] == 0.0) ? 1 : 0;
   return GMG_OK;
 }
 
@@ -2956,7 +2886,7 @@ int gmg_spmv(gmg_context *ctx, int which, double *dst, const double *src) {
   if (!m || !m->valid) return fail(ctx, GMG_ERR_INVALID, "gmg_spmv: operator not set");
   if (m->halo.active) {
     // the caller's src holds owned entries only: stage it in a buffer with a ghost tail
-    double *tmp = (which == GMG_SYSTEM) ? ctx->S_tmp : ctx->lv[(size_t)which].w3;
+    double *tmp = (which == GMG_SYSTEM) ? ctx->S_tmp.get() : ctx->lv[(size_t)which].w3.get();
     HIPC(hipMemcpyAsync(tmp, src, sizeof(double) * (size_t)m->n_rows, hipMemcpyDeviceToDevice, ctx->stream));
     CHK(import_ghosts(ctx, *m, tmp));
     return spmv(ctx, *m, kStore, tmp, dst);
@@ -2972,7 +2902,7 @@ int gmg_precondition(gmg_context *ctx, double *dst, const double *src) {
 int gmg_precondition_jacobi(gmg_context *ctx, double omega, double *dst, const double *src) {
   if (!ctx || !ctx->S.valid) return GMG_ERR_INVALID;
   hipLaunchKernelGGL(vec_scale_mul_kernel, dim3(grid_for(ctx->S.n_rows)), dim3(kThreads), 0, ctx->stream, dst, omega, src,
-                     (const double *)ctx->S_invd, ctx->S.n_rows);
+                     (const double *)ctx->S_invd.get(), ctx->S.n_rows);
   RETURN_LAUNCHED(ctx);
 }
 
@@ -2981,9 +2911,9 @@ int gmg_coarse_solve(gmg_context *ctx, double *dst, const double *src, int *iter
   Level &L0 = ctx->lv[0];
   if (!L0.A.valid) return fail(ctx, GMG_ERR_INVALID, "level-0 matrix not set");
   // run on the level's own vectors (ghost tails), then hand the owned part back
-  HIPC(hipMemcpyAsync(L0.def, src, sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
-  int rc = coarse_solve(ctx, L0.sol, L0.def, iterations, residual);
-  HIPC(hipMemcpyAsync(dst, L0.sol, sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L0.def.get(), src, sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
+  int rc = coarse_solve(ctx, L0.sol.get(), L0.def.get(), iterations, residual);
+  HIPC(hipMemcpyAsync(dst, L0.sol.get(), sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   return rc;
 }
@@ -2992,10 +2922,10 @@ int gmg_smoother_step(gmg_context *ctx, int level, double *u, const double *rhs,
   if (!ctx || level < 0 || level >= ctx->n_levels) return GMG_ERR_INVALID;
   Level &L = ctx->lv[(size_t)level];
   if (!L.A.valid) return fail(ctx, GMG_ERR_INVALID, "level matrix not set");
-  HIPC(hipMemcpyAsync(L.sol, u, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.def, rhs, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
-  CHK(smooth_level(ctx, level, &L.sol, L.def, from_zero != 0, &L.w1));
-  HIPC(hipMemcpyAsync(u, L.sol, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.sol.get(), u, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(L.def.get(), rhs, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
+  CHK(smooth_level(ctx, level, L.sol, L.def.get(), from_zero != 0, L.w1));
+  HIPC(hipMemcpyAsync(u, L.sol.get(), sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
   return GMG_OK;
 }
 
@@ -3004,9 +2934,9 @@ int gmg_prolongate(gmg_context *ctx, int level, double *dst_fine, const double *
   Level &L = ctx->lv[(size_t)level];
   if (!L.has_P) return fail(ctx, GMG_ERR_INVALID, "prolongation not set");
   if (L.P.halo.active) {
-    HIPC(hipMemcpyAsync(L.w3, src_coarse, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
-    CHK(import_ghosts(ctx, L.P, L.w3));
-    return spmv(ctx, L.P, kStore, L.w3, dst_fine);
+    HIPC(hipMemcpyAsync(L.w3.get(), src_coarse, sizeof(double) * (size_t)L.n, hipMemcpyDeviceToDevice, ctx->stream));
+    CHK(import_ghosts(ctx, L.P, L.w3.get()));
+    return spmv(ctx, L.P, kStore, L.w3.get(), dst_fine);
   }
   return spmv(ctx, L.P, kStore, src_coarse, dst_fine);
 }
@@ -3017,9 +2947,9 @@ int gmg_restrict_and_add(gmg_context *ctx, int level, double *dst_coarse, const 
   if (!L.has_P) return fail(ctx, GMG_ERR_INVALID, "prolongation not set");
   if (L.Pt.halo.active) {
     Level &F = ctx->lv[(size_t)level + 1];
-    HIPC(hipMemcpyAsync(F.w3, src_fine, sizeof(double) * (size_t)F.n, hipMemcpyDeviceToDevice, ctx->stream));
-    CHK(import_ghosts(ctx, L.Pt, F.w3));
-    return spmv(ctx, L.Pt, kStore, F.w3, dst_coarse, dst_coarse);
+    HIPC(hipMemcpyAsync(F.w3.get(), src_fine, sizeof(double) * (size_t)F.n, hipMemcpyDeviceToDevice, ctx->stream));
+    CHK(import_ghosts(ctx, L.Pt, F.w3.get()));
+    return spmv(ctx, L.Pt, kStore, F.w3.get(), dst_coarse, dst_coarse);
   }
   return spmv(ctx, L.Pt, kStore, src_fine, dst_coarse, dst_coarse);
 }
@@ -3029,11 +2959,11 @@ int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, i
                  double *starting_value, double *convergence_value) {
   if (!ctx || !ctx->S.valid) return GMG_ERR_INVALID;
   const int64_t n = ctx->S.n_rows;
-  double *g = nullptr, *d = nullptr, *h = nullptr;
-  CHK(alloc_vec(ctx, &g, ctx->S.n_cols));
-  CHK(alloc_vec(ctx, &d, ctx->S.n_cols));
-  CHK(alloc_vec(ctx, &h, ctx->S.n_cols));
-  auto cleanup = [&]() { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(g); (void)hipFree(d); (void)hipFree(h); };
+  DevPtr<double> g_own, d_own, h_own;
+  CHK(alloc_vec(ctx, g_own, ctx->S.n_cols));
+  CHK(alloc_vec(ctx, d_own, ctx->S.n_cols));
+  CHK(alloc_vec(ctx, h_own, ctx->S.n_cols));
+  double *const g = g_own.get(), *const d = d_own.get(), *const h = h_own.get();
   auto apply_precond = [&](double *dst, const double *src) -> int {
     if (precond == GMG_PRECOND_GMG) return vcycle(ctx, dst, src);
     if (precond == GMG_PRECOND_JACOBI) return gmg_precondition_jacobi(ctx, 0.6, dst, src);
@@ -3091,7 +3021,7 @@ int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, i
   } while (0);
   if (iterations) *iterations = it;
   if (convergence_value) *convergence_value = res;
-  cleanup();
+  (void)hipStreamSynchronize(ctx->stream);  // (the vectors are freed on return)
   return rc;
 }
 
@@ -3112,55 +3042,38 @@ int gmg_charge_density(gmg_context *ctx, int64_t n_cells, const double *cell_lo,
   const double *lo = B.lo;
   const int *bn = B.n;
   const std::vector<int32_t> &bptr = B.ptr, &bitems = B.items;
-  double *d_lo = nullptr, *d_h = nullptr, *d_root = nullptr, *d_xyz = nullptr, *d_q = nullptr, *d_qp = nullptr, *d_dens = nullptr;
-  int32_t *d_bptr = nullptr, *d_bitems = nullptr;
-  auto cleanup = [&]() {
-    for (void *p : {(void *)d_lo, (void *)d_h, (void *)d_root, (void *)d_xyz, (void *)d_q, (void *)d_qp, (void *)d_dens, (void *)d_bptr, (void *)d_bitems})
-      if (p) (void)hipFree(p);
-  };
-#define UP(dst, src, bytes)                                                                   \
-  do {                                                                                        \
-    if (hipMalloc(&dst, std::max<size_t>((bytes), 8)) != hipSuccess ||                         \
-        ((bytes) && hipMemcpyAsync(dst, src, (bytes), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)) { \
-      cleanup();                                                                              \
-      return fail(ctx, GMG_ERR_HIP, "gmg_charge_density: upload failed");                     \
-    }                                                                                         \
-  } while (0)
-  UP(d_lo, cell_lo, sizeof(double) * 3 * (size_t)n_cells);
-  UP(d_h, cell_h, sizeof(double) * (size_t)n_cells);
-  UP(d_root, root_lo, sizeof(double) * 3 * (size_t)n_cells);
-  UP(d_xyz, atom_xyz, sizeof(double) * 3 * (size_t)n_atoms);
-  UP(d_q, atom_q, sizeof(double) * (size_t)n_atoms);
-  UP(d_qp, quadrature_points, sizeof(double) * 3 * (size_t)nq);
-  UP(d_bptr, bptr.data(), sizeof(int32_t) * bptr.size());
-  UP(d_bitems, bitems.data(), sizeof(int32_t) * bitems.size());
-#undef UP
-  if (hipMalloc(&d_dens, sizeof(double) * (size_t)n_cells * (size_t)nq) != hipSuccess) { cleanup(); return fail(ctx, GMG_ERR_HIP, "gmg_charge_density: out of memory"); }
-  if (ctx->dens_dev) { (void)hipFree(ctx->dens_dev); ctx->dens_dev = nullptr; ctx->dens_cells = 0; ctx->dens_nq = 0; }
-  a.cell_lo = d_lo; a.cell_h = d_h; a.root_lo = d_root; a.root_h = root_h;
-  a.atom_xyz = d_xyz; a.atom_q = d_q; a.n_atoms = (int)n_atoms;
+  DevPtr<double> d_lo, d_h, d_root, d_xyz, d_q, d_qp, d_dens;
+  DevPtr<int32_t> d_bptr, d_bitems;
+  // (allocations of at least 8 bytes: two int32_t)
+  if (upload(d_lo, cell_lo, 3 * (size_t)n_cells, ctx->stream) != hipSuccess || upload(d_h, cell_h, (size_t)n_cells, ctx->stream) != hipSuccess ||
+      upload(d_root, root_lo, 3 * (size_t)n_cells, ctx->stream) != hipSuccess || upload(d_xyz, atom_xyz, 3 * (size_t)n_atoms, ctx->stream) != hipSuccess ||
+      upload(d_q, atom_q, (size_t)n_atoms, ctx->stream) != hipSuccess || upload(d_qp, quadrature_points, 3 * (size_t)nq, ctx->stream) != hipSuccess ||
+      upload(d_bptr, bptr, ctx->stream, 2) != hipSuccess || upload(d_bitems, bitems, ctx->stream, 2) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, "gmg_charge_density: upload failed");
+  if (d_dens.alloc((size_t)n_cells * (size_t)nq) != hipSuccess) return fail(ctx, GMG_ERR_HIP, "gmg_charge_density: out of memory");
+  ctx->dens_dev.reset(); ctx->dens_cells = 0; ctx->dens_nq = 0;
+  a.cell_lo = d_lo.get(); a.cell_h = d_h.get(); a.root_lo = d_root.get(); a.root_h = root_h;
+  a.atom_xyz = d_xyz.get(); a.atom_q = d_q.get(); a.n_atoms = (int)n_atoms;
   a.bin_lo0 = lo[0]; a.bin_lo1 = lo[1]; a.bin_lo2 = lo[2]; a.bin_size = bs;
   a.bin_n0 = bn[0]; a.bin_n1 = bn[1]; a.bin_n2 = bn[2];
-  a.bin_ptr = d_bptr; a.bin_items = d_bitems;
+  a.bin_ptr = d_bptr.get(); a.bin_items = d_bitems.get();
   a.cutoff = cutoff; a.r_c = r_c; a.use_lists = use_lists;
-  a.qp = d_qp; a.nq = nq; a.n_cells = (int)n_cells; a.dens = d_dens;
+  a.qp = d_qp.get(); a.nq = nq; a.n_cells = (int)n_cells; a.dens = d_dens.get();
   hipLaunchKernelGGL(charge_density_kernel, dim3((unsigned)((n_cells + 3) / 4)), dim3(kThreads), 0, ctx->stream, a);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess && dens) e = hipMemcpyAsync(dens, d_dens, sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess && dens) e = hipMemcpyAsync(dens, d_dens.get(), sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess && !dens) {  // the densities stay in HBM for gmg_rhs_assemble (gmg_get_charge_density copies them out on demand)
-    ctx->dens_dev = d_dens; ctx->dens_cells = n_cells; ctx->dens_nq = nq;
-    d_dens = nullptr;
+    ctx->dens_dev = std::move(d_dens); ctx->dens_cells = n_cells; ctx->dens_nq = nq;
   }
-  cleanup();
   if (e != hipSuccess) { ctx->err = std::string("gmg_charge_density: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
   return GMG_OK;
 }
 
 int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *dens) {
   if (!ctx || !dens) return GMG_ERR_INVALID;
-  if (!ctx->dens_dev || ctx->dens_cells != n_cells || ctx->dens_nq != nq) return fail(ctx, GMG_ERR_INVALID, "gmg_get_charge_density: no densities of this shape on the device");
-  HIPC(hipMemcpyAsync(dens, ctx->dens_dev, sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
+  if (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq) return fail(ctx, GMG_ERR_INVALID, "gmg_get_charge_density: no densities of this shape on the device");
+  HIPC(hipMemcpyAsync(dens, ctx->dens_dev.get(), sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   return GMG_OK;
 }
@@ -3170,18 +3083,6 @@ int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *de
 }  // extern "C"
 
 namespace {
-// device buffers of one force call, freed on every way out
-struct DevBufs {
-  std::vector<void *> p;
-  ~DevBufs() { for (void *q : p) (void)hipFree(q); }
-  template <class T>
-  T *alloc(size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n * sizeof(T), 8)) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return (T *)q;
-  }
-};
 bool atoms_ok(int64_t n_atoms, const double *xyz, const double *q) {
   return n_atoms >= 0 && n_atoms < ((int64_t)1 << 31) && (n_atoms == 0 || (xyz && q));
 }
@@ -3196,7 +3097,7 @@ std::vector<double> pack_xq(int64_t n, const double *xyz, const double *q) {
 // per-atom (F, e) of a pair law into out_dev [n][4]: all pairs (rcut = inf, N-body tiles) or the pairs closer than rcut
 // through the bins of gmg_forces::force_bins
 template <class Law>
-int launch_pairs(gmg_context *ctx, DevBufs &m, const Law &law, double rcut, int64_t n, const double *xyz, const double *xq_host,
+int launch_pairs(gmg_context *ctx, const Law &law, double rcut, int64_t n, const double *xyz, const double *xq_host,
                  const double *xq_dev, double *out_dev) {
   const int bs = ctx->force_block;
   const size_t lds = sizeof(double) * 4 * (size_t)bs;
@@ -3213,18 +3114,20 @@ int launch_pairs(gmg_context *ctx, DevBufs &m, const Law &law, double rcut, int6
   std::vector<int32_t> ubin, ustart;
   for (size_t b = 0; b + 1 < B.ptr.size(); ++b)
     for (int32_t s = 0; s < B.ptr[b + 1] - B.ptr[b]; s += bs) { ubin.push_back((int32_t)b); ustart.push_back(s); }
-  double *d_sorted = m.alloc<double>(sorted.size());
-  int32_t *d_items = m.alloc<int32_t>(B.items.size()), *d_ptr = m.alloc<int32_t>(B.ptr.size());
-  int32_t *d_ubin = m.alloc<int32_t>(ubin.size()), *d_ustart = m.alloc<int32_t>(ustart.size());
-  if (!d_sorted || !d_items || !d_ptr || !d_ubin || !d_ustart) return fail(ctx, GMG_ERR_HIP, "atom forces: out of memory");
-  HIPC(hipMemcpyAsync(d_sorted, sorted.data(), sizeof(double) * sorted.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_items, B.items.data(), sizeof(int32_t) * B.items.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_ptr, B.ptr.data(), sizeof(int32_t) * B.ptr.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_ubin, ubin.data(), sizeof(int32_t) * ubin.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_ustart, ustart.data(), sizeof(int32_t) * ustart.size(), hipMemcpyHostToDevice, ctx->stream));
-  gmg_forces::BinnedArgs a{d_sorted, d_items, d_ptr, d_ubin, d_ustart, {B.n[0], B.n[1], B.n[2]}, out_dev};
+  DevPtr<double> d_sorted;
+  DevPtr<int32_t> d_items, d_ptr, d_ubin, d_ustart;
+  if (d_sorted.alloc(std::max<size_t>(sorted.size(), 1)) != hipSuccess || d_items.alloc(std::max<size_t>(B.items.size(), 2)) != hipSuccess ||
+      d_ptr.alloc(std::max<size_t>(B.ptr.size(), 2)) != hipSuccess || d_ubin.alloc(std::max<size_t>(ubin.size(), 2)) != hipSuccess ||
+      d_ustart.alloc(std::max<size_t>(ustart.size(), 2)) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, "atom forces: out of memory");  // (sizes: at least 8 bytes each)
+  HIPC(hipMemcpyAsync(d_sorted.get(), sorted.data(), sizeof(double) * sorted.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_items.get(), B.items.data(), sizeof(int32_t) * B.items.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ptr.get(), B.ptr.data(), sizeof(int32_t) * B.ptr.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ubin.get(), ubin.data(), sizeof(int32_t) * ubin.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_ustart.get(), ustart.data(), sizeof(int32_t) * ustart.size(), hipMemcpyHostToDevice, ctx->stream));
+  gmg_forces::BinnedArgs a{d_sorted.get(), d_items.get(), d_ptr.get(), d_ubin.get(), d_ustart.get(), {B.n[0], B.n[1], B.n[2]}, out_dev};
   hipLaunchKernelGGL(gmg_forces::pair_binned_kernel<Law>, dim3((unsigned)ubin.size()), dim3(bs), lds, ctx->stream, law, rcut, a);
-  HIPC(hipStreamSynchronize(ctx->stream));  // (the host arrays above are the sources of the copies)
+  HIPC(hipStreamSynchronize(ctx->stream));  // (the host arrays above are the sources of the copies, the buffers the kernel's inputs)
   return GMG_OK;
 }
 }  // namespace
@@ -3261,18 +3164,15 @@ int gmg_set_point_locator(gmg_context *ctx, const int32_t n0[3], const double or
     if (active_dofs[i] < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_set_point_locator: negative DoF");
     max_dof = std::max<int64_t>(max_dof, active_dofs[i]);
   }
-  int32_t *d_node = nullptr, *d_dofs = nullptr;
-  if (hipMalloc(&d_node, sizeof(int32_t) * (size_t)n_nodes) != hipSuccess) return fail(ctx, GMG_ERR_HIP, "gmg_set_point_locator: out of memory");
-  if (hipMalloc(&d_dofs, sizeof(int32_t) * 8 * (size_t)n_active) != hipSuccess) {
-    (void)hipFree(d_node);
+  DevPtr<int32_t> d_node, d_dofs;
+  if (d_node.alloc((size_t)n_nodes) != hipSuccess || d_dofs.alloc(8 * (size_t)n_active) != hipSuccess)
     return fail(ctx, GMG_ERR_HIP, "gmg_set_point_locator: out of memory");
-  }
-  ctx->loc_node = d_node;
-  ctx->loc_dofs = d_dofs;
-  HIPC(hipMemcpyAsync(d_node, node, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_dofs, active_dofs, sizeof(int32_t) * 8 * (size_t)n_active, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_node.get(), node, sizeof(int32_t) * (size_t)n_nodes, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(d_dofs.get(), active_dofs, sizeof(int32_t) * 8 * (size_t)n_active, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
-  ctx->loc = gmg_forces::Locator{{n0[0], n0[1], n0[2]}, {origin[0], origin[1], origin[2]}, h0, d_node, d_dofs};
+  ctx->loc = gmg_forces::Locator{{n0[0], n0[1], n0[2]}, {origin[0], origin[1], origin[2]}, h0, d_node.get(), d_dofs.get()};
+  ctx->loc_node = std::move(d_node);  // (the context's only once the locator is complete)
+  ctx->loc_dofs = std::move(d_dofs);
   ctx->loc_max_dof = max_dof;
   return GMG_OK;
 }
@@ -3288,16 +3188,17 @@ int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, c
   const int64_t n = n_atoms;
   const bool want_field = phi || field || force, want_pairs = force || force_short || e_short;
   const std::vector<double> xq = pack_xq(n, atom_xyz, atom_q);
-  DevBufs m;
-  double *d_xq = m.alloc<double>((size_t)n * 4), *d_phi = m.alloc<double>((size_t)n), *d_E = m.alloc<double>((size_t)n * 3);
-  double *d_pair = m.alloc<double>((size_t)n * 4);
-  if (!d_xq || !d_phi || !d_E || !d_pair) return fail(ctx, GMG_ERR_HIP, "gmg_atom_forces: out of memory");
+  DevPtr<double> xq_own, phi_own, E_own, pair_own;
+  if (xq_own.alloc((size_t)n * 4) != hipSuccess || phi_own.alloc((size_t)n) != hipSuccess || E_own.alloc((size_t)n * 3) != hipSuccess ||
+      pair_own.alloc((size_t)n * 4) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, "gmg_atom_forces: out of memory");
+  double *const d_xq = xq_own.get(), *const d_phi = phi_own.get(), *const d_E = E_own.get(), *const d_pair = pair_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   const int bs = ctx->force_block;
   if (want_field)
     hipLaunchKernelGGL(gmg_forces::atom_field_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, ctx->stream, ctx->loc, u, d_xq, (int)n,
                        d_phi, d_E);
-  if (want_pairs) CHK(launch_pairs(ctx, m, gmg_forces::ShortLaw::make(r_c), cutoff > 0.0 ? cutoff * r_c : INFINITY, n, atom_xyz,
+  if (want_pairs) CHK(launch_pairs(ctx, gmg_forces::ShortLaw::make(r_c), cutoff > 0.0 ? cutoff * r_c : INFINITY, n, atom_xyz,
                                    xq.data(), d_xq, d_pair));
   HIPC(hipGetLastError());
   std::vector<double> E((size_t)n * 3), pair((size_t)n * 4);
@@ -3323,11 +3224,11 @@ int gmg_direct_coulomb(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz
   (void)hipSetDevice(ctx->device);
   const int64_t n = n_atoms;
   const std::vector<double> xq = pack_xq(n, atom_xyz, atom_q);
-  DevBufs m;
-  double *d_xq = m.alloc<double>((size_t)n * 4), *d_pair = m.alloc<double>((size_t)n * 4);
-  if (!d_xq || !d_pair) return fail(ctx, GMG_ERR_HIP, "gmg_direct_coulomb: out of memory");
+  DevPtr<double> xq_own, pair_own;
+  if (xq_own.alloc((size_t)n * 4) != hipSuccess || pair_own.alloc((size_t)n * 4) != hipSuccess) return fail(ctx, GMG_ERR_HIP, "gmg_direct_coulomb: out of memory");
+  double *const d_xq = xq_own.get(), *const d_pair = pair_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  CHK(launch_pairs(ctx, m, gmg_forces::DirectLaw{}, INFINITY, n, atom_xyz, xq.data(), d_xq, d_pair));
+  CHK(launch_pairs(ctx, gmg_forces::DirectLaw{}, INFINITY, n, atom_xyz, xq.data(), d_xq, d_pair));
   HIPC(hipGetLastError());
   std::vector<double> pair((size_t)n * 4);
   HIPC(hipMemcpyAsync(pair.data(), d_pair, sizeof(double) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -3352,10 +3253,11 @@ int gmg_gaussian_potential(gmg_context *ctx, int64_t n_atoms, const double *atom
   if (n_points == 0 || (!phi && !grad)) return GMG_OK;
   (void)hipSetDevice(ctx->device);
   const std::vector<double> xq = pack_xq(n_atoms, atom_xyz, atom_q);
-  DevBufs m;
-  double *d_xq = m.alloc<double>(xq.size()), *d_pts = m.alloc<double>(3 * (size_t)n_points);
-  double *d_phi = phi ? m.alloc<double>((size_t)n_points) : nullptr, *d_grad = grad ? m.alloc<double>(3 * (size_t)n_points) : nullptr;
-  if (!d_xq || !d_pts || (phi && !d_phi) || (grad && !d_grad)) return fail(ctx, GMG_ERR_HIP, "gmg_gaussian_potential: out of memory");
+  DevPtr<double> xq_own, pts_own, phi_own, grad_own;
+  if (xq_own.alloc(xq.size()) != hipSuccess || pts_own.alloc(3 * (size_t)n_points) != hipSuccess || (phi && phi_own.alloc((size_t)n_points) != hipSuccess) ||
+      (grad && grad_own.alloc(3 * (size_t)n_points) != hipSuccess))
+    return fail(ctx, GMG_ERR_HIP, "gmg_gaussian_potential: out of memory");
+  double *const d_xq = xq_own.get(), *const d_pts = pts_own.get(), *const d_phi = phi_own.get(), *const d_grad = grad_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * xq.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_pts, point_xyz, sizeof(double) * 3 * (size_t)n_points, hipMemcpyHostToDevice, ctx->stream));
   const int bs = ctx->force_block;
@@ -3397,11 +3299,15 @@ int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_
   (void)hipSetDevice(ctx->device);
   const std::vector<double> xq = pack_xq(n_atoms, atom_xyz, atom_q);
   const size_t nc = (size_t)n_cells;
-  DevBufs m;
-  double *d_xq = m.alloc<double>(xq.size()), *d_lo = m.alloc<double>(3 * nc), *d_h = m.alloc<double>(nc), *d_err = m.alloc<double>(nc);
-  double *d_qp = m.alloc<double>(3 * (size_t)nq), *d_w = m.alloc<double>((size_t)nq), *d_sg = m.alloc<double>(24 * (size_t)nq);
-  int32_t *d_dofs = m.alloc<int32_t>(8 * nc);
-  if (!d_xq || !d_lo || !d_h || !d_err || !d_qp || !d_w || !d_sg || !d_dofs) return fail(ctx, GMG_ERR_HIP, "gmg_energy_norm_error: out of memory");
+  DevPtr<double> xq_own, lo_own, h_own, err_own, qp_own, w_own, sg_own;
+  DevPtr<int32_t> dofs_own;
+  if (xq_own.alloc(xq.size()) != hipSuccess || lo_own.alloc(3 * nc) != hipSuccess || h_own.alloc(nc) != hipSuccess || err_own.alloc(nc) != hipSuccess ||
+      qp_own.alloc(3 * (size_t)nq) != hipSuccess || w_own.alloc((size_t)nq) != hipSuccess || sg_own.alloc(24 * (size_t)nq) != hipSuccess ||
+      dofs_own.alloc(8 * nc) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, "gmg_energy_norm_error: out of memory");
+  double *const d_xq = xq_own.get(), *const d_lo = lo_own.get(), *const d_h = h_own.get(), *const d_err = err_own.get();
+  double *const d_qp = qp_own.get(), *const d_w = w_own.get(), *const d_sg = sg_own.get();
+  int32_t *const d_dofs = dofs_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * xq.size(), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_lo, cell_lo, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_h, cell_h, sizeof(double) * nc, hipMemcpyHostToDevice, ctx->stream));
@@ -3421,12 +3327,12 @@ int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_
   }
   // sum over the cells: partials per workgroup, then one workgroup (the grid depends on n_cells alone)
   const int grid = grid_for(n_cells);
-  hipLaunchKernelGGL(sum_partial_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, (const double *)d_err, n_cells, ctx->part_a);
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a, grid, 1, 0u, ctx->scal_dev);
+  hipLaunchKernelGGL(sum_partial_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, (const double *)d_err, n_cells, ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), grid, 1, 0u, ctx->scal_dev.get());
   HIPC(hipGetLastError());
   if (cell_err2) HIPC(hipMemcpyAsync(cell_err2, d_err, sizeof(double) * nc, hipMemcpyDeviceToHost, ctx->stream));
   CHK(fetch_scalars(ctx, 1));
-  if (error) *error = std::sqrt(ctx->scal_host[0]);
+  if (error) *error = std::sqrt(ctx->scal_host.get()[0]);
   return GMG_OK;
 }
 
@@ -3440,7 +3346,7 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
   if (!ctx || n_cells < 0 || nq < 1 || nq > 512 || (dim != 2 && dim != 3) || !shape || !weight || !cell_level || !jxw_of_level || n_terms < 0 || n_dofs < 0 ||
       !dof_ptr || !coef_table || !rhs)
     return GMG_ERR_INVALID;
-  if (!ctx->dens_dev || ctx->dens_cells != n_cells || ctx->dens_nq != nq)
+  if (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq)
     return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: call gmg_charge_density(..., dens = NULL) for these cells first");
   const int nv = 1 << dim;
   const int64_t n_slots = n_cells * nv, n_ent = dof_ptr[n_dofs];
@@ -3449,15 +3355,11 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
     return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: a list of nonzero length is NULL");
   if (n_slots >= ((int64_t)1 << 31) || n_ent >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_rhs_assemble: more than 2^31 slots");
   (void)hipSetDevice(ctx->device);
-  double *d_F = nullptr, *d_tv = nullptr;
-  uint8_t *d_lv = nullptr, *d_ec = nullptr;
-  int32_t *d_ts = nullptr, *d_es = nullptr, *d_ptr = nullptr;
+  DevPtr<double> d_F, d_tv;
+  DevPtr<uint8_t> d_lv, d_ec;
+  DevPtr<int32_t> d_ts, d_es, d_ptr;
+  DevPtr<RhsArgs> d_a;  // (the argument block is 39 KB: it travels through memory, not through the kernel-argument segment)
   RhsArgs a{};
-  auto cleanup = [&]() {
-    for (void *q : {(void *)d_F, (void *)d_tv, (void *)d_lv, (void *)d_ec, (void *)d_ts, (void *)d_es, (void *)d_ptr})
-      if (q) (void)hipFree(q);
-  };
-#define RHC(call) do { if ((call) != hipSuccess) { cleanup(); return fail(ctx, GMG_ERR_HIP, "gmg_rhs_assemble: " #call " failed"); } } while (0)
   std::vector<int32_t> ptr32((size_t)n_dofs + 1);
   for (int64_t i = 0; i <= n_dofs; ++i) {
     if (i && dof_ptr[i] < dof_ptr[i - 1]) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: dof_ptr not monotone");
@@ -3469,45 +3371,31 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
     if (entry_slot[e] < 0 || entry_slot[e] >= n_slots) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: slot out of range");
   for (int64_t t = 0; t < n_terms; ++t)
     if (term_slot[t] < 0 || term_slot[t] >= n_slots || (t && term_slot[t] < term_slot[t - 1])) return fail(ctx, GMG_ERR_INVALID, "gmg_rhs_assemble: term slots must ascend inside the slot range");
-  RHC(hipMalloc(&d_F, sizeof(double) * (size_t)std::max<int64_t>(n_slots, 1)));
-  RHC(hipMalloc(&d_lv, (size_t)std::max<int64_t>(n_cells, 1)));
-  RHC(hipMalloc(&d_ptr, sizeof(int32_t) * ptr32.size()));
-  RHC(hipMalloc(&d_es, sizeof(int32_t) * (size_t)std::max<int64_t>(n_ent, 1)));
-  RHC(hipMalloc(&d_ec, (size_t)std::max<int64_t>(n_ent, 1)));
-  RHC(hipMalloc(&d_ts, sizeof(int32_t) * (size_t)std::max<int64_t>(n_terms, 1)));
-  RHC(hipMalloc(&d_tv, sizeof(double) * (size_t)std::max<int64_t>(n_terms, 1)));
-  if (n_cells) RHC(hipMemcpyAsync(d_lv, cell_level, (size_t)n_cells, hipMemcpyHostToDevice, ctx->stream));
-  RHC(hipMemcpyAsync(d_ptr, ptr32.data(), sizeof(int32_t) * ptr32.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (n_ent) {
-    RHC(hipMemcpyAsync(d_es, entry_slot, sizeof(int32_t) * (size_t)n_ent, hipMemcpyHostToDevice, ctx->stream));
-    RHC(hipMemcpyAsync(d_ec, entry_coef, (size_t)n_ent, hipMemcpyHostToDevice, ctx->stream));
-  }
-  if (n_terms) {
-    RHC(hipMemcpyAsync(d_ts, term_slot, sizeof(int32_t) * (size_t)n_terms, hipMemcpyHostToDevice, ctx->stream));
-    RHC(hipMemcpyAsync(d_tv, term_value, sizeof(double) * (size_t)n_terms, hipMemcpyHostToDevice, ctx->stream));
-  }
-  a.dens = ctx->dens_dev; a.n_cells = n_cells; a.nq = nq; a.nv = nv; a.cell_level = d_lv; a.F = d_F;
+  HIPC(d_F.alloc((size_t)std::max<int64_t>(n_slots, 1)));
+  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+  HIPC(upload(d_ptr, ptr32, ctx->stream));
+  HIPC(upload(d_es, entry_slot, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_ec, entry_coef, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_ts, term_slot, (size_t)n_terms, ctx->stream));
+  HIPC(upload(d_tv, term_value, (size_t)n_terms, ctx->stream));
+  a.dens = ctx->dens_dev.get(); a.n_cells = n_cells; a.nq = nq; a.nv = nv; a.cell_level = d_lv.get(); a.F = d_F.get();
   for (int q = 0; q < nq; ++q) {
     a.weight[q] = weight[q];
     for (int i = 0; i < nv; ++i) a.shape[q * 8 + i] = shape[q * nv + i];
   }
   for (int l = 0; l < 16; ++l) a.jxw[l] = jxw_of_level[l];
-  a.n_terms = n_terms; a.term_slot = d_ts; a.term_value = d_tv;
-  a.n_dofs = n_dofs; a.dof_ptr = d_ptr; a.entry_slot = d_es; a.entry_coef = d_ec; a.rhs = rhs;
+  a.n_terms = n_terms; a.term_slot = d_ts.get(); a.term_value = d_tv.get();
+  a.n_dofs = n_dofs; a.dof_ptr = d_ptr.get(); a.entry_slot = d_es.get(); a.entry_coef = d_ec.get(); a.rhs = rhs;
   for (int c = 0; c < 256; ++c) a.coef[c] = coef_table[c];
-  RhsArgs *d_a = nullptr;  // (the argument block is 39 KB: it travels through memory, not through the kernel-argument segment)
-  RHC(hipMalloc(&d_a, sizeof(RhsArgs)));
-  hipError_t e = hipMemcpyAsync(d_a, &a, sizeof(RhsArgs), hipMemcpyHostToDevice, ctx->stream);
+  HIPC(d_a.alloc(1));
+  hipError_t e = hipMemcpyAsync(d_a.get(), &a, sizeof(RhsArgs), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    if (n_cells) hipLaunchKernelGGL(rhs_cell_kernel, dim3(grid_for(n_cells)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a);
-    if (n_terms) hipLaunchKernelGGL(rhs_terms_kernel, dim3(grid_for(n_terms)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a);
-    if (n_dofs) hipLaunchKernelGGL(rhs_gather_kernel, dim3(grid_for(n_dofs)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a);
+    if (n_cells) hipLaunchKernelGGL(rhs_cell_kernel, dim3(grid_for(n_cells)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a.get());
+    if (n_terms) hipLaunchKernelGGL(rhs_terms_kernel, dim3(grid_for(n_terms)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a.get());
+    if (n_dofs) hipLaunchKernelGGL(rhs_gather_kernel, dim3(grid_for(n_dofs)), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_a.get());
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_a);
-#undef RHC
-  cleanup();
   if (e != hipSuccess) { ctx->err = std::string("gmg_rhs_assemble: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
   return GMG_OK;
 }
@@ -3583,7 +3471,7 @@ int gmg_set_halo_plan(gmg_context *ctx, int which, int n_neighbors, const int32_
   else if (which >= 3000 && which < 3000 + ctx->n_levels) targets = {&ctx->lv[(size_t)which - 3000].It};
   else return fail(ctx, GMG_ERR_INVALID, "gmg_set_halo_plan: bad operator id");
   for (DevCSR *m : targets) {
-    free_halo(m->halo);
+    m->halo = HaloPlan();
     if (build_halo(m->halo, n_neighbors, neighbor_rank, send_count, send_idx, recv_count, ctx->stream))
       return fail(ctx, GMG_ERR_HIP, "halo plan upload failed");
   }
@@ -3614,7 +3502,7 @@ int gmg_set_profiling(gmg_context *ctx, int sample_every) {
   if (sample_every > 0 && ctx->ev_a.empty()) {
     for (auto *v : {&ctx->ev_a, &ctx->ev_b, &ctx->ev_c, &ctx->ev_d, &ctx->ev_e, &ctx->ev_f}) {
       v->resize(256);
-      for (auto &e : *v) HIPC(hipEventCreate(&e));
+      for (auto &e : *v) HIPC(e.create());
     }
   }
   return GMG_OK;
@@ -3622,19 +3510,21 @@ int gmg_set_profiling(gmg_context *ctx, int sample_every) {
 int gmg_calibrate_hbm(gmg_context *ctx, int64_t n_bytes, int reps, double *read_gbps, double *copy_gbps) {
   if (!ctx || n_bytes < (1 << 20) || reps < 1) return GMG_ERR_INVALID;
   const int64_t n2 = n_bytes / 16;
-  double2 *a = nullptr, *b = nullptr;
-  HIPC(hipMalloc(&a, (size_t)n2 * 16));
-  HIPC(hipMalloc(&b, (size_t)n2 * 16));
+  DevPtr<double2> a_own, b_own;
+  Event e0_own, e1_own;
+  HIPC(a_own.alloc((size_t)n2));
+  HIPC(b_own.alloc((size_t)n2));
+  double2 *const a = a_own.get(), *const b = b_own.get();
   HIPC(hipMemsetAsync(a, 0, (size_t)n2 * 16, ctx->stream));
   HIPC(hipMemsetAsync(b, 0, (size_t)n2 * 16, ctx->stream));
-  hipEvent_t e0, e1;
-  HIPC(hipEventCreate(&e0));
-  HIPC(hipEventCreate(&e1));
+  HIPC(e0_own.create());
+  HIPC(e1_own.create());
+  const hipEvent_t e0 = e0_own.get(), e1 = e1_own.get();
   float ms = 0.f;
   for (int pass = 0; pass < 2; ++pass) {  // pass 0 warms up
     HIPC(hipEventRecord(e0, ctx->stream));
     for (int r = 0; r < reps; ++r)
-      hipLaunchKernelGGL(stream_read_kernel, dim3(kMaxPartials), dim3(kThreads), 0, ctx->stream, (const double2 *)a, n2, ctx->part_a);
+      hipLaunchKernelGGL(stream_read_kernel, dim3(kMaxPartials), dim3(kThreads), 0, ctx->stream, (const double2 *)a, n2, ctx->part_a.get());
     HIPC(hipEventRecord(e1, ctx->stream));
     HIPC(hipEventSynchronize(e1));
     HIPC(hipEventElapsedTime(&ms, e0, e1));
@@ -3649,8 +3539,6 @@ int gmg_calibrate_hbm(gmg_context *ctx, int64_t n_bytes, int reps, double *read_
     HIPC(hipEventElapsedTime(&ms, e0, e1));
   }
   if (copy_gbps) *copy_gbps = (double)n2 * 32 * reps / (ms * 1e-3) / 1e9;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(a); (void)hipFree(b);
   return GMG_OK;
 }
 

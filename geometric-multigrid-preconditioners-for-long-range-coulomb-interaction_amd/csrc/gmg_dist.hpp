@@ -24,7 +24,7 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
   const int64_t n = L0.n;
   const int g_vec = grid_for(n);
   const int g_upd = grid_for(n / 2);
-  double *s_gg = ctx->scal_dev + 4, *s_dh = ctx->scal_dev + 5;
+  double *s_gg = ctx->scal_dev.get() + 4, *s_dh = ctx->scal_dev.get() + 5;
   // ring of direction vectors (with ghost tails): x += alpha d is applied kXRing iterations at a time
   const bool peer = comm && ctx->comm.peer;  // sums and halo entries travel inside the iteration's own kernels (gmg_device.hpp: PeerCG)
   if (!ctx->cg_ring[0]) {
@@ -41,12 +41,15 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
       int64_t ro = 0;
       for (int i = 0; i < A.halo.n_neighbors; ++i) { mine[4 + A.halo.rank[(size_t)i]] = ro; ro += A.halo.recv_count[(size_t)i]; }
       if (comm_exchange_meta(ctx->comm, mine, 4 + kPeerMaxRanks, ctx->peer_meta)) return fail(ctx, GMG_ERR_COMM, "coarse CG: meta exchange failed");
-      if (!ctx->peer_push_cnt) {
-        HIPC(hipMalloc(&ctx->peer_push_cnt, sizeof(unsigned int)));
-        HIPC(hipMemsetAsync(ctx->peer_push_cnt, 0, sizeof(unsigned int), ctx->stream));
+      if (!ctx->peer_push_cnt.get()) {
+        HIPC(ctx->peer_push_cnt.alloc(1));
+        HIPC(hipMemsetAsync(ctx->peer_push_cnt.get(), 0, sizeof(unsigned int), ctx->stream));
       }
     } else {
-      for (int r = 0; r < kXRing; ++r) CHK(alloc_vec(ctx, &ctx->cg_ring[r], A.n_cols));
+      for (int r = 0; r < kXRing; ++r) {
+        CHK(alloc_vec(ctx, ctx->cg_ring_own[r], A.n_cols));
+        ctx->cg_ring[r] = ctx->cg_ring_own[r].get();
+      }
     }
     ctx->cg_ring_len = A.n_cols;
   }
@@ -60,24 +63,24 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
       if (A.halo.recv_count[(size_t)i] > 0) pc.nb_mask |= 1u << A.halo.rank[(size_t)i];
     pc.tag0 = ctx->peer_tag0;
     ctx->peer_tag0 += (unsigned long long)ctx->coarse_maxit + 16ull;  // the same stride on every rank
-    pc.abort_flag = ctx->comm.abort_host;
+    pc.abort_flag = ctx->comm.abort_host.get();
   }
   auto peer_sum = [&](const double *part, int n_part, int kind, int from_init, double *out) {
-    PeerSumArgs ps{pc, part, n_part, kind, from_init, ctx->st, out};
+    PeerSumArgs ps{pc, part, n_part, kind, from_init, ctx->st.get(), out};
     hipLaunchKernelGGL(peer_allsum_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, ps);
   };
 
   // the direction read by iteration 0 (beta = 0) must be finite: the init kernel zeroes it
-  CGInitArgs ia{b, x, ctx->cg_g, ctx->cg_ring[kXRing - 1], ctx->cg_ring[kXRing - 1], n, ctx->st, ctx->part_b};
+  CGInitArgs ia{b, x, ctx->cg_g.get(), ctx->cg_ring[kXRing - 1], ctx->cg_ring[kXRing - 1], n, ctx->st.get(), ctx->part_b.get()};
   hipLaunchKernelGGL(cg_init_kernel, dim3(g_vec), dim3(kThreads), 0, ctx->stream, ia);
   // where the consumers find the reduced scalars: all-reduced single values, or the raw partials
-  const double *gg_src = ctx->part_b;
+  const double *gg_src = ctx->part_b.get();
   int gg_n = g_vec;
   if (peer) {
-    peer_sum(ctx->part_b, g_vec, 0, 1, s_gg);  // |g|^2 that opens iteration 0: every rank's sum to every rank, total in s_gg
+    peer_sum(ctx->part_b.get(), g_vec, 0, 1, s_gg);  // |g|^2 that opens iteration 0: every rank's sum to every rank, total in s_gg
     gg_src = s_gg; gg_n = 1;
   } else if (comm) {
-    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_b, g_vec, 1, 0u, s_gg);
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_b.get(), g_vec, 1, 0u, s_gg);
     if (allreduce_sum(ctx->comm, s_gg, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
     gg_src = s_gg; gg_n = 1;
   }
@@ -86,7 +89,7 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
   ctx->ev_used = 0; ctx->ev2_used = 0;
   auto flush_x = [&](int lo, int upto) {
     CGXFlushArgs fa{};
-    fa.x = x; fa.n = n; fa.st = ctx->st; fa.lo = lo; fa.upto = upto;
+    fa.x = x; fa.n = n; fa.st = ctx->st.get(); fa.lo = lo; fa.upto = upto;
     for (int r = 0; r < kXRing; ++r) fa.ring[r] = ctx->cg_ring[r];
     hipLaunchKernelGGL(cg_xflush_kernel, dim3(g_upd), dim3(kThreads), 0, ctx->stream, fa);
   };
@@ -95,11 +98,11 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
     launched_total = launched + 1;
     double *d = ctx->cg_ring[launched % kXRing];
     CGDirArgs da{};
-    da.d = d; da.d_old = ctx->cg_ring[(launched + kXRing - 1) % kXRing]; da.g = ctx->cg_g; da.n = n; da.st = ctx->st;
+    da.d = d; da.d_old = ctx->cg_ring[(launched + kXRing - 1) % kXRing]; da.g = ctx->cg_g.get(); da.n = n; da.st = ctx->st.get();
     da.part_in = gg_src; da.n_part_in = gg_n; da.tol = ctx->coarse_tol; da.maxit = maxit;
     if (peer) {
       da.pc = pc;
-      da.send_idx = A.halo.send_idx; da.cnt = ctx->peer_push_cnt;
+      da.send_idx = A.halo.send_idx.get(); da.cnt = ctx->peer_push_cnt.get();
       int so = 0;
       for (int i = 0; i < A.halo.n_neighbors; ++i) {
         if (A.halo.send_count[(size_t)i] > 0) {
@@ -115,35 +118,35 @@ int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iter
     }
     hipLaunchKernelGGL(cg_direction_kernel, dim3(g_vec), dim3(kThreads), 0, ctx->stream, da);
     if (comm && !peer && halo_exchange(ctx->comm, A.halo, d, n, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "halo exchange failed");
-    if (peer && pc.nb_mask) hipLaunchKernelGGL(peer_wait_halo_kernel, dim3(1), dim3(64), 0, ctx->stream, pc, (const CGState *)ctx->st);
-    SpmvArgs a = base_args(A, d, ctx->cg_h);
-    a.st = ctx->st;
-    a.part_out = ctx->part_a;
+    if (peer && pc.nb_mask) hipLaunchKernelGGL(peer_wait_halo_kernel, dim3(1), dim3(64), 0, ctx->stream, pc, (const CGState *)ctx->st.get());
+    SpmvArgs a = base_args(A, d, ctx->cg_h.get());
+    a.st = ctx->st.get();
+    a.part_out = ctx->part_a.get();
     const bool sample = ctx->prof_every > 0 && (launched % ctx->prof_every) == 0 && ctx->ev_used < (int)ctx->ev_a.size();
-    if (sample) { ctx->timed_start = ctx->ev_a[(size_t)ctx->ev_used]; ctx->timed_stop = ctx->ev_b[(size_t)ctx->ev_used++]; }
+    if (sample) { ctx->timed_start = ctx->ev_a[(size_t)ctx->ev_used].get(); ctx->timed_stop = ctx->ev_b[(size_t)ctx->ev_used++].get(); }
     const int n_part_dh = launch_op<kStore, 2>(ctx, A, a);
-    const double *dh_src = ctx->part_a;
+    const double *dh_src = ctx->part_a.get();
     int dh_n = n_part_dh;
     if (peer) {
-      peer_sum(ctx->part_a, n_part_dh, 1, 0, s_dh);
+      peer_sum(ctx->part_a.get(), n_part_dh, 1, 0, s_dh);
       dh_src = s_dh; dh_n = 1;
     } else if (comm) {
-      hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a, n_part_dh, 1, 0u, s_dh);
+      hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), n_part_dh, 1, 0u, s_dh);
       if (allreduce_sum(ctx->comm, s_dh, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
       dh_src = s_dh; dh_n = 1;
     }
-    CGUpdateGArgs ua{ctx->cg_g, ctx->cg_h, n, ctx->st, dh_src, dh_n, ctx->part_b};
+    CGUpdateGArgs ua{ctx->cg_g.get(), ctx->cg_h.get(), n, ctx->st.get(), dh_src, dh_n, ctx->part_b.get()};
     const bool sample2 = sample && ctx->ev2_used < (int)ctx->ev_c.size();
-    if (sample2) { ctx->timed_start = ctx->ev_c[(size_t)ctx->ev2_used]; ctx->timed_stop = ctx->ev_d[(size_t)ctx->ev2_used++]; }
+    if (sample2) { ctx->timed_start = ctx->ev_c[(size_t)ctx->ev2_used].get(); ctx->timed_stop = ctx->ev_d[(size_t)ctx->ev2_used++].get(); }
     launch_timed(ctx, cg_update_g_kernel, dim3(g_upd), dim3(kThreads), 0, ua);
     if ((launched + 1) % kXRing == 0) flush_x(launched + 1 - kXRing, launched + 1);
     if (peer) {
-      peer_sum(ctx->part_b, g_upd, 0, 0, s_gg);
+      peer_sum(ctx->part_b.get(), g_upd, 0, 0, s_gg);
     } else if (comm) {
-      hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_b, g_upd, 1, 0u, s_gg);
+      hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_b.get(), g_upd, 1, 0u, s_gg);
       if (allreduce_sum(ctx->comm, s_gg, 1, ctx->stream)) return fail(ctx, GMG_ERR_COMM, "all-reduce failed");
     } else {
-      gg_src = ctx->part_b; gg_n = g_upd;
+      gg_src = ctx->part_b.get(); gg_n = g_upd;
     }
     return GMG_OK;
   }));
