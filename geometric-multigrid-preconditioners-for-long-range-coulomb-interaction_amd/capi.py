@@ -23,6 +23,7 @@ UNIQUE_ID_BYTES = 128
 SYMBOLS = [
     "gmg_create", "gmg_destroy", "gmg_reset", "gmg_last_error", "gmg_synchronize",
     "gmg_set_system_matrix", "gmg_set_level_matrix", "gmg_set_level_matrix_lattice", "gmg_set_edge_matrix", "gmg_set_prolongation", "gmg_build_transfer", "gmg_get_transfer",
+    "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
     "gmg_vec_add", "gmg_vec_sadd", "gmg_vec_dot", "gmg_vec_norms", "gmg_vec_all_zero",
@@ -384,6 +385,56 @@ class Context:
         self._chk(self.L.gmg_rhs_assemble(self.h, C.c_int64(n_cells), C.c_int(len(w)), C.c_int(dim), D(sh), D(w), _p(lv, C.c_uint8), D(jxw),
                                           C.c_int64(len(ts)), _p(ts, C.c_int32), D(tv), C.c_int64(len(ptr) - 1), _p(ptr, C.c_int64),
                                           _p(es, C.c_int32), _p(ec, C.c_uint8), D(ct), rhs.ptr))
+
+    def assemble_system_matrix(self, dim, n_dofs, cell_dofs, cell_level, K_of_level, constraint_of_dof, line_ptr, line_master, line_weight,
+                               validate=True):
+        """The active-mesh system matrix formed on the device (gmg_assemble_system_matrix); returns the device time in ms.
+        cell_dofs [n_cells, 2^dim], cell_level [n_cells], K_of_level [16, 2^dim, 2^dim], constraint_of_dof [n_dofs], the lines
+        in CSR form (line_ptr [n_lines + 1]; None or empty: no lines).  validate=True checks the shapes here (ValueError)
+        before the library sees them; the library checks the contents."""
+        nv = 1 << int(dim) if dim in (2, 3) else 0
+        cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        lv = np.ascontiguousarray(cell_level, dtype=np.uint8)
+        K = np.ascontiguousarray(K_of_level, dtype=np.float64)
+        cons = np.ascontiguousarray(constraint_of_dof, dtype=np.int32)
+        lp = np.ascontiguousarray([] if line_ptr is None else line_ptr, dtype=np.int64)
+        lm = np.ascontiguousarray([] if line_master is None else line_master, dtype=np.int32)
+        lw = np.ascontiguousarray([] if line_weight is None else line_weight, dtype=np.float64)
+        n_cells, n_lines = len(lv), max(len(lp) - 1, 0)
+        if validate:
+            if nv == 0:
+                raise ValueError("assemble_system_matrix: dim must be 2 or 3")
+            if n_dofs < 0 or cons.size != n_dofs:
+                raise ValueError("assemble_system_matrix: constraint_of_dof must have n_dofs entries")
+            if cd.size != n_cells * nv:
+                raise ValueError("assemble_system_matrix: cell_dofs must be [n_cells, 2^dim]")
+            if K.size != 16 * nv * nv:
+                raise ValueError("assemble_system_matrix: K_of_level must be [16, 2^dim, 2^dim]")
+            if len(lm) != len(lw) or (n_lines and len(lm) < lp[-1]) or (not n_lines and len(lm)):
+                raise ValueError("assemble_system_matrix: line_master / line_weight do not match line_ptr")
+        opt = lambda a, t: _p(a, t) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_system_matrix(self.h, C.c_int(int(dim)), C.c_int64(int(n_dofs)), C.c_int64(n_cells), opt(cd, C.c_int32),
+                                                    opt(lv, C.c_uint8), opt(K, C.c_double), opt(cons, C.c_int32), C.c_int64(n_lines),
+                                                    opt(lp, C.c_int64), opt(lm, C.c_int32), opt(lw, C.c_double), C.byref(ms)))
+        self.n_system = int(n_dofs)
+        return ms.value
+
+    def get_system_matrix(self):
+        """The CSR of the system matrix as the device holds it (after assemble_system_matrix)."""
+        from types import SimpleNamespace
+        nr, nz = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_system_matrix(self.h, C.byref(nr), C.byref(nz), None, None, None))
+        rp = np.zeros(nr.value + 1, dtype=np.int64)
+        col, val = np.zeros(max(nz.value, 1), dtype=np.int32), np.zeros(max(nz.value, 1))
+        self._chk(self.L.gmg_get_system_matrix(self.h, C.byref(nr), C.byref(nz), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double)))
+        return SimpleNamespace(n_rows=nr.value, n_cols=nr.value, nnz=nz.value, rowptr=rp, col=col[:nz.value], val=val[:nz.value])
+
+    def system_matrix_norms(self):
+        """(l1, linf, frobenius) of the device's system matrix CSR"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._chk(self.L.gmg_system_matrix_norms(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

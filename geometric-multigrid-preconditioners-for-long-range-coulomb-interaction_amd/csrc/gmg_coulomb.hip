@@ -19,6 +19,7 @@
 #include "gmg_transfer.hpp"
 #include "gmg_forces.hpp"
 #include "gmg_exact.hpp"
+#include "gmg_assemble.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -211,6 +212,7 @@ struct gmg_context {
   int64_t loc_max_dof = -1;  // -1: no locator set
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
+  int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
   int64_t sys_global = 0, l0_global = 0;  // l0_global == 0 on a communicator: level 0 is replicated, only the outer CG is partitioned
@@ -3400,6 +3402,185 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
   return GMG_OK;
 }
 
+// ---- the active-mesh system matrix formed on the device (gmg_assemble.hpp) ----
+
+int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                               const double *K_of_level, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                               const int32_t *line_master, const double *line_weight, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: not on a communicator (rank-local assembly does not exist yet)");
+  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: dim must be 2 or 3");
+  if (n_dofs < 0 || n_cells < 0 || n_lines < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: negative size");
+  const int nv = 1 << dim;
+  if ((n_cells > 0 && (!cell_dofs || !cell_level || !K_of_level)) || (n_dofs > 0 && !constraint_of_dof) || (n_lines > 0 && !line_ptr))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: an array of nonzero length is NULL");
+  if (n_dofs >= ((int64_t)1 << 31) || n_cells * nv >= ((int64_t)1 << 31) || n_lines >= ((int64_t)1 << 31))
+    return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 DoFs, slots or lines");
+  std::vector<int32_t> lp32((size_t)n_lines + 1, 0);
+  int64_t max_line = 0;
+  if (n_lines > 0) {
+    if (line_ptr[0] < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line_ptr starts below 0");
+    for (int64_t l = 0; l < n_lines; ++l) {
+      if (line_ptr[l + 1] < line_ptr[l]) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line_ptr decreases");
+      max_line = std::max(max_line, line_ptr[l + 1] - line_ptr[l]);
+    }
+    if (line_ptr[n_lines] >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 line entries");
+    for (int64_t l = 0; l <= n_lines; ++l) lp32[(size_t)l] = (int32_t)line_ptr[l];
+  }
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
+  if (n_ent > 0 && (!line_master || !line_weight)) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: an array of nonzero length is NULL");
+  for (int64_t e = line_ptr && n_lines > 0 ? line_ptr[0] : 0; e < n_ent; ++e)
+    if (line_master[e] < 0 || line_master[e] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: master outside [0, n_dofs)");
+  for (int64_t d = 0; d < n_dofs; ++d)
+    if (constraint_of_dof[d] < -1 || constraint_of_dof[d] >= n_lines) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line index outside [0, n_lines)");
+  for (int64_t s = 0; s < n_slots; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: DoF outside [0, n_dofs)");
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: cell level of 16 or more");
+  // (32-bit slot lists: every slot goes to its DoF and to at most max_line masters)
+  if (n_slots * (1 + max_line) >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 (row, slot) pairs");
+  (void)hipSetDevice(ctx->device);
+  DevCSR &m = ctx->S;
+  reset_keep_halo(m);
+  ctx->S_invd.reset(); ctx->S_tmp.reset();
+  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm, d_iptr, d_ipos, d_islot;
+  DevPtr<uint8_t> d_lv;
+  DevPtr<double> d_K, d_lw;
+  DevPtr<unsigned long long> d_total;
+  DevPtr<int> d_over;
+  Event e0, e1;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+  HIPC(upload(d_K, K_of_level, n_cells > 0 ? (size_t)16 * nv * nv : 0, ctx->stream));
+  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
+  HIPC(upload(d_lp, lp32, ctx->stream));
+  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
+  HIPC(d_iptr.alloc((size_t)n_dofs + 1));
+  HIPC(d_ipos.alloc((size_t)n_dofs + 1));
+  HIPC(m.rowptr.alloc((size_t)n_dofs + 1));
+  HIPC(d_total.alloc(1));
+  HIPC(d_over.alloc(1));
+  CHK(alloc_vec(ctx, ctx->S_invd, n_dofs));
+  CHK(alloc_vec(ctx, ctx->S_tmp, n_dofs));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(hipMemsetAsync(d_iptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(d_ipos.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(m.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(d_total.get(), 0, sizeof(unsigned long long), ctx->stream));
+  HIPC(hipMemsetAsync(d_over.get(), 0, sizeof(int), ctx->stream));
+  AsmArgs a{};
+  a.nv = nv; a.lg_nv = dim; a.max_line = (int)max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
+  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.K = d_K.get(); a.cons = d_cons.get();
+  a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
+  a.inc_ptr = d_iptr.get(); a.inc_pos = d_ipos.get(); a.rowptr = m.rowptr.get(); a.invd = ctx->S_invd.get();
+  a.total = d_total.get(); a.overflow = d_over.get();
+  const int cap = ctx->assemble_max_blocks;
+  auto blocks = [&](int64_t n, int per_block, int most) {
+    int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + per_block - 1) / per_block));
+    if (cap > 0) g = std::min<int64_t>(g, cap);
+    return dim3((unsigned)g);
+  };
+  const dim3 g_slots = blocks(n_slots, 256, 1 << 16), g_dofs = blocks(n_dofs, 256, 1 << 16), g_rows = blocks(n_dofs, 1, 1 << 16);
+  if (n_slots) hipLaunchKernelGGL(asm_incidence_kernel<false>, g_slots, dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_iptr.get(), n_dofs);
+  int32_t n_inc = 0;
+  HIPC(hipMemcpyAsync(&n_inc, d_iptr.get() + n_dofs, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  HIPC(d_islot.alloc((size_t)std::max<int32_t>(n_inc, 1)));
+  a.inc_slot = d_islot.get();
+  if (n_slots) {
+    hipLaunchKernelGGL(asm_incidence_kernel<true>, g_slots, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(asm_sort_incidence_kernel, g_dofs, dim3(256), 0, ctx->stream, a);
+  }
+  if (n_dofs) hipLaunchKernelGGL(asm_row_kernel<false>, g_rows, dim3(64), 0, ctx->stream, a);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr.get(), n_dofs);
+  std::vector<int32_t> rp((size_t)n_dofs + 1);
+  unsigned long long total = 0;
+  int over = 0;
+  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&total, d_total.get(), sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (over || total >= (1ull << 31)) { reset_keep_halo(m); ctx->S_invd.reset(); ctx->S_tmp.reset(); }
+  if (over) { return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: a row with more than 512 columns"); }
+  if (total >= (1ull << 31)) { return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: operator needs 64-bit device indices (nnz >= 2^31)"); }
+  const int64_t nnz = (int64_t)total;
+  const size_t pad = 8;
+  HIPC(m.col.alloc((size_t)nnz + pad));
+  HIPC(m.val.alloc((size_t)nnz + pad));
+  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
+  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
+  a.col = m.col.get(); a.val = m.val.get();
+  if (n_dofs) hipLaunchKernelGGL(asm_row_kernel<true>, g_rows, dim3(64), 0, ctx->stream, a);
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  // the row-window tiling (host: a pass over the row pointers, as gmg_build_transfer does for its operators)
+  const std::vector<int32_t> tiles = window_tiles(rp.data(), n_dofs);
+  m.n_rows = m.n_cols = n_dofs; m.nnz = nnz;
+  m.n_tiles = (int)tiles.size() - 1;
+  m.tiles_per_xcd = (m.n_tiles + 7) / 8;
+  m.grid = 8 * std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
+  HIPC(upload(m.tile_row, tiles, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(launch_status(ctx));
+  m.valid = true;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] system matrix assembled on the device: %lld rows nnz %lld, %lld (row, slot) pairs, %.3f ms\n", (long long)n_dofs, (long long)nnz, (long long)n_inc, ms);
+  return GMG_OK;
+}
+
+int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const DevCSR &m = ctx->S;
+  if (!m.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_system_matrix: system matrix not set");
+  if (!m.rowptr.get() || !m.col.get() || !m.val.get()) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_system_matrix: no CSR copy of the system matrix on the device");
+  if (n_rows) *n_rows = m.n_rows;
+  if (nnz) *nnz = m.nnz;
+  if (!rowptr) return GMG_OK;
+  if (m.nnz && (!col || !val)) return fail(ctx, GMG_ERR_INVALID, "gmg_get_system_matrix: col / val are NULL");
+  (void)hipSetDevice(ctx->device);
+  std::vector<int32_t> rp((size_t)m.n_rows + 1);
+  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (m.nnz) {
+    HIPC(hipMemcpyAsync(col, m.col.get(), sizeof(int32_t) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(val, m.val.get(), sizeof(double) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < rp.size(); ++i) rowptr[i] = rp[i];
+  return GMG_OK;
+}
+
+int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *frobenius) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const DevCSR &m = ctx->S;
+  if (!m.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_system_matrix_norms: system matrix not set");
+  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_system_matrix_norms: not on a communicator");
+  if (!m.rowptr.get() || !m.col.get() || !m.val.get() || m.n_rows != m.n_cols)
+    return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_system_matrix_norms: no CSR copy of the system matrix on the device");
+  (void)hipSetDevice(ctx->device);
+  DevPtr<double> rs, cs;
+  CHK(alloc_vec(ctx, rs, m.n_rows));
+  CHK(alloc_vec(ctx, cs, m.n_rows));
+  int64_t g = std::max<int64_t>(1, std::min<int64_t>(1 << 16, (m.n_rows + 255) / 256));
+  if (ctx->assemble_max_blocks > 0) g = std::min<int64_t>(g, ctx->assemble_max_blocks);
+  if (m.n_rows)
+    hipLaunchKernelGGL(asm_norm_sums_kernel, dim3((unsigned)g), dim3(256), 0, ctx->stream, (const int32_t *)m.rowptr.get(), (const int32_t *)m.col.get(),
+                       (const double *)m.val.get(), m.n_rows, rs.get(), cs.get());
+  double s1, s2, mx;
+  CHK(gmg_vec_norms(ctx, rs.get(), m.n_rows, &s1, &s2, &mx));
+  if (linf) *linf = mx;
+  CHK(gmg_vec_norms(ctx, cs.get(), m.n_rows, &s1, &s2, &mx));
+  if (l1) *l1 = mx;
+  CHK(gmg_vec_norms(ctx, m.val.get(), m.nnz, &s1, &s2, &mx));
+  if (frobenius) *frobenius = s2;
+  return GMG_OK;
+}
+
 // ---- distributed ----
 
 int gmg_comm_unique_id(void *out_id) { return comm_unique_id(out_id) ? GMG_ERR_COMM : GMG_OK; }
@@ -3584,6 +3765,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "force_block") {
     if (value != 64 && value != 128 && value != 256) return fail(ctx, GMG_ERR_INVALID, "force_block: 64, 128 or 256");
     ctx->force_block = (int)value;
+  }
+  else if (k == "assemble_max_blocks") {
+    if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "assemble_max_blocks: an integer in 0 .. 65536");
+    ctx->assemble_max_blocks = (int)value;
   }
   else if (k == "exact_chunk_log2") {
     if (!(value >= 0 && value <= 35) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "exact_chunk_log2: an integer in 0 .. 35");

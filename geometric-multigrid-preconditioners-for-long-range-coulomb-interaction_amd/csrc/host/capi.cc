@@ -35,7 +35,7 @@ int guarded(step50_problem *h, F f) {
 }
 const CSRMatrix *pick_matrix(step50_problem *h, int kind, int level) {
   // kind 0 system, 1 level, 2 edge, 3 prolongation
-  if (kind == 0) return &DISPATCH(h, system_matrix);
+  if (kind == 0) { DISPATCH(h, ensure_system_matrix()); return &DISPATCH(h, system_matrix); }  // (it may have been left to the device)
   if (kind == 1) DISPATCH(h, ensure_level_matrix(level));  // (level 0 may have been left to the device: assemble it now)
   if (kind == 3) DISPATCH(h, ensure_prolongation(level));   // (the transfers likewise)
   auto &v = kind == 1 ? DISPATCH(h, mg_matrices) : kind == 2 ? DISPATCH(h, mg_interface_matrices) : DISPATCH(h, mg_prolongation);
@@ -312,6 +312,42 @@ int step50_constrained_mask(step50_problem *h, int8_t *out) {
   return 0;
 }
 void *step50_gmg_context(step50_problem *h) { return DISPATCH(h, gmg); }
+
+// ---- "System matrix on device" (DESIGN.md section 12): the arrays the driver hands to gmg_assemble_system_matrix for the
+// current mesh, so that a test can restate the assembly from the same inputs.  sizes: n_dofs, n_cells, n_lines, n_entries
+int step50_dim(step50_problem *h) { return h->dim; }
+int step50_system_matrix_on_device(step50_problem *h) { return DISPATCH(h, system_on_device) ? 1 : 0; }
+int step50_system_assembly_sizes(step50_problem *h, int64_t sizes[4]) {
+  return guarded(h, [&] {
+    auto fill = [&](auto &P) {
+      sizes[0] = (int64_t)P.vertex_of_dof.size(); sizes[1] = (int64_t)P.active_cells.size(); sizes[2] = (int64_t)P.constraint_lines.size();
+      sizes[3] = 0;
+      for (auto &l : P.constraint_lines) sizes[3] += (int64_t)l.entries.size();
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
+int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t *cell_level, double *K_of_level, int32_t *constraint_of_dof,
+                                  int64_t *line_ptr, int32_t *line_master, double *line_weight, double *line_inhomogeneity) {
+  return guarded(h, [&] {
+    auto fill = [&](auto &P) {
+      const auto in = P.system_assembly_inputs();
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(in.cell_dofs, cell_dofs); put(in.cell_level, cell_level); put(in.K_of_level, K_of_level); put(P.constraint_of_dof, constraint_of_dof);
+      put(in.line_ptr, line_ptr); put(in.line_master, line_master); put(in.line_weight, line_weight); put(in.line_inhomogeneity, line_inhomogeneity);
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
+// the refinement marks of the cycle just estimated, all levels concatenated; returns their number (out may be null)
+int64_t step50_refine_flags(step50_problem *h, uint8_t *out) {
+  int64_t n = 0;
+  for (auto &lv : DISPATCH(h, refine_flags))
+    for (char f : lv) { if (out) out[n] = (uint8_t)(f != 0); ++n; }
+  return n;
+}
 
 // host threads of the replicated setup (one process per GPU: cores / world size)
 void step50_set_threads(int n) {

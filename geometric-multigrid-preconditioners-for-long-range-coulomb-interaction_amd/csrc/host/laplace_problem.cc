@@ -22,8 +22,12 @@
 namespace step50 {
 
 // STEP50_TIMING=2: wall time of the pieces of a host phase on stderr (since the previous call; nullptr restarts the clock)
-void sublap(const char *what) {
+bool sublap_on() {
   static const bool on = std::getenv("STEP50_TIMING") != nullptr && std::atoi(std::getenv("STEP50_TIMING")) >= 2;
+  return on;
+}
+void sublap(const char *what) {
+  const bool on = sublap_on();
   static auto t_last = std::chrono::steady_clock::now();
   if (!on) return;
   const auto now = std::chrono::steady_clock::now();
@@ -224,6 +228,10 @@ void ParameterReader::declare_parameters() {
             // the level-0 matrix formed on the device from (lattice size, cell matrix) instead of assembled here and uploaded
             // as CSR (gmg_set_level_matrix_lattice; 3D constant-coefficient problems with a lexicographic, unpartitioned level 0)
             {"Level 0 matrix on device", "true"},
+            // the active-mesh system matrix formed on the device from the cells' DoFs, the per-level cell matrix and the
+            // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; constant-coefficient
+            // problems on one rank, DESIGN.md section 12
+            {"System matrix on device", "false"},
             // MGTransferPrebuilt::build_matrices on the device (gmg_build_transfer) instead of here + upload
             {"Transfer matrices on device", "true"},
             // the right-hand side integrated on the device from densities that stay there (gmg_rhs_assemble)
@@ -308,6 +316,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   if (p.refinement_estimator != "Kelly + residual" && p.refinement_estimator != "Kelly")
     throw std::runtime_error("Refinement estimator must be <Kelly + residual> or <Kelly>");
   p.level0_matrix_on_device = prm.get_bool("Level 0 matrix on device");
+  p.system_matrix_on_device = prm.get_bool("System matrix on device");
   p.transfer_on_device = prm.get_bool("Transfer matrices on device");
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
@@ -895,16 +904,102 @@ void cell_matrix(const Quadrature<dim> &q2, double h, const double x0[3], Coef c
       }
   }
 }
+
+// The cell matrix and the constraint lines of an active cell as assemble_system takes them.  One text for the matrix pass,
+// the right-hand-side pass and the K_of_level table of gmg_assemble_system_matrix: the device's matrix has the host's bits
+// only as long as all three scale the cell matrix the same way.
+template <int dim>
+struct CellAssembly {
+  static constexpr int nv = 1 << dim;
+  using Line = typename LaplaceProblem<dim>::ConstraintLine;
+  const LaplaceProblem<dim> &P;
+  const Quadrature<dim> q_laplace;
+  const bool constant_coef;
+  double Kc[nv][nv];  // constant coefficient: the cell matrix of the unit cell
+  explicit CellAssembly(const LaplaceProblem<dim> &p) : P(p), q_laplace((int)p.par.degree + 1), constant_coef(p.par.Problemtype != "Step16") {
+    double x0[3] = {0, 0, 0};
+    if (constant_coef) cell_matrix<dim>(q_laplace, 1.0, x0, [](const double *) { return 1.0; }, true, Kc);
+  }
+  // constant coefficient: the cell matrix of a cell with edge h
+  void scaled(double h, double (&K)[nv][nv]) const {
+    const double s = std::pow(h, dim - 2);
+    for (int i = 0; i < nv; ++i)
+      for (int j = 0; j < nv; ++j) K[i][j] = Kc[i][j] * s;
+  }
+  void cell_K(size_t ci, double (&K)[nv][nv], double (&x0)[3], double &h) const {
+    const auto &ac = P.active_cells[ci];
+    const Cell &cell = P.triangulation.levels[(size_t)ac.level][(size_t)ac.index];
+    h = P.triangulation.cell_size(ac.level);
+    P.triangulation.cell_origin(ac.level, cell, x0);
+    if (constant_coef) scaled(h, K);
+    else cell_matrix<dim>(q_laplace, h, x0, [&](const double *x) { return P.coefficient(x); }, false, K);
+  }
+  // ConstraintMatrix::distribute_local_to_global (:793-795, 825-828)
+  void cell_lines(size_t ci, int32_t (&dofs)[nv], const Line *(&line)[nv]) const {
+    P.cell_dofs(P.active_cells[ci], dofs);
+    for (int a = 0; a < nv; ++a) {
+      const int32_t cl = P.constraint_of_dof[(size_t)dofs[a]];
+      line[a] = cl >= 0 ? &P.constraint_lines[(size_t)cl] : nullptr;
+    }
+  }
+};
 }  // namespace
 
+// Is the system matrix the kind of operator gmg_assemble_system_matrix forms?  Says so once when the key asks for it in vain.
 template <int dim>
-void LaplaceProblem<dim>::assemble_system() {
+bool LaplaceProblem<dim>::decide_system_on_device() {
+  if (!par.system_matrix_on_device) return false;
+  const char *why = !solve_on_device_requested ? "the cycle does not run on the device"
+                    : distributed              ? "the run is distributed"
+                    : par.Problemtype == "Step16" ? "the coefficient varies"
+                                                  : nullptr;
+  if (!why) return true;
+  if (!system_fallback_reported) pcout(std::string("   System matrix on device: not applicable (") + why + "), assembled on the host");
+  system_fallback_reported = true;
+  return false;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::ensure_system_matrix() {
+  // (outside assemble_system: without its sublaps, which belong to that phase's clock)
+  if (system_on_device && system_matrix.n_rows == 0 && !vertex_of_dof.empty()) assemble_system_matrix_host(false);
+}
+
+// the arrays of gmg_assemble_system_matrix: cell DoFs and levels, the cell matrix as cell_K scales it per level, the lines
+template <int dim>
+typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_assembly_inputs() const {
+  constexpr int nv = 1 << dim;
+  SystemAssemblyInputs in;
+  in.cell_dofs.resize(active_cells.size() * nv);
+  in.cell_level.resize(active_cells.size());
+  for (size_t ci = 0; ci < active_cells.size(); ++ci) {
+    cell_dofs(active_cells[ci], &in.cell_dofs[ci * nv]);
+    if (active_cells[ci].level > 15) throw std::runtime_error("System matrix on device: more than 16 levels");
+    in.cell_level[ci] = (uint8_t)active_cells[ci].level;
+  }
+  const CellAssembly<dim> ca(*this);
+  in.K_of_level.resize((size_t)16 * nv * nv);
+  for (int l = 0; l < 16; ++l) {
+    double K[nv][nv];
+    ca.scaled(triangulation.cell_size(l), K);
+    for (int i = 0; i < nv; ++i)
+      for (int j = 0; j < nv; ++j) in.K_of_level[((size_t)l * nv + (size_t)i) * nv + (size_t)j] = K[i][j];
+  }
+  in.line_ptr.assign(constraint_lines.size() + 1, 0);
+  for (size_t l = 0; l < constraint_lines.size(); ++l) {
+    in.line_ptr[l + 1] = in.line_ptr[l] + (int64_t)constraint_lines[l].entries.size();
+    in.line_inhomogeneity.push_back(constraint_lines[l].inhomogeneity);
+    for (auto &e : constraint_lines[l].entries) { in.line_master.push_back(e.first); in.line_weight.push_back(e.second); }
+  }
+  return in;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::assemble_system_matrix_host(bool laps) {
   constexpr int nv = 1 << dim;
   const int64_t n = (int64_t)vertex_of_dof.size();
-  const Quadrature<dim> q_laplace((int)par.degree + 1), q_rhs((int)(par.degree + par.quadrature_degree_rhs));
-  const bool constant_coef = par.Problemtype != "Step16";
   // coupling lists: the cell's DoFs plus the masters of its constrained DoFs
-  sublap(nullptr);
+  if (laps) sublap(nullptr);
   std::vector<int64_t> cptr(active_cells.size() + 1, 0);
   std::vector<int32_t> citems;
   citems.reserve(active_cells.size() * nv);
@@ -922,56 +1017,14 @@ void LaplaceProblem<dim>::assemble_system() {
     citems.erase(std::unique(citems.begin() + (std::ptrdiff_t)begin, citems.end()), citems.end());
     cptr[ci + 1] = (int64_t)citems.size();
   }
-  sublap("assemble: coupling lists");
+  if (laps) sublap("assemble: coupling lists");
   system_matrix = pattern_from_cells(n, cptr, citems);
-  sublap("assemble: sparsity pattern");
-  system_rhs.assign((size_t)n, 0.0);
-  // "RHS on device": the cell loop records WHERE every F_i goes (DoF, slot = cell * 2^dim + i, weight) and which Dirichlet
-  // terms it loses instead of forming F from densities the host does not have; gmg_rhs_assemble does the arithmetic
-  const bool rhs_dev = lammpsinput && densities_device_resident;
-  std::vector<int32_t> plan_dof, plan_slot, term_slot;
-  std::vector<uint8_t> plan_code;
-  std::vector<double> term_value, coef_table(256, 0.0);
-  int n_codes = 1;  // code 0: the slot's value as it is
-  auto code_of = [&](double w) -> int {
-    for (int c = 1; c < n_codes; ++c)
-      if (coef_table[(size_t)c] == w) return c;
-    if (n_codes >= 256) throw std::runtime_error("RHS on device: more than 255 distinct constraint weights");
-    coef_table[(size_t)n_codes] = w;
-    return n_codes++;
-  };
-  if (rhs_dev) { plan_dof.reserve(active_cells.size() * nv); plan_slot.reserve(active_cells.size() * nv); plan_code.reserve(active_cells.size() * nv); }
-
-  double Kc[nv][nv];
-  if (constant_coef) {
-    double x0[3] = {0, 0, 0};
-    cell_matrix<dim>(q_laplace, 1.0, x0, [&](const double *) { return 1.0; }, true, Kc);
-  }
+  if (laps) sublap("assemble: sparsity pattern");
   // One pass over the cells per THREAD for the matrix, restricted to the rows the thread owns (SURVEY 8 / VERDICT r02 #8:
   // threaded host setup): a cell is visited by the threads whose row range meets its coupling list, every entry still
   // receives its cells' contributions in cell order -- the same bits as the sequential loop, whatever the thread count.
   // The right-hand side (or the plan for gmg_rhs_assemble) follows in a sequential pass of its own.
-  auto cell_K = [&](size_t ci, double (&K)[nv][nv], double (&x0)[3], double &h) {
-    const ActiveCell &ac = active_cells[ci];
-    const Cell &cell = triangulation.levels[(size_t)ac.level][(size_t)ac.index];
-    h = triangulation.cell_size(ac.level);
-    triangulation.cell_origin(ac.level, cell, x0);
-    if (constant_coef) {
-      const double s = std::pow(h, dim - 2);
-      for (int i = 0; i < nv; ++i)
-        for (int j = 0; j < nv; ++j) K[i][j] = Kc[i][j] * s;
-    } else {
-      cell_matrix<dim>(q_laplace, h, x0, [&](const double *x) { return coefficient(x); }, false, K);
-    }
-  };
-  auto cell_lines = [&](size_t ci, int32_t (&dofs)[nv], const ConstraintLine *(&line)[nv]) {
-    cell_dofs(active_cells[ci], dofs);
-    // ConstraintMatrix::distribute_local_to_global (:793-795, 825-828)
-    for (int a = 0; a < nv; ++a) {
-      const int32_t cl = constraint_of_dof[(size_t)dofs[a]];
-      line[a] = cl >= 0 ? &constraint_lines[(size_t)cl] : nullptr;
-    }
-  };
+  const CellAssembly<dim> ca(*this);
 #pragma omp parallel
   {
     int nt = 1, tid = 0;
@@ -984,10 +1037,10 @@ void LaplaceProblem<dim>::assemble_system() {
       // (the coupling list of a cell is sorted: its first and last entries bound the rows the cell can touch)
       if (citems[(size_t)cptr[ci + 1] - 1] < r0 || citems[(size_t)cptr[ci]] >= r1) continue;
       double K[nv][nv], x0[3], h;
-      cell_K(ci, K, x0, h);
+      ca.cell_K(ci, K, x0, h);
       int32_t dofs[nv];
       const ConstraintLine *line[nv];
-      cell_lines(ci, dofs, line);
+      ca.cell_lines(ci, dofs, line);
       for (int i = 0; i < nv; ++i) {
         if (line[i]) add(dofs[i], dofs[i], std::fabs(K[i][i]));
         for (int j = 0; j < nv; ++j) {
@@ -1006,15 +1059,45 @@ void LaplaceProblem<dim>::assemble_system() {
       }
     }
   }
-  sublap("assemble: matrix pass");
+  if (laps) sublap("assemble: matrix pass");
+}
+
+template <int dim>
+void LaplaceProblem<dim>::assemble_system() {
+  constexpr int nv = 1 << dim;
+  const int64_t n = (int64_t)vertex_of_dof.size();
+  const Quadrature<dim> q_rhs((int)(par.degree + par.quadrature_degree_rhs));
+  // "System matrix on device": coupling lists, pattern and matrix pass are left to gmg_assemble_system_matrix at upload();
+  // the host forms the matrix only when somebody asks for it (ensure_system_matrix)
+  system_on_device = decide_system_on_device();
+  if (system_on_device) { system_matrix = CSRMatrix(); sublap(nullptr); }
+  else assemble_system_matrix_host();
+  system_rhs.assign((size_t)n, 0.0);
+  // "RHS on device": the cell loop records WHERE every F_i goes (DoF, slot = cell * 2^dim + i, weight) and which Dirichlet
+  // terms it loses instead of forming F from densities the host does not have; gmg_rhs_assemble does the arithmetic
+  const bool rhs_dev = lammpsinput && densities_device_resident;
+  std::vector<int32_t> plan_dof, plan_slot, term_slot;
+  std::vector<uint8_t> plan_code;
+  std::vector<double> term_value, coef_table(256, 0.0);
+  int n_codes = 1;  // code 0: the slot's value as it is
+  auto code_of = [&](double w) -> int {
+    for (int c = 1; c < n_codes; ++c)
+      if (coef_table[(size_t)c] == w) return c;
+    if (n_codes >= 256) throw std::runtime_error("RHS on device: more than 255 distinct constraint weights");
+    coef_table[(size_t)n_codes] = w;
+    return n_codes++;
+  };
+  if (rhs_dev) { plan_dof.reserve(active_cells.size() * nv); plan_slot.reserve(active_cells.size() * nv); plan_code.reserve(active_cells.size() * nv); }
+
+  const CellAssembly<dim> ca(*this);
   for (size_t ci = 0; ci < active_cells.size(); ++ci) {
     double K[nv][nv], x0[3], h;
     int32_t dofs[nv];
     const ConstraintLine *line[nv];
-    cell_lines(ci, dofs, line);
+    ca.cell_lines(ci, dofs, line);
     bool any_inhom = false;
     for (int a = 0; a < nv; ++a) any_inhom = any_inhom || (line[a] && line[a]->inhomogeneity != 0.0);
-    if (!rhs_dev || any_inhom) cell_K(ci, K, x0, h);
+    if (!rhs_dev || any_inhom) ca.cell_K(ci, K, x0, h);
     else { h = triangulation.cell_size(active_cells[ci].level); }
     double F[nv];
     for (int i = 0; i < nv; ++i) F[i] = 0;
@@ -1303,7 +1386,32 @@ int LaplaceProblem<dim>::upload() {
   // (the default leaves the context's own setting: GMG_OPTIONS=ssor_balanced=1 measures the unchanged driver)
   if (par.ssor_partition == "balanced") GMGC(gmg_set_ssor_partition(gmg, GMG_SSOR_PARTITION_BALANCED));
   const CSRMatrix &S = system_matrix;
-  if (distributed) {
+  const int64_t n_system = (int64_t)vertex_of_dof.size();
+  if (system_on_device) {
+    // the active-mesh matrix is formed on the device from the cells' DoFs and the constraint lines
+    const SystemAssemblyInputs in = system_assembly_inputs();
+    sublap(nullptr);
+    double build_ms = 0.0;
+    const int rc_asm = gmg_assemble_system_matrix(gmg, dim, n_system, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(),
+                                                  in.K_of_level.data(), constraint_of_dof.data(), (int64_t)constraint_lines.size(), in.line_ptr.data(),
+                                                  in.line_master.data(), in.line_weight.data(), &build_ms);
+    if (rc_asm == GMG_ERR_UNSUPPORTED) {
+      // a mesh the device assembly does not take (a row wider than its limit, sizes beyond 32-bit indices): the host path
+      if (!system_fallback_reported) pcout(std::string("   System matrix on device: not applicable (") + gmg_last_error(gmg) + "), assembled on the host");
+      system_fallback_reported = true;
+      system_on_device = false;
+      assemble_system_matrix_host(false);
+    } else if (rc_asm != GMG_OK) {
+      last_error = std::string("gmg_assemble_system_matrix: ") + gmg_last_error(gmg);
+      return rc_asm;
+    } else {
+      sublap("assemble: matrix on device");
+      if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+      d_begin = 0; d_n = d_nvec = n_system;
+    }
+  }
+  if (system_on_device) {  // (formed above)
+  } else if (distributed) {
     // system matrix + outer-CG vectors and level 0 are row-partitioned (canonical equal chunks),
     // levels >= 1, transfers and copy indices are replicated.  A level 0 whose
     // coarse-CG iteration is shorter than the three collectives it would need stays replicated.
@@ -1363,7 +1471,7 @@ int LaplaceProblem<dim>::upload() {
   GMGC(gmg_set_coarse(gmg, 1e-10, 1000));  // :962
   GMGC(gmg_vec_alloc(gmg, d_nvec, &d_solution));
   GMGC(gmg_vec_alloc(gmg, d_nvec, &d_rhs));
-  const int64_t chunk = (S.n_rows + n_ranks - 1) / n_ranks;
+  const int64_t chunk = (n_system + n_ranks - 1) / n_ranks;
   GMGC(gmg_vec_alloc(gmg, chunk * n_ranks, &d_full));
   GMGC(gmg_vec_upload(gmg, d_rhs, system_rhs.data() + d_begin, d_n));
   GMGC(gmg_comm_barrier(gmg));  // the ranks' assembly times differ by seconds; inside the solve they wait for each other in kernels
@@ -1462,9 +1570,13 @@ int LaplaceProblem<dim>::solve() {
   rep.rhs_l1 = rep.rhs_l2 = rep.rhs_linf = 0;
   for (double v : system_rhs) { rep.rhs_l1 += std::fabs(v); rep.rhs_l2 += v * v; rep.rhs_linf = std::max(rep.rhs_linf, std::fabs(v)); }
   rep.rhs_l2 = std::sqrt(rep.rhs_l2);
-  rep.matrix_l1 = system_matrix.l1_norm();
-  rep.matrix_linf = system_matrix.linfty_norm();
-  rep.matrix_frobenius = system_matrix.frobenius_norm();
+  if (system_on_device && system_matrix.n_rows == 0) {  // the matrix exists on the device only
+    GMGC(gmg_system_matrix_norms(gmg, &rep.matrix_l1, &rep.matrix_linf, &rep.matrix_frobenius));
+  } else {
+    rep.matrix_l1 = system_matrix.l1_norm();
+    rep.matrix_linf = system_matrix.linfty_norm();
+    rep.matrix_frobenius = system_matrix.frobenius_norm();
+  }
   pcout("   L1 rhs norm " + fmt("%.10e", rep.rhs_l1));
   pcout("   L2 rhs norm " + fmt("%.10e", rep.rhs_l2));
   pcout("   LInfinity rhs norm " + fmt("%.10e", rep.rhs_linf));

@@ -78,6 +78,7 @@ struct Parameters {
   bool rhs_on_device = true;            // gmg_rhs_assemble: F integrated on the device from densities that stay there
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
+  bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (constant coefficient, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   static Parameters from(const ParameterReader &prm);
 };
@@ -118,6 +119,17 @@ class LaplaceProblem {
   void ensure_host_densities();                                          // copy device-resident densities out when the host needs them
   void compute_moments();                                                // :577-644
   void assemble_system();                                                // :735-833
+  void assemble_system_matrix_host(bool laps = true);                               // the matrix part of assemble_system: coupling lists, pattern, values
+  void ensure_system_matrix();                                           // assemble a system matrix that was left to the device, on demand
+  bool decide_system_on_device();                                        // system matrix formed on the device (gmg_assemble_system_matrix)?
+  // what gmg_assemble_system_matrix takes, from the current mesh and constraints
+  struct SystemAssemblyInputs {
+    std::vector<int32_t> cell_dofs, line_master;
+    std::vector<uint8_t> cell_level;
+    std::vector<double> K_of_level, line_weight, line_inhomogeneity;
+    std::vector<int64_t> line_ptr;
+  };
+  SystemAssemblyInputs system_assembly_inputs() const;
   void assemble_multigrid();                                             // :835-933
   void assemble_level(int l);                                            // one level's matrix + interface matrix (:869-931)
   void ensure_level_matrix(int l);                                       // assemble a level that was left to the device, on demand
@@ -173,6 +185,8 @@ class LaplaceProblem {
   gmg_context *gmg = nullptr;
   bool operators_uploaded = false, densities_on_device = false;
   bool solve_on_device_requested = false, level0_on_device = false, transfer_on_device = false;
+  bool system_on_device = false;           // this cycle's system matrix is formed by gmg_assemble_system_matrix at upload()
+  bool system_fallback_reported = false;   // "System matrix on device" was set but not applicable: said once
   bool densities_device_resident = false;  // compute_charge_densities left them in HBM for gmg_rhs_assemble
   double build_matrices_ms = 0.0;  // device time of gmg_build_transfer for the current cycle's operators
   std::string last_error;

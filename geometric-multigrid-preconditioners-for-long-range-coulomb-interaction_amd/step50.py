@@ -83,6 +83,7 @@ def prm_text(**kw) -> str:
         "refinement_estimator": ("Misc", "Refinement estimator"),
         "level0_numbering": ("Misc", "Level 0 numbering"),
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
+        "system_matrix_on_device": ("Misc", "System matrix on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
         "rhs_on_device": ("Misc", "RHS on device"),
         "short_range_cutoff": ("Misc", "Short-range cutoff in smoothing lengths"),
@@ -297,6 +298,42 @@ class Problem:
             copy_global=[self.copy_indices(l)[0] for l in range(L)],
             copy_level=[self.copy_indices(l)[1] for l in range(L)],
             constrained=self.constrained_mask())
+
+    def system_assembly_inputs(self):
+        """The arrays the driver hands to gmg_assemble_system_matrix for the current mesh: namespace(dim, n_dofs, cell_dofs
+        [n_cells, 2^dim], cell_level, K_of_level [16, 2^dim, 2^dim], constraint_of_dof, line_ptr, line_master, line_weight,
+        line_inhomogeneity [n_lines])."""
+        sz = (C.c_int64 * 4)()
+        self._chk(self.L.step50_system_assembly_sizes(self.h, sz), "system_assembly_inputs")
+        n_dofs, n_cells, n_lines, n_ent = (int(v) for v in sz)
+        dim = int(self.L.step50_dim(self.h))
+        nv = 1 << dim
+        cd, lv = np.zeros((n_cells, nv), dtype=np.int32), np.zeros(n_cells, dtype=np.uint8)
+        K, cons = np.zeros((16, nv, nv)), np.zeros(n_dofs, dtype=np.int32)
+        lp, lm, lw, li = np.zeros(n_lines + 1, dtype=np.int64), np.zeros(n_ent, dtype=np.int32), np.zeros(n_ent), np.zeros(n_lines)
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        self._chk(self.L.step50_system_assembly_inputs(self.h, P(cd, C.c_int32), P(lv, C.c_uint8), P(K, C.c_double), P(cons, C.c_int32),
+                                                       P(lp, C.c_int64), P(lm, C.c_int32), P(lw, C.c_double), P(li, C.c_double)),
+                  "system_assembly_inputs")
+        return SimpleNamespace(dim=dim, n_dofs=n_dofs, cell_dofs=cd, cell_level=lv, K_of_level=K, constraint_of_dof=cons, line_ptr=lp,
+                               line_master=lm, line_weight=lw, line_inhomogeneity=li)
+
+    def device_system_matrix(self):
+        """The system matrix as the device holds it after a cycle with "System matrix on device" (gmg_get_system_matrix)."""
+        from . import capi
+        return capi.Context.view(self.gmg_context()).get_system_matrix()
+
+    def system_matrix_on_device(self) -> bool:
+        """Did the last upload form the system matrix on the device?"""
+        return bool(self.L.step50_system_matrix_on_device(self.h))
+
+    def refine_flags(self):
+        """The refinement marks of the cycle just estimated, all levels concatenated (uint8)."""
+        self.L.step50_refine_flags.restype = C.c_int64
+        n = self.L.step50_refine_flags(self.h, None)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self.L.step50_refine_flags(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out[:n]
 
     def set_communicator(self, rank, n_ranks, uid: bytes):
         buf = C.create_string_buffer(uid, 128)

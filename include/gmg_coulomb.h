@@ -286,6 +286,42 @@ int gmg_build_transfer(gmg_context *ctx, int level, int dim, int64_t n_coarse, c
 int gmg_get_transfer(gmg_context *ctx, int level, int transposed, int64_t *n_rows, int64_t *n_cols, int64_t *nnz,
                      int64_t *rowptr, int32_t *col, double *val);
 
+/* The active-mesh system matrix formed on the device instead of a host-assembled CSR (gmg_set_system_matrix): pattern and
+ * values of LaplaceProblem::assemble_system for a constant-coefficient problem, from the cells' DoFs cell_dofs
+ * [n_cells * 2^dim] (vertex a = bx + 2 by + 4 bz), their levels cell_level [n_cells] (< 16), the cell matrix as the host
+ * scales it per level K_of_level [16][2^dim][2^dim] (row-major), constraint_of_dof [n_dofs] (-1 or a line index) and the
+ * constraint lines in CSR form (line l: entries e in [line_ptr[l], line_ptr[l + 1]) with master line_master[e] and weight
+ * line_weight[e]; a Dirichlet line has no entries).  Afterwards the context is in the state gmg_set_system_matrix leaves
+ * it in (operator, Jacobi diagonal, scratch): gmg_spmv(GMG_SYSTEM), gmg_precondition_jacobi and gmg_cg_solve work on it;
+ * the operator is kept as CSR and applied by the row-window kernel, whose rows are summed in stored order.
+ * Pattern: a cell's coupling list is its DoFs plus the masters of its constrained DoFs; row r stores the sorted union of
+ * the coupling lists of all cells whose list contains r.  Stored zeros are kept (a constrained row carries all of its
+ * couplings as zeros).
+ * Values: every stored entry starts at +0.0 and receives its contributions in the order of the sequential loop -- cells
+ * ascending, then i, then j, then the entries ri of i's line, then the entries rj of j's line:
+ *   neither constrained: (dofs[i], dofs[j]) += K[i][j];   i constrained: (master(ri), dofs[j]) += w(ri) * K[i][j];
+ *   j constrained: (dofs[i], master(rj)) += w(rj) * K[i][j];   both: (master(ri), master(rj)) += (w(ri) * w(rj)) * K[i][j];
+ * a pair is skipped when either side is a line without entries, and a constrained i adds |K[i][i]| to (dofs[i], dofs[i])
+ * before its j loop.  fp64, no contraction into fused multiply-adds, no floating-point atomics: the same bits as the host's
+ * CSRMatrix for any launch shape (option assemble_max_blocks).  build_ms (may be NULL): device time of the build.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a DoF or master outside
+ * [0, n_dofs), a line index outside [0, n_lines), a line_ptr that starts below 0 or decreases, a level of 16 or more, or a
+ * NULL array of nonzero length.  GMG_ERR_UNSUPPORTED on a context with a communicator, for a row with more than 512
+ * columns and for sizes beyond 32-bit device indices; the context then holds no system matrix and the caller assembles on
+ * the host (gmg_set_system_matrix).  Zero cells are valid: n_dofs empty rows.                                          */
+int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                               const uint8_t *cell_level, const double *K_of_level, const int32_t *constraint_of_dof,
+                               int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master, const double *line_weight,
+                               double *build_ms);
+/* The CSR of the system matrix as the device holds it (after gmg_assemble_system_matrix; gmg_set_system_matrix keeps no CSR
+ * copy: GMG_ERR_UNSUPPORTED): with rowptr == NULL only the sizes are returned.                                         */
+int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val);
+/* Norms of that CSR (any output may be NULL).  linf: the maximum over rows of the sequential sum of |a| in stored order;
+ * l1: the maximum over columns of the sum of |a| in ascending row order, gathered through the structurally symmetric
+ * pattern -- both bit-equal to the host's CSRMatrix::linfty_norm / l1_norm.  frobenius: sqrt of the sum of squares by the
+ * two-stage partial reduction (not bit-equal: relative error at most (nnz + 2) 2^-53).                                 */
+int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *frobenius);
+
 /* ---- measurement -------------------------------------------------------------------- */
 typedef struct gmg_stats {
   int64_t coarse_solves;        /* calls of the coarse solver since the last reset           */
