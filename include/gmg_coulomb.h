@@ -120,7 +120,10 @@ int gmg_precondition(gmg_context *ctx, double *dst, const double *src);
 /* PreconditionJacobi(omega).vmult on the system matrix (:999-1004, omega = 0.6).           */
 int gmg_precondition_jacobi(gmg_context *ctx, double omega, double *dst, const double *src);
 /* MGCoarseGridIterativeSolver::operator()(0, dst, src) (:965-967): unpreconditioned CG from
- * zero on mg_matrices[0], device resident; returns iteration count and final residual.    */
+ * zero on mg_matrices[0], device resident; returns iteration count and final residual.
+ * After GMG_ERR_COARSE_NOCONV (max_it reached, or a NaN residual) dst holds the iterate after
+ * `iterations` steps, as SolverCG leaves it in dst when SolverControl throws; the context
+ * stays usable.                                                                            */
 int gmg_coarse_solve(gmg_context *ctx, double *dst, const double *src, int *iterations, double *residual);
 /* MGSmootherBase::apply (from_zero != 0) / ::smooth (from_zero == 0) on one level (:983-984). */
 int gmg_smoother_step(gmg_context *ctx, int level, double *u, const double *rhs, int from_zero);

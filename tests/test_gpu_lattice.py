@@ -10,49 +10,11 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
+from cg_reference import cell_matrix_operator, lattice_operator, q1_cell_matrix
 from gpu_util import capi
 from oracle import gmg_oracle as go
 
 pytestmark = pytest.mark.gpu
-
-
-def lattice_operator(nx, ny, nz, rng, dirichlet=True):
-    """27-point operator on an nx x ny x nz lattice, lexicographic numbering (x fastest), CSR with ascending columns.
-    Boundary vertices are Dirichlet rows (diagonal by vertex type, stored zeros towards their existing neighbours);
-    interior rows have zeros in the columns of boundary vertices (the eliminated couplings the reference keeps as stored
-    zeros); the interior coefficients are the Q1 Laplace stencil's values times h."""
-    h = 0.25
-    w = np.empty((3, 3, 3))
-    for dz in range(3):
-        for dy in range(3):
-            for dx in range(3):
-                m = abs(dz - 1) + abs(dy - 1) + abs(dx - 1)
-                w[dz, dy, dx] = h * (8.0 / 3.0, 0.0, -1.0 / 6.0, -1.0 / 12.0)[m]
-    z, y, x = np.meshgrid(np.arange(nz, dtype=np.int32), np.arange(ny, dtype=np.int32), np.arange(nx, dtype=np.int32), indexing="ij")
-    x, y, z = x.ravel(), y.ravel(), z.ravel()
-    n = nx * ny * nz
-    bnd = ((x == 0) | (x == nx - 1) | (y == 0) | (y == ny - 1) | (z == 0) | (z == nz - 1)) if dirichlet else np.zeros(n, bool)
-    kind = (x == 0).astype(np.int8) + (x == nx - 1) + (y == 0) + (y == ny - 1) + (z == 0) + (z == nz - 1)
-    # (n, 27) tables in offset order = ascending column order inside a row: no sort needed
-    ok = np.empty((n, 27), dtype=bool)
-    col = np.empty((n, 27), dtype=np.int32)
-    val = np.empty((n, 27), dtype=np.float64)
-    row = np.arange(n, dtype=np.int64)
-    j = 0
-    for dz in (-1, 0, 1):
-        for dy in (-1, 0, 1):
-            for dx in (-1, 0, 1):
-                o = (x + dx >= 0) & (x + dx < nx) & (y + dy >= 0) & (y + dy < ny) & (z + dz >= 0) & (z + dz < nz)
-                c = row + (dx + nx * dy + nx * ny * dz)
-                cc = np.where(o, c, 0)
-                v = np.where(bnd | bnd[cc], 0.0, w[dz + 1, dy + 1, dx + 1])  # eliminated rows / columns: stored zeros
-                if dz == dy == dx == 0:
-                    v = np.where(bnd, h * (4.0 / 3.0) / np.maximum(kind, 1), w[1, 1, 1])
-                ok[:, j], col[:, j], val[:, j] = o, cc, v
-                j += 1
-    rp = np.zeros(n + 1, dtype=np.int64)
-    rp[1:] = np.cumsum(ok.sum(axis=1))
-    return SimpleNamespace(n_rows=n, n_cols=n, rowptr=rp, col=col[ok], val=val[ok], nnz=int(rp[-1]))
 
 
 # (shape, lattice kernel expected): thin lattices are mostly boundary rows -- SELL padding beyond 12 % keeps them on the CSR
@@ -193,36 +155,10 @@ def test_level0_formed_on_the_device_equals_the_csr_path(shape):
     h = 0.25
     # Q1 Laplace cell matrix on a cube of edge h (the reference's K_e), any symmetric 8 x 8 matrix would do
     rng = np.random.default_rng(nx * 1000 + ny)
-    Ke = np.zeros((8, 8))
-    for a in range(8):
-        for b in range(8):
-            m = bin(a ^ b).count("1")
-            Ke[a, b] = h * (1.0 / 3.0, 0.0, -1.0 / 12.0, -1.0 / 12.0)[m]
-    Ke += 1e-3 * np.diag(rng.random(8))  # (break the symmetry between the vertices of a cell: the sums must follow the cell order)
+    Ke = q1_cell_matrix(h, rng)
     # host-style assembly: cells in lexicographic order, every cell adds Ke; CSR pattern = all pairs sharing a cell
     n = nx * ny * nz
-    bnd = np.zeros((nz, ny, nx), bool)
-    bnd[0], bnd[-1], bnd[:, 0], bnd[:, -1], bnd[:, :, 0], bnd[:, :, -1] = True, True, True, True, True, True
-    bnd = bnd.ravel()
-    dense = {}
-    import itertools
-    for cz, cy, cx in itertools.product(range(nz - 1), range(ny - 1), range(nx - 1)):
-        d = [cx + (a & 1) + nx * (cy + ((a >> 1) & 1)) + nx * ny * (cz + ((a >> 2) & 1)) for a in range(8)]
-        for a in range(8):
-            for b in range(8):
-                key = (d[a], d[b])
-                dense.setdefault(key, 0.0)
-            if bnd[d[a]]:
-                dense[(d[a], d[a])] += abs(Ke[a, a])
-            else:
-                for b in range(8):
-                    if not bnd[d[b]]:
-                        dense[(d[a], d[b])] += Ke[a, b]
-    keys = sorted(dense)
-    rows = np.array([k[0] for k in keys]); cols = np.array([k[1] for k in keys], dtype=np.int32)
-    rp = np.zeros(n + 1, dtype=np.int64)
-    np.add.at(rp, rows + 1, 1)
-    m = SimpleNamespace(n_rows=n, n_cols=n, rowptr=np.cumsum(rp), col=cols, val=np.array([dense[k] for k in keys]), nnz=len(keys))
+    m = cell_matrix_operator(shape, Ke)
     x = rng.standard_normal(n)
     ref = go.spmv(m, x)
     c = capi().Context(1)
