@@ -24,6 +24,7 @@ SYMBOLS = [
     "gmg_create", "gmg_destroy", "gmg_reset", "gmg_last_error", "gmg_synchronize",
     "gmg_set_system_matrix", "gmg_set_level_matrix", "gmg_set_level_matrix_lattice", "gmg_set_edge_matrix", "gmg_set_prolongation", "gmg_build_transfer", "gmg_get_transfer",
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
+    "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
     "gmg_vec_add", "gmg_vec_sadd", "gmg_vec_dot", "gmg_vec_norms", "gmg_vec_all_zero",
@@ -435,6 +436,51 @@ class Context:
         a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
         self._chk(self.L.gmg_system_matrix_norms(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def estimate_error(self, dim, cell_dofs, cell_level, face_kind, face_cell, h_of_level, face_measure_of_level, diameter_of_level,
+                       gauss_x, gauss_w, u, residual=0, weight=None, jxw_of_level=None, dens=None, fraction=0.6, n_u=None, validate=True):
+        """The error estimator and the refinement marks formed on the device (gmg_estimate_error): namespace(eta [n_cells]
+        float32, kelly_sq, residual_sq [n_cells], face_int [n_cells, 2 dim], threshold, mark [n_cells] uint8, n_marked,
+        build_ms).  u: a DeviceVector with the constraint-distributed solution; dens: [n_cells, nq] host array, or None for
+        the densities charge_density(..., dens=None) left on the device (nq = len(weight)).  validate=True checks the shapes
+        here (ValueError) before the library sees them; the library checks the contents."""
+        from types import SimpleNamespace
+        ok = dim in (2, 3)
+        nv, nfc, nf = (1 << int(dim), 1 << (int(dim) - 1), 2 * int(dim)) if ok else (8, 4, 6)
+        cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        lv = np.ascontiguousarray(cell_level, dtype=np.uint8)
+        fk = np.ascontiguousarray(face_kind, dtype=np.uint8)
+        fc = np.ascontiguousarray(face_cell, dtype=np.int32)
+        tabs = [np.ascontiguousarray(t, dtype=np.float64) for t in (h_of_level, face_measure_of_level, diameter_of_level)]
+        gx, gw = np.ascontiguousarray(gauss_x, dtype=np.float64), np.ascontiguousarray(gauss_w, dtype=np.float64)
+        w = np.ascontiguousarray([] if weight is None else weight, dtype=np.float64)
+        jxw = np.ascontiguousarray([] if jxw_of_level is None else jxw_of_level, dtype=np.float64)
+        de = None if dens is None else np.ascontiguousarray(dens, dtype=np.float64)
+        n_cells, nq = len(lv), len(w)
+        if validate:
+            if not ok:
+                raise ValueError("estimate_error: dim must be 2 or 3")
+            if cd.size != n_cells * nv or fk.size != n_cells * nf or fc.size != n_cells * nf * nfc:
+                raise ValueError("estimate_error: cell_dofs / face_kind / face_cell do not match cell_level")
+            if any(t.size != 16 for t in tabs) or (residual and jxw.size != 16):
+                raise ValueError("estimate_error: the per-level tables have 16 entries")
+            if len(gx) != len(gw):
+                raise ValueError("estimate_error: gauss_x / gauss_w differ in length")
+            if de is not None and de.size != n_cells * nq:
+                raise ValueError("estimate_error: dens must be [n_cells, nq]")
+        eta, mark = np.zeros(n_cells, dtype=np.float32), np.zeros(n_cells, dtype=np.uint8)
+        ksq, rsq, fi = np.zeros(n_cells), np.zeros(n_cells), np.zeros((n_cells, nf))
+        thr, ms, nm = C.c_double(0), C.c_double(0), C.c_int64(0)
+        opt = lambda a, t: _p(a, t) if a is not None and a.size else None
+        D = C.c_double
+        self._chk(self.L.gmg_estimate_error(self.h, C.c_int(int(dim)), C.c_int64(n_cells), opt(cd, C.c_int32), opt(lv, C.c_uint8), opt(fk, C.c_uint8),
+                                            opt(fc, C.c_int32), opt(tabs[0], D), opt(tabs[1], D), opt(tabs[2], D), C.c_int(len(gx)), opt(gx, D),
+                                            opt(gw, D), u.ptr if u is not None else None, C.c_int64(int(u.n if n_u is None else n_u) if u is not None else 0),
+                                            C.c_int(int(residual)), C.c_int(nq), opt(w, D), opt(jxw, D), opt(de, D), C.c_double(fraction),
+                                            opt(eta, C.c_float), opt(ksq, D), opt(rsq, D), opt(fi, D), C.byref(thr), opt(mark, C.c_uint8),
+                                            C.byref(nm), C.byref(ms)))
+        return SimpleNamespace(eta=eta, kelly_sq=ksq, residual_sq=rsq, face_int=fi, threshold=thr.value, mark=mark, n_marked=nm.value,
+                               build_ms=ms.value)
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

@@ -20,6 +20,7 @@
 #include "gmg_forces.hpp"
 #include "gmg_exact.hpp"
 #include "gmg_assemble.hpp"
+#include "gmg_estimate.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -213,6 +214,7 @@ struct gmg_context {
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
+  int estimate_max_blocks = 0;  // gmg_estimate.hpp: the same cap for the estimator's kernels (option "estimate_max_blocks"); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
   int64_t sys_global = 0, l0_global = 0;  // l0_global == 0 on a communicator: level 0 is replicated, only the outer CG is partitioned
@@ -3581,6 +3583,123 @@ int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *
   return GMG_OK;
 }
 
+// ---- error estimator and refinement marks formed on the device (gmg_estimate.hpp) ----
+
+int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level, const uint8_t *face_kind,
+                       const int32_t *face_cell, const double *h_of_level, const double *face_measure_of_level, const double *diameter_of_level,
+                       int ng, const double *gauss_x, const double *gauss_w, const double *u, int64_t n_u, int residual, int nq,
+                       const double *weight, const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq,
+                       double *residual_sq, double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: dim must be 2 or 3");
+  if (n_cells < 0 || n_u < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: negative size");
+  if (ng < 1 || ng > kEstMaxGauss) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: ng must be in 1 .. 8");
+  if (residual < 0 || residual > 2) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: residual must be 0, 1 or 2");
+  if (residual && (nq < 1 || nq > 512)) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: nq must be in 1 .. 512");
+  if (!std::isfinite(fraction) || fraction < 0.0) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: fraction must be finite and not negative");
+  const int nv = 1 << dim, nfc = 1 << (dim - 1), nf = 2 * dim;
+  if (!gauss_x || !gauss_w || !h_of_level || !face_measure_of_level || !diameter_of_level || (residual && (!weight || !jxw_of_level)) ||
+      (n_cells > 0 && (!cell_dofs || !cell_level || !face_kind || !face_cell)) || (n_u > 0 && !u))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: an array of nonzero length is NULL");
+  if (n_cells * nf * nfc >= ((int64_t)1 << 31) || n_cells * (residual ? nq : 1) >= ((int64_t)1 << 40))
+    return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_estimate_error: more than 2^31 face entries");
+  if (residual && !dens && n_cells > 0 && (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq))
+    return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: no densities of this shape on the device (gmg_charge_density(..., dens = NULL))");
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: cell level of 16 or more");
+  for (int64_t s = 0; s < n_cells * nv; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: DoF outside [0, n_u)");
+  for (int64_t c = 0; c < n_cells; ++c)
+    for (int f = 0; f < nf; ++f) {
+      const int64_t slot = c * nf + f;
+      const int kind = face_kind[slot], l = cell_level[c];
+      const int32_t *fc = face_cell + slot * nfc;
+      if (kind > 3) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face kind above 3");
+      const int n_idx = kind == 0 ? 0 : kind == 2 ? nfc : 1, want = kind == 1 ? l : kind == 2 ? l + 1 : l - 1;
+      for (int k = 0; k < n_idx; ++k) {
+        if (fc[k] < 0 || fc[k] >= n_cells) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face_cell index outside [0, n_cells)");
+        if ((int)cell_level[fc[k]] != want) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: the level of a face neighbour does not fit the kind of its face");
+      }
+      if (kind == 3 && (fc[1] < 0 || fc[1] >= nfc)) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: quadrant outside [0, 2^(dim-1))");
+    }
+  if (n_cells == 0) {  // as the host: the maximum over nothing is 0
+    if (threshold) *threshold = fraction * 0.0;
+    if (n_marked) *n_marked = 0;
+    if (build_ms) *build_ms = 0.0;
+    return GMG_OK;
+  }
+  (void)hipSetDevice(ctx->device);
+  const size_t nc = (size_t)n_cells;
+  DevPtr<int32_t> d_cd, d_fc;
+  DevPtr<uint8_t> d_lv, d_fk, d_mark;
+  DevPtr<double> d_dens, d_w, d_fi, d_k, d_r, d_thr;
+  DevPtr<float> d_eta, d_part;
+  DevPtr<unsigned long long> d_count;
+  Event e0, e1;
+  HIPC(upload(d_cd, cell_dofs, nc * nv, ctx->stream));
+  HIPC(upload(d_lv, cell_level, nc, ctx->stream));
+  HIPC(upload(d_fk, face_kind, nc * nf, ctx->stream));
+  HIPC(upload(d_fc, face_cell, nc * nf * nfc, ctx->stream));
+  if (residual) {
+    HIPC(upload(d_w, weight, (size_t)nq, ctx->stream));
+    if (dens) HIPC(upload(d_dens, dens, nc * (size_t)nq, ctx->stream));
+  }
+  HIPC(d_fi.alloc(nc * nf));
+  HIPC(d_k.alloc(nc));
+  HIPC(d_r.alloc(nc));
+  HIPC(d_eta.alloc(nc));
+  HIPC(d_mark.alloc(nc));
+  HIPC(d_thr.alloc(1));
+  HIPC(d_count.alloc(1));
+  const int cap = ctx->estimate_max_blocks;
+  auto blocks = [&](int64_t n, int most) {
+    int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + kEstThreads - 1) / kEstThreads));
+    if (cap > 0) g = std::min<int64_t>(g, cap);
+    return (unsigned)g;
+  };
+  const unsigned g_slots = blocks(n_cells * nf, 1 << 16), g_cells = blocks(n_cells, kEstMaxBlocks);
+  HIPC(d_part.alloc(g_cells));
+  EstArgs a{};
+  a.dim = dim; a.nv = nv; a.nfc = nfc; a.nf = nf; a.ng = ng; a.nq = residual ? nq : 0; a.residual = residual; a.n_cells = n_cells;
+  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.face_kind = d_fk.get(); a.face_cell = d_fc.get(); a.u = u;
+  a.dens = !residual ? nullptr : dens ? d_dens.get() : ctx->dens_dev.get();
+  a.weight = d_w.get();
+  for (int l = 0; l < 16; ++l) {
+    a.h[l] = h_of_level[l]; a.measure[l] = face_measure_of_level[l]; a.diameter[l] = diameter_of_level[l];
+    a.jxw[l] = residual ? jxw_of_level[l] : 0.0;
+  }
+  for (int q = 0; q < ng; ++q) { a.gx[q] = gauss_x[q]; a.gw[q] = gauss_w[q]; }
+  a.fraction = fraction;
+  a.face_int = d_fi.get(); a.kelly_sq = d_k.get(); a.residual_sq = d_r.get(); a.eta = d_eta.get(); a.partial = d_part.get();
+  a.n_partial = (int)g_cells; a.threshold = d_thr.get(); a.mark = d_mark.get(); a.n_marked = d_count.get();
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(hipMemsetAsync(d_count.get(), 0, sizeof(unsigned long long), ctx->stream));
+  if (dim == 2) hipLaunchKernelGGL(est_face_kernel<2>, dim3(g_slots), dim3(kEstThreads), 0, ctx->stream, a);
+  else hipLaunchKernelGGL(est_face_kernel<3>, dim3(g_slots), dim3(kEstThreads), 0, ctx->stream, a);
+  hipLaunchKernelGGL(est_cell_kernel, dim3(g_cells), dim3(kEstThreads), 0, ctx->stream, a);
+  hipLaunchKernelGGL(est_mark_kernel, dim3(g_cells), dim3(kEstThreads), 0, ctx->stream, a);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  double thr = 0.0;
+  unsigned long long count = 0;
+  if (eta) HIPC(hipMemcpyAsync(eta, d_eta.get(), sizeof(float) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  if (kelly_sq) HIPC(hipMemcpyAsync(kelly_sq, d_k.get(), sizeof(double) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  if (residual_sq) HIPC(hipMemcpyAsync(residual_sq, d_r.get(), sizeof(double) * nc, hipMemcpyDeviceToHost, ctx->stream));
+  if (face_int) HIPC(hipMemcpyAsync(face_int, d_fi.get(), sizeof(double) * nc * nf, hipMemcpyDeviceToHost, ctx->stream));
+  if (mark) HIPC(hipMemcpyAsync(mark, d_mark.get(), nc, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&thr, d_thr.get(), sizeof thr, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&count, d_count.get(), sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (threshold) *threshold = thr;
+  if (n_marked) *n_marked = (int64_t)count;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  RETURN_LAUNCHED(ctx);
+}
+
 // ---- distributed ----
 
 int gmg_comm_unique_id(void *out_id) { return comm_unique_id(out_id) ? GMG_ERR_COMM : GMG_OK; }
@@ -3769,6 +3888,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "assemble_max_blocks") {
     if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "assemble_max_blocks: an integer in 0 .. 65536");
     ctx->assemble_max_blocks = (int)value;
+  }
+  else if (k == "estimate_max_blocks") {
+    if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "estimate_max_blocks: an integer in 0 .. 65536");
+    ctx->estimate_max_blocks = (int)value;
   }
   else if (k == "exact_chunk_log2") {
     if (!(value >= 0 && value <= 35) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "exact_chunk_log2: an integer in 0 .. 35");

@@ -19,7 +19,7 @@
 namespace step50 {
 
 template <int dim>
-void LaplaceProblem<dim>::estimate_error_and_mark_cells() {
+void LaplaceProblem<dim>::estimate_error_host() {
   constexpr int nv = 1 << dim;
   constexpr int nfc = 1 << (dim - 1);  // corners of a face
   const size_t nc = active_cells.size();
@@ -183,11 +183,191 @@ void LaplaceProblem<dim>::estimate_error_and_mark_cells() {
   reports.back().refine_threshold = threshold;
   pcout("Threshold value for refinement:\t" + fmt("%.10e", threshold));
   error_per_cell = estimated_error_per_cell;
+  face_integrals.swap(face_int);
+  estimated_on_device = false;
   refine_flags.assign(triangulation.levels.size(), {});
   for (size_t l = 0; l < triangulation.levels.size(); ++l) refine_flags[l].assign(triangulation.levels[l].size(), 0);
   for (size_t a = 0; a < nc; ++a)
     if ((double)std::fabs(estimated_error_per_cell[a]) >= threshold)
       refine_flags[(size_t)active_cells[a].level][(size_t)active_cells[a].index] = 1;
+}
+
+// ---- "Error estimator on device" (DESIGN.md section 14): the same estimate through gmg_estimate_error
+
+// Every (cell, face) slot by kind, as include/gmg_coulomb.h defines them: 0 boundary, 1 active neighbour of the same level,
+// 2 neighbour refined once (its children on the face by quadrant), 3 neighbour one level coarser (its index, this cell's
+// quadrant of the coarse face).
+template <int dim>
+void LaplaceProblem<dim>::face_table(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) const {
+  constexpr int nv = 1 << dim;
+  constexpr int nfc = 1 << (dim - 1);
+  const size_t nc = active_cells.size();
+  face_kind.assign(nc * 2 * dim, 0);
+  face_cell.assign(nc * 2 * dim * nfc, 0);
+  bool unbalanced = false;
+#pragma omp parallel for schedule(static)
+  for (int64_t ai = 0; ai < (int64_t)nc; ++ai) {
+    const size_t a = (size_t)ai;
+    const int l = active_cells[a].level;
+    const Cell &c = triangulation.levels[(size_t)l][(size_t)active_cells[a].index];
+    const int nl = triangulation.n0 << l;
+    for (int d = 0; d < dim; ++d)
+      for (int side = 0; side < 2; ++side) {
+        const size_t slot = a * 2 * dim + (size_t)(2 * d + side);
+        int nb[3] = {c.c[0], c.c[1], c.c[2]};
+        nb[d] += side ? 1 : -1;
+        if (nb[d] < 0 || nb[d] >= nl) continue;  // boundary face
+        const int32_t N = triangulation.find(l, nb[0], nb[1], nb[2]);
+        int32_t bad = 0;
+        if (N < 0) {
+          // coarser neighbour; this cell's quadrant of its face from the in-face bits of the cell's own position
+          const int32_t P = l > 0 ? triangulation.find(l - 1, nb[0] >> 1, nb[1] >> 1, dim == 3 ? nb[2] >> 1 : 0) : -1;
+          const int32_t pa = P >= 0 ? active_index_of_cell[(size_t)l - 1][(size_t)P] : -1;
+          int quad = 0, k = 0;
+          for (int e = 0; e < dim; ++e)
+            if (e != d) quad |= (c.c[e] & 1) << k++;
+          face_kind[slot] = 3;
+          face_cell[slot * nfc] = pa;
+          face_cell[slot * nfc + 1] = quad;
+          bad = pa < 0;
+        } else if (triangulation.active(l, N)) {
+          face_kind[slot] = 1;
+          face_cell[slot * nfc] = active_index_of_cell[(size_t)l][(size_t)N];
+        } else {
+          const Cell &nc_ = triangulation.levels[(size_t)l][(size_t)N];
+          face_kind[slot] = 2;
+          int k = 0;
+          for (int ch = 0; ch < nv; ++ch) {
+            if (((ch >> d) & 1) != (side ? 0 : 1)) continue;
+            const int32_t fa = active_index_of_cell[(size_t)l + 1][(size_t)(nc_.first_child + ch)];
+            face_cell[slot * nfc + (size_t)k++] = fa;
+            bad |= fa < 0;
+          }
+        }
+        if (bad) {  // (reported after the loop: no exception leaves a parallel region)
+#pragma omp atomic write
+          unbalanced = true;
+        }
+      }
+  }
+  if (unbalanced) throw std::logic_error("mesh not 2:1 balanced across a face");
+}
+
+template <int dim>
+typename LaplaceProblem<dim>::EstimatorInputs LaplaceProblem<dim>::estimator_inputs() {
+  EstimatorInputs in;
+  const size_t nc = active_cells.size();
+  in.cell_dofs = active_cell_dof_table;
+  in.cell_level.resize(nc);
+  for (size_t a = 0; a < nc; ++a) {
+    if (active_cells[a].level > 15) throw std::runtime_error("Error estimator on device: more than 16 levels");
+    in.cell_level[a] = (uint8_t)active_cells[a].level;
+  }
+  face_table(in.face_kind, in.face_cell);
+  // the per-level factors exactly as the host loop forms them
+  for (int l = 0; l < 16; ++l) {
+    const double h = triangulation.cell_size(l);
+    in.h_of_level.push_back(h);
+    in.face_measure_of_level.push_back(std::pow(h, dim - 1));
+    in.diameter_of_level.push_back(h * std::sqrt((double)dim));
+    in.jxw_of_level.push_back(std::pow(h, dim));
+  }
+  gauss01((int)par.degree + 1, in.gauss_x, in.gauss_w);
+  const Quadrature<dim> q_rhs((int)(par.degree + par.quadrature_degree_rhs));
+  in.nq = (int)q_rhs.p.size();
+  in.weight = q_rhs.w;
+  const bool kelly_only = par.refinement_estimator == "Kelly";
+  // HEAD's rule takes the densities where they are; the Kelly rule forms the residual term only from densities the host
+  // has anyway (estimate_error_host: with the densities left on the device it is not formed at all)
+  if (!kelly_only && lammpsinput && densities_device_resident) {
+    in.residual = 1;
+    in.dens_resident = true;
+    return in;
+  }
+  if (lammpsinput && density_values_for_each_cell.size() != nc) return in;  // residual 0
+  in.residual = kelly_only ? 2 : 1;
+  in.dens.resize(nc * (size_t)in.nq);
+#pragma omp parallel for schedule(static)
+  for (int64_t ai = 0; ai < (int64_t)nc; ++ai) {
+    const size_t a = (size_t)ai;
+    if (lammpsinput) {
+      std::copy(density_values_for_each_cell[a].begin(), density_values_for_each_cell[a].end(), in.dens.begin() + (std::ptrdiff_t)(a * (size_t)in.nq));
+      continue;
+    }
+    const ActiveCell &ac = active_cells[a];
+    const double h = triangulation.cell_size(ac.level);
+    double x0[3];
+    triangulation.cell_origin(ac.level, triangulation.levels[(size_t)ac.level][(size_t)ac.index], x0);
+    for (size_t q = 0; q < q_rhs.p.size(); ++q) {
+      double x[3] = {0, 0, 0};
+      for (int d = 0; d < dim; ++d) x[d] = x0[d] + h * q_rhs.p[q][(size_t)d];
+      in.dens[a * (size_t)in.nq + q] = rhs_function(x);
+    }
+  }
+  return in;
+}
+
+// Is this cycle's estimate one gmg_estimate_error forms?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_estimator_on_device() {
+  if (!par.estimator_on_device) return false;
+  const char *why = !solve_on_device_requested ? "the cycle does not run on the device" : distributed ? "the run is distributed" : nullptr;
+  if (!why) return true;
+  if (!estimator_fallback_reported) pcout(std::string("   Error estimator on device: not applicable (") + why + "), estimated on the host");
+  estimator_fallback_reported = true;
+  return false;
+}
+
+template <int dim>
+int LaplaceProblem<dim>::estimate_error_device() {
+  if (solution.size() != vertex_of_dof.size()) { last_error = "error estimator: no solution of this mesh"; return GMG_ERR_INVALID; }
+  const size_t nc = active_cells.size();
+  sublap(nullptr);
+  const EstimatorInputs in = estimator_inputs();
+  sublap("estimate: face table, inputs");
+  if (ensure_context() != GMG_OK) return GMG_ERR_HIP;
+  double *d_u = nullptr;
+  if (gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u) != GMG_OK) { last_error = std::string("gmg_vec_alloc: ") + gmg_last_error(gmg); return GMG_ERR_HIP; }
+  std::vector<float> eta(nc, 0.f);
+  std::vector<double> kelly(nc, 0.0), res(nc, 0.0), fi(nc * 2 * dim, 0.0);
+  std::vector<uint8_t> mark(nc, 0);
+  double threshold = 0.0, build_ms = 0.0;
+  int64_t n_marked = 0;
+  int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+  sublap("estimate: upload of u");
+  if (rc == GMG_OK)
+    rc = gmg_estimate_error(gmg, dim, (int64_t)nc, in.cell_dofs.data(), in.cell_level.data(), in.face_kind.data(), in.face_cell.data(),
+                            in.h_of_level.data(), in.face_measure_of_level.data(), in.diameter_of_level.data(), (int)in.gauss_x.size(),
+                            in.gauss_x.data(), in.gauss_w.data(), d_u, (int64_t)solution.size(), in.residual, in.nq, in.weight.data(),
+                            in.jxw_of_level.data(), in.dens_resident || in.dens.empty() ? nullptr : in.dens.data(), in.fraction, eta.data(),
+                            kelly.data(), res.data(), fi.data(), &threshold, mark.data(), &n_marked, &build_ms);
+  if (rc != GMG_OK) last_error = std::string("gmg_estimate_error: ") + gmg_last_error(gmg);
+  gmg_vec_free(gmg, d_u);
+  if (rc != GMG_OK) return rc;
+  sublap("estimate: on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+  error_per_cell.swap(eta);
+  estimator_kelly_sq.swap(kelly);
+  estimator_residual_sq.swap(res);
+  face_integrals.swap(fi);
+  estimated_on_device = true;
+  reports.back().refine_threshold = threshold;
+  pcout("Threshold value for refinement:\t" + fmt("%.10e", threshold));
+  refine_flags.assign(triangulation.levels.size(), {});
+  for (size_t l = 0; l < triangulation.levels.size(); ++l) refine_flags[l].assign(triangulation.levels[l].size(), 0);
+  for (size_t a = 0; a < nc; ++a)
+    if (mark[a]) refine_flags[(size_t)active_cells[a].level][(size_t)active_cells[a].index] = 1;
+  sublap("estimate: marks");
+  return GMG_OK;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::estimate_error_and_mark_cells() {
+  if (decide_estimator_on_device()) {
+    if (estimate_error_device() != GMG_OK) throw std::runtime_error(last_error);
+  } else {
+    estimate_error_host();
+  }
 }
 
 template <int dim>

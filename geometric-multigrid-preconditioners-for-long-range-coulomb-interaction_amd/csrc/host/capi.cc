@@ -349,6 +349,69 @@ int64_t step50_refine_flags(step50_problem *h, uint8_t *out) {
   return n;
 }
 
+// ---- "Error estimator on device" (DESIGN.md section 14).  step50_estimate re-runs the estimator on the current solution
+// (where: 0 the host loops, 1 gmg_estimate_error); the outputs of the last estimate; and the arrays the driver hands to
+// gmg_estimate_error for the current mesh.  sizes: dim, n_cells, n_u, ng, nq, residual, densities resident on the device
+// (dens is then not written: the driver passes NULL), length of dens
+int step50_estimate(step50_problem *h, int where) {
+  return guarded(h, [&] {
+    if (DISPATCH(h, reports).empty()) throw std::runtime_error("step50_estimate: no cycle has run");
+    if (where == 0) { DISPATCH(h, estimate_error_host()); return 0; }
+    return DISPATCH(h, estimate_error_device());
+  });
+}
+int step50_estimated_on_device(step50_problem *h) { return DISPATCH(h, estimated_on_device) ? 1 : 0; }
+int64_t step50_host_density_copies(step50_problem *h) { return DISPATCH(h, host_density_copies); }
+int step50_error_per_cell(step50_problem *h, float *eta) {
+  const auto &e = DISPATCH(h, error_per_cell);
+  if (!e.empty()) std::memcpy(eta, e.data(), sizeof(float) * e.size());
+  return 0;
+}
+// the refinement marks per active cell (step50_refine_flags: per cell of every level)
+int step50_marks(step50_problem *h, uint8_t *mark) {
+  return guarded(h, [&] {
+    auto fill = [&](auto &P) {
+      if (P.refine_flags.empty()) throw std::runtime_error("step50_marks: no cells were marked (run the estimator first)");
+      for (size_t a = 0; a < P.active_cells.size(); ++a)
+        mark[a] = P.refine_flags[(size_t)P.active_cells[a].level][(size_t)P.active_cells[a].index] != 0;
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
+int step50_face_integrals(step50_problem *h, double *face_int) {
+  const auto &f = DISPATCH(h, face_integrals);
+  if (!f.empty()) std::memcpy(face_int, f.data(), sizeof(double) * f.size());
+  return 0;
+}
+int step50_estimator_sizes(step50_problem *h, int64_t sizes[8]) {
+  return guarded(h, [&] {
+    auto fill = [&](const auto &in, int64_t n_u) {
+      sizes[0] = h->dim; sizes[1] = (int64_t)in.cell_level.size(); sizes[2] = n_u; sizes[3] = (int64_t)in.gauss_x.size();
+      sizes[4] = in.nq; sizes[5] = in.residual; sizes[6] = in.dens_resident ? 1 : 0; sizes[7] = (int64_t)in.dens.size();
+    };
+    if (h->dim == 2) fill(h->p2->estimator_inputs(), (int64_t)h->p2->vertex_of_dof.size());
+    else fill(h->p3->estimator_inputs(), (int64_t)h->p3->vertex_of_dof.size());
+    return 0;
+  });
+}
+int step50_estimator_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t *cell_level, uint8_t *face_kind, int32_t *face_cell, double *h_of_level,
+                            double *face_measure_of_level, double *diameter_of_level, double *gauss_x, double *gauss_w, double *weight,
+                            double *jxw_of_level, double *dens, double *fraction) {
+  return guarded(h, [&] {
+    auto fill = [&](const auto &in, int64_t) {
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(in.cell_dofs, cell_dofs); put(in.cell_level, cell_level); put(in.face_kind, face_kind); put(in.face_cell, face_cell);
+      put(in.h_of_level, h_of_level); put(in.face_measure_of_level, face_measure_of_level); put(in.diameter_of_level, diameter_of_level);
+      put(in.gauss_x, gauss_x); put(in.gauss_w, gauss_w); put(in.weight, weight); put(in.jxw_of_level, jxw_of_level); put(in.dens, dens);
+      *fraction = in.fraction;
+    };
+    if (h->dim == 2) fill(h->p2->estimator_inputs(), (int64_t)h->p2->vertex_of_dof.size());
+    else fill(h->p3->estimator_inputs(), (int64_t)h->p3->vertex_of_dof.size());
+    return 0;
+  });
+}
+
 // host threads of the replicated setup (one process per GPU: cores / world size)
 void step50_set_threads(int n) {
 #ifdef _OPENMP

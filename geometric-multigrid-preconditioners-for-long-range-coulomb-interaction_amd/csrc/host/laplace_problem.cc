@@ -232,6 +232,10 @@ void ParameterReader::declare_parameters() {
             // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; constant-coefficient
             // problems on one rank, DESIGN.md section 12
             {"System matrix on device", "false"},
+            // the error estimator and the refinement marks formed on the device from a face table of the forest and the
+            // solution (gmg_estimate_error) instead of the host loops of estimate_error_and_mark_cells; cycles that ran on
+            // the device, one rank, DESIGN.md section 14
+            {"Error estimator on device", "false"},
             // MGTransferPrebuilt::build_matrices on the device (gmg_build_transfer) instead of here + upload
             {"Transfer matrices on device", "true"},
             // the right-hand side integrated on the device from densities that stay there (gmg_rhs_assemble)
@@ -317,6 +321,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
     throw std::runtime_error("Refinement estimator must be <Kelly + residual> or <Kelly>");
   p.level0_matrix_on_device = prm.get_bool("Level 0 matrix on device");
   p.system_matrix_on_device = prm.get_bool("System matrix on device");
+  p.estimator_on_device = prm.get_bool("Error estimator on device");
   p.transfer_on_device = prm.get_bool("Transfer matrices on device");
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
@@ -866,6 +871,7 @@ void LaplaceProblem<dim>::ensure_host_densities() {
   const Quadrature<dim> quad((int)(par.degree + par.quadrature_degree_rhs));
   const size_t nq = quad.p.size(), nc = active_cells.size();
   std::vector<double> dens(nc * nq);
+  ++host_density_copies;
   if (gmg_get_charge_density(gmg, (int64_t)nc, (int)nq, dens.data()) != GMG_OK) throw std::runtime_error(std::string("gmg_get_charge_density: ") + gmg_last_error(gmg));
   density_values_for_each_cell.assign(nc, {});
   for (size_t ci = 0; ci < nc; ++ci) density_values_for_each_cell[ci].assign(dens.begin() + (std::ptrdiff_t)(ci * nq), dens.begin() + (std::ptrdiff_t)((ci + 1) * nq));

@@ -79,6 +79,7 @@ struct Parameters {
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (constant coefficient, one rank)
+  bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   static Parameters from(const ParameterReader &prm);
 };
@@ -142,6 +143,20 @@ class LaplaceProblem {
   int upload();                                                          // hand the operators over the C-ABI
   int solve();                                                           // :938-1017
   void estimate_error_and_mark_cells();                                  // :1020-1090
+  void estimate_error_host();                                            // its host loops
+  int estimate_error_device();                                           // the same through gmg_estimate_error
+  bool decide_estimator_on_device();                                     // "Error estimator on device" set and applicable to this cycle?
+  // what gmg_estimate_error takes, from the current forest, the parameters and the densities
+  struct EstimatorInputs {
+    std::vector<int32_t> cell_dofs, face_cell;
+    std::vector<uint8_t> cell_level, face_kind;
+    std::vector<double> h_of_level, face_measure_of_level, diameter_of_level, jxw_of_level, gauss_x, gauss_w, weight, dens;
+    int residual = 0, nq = 0;    // residual: 0 Kelly term only, 1 HEAD's rule, 2 the residual term beside the Kelly rule
+    bool dens_resident = false;  // dens stays NULL: the densities gmg_charge_density left on the device
+    double fraction = 0.6;       // :1084
+  };
+  EstimatorInputs estimator_inputs();
+  void face_table(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) const;  // the forest's faces by kind
   void refine_grid(unsigned int cycle);                                  // :1095-1121
   void postprocess_electrostatic_energy();                               // :1310-1420
   void postprocess_error_in_energy_norm();                               // :1423-1461
@@ -221,6 +236,10 @@ class LaplaceProblem {
   std::vector<float> error_per_cell;
   std::vector<double> estimator_kelly_sq, estimator_residual_sq;  // per active cell: face-jump sum / h_K^2 int (4 pi rho)^2 (kept for the marking-rule study)
   std::vector<std::vector<char>> refine_flags;
+  std::vector<double> face_integrals;      // [active cell][face]: the face integrals of the last estimate (tests)
+  bool estimated_on_device = false;        // the last estimate came from gmg_estimate_error
+  bool estimator_fallback_reported = false;  // "Error estimator on device" was set but not applicable: said once
+  int64_t host_density_copies = 0;         // how often ensure_host_densities() fetched device-resident densities
 
   void pcout(const std::string &s);
   void distribute_dofs();

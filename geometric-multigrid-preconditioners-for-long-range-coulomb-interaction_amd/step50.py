@@ -84,6 +84,7 @@ def prm_text(**kw) -> str:
         "level0_numbering": ("Misc", "Level 0 numbering"),
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
         "system_matrix_on_device": ("Misc", "System matrix on device"),
+        "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
         "rhs_on_device": ("Misc", "RHS on device"),
         "short_range_cutoff": ("Misc", "Short-range cutoff in smoothing lengths"),
@@ -334,6 +335,64 @@ class Problem:
         out = np.zeros(max(n, 1), dtype=np.uint8)
         self.L.step50_refine_flags(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         return out[:n]
+
+    def estimator_inputs(self):
+        """The arrays the driver hands to gmg_estimate_error for the current mesh: namespace(dim, n_cells, n_u, ng, nq,
+        residual, dens_resident, cell_dofs [n_cells, 2^dim], cell_level, face_kind [n_cells, 2 dim], face_cell [n_cells, 2 dim,
+        2^(dim-1)], h_of_level, face_measure_of_level, diameter_of_level, jxw_of_level [16], gauss_x, gauss_w [ng], weight [nq],
+        dens [n_cells, nq] or None (residual 0, or dens_resident: the driver passes NULL and the library takes the densities
+        gmg_charge_density left on the device), fraction)."""
+        sz = (C.c_int64 * 8)()
+        self._chk(self.L.step50_estimator_sizes(self.h, sz), "estimator_inputs")
+        dim, n_cells, n_u, ng, nq, residual, resident, n_dens = (int(v) for v in sz)
+        nv, nfc, nf = 1 << dim, 1 << (dim - 1), 2 * dim
+        cd, lv = np.zeros((n_cells, nv), dtype=np.int32), np.zeros(n_cells, dtype=np.uint8)
+        fk, fc = np.zeros((n_cells, nf), dtype=np.uint8), np.zeros((n_cells, nf, nfc), dtype=np.int32)
+        hl, fm, dl, jl = np.zeros(16), np.zeros(16), np.zeros(16), np.zeros(16)
+        gx, gw, w, dens, frac = np.zeros(ng), np.zeros(ng), np.zeros(nq), np.zeros(max(n_dens, 1)), C.c_double(0)
+        P = lambda a, t=C.c_double: a.ctypes.data_as(C.POINTER(t))
+        self._chk(self.L.step50_estimator_inputs(self.h, P(cd, C.c_int32), P(lv, C.c_uint8), P(fk, C.c_uint8), P(fc, C.c_int32), P(hl), P(fm),
+                                                 P(dl), P(gx), P(gw), P(w), P(jl), P(dens), C.byref(frac)), "estimator_inputs")
+        return SimpleNamespace(dim=dim, n_cells=n_cells, n_u=n_u, ng=ng, nq=nq, residual=residual, dens_resident=bool(resident), cell_dofs=cd,
+                               cell_level=lv, face_kind=fk, face_cell=fc, h_of_level=hl, face_measure_of_level=fm, diameter_of_level=dl,
+                               jxw_of_level=jl, gauss_x=gx, gauss_w=gw, weight=w,
+                               dens=dens[:n_dens].reshape(n_cells, nq) if n_dens else None, fraction=frac.value)
+
+    def estimate(self, on_device: bool):
+        """Re-run the estimator and the marking on the current solution: the host loops (False) or gmg_estimate_error (True),
+        whatever the prm says.  Returns the report with the new refine_threshold."""
+        self._chk(self.L.step50_estimate(self.h, C.c_int(1 if on_device else 0)), "estimate")
+        return self.report(-1)
+
+    def estimated_on_device(self) -> bool:
+        """Did the last estimate come from gmg_estimate_error?"""
+        return bool(self.L.step50_estimated_on_device(self.h))
+
+    def host_density_copies(self) -> int:
+        """How often device-resident charge densities were copied to the host (ensure_host_densities)."""
+        self.L.step50_host_density_copies.restype = C.c_int64
+        return int(self.L.step50_host_density_copies(self.h))
+
+    def error_per_cell(self):
+        """eta per active cell of the last estimate (float32)."""
+        self.L.step50_n_cells.restype = C.c_int64
+        out = np.zeros(self.L.step50_n_cells(self.h), dtype=np.float32)
+        self.L.step50_error_per_cell(self.h, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
+
+    def marks(self):
+        """The refinement marks of the last estimate per active cell (uint8)."""
+        self.L.step50_n_cells.restype = C.c_int64
+        out = np.zeros(self.L.step50_n_cells(self.h), dtype=np.uint8)
+        self._chk(self.L.step50_marks(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8))), "marks")
+        return out
+
+    def face_integrals(self):
+        """The face integrals of the last estimate, [active cells, 2 dim]."""
+        self.L.step50_n_cells.restype = C.c_int64
+        out = np.zeros((self.L.step50_n_cells(self.h), 2 * int(self.L.step50_dim(self.h))))
+        self.L.step50_face_integrals(self.h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        return out
 
     def set_communicator(self, rank, n_ranks, uid: bytes):
         buf = C.create_string_buffer(uid, 128)

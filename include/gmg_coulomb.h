@@ -325,6 +325,55 @@ int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64
  * two-stage partial reduction (not bit-equal: relative error at most (nnz + 2) 2^-53).                                 */
 int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *frobenius);
 
+/* The error estimator and the refinement marks of an adaptive cycle (src/step-50.cc:1020-1089: KellyErrorEstimator with the
+ * cell diameter as scaling, the cell residual, cells at or above a fraction of the largest indicator are marked) formed on
+ * the device from the cells' DoFs cell_dofs [n_cells * 2^dim] (vertex a = bx + 2 by + 4 bz), their levels cell_level
+ * [n_cells] (< 16), a face table and the constraint-distributed solution u (device vector, n_u entries).
+ * Face table: slot = cell * 2 dim + f, face f = 2 d + side (deal.II order), nfc = 2^(dim-1) integers per slot:
+ *   face_kind 0  domain boundary; the slot contributes nothing
+ *   face_kind 1  active neighbour on the same level; face_cell[slot * nfc] is its index
+ *   face_kind 2  the neighbour is refined once; face_cell[slot * nfc + k] is the active child occupying quadrant k of the
+ *                face (children in ascending child number; bit 0 of k is the lower in-face direction)
+ *   face_kind 3  the neighbour is one level coarser; face_cell[slot * nfc] is its index, face_cell[slot * nfc + 1] the
+ *                quadrant of the coarse face this cell occupies
+ * Values (fp64, no contraction into fused multiply-adds, this operand order):
+ *   U[c][v] = u[cell_dofs[c * 2^dim + v]];   for v ascending over the vertices with bit d clear,
+ *   g_c[k] = (U[c][v | 1 << d] - U[c][v]) / h_of_level[level(c)];
+ *   B(c, s, t) = c0 * (1 - s) * (1 - t) + c1 * s * (1 - t) + c2 * (1 - s) * t + c3 * s * t, left to right
+ *                (2D: c0 * (1 - s) + c1 * s);   gx, gw: the 1-D Gauss rule on [0, 1] with ng = degree + 1 points;
+ *   kind 1, m the minus-side and p the plus-side cell of the face: jump[k] = g_p[k] - g_m[k],
+ *     I = sum_{q1} sum_{q0} ((((j * j) * gw[q0]) * gw[q1]) * face_measure_of_level[l]) from +0.0, j = B(jump, gx[q0], gx[q1])
+ *     (2D: one q1 with weight 1.0); both cells' slots hold the same I;
+ *   sub-face of a coarse cell C (level l) and a fine cell F (level l + 1) in quadrant (Q0, Q1):
+ *     j = B(g_F, s, t) - B(g_C, 0.5 * (Q0 + s), 0.5 * (Q1 + t)), I_sub summed the same way with
+ *     face_measure_of_level[l + 1]; the kind-3 slot of F holds I_sub, the kind-2 slot of C the sum of its nfc sub-face
+ *     integrals from +0.0 in ascending k;
+ *   per cell: float acc = 0; for f ascending acc += (float)(diameter_of_level[l] * face_int[a][f]);
+ *     kelly_sq = (double)acc; eta = sqrtf(acc), correctly rounded;
+ *   residual != 0: error = sum_q ((t * t) * weight[q]) * jxw_of_level[l] with t = 0.0 + (4.0 * pi) * dens[a * nq + q] (the
+ *     densities already carry one factor 4 pi: the reference's quirk is kept); residual_sq = (diam * diam) * error;
+ *     residual == 1 (Kelly + residual): eta = (float)sqrt((double)e * e + residual_sq) with e the Kelly eta and a correctly
+ *     rounded fp64 square root; residual == 2 forms residual_sq only.  dens == NULL: the densities
+ *     gmg_charge_density(..., dens = NULL) left on the device (they must be n_cells x nq); otherwise a host array;
+ *   mx = max |eta| in fp32, threshold = fraction * (double)mx, mark[a] = |eta[a]| >= threshold, n_marked their number.
+ *     Zero cells, or u constant, give threshold 0 (and every cell marked).
+ * Every output is one sequential sum, or a maximum, per slot or cell; no floating-point atomics: the same bits as
+ * LaplaceProblem::estimate_error_and_mark_cells for any launch shape (option estimate_max_blocks).  The outputs eta
+ * [n_cells], kelly_sq, residual_sq [n_cells], face_int [n_cells * 2 dim], threshold, mark [n_cells], n_marked and build_ms
+ * (device time of the three kernels) are host memory and any of them may be NULL.  Nothing is kept in the context.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a level of 16 or more, a
+ * DoF outside [0, n_u), a kind above 3, a face_cell index outside [0, n_cells), a kind-1, -2 or -3 neighbour whose level is
+ * not l, l + 1 or l - 1, a quadrant of 2^(dim-1) or more, ng outside 1 .. 8, residual outside 0 .. 2, nq outside 1 .. 512
+ * when residual != 0, a fraction that is negative or not finite, device densities that are missing or of another shape,
+ * or a NULL array of nonzero length.                                                                                    */
+int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                       const uint8_t *face_kind, const int32_t *face_cell, const double *h_of_level,
+                       const double *face_measure_of_level, const double *diameter_of_level, int ng, const double *gauss_x,
+                       const double *gauss_w, const double *u, int64_t n_u, int residual, int nq, const double *weight,
+                       const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq,
+                       double *residual_sq, double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked,
+                       double *build_ms);
+
 /* ---- measurement -------------------------------------------------------------------- */
 typedef struct gmg_stats {
   int64_t coarse_solves;        /* calls of the coarse solver since the last reset           */
