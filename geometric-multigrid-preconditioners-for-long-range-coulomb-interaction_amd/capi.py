@@ -17,6 +17,7 @@ SYSTEM = -1
 JACOBI, SSOR, CHEBYSHEV = 0, 1, 2
 PRECOND_GMG, PRECOND_JACOBI, PRECOND_IDENTITY = 0, 1, 2
 SSOR_PARTITION_ROWS, SSOR_PARTITION_BALANCED = 0, 1
+COARSE_CG, COARSE_DIRECT = 0, 1
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/gmg_coulomb.h declares (checked by tests/test_abi.py)
@@ -26,6 +27,7 @@ SYMBOLS = [
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
+    "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
     "gmg_vec_add", "gmg_vec_sadd", "gmg_vec_dot", "gmg_vec_norms", "gmg_vec_all_zero",
     "gmg_spmv", "gmg_precondition", "gmg_precondition_jacobi", "gmg_coarse_solve", "gmg_smoother_step",
@@ -47,7 +49,7 @@ class Stats(C.Structure):
                 ("spmv0_pattern_slices", C.c_int64), ("spmv0_slices", C.c_int64), ("coarse_enqueued", C.c_int64),
                 ("spmv0_noop_samples", C.c_int64), ("spmv0_noop_ms_total", C.c_double),
                 ("sgs_samples", C.c_int64), ("sgs_ms_total", C.c_double), ("sgs_substeps", C.c_int64), ("sgs_stream_bytes", C.c_int64),
-                ("sgs_launches", C.c_int64), ("build_matrices_ms", C.c_double)]
+                ("sgs_launches", C.c_int64), ("build_matrices_ms", C.c_double), ("coarse_solver", C.c_int64)]
 
 
 class GMGError(RuntimeError):
@@ -204,6 +206,21 @@ class Context:
     def set_coarse(self, abs_tol=1e-10, max_it=1000):
         self._chk(self.L.gmg_set_coarse(self.h, C.c_double(abs_tol), C.c_int(max_it)))
 
+    def set_coarse_solver(self, kind):
+        """COARSE_CG or COARSE_DIRECT (fast diagonalisation on a lattice level 0); GMGError with code ERR_UNSUPPORTED and
+        the reason where level 0 does not qualify -- the coarse CG then stays selected."""
+        self._chk(self.L.gmg_set_coarse_solver(self.h, C.c_int(kind)))
+
+    def coarse_direct_transform(self, axis, dst, src):
+        """dst <- S_axis src on the interior of a level-0 vector (one pass of the direct coarse solver)"""
+        self._chk(self.L.gmg_coarse_direct_transform(self.h, C.c_int(axis), dst.ptr, src.ptr))
+
+    def coarse_direct_profile(self, dst, src):
+        """one direct coarse solve; the kernel times in ms of its seven launches (x, y, z + scaling, z, y, x, boundary rows)"""
+        ms = np.zeros(7)
+        self._chk(self.L.gmg_coarse_direct_profile(self.h, dst.ptr, src.ptr, _p(ms, C.c_double)))
+        return ms
+
     def load_hierarchy(self, hier):
         """Upload everything LaplaceProblem::solve consumes (any object with the attribute
         names of the hierarchy the host side produces)."""
@@ -261,9 +278,9 @@ class Context:
     def precondition_jacobi(self, omega, dst, src):
         self._chk(self.L.gmg_precondition_jacobi(self.h, C.c_double(omega), dst.ptr, src.ptr))
 
-    def coarse_solve(self, dst, src):
+    def coarse_solve(self, dst, src, want_residual=True):
         it, res = C.c_int(0), C.c_double(0)
-        rc = self.L.gmg_coarse_solve(self.h, dst.ptr, src.ptr, C.byref(it), C.byref(res))
+        rc = self.L.gmg_coarse_solve(self.h, dst.ptr, src.ptr, C.byref(it), C.byref(res) if want_residual else None)
         return it.value, res.value, rc
 
     def smoother_step(self, level, u, rhs, from_zero):
@@ -573,3 +590,25 @@ def ssor_balance_rows(m, n_blocks, use_values=True):
     if rc != OK:
         raise GMGError(rc, "gmg_ssor_balance_rows")
     return br, cost
+
+
+def coarse_direct_tables(n_cells):
+    """gmg_coarse_direct_tables (needs no device): (S [m, m], lambda [m], mu [m]) of an axis with n_cells cells, m = n_cells - 1."""
+    m = int(n_cells) - 1
+    S, lam, mu = np.zeros((max(m, 1), max(m, 1))), np.zeros(max(m, 1)), np.zeros(max(m, 1))
+    rc = load().gmg_coarse_direct_tables(C.c_int(int(n_cells)), _p(S, C.c_double), _p(lam, C.c_double), _p(mu, C.c_double))
+    if rc != OK:
+        raise GMGError(rc, "gmg_coarse_direct_tables")
+    return S, lam, mu
+
+
+def coarse_direct_separable(Ke):
+    """gmg_coarse_direct_separable (needs no device): the scale s if Ke is the separable Q1 Laplacian cell matrix, else None."""
+    ke = np.ascontiguousarray(Ke, dtype=np.float64).reshape(64)
+    s = C.c_double(0)
+    rc = load().gmg_coarse_direct_separable(_p(ke, C.c_double), C.byref(s))
+    if rc == ERR_UNSUPPORTED:
+        return None
+    if rc != OK:
+        raise GMGError(rc, "gmg_coarse_direct_separable")
+    return s.value

@@ -21,6 +21,7 @@
 #include "gmg_exact.hpp"
 #include "gmg_assemble.hpp"
 #include "gmg_estimate.hpp"
+#include "gmg_fastdiag.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -82,6 +83,8 @@ struct DevCSR {
   int64_t lat_fast_rows = 0;
   int lat_classes = 0, lat_nx = 0, lat_nxy = 0, lat_R0 = 0, lat_R1 = 0, lat_C = 0, lat_K = 0, lat_S = 0, lat_fast_blocks = 0, lat_n_gen = 0, lat_grid = 0;
   int64_t lat_gen_bytes = 0;  // stream bytes of the slices outside the interior
+  int lat_nv[3] = {0, 0, 0};  // lat_only: what gmg_set_level_matrix_lattice was given (the direct coarse solver reads them)
+  double lat_Ke[64] = {};
 };
 
 struct SgsPlan {
@@ -130,6 +133,15 @@ struct Level {
   SgsPlan sgs;
 };
 
+// the direct coarse solver's tables and scratch (gmg_fastdiag.hpp); ready while GMG_COARSE_DIRECT is selected
+struct FastDiag {
+  bool ready = false;
+  double s = 0.0;
+  int m[3] = {0, 0, 0}, ld[3] = {0, 0, 0};
+  DevPtr<double> S[3], lam[3], mu[3];
+  DevPtr<double> t1, t2;  // level-0 vectors between the passes
+};
+
 }  // namespace
 
 struct gmg_context {
@@ -148,6 +160,10 @@ struct gmg_context {
   double cheb_ratio = 30.0, cheb_lmax_user = 0.0;
   double coarse_tol = 1e-10;
   int coarse_maxit = 1000;
+  int coarse_solver = GMG_COARSE_CG;  // gmg_set_coarse_solver; back to CG with every new level-0 matrix and gmg_reset
+  bool coarse_direct_opt = false;     // option coarse_direct: select the direct solver whenever a lattice level 0 qualifies
+  int coarse_direct_max_blocks = 0;   // option coarse_direct_max_blocks: cap on the grids of its passes (0: by size); results do not depend on it
+  FastDiag fd;
   // coarse CG work space (level-0 sized)
   int64_t cg_n = 0;
   DevPtr<double> cg_g, cg_d0, cg_d1, cg_h;
@@ -892,13 +908,13 @@ int alloc_vec(gmg_context *ctx, DevPtr<double> &p, int64_t n) {
 // attached to the dispatch itself (hipExtLaunchKernelGGL): hipEventElapsedTime then gives the kernel's own
 // begin-to-end time -- what rocprofv3 --kernel-trace reports -- instead of event-record to event-record,
 // which includes the launch gap.
-template <typename K, typename A>
-inline void launch_timed(gmg_context *ctx, K kernel, dim3 grid, dim3 block, size_t lds, const A &args) {
+template <typename K, typename... A>
+inline void launch_timed(gmg_context *ctx, K kernel, dim3 grid, dim3 block, size_t lds, const A &...args) {
   if (ctx->timed_start) {
-    hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)lds, ctx->stream, ctx->timed_start, ctx->timed_stop, 0u, args);
+    hipExtLaunchKernelGGL(kernel, grid, block, (std::uint32_t)lds, ctx->stream, ctx->timed_start, ctx->timed_stop, 0u, args...);
     ctx->timed_start = ctx->timed_stop = nullptr;
   } else {
-    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args);
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx->stream, args...);
   }
 }
 
@@ -1324,18 +1340,22 @@ int run_cg_chunks(gmg_context *ctx, int later_default, EnqueueOne enqueue_one) {
 
 int coarse_solve_unfused(gmg_context *ctx, double *x, const double *b, int *iters_out, double *res_out);
 void collect_profile_samples(gmg_context *ctx);
+int coarse_solve_direct(gmg_context *ctx, double *x, const double *b, int *iters_out, double *res_out, Event *pass_ev = nullptr);
 
 int coarse_solve(gmg_context *ctx, double *x, const double *b, int *iters_out, double *res_out) {
   Level &L0 = ctx->lv[0];
   const DevCSR &A = L0.A;
   if (!A.valid) return fail(ctx, GMG_ERR_INVALID, "level-0 matrix not set");
+  if (ctx->coarse_solver == GMG_COARSE_DIRECT) return coarse_solve_direct(ctx, x, b, iters_out, res_out);
   int variant = ctx->cg_variant;
   if (l0_partitioned(ctx) || (variant == 0 && L0.n >= kUnfusedMinRowsDecl) || variant == 2 || A.lat_only)
   {
     ctx->stats.coarse_variant = 2;
+    ctx->stats.coarse_solver = GMG_COARSE_CG;
     return coarse_solve_unfused(ctx, x, b, iters_out, res_out);
   }
   ctx->stats.coarse_variant = 1;
+  ctx->stats.coarse_solver = GMG_COARSE_CG;
   const int64_t n = L0.n;
   const int g_upd = grid_for((n / 2 + 0));
   const int g_init = grid_for(n);
@@ -1371,6 +1391,112 @@ int coarse_solve(gmg_context *ctx, double *x, const double *b, int *iters_out, d
   if (res_out) *res_out = ctx->st_final.res;
   if (ctx->st_final.status != 0) return fail(ctx, GMG_ERR_COARSE_NOCONV, "coarse CG did not converge within max_it");
   return GMG_OK;
+}
+
+
+// ---- direct coarse solver (gmg_fastdiag.hpp): six transforms, one of them with the D^-1 scaling, and the boundary rows ----
+
+void drop_coarse_direct(gmg_context *ctx) {
+  ctx->fd = FastDiag();
+  ctx->coarse_solver = GMG_COARSE_CG;
+}
+
+// GMG_COARSE_DIRECT if level 0 qualifies (tables uploaded, scratch allocated); otherwise GMG_ERR_UNSUPPORTED with the
+// reason, and the context stays with the coarse CG
+int select_coarse_direct(gmg_context *ctx) {
+  drop_coarse_direct(ctx);
+  Level &L0 = ctx->lv[0];
+  const DevCSR &m = L0.A;
+  if (!m.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_set_coarse_solver: level-0 matrix not set");
+  if (l0_partitioned(ctx)) return fail(ctx, GMG_ERR_UNSUPPORTED, "level 0 is partitioned over the ranks");
+  if (!m.lat_only) return fail(ctx, GMG_ERR_UNSUPPORTED, "level 0 was not formed by gmg_set_level_matrix_lattice");
+  for (int d = 0; d < 3; ++d)  // (gmg_set_level_matrix_lattice takes no fewer than 5)
+    if (m.lat_nv[d] > fastdiag::kMaxNv) return fail(ctx, GMG_ERR_UNSUPPORTED, "level 0 has more than 1024 vertices in a direction");
+  double s = 0.0;
+  if (!fastdiag::separable(m.lat_Ke, &s)) return fail(ctx, GMG_ERR_UNSUPPORTED, "the level-0 cell matrix is not the separable constant-coefficient Q1 Laplacian");
+  (void)hipSetDevice(ctx->device);
+  FastDiag fd;
+  fd.s = s;
+  std::vector<double> S, Sp, lam, mu;
+  for (int d = 0; d < 3; ++d) {
+    const int mm = m.lat_nv[d] - 2, ld = (mm + fastdiag::kPad - 1) / fastdiag::kPad * fastdiag::kPad;
+    fd.m[d] = mm; fd.ld[d] = ld;
+    S.assign((size_t)mm * mm, 0.0); lam.assign((size_t)mm, 0.0); mu.assign((size_t)mm, 0.0);
+    fastdiag::tables(mm + 1, S.data(), lam.data(), mu.data());
+    Sp.assign((size_t)ld * ld, 0.0);
+    for (int j = 0; j < mm; ++j) std::copy(S.begin() + (size_t)j * mm, S.begin() + (size_t)(j + 1) * mm, Sp.begin() + (size_t)j * ld);
+    HIPC(upload(fd.S[d], Sp, ctx->stream));
+    HIPC(upload(fd.lam[d], lam, ctx->stream));
+    HIPC(upload(fd.mu[d], mu, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));  // (the host tables are reused by the next axis)
+  }
+  CHK(alloc_vec(ctx, fd.t1, L0.n));
+  CHK(alloc_vec(ctx, fd.t2, L0.n));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  fd.ready = true;
+  ctx->fd = std::move(fd);
+  ctx->coarse_solver = GMG_COARSE_DIRECT;
+  return GMG_OK;
+}
+
+// one pass: dst <- S_axis src on the interior (scale: divided by D_abc as well; axis 2 only)
+void launch_fastdiag_pass(gmg_context *ctx, int axis, double *dst, const double *src, bool scale) {
+  const FastDiag &fd = ctx->fd;
+  const DevCSR &m = ctx->lv[0].A;
+  fastdiag::PassArgs a{};
+  a.src = src; a.dst = dst;
+  for (int d = 0; d < 3; ++d) a.ax[d] = fastdiag::Axis{fd.S[d].get(), fd.lam[d].get(), fd.mu[d].get(), fd.m[d], fd.ld[d]};
+  a.nx = m.lat_nx; a.nxy = m.lat_nxy; a.axis = axis; a.s = fd.s;
+  // panels of 16 lines, one per wave
+  const int64_t panels = axis == 0 ? (int64_t)((fd.m[1] + 15) / 16) * fd.m[2] : (int64_t)((fd.m[0] + 15) / 16) * fd.m[3 - axis];
+  int64_t grid = std::min<int64_t>((panels + 3) / 4, 8192);
+  if (ctx->coarse_direct_max_blocks > 0) grid = std::min<int64_t>(grid, ctx->coarse_direct_max_blocks);
+  grid = std::max<int64_t>(grid, 1);
+  if (axis == 0) launch_timed(ctx, fastdiag::fastdiag_pass_x_kernel, dim3((unsigned)grid), dim3(kThreads), 0, a);
+  else if (scale) launch_timed(ctx, fastdiag::fastdiag_pass_yz_kernel<true>, dim3((unsigned)grid), dim3(kThreads), 0, a);
+  else launch_timed(ctx, fastdiag::fastdiag_pass_yz_kernel<false>, dim3((unsigned)grid), dim3(kThreads), 0, a);
+}
+
+int coarse_solve_direct(gmg_context *ctx, double *x, const double *b, int *iters_out, double *res_out, Event *pass_ev) {
+  Level &L0 = ctx->lv[0];
+  const DevCSR &A = L0.A;
+  FastDiag &fd = ctx->fd;
+  if (!fd.ready || !A.lat_only || l0_partitioned(ctx)) return fail(ctx, GMG_ERR_INVALID, "direct coarse solver selected without its tables, or on a partitioned level 0");
+  double *t1 = fd.t1.get(), *t2 = fd.t2.get();
+  // launch k carries the events of pass_ev[k] when the caller asked for the passes' own times (gmg_coarse_direct_profile)
+  int k = 0;
+  auto arm = [&]() {
+    if (pass_ev) { ctx->timed_start = pass_ev[2 * k].get(); ctx->timed_stop = pass_ev[2 * k + 1].get(); }
+    ++k;
+  };
+  arm(); launch_fastdiag_pass(ctx, 0, t1, b, false);
+  arm(); launch_fastdiag_pass(ctx, 1, t2, t1, false);
+  arm(); launch_fastdiag_pass(ctx, 2, t1, t2, true);   // forward along z, then D^-1
+  arm(); launch_fastdiag_pass(ctx, 2, t2, t1, false);
+  arm(); launch_fastdiag_pass(ctx, 1, t1, t2, false);
+  arm(); launch_fastdiag_pass(ctx, 0, x, t1, false);
+  int grid = grid_for(L0.n);
+  if (ctx->coarse_direct_max_blocks > 0) grid = std::min(grid, ctx->coarse_direct_max_blocks);
+  arm();
+  launch_timed(ctx, fastdiag::fastdiag_boundary_kernel, dim3(grid), dim3(kThreads), 0, x, b, (const uint8_t *)A.lat_rowcls.get(), (const double *)A.lat_ctab.get(), A.lat_nv[0],
+               A.lat_nv[1], A.lat_nv[2]);
+  ctx->stats.coarse_solves++;
+  ctx->stats.coarse_solver = GMG_COARSE_DIRECT;
+  ctx->last_coarse_iters = 0;
+  if (iters_out) *iters_out = 0;
+  if (res_out) {
+    // the true |b - A x|_2: one lattice product and the norm kernels (level 0 is whole on this rank: no all-reduce)
+    CHK(spmv(ctx, A, kStore, x, t1));
+    const int g = grid_for(L0.n);
+    hipLaunchKernelGGL(vec_sadd_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, t1, -1.0, 1.0, b, L0.n);
+    hipLaunchKernelGGL(norms_partial_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, (const double *)t1, L0.n, ctx->part_a.get());
+    hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), g, 4, 4u, ctx->scal_dev.get());
+    CHK(launch_status(ctx));
+    CHK(fetch_scalars(ctx, 4));
+    *res_out = std::sqrt(ctx->scal_host.get()[1]);
+    return GMG_OK;
+  }
+  return launch_status(ctx);
 }
 
 
@@ -2322,6 +2448,7 @@ void release_operators(gmg_context *ctx) {
   ctx->S = DevCSR();
   for (DevPtr<double> *p : {&ctx->sys_full_a, &ctx->sys_full_b, &ctx->S_invd, &ctx->S_tmp, &ctx->cg_g, &ctx->cg_d0, &ctx->cg_d1, &ctx->cg_h}) p->reset();
   free_cg_ring(ctx);
+  drop_coarse_direct(ctx);
 }
 
 // tiles of the CSR row-window kernel: consecutive rows whose nonzeros fit the LDS window (as in upload_csr)
@@ -2511,6 +2638,7 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
     return fail(ctx, GMG_ERR_INVALID, "gmg_set_level_matrix: the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_rows");
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
+  if (level == 0) drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
   CHK(upload_csr(ctx, L.A, n_rows, n_cols, rowptr, col, val, level > 0));
   CHK(setup_diag(ctx, n_rows, rowptr, col, val, L.invd, &L.cheb_lmax));
   if (level > 0) {
@@ -2540,7 +2668,10 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[0];
   DevCSR &m = L.A;
+  drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
   reset_keep_halo(m);
+  for (int d = 0; d < 3; ++d) m.lat_nv[d] = nv[d];
+  std::copy(Ke, Ke + 64, m.lat_Ke);
   // ---- class table
   const int64_t dims[3] = {nx, ny, nz};
   auto rep = [&](int t, int64_t mdim) -> int64_t { return t == 0 ? 0 : t == 1 ? 1 : t == 2 ? 2 : t == 3 ? mdim - 2 : mdim - 1; };
@@ -2620,7 +2751,13 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   if (ctx->debug_upload)
     std::fprintf(stderr, "[gmg] lattice operator %lld x %lld x %lld formed on the device: %d columns x %d steps, %d segments per XCD slab, grid %d, %d edge chunks\n", (long long)nx,
                  (long long)ny, (long long)nz, m.lat_C, m.lat_K, m.lat_S, m.lat_grid, m.lat_n_gen);
-  return finish_level(ctx, 0, n, n, m.nnz);
+  CHK(finish_level(ctx, 0, n, n, m.nnz));
+  if (ctx->coarse_direct_opt) {  // option coarse_direct: the direct coarse solver where this level 0 qualifies, the CG otherwise
+    const int rc = select_coarse_direct(ctx);
+    if (rc != GMG_OK && rc != GMG_ERR_UNSUPPORTED) return rc;
+    if (rc == GMG_ERR_UNSUPPORTED) ctx->err.clear();
+  }
+  return GMG_OK;
 }
 
 int gmg_set_edge_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_cols, const int64_t *rowptr,
@@ -2801,6 +2938,56 @@ int gmg_set_coarse(gmg_context *ctx, double abs_tol, int max_it) {
   if (!ctx || max_it < 1) return GMG_ERR_INVALID;
   ctx->coarse_tol = abs_tol; ctx->coarse_maxit = max_it;
   return GMG_OK;
+}
+
+int gmg_set_coarse_solver(gmg_context *ctx, int kind) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (kind == GMG_COARSE_CG) {
+    HIPC(hipStreamSynchronize(ctx->stream));  // (a solve still in flight uses the tables)
+    drop_coarse_direct(ctx);
+    return GMG_OK;
+  }
+  if (kind != GMG_COARSE_DIRECT) return fail(ctx, GMG_ERR_INVALID, "gmg_set_coarse_solver: GMG_COARSE_CG or GMG_COARSE_DIRECT");
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return select_coarse_direct(ctx);
+}
+
+int gmg_coarse_direct_tables(int n_cells, double *S, double *lambda, double *mu) {
+  if (n_cells < fastdiag::kMinNv - 1 || n_cells > fastdiag::kMaxNv - 1 || (!S && !lambda && !mu)) return GMG_ERR_INVALID;
+  fastdiag::tables(n_cells, S, lambda, mu);
+  return GMG_OK;
+}
+
+int gmg_coarse_direct_separable(const double Ke[64], double *s) {
+  if (!Ke) return GMG_ERR_INVALID;
+  return fastdiag::separable(Ke, s) ? GMG_OK : GMG_ERR_UNSUPPORTED;
+}
+
+int gmg_coarse_direct_profile(gmg_context *ctx, double *dst, const double *src, double pass_ms[7]) {
+  if (!ctx || !dst || !src || !pass_ms) return GMG_ERR_INVALID;
+  if (ctx->coarse_solver != GMG_COARSE_DIRECT || !ctx->fd.ready) return fail(ctx, GMG_ERR_INVALID, "gmg_coarse_direct_profile: the direct coarse solver is not selected");
+  Level &L0 = ctx->lv[0];
+  Event ev[14];
+  for (auto &e : ev) HIPC(e.create());
+  HIPC(hipMemcpyAsync(L0.def.get(), src, sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
+  CHK(coarse_solve_direct(ctx, L0.sol.get(), L0.def.get(), nullptr, nullptr, ev));
+  HIPC(hipMemcpyAsync(dst, L0.sol.get(), sizeof(double) * (size_t)L0.n, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 7; ++k) {
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev[2 * k].get(), ev[2 * k + 1].get()));
+    pass_ms[k] = ms;
+  }
+  return GMG_OK;
+}
+
+int gmg_coarse_direct_transform(gmg_context *ctx, int axis, double *dst, const double *src) {
+  if (!ctx || !dst || !src) return GMG_ERR_INVALID;
+  if (axis < 0 || axis > 2) return fail(ctx, GMG_ERR_INVALID, "gmg_coarse_direct_transform: axis 0, 1 or 2");
+  if (dst == src) return fail(ctx, GMG_ERR_INVALID, "gmg_coarse_direct_transform: dst and src must differ");
+  if (ctx->coarse_solver != GMG_COARSE_DIRECT || !ctx->fd.ready) return fail(ctx, GMG_ERR_INVALID, "gmg_coarse_direct_transform: the direct coarse solver is not selected");
+  launch_fastdiag_pass(ctx, axis, dst, src, false);
+  RETURN_LAUNCHED(ctx);
 }
 
 // ---- vectors ----
@@ -3740,6 +3927,10 @@ int gmg_set_global_sizes(gmg_context *ctx, int64_t n_system_global, int64_t n_le
   if (!ctx->dist) return fail(ctx, GMG_ERR_INVALID, "gmg_set_global_sizes: call gmg_comm_init first");
   ctx->sys_global = n_system_global;
   ctx->l0_global = n_level0_global;
+  if (l0_partitioned(ctx) && ctx->coarse_solver == GMG_COARSE_DIRECT) {  // (the direct solver needs level 0 whole: back to the CG)
+    HIPC(hipStreamSynchronize(ctx->stream));
+    drop_coarse_direct(ctx);
+  }
   return GMG_OK;
 }
 
@@ -3788,6 +3979,7 @@ int gmg_stats_reset(gmg_context *ctx) {
   ctx->stats.spmv0_rows = keep.spmv0_rows; ctx->stats.spmv0_nnz = keep.spmv0_nnz; ctx->stats.coarse_variant = keep.coarse_variant;
   ctx->stats.spmv0_layout = keep.spmv0_layout; ctx->stats.spmv0_matrix_bytes = keep.spmv0_matrix_bytes;
   ctx->stats.spmv0_pattern_slices = keep.spmv0_pattern_slices; ctx->stats.spmv0_slices = keep.spmv0_slices;
+  ctx->stats.coarse_solver = keep.coarse_solver;
   return GMG_OK;
 }
 int gmg_stats_get(gmg_context *ctx, gmg_stats *out) {
@@ -3861,6 +4053,11 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "sellp_rr") ctx->sellp_rr = (int)value;
   else if (k == "cg_variant") ctx->cg_variant = (int)value;
   else if (k == "coarse_chunk") ctx->coarse_chunk = (int)value;
+  else if (k == "coarse_direct") ctx->coarse_direct_opt = on;
+  else if (k == "coarse_direct_max_blocks") {
+    if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "coarse_direct_max_blocks: an integer in 0 .. 65536");
+    ctx->coarse_direct_max_blocks = (int)value;
+  }
   else if (k == "ssor_balanced") ctx->ssor_partition = on ? GMG_SSOR_PARTITION_BALANCED : GMG_SSOR_PARTITION_ROWS;
   else if (k == "sgs_y_slots") ctx->sgs_y_slots = (int)value;
   else if (k == "sgs_disable_wave") ctx->sgs_disable_wave = on;

@@ -156,6 +156,7 @@ struct step50_report {
   double build_matrices_ms;  // device time of MGTransferPrebuilt::build_matrices (gmg_build_transfer) for this cycle; 0: built on the host
   int32_t has_forces, pad2;  // "Compute forces": net force, largest |F_i|, relative RMS error against the direct sum (0: not checked)
   double force_net[3], force_max, force_rel_error;
+  int64_t coarse_solver;  // GMG_COARSE_CG (0) / GMG_COARSE_DIRECT (1): what the cycle's last coarse solve ran
 };
 int step50_get_report(step50_problem *h, int i, step50_report *out) {
   const auto &reps = DISPATCH(h, reports);
@@ -179,6 +180,7 @@ int step50_get_report(step50_problem *h, int i, step50_report *out) {
   out->has_forces = r.has_forces;
   for (int d = 0; d < 3; ++d) out->force_net[d] = r.force_net[d];
   out->force_max = r.force_max; out->force_rel_error = r.force_rel_error;
+  out->coarse_solver = r.coarse_solver;
   return 0;
 }
 

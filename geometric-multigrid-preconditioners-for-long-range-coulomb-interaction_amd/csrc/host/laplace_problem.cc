@@ -232,6 +232,9 @@ void ParameterReader::declare_parameters() {
             // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; constant-coefficient
             // problems on one rank, DESIGN.md section 12
             {"System matrix on device", "false"},
+            // what stands behind mg_coarse: the reference's unpreconditioned CG (:962-967), or fast diagonalisation on the
+            // level-0 lattice (gmg_set_coarse_solver; where level 0 does not qualify the CG stays), DESIGN.md section 15
+            {"Coarse solver", "CG"},
             // the error estimator and the refinement marks formed on the device from a face table of the forest and the
             // solution (gmg_estimate_error) instead of the host loops of estimate_error_and_mark_cells; cycles that ran on
             // the device, one rank, DESIGN.md section 14
@@ -321,6 +324,8 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
     throw std::runtime_error("Refinement estimator must be <Kelly + residual> or <Kelly>");
   p.level0_matrix_on_device = prm.get_bool("Level 0 matrix on device");
   p.system_matrix_on_device = prm.get_bool("System matrix on device");
+  p.coarse_solver = prm.get("Coarse solver");
+  if (p.coarse_solver != "CG" && p.coarse_solver != "direct") throw std::runtime_error("Coarse solver must be <CG> or <direct>");
   p.estimator_on_device = prm.get_bool("Error estimator on device");
   p.transfer_on_device = prm.get_bool("Transfer matrices on device");
   p.rhs_on_device = prm.get_bool("RHS on device");
@@ -1475,6 +1480,16 @@ int LaplaceProblem<dim>::upload() {
   const int kind = par.smoother == "Jacobi" ? GMG_SMOOTHER_JACOBI : par.smoother == "Chebyshev" ? GMG_SMOOTHER_CHEBYSHEV : GMG_SMOOTHER_SSOR;
   GMGC(gmg_set_smoother(gmg, kind, par.smoother_omega, par.smoother_steps, par.chebyshev_degree, 0.0, 0.0));
   GMGC(gmg_set_coarse(gmg, 1e-10, 1000));  // :962
+  if (par.coarse_solver == "direct") {
+    const int rc_cs = gmg_set_coarse_solver(gmg, GMG_COARSE_DIRECT);
+    if (rc_cs == GMG_ERR_UNSUPPORTED) {
+      if (!coarse_fallback_reported) pcout(std::string("   Coarse solver direct: not applicable (") + gmg_last_error(gmg) + "), coarse CG");
+      coarse_fallback_reported = true;
+    } else if (rc_cs != GMG_OK) {
+      last_error = std::string("gmg_set_coarse_solver: ") + gmg_last_error(gmg);
+      return rc_cs;
+    }
+  }
   GMGC(gmg_vec_alloc(gmg, d_nvec, &d_solution));
   GMGC(gmg_vec_alloc(gmg, d_nvec, &d_rhs));
   const int64_t chunk = (n_system + n_ranks - 1) / n_ranks;
@@ -1562,6 +1577,7 @@ int LaplaceProblem<dim>::solve_on_device(CycleReport &rep) {
   gmg_stats st;
   gmg_stats_get(gmg, &st);
   rep.coarse_iterations = st.coarse_iterations - st0.coarse_iterations;
+  rep.coarse_solver = (int)st.coarse_solver;
   if (rc != GMG_OK) { last_error = std::string("solve: ") + gmg_last_error(gmg); return rc; }
   GMGC(gmg_vec_norms(gmg, d_solution, d_n, &rep.sol_l1, &rep.sol_l2, &rep.sol_linf));  // :1012-1014
   GMGC(gmg_vec_allgather(gmg, (int64_t)solution.size(), d_full, d_solution));  // every rank keeps the whole solution
@@ -1608,6 +1624,7 @@ int LaplaceProblem<dim>::solve_again() {
   reports.back().solve_seconds = rep.solve_seconds;
   reports.back().cg_iterations = rep.cg_iterations;
   reports.back().coarse_iterations = rep.coarse_iterations;
+  reports.back().coarse_solver = rep.coarse_solver;
   return rc;
 }
 

@@ -81,6 +81,7 @@ struct Parameters {
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (constant coefficient, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
+  std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
   static Parameters from(const ParameterReader &prm);
 };
 
@@ -99,6 +100,7 @@ struct CycleReport {  // the values the reference prints per cycle (src/step-50.
   double solve_seconds = 0;  // first residual to convergence, excluding upload / build_matrices
   double build_matrices_ms = 0;  // device time of mg_transfer.build_matrices (:957-958) when the device builds the transfers
   int status = 0;
+  int coarse_solver = 0;  // GMG_COARSE_CG / GMG_COARSE_DIRECT: what the cycle's last coarse solve ran (gmg_stats.coarse_solver)
   bool has_forces = false;  // "Compute forces": sum_i F_i, max_i |F_i|, ||F - F^d|| / ||F^d|| ("Direct Coulomb check", else 0)
   double force_net[3] = {0, 0, 0}, force_max = 0, force_rel_error = 0;
 };
@@ -202,6 +204,7 @@ class LaplaceProblem {
   bool solve_on_device_requested = false, level0_on_device = false, transfer_on_device = false;
   bool system_on_device = false;           // this cycle's system matrix is formed by gmg_assemble_system_matrix at upload()
   bool system_fallback_reported = false;   // "System matrix on device" was set but not applicable: said once
+  bool coarse_fallback_reported = false;   // "Coarse solver = direct" was set but not applicable: said once
   bool densities_device_resident = false;  // compute_charge_densities left them in HBM for gmg_rhs_assemble
   double build_matrices_ms = 0.0;  // device time of gmg_build_transfer for the current cycle's operators
   std::string last_error;

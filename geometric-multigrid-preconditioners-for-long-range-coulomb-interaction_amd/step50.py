@@ -27,7 +27,8 @@ class Report(C.Structure):
                 ("energy_self", C.c_double), ("energy_total", C.c_double), ("energy_abs_error", C.c_double),
                 ("solve_seconds", C.c_double), ("energy_norm_error", C.c_double), ("build_matrices_ms", C.c_double),
                 ("has_forces", C.c_int32), ("pad2", C.c_int32),
-                ("force_net", C.c_double * 3), ("force_max", C.c_double), ("force_rel_error", C.c_double)]
+                ("force_net", C.c_double * 3), ("force_max", C.c_double), ("force_rel_error", C.c_double),
+                ("coarse_solver", C.c_int64)]
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("dofs_by_level", "pad", "pad2", "force_net")}
@@ -84,6 +85,7 @@ def prm_text(**kw) -> str:
         "level0_numbering": ("Misc", "Level 0 numbering"),
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
         "system_matrix_on_device": ("Misc", "System matrix on device"),
+        "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
         "rhs_on_device": ("Misc", "RHS on device"),

@@ -96,6 +96,38 @@ int gmg_set_smoother(gmg_context *ctx, int kind, double omega, int steps, int ch
                      double cheb_lmax);
 /* SolverControl coarse_solver_control(1000, 1e-10, false, false), :962.                    */
 int gmg_set_coarse(gmg_context *ctx, double abs_tol, int max_it);
+/* Which solver stands behind mg_coarse (:965-967): GMG_COARSE_CG, the reference's unpreconditioned CG (default), or
+ * GMG_COARSE_DIRECT, fast diagonalisation on the level-0 lattice (not in the reference):
+ *   x_int = (S_x (x) S_y (x) S_z) D^-1 (S_x (x) S_y (x) S_z) b_int,   x_i = b_i / a_ii on a boundary row,
+ * six batched products with the sine matrices of the axes and one scaling, no iterations and no reductions.  Call it after
+ * level 0 has been set.  DIRECT is accepted only if level 0 was formed by gmg_set_level_matrix_lattice, is not partitioned
+ * over ranks, has 5 .. 1024 vertices in every direction, and its Ke is separable (gmg_coarse_direct_separable); otherwise
+ * GMG_ERR_UNSUPPORTED with the reason in gmg_last_error, and the CG stays selected.  gmg_reset and a new level-0 matrix
+ * return the context to the CG.  The option coarse_direct (gmg_set_option / GMG_OPTIONS) selects DIRECT whenever a later
+ * gmg_set_level_matrix_lattice forms a level 0 that qualifies and silently leaves the CG otherwise.  With DIRECT,
+ * gmg_coarse_solve reports iterations = 0 and, only when `residual` is non-NULL, the true |b - A_0 x|_2 (one more product
+ * and a host wait); gmg_stats.coarse_iterations does not move.  Results are deterministic and independent of the launch
+ * shape (option coarse_direct_max_blocks); they are not the bits of the CG.                                             */
+#define GMG_COARSE_CG 0
+#define GMG_COARSE_DIRECT 1
+int gmg_set_coarse_solver(gmg_context *ctx, int kind);
+/* The tables of one axis with n_cells cells (4 .. 1023), m = n_cells - 1 interior vertices, without a context or a device:
+ *   S[(j-1) m + (k-1)] = sqrt(2 / n) sin(pi j k / n),  lambda[k-1] = 2 - 2 cos(pi k / n),  mu[k-1] = (4 + 2 cos(pi k / n)) / 6
+ * (j, k = 1 .. m; any output may be NULL).  The sine is taken of the integer (j k) mod 2n folded into [0, n / 2], so the
+ * error of an entry is a few ulp whatever the size of j k.  These are the numbers the device uses.                      */
+int gmg_coarse_direct_tables(int n_cells, double *S, double *lambda, double *mu);
+/* Is Ke (8 x 8, row-major, local index bit 0 = x, bit 1 = y, bit 2 = z) the cell matrix of the constant-coefficient Q1
+ * Laplacian, Ke = s (k (x) m (x) m + m (x) k (x) m + m (x) m (x) k) with k = [[1, -1], [-1, 1]], m = [[2, 1], [1, 2]] / 6 and
+ * s = 3 Ke[0][0] > 0, every entry within 64 * 2^-53 * max |Ke|?  GMG_OK and *s (may be NULL), or GMG_ERR_UNSUPPORTED.
+ * Host only.                                                                                                            */
+int gmg_coarse_direct_separable(const double Ke[64], double *s);
+/* dst <- S_axis src along one axis (0 = x, 1 = y, 2 = z) on the interior of a level-0 vector, one pass of the direct
+ * solver (which must be selected); boundary rows of dst are left untouched; dst != src.  Asynchronous.                 */
+int gmg_coarse_direct_transform(gmg_context *ctx, int axis, double *dst, const double *src);
+/* One direct coarse solve dst <- A_0^-1 src with HIP events attached to each of its seven launches: pass_ms[0..6] = the
+ * kernels' own begin-to-end times of x, y, z + scaling, z, y, x and the boundary rows (what a kernel trace reports; launch
+ * gaps are not in them).  Blocks.  For tools/coarse_direct_probe.py; the direct solver must be selected.               */
+int gmg_coarse_direct_profile(gmg_context *ctx, double *dst, const double *src, double pass_ms[7]);
 
 /* ---- vector_t (LA::MPI::Vector, include/step_50.h:154) ----------------------------- */
 int gmg_vec_alloc(gmg_context *ctx, int64_t n, double **dptr);
@@ -397,6 +429,7 @@ typedef struct gmg_stats {
   int64_t sgs_stream_bytes;     /* record bytes they streamed                                                        */
   int64_t sgs_launches;         /* all SSOR sweep launches while profiling was on (every sample_every-th one is timed)  */
   double build_matrices_ms;     /* device time of gmg_build_transfer calls since the last reset (the reference counts build_matrices in its Solve timer, :941-958) */
+  int64_t coarse_solver;        /* GMG_COARSE_CG (0) or GMG_COARSE_DIRECT (1), of the last coarse solve */
 } gmg_stats;
 int gmg_stats_reset(gmg_context *ctx);
 int gmg_stats_get(gmg_context *ctx, gmg_stats *out);
@@ -412,7 +445,8 @@ int gmg_calibrate_hbm(gmg_context *ctx, int64_t n_bytes, int reps, double *read_
 int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
 /* Diagnostic / measurement options by name (defaults are the production paths).  Keys: host_threads,
  * debug_upload, disable_sell, disable_patterns, disable_compression, disable_sellp, disable_rowclass, sell_grid, sellp_cost,
- * cg_variant, coarse_chunk, sgs_y_slots (doubles of LDS the SSOR sweep may use for y: small values force
+ * cg_variant, coarse_chunk, coarse_direct (0 / 1, see gmg_set_coarse_solver), coarse_direct_max_blocks (cap on the grids of the direct
+ * coarse solver's passes, 0 = by size; the results do not depend on it), sgs_y_slots (doubles of LDS the SSOR sweep may use for y: small values force
  * several LDS ranges), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
  * sgs_phase_profile (cycle counters of the four-wave sweep: same results, one rank only), sgs_profile (instrumented
  * one-wave sweep; its wrong-result timing modes exist only in a -DGMG_EXPERIMENTS build, tools/build_experiments.sh),
