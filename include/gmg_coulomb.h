@@ -147,7 +147,9 @@ int gmg_vec_all_zero(gmg_context *ctx, const double *x, int64_t n, int *out);   
  * also mg::Matrix::vmult(level, ...) (:975).  Includes the ghost import.                  */
 int gmg_spmv(gmg_context *ctx, int which, double *dst, const double *src);
 /* PreconditionMG::vmult(dst, src): copy_to_mg, one V-cycle (Multigrid::cycle), copy_from_mg
- * (:980-989).  Fails with GMG_ERR_COARSE_NOCONV like the reference's exception.           */
+ * (:980-989).  Fails with GMG_ERR_COARSE_NOCONV like the reference's exception.  dst is
+ * zeroed first (entries outside every copy list come back exactly 0).  With steps = 0 no
+ * level is smoothed: the cycle restricts the defects, solves level 0 and prolongates.     */
 int gmg_precondition(gmg_context *ctx, double *dst, const double *src);
 /* PreconditionJacobi(omega).vmult on the system matrix (:999-1004, omega = 0.6).           */
 int gmg_precondition_jacobi(gmg_context *ctx, double omega, double *dst, const double *src);
@@ -157,7 +159,9 @@ int gmg_precondition_jacobi(gmg_context *ctx, double omega, double *dst, const d
  * `iterations` steps, as SolverCG leaves it in dst when SolverControl throws; the context
  * stays usable.                                                                            */
 int gmg_coarse_solve(gmg_context *ctx, double *dst, const double *src, int *iterations, double *residual);
-/* MGSmootherBase::apply (from_zero != 0) / ::smooth (from_zero == 0) on one level (:983-984). */
+/* MGSmootherBase::apply (from_zero != 0) / ::smooth (from_zero == 0) on one level (:983-984):
+ * `steps` steps of u <- u + S (rhs - A u), the first of apply from u = 0 (the caller's u is
+ * not read).  With steps = 0 both leave u as the caller gave it; apply does not zero it.   */
 int gmg_smoother_step(gmg_context *ctx, int level, double *u, const double *rhs, int from_zero);
 /* MGTransferBase::prolongate(level+1, dst, src) / restrict_and_add(level+1, dst, src).     */
 int gmg_prolongate(gmg_context *ctx, int level, double *dst_fine, const double *src_coarse);
