@@ -38,6 +38,7 @@ SYMBOLS = [
     "gmg_set_ssor_block_rows", "gmg_set_ssor_partition", "gmg_get_ssor_partition", "gmg_ssor_balance_rows", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
     "gmg_set_point_locator", "gmg_atom_forces", "gmg_direct_coulomb",
     "gmg_gaussian_potential", "gmg_energy_norm_error",
+    "gmg_get_ssor_plan", "gmg_get_ssor_backward_rows", "gmg_ssor_slot_plan",
 ]
 
 
@@ -578,6 +579,39 @@ class Context:
         br, st = np.zeros(nb.value + 1, dtype=np.int64), np.zeros(max(nb.value, 1), dtype=np.int64)
         self._chk(self.L.gmg_get_ssor_partition(self.h, C.c_int(level), C.byref(nb), _p(br, C.c_int64), _p(st, C.c_int64)))
         return br, st[:nb.value]
+
+    def get_ssor_plan(self, level):
+        """gmg_get_ssor_plan as a dict (SSOR_PLAN_KEYS)."""
+        out = np.zeros(8, dtype=np.int64)
+        self._chk(self.L.gmg_get_ssor_plan(self.h, C.c_int(level), _p(out, C.c_int64)))
+        return dict(zip(SSOR_PLAN_KEYS, (int(v) for v in out)))
+
+    def get_ssor_backward_rows(self, level):
+        """gmg_get_ssor_backward_rows: the level rows the self-contained backward records store to, in stream order."""
+        cnt = C.c_int64(0)
+        self._chk(self.L.gmg_get_ssor_backward_rows(self.h, C.c_int(level), C.byref(cnt), None))
+        rows = np.zeros(max(cnt.value, 1), dtype=np.int32)
+        self._chk(self.L.gmg_get_ssor_backward_rows(self.h, C.c_int(level), C.byref(cnt), _p(rows, C.c_int32)))
+        return rows[:cnt.value]
+
+
+SSOR_PLAN_KEYS = ("forward_ranges", "backward_ranges", "self_contained_ranges", "y_slots", "max_live_forward", "max_live_backward", "steps", "stream_bytes")
+
+
+def ssor_slot_plan(m, row_begin, row_end, backward):
+    """gmg_ssor_slot_plan on a host CSR (needs no device): (step, last_reader, slot, n_steps, n_slots) of one block and direction;
+    the three arrays have one entry per row of the block, -1 for a row without couplings inside it."""
+    rp, col, val = _csr(m)
+    n = len(rp) - 1
+    k = max(int(row_end) - int(row_begin), 1)
+    step, last, slot = (np.full(k, -1, dtype=np.int32) for _ in range(3))
+    ns, nl = C.c_int64(0), C.c_int64(0)
+    rc = load().gmg_ssor_slot_plan(C.c_int64(n), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double), C.c_int64(int(row_begin)), C.c_int64(int(row_end)),
+                                   C.c_int(int(bool(backward))), _p(step, C.c_int32), _p(last, C.c_int32), _p(slot, C.c_int32), C.byref(ns), C.byref(nl))
+    if rc != OK:
+        raise GMGError(rc, "gmg_ssor_slot_plan")
+    k = int(row_end) - int(row_begin)
+    return step[:k], last[:k], slot[:k], ns.value, nl.value
 
 
 def ssor_balance_rows(m, n_blocks, use_values=True):

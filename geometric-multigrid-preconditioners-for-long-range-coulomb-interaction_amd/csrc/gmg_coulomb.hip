@@ -34,6 +34,7 @@
 #include <cstring>
 #include <climits>
 #include <map>
+#include <queue>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -99,6 +100,9 @@ struct SgsPlan {
   DevPtr<char> w_stream;
   DevPtr<double> w_ycur, w_iso_diag, w_iso_invd;
   int w_y_slots = 0, w_lds_bytes = 0, w_n_ranges = 0;
+  int n_bwd = 0;  // backward ranges among w_n_ranges
+  std::vector<int32_t> host_bwd_rows;  // level rows the self-contained backward records store their results to (their aux words, stream order)
+  int n_self = 0, live_max[2] = {0, 0};  // self-contained ranges of the four-wave sweep; most y slots live at once per direction, as the allocator found them (0: not run)
   int64_t w_n_coupled = 0, w_stream_bytes = 0, w_steps = 0, w_stages = 0;
   std::vector<int32_t> host_block_row;  // n_blocks + 1 (several ranks: who sweeps which rows)
   std::vector<int64_t> host_block_steps;  // n_blocks: sub-steps of each block's chain (both directions; gmg_get_ssor_partition)
@@ -191,6 +195,7 @@ struct gmg_context {
   int coarse_chunk = 0;
   // diagnostic options (gmg_set_option / GMG_OPTIONS); the defaults are the fast paths
   int sgs_y_slots = 0;      // 0 = kSwYSlots; tests shrink it to force several LDS ranges
+  bool sgs_sliding = true;  // four-wave sweep: one self-contained range per direction where a block's live rows fit the y slots
   bool sgs_disable_wave = false, sgs_disable_phase = false, sgs_chain = false, sgs_dep = false, sgs_reg = false, debug_upload = false, sgs_profile = false;
   int sgs_profile_mode = 0;
   int sgs_phase_chunk = 0;         // steps per chunk of one shape (0: default)
@@ -1119,7 +1124,7 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
           else
 #endif
           if (L.sgs.reg) hipLaunchKernelGGL(sgs_regs_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q);
-          else hipLaunchKernelGGL(sgs_phase_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q);
+          else hipLaunchKernelGGL(sgs_phase_profile_kernel, dim3(nbl), dim3(kPhThreads), lds, ctx->stream, q);
           hipError_t e = hipMemcpyAsync(h.data(), d.get(), sizeof(unsigned long long) * 12 * nr, hipMemcpyDeviceToHost, ctx->stream);
           if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
           if (e != hipSuccess) { ctx->err = std::string("SSOR sweep profile: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
@@ -1747,8 +1752,144 @@ std::vector<double> ssor_block_costs(const SsorPattern &P, const std::vector<int
   return c;
 }
 
+// The part of a level matrix one SSOR block [rb, re) sweeps: its pruned entries (stored value != 0, column inside the
+// block; local column numbers), which rows couple at all, and the dependency stages
+// stage(i) = 1 + max stage(j) over the j < i coupled to i through a_ij or a_ji.  false: a row's columns do not ascend.
+struct SsorBlockGraph {
+  std::vector<int32_t> prp, pcol, stage, crow, sptr, by_stage;  // crow: coupled rows, ascending; by_stage[sptr[t] .. sptr[t + 1]): those of stage t
+  std::vector<double> pval;
+  std::vector<char> coupled;
+  int n_stages = 0;
+};
+bool ssor_block_graph(int64_t rb, int64_t re, const int64_t *rp, const int32_t *col, const double *val, SsorBlockGraph &B) {
+  const int m = (int)(re - rb);
+  B.prp.assign((size_t)m + 1, 0); B.pcol.clear(); B.pval.clear();
+  B.coupled.assign((size_t)m, 0);
+  std::vector<int32_t> low_cnt((size_t)m + 1, 0);
+  for (int i = 0; i < m; ++i) {
+    for (int64_t k = rp[rb + i]; k < rp[rb + i + 1]; ++k) {
+      const int64_t c = col[k];
+      if (k > rp[rb + i] && c <= col[k - 1]) return false;
+      if (c < rb || c >= re || val[k] == 0.0) continue;
+      B.pcol.push_back((int32_t)(c - rb));
+      B.pval.push_back(val[k]);
+      if (c != rb + i) {
+        B.coupled[(size_t)i] = 1; B.coupled[(size_t)(c - rb)] = 1;
+        low_cnt[(size_t)std::max<int64_t>(i, c - rb) + 1]++;
+      }
+    }
+    B.prp[(size_t)i + 1] = (int32_t)B.pcol.size();
+  }
+  for (int i = 0; i < m; ++i) low_cnt[(size_t)i + 1] += low_cnt[(size_t)i];
+  std::vector<int32_t> low((size_t)low_cnt[(size_t)m]), fill(low_cnt.begin(), low_cnt.end() - 1);
+  for (int i = 0; i < m; ++i)
+    for (int32_t k = B.prp[(size_t)i]; k < B.prp[(size_t)i + 1]; ++k)
+      if (B.pcol[(size_t)k] != i) low[(size_t)fill[(size_t)std::max(i, B.pcol[(size_t)k])]++] = std::min(i, B.pcol[(size_t)k]);
+  B.stage.assign((size_t)m, 0);
+  B.n_stages = 0;
+  B.crow.clear();
+  for (int i = 0; i < m; ++i) {
+    if (!B.coupled[(size_t)i]) continue;
+    int st = 0;
+    for (int32_t k = low_cnt[(size_t)i]; k < low_cnt[(size_t)i + 1]; ++k) st = std::max(st, B.stage[(size_t)low[(size_t)k]] + 1);
+    B.stage[(size_t)i] = st;
+    B.n_stages = std::max(B.n_stages, st + 1);
+    B.crow.push_back(i);
+  }
+  B.sptr.assign((size_t)B.n_stages + 1, 0);
+  B.by_stage.assign(B.crow.size(), 0);
+  for (int32_t i : B.crow) B.sptr[(size_t)B.stage[(size_t)i] + 1]++;
+  for (int t = 0; t < B.n_stages; ++t) B.sptr[(size_t)t + 1] += B.sptr[(size_t)t];
+  if (B.n_stages > 0) {
+    std::vector<int32_t> pos(B.sptr.begin(), B.sptr.end() - 1);
+    for (int32_t i : B.crow) B.by_stage[(size_t)pos[(size_t)B.stage[(size_t)i]]++] = i;
+  }
+  return true;
+}
+
+// ---- steps of one sweep direction of a block, and the y slots of a self-contained range (gmg_sgs_phase.hpp) ----------
+// prp / pcol: the block's pruned entries (stored value != 0, column inside the block; local numbers, ascending);
+// sptr / by_stage: its coupled rows stage by stage, ascending inside a stage.  dir 0 = forward, 1 = backward.
+struct SsorStep { int32_t first, nrows, len; };  // rows seq[first, first + nrows) of one stage; len: entries of its widest row
+
+inline int ssor_dir_entries(const std::vector<int32_t> &prp, const std::vector<int32_t> &pcol, int dir, int i) {
+  int c = 0;
+  for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) c += dir == 0 ? pcol[(size_t)k] < i : pcol[(size_t)k] >= i;
+  return c;
+}
+
+// The steps: the stages in sweep order, at most max_rows rows of a stage per step (one-wave sweep: records of a step
+// <= kSwMaxBlock bytes), a step's rows and columns <= y_cap slots.  Rows of a stage are independent: the backward sweep
+// takes them in descending order, so that the rows a backward range updates are a DEscending contiguous piece of ycur,
+// as those of a forward range are an ascending one.
+void ssor_build_steps(int dir, int n_stages, const std::vector<int32_t> &sptr, const std::vector<int32_t> &by_stage, const std::vector<int32_t> &prp,
+                      const std::vector<int32_t> &pcol, int max_rows, bool ph, int stride, int y_cap, std::vector<int32_t> &seq, std::vector<SsorStep> &steps) {
+  seq.clear(); steps.clear();
+  seq.reserve(by_stage.size());
+  for (int t = 0; t < n_stages; ++t) {
+    const int tt = dir == 0 ? t : n_stages - 1 - t;
+    SsorStep cur{(int32_t)seq.size(), 0, 0};
+    for (int32_t qq = sptr[(size_t)tt]; qq < sptr[(size_t)tt + 1]; ++qq) {
+      const int32_t q = dir == 0 ? qq : sptr[(size_t)tt] + sptr[(size_t)tt + 1] - 1 - qq;
+      const int i = by_stage[(size_t)q];
+      const int li = ssor_dir_entries(prp, pcol, dir, i);
+      const int nl = std::max(cur.len, li);
+      const int64_t raw = 16 + (int64_t)(cur.nrows + 1) * stride;
+      if (cur.nrows > 0 && (cur.nrows == max_rows || (!ph && raw > kSwMaxBlock) || (cur.nrows + 1) * (nl + 1) > y_cap)) {
+        steps.push_back(cur);
+        cur = SsorStep{(int32_t)seq.size(), 0, 0};
+      }
+      cur.len = std::max(cur.len, li);
+      cur.nrows++;
+      seq.push_back(i);
+    }
+    if (cur.nrows) steps.push_back(cur);
+  }
+}
+
+// y slots of a whole sweep direction as ONE range: a row owns a slot from its step to the step of its last reader (a
+// row i of this direction with a pruned entry a_ic it gathers: c < i forward, c > i backward; the row itself counts).
+// Walking the steps in order, the slots of the rows whose last reader is behind are returned to a free list before the
+// step's rows take theirs, lowest free slot first -- deterministic.  A slot is free for step s when its owner's last
+// reader is < s - 1: a step touches its rows' slots one phase before its dependent phase already (backward, it puts the
+// row's forward value there; forward, the padding entries of a record read it), while the step before may still
+// read or write (gmg_sgs_phase.hpp).
+// A row nobody reads still gets a slot (the step stores to it).  n_slots = the most slots ever live = the highest + 1.
+struct SsorSlotPlan {
+  std::vector<int32_t> step, last, slot;  // per row of the block; -1: a row without couplings
+  int n_slots = 0;
+};
+void ssor_slot_alloc(int m, const std::vector<int32_t> &prp, const std::vector<int32_t> &pcol, int dir, const std::vector<int32_t> &seq,
+                     const std::vector<SsorStep> &steps, SsorSlotPlan &out) {
+  out.step.assign((size_t)m, -1); out.last.assign((size_t)m, -1); out.slot.assign((size_t)m, -1);
+  out.n_slots = 0;
+  for (size_t s = 0; s < steps.size(); ++s)
+    for (int u = 0; u < steps[s].nrows; ++u) out.step[(size_t)seq[(size_t)(steps[s].first + u)]] = (int32_t)s;
+  for (int32_t i : seq) {
+    out.last[(size_t)i] = std::max(out.last[(size_t)i], out.step[(size_t)i]);
+    for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
+      const int c = pcol[(size_t)k];
+      if (dir == 0 ? c < i : c > i) out.last[(size_t)c] = std::max(out.last[(size_t)c], out.step[(size_t)i]);
+    }
+  }
+  const int hold = 2;  // steps behind the last reader before the slot changes hands
+  std::vector<std::vector<int32_t>> due(steps.size() + 1);  // rows whose slot is free from step s on
+  std::priority_queue<int32_t, std::vector<int32_t>, std::greater<int32_t>> free_slots;
+  for (size_t s = 0; s < steps.size(); ++s) {
+    for (int32_t i : due[s]) free_slots.push(out.slot[(size_t)i]);
+    for (int u = 0; u < steps[s].nrows; ++u) {
+      const int i = seq[(size_t)(steps[s].first + u)];
+      if (free_slots.empty()) out.slot[(size_t)i] = out.n_slots++;
+      else { out.slot[(size_t)i] = free_slots.top(); free_slots.pop(); }
+      const size_t rel = (size_t)out.last[(size_t)i] + (size_t)hold;
+      if (rel < steps.size()) due[rel].push_back(i);
+    }
+  }
+}
+
 // Plan of the wavefront sweep (gmg_sgs.hpp): per block the pruned rows, the dependency stages, the steps of both
-// sweep directions, their grouping into LDS-sized ranges, and the record stream in consumption order.
+// sweep directions, their grouping into LDS-sized ranges (or one self-contained range per direction where the live
+// rows fit), and the record stream in consumption order.
 int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val, int n_blocks,
                    const std::vector<int32_t> &block_row, bool allow_phase = true) {
   SgsPlan &G = L.sgs;
@@ -1762,6 +1903,11 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   const bool dep = ph && ctx->sgs_dep;  // one dependent wave + three preparing waves (gmg_sgs_dep.hpp)
   const bool reg = ph && !dep && ctx->sgs_reg && !ctx->sgs_chain;  // four waves, records global -> registers (gmg_sgs_reg.hpp)
   const bool fieldmajor = dep || reg;
+  // one self-contained range per direction (gmg_sgs_phase.hpp) where a block's live rows fit: the default four-wave sweep only
+  const bool slide_ok = ph && !dep && !reg && !ctx->sgs_chain && ctx->sgs_sliding;
+  int n_self = 0, live_max[2] = {0, 0};
+  uint64_t max_yrow = 0;  // largest level row number a self-contained backward record stores through
+  std::vector<int32_t> bwd_rows;  // the aux words of the self-contained backward records, in stream order
   const int late_steps = dep ? kDpLate : 1;
   const int y_max = dep ? kDpYSlots : reg ? kRgYSlots : ph ? kPhYSlots : kSwYSlots;
   int y_cap = ctx->sgs_y_slots > 0 ? ctx->sgs_y_slots : y_max;
@@ -1786,46 +1932,20 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
     block_rng[(size_t)b] = (int32_t)(ph ? pranges.size() : ranges.size());
     blk_steps0[(size_t)b] = total_steps; blk_bytes0[(size_t)b] = (int64_t)stream.size();
     if (m == 0) continue;
-    // ---- in-block nonzero entries of every row (local column numbers), 1 / a_ii as in setup_diag
-    std::vector<int32_t> prp((size_t)m + 1, 0), pcol;
-    std::vector<double> pval, invd((size_t)m, 1.0);
-    std::vector<char> coupled((size_t)m, 0);
-    std::vector<int32_t> low_cnt((size_t)m + 1, 0);
+    // ---- in-block nonzero entries of every row (local column numbers), stages; 1 / a_ii as in setup_diag
+    SsorBlockGraph BG;
+    if (!ssor_block_graph(rb, re, rp, col, val, BG)) return GMG_OK;  // the prefix hand-over needs ascending columns: generic sweep
+    const std::vector<int32_t> &prp = BG.prp, &pcol = BG.pcol, &stage = BG.stage, &crow = BG.crow, &sptr = BG.sptr, &by_stage = BG.by_stage;
+    const std::vector<double> &pval = BG.pval;
+    const int n_stages = BG.n_stages;
+    std::vector<double> invd((size_t)m, 1.0);
     for (int i = 0; i < m; ++i) {
       double aii = 1.0, dstored = 0.0;
-      for (int64_t k = rp[rb + i]; k < rp[rb + i + 1]; ++k) {
-        const int64_t c = col[k];
-        if (k > rp[rb + i] && c <= col[k - 1]) return GMG_OK;  // the prefix hand-over needs ascending columns: generic sweep
-        if (c == rb + i) { aii = val[k]; dstored = val[k]; }
-        if (c < rb || c >= re || val[k] == 0.0) continue;
-        pcol.push_back((int32_t)(c - rb));
-        pval.push_back(val[k]);
-        if (c != rb + i) {
-          coupled[(size_t)i] = 1; coupled[(size_t)(c - rb)] = 1;
-          low_cnt[(size_t)std::max<int64_t>(i, c - rb) + 1]++;
-        }
-      }
-      prp[(size_t)i + 1] = (int32_t)pcol.size();
+      for (int64_t k = rp[rb + i]; k < rp[rb + i + 1]; ++k)
+        if (col[k] == rb + i) { aii = val[k]; dstored = val[k]; }
       invd[(size_t)i] = 1.0 / aii;
       iso_diag[(size_t)(rb + i)] = dstored;
       iso_invd[(size_t)(rb + i)] = 1.0 / aii;
-    }
-    // ---- stages: stage(i) = 1 + max stage(j) over the j < i coupled to i through a_ij or a_ji
-    for (int i = 0; i < m; ++i) low_cnt[(size_t)i + 1] += low_cnt[(size_t)i];
-    std::vector<int32_t> low((size_t)low_cnt[(size_t)m]), fill(low_cnt.begin(), low_cnt.end() - 1);
-    for (int i = 0; i < m; ++i)
-      for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k)
-        if (pcol[(size_t)k] != i) low[(size_t)fill[(size_t)std::max(i, pcol[(size_t)k])]++] = std::min(i, pcol[(size_t)k]);
-    std::vector<int32_t> stage((size_t)m, 0);
-    int n_stages = 0;
-    std::vector<int32_t> crow;  // coupled rows, ascending
-    for (int i = 0; i < m; ++i) {
-      if (!coupled[(size_t)i]) continue;
-      int st = 0;
-      for (int32_t k = low_cnt[(size_t)i]; k < low_cnt[(size_t)i + 1]; ++k) st = std::max(st, stage[(size_t)low[(size_t)k]] + 1);
-      stage[(size_t)i] = st;
-      n_stages = std::max(n_stages, st + 1);
-      crow.push_back(i);
     }
     const size_t ci_base = ci_row.size();
     ci_row.resize(ci_base + crow.size());
@@ -1833,13 +1953,6 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
     rpos_b.resize(ci_row.size(), 0);
     if (crow.empty()) continue;
     total_stages += n_stages;
-    std::vector<int32_t> sptr((size_t)n_stages + 1, 0), by_stage(crow.size());
-    for (int32_t i : crow) sptr[(size_t)stage[(size_t)i] + 1]++;
-    for (int t = 0; t < n_stages; ++t) sptr[(size_t)t + 1] += sptr[(size_t)t];
-    {
-      std::vector<int32_t> pos(sptr.begin(), sptr.end() - 1);
-      for (int32_t i : crow) by_stage[(size_t)pos[(size_t)stage[(size_t)i]]++] = i;
-    }
     // The compact copy ycur is numbered in SWEEP order (stage by stage): the rows a forward range updates are one contiguous
     // piece of it, those of a backward range a run of stage-long pieces -- the working-set loads and write-backs at the range
     // boundaries (a tenth of the sweep) then touch consecutive addresses instead of one cache line per row.
@@ -1854,6 +1967,20 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
     std::vector<int32_t> step_of((size_t)m, -1);
     std::vector<int32_t> upd_stamp((size_t)m, -1);  // == stamp_id: the row is updated in the current range
     int stamp_id = 0, tmp_id = 0;
+    // ---- self-contained ranges: both directions of the block must fit; else the ranged plan, unchanged
+    SsorSlotPlan slide[2];
+    std::vector<int32_t> slide_seq[2];  // the steps the slots were handed out for: the records below are built from these very lists
+    std::vector<SsorStep> slide_steps[2];
+    bool sliding = false;
+    if (slide_ok) {
+      sliding = true;
+      for (int dir = 0; dir < 2; ++dir) {
+        ssor_build_steps(dir, n_stages, sptr, by_stage, prp, pcol, kPhMaxRows, true, 0, y_max, slide_seq[dir], slide_steps[dir]);
+        ssor_slot_alloc(m, prp, pcol, dir, slide_seq[dir], slide_steps[dir], slide[dir]);
+        live_max[dir] = std::max(live_max[dir], slide[dir].n_slots);
+        if (((slide[dir].n_slots + 1) & ~1) > y_cap) sliding = false;
+      }
+    }
     for (int dir = 1; dir >= 0; --dir) {  // backward first: the forward records point into the backward ones
       // entries of a row in this direction: forward = the columns j < i (y_j = 0 for j >= i); backward = the columns
       // j >= i, continuing the forward sum
@@ -1880,86 +2007,74 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
       const int w_dir = 8 * g_dir, stride = ph ? ph_stride(3, 12) : sw_stride(g_dir);
       const int max_rows = ph ? kPhMaxRows : 64;
       // ---- steps: <= 64 rows of one stage, records of a sub-step <= kSwMaxBlock bytes, working set <= y_cap
-      struct Step { int32_t first, nrows, len; };
+      // (self-contained: the allocator's own lists -- the LDS bound is the allocator's, not the step's)
+      using Step = SsorStep;
       std::vector<int32_t> seq;
       std::vector<Step> steps;
-      seq.reserve(crow.size());
-      for (int t = 0; t < n_stages; ++t) {
-        const int tt = dir == 0 ? t : n_stages - 1 - t;
-        Step cur{(int32_t)seq.size(), 0, 0};
-        // (rows of a stage are independent: the backward sweep takes them in descending order, so that the rows a backward range
-        // updates are a DEscending contiguous piece of ycur, as those of a forward range are an ascending one)
-        for (int32_t qq = sptr[(size_t)tt]; qq < sptr[(size_t)tt + 1]; ++qq) {
-          const int32_t q = dir == 0 ? qq : sptr[(size_t)tt] + sptr[(size_t)tt + 1] - 1 - qq;
-          const int i = by_stage[(size_t)q];
-          const int li = n_ent(i);
-          const int nl = std::max(cur.len, li);
-          const int64_t raw = 16 + (int64_t)(cur.nrows + 1) * stride;
-          if (cur.nrows > 0 && (cur.nrows == max_rows || (!ph && raw > kSwMaxBlock) || (cur.nrows + 1) * (nl + 1) > y_cap)) {
-            steps.push_back(cur);
-            cur = Step{(int32_t)seq.size(), 0, 0};
-          }
-          cur.len = std::max(cur.len, li);
-          cur.nrows++;
-          seq.push_back(i);
-        }
-        if (cur.nrows) steps.push_back(cur);
-      }
+      if (sliding) { seq.swap(slide_seq[dir]); steps.swap(slide_steps[dir]); }
+      else ssor_build_steps(dir, n_stages, sptr, by_stage, prp, pcol, max_rows, ph, stride, y_cap, seq, steps);
       // ---- ranges: greedy runs of steps whose rows + referenced rows fit y_cap
       size_t s0 = 0;
       while (s0 < steps.size()) {
         ++stamp_id;
-        int ws = 0;
         size_t s1 = s0;
-        while (s1 < steps.size()) {
-          ++tmp_id;
-          int add = 0;
-          const Step &S = steps[s1];
-          for (int u = 0; u < S.nrows; ++u) {
-            const int i = seq[(size_t)(S.first + u)];
-            if (ws_stamp[(size_t)i] != stamp_id && tmp_stamp[(size_t)i] != tmp_id) { tmp_stamp[(size_t)i] = tmp_id; ++add; }
-            for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-              const int c = pcol[(size_t)k];
-              if (!in_dir(i, c)) continue;
-              if (ws_stamp[(size_t)c] != stamp_id && tmp_stamp[(size_t)c] != tmp_id) { tmp_stamp[(size_t)c] = tmp_id; ++add; }
-            }
-          }
-          if (ws + add > y_cap && s1 > s0) break;
-          if (ws + add > y_cap) return fail(ctx, GMG_ERR_UNSUPPORTED, "SGS plan: one step exceeds the LDS working set");
-          ws += add;
-          for (int u = 0; u < S.nrows; ++u) {
-            const int i = seq[(size_t)(S.first + u)];
-            ws_stamp[(size_t)i] = stamp_id;
-            for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k)
-              if (in_dir(i, pcol[(size_t)k])) ws_stamp[(size_t)pcol[(size_t)k]] = stamp_id;
-          }
-          ++s1;
-        }
-        // slots: rows updated here first (step order), then the rows only read (first touch)
         SwRange R{};
         R.ws_off = (int32_t)ws_ci.size();
         int n_slot = 0;
-        for (size_t st = s0; st < s1; ++st)
-          for (int u = 0; u < steps[st].nrows; ++u) {
-            const int i = seq[(size_t)(steps[st].first + u)];
-            own_stamp[(size_t)i] = stamp_id;
-            slot_of[(size_t)i] = n_slot++;
-            ws_ci.push_back(row_ci[(size_t)(rb + i)]);
-          }
-        R.n_own = n_slot;
-        for (size_t st = s0; st < s1; ++st)
-          for (int u = 0; u < steps[st].nrows; ++u) {
-            const int i = seq[(size_t)(steps[st].first + u)];
-            for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-              const int c = pcol[(size_t)k];
-              if (!in_dir(i, c) || own_stamp[(size_t)c] == stamp_id) continue;
-              own_stamp[(size_t)c] = stamp_id;  // now "has a slot"
-              slot_of[(size_t)c] = n_slot++;
-              ws_ci.push_back(row_ci[(size_t)(rb + c)]);
+        if (sliding) {
+          // the whole direction is the range: the allocator's slots, no working-set list (n_own = n_ws = 0)
+          s1 = steps.size();
+          for (int32_t i : seq) slot_of[(size_t)i] = slide[dir].slot[(size_t)i];
+          max_ws = std::max(max_ws, slide[dir].n_slots);
+        } else {
+          int ws = 0;
+          while (s1 < steps.size()) {
+            ++tmp_id;
+            int add = 0;
+            const Step &S = steps[s1];
+            for (int u = 0; u < S.nrows; ++u) {
+              const int i = seq[(size_t)(S.first + u)];
+              if (ws_stamp[(size_t)i] != stamp_id && tmp_stamp[(size_t)i] != tmp_id) { tmp_stamp[(size_t)i] = tmp_id; ++add; }
+              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
+                const int c = pcol[(size_t)k];
+                if (!in_dir(i, c)) continue;
+                if (ws_stamp[(size_t)c] != stamp_id && tmp_stamp[(size_t)c] != tmp_id) { tmp_stamp[(size_t)c] = tmp_id; ++add; }
+              }
             }
+            if (ws + add > y_cap && s1 > s0) break;
+            if (ws + add > y_cap) return fail(ctx, GMG_ERR_UNSUPPORTED, "SGS plan: one step exceeds the LDS working set");
+            ws += add;
+            for (int u = 0; u < S.nrows; ++u) {
+              const int i = seq[(size_t)(S.first + u)];
+              ws_stamp[(size_t)i] = stamp_id;
+              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k)
+                if (in_dir(i, pcol[(size_t)k])) ws_stamp[(size_t)pcol[(size_t)k]] = stamp_id;
+            }
+            ++s1;
           }
-        R.n_ws = n_slot;
-        max_ws = std::max(max_ws, n_slot);
+          // slots: rows updated here first (step order), then the rows only read (first touch)
+          for (size_t st = s0; st < s1; ++st)
+            for (int u = 0; u < steps[st].nrows; ++u) {
+              const int i = seq[(size_t)(steps[st].first + u)];
+              own_stamp[(size_t)i] = stamp_id;
+              slot_of[(size_t)i] = n_slot++;
+              ws_ci.push_back(row_ci[(size_t)(rb + i)]);
+            }
+          R.n_own = n_slot;
+          for (size_t st = s0; st < s1; ++st)
+            for (int u = 0; u < steps[st].nrows; ++u) {
+              const int i = seq[(size_t)(steps[st].first + u)];
+              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
+                const int c = pcol[(size_t)k];
+                if (!in_dir(i, c) || own_stamp[(size_t)c] == stamp_id) continue;
+                own_stamp[(size_t)c] = stamp_id;  // now "has a slot"
+                slot_of[(size_t)c] = n_slot++;
+                ws_ci.push_back(row_ci[(size_t)(rb + c)]);
+              }
+            }
+          R.n_ws = n_slot;
+          max_ws = std::max(max_ws, n_slot);
+        }
         R.backward = dir;
         R.groups = g_dir;
         R.n_steps = 0;
@@ -2067,6 +2182,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
           P.own_dir = dir == 0 ? 1 : -1;
           for (int k = 0; k < R.n_own && P.own_dir; ++k)
             if (ws_ci[(size_t)R.ws_off + (size_t)k] != P.own_ci0 + P.own_dir * k) P.own_dir = 0;
+          if (sliding) { P.own_dir = 0; P.pad0[0] = 1; P.pad0[1] = slide[dir].n_slots; ++n_self; }
           P.n_steps = (int32_t)(s1 - s0);
           const int64_t base = ((int64_t)stream.size() + 1023) / 1024 * 1024;
           P.stream_off = base;
@@ -2112,8 +2228,12 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
               const uint32_t my = (uint32_t)slot_of[(size_t)i] * 8u;
               f[0] = 0.0; f[1] = invd[(size_t)i]; f[2] = 0.0;
               wv[6] = my;
-              wv[7] = dir == 0 ? (uint32_t)prefix_pos[(size_t)i] : 0u;
-              max_aux = std::max<uint64_t>(max_aux, wv[7]); max_lds_addr = std::max<uint64_t>(max_lds_addr, my);
+              // aux: forward, where the row's sum goes; backward, self-contained: the level row the result is stored to
+              wv[7] = dir == 0 ? (uint32_t)prefix_pos[(size_t)i] : sliding ? (uint32_t)(rb + i) : 0u;
+              if (dir == 0) max_aux = std::max<uint64_t>(max_aux, wv[7]);
+              else max_yrow = std::max<uint64_t>(max_yrow, wv[7]);
+              if (dir == 1 && sliding) bwd_rows.push_back((int32_t)wv[7]);  // (host copy of what the records carry: gmg_get_ssor_backward_rows)
+              max_lds_addr = std::max<uint64_t>(max_lds_addr, my);
               double *hv = f + 4, *tv = f + 4 + 8 * gW;
               uint32_t *ha = reinterpret_cast<uint32_t *>(rec + 32 + 64 * gW + 8 * Lr), *ta = ha + 8 * gW;
               for (int e = 0; e < 8 * gW; ++e) { hv[e] = 0.0; ha[e] = my; }
@@ -2253,6 +2373,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   // ---- the plan is memory-safe by construction, and checked: every address a record carries lies inside what is allocated
   if (!stream.empty() && (max_aux * 8 + 8 > stream.size() || max_lds_addr + 8 > (uint64_t)y_slots * 8))
     return fail(ctx, GMG_ERR_INVALID, "SSOR plan: a record addresses memory outside the stream / the LDS slots (internal error)");
+  if (max_yrow >= (uint64_t)n) return fail(ctx, GMG_ERR_INVALID, "SSOR plan: a backward record stores outside the level vector (internal error)");
   for (int32_t ci : ws_ci)
     if (ci < 0 || (size_t)ci >= ci_row.size()) return fail(ctx, GMG_ERR_INVALID, "SSOR plan: working-set entry out of range (internal error)");
   for (size_t q = 0; q < rpos_f.size(); ++q)
@@ -2270,8 +2391,11 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   HIPC(upload(G.w_stream, stream, ctx->stream));
   HIPC(upload(G.w_iso_diag, iso_diag, ctx->stream));
   HIPC(upload(G.w_iso_invd, iso_invd, ctx->stream));
-  HIPC(G.w_ycur.alloc(std::max<size_t>(ci_row.size(), 1)));
+  // (every range self-contained: nobody reads or writes ycur -- it is not allocated and the pre-pass gets a null pointer)
+  if (!(ph && n_self == (int)pranges.size())) HIPC(G.w_ycur.alloc(std::max<size_t>(ci_row.size(), 1)));
   HIPC(hipStreamSynchronize(ctx->stream));
+  G.host_bwd_rows = bwd_rows;
+  G.n_self = n_self; G.live_max[0] = live_max[0]; G.live_max[1] = live_max[1];
   G.host_block_row = block_row;
   G.host_block_rng = block_rng;
   G.host_block_steps.assign((size_t)n_blocks, 0);
@@ -2303,6 +2427,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPC(hipFuncSetAttribute((const void *)sgs_phase_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_phase_profile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPC(hipFuncSetAttribute((const void *)sgs_dep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPC(hipFuncSetAttribute((const void *)sgs_regs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
 #ifdef GMG_EXPERIMENTS
@@ -2312,6 +2437,10 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   hipFuncAttributes fa{};
   HIPC(hipFuncGetAttributes(&fa, ph ? (const void *)sgs_phase_kernel : (const void *)sgs_wave_kernel<false>));
   G.wave = fa.sharedSizeBytes == 0;
+  if (ph) {
+    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_phase_profile_kernel));
+    G.wave = G.wave && fa.sharedSizeBytes == 0;
+  }
   if (dep) {
     HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_dep_kernel));
     G.wave = G.wave && fa.sharedSizeBytes == 0;
@@ -2330,10 +2459,16 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
     std::fprintf(stderr, "[gmg] SGS step shapes: G %lld %lld %lld %lld | L1/4 %lld %lld %lld %lld %lld %lld %lld %lld | L2/8 %lld %lld %lld %lld\n", (long long)hist_g[0], (long long)hist_g[1],
                  (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
                  (long long)hist_l1[5], (long long)hist_l1[6], (long long)hist_l1[7], (long long)hist_l2[0], (long long)hist_l2[1], (long long)hist_l2[2], (long long)hist_l2[3]);
-  if (ctx->debug_upload)
-    std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges, y slots %d, stream %.1f MB\n",
-                 ph ? "four-wave" : "one-wave", (long long)n, (long long)G.w_n_coupled, n_blocks, (long long)total_stages, (long long)total_steps, G.w_n_ranges, y_slots,
-                 (double)stream.size() / 1e6);
+  int n_bwd = 0;
+  for (const PhRange &P : pranges) n_bwd += P.backward;
+  for (const SwRange &R : ranges) n_bwd += R.backward;
+  G.n_bwd = n_bwd;
+  if (ctx->debug_upload) {
+    std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
+                 "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
+                 ph ? "four-wave" : "one-wave", (long long)n, (long long)G.w_n_coupled, n_blocks, (long long)total_stages, (long long)total_steps, G.w_n_ranges,
+                 G.w_n_ranges - n_bwd, n_bwd, n_self, y_slots, live_max[0], live_max[1], (double)stream.size() / 1e6);
+  }
   return GMG_OK;
 }
 
@@ -4060,6 +4195,7 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   }
   else if (k == "ssor_balanced") ctx->ssor_partition = on ? GMG_SSOR_PARTITION_BALANCED : GMG_SSOR_PARTITION_ROWS;
   else if (k == "sgs_y_slots") ctx->sgs_y_slots = (int)value;
+  else if (k == "sgs_sliding") ctx->sgs_sliding = on;
   else if (k == "sgs_disable_wave") ctx->sgs_disable_wave = on;
   else if (k == "sgs_disable_phase") ctx->sgs_disable_phase = on;
   else if (k == "sgs_dep") ctx->sgs_dep = on;
@@ -4173,6 +4309,52 @@ int gmg_ssor_balance_rows(int64_t n, const int64_t *rowptr, const int32_t *col, 
   }
   std::copy(br.begin(), br.end(), block_row);
   if (block_cost) std::copy(cost.begin(), cost.end(), block_cost);
+  return GMG_OK;
+}
+
+int gmg_get_ssor_plan(gmg_context *ctx, int level, int64_t out[8]) {
+  if (!ctx || !out || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const SgsPlan &G = ctx->lv[(size_t)level].sgs;
+  if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_plan: the level matrix has not been set");
+  std::fill(out, out + 8, (int64_t)0);
+  if (!G.wave) return GMG_OK;  // the generic CSR sweep has no plan
+  out[0] = G.w_n_ranges - G.n_bwd; out[1] = G.n_bwd; out[2] = G.n_self; out[3] = G.w_y_slots;
+  out[4] = G.live_max[0]; out[5] = G.live_max[1]; out[6] = G.w_steps; out[7] = G.w_stream_bytes;
+  return GMG_OK;
+}
+
+int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int32_t *rows) {
+  if (!ctx || !count || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const SgsPlan &G = ctx->lv[(size_t)level].sgs;
+  if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_backward_rows: the level matrix has not been set");
+  *count = G.wave ? (int64_t)G.host_bwd_rows.size() : 0;
+  if (rows && G.wave) std::copy(G.host_bwd_rows.begin(), G.host_bwd_rows.end(), rows);
+  return GMG_OK;
+}
+
+int gmg_ssor_slot_plan(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end, int backward,
+                       int32_t *step, int32_t *last_reader, int32_t *slot, int64_t *n_steps, int64_t *n_slots) {
+  if (n < 0 || n > INT32_MAX || row_begin < 0 || row_end < row_begin || row_end > n || (n > 0 && (!rowptr || !col || !val)) || (n > 0 && rowptr[0] != 0)) return GMG_ERR_INVALID;
+  for (int64_t i = 0; i < n; ++i) {
+    if (rowptr[i + 1] < rowptr[i]) return GMG_ERR_INVALID;
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+      if (col[k] < 0 || col[k] >= n) return GMG_ERR_INVALID;
+  }
+  const int m = (int)(row_end - row_begin), dir = backward ? 1 : 0;
+  SsorBlockGraph B;
+  SsorSlotPlan S;
+  std::vector<int32_t> seq;
+  std::vector<SsorStep> steps;
+  if (m > 0) {
+    if (!ssor_block_graph(row_begin, row_end, rowptr, col, val, B)) return GMG_ERR_INVALID;  // (ascending columns expected)
+    ssor_build_steps(dir, B.n_stages, B.sptr, B.by_stage, B.prp, B.pcol, kPhMaxRows, true, 0, kPhYSlots, seq, steps);
+    ssor_slot_alloc(m, B.prp, B.pcol, dir, seq, steps, S);
+  }
+  if (step) std::copy(S.step.begin(), S.step.end(), step);
+  if (last_reader) std::copy(S.last.begin(), S.last.end(), last_reader);
+  if (slot) std::copy(S.slot.begin(), S.slot.end(), slot);
+  if (n_steps) *n_steps = (int64_t)steps.size();
+  if (n_slots) *n_slots = S.n_slots;
   return GMG_OK;
 }
 

@@ -108,7 +108,7 @@ struct SgsWaveArgs {
   unsigned long long *prof;  // PROFILE variant: per range {cycles of the sweep, of them waiting for the ring, working-set load, write-back}
 };
 
-// rhs -> stream, ycur = 0, and the closed form of the two sweeps for rows without couplings:
+// rhs -> stream, ycur = 0 (where a range reads it), and the closed form of the two sweeps for rows without couplings:
 //   forward  y1 = 0 + (omega (r - 0)) / a_ii ;  backward  y2 = y1 + (omega (r - a_ii y1)) / a_ii
 __global__ __launch_bounds__(256) void sgs_wave_prepass_kernel(SgsWaveArgs a) {
   double *sd = reinterpret_cast<double *>(a.stream);
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(256) void sgs_wave_prepass_kernel(SgsWaveArgs a) {
     } else {
       sd[a.rpos_f[ci]] = ri;
       sd[a.rpos_b[ci]] = ri;
-      a.ycur[ci] = 0.0;
+      if (a.ycur) a.ycur[ci] = 0.0;  // (null: every range of the level is self-contained, gmg_sgs_phase.hpp)
     }
   }
 }

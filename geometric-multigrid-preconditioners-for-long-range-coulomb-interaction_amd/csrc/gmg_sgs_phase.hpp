@@ -19,6 +19,8 @@
 // so that in every phase one wave is in CRIT and the dependent chain is barrier -> <= L1 gathers -> L1 multiply-adds +
 // L2 adds -> one LDS store -> barrier.  A fifth wave touches the record stream ahead of the copies so that they hit
 // the L2.  Nobody spins: every wave executes exactly n_steps + 3 barriers per range.
+// A range is either one of several per direction, with its working set loaded from and written back to ycur at its ends, or
+// SELF-CONTAINED: the whole direction of its block, y slots recycled, nothing loaded or written back (see PhRange below).
 //
 // Shapes.  The code of a step is straight-line for its shape (G groups of 8 head slots, L1, L2): 51 shapes x 2
 // directions are instantiated, the host picks per CHUNK of 32 steps the cheapest shape that holds every row (measured
@@ -64,10 +66,23 @@ struct PhRange {
   int32_t n_steps, ws_off, n_own, n_ws, backward, G, L;  // L = L1 + L2
   uint32_t blk_tab, L1;               // first entry of the range in the block table
   int32_t own_ci0, own_dir, pad0[2];  // own_dir = +1 / -1: slot k of the rows updated here is ycur[own_ci0 + own_dir * k] (ycur is numbered in sweep order); 0: see ws_ci
+                                      // pad0[0] = 1: the range is SELF-CONTAINED (a whole sweep direction of its block, y slots recycled, see below); pad0[1]: its y slots
   uint32_t pf_lead, pf_step;          // prefetch wave: bytes ahead at phase 0, bytes per phase (multiples of 128)
   uint32_t stream_bytes, pad;
 };
 
+// A SELF-CONTAINED range is a whole sweep direction of its block with nothing loaded and nothing written back.  The
+// planner hands a y slot to the next row once the last reader of its owner has run (so the live rows, not the touched
+// ones, must fit the LDS), and what a range used to fetch is known without a load:
+//   forward   starts from y = 0, and every column j < i a row reads was updated earlier in the same sweep;
+//   backward  the columns j > i were updated earlier in the same sweep; the row's own old value is the forward result
+//             y1_i = 0 + (omega (r_i - prefix_i)) / a_ii, formed from the record's own fields by the forward sweep's expression
+//             (same bits) -- in P2, where it is also put into the row's slot for the diagonal term a_ii y1_i of the sum;
+//             the new value goes to the slot and straight to y[aux] (aux: the row's level row number).
+// Who touches a slot when: step t writes its rows' slots in phase t (CRIT), the backward step also in phase t - 1 (P2);
+// the padding entries of its records read them in phases t - 1 and t; the readers of step u read in phases u - 1 and
+// u.  So a slot goes to a row of step t only if its owner's last reader u (>= the owner's own step) is <= t - 2: a
+// barrier lies between every access of the old owner's value and the first access by the new one.
 struct SgsPhaseArgs {
   const PhRange *ranges;
   const int32_t *block_rng;
@@ -130,8 +145,10 @@ struct Turn {
 __host__ __device__ constexpr int ph_key(int g, int l1, int l2) { return g * 64 + (l1 / 4) * 8 + l2 / 8; }
 
 // One step of shape (G, L1, L2) by one wave: four phases, four barriers.
-template <int G, int L1, int L2, bool FWD, bool TIMED>
-__device__ __forceinline__ void turn(Turn &T, bool first, const char *base, double *stream_d, uint32_t region, int lane, double omega) {
+// SC: a backward step of a self-contained range (the forward step is the same code in both kinds of range).
+template <int G, int L1, int L2, bool FWD, bool TIMED, bool SC>
+__device__ __forceinline__ void turn(Turn &T, bool first, const char *base, double *stream_d, double *yout, uint32_t region, int lane, double omega) {
+  static_assert(!(FWD && SC), "the forward step has one form");
   constexpr int L = L1 + L2;
   constexpr uint32_t stride = (uint32_t)ph_stride(G, L);
   Rec<G, L> C;
@@ -142,7 +159,7 @@ __device__ __forceinline__ void turn(Turn &T, bool first, const char *base, doub
   // vmcnt counts this wave's vector-memory operations in issue order (gfx9: loads, LDS copies and stores share the counter):
   // all but the newest one done = the block has arrived; the prefix store of my last step may still be on its way (waiting
   // for it too costs 4 % of the sweep)
-  if (FWD && !first) __builtin_amdgcn_s_waitcnt(0x0f71);
+  if ((FWD || SC) && !first) __builtin_amdgcn_s_waitcnt(0x0f71);  // (SC: the newest is the store to y)
   else __builtin_amdgcn_s_waitcnt(0x0f70);                 // vmcnt(0)
   PH_T(c_wait)
   {
@@ -189,11 +206,19 @@ __device__ __forceinline__ void turn(Turn &T, bool first, const char *base, doub
   PH_T(c_bar)
   // ---- P2: the head (no column of it is written in this phase or the next) and the products behind the last late column
   {
+    C.yold = 0.0;
+    if constexpr (SC) {
+      // the forward result of the row, as the forward CRIT formed it (pinned like the head sum: formed here); into its slot
+      // before the gathers below, the diagonal term reads it there
+      double y1 = 0.0 + (omega * (C.r - C.prefix)) * C.invd;
+      asm volatile("" : "+v"(y1));
+      C.yold = y1;
+      if (lane < C.nrows) lds_st<double>(C.my, y1);
+    }
     double yh[G > 0 ? 8 * G : 1];
 #pragma unroll
     for (int k = 0; k < 8 * G; ++k) yh[k] = lds_ld<double>(C.ha[k]);
-    C.yold = 0.0;
-    if constexpr (!FWD) C.yold = lds_ld<double>(C.my);
+    if constexpr (!FWD && !SC) C.yold = lds_ld<double>(C.my);
     double y2[L2 > 0 ? L2 : 1];
 #pragma unroll
     for (int k = 0; k < L2; ++k) y2[k] = lds_ld<double>(C.ta[L1 + k]);
@@ -232,8 +257,10 @@ __device__ __forceinline__ void turn(Turn &T, bool first, const char *base, doub
 #pragma unroll
     for (int k = 0; k < L2; ++k) acc += C.tv[L1 + k];
     if (lane < C.nrows) {
-      lds_st<double>(C.my, C.yold + (omega * (C.r - acc)) * C.invd);
+      const double ynew = C.yold + (omega * (C.r - acc)) * C.invd;
+      lds_st<double>(C.my, ynew);
       if constexpr (FWD) stream_d[C.aux] = acc;
+      if constexpr (SC) yout[C.aux] = ynew;
     }
   }
   if constexpr (TIMED) { __builtin_amdgcn_s_waitcnt(0xc07f); }
@@ -245,8 +272,8 @@ __device__ __forceinline__ void turn(Turn &T, bool first, const char *base, doub
 
 // The steps t = w, w + 4, ... of a range by compute wave w.  Every step has its own shape (its key travels in the header
 // of the wave's previous block): one indirect branch per turn, in the phase that only reads records.
-template <bool FWD, bool TIMED>
-__device__ __forceinline__ void sweep(const PhRange *R, const uint4 *tab, const char *stream, double *stream_d, uint32_t region, int w, int lane, double omega,
+template <bool FWD, bool TIMED, bool SC>
+__device__ __forceinline__ void sweep(const PhRange *R, const uint4 *tab, const char *stream, double *stream_d, double *yout, uint32_t region, int w, int lane, double omega,
                                       unsigned long long *tp) {
   const int n = R->n_steps;
   const char *base = stream + R->stream_off;
@@ -264,7 +291,7 @@ __device__ __forceinline__ void sweep(const PhRange *R, const uint4 *tab, const 
 #define PH_CASE(g, l1, l2) \
     case ph_key(g, l1, l2): \
       do { \
-        turn<g, l1, l2, FWD, TIMED>(T, t == w, base, stream_d, region, lane, omega); \
+        turn<g, l1, l2, FWD, TIMED, SC>(T, t == w, base, stream_d, yout, region, lane, omega); \
         t += kPhWaves; done += kPhWaves; \
       } while (t < n && (T.key & 0xff) == ph_key(g, l1, l2));  /* (steps of one shape in a row: no dispatch in between) */ \
       break;
@@ -291,20 +318,31 @@ __device__ __forceinline__ void sweep(const PhRange *R, const uint4 *tab, const 
 
 }  // namespace ph
 
-__global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) {
+// The sweep of a launch's blocks.  TIMED: the instrumented variant (s_memtime around every phase, a.prof must be set) --
+// a kernel of its own, so that the production kernel carries neither its timer branches nor its 3 x 51 extra shapes.
+template <bool TIMED>
+__device__ __forceinline__ void sgs_phase_body(const SgsPhaseArgs &a) {
   extern __shared__ __attribute__((aligned(16))) char lds[];  // at LDS address 0: [y slots][3 regions][junk]
   double *ylds = reinterpret_cast<double *>(lds);
   const uint32_t ring0 = (uint32_t)a.y_slots * 8u;
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r_begin = a.block_rng[a.block0 + blockIdx.x], r_end = a.block_rng[a.block0 + blockIdx.x + 1];
+  bool slots_clean = false;
   for (int rg = r_begin; rg < r_end; ++rg) {
     const PhRange *Rp = a.ranges + rg;
     struct { int n_steps, ws_off, n_own, n_ws, backward, G, L; uint32_t pf_lead, pf_step, stream_bytes; int64_t stream_off; } R;
     R.n_steps = Rp->n_steps; R.ws_off = Rp->ws_off; R.n_own = Rp->n_own; R.n_ws = Rp->n_ws; R.backward = Rp->backward; R.G = Rp->G; R.L = Rp->L;
     R.pf_lead = Rp->pf_lead; R.pf_step = Rp->pf_step; R.stream_bytes = Rp->stream_bytes; R.stream_off = Rp->stream_off;
     const int32_t *ws = a.ws_ci + R.ws_off;
+    const bool sc = Rp->pad0[0] != 0;  // self-contained: nothing to load, nothing to write back (n_own = n_ws = 0)
+    if (sc && !slots_clean) {
+      // the padding entries of a record multiply whatever their slot holds by +0.0: it must be finite.  Once per launch:
+      // from here on the slots hold values of the sweep.
+      for (int k = tid; k < a.y_slots; k += kPhThreads) ylds[k] = 0.0;
+      slots_clean = true;
+    }
     unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-    if (a.prof) t0 = __builtin_amdgcn_s_memtime();
+    if constexpr (TIMED) t0 = __builtin_amdgcn_s_memtime();
     // working set -> LDS.  The rows updated here are a contiguous piece of ycur (ascending in a forward range, descending in a
     // backward one): coalesced loads, no index list; the rows only read (~900 .. 5 000 of ~12 000) are gathered through ws_ci.
     // Branch-free: a lane beyond the end repeats the last element (same value, same slot), so every load of a pass is issued
@@ -314,7 +352,7 @@ __global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) {
     const int own_dir = Rp->own_dir, own_ci0 = Rp->own_ci0;
     const int n_direct = own_dir ? R.n_own : 0;
     constexpr int kU = 20;  // elements per thread and pass: two passes cover the 12 256 slots (one pass of 39 was measured slower: 35 k cycles)
-    {
+    if (!sc) {
       const int n_g = R.n_ws - n_direct;  // gathered rows: slots [n_direct, n_ws)
       int gi[kU];
       if (n_g > 0) {
@@ -341,18 +379,20 @@ __global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) {
       }
     }
     __syncthreads();
-    if (a.prof) t1 = __builtin_amdgcn_s_memtime();
+    if constexpr (TIMED) t1 = __builtin_amdgcn_s_memtime();
     if (wid < kPhWaves) {
       double *stream_d = reinterpret_cast<double *>(a.stream);
       const uint32_t region = ring0 + (uint32_t)wid * (uint32_t)kPhRegion;
-      unsigned long long *tp = a.prof ? a.prof + 12 * (size_t)rg + 4 : nullptr;
       const uint4 *tab = a.blk_tab + Rp->blk_tab;
-      if (tp) {  // (the instrumented variant is code of its own: the production sweep carries no timer branches)
-        if (R.backward) ph::sweep<false, true>(Rp, tab, a.stream, stream_d, region, wid, lane, a.omega, tp);
-        else ph::sweep<true, true>(Rp, tab, a.stream, stream_d, region, wid, lane, a.omega, tp);
+      if constexpr (TIMED) {
+        unsigned long long *tp = a.prof + 12 * (size_t)rg + 4;
+        if (R.backward && sc) ph::sweep<false, true, true>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, tp);
+        else if (R.backward) ph::sweep<false, true, false>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, tp);
+        else ph::sweep<true, true, false>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, tp);
       } else {
-        if (R.backward) ph::sweep<false, false>(Rp, tab, a.stream, stream_d, region, wid, lane, a.omega, nullptr);
-        else ph::sweep<true, false>(Rp, tab, a.stream, stream_d, region, wid, lane, a.omega, nullptr);
+        if (R.backward && sc) ph::sweep<false, false, true>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, nullptr);
+        else if (R.backward) ph::sweep<false, false, false>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, nullptr);
+        else ph::sweep<true, false, false>(Rp, tab, a.stream, stream_d, a.y, region, wid, lane, a.omega, nullptr);
       }
     } else {
       // prefetch wave: one 4-byte copy per 128-byte line, pf_step bytes per phase, into the junk area
@@ -373,8 +413,8 @@ __global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) {
     }
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): prefix stores, leftover copies
     __syncthreads();
-    if (a.prof) t2 = __builtin_amdgcn_s_memtime();
-    // LDS -> ycur (and, after the backward sweep, y): the same lanes-repeat-the-last-element form
+    if constexpr (TIMED) t2 = __builtin_amdgcn_s_memtime();
+    // LDS -> ycur (and, after the backward sweep, y): the same lanes-repeat-the-last-element form (self-contained: n_own = 0)
     for (int k0 = 0; k0 < R.n_own; k0 += kU * kPhThreads) {
       int kc[kU], ci[kU];
       double v[kU];
@@ -403,14 +443,17 @@ __global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) {
       }
     }
     __syncthreads();
-    if (a.prof) {
+    if constexpr (TIMED) {
       t3 = __builtin_amdgcn_s_memtime();
       if (tid == 0) {
         unsigned long long *o = a.prof + 12 * (size_t)rg;
-        o[0] = t2 - t1; o[1] = 0; o[2] = t1 - t0; o[3] = t3 - t2;
+        o[0] = t2 - t1; o[1] = 0; o[2] = sc ? 0 : t1 - t0; o[3] = sc ? 0 : t3 - t2;
       }
     }
   }
 }
+
+__global__ __launch_bounds__(kPhThreads) void sgs_phase_kernel(SgsPhaseArgs a) { sgs_phase_body<false>(a); }
+__global__ __launch_bounds__(kPhThreads) void sgs_phase_profile_kernel(SgsPhaseArgs a) { sgs_phase_body<true>(a); }  // option sgs_phase_profile
 
 }  // namespace gmg

@@ -451,7 +451,8 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * debug_upload, disable_sell, disable_patterns, disable_compression, disable_sellp, disable_rowclass, sell_grid, sellp_cost,
  * cg_variant, coarse_chunk, coarse_direct (0 / 1, see gmg_set_coarse_solver), coarse_direct_max_blocks (cap on the grids of the direct
  * coarse solver's passes, 0 = by size; the results do not depend on it), sgs_y_slots (doubles of LDS the SSOR sweep may use for y: small values force
- * several LDS ranges), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
+ * several LDS ranges), sgs_sliding (default 1: the four-wave sweep takes a whole sweep direction of a block as one self-contained LDS range, y slots
+ * recycled, wherever the block's live rows fit; 0: always the ranged plan; same bits either way, see gmg_get_ssor_plan), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
  * sgs_phase_profile (cycle counters of the four-wave sweep: same results, one rank only), sgs_profile (instrumented
  * one-wave sweep; its wrong-result timing modes exist only in a -DGMG_EXPERIMENTS build, tools/build_experiments.sh),
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
@@ -493,6 +494,26 @@ int gmg_get_ssor_partition(gmg_context *ctx, int level, int *n_blocks, int64_t *
  * sweep time in microseconds.                                                                                         */
 int gmg_ssor_balance_rows(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int n_blocks,
                           int64_t *block_row, double *block_cost);
+/* What the SSOR sweep's plan of a level (>= 1) looks like.  out: [0] forward LDS ranges, [1] backward LDS ranges (all blocks),
+ * [2] how many of them are self-contained (a whole sweep direction of a block in one range, nothing loaded or written back at
+ * its ends: option sgs_sliding), [3] y slots (doubles of LDS) the sweep kernel is launched with, [4] / [5] the most y slots
+ * live at once in a forward / backward direction of any block as the slot allocator found them (0: it did not run), [6]
+ * dependent sub-steps, [7] bytes of the record stream.  All 0 for a level on the generic CSR sweep.                          */
+int gmg_get_ssor_plan(gmg_context *ctx, int level, int64_t out[8]);
+/* The level rows the self-contained backward ranges of a level store their results to: the row number every backward
+ * record carries, as written into the record stream, in stream order (block by block, step by step).  count: how many
+ * (0 without self-contained ranges); rows: count entries, may be NULL (call twice).  Each coupled row of each
+ * self-contained block appears exactly once.                                                                       */
+int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int32_t *rows);
+/* The slot allocator of the self-contained ranges for ONE block [row_begin, row_end) and one direction (backward: 0 / 1) of
+ * a level matrix (host CSR, ascending columns, values required: stored zeros do not couple), without a context or a device:
+ * the routine the plan uses.  Per row of the block (row_end - row_begin entries each, any may be NULL; -1 for a row without
+ * couplings inside the block): the step that updates it, the step of its last reader (a row of this direction that gathers
+ * it: c < i forward, c > i backward; at least its own step), its y slot.  A slot changes hands two steps after the last
+ * reader at the earliest.  n_steps: steps of the direction; n_slots: slots used = the
+ * most ever live (the lowest free slot is always taken).                                                                  */
+int gmg_ssor_slot_plan(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end,
+                       int backward, int32_t *step, int32_t *last_reader, int32_t *slot, int64_t *n_steps, int64_t *n_slots);
 
 #ifdef __cplusplus
 }
