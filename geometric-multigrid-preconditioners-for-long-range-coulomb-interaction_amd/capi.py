@@ -18,6 +18,7 @@ JACOBI, SSOR, CHEBYSHEV = 0, 1, 2
 PRECOND_GMG, PRECOND_JACOBI, PRECOND_IDENTITY = 0, 1, 2
 SSOR_PARTITION_ROWS, SSOR_PARTITION_BALANCED = 0, 1
 COARSE_CG, COARSE_DIRECT = 0, 1
+LEVEL_A, LEVEL_EDGE, LEVEL_EDGE_T = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 
 # every symbol include/gmg_coulomb.h declares (checked by tests/test_abi.py)
@@ -25,6 +26,7 @@ SYMBOLS = [
     "gmg_create", "gmg_destroy", "gmg_reset", "gmg_last_error", "gmg_synchronize",
     "gmg_set_system_matrix", "gmg_set_level_matrix", "gmg_set_level_matrix_lattice", "gmg_set_edge_matrix", "gmg_set_prolongation", "gmg_build_transfer", "gmg_get_transfer",
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
+    "gmg_assemble_level_matrix", "gmg_get_level_matrix",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -454,6 +456,42 @@ class Context:
         a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
         self._chk(self.L.gmg_system_matrix_norms(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def assemble_level_matrix(self, level, dim, n_dofs, cell_dofs, K, dof_flags, validate=True):
+        """A level matrix and its interface matrix formed on the device (gmg_assemble_level_matrix); returns the device time in
+        ms.  cell_dofs [n_cells, 2^dim], K [2^dim, 2^dim], dof_flags [n_dofs] (bit 0 boundary, bit 1 refinement edge).
+        validate=True checks the shapes here (ValueError) before the library sees them; the library checks the contents."""
+        nv = 1 << int(dim) if dim in (2, 3) else 0
+        cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        k = np.ascontiguousarray(K, dtype=np.float64)
+        fl = np.ascontiguousarray(dof_flags, dtype=np.uint8)
+        if validate:
+            if nv == 0:
+                raise ValueError("assemble_level_matrix: dim must be 2 or 3")
+            if cd.size % nv or (cd.ndim == 2 and cd.shape[1] != nv):
+                raise ValueError("assemble_level_matrix: cell_dofs must be [n_cells, 2^dim]")
+            if k.size != nv * nv:
+                raise ValueError("assemble_level_matrix: K must be [2^dim, 2^dim]")
+            if n_dofs < 0 or fl.size != n_dofs:
+                raise ValueError("assemble_level_matrix: dof_flags must have n_dofs entries")
+        n_cells = cd.size // nv if nv else len(cd)
+        opt = lambda a, t: _p(a, t) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_level_matrix(self.h, C.c_int(int(level)), C.c_int(int(dim)), C.c_int64(int(n_dofs)), C.c_int64(n_cells),
+                                                   opt(cd, C.c_int32), opt(k, C.c_double), opt(fl, C.c_uint8), C.byref(ms)))
+        return ms.value
+
+    def get_level_matrix(self, level, which=LEVEL_A):
+        """The CSR of a level's operator as the device holds it (gmg_get_level_matrix): which = LEVEL_A, LEVEL_EDGE or
+        LEVEL_EDGE_T; an absent interface matrix comes back with nnz 0."""
+        from types import SimpleNamespace
+        nr, nc, nz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_level_matrix(self.h, C.c_int(level), C.c_int(which), C.byref(nr), C.byref(nc), C.byref(nz), None, None, None))
+        rp = np.zeros(nr.value + 1, dtype=np.int64)
+        col, val = np.zeros(max(nz.value, 1), dtype=np.int32), np.zeros(max(nz.value, 1))
+        self._chk(self.L.gmg_get_level_matrix(self.h, C.c_int(level), C.c_int(which), C.byref(nr), C.byref(nc), C.byref(nz),
+                                              _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double)))
+        return SimpleNamespace(n_rows=nr.value, n_cols=nc.value, nnz=nz.value, rowptr=rp, col=col[:nz.value], val=val[:nz.value])
 
     def estimate_error(self, dim, cell_dofs, cell_level, face_kind, face_cell, h_of_level, face_measure_of_level, diameter_of_level,
                        gauss_x, gauss_w, u, residual=0, weight=None, jxw_of_level=None, dens=None, fraction=0.6, n_u=None, validate=True):

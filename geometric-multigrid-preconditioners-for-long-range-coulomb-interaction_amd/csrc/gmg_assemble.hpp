@@ -34,6 +34,30 @@
 // (4) asm_norm_sums_kernel, one thread per row: sum |a| over the row in stored order, and over the column of the same
 // index in ascending row order -- the pattern is structurally symmetric, so column c's rows are row c's columns, found in
 // each of those rows by bisection (a gather: no atomics, no transpose).
+//
+// ---- The multigrid level matrices A_l and the interface ("edge") matrices I_l (gmg_assemble_level_matrix, DESIGN.md section
+// 17): LaplaceProblem::assemble_level from one level's cell table, with the same machinery (the kernels' LEVEL form).
+//
+// Inputs.  cell_dofs [n_cells][nv] (all cells of the level, vertex a = bx + 2 by + 4 bz), ONE cell matrix K [nv][nv] row-major
+// as the host scales it for the level (Kc[i][j] * pow(h_l, dim - 2)), dof_flags [n_dofs]: bit 0 = the DoF is on the boundary
+// (level_boundary), bit 1 = it is on the refinement edge (level_refinement_edge).  There are no constraint lines.
+//
+// A_l pattern.  Row r stores the sorted union of the DoFs of all cells that contain r.  Stored zeros are kept; a flagged row
+// keeps its whole pattern.
+// A_l values.  Every entry starts at +0.0; cells ascending, then i ascending: if dof_flags[dofs[i]] != 0,
+//   (dofs[i], dofs[i]) += |K[i][i]|   and nothing else from this i;
+// otherwise, for j ascending with dof_flags[dofs[j]] == 0,   (dofs[i], dofs[j]) += K[i][j].
+// Jacobi diagonal and Chebyshev bound (setup_diag).  invd[r] = 1 / a_rr; cheb_lmax = max_r (sum_k |a_rk| in stored order) /
+// |a_rr|: asm_gershgorin_kernel, one sequential sum per row, the maximum through an integer atomicMax on the bits of the
+// non-negative ratios (order-independent; a NaN ratio -- an empty row -- is skipped as std::max skips it).
+// I_l pattern.  The pairs (dofs[i], dofs[j]) of any cell with dof_flags[dofs[i]] == 2 (on the edge, not on the boundary) and
+// dof_flags[dofs[j]] == 0: row r of A_l filtered by the column flags, for the rows r with flag 2.
+// I_l values.  The sum of its cells' K[i][j] in ascending cell order (then i, then j), starting from the first contribution;
+// entries whose sum == 0.0 are then dropped, as gmg_set_edge_matrix drops them.  The FILL pass of asm_row_kernel forms them
+// beside A_l's values (one lane per stored column) and counts the survivors; asm_edge_fill_kernel compacts them.
+// I_l^T.  Row j lists the entries (r, j) of I_l in ascending r: the rows that may hold column j are the columns of row j of A_l
+// (structural symmetry), and j is found in each of those rows of I_l by bisection (asm_edge_transpose_kernel, count and
+// fill) -- what the stable host transpose of gmg_set_edge_matrix gives, without atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,6 +78,7 @@ struct AsmArgs {
   const int32_t *line_ptr;    // [n_lines + 1]
   const int32_t *line_master;
   const double *line_weight;
+  const uint8_t *flags;       // LEVEL form: [n_dofs], bit 0 boundary, bit 1 refinement edge (cell_level, cons and the lines are unused, K is one matrix)
   int32_t *inc_ptr;   // [n_dofs + 1]: slots of every row (counts before the scan)
   int32_t *inc_pos;   // [n_dofs]: fill cursors
   int32_t *inc_slot;  // [inc_ptr[n_dofs]]
@@ -63,10 +88,13 @@ struct AsmArgs {
   double *invd;                    // [n_dofs]: 1 / a_rr (1 / +0.0 where the row stores no diagonal)
   unsigned long long *total;       // sum of the row lengths in 64 bits (the scan is 32-bit)
   int *overflow;                   // a row with more than kAsmMaxRow columns was met
+  double *edge_val;                // LEVEL form: beside val, the interface-matrix sum of every stored entry (0.0: not an entry of I_l); rows with flag 2 only
+  int32_t *edge_cnt;               // LEVEL form: [n_dofs + 1]: entries of I_l per row (sums != 0.0)
 };
 
 // the rows slot s contributes to: its DoF, and the masters of the DoF's line that are neither the DoF nor an earlier master
-template <bool FILL>
+// (LEVEL: its DoF)
+template <bool FILL, bool LEVEL = false>
 __global__ __launch_bounds__(256) void asm_incidence_kernel(AsmArgs a) {
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < a.n_slots; s += (int64_t)gridDim.x * blockDim.x) {
     const int32_t d = a.cell_dofs[s];
@@ -75,6 +103,7 @@ __global__ __launch_bounds__(256) void asm_incidence_kernel(AsmArgs a) {
       else atomicAdd(&a.inc_ptr[x], 1);
     };
     emit(d);
+    if constexpr (LEVEL) continue;
     const int32_t l = a.cons[d];
     if (l < 0) continue;
     const int32_t e0 = a.line_ptr[l], e1 = a.line_ptr[l + 1];
@@ -145,9 +174,36 @@ __device__ __forceinline__ void asm_add_slot(const AsmArgs &a, int32_t slot, int
   }
 }
 
+// LEVEL form: what assemble_level adds to (r, c) of A_l for slot (cell, i) -- dofs[i] == r -- in its order of j
+__device__ __forceinline__ void asm_add_level_slot(const AsmArgs &a, int32_t slot, int32_t r, int32_t c, double &acc) {
+  const int nv = a.nv;
+  const int i = slot & (nv - 1);
+  const int32_t *cd = a.cell_dofs + (int64_t)(slot >> a.lg_nv) * nv;
+  if (a.flags[r] != 0) {
+    if (c == r) acc += fabs(a.K[i * nv + i]);
+    return;
+  }
+  for (int j = 0; j < nv; ++j)
+    if (cd[j] == c && a.flags[c] == 0) acc += a.K[i * nv + j];
+}
+
+// LEVEL form: what slot (cell, i) contributes to (r, c) of I_l (flag 2 on r, flag 0 on c): the sum starts from its first term
+__device__ __forceinline__ void asm_add_edge_slot(const AsmArgs &a, int32_t slot, int32_t c, double &acc, bool &any) {
+  const int nv = a.nv;
+  const int i = slot & (nv - 1);
+  const int32_t *cd = a.cell_dofs + (int64_t)(slot >> a.lg_nv) * nv;
+  for (int j = 0; j < nv; ++j)
+    if (cd[j] == c) {
+      const double v = a.K[i * nv + j];
+      acc = any ? acc + v : v;
+      any = true;
+    }
+}
+
 // One wavefront per row (workgroups of 64).  FILL = false: rowptr[r] = number of distinct columns.  FILL = true (rowptr
-// scanned): the columns in ascending order, the values, the Jacobi diagonal.
-template <bool FILL>
+// scanned): the columns in ascending order, the values, the Jacobi diagonal.  LEVEL: a cell's coupling list is its DoFs, the
+// values are assemble_level's, and the rows with flag 2 also form their interface-matrix sums (edge_val) and count them.
+template <bool FILL, bool LEVEL = false>
 __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
   __shared__ int32_t set[kAsmMaxRow + 64];
   __shared__ int32_t sorted[FILL ? kAsmMaxRow : 1];
@@ -171,7 +227,7 @@ __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
         if (b < nv) {
           const int32_t d = a.cell_dofs[(int64_t)cell * nv + b];
           if (k == 0) c = d;
-          else {
+          else if constexpr (!LEVEL) {
             const int32_t l = a.cons[d];
             if (l >= 0) {
               const int32_t e = a.line_ptr[l] + (k - 1);
@@ -208,14 +264,32 @@ __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
       }
       __syncthreads();
       bool has_diag = false;
+      int n_edge = 0;
+      const bool edge_row = LEVEL && n > 0 && a.flags[r] == 2;
       for (int k = lane; k < n; k += 64) {
         const int32_t c = sorted[k];
         double acc = 0.0;
-        for (int32_t q = q0; q < q1; ++q) asm_add_slot(a, a.inc_slot[q], (int32_t)r, c, acc);
+        for (int32_t q = q0; q < q1; ++q) {
+          if constexpr (LEVEL) asm_add_level_slot(a, a.inc_slot[q], (int32_t)r, c, acc);
+          else asm_add_slot(a, a.inc_slot[q], (int32_t)r, c, acc);
+        }
         a.val[k0 + k] = acc;
         if (c == (int32_t)r) { a.invd[r] = 1.0 / acc; has_diag = true; }
+        if (edge_row) {
+          double e = 0.0;
+          if (a.flags[c] == 0) {
+            bool any = false;
+            for (int32_t q = q0; q < q1; ++q) asm_add_edge_slot(a, a.inc_slot[q], c, e, any);
+          }
+          a.edge_val[k0 + k] = e;
+          n_edge += e != 0.0 ? 1 : 0;
+        }
       }
       if (__ballot(has_diag) == 0ull && lane == 0) a.invd[r] = __builtin_inf();  // (setup_diag: a row without a diagonal)
+      if constexpr (LEVEL) {
+        for (int off = 32; off > 0; off >>= 1) n_edge += __shfl_down(n_edge, off);
+        if (lane == 0) a.edge_cnt[r] = n_edge;
+      }
       __syncthreads();
     }
   }
@@ -243,6 +317,59 @@ __global__ __launch_bounds__(256) void asm_norm_sums_kernel(const int32_t *rowpt
     }
     row_sum[c] = rs;
     col_sum[c] = cs;
+  }
+}
+
+// cheb_lmax of setup_diag on the device's CSR: max over the rows of (sum |a_rk| in stored order) / |a_rr| -- a_rr = 0.0 where
+// the row stores no diagonal -- as the bits of a non-negative double (*lmax_bits starts at 0)
+__global__ __launch_bounds__(256) void asm_gershgorin_kernel(const int32_t *rowptr, const int32_t *col, const double *val, int64_t n,
+                                                             unsigned long long *lmax_bits) {
+  double m = 0.0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    double aii = 0.0, rs = 0.0;
+    for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k) {
+      if (col[k] == (int32_t)r) aii = val[k];
+      rs += fabs(val[k]);
+    }
+    const double ratio = rs / fabs(aii);
+    if (m < ratio) m = ratio;  // (std::max(m, ratio): a NaN is skipped)
+  }
+  if (m > 0.0) atomicMax(lmax_bits, (unsigned long long)__double_as_longlong(m));
+}
+
+// I_l from the sums the row kernel left beside A_l's values: the entries != 0.0 of every row, in stored order (irp scanned)
+__global__ __launch_bounds__(256) void asm_edge_fill_kernel(const int32_t *rowptr, const int32_t *col, const double *edge_val, int64_t n,
+                                                            const int32_t *irp, int32_t *icol, double *ival) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
+    int32_t p = irp[r];
+    if (p == irp[r + 1]) continue;  // (edge_val is only written for the rows that have entries to count)
+    for (int32_t k = rowptr[r]; k < rowptr[r + 1]; ++k)
+      if (edge_val[k] != 0.0) { icol[p] = col[k]; ival[p] = edge_val[k]; ++p; }
+  }
+}
+
+// I_l^T, one thread per row j of it: the rows r of I_l that store column j, ascending, among the columns of row j of A_l.
+// FILL = false: trp[j] = their number; FILL = true (trp scanned): the entries.
+template <bool FILL>
+__global__ __launch_bounds__(256) void asm_edge_transpose_kernel(const int32_t *rowptr, const int32_t *col, int64_t n, const int32_t *irp,
+                                                                 const int32_t *icol, const double *ival, int32_t *trp, int32_t *tcol, double *tval) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+    int32_t p = FILL ? trp[j] : 0;
+    for (int32_t k = rowptr[j]; k < rowptr[j + 1]; ++k) {
+      const int32_t r = col[k];
+      int32_t lo = irp[r], hi = irp[r + 1];
+      const int32_t end = hi;
+      while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (icol[mid] < (int32_t)j) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < end && icol[lo] == (int32_t)j) {
+        if constexpr (FILL) { tcol[p] = r; tval[p] = ival[lo]; }
+        ++p;
+      }
+    }
+    if constexpr (!FILL) trp[j] = p;
   }
 }
 

@@ -2603,6 +2603,87 @@ std::vector<int32_t> window_tiles(const RP *rowptr, int64_t n_rows) {
   return tiles;
 }
 
+// a CSR the device formed in place (rowptr / col / val of m): its sizes and the row-window tiling from the row pointers
+int tile_device_csr(gmg_context *ctx, DevCSR &m, const std::vector<int32_t> &rp, int64_t n_rows, int64_t n_cols, int64_t nnz) {
+  const std::vector<int32_t> tiles = window_tiles(rp.data(), n_rows);
+  m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
+  m.n_tiles = (int)tiles.size() - 1;
+  m.tiles_per_xcd = (m.n_tiles + 7) / 8;
+  m.grid = 8 * std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
+  HIPC(upload(m.tile_row, tiles, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(launch_status(ctx));
+  m.valid = true;
+  return GMG_OK;
+}
+
+// grid of an assembly kernel: by size, at most `most` workgroups, capped by option assemble_max_blocks
+dim3 asm_blocks(const gmg_context *ctx, int64_t n, int per_block, int most = 1 << 16) {
+  int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + per_block - 1) / per_block));
+  if (ctx->assemble_max_blocks > 0) g = std::min<int64_t>(g, ctx->assemble_max_blocks);
+  return dim3((unsigned)g);
+}
+
+struct AsmScratch {  // lives until the stream has run the kernels
+  DevPtr<int32_t> iptr, ipos, islot;
+  DevPtr<unsigned long long> total;
+  DevPtr<int> over;
+};
+
+// What the two device assemblies share (gmg_assemble.hpp; LEVEL: the level-matrix form): the incidence lists, the pattern,
+// and the FILL pass of the row kernel.  a holds the inputs and the outputs the caller owns (invd, ...); m receives rowptr /
+// col / val, rp the row pointers on the host, n_inc the (row, slot) pairs.  before_fill(nnz) may point a at further outputs of
+// the FILL pass once their size is known.  The FILL pass is enqueued, not waited for.
+template <bool LEVEL, class BeforeFill>
+int assemble_rows(gmg_context *ctx, const char *who, AsmArgs &a, AsmScratch &w, DevCSR &m, std::vector<int32_t> &rp, int64_t &nnz, int32_t &n_inc,
+                  BeforeFill before_fill) {
+  const int64_t n_dofs = a.n_dofs, n_slots = a.n_slots;
+  HIPC(w.iptr.alloc((size_t)n_dofs + 1));
+  HIPC(w.ipos.alloc((size_t)n_dofs + 1));
+  HIPC(m.rowptr.alloc((size_t)n_dofs + 1));
+  HIPC(w.total.alloc(1));
+  HIPC(w.over.alloc(1));
+  HIPC(hipMemsetAsync(w.iptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(w.ipos.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(m.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(w.total.get(), 0, sizeof(unsigned long long), ctx->stream));
+  HIPC(hipMemsetAsync(w.over.get(), 0, sizeof(int), ctx->stream));
+  a.inc_ptr = w.iptr.get(); a.inc_pos = w.ipos.get(); a.rowptr = m.rowptr.get(); a.total = w.total.get(); a.overflow = w.over.get();
+  const dim3 g_slots = asm_blocks(ctx, n_slots, 256), g_dofs = asm_blocks(ctx, n_dofs, 256), g_rows = asm_blocks(ctx, n_dofs, 1);
+  if (n_slots) hipLaunchKernelGGL((asm_incidence_kernel<false, LEVEL>), g_slots, dim3(256), 0, ctx->stream, a);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w.iptr.get(), n_dofs);
+  n_inc = 0;
+  HIPC(hipMemcpyAsync(&n_inc, w.iptr.get() + n_dofs, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  HIPC(w.islot.alloc((size_t)std::max<int32_t>(n_inc, 1)));
+  a.inc_slot = w.islot.get();
+  if (n_slots) {
+    hipLaunchKernelGGL((asm_incidence_kernel<true, LEVEL>), g_slots, dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(asm_sort_incidence_kernel, g_dofs, dim3(256), 0, ctx->stream, a);
+  }
+  if (n_dofs) hipLaunchKernelGGL((asm_row_kernel<false, LEVEL>), g_rows, dim3(64), 0, ctx->stream, a);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr.get(), n_dofs);
+  rp.assign((size_t)n_dofs + 1, 0);
+  unsigned long long total = 0;
+  int over = 0;
+  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&total, w.total.get(), sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&over, w.over.get(), sizeof over, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (over) return fail(ctx, GMG_ERR_UNSUPPORTED, (std::string(who) + ": a row with more than 512 columns").c_str());
+  if (total >= (1ull << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, (std::string(who) + ": operator needs 64-bit device indices (nnz >= 2^31)").c_str());
+  nnz = (int64_t)total;
+  const size_t pad = 8;
+  HIPC(m.col.alloc((size_t)nnz + pad));
+  HIPC(m.val.alloc((size_t)nnz + pad));
+  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
+  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
+  a.col = m.col.get(); a.val = m.val.get();
+  CHK(before_fill(nnz));
+  if (n_dofs) hipLaunchKernelGGL((asm_row_kernel<true, LEVEL>), g_rows, dim3(64), 0, ctx->stream, a);
+  return GMG_OK;
+}
+
 DevCSR *which_matrix(gmg_context *ctx, int which) {
   if (which == GMG_SYSTEM) return &ctx->S;
   if (which < 0 || which >= ctx->n_levels) return nullptr;
@@ -3767,11 +3848,10 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
   DevCSR &m = ctx->S;
   reset_keep_halo(m);
   ctx->S_invd.reset(); ctx->S_tmp.reset();
-  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm, d_iptr, d_ipos, d_islot;
+  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
   DevPtr<uint8_t> d_lv;
   DevPtr<double> d_K, d_lw;
-  DevPtr<unsigned long long> d_total;
-  DevPtr<int> d_over;
+  AsmScratch w;
   Event e0, e1;
   HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
   HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
@@ -3780,76 +3860,29 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
   HIPC(upload(d_lp, lp32, ctx->stream));
   HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
   HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
-  HIPC(d_iptr.alloc((size_t)n_dofs + 1));
-  HIPC(d_ipos.alloc((size_t)n_dofs + 1));
-  HIPC(m.rowptr.alloc((size_t)n_dofs + 1));
-  HIPC(d_total.alloc(1));
-  HIPC(d_over.alloc(1));
   CHK(alloc_vec(ctx, ctx->S_invd, n_dofs));
   CHK(alloc_vec(ctx, ctx->S_tmp, n_dofs));
   HIPC(e0.create());
   HIPC(e1.create());
   HIPC(hipEventRecord(e0.get(), ctx->stream));
-  HIPC(hipMemsetAsync(d_iptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
-  HIPC(hipMemsetAsync(d_ipos.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
-  HIPC(hipMemsetAsync(m.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
-  HIPC(hipMemsetAsync(d_total.get(), 0, sizeof(unsigned long long), ctx->stream));
-  HIPC(hipMemsetAsync(d_over.get(), 0, sizeof(int), ctx->stream));
   AsmArgs a{};
   a.nv = nv; a.lg_nv = dim; a.max_line = (int)max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
   a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.K = d_K.get(); a.cons = d_cons.get();
   a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
-  a.inc_ptr = d_iptr.get(); a.inc_pos = d_ipos.get(); a.rowptr = m.rowptr.get(); a.invd = ctx->S_invd.get();
-  a.total = d_total.get(); a.overflow = d_over.get();
-  const int cap = ctx->assemble_max_blocks;
-  auto blocks = [&](int64_t n, int per_block, int most) {
-    int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + per_block - 1) / per_block));
-    if (cap > 0) g = std::min<int64_t>(g, cap);
-    return dim3((unsigned)g);
-  };
-  const dim3 g_slots = blocks(n_slots, 256, 1 << 16), g_dofs = blocks(n_dofs, 256, 1 << 16), g_rows = blocks(n_dofs, 1, 1 << 16);
-  if (n_slots) hipLaunchKernelGGL(asm_incidence_kernel<false>, g_slots, dim3(256), 0, ctx->stream, a);
-  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_iptr.get(), n_dofs);
+  a.invd = ctx->S_invd.get();
+  std::vector<int32_t> rp;
+  int64_t nnz = 0;
   int32_t n_inc = 0;
-  HIPC(hipMemcpyAsync(&n_inc, d_iptr.get() + n_dofs, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  HIPC(d_islot.alloc((size_t)std::max<int32_t>(n_inc, 1)));
-  a.inc_slot = d_islot.get();
-  if (n_slots) {
-    hipLaunchKernelGGL(asm_incidence_kernel<true>, g_slots, dim3(256), 0, ctx->stream, a);
-    hipLaunchKernelGGL(asm_sort_incidence_kernel, g_dofs, dim3(256), 0, ctx->stream, a);
+  int rc = assemble_rows<false>(ctx, "gmg_assemble_system_matrix", a, w, m, rp, nnz, n_inc, [](int64_t) { return (int)GMG_OK; });
+  if (rc == GMG_OK) {
+    rc = hipEventRecord(e1.get(), ctx->stream) == hipSuccess ? GMG_OK : fail(ctx, GMG_ERR_HIP, "gmg_assemble_system_matrix: hipEventRecord");
+    if (rc == GMG_OK) rc = tile_device_csr(ctx, m, rp, n_dofs, n_dofs, nnz);
   }
-  if (n_dofs) hipLaunchKernelGGL(asm_row_kernel<false>, g_rows, dim3(64), 0, ctx->stream, a);
-  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr.get(), n_dofs);
-  std::vector<int32_t> rp((size_t)n_dofs + 1);
-  unsigned long long total = 0;
-  int over = 0;
-  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipMemcpyAsync(&total, d_total.get(), sizeof total, hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipMemcpyAsync(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  if (over || total >= (1ull << 31)) { reset_keep_halo(m); ctx->S_invd.reset(); ctx->S_tmp.reset(); }
-  if (over) { return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: a row with more than 512 columns"); }
-  if (total >= (1ull << 31)) { return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: operator needs 64-bit device indices (nnz >= 2^31)"); }
-  const int64_t nnz = (int64_t)total;
-  const size_t pad = 8;
-  HIPC(m.col.alloc((size_t)nnz + pad));
-  HIPC(m.val.alloc((size_t)nnz + pad));
-  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
-  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
-  a.col = m.col.get(); a.val = m.val.get();
-  if (n_dofs) hipLaunchKernelGGL(asm_row_kernel<true>, g_rows, dim3(64), 0, ctx->stream, a);
-  HIPC(hipEventRecord(e1.get(), ctx->stream));
-  // the row-window tiling (host: a pass over the row pointers, as gmg_build_transfer does for its operators)
-  const std::vector<int32_t> tiles = window_tiles(rp.data(), n_dofs);
-  m.n_rows = m.n_cols = n_dofs; m.nnz = nnz;
-  m.n_tiles = (int)tiles.size() - 1;
-  m.tiles_per_xcd = (m.n_tiles + 7) / 8;
-  m.grid = 8 * std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
-  HIPC(upload(m.tile_row, tiles, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  CHK(launch_status(ctx));
-  m.valid = true;
+  if (rc != GMG_OK) {  // (nothing half-built stays behind)
+    (void)hipStreamSynchronize(ctx->stream);
+    reset_keep_halo(m); ctx->S_invd.reset(); ctx->S_tmp.reset();
+    return rc;
+  }
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
   if (build_ms) *build_ms = ms;
@@ -3902,6 +3935,174 @@ int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *
   if (l1) *l1 = mx;
   CHK(gmg_vec_norms(ctx, m.val.get(), m.nnz, &s1, &s2, &mx));
   if (frobenius) *frobenius = s2;
+  return GMG_OK;
+}
+
+// ---- the multigrid level and interface matrices formed on the device (gmg_assemble.hpp) ----
+
+static int assemble_level_checked(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
+                           const uint8_t *dof_flags, double *build_ms) {
+  const char *who = "gmg_assemble_level_matrix";
+  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: not on a communicator (rank-local assembly does not exist yet)");
+  if (level == 0 && l0_partitioned(ctx)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: a row-partitioned level 0 takes its local rows as CSR (gmg_set_level_matrix)");
+  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: dim must be 2 or 3");
+  if (n_dofs < 0 || n_cells < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: negative size");
+  const int nv = 1 << dim;
+  if ((n_cells > 0 && (!cell_dofs || !K)) || (n_dofs > 0 && !dof_flags)) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: an array of nonzero length is NULL");
+  if (n_dofs >= ((int64_t)1 << 31) || n_cells >= ((int64_t)1 << 31) / nv) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: more than 2^31 DoFs or slots");
+  const int64_t n_slots = n_cells * nv;
+  for (int64_t s = 0; s < n_slots; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: DoF outside [0, n_dofs)");
+  for (int64_t d = 0; d < n_dofs; ++d)
+    if (dof_flags[d] > 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: flag bits above 1");
+  const auto ex = level > 0 ? ctx->ssor_block_rows.find(level) : ctx->ssor_block_rows.end();
+  const std::vector<int64_t> *explicit_rows = ex == ctx->ssor_block_rows.end() ? nullptr : &ex->second;
+  if (explicit_rows && explicit_rows->back() != n_dofs)
+    return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_dofs");
+  Level &L = ctx->lv[(size_t)level];
+  DevCSR &m = L.A;
+  DevPtr<int32_t> d_cd;
+  DevPtr<uint8_t> d_fl;
+  DevPtr<double> d_K, d_eval;
+  DevPtr<unsigned long long> d_lmax;
+  AsmScratch w;
+  Event e0, e1;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_K, K, n_cells > 0 ? (size_t)nv * nv : 0, ctx->stream));
+  HIPC(upload(d_fl, dof_flags, (size_t)n_dofs, ctx->stream));
+  HIPC(L.I.rowptr.alloc((size_t)n_dofs + 1));  // (the row kernel counts I_l's entries into it)
+  HIPC(d_lmax.alloc(1));
+  CHK(alloc_vec(ctx, L.invd, n_dofs));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(hipMemsetAsync(L.I.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(d_lmax.get(), 0, sizeof(unsigned long long), ctx->stream));
+  AsmArgs a{};
+  a.nv = nv; a.lg_nv = dim; a.max_line = 0; a.n_dofs = n_dofs; a.n_slots = n_slots;
+  a.cell_dofs = d_cd.get(); a.K = d_K.get(); a.flags = d_fl.get(); a.invd = L.invd.get(); a.edge_cnt = L.I.rowptr.get();
+  std::vector<int32_t> rp;
+  int64_t nnz = 0;
+  int32_t n_inc = 0;
+  CHK(assemble_rows<true>(ctx, who, a, w, m, rp, nnz, n_inc, [&](int64_t nz) {
+    HIPC(d_eval.alloc((size_t)std::max<int64_t>(nz, 1)));
+    a.edge_val = d_eval.get();
+    return (int)GMG_OK;
+  }));
+  const dim3 g_dofs = asm_blocks(ctx, n_dofs, 256);
+  const int32_t *c_rp = m.rowptr.get(), *c_col = m.col.get();
+  if (n_dofs) hipLaunchKernelGGL(asm_gershgorin_kernel, g_dofs, dim3(256), 0, ctx->stream, c_rp, c_col, (const double *)m.val.get(), n_dofs, d_lmax.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, L.I.rowptr.get(), n_dofs);
+  // the host needs the CSR for the SSOR plan (setup_sgs) and the row pointers for the tilings
+  std::vector<int32_t> col_h((size_t)nnz), irp((size_t)n_dofs + 1), trp;
+  std::vector<double> val_h((size_t)nnz);
+  unsigned long long lmax_bits = 0;
+  HIPC(hipMemcpyAsync(irp.data(), L.I.rowptr.get(), sizeof(int32_t) * irp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&lmax_bits, d_lmax.get(), sizeof lmax_bits, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const int64_t n_edge = irp[(size_t)n_dofs];
+  if (n_edge > 0) {
+    const size_t pad = 8;
+    for (DevCSR *x : {&L.I, &L.It}) {
+      HIPC(x->col.alloc((size_t)n_edge + pad));
+      HIPC(x->val.alloc((size_t)n_edge + pad));
+      HIPC(hipMemsetAsync(x->col.get() + n_edge, 0, sizeof(int32_t) * pad, ctx->stream));
+      HIPC(hipMemsetAsync(x->val.get() + n_edge, 0, sizeof(double) * pad, ctx->stream));
+    }
+    HIPC(L.It.rowptr.alloc((size_t)n_dofs + 1));
+    const int32_t *c_irp = L.I.rowptr.get(), *c_icol = L.I.col.get();
+    const double *c_ival = L.I.val.get();
+    hipLaunchKernelGGL(asm_edge_fill_kernel, g_dofs, dim3(256), 0, ctx->stream, c_rp, c_col, (const double *)d_eval.get(), n_dofs, c_irp, L.I.col.get(), L.I.val.get());
+    hipLaunchKernelGGL(asm_edge_transpose_kernel<false>, g_dofs, dim3(256), 0, ctx->stream, c_rp, c_col, n_dofs, c_irp, c_icol, c_ival, L.It.rowptr.get(), L.It.col.get(), L.It.val.get());
+    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, L.It.rowptr.get(), n_dofs);
+    hipLaunchKernelGGL(asm_edge_transpose_kernel<true>, g_dofs, dim3(256), 0, ctx->stream, c_rp, c_col, n_dofs, c_irp, c_icol, c_ival, L.It.rowptr.get(), L.It.col.get(), L.It.val.get());
+    trp.resize((size_t)n_dofs + 1);
+    HIPC(hipMemcpyAsync(trp.data(), L.It.rowptr.get(), sizeof(int32_t) * trp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  if (level > 0 && nnz) {
+    HIPC(hipMemcpyAsync(col_h.data(), m.col.get(), sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(val_h.data(), m.val.get(), sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(tile_device_csr(ctx, m, rp, n_dofs, n_dofs, nnz));
+  if (n_edge > 0) {
+    if (trp[(size_t)n_dofs] != n_edge) return fail(ctx, GMG_ERR_HIP, "gmg_assemble_level_matrix: the transposed interface matrix lost entries");
+    CHK(tile_device_csr(ctx, L.I, irp, n_dofs, n_dofs, n_edge));
+    CHK(tile_device_csr(ctx, L.It, trp, n_dofs, n_dofs, n_edge));
+    L.has_I = true;
+  } else {
+    L.I = DevCSR(); L.It = DevCSR();
+  }
+  std::memcpy(&L.cheb_lmax, &lmax_bits, sizeof(double));
+  if (level > 0) {
+    L.n = n_dofs;  // (the SGS plan reads it)
+    const std::vector<int64_t> rp64(rp.begin(), rp.end());
+    CHK(setup_sgs(ctx, L, n_dofs, rp64.data(), col_h.data(), val_h.data(), explicit_rows));
+  }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] level %d matrix assembled on the device: %lld rows nnz %lld, %lld (row, slot) pairs, interface matrix nnz %lld, %.3f ms\n", level,
+                 (long long)n_dofs, (long long)nnz, (long long)n_inc, (long long)n_edge, ms);
+  return finish_level(ctx, level, n_dofs, n_dofs, nnz);
+}
+
+int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
+                              const uint8_t *dof_flags, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: level outside the context");
+  (void)hipSetDevice(ctx->device);
+  Level &L = ctx->lv[(size_t)level];
+  // whatever the level held goes first: after a failure it holds no operator
+  auto clear = [&] {
+    reset_keep_halo(L.A);
+    L.I = DevCSR(); L.It = DevCSR();
+    L.has_I = false;
+    L.invd.reset();
+    L.cheb_lmax = 0.0;
+    L.sgs = SgsPlan();
+  };
+  clear();
+  if (level == 0) drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
+  const int rc = assemble_level_checked(ctx, level, dim, n_dofs, n_cells, cell_dofs, K, dof_flags, build_ms);
+  if (rc != GMG_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    clear();
+  }
+  return rc;
+}
+
+int gmg_get_level_matrix(gmg_context *ctx, int level, int which, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, "gmg_get_level_matrix: level outside the context");
+  if (which != GMG_LEVEL_A && which != GMG_LEVEL_EDGE && which != GMG_LEVEL_EDGE_T) return fail(ctx, GMG_ERR_INVALID, "gmg_get_level_matrix: which must be GMG_LEVEL_A, GMG_LEVEL_EDGE or GMG_LEVEL_EDGE_T");
+  const Level &L = ctx->lv[(size_t)level];
+  if (!L.A.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_level_matrix: level matrix not set");
+  if (which != GMG_LEVEL_A && !L.has_I) {  // no interface matrix on this level
+    if (n_rows) *n_rows = L.A.n_rows;
+    if (n_cols) *n_cols = L.A.n_rows;
+    if (nnz) *nnz = 0;
+    if (rowptr) std::fill(rowptr, rowptr + L.A.n_rows + 1, (int64_t)0);
+    return GMG_OK;
+  }
+  const DevCSR &m = which == GMG_LEVEL_A ? L.A : which == GMG_LEVEL_EDGE ? L.I : L.It;
+  if (!m.rowptr.get() || !m.col.get() || !m.val.get()) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_level_matrix: no CSR copy of this operator on the device");
+  if (n_rows) *n_rows = m.n_rows;
+  if (n_cols) *n_cols = m.n_cols;
+  if (nnz) *nnz = m.nnz;
+  if (!rowptr) return GMG_OK;
+  if (m.nnz && (!col || !val)) return fail(ctx, GMG_ERR_INVALID, "gmg_get_level_matrix: col / val are NULL");
+  (void)hipSetDevice(ctx->device);
+  std::vector<int32_t> rp((size_t)m.n_rows + 1);
+  HIPC(hipMemcpyAsync(rp.data(), m.rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream));
+  if (m.nnz) {
+    HIPC(hipMemcpyAsync(col, m.col.get(), sizeof(int32_t) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(val, m.val.get(), sizeof(double) * (size_t)m.nnz, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < rp.size(); ++i) rowptr[i] = rp[i];
   return GMG_OK;
 }
 

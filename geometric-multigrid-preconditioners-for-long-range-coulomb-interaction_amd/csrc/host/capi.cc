@@ -37,6 +37,7 @@ const CSRMatrix *pick_matrix(step50_problem *h, int kind, int level) {
   // kind 0 system, 1 level, 2 edge, 3 prolongation
   if (kind == 0) { DISPATCH(h, ensure_system_matrix()); return &DISPATCH(h, system_matrix); }  // (it may have been left to the device)
   if (kind == 1) DISPATCH(h, ensure_level_matrix(level));  // (level 0 may have been left to the device: assemble it now)
+  if (kind == 2 && DISPATCH(h, par.level_matrices_on_device)) DISPATCH(h, ensure_level_matrix(level));  // (I_l comes with A_l)
   if (kind == 3) DISPATCH(h, ensure_prolongation(level));   // (the transfers likewise)
   auto &v = kind == 1 ? DISPATCH(h, mg_matrices) : kind == 2 ? DISPATCH(h, mg_interface_matrices) : DISPATCH(h, mg_prolongation);
   if (level < 0 || level >= (int)v.size()) return nullptr;
@@ -338,6 +339,30 @@ int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t
       auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
       put(in.cell_dofs, cell_dofs); put(in.cell_level, cell_level); put(in.K_of_level, K_of_level); put(P.constraint_of_dof, constraint_of_dof);
       put(in.line_ptr, line_ptr); put(in.line_master, line_master); put(in.line_weight, line_weight); put(in.line_inhomogeneity, line_inhomogeneity);
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
+// ---- "Level matrices on device" (DESIGN.md section 17): what the driver hands to gmg_assemble_level_matrix for one level of
+// the current mesh.  sizes: dim, n_dofs, n_cells
+int step50_level_matrices_on_device(step50_problem *h) { return DISPATCH(h, levels_on_device) ? 1 : 0; }
+int step50_level_assembly_sizes(step50_problem *h, int level, int64_t sizes[3]) {
+  return guarded(h, [&] {
+    if (level < 0 || level >= step50_n_levels(h)) throw std::runtime_error("level_assembly_inputs: no such level");
+    sizes[0] = h->dim;
+    sizes[1] = (int64_t)DISPATCH(h, level_vertex_of_dof)[(size_t)level].size();
+    sizes[2] = (int64_t)DISPATCH(h, level_cell_dof_table)[(size_t)level].size() >> h->dim;
+    return 0;
+  });
+}
+int step50_level_assembly_inputs(step50_problem *h, int level, int32_t *cell_dofs, double *K, uint8_t *dof_flags) {
+  return guarded(h, [&] {
+    if (level < 0 || level >= step50_n_levels(h)) throw std::runtime_error("level_assembly_inputs: no such level");
+    auto fill = [&](auto &P) {
+      const auto in = P.level_assembly_inputs(level);
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(P.level_cell_dof_table[(size_t)level], cell_dofs); put(in.K, K); put(in.dof_flags, dof_flags);
     };
     if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
     return 0;

@@ -232,6 +232,10 @@ void ParameterReader::declare_parameters() {
             // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; constant-coefficient
             // problems on one rank, DESIGN.md section 12
             {"System matrix on device", "false"},
+            // the level matrices A_l and the interface matrices I_l formed on the device from the levels' cell tables, one
+            // cell matrix and the boundary / refinement-edge flags (gmg_assemble_level_matrix) instead of assembled here and
+            // uploaded as CSR; constant-coefficient problems on one rank, DESIGN.md section 17
+            {"Level matrices on device", "false"},
             // what stands behind mg_coarse: the reference's unpreconditioned CG (:962-967), or fast diagonalisation on the
             // level-0 lattice (gmg_set_coarse_solver; where level 0 does not qualify the CG stays), DESIGN.md section 15
             {"Coarse solver", "CG"},
@@ -324,6 +328,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
     throw std::runtime_error("Refinement estimator must be <Kelly + residual> or <Kelly>");
   p.level0_matrix_on_device = prm.get_bool("Level 0 matrix on device");
   p.system_matrix_on_device = prm.get_bool("System matrix on device");
+  p.level_matrices_on_device = prm.get_bool("Level matrices on device");
   p.coarse_solver = prm.get("Coarse solver");
   if (p.coarse_solver != "CG" && p.coarse_solver != "direct") throw std::runtime_error("Coarse solver must be <CG> or <direct>");
   p.estimator_on_device = prm.get_bool("Error estimator on device");
@@ -1190,10 +1195,47 @@ void LaplaceProblem<dim>::assemble_multigrid() {
   mg_matrices.assign((size_t)L, {});
   mg_interface_matrices.assign((size_t)L, {});
   level0_on_device = decide_level0_on_device();
+  levels_on_device = decide_levels_on_device();
   for (int l = 0; l < L; ++l) {
     if (l == 0 && level0_on_device) continue;  // formed on the device at upload; assembled here only when somebody asks for it
+    if (levels_on_device) continue;            // likewise, by gmg_assemble_level_matrix
     assemble_level(l);
   }
+}
+
+// Are the level matrices the kind of operator gmg_assemble_level_matrix forms?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_levels_on_device() {
+  if (!par.level_matrices_on_device) return false;
+  const char *why = !solve_on_device_requested ? "the cycle does not run on the device"
+                    : distributed              ? "the run is distributed"
+                    : par.Problemtype == "Step16" ? "the coefficient varies"
+                                                  : nullptr;
+  if (!why) return true;
+  if (!levels_fallback_reported) pcout(std::string("   Level matrices on device: not applicable (") + why + "), assembled on the host");
+  levels_fallback_reported = true;
+  return false;
+}
+
+// the arrays of gmg_assemble_level_matrix besides the cell table: the cell matrix exactly as assemble_level scales it (the
+// device's matrices have the host's bits only as long as both scale it the same way) and the two flags of every DoF
+template <int dim>
+typename LaplaceProblem<dim>::LevelAssemblyInputs LaplaceProblem<dim>::level_assembly_inputs(int l) const {
+  constexpr int nv = 1 << dim;
+  LevelAssemblyInputs in;
+  const Quadrature<dim> q_laplace((int)par.degree + 1);
+  double Kc[nv][nv];
+  double x0[3] = {0, 0, 0};
+  cell_matrix<dim>(q_laplace, 1.0, x0, [&](const double *) { return 1.0; }, true, Kc);
+  const double s = std::pow(triangulation.cell_size(l), dim - 2);
+  in.K.resize((size_t)nv * nv);
+  for (int i = 0; i < nv; ++i)
+    for (int j = 0; j < nv; ++j) in.K[(size_t)i * nv + (size_t)j] = Kc[i][j] * s;
+  const auto &bnd = level_boundary[(size_t)l];
+  const auto &edge = level_refinement_edge[(size_t)l];
+  in.dof_flags.resize(bnd.size());
+  for (size_t d = 0; d < bnd.size(); ++d) in.dof_flags[d] = (uint8_t)((bnd[d] ? 1 : 0) | (edge[d] ? 2 : 0));
+  return in;
 }
 
 // Is level 0 the kind of operator gmg_set_level_matrix_lattice forms (and is it going to stay whole on this rank)?
@@ -1441,18 +1483,42 @@ int LaplaceProblem<dim>::upload() {
     GMGC(gmg_set_system_matrix(gmg, S.n_rows, S.n_cols, S.rowptr.data(), S.col.data(), S.val.data()));
     d_begin = 0; d_n = d_nvec = S.n_rows;
   }
+  double levels_build_ms = 0.0, levels_wall_s = 0.0;  // (STEP50_TIMING=2: the device-formed levels, inputs included)
   for (int l = 0; l < L; ++l) {
-    if (l == 0 && level0_on_device && !(distributed && level0_partitioned)) {
+    const bool lattice0 = l == 0 && level0_on_device && !(distributed && level0_partitioned);
+    bool level_formed = false;  // A_l and I_l by gmg_assemble_level_matrix
+    if (lattice0) {
       // the lattice operator is formed on the device from its size and the cell matrix
       double Ke[64];
       level0_cell_matrix(Ke);
       const int32_t nvv[3] = {triangulation.n0 + 1, triangulation.n0 + 1, triangulation.n0 + 1};
       GMGC(gmg_set_level_matrix_lattice(gmg, 0, nvv, Ke));
+    } else if (levels_on_device) {
+      // the level's operators are formed on the device from its cell table and the DoF flags
+      const auto t_level = std::chrono::steady_clock::now();
+      const LevelAssemblyInputs in = level_assembly_inputs(l);
+      double build_ms = 0.0;
+      const int rc_asm = gmg_assemble_level_matrix(gmg, l, dim, (int64_t)level_vertex_of_dof[(size_t)l].size(), (int64_t)triangulation.levels[(size_t)l].size(),
+                                                   level_cell_dof_table[(size_t)l].data(), in.K.data(), in.dof_flags.data(), &build_ms);
+      if (rc_asm == GMG_ERR_UNSUPPORTED) {
+        // a level the device assembly does not take (a row wider than its limit, sizes beyond 32-bit indices): the host path
+        if (!levels_fallback_reported) pcout(std::string("   Level matrices on device: not applicable (") + gmg_last_error(gmg) + "), assembled on the host");
+        levels_fallback_reported = true;
+        levels_on_device = false;
+        ensure_level_matrix(l);
+      } else if (rc_asm != GMG_OK) {
+        last_error = std::string("gmg_assemble_level_matrix: ") + gmg_last_error(gmg);
+        return rc_asm;
+      } else {
+        level_formed = true;
+        levels_build_ms += build_ms;
+        levels_wall_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_level).count();
+      }
     } else {
       ensure_level_matrix(l);
     }
     const CSRMatrix &A = mg_matrices[(size_t)l];
-    if (l == 0 && level0_on_device && !(distributed && level0_partitioned)) {
+    if (lattice0 || level_formed) {
     } else if (distributed && level0_partitioned && l == 0) {
       const LocalOperator Al = localize(A, rank, n_ranks);
       GMGC(gmg_set_level_matrix(gmg, 0, Al.A.n_rows, Al.A.n_cols, Al.A.rowptr.data(), Al.A.col.data(), Al.A.val.data()));
@@ -1462,7 +1528,7 @@ int LaplaceProblem<dim>::upload() {
       GMGC(gmg_set_level_matrix(gmg, l, A.n_rows, A.n_cols, A.rowptr.data(), A.col.data(), A.val.data()));
     }
     const CSRMatrix &I = mg_interface_matrices[(size_t)l];
-    if (I.nnz() > 0) GMGC(gmg_set_edge_matrix(gmg, l, I.n_rows, I.n_cols, I.rowptr.data(), I.col.data(), I.val.data()));
+    if (!level_formed && I.nnz() > 0) GMGC(gmg_set_edge_matrix(gmg, l, I.n_rows, I.n_cols, I.rowptr.data(), I.col.data(), I.val.data()));
     GMGC(gmg_set_copy_indices(gmg, l, (int64_t)copy_global[(size_t)l].size(), copy_global[(size_t)l].data(), copy_level[(size_t)l].data()));
     if (l + 1 < L && transfer_on_device) {
       // P_l and its transpose are formed on the device from the vertex tables of the two levels
@@ -1476,6 +1542,10 @@ int LaplaceProblem<dim>::upload() {
       const CSRMatrix &P = mg_prolongation[(size_t)l];
       GMGC(gmg_set_prolongation(gmg, l, P.n_rows, P.n_cols, P.rowptr.data(), P.col.data(), P.val.data()));
     }
+  }
+  if (levels_on_device && sublap_on()) {
+    std::fprintf(stderr, "[step50]     . %-32s %8.3f s\n", "level matrices on device", levels_wall_s);
+    std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", levels_build_ms);
   }
   const int kind = par.smoother == "Jacobi" ? GMG_SMOOTHER_JACOBI : par.smoother == "Chebyshev" ? GMG_SMOOTHER_CHEBYSHEV : GMG_SMOOTHER_SSOR;
   GMGC(gmg_set_smoother(gmg, kind, par.smoother_omega, par.smoother_steps, par.chebyshev_degree, 0.0, 0.0));

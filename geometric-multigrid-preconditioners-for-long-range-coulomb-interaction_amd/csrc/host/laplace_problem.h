@@ -79,6 +79,7 @@ struct Parameters {
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (constant coefficient, one rank)
+  bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (constant coefficient, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
@@ -136,6 +137,13 @@ class LaplaceProblem {
   void assemble_multigrid();                                             // :835-933
   void assemble_level(int l);                                            // one level's matrix + interface matrix (:869-931)
   void ensure_level_matrix(int l);                                       // assemble a level that was left to the device, on demand
+  bool decide_levels_on_device();                                        // level + interface matrices formed on the device (gmg_assemble_level_matrix)?
+  // what gmg_assemble_level_matrix takes for one level: the cell table is level_cell_dof_table[l]
+  struct LevelAssemblyInputs {
+    std::vector<double> K;           // [nv][nv]: the cell matrix as assemble_level scales it
+    std::vector<uint8_t> dof_flags;  // bit 0 level_boundary, bit 1 level_refinement_edge
+  };
+  LevelAssemblyInputs level_assembly_inputs(int l) const;
   bool decide_level0_on_device() const;                                  // level 0 formed on the device (gmg_set_level_matrix_lattice)?
   void level0_cell_matrix(double *Ke) const;
   void build_transfer();                                                 // mg_transfer.build_matrices, :957-958
@@ -203,6 +211,8 @@ class LaplaceProblem {
   bool operators_uploaded = false, densities_on_device = false;
   bool solve_on_device_requested = false, level0_on_device = false, transfer_on_device = false;
   bool system_on_device = false;           // this cycle's system matrix is formed by gmg_assemble_system_matrix at upload()
+  bool levels_on_device = false;           // this cycle's level and interface matrices are formed by gmg_assemble_level_matrix at upload()
+  bool levels_fallback_reported = false;   // "Level matrices on device" was set but not applicable: said once
   bool system_fallback_reported = false;   // "System matrix on device" was set but not applicable: said once
   bool coarse_fallback_reported = false;   // "Coarse solver = direct" was set but not applicable: said once
   bool densities_device_resident = false;  // compute_charge_densities left them in HBM for gmg_rhs_assemble

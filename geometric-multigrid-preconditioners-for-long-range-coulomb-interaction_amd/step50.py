@@ -85,6 +85,7 @@ def prm_text(**kw) -> str:
         "level0_numbering": ("Misc", "Level 0 numbering"),
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
         "system_matrix_on_device": ("Misc", "System matrix on device"),
+        "level_matrices_on_device": ("Misc", "Level matrices on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
@@ -329,6 +330,30 @@ class Problem:
     def system_matrix_on_device(self) -> bool:
         """Did the last upload form the system matrix on the device?"""
         return bool(self.L.step50_system_matrix_on_device(self.h))
+
+    def level_assembly_inputs(self, level):
+        """The arrays the driver hands to gmg_assemble_level_matrix for one level of the current mesh: namespace(dim, n_dofs,
+        cell_dofs [n_cells, 2^dim], K [2^dim, 2^dim], dof_flags [n_dofs]: bit 0 boundary, bit 1 refinement edge)."""
+        sz = (C.c_int64 * 3)()
+        self._chk(self.L.step50_level_assembly_sizes(self.h, C.c_int(level), sz), "level_assembly_inputs")
+        dim, n_dofs, n_cells = (int(v) for v in sz)
+        nv = 1 << dim
+        cd, K, fl = np.zeros((n_cells, nv), dtype=np.int32), np.zeros((nv, nv)), np.zeros(n_dofs, dtype=np.uint8)
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        self._chk(self.L.step50_level_assembly_inputs(self.h, C.c_int(level), P(cd, C.c_int32), P(K, C.c_double), P(fl, C.c_uint8)),
+                  "level_assembly_inputs")
+        return SimpleNamespace(dim=dim, n_dofs=n_dofs, cell_dofs=cd, K=K, dof_flags=fl)
+
+    def device_level_matrix(self, level, which="level"):
+        """A level's operator as the device holds it (gmg_get_level_matrix): which = 'level' (A_l) | 'edge' (I_l, without
+        its zeros) | 'edge_t' (I_l^T)."""
+        from . import capi
+        w = {"level": capi.LEVEL_A, "edge": capi.LEVEL_EDGE, "edge_t": capi.LEVEL_EDGE_T}[which]
+        return capi.Context.view(self.gmg_context()).get_level_matrix(level, w)
+
+    def level_matrices_on_device(self) -> bool:
+        """Did the last upload form the level and interface matrices on the device?"""
+        return bool(self.L.step50_level_matrices_on_device(self.h))
 
     def refine_flags(self):
         """The refinement marks of the cycle just estimated, all levels concatenated (uint8)."""

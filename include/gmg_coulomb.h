@@ -361,6 +361,40 @@ int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64
  * two-stage partial reduction (not bit-equal: relative error at most (nnz + 2) 2^-53).                                 */
 int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *frobenius);
 
+/* A multigrid level matrix A_l and its interface ("edge") matrix I_l formed on the device instead of host-assembled CSRs
+ * (gmg_set_level_matrix + gmg_set_edge_matrix): LaplaceProblem::assemble_level for a constant-coefficient problem, from
+ * the level's cell table cell_dofs [n_cells * 2^dim] (vertex a = bx + 2 by + 4 bz), ONE cell matrix K [2^dim][2^dim]
+ * (row-major, as the host scales it for the level) and dof_flags [n_dofs]: bit 0 = on the boundary, bit 1 = on the
+ * refinement edge.  Afterwards the level is in the state gmg_set_level_matrix followed by gmg_set_edge_matrix leaves it in
+ * with the host's matrices: operator, Jacobi diagonal, Chebyshev bound, SSOR plan (gmg_set_ssor_blocks /
+ * gmg_set_ssor_block_rows / gmg_set_ssor_partition are honoured; the plan is built on the host from one download of the
+ * CSR), work vectors, on level 0 the coarse CG's vectors and the coarse CG selected, I_l and I_l^T (or none).  A_l is kept as
+ * CSR and applied by the row-window kernel.
+ * A_l pattern: row r stores the sorted union of the DoFs of all cells that contain r; stored zeros are kept.
+ * A_l values: every entry starts at +0.0; cells ascending, then i ascending: if dof_flags[dofs[i]] != 0, (dofs[i], dofs[i])
+ * += |K[i][i]| and nothing else from this i; otherwise, for j ascending with dof_flags[dofs[j]] == 0, (dofs[i], dofs[j]) +=
+ * K[i][j].  Jacobi diagonal 1 / a_rr; Chebyshev bound max_r (sum_k |a_rk| in stored order) / |a_rr|.
+ * I_l: the pairs (dofs[i], dofs[j]) of any cell with dof_flags[dofs[i]] == 2 and dof_flags[dofs[j]] == 0, each the sum of its
+ * cells' K[i][j] in ascending cell order starting from the first contribution; sums == 0.0 are dropped (as
+ * gmg_set_edge_matrix drops them); I_l^T lists every column's entries in ascending row.  A level without a surviving entry
+ * has no interface matrix.  fp64, no contraction into fused multiply-adds, no floating-point atomics: the same bits as the
+ * host's matrices for any launch shape (option assemble_max_blocks).  build_ms (may be NULL): device time of the build.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a level outside the
+ * context, a DoF outside [0, n_dofs), flag bits above 1, a NULL array of nonzero length, a negative size, or SSOR block
+ * boundaries of this level that do not end at n_dofs.  GMG_ERR_UNSUPPORTED on a context with a communicator (a
+ * row-partitioned level 0 included), for a row with more than 512 columns and for sizes beyond 32-bit device indices.
+ * After any failure the level holds no operator.  Zero cells are valid: n_dofs empty rows.                              */
+int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                              const double *K, const uint8_t *dof_flags, double *build_ms);
+/* The CSR of a level's operators as the device holds them: which = GMG_LEVEL_A, GMG_LEVEL_EDGE (I_l) or GMG_LEVEL_EDGE_T
+ * (I_l^T).  With rowptr == NULL only the sizes are returned.  GMG_ERR_UNSUPPORTED where the device keeps no CSR copy (a
+ * lattice level 0, an operator stored in a SELL layout); an absent interface matrix returns nnz = 0.                       */
+#define GMG_LEVEL_A 0
+#define GMG_LEVEL_EDGE 1
+#define GMG_LEVEL_EDGE_T 2
+int gmg_get_level_matrix(gmg_context *ctx, int level, int which, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *rowptr,
+                         int32_t *col, double *val);
+
 /* The error estimator and the refinement marks of an adaptive cycle (src/step-50.cc:1020-1089: KellyErrorEstimator with the
  * cell diameter as scaling, the cell residual, cells at or above a fraction of the largest indicator are marked) formed on
  * the device from the cells' DoFs cell_dofs [n_cells * 2^dim] (vertex a = bx + 2 by + 4 bz), their levels cell_level
