@@ -26,7 +26,7 @@ SYMBOLS = [
     "gmg_create", "gmg_destroy", "gmg_reset", "gmg_last_error", "gmg_synchronize",
     "gmg_set_system_matrix", "gmg_set_level_matrix", "gmg_set_level_matrix_lattice", "gmg_set_edge_matrix", "gmg_set_prolongation", "gmg_build_transfer", "gmg_get_transfer",
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
-    "gmg_assemble_level_matrix", "gmg_get_level_matrix",
+    "gmg_assemble_level_matrix", "gmg_get_level_matrix", "gmg_assemble_system_matrix_coef", "gmg_assemble_level_matrix_coef",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -441,6 +441,41 @@ class Context:
         self.n_system = int(n_dofs)
         return ms.value
 
+    def assemble_system_matrix_coef(self, dim, n_dofs, cell_dofs, cell_level, nq, cell_coef, G, qw, scale_of_level, constraint_of_dof, line_ptr,
+                                    line_master, line_weight, validate=True):
+        """The active-mesh system matrix of a variable coefficient formed on the device (gmg_assemble_system_matrix_coef);
+        returns the device time in ms.  As assemble_system_matrix with, instead of K_of_level, nq, cell_coef [n_cells, nq], G
+        [nq, 2^dim, 2^dim], qw [nq] and scale_of_level [16].  validate=True checks the shapes here (ValueError) before the
+        library sees them; the library checks the contents."""
+        nv = 1 << int(dim) if dim in (2, 3) else 0
+        cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        lv = np.ascontiguousarray(cell_level, dtype=np.uint8)
+        cc, g, w, sc = (np.ascontiguousarray([] if a is None else a, dtype=np.float64) for a in (cell_coef, G, qw, scale_of_level))
+        cons = np.ascontiguousarray(constraint_of_dof, dtype=np.int32)
+        lp = np.ascontiguousarray([] if line_ptr is None else line_ptr, dtype=np.int64)
+        lm = np.ascontiguousarray([] if line_master is None else line_master, dtype=np.int32)
+        lw = np.ascontiguousarray([] if line_weight is None else line_weight, dtype=np.float64)
+        n_cells, n_lines = len(lv), max(len(lp) - 1, 0)
+        if validate:
+            if nv == 0:
+                raise ValueError("assemble_system_matrix_coef: dim must be 2 or 3")
+            if n_dofs < 0 or cons.size != n_dofs:
+                raise ValueError("assemble_system_matrix_coef: constraint_of_dof must have n_dofs entries")
+            if cd.size != n_cells * nv:
+                raise ValueError("assemble_system_matrix_coef: cell_dofs must be [n_cells, 2^dim]")
+            if not 1 <= nq <= 64 or cc.size != n_cells * nq or g.size != nq * nv * nv or w.size != nq or sc.size != 16:
+                raise ValueError("assemble_system_matrix_coef: nq in 1 .. 64, cell_coef [n_cells, nq], G [nq, 2^dim, 2^dim], qw [nq], scale_of_level [16]")
+            if len(lm) != len(lw) or (n_lines and len(lm) < lp[-1]) or (not n_lines and len(lm)):
+                raise ValueError("assemble_system_matrix_coef: line_master / line_weight do not match line_ptr")
+        opt = lambda a, t: _p(a, t) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_system_matrix_coef(self.h, C.c_int(int(dim)), C.c_int64(int(n_dofs)), C.c_int64(n_cells), opt(cd, C.c_int32),
+                                                         opt(lv, C.c_uint8), C.c_int(int(nq)), opt(cc, C.c_double), opt(g, C.c_double),
+                                                         opt(w, C.c_double), opt(sc, C.c_double), opt(cons, C.c_int32), C.c_int64(n_lines),
+                                                         opt(lp, C.c_int64), opt(lm, C.c_int32), opt(lw, C.c_double), C.byref(ms)))
+        self.n_system = int(n_dofs)
+        return ms.value
+
     def get_system_matrix(self):
         """The CSR of the system matrix as the device holds it (after assemble_system_matrix)."""
         from types import SimpleNamespace
@@ -479,6 +514,32 @@ class Context:
         ms = C.c_double(0)
         self._chk(self.L.gmg_assemble_level_matrix(self.h, C.c_int(int(level)), C.c_int(int(dim)), C.c_int64(int(n_dofs)), C.c_int64(n_cells),
                                                    opt(cd, C.c_int32), opt(k, C.c_double), opt(fl, C.c_uint8), C.byref(ms)))
+        return ms.value
+
+    def assemble_level_matrix_coef(self, level, dim, n_dofs, cell_dofs, nq, cell_coef, G, qw, scale, dof_flags, validate=True):
+        """A level matrix and its interface matrix of a variable coefficient formed on the device
+        (gmg_assemble_level_matrix_coef); returns the device time in ms.  As assemble_level_matrix with, instead of K, nq,
+        cell_coef [n_cells, nq], G [nq, 2^dim, 2^dim], qw [nq] and one scale.  validate=True checks the shapes here (ValueError)
+        before the library sees them; the library checks the contents."""
+        nv = 1 << int(dim) if dim in (2, 3) else 0
+        cd = np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        cc, g, w = (np.ascontiguousarray([] if a is None else a, dtype=np.float64) for a in (cell_coef, G, qw))
+        fl = np.ascontiguousarray(dof_flags, dtype=np.uint8)
+        n_cells = cd.size // nv if nv else len(cd)
+        if validate:
+            if nv == 0:
+                raise ValueError("assemble_level_matrix_coef: dim must be 2 or 3")
+            if cd.size % nv or (cd.ndim == 2 and cd.shape[1] != nv):
+                raise ValueError("assemble_level_matrix_coef: cell_dofs must be [n_cells, 2^dim]")
+            if not 1 <= nq <= 64 or cc.size != n_cells * nq or g.size != nq * nv * nv or w.size != nq:
+                raise ValueError("assemble_level_matrix_coef: nq in 1 .. 64, cell_coef [n_cells, nq], G [nq, 2^dim, 2^dim], qw [nq]")
+            if n_dofs < 0 or fl.size != n_dofs:
+                raise ValueError("assemble_level_matrix_coef: dof_flags must have n_dofs entries")
+        opt = lambda a, t: _p(a, t) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_level_matrix_coef(self.h, C.c_int(int(level)), C.c_int(int(dim)), C.c_int64(int(n_dofs)), C.c_int64(n_cells),
+                                                        opt(cd, C.c_int32), C.c_int(int(nq)), opt(cc, C.c_double), opt(g, C.c_double),
+                                                        opt(w, C.c_double), C.c_double(float(scale)), opt(fl, C.c_uint8), C.byref(ms)))
         return ms.value
 
     def get_level_matrix(self, level, which=LEVEL_A):

@@ -58,6 +58,15 @@
 // I_l^T.  Row j lists the entries (r, j) of I_l in ascending r: the rows that may hold column j are the columns of row j of A_l
 // (structural symmetry), and j is found in each of those rows of I_l by bisection (asm_edge_transpose_kernel, count and
 // fill) -- what the stable host transpose of gmg_set_edge_matrix gives, without atomics.
+//
+// ---- The coefficient form of both assemblies (gmg_assemble_system_matrix_coef, gmg_assemble_level_matrix_coef, DESIGN.md
+// section 18): a coefficient that varies in space.  Inputs instead of K: nq (1 .. kAsmMaxNq), cell_coef [n_cells][nq] (the
+// coefficient at the quadrature points of every cell), G [nq][nv][nv] (the reference-cell products sum_d d_d phi_i d_d phi_j
+// at each point; the caller forms them), qw [nq], and scale [16] by cell level (system matrix) or one scale (a level).  The
+// cell matrix of cell c is
+//   K_c[i][j] = +0.0;   for q ascending:   K_c[i][j] += ((cell_coef[c][q] * G[q][i][j]) * qw[q]) * scale
+// (fp64, no contraction), and everything above holds word for word with K_c in place of K[level] / K.  No K_c is stored: a
+// lane forms the entry it needs where it consumes it (asm_cell_k), selected by the template flag COEF of the FILL pass.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +74,7 @@
 
 namespace gmg {
 
+constexpr int kAsmMaxNq = 64;    // quadrature points per cell the coefficient form takes
 constexpr int kAsmMaxRow = 512;  // distinct columns of a row the wavefront's LDS set holds (+ one batch of 64 candidates)
 
 struct AsmArgs {
@@ -79,6 +89,12 @@ struct AsmArgs {
   const int32_t *line_master;
   const double *line_weight;
   const uint8_t *flags;       // LEVEL form: [n_dofs], bit 0 boundary, bit 1 refinement edge (cell_level, cons and the lines are unused, K is one matrix)
+  // COEF form (K is unused): the cell matrices are formed from coefficient values where they are consumed (asm_cell_k)
+  int nq;                     // quadrature points per cell (1 .. kAsmMaxNq)
+  const double *cell_coef;    // [n_cells * nq]
+  const double *G;            // [nq * nv * nv]
+  const double *qw;           // [nq]
+  const double *scale;        // [16] by cell level; LEVEL form: [1]
   int32_t *inc_ptr;   // [n_dofs + 1]: slots of every row (counts before the scan)
   int32_t *inc_pos;   // [n_dofs]: fill cursors
   int32_t *inc_slot;  // [inc_ptr[n_dofs]]
@@ -130,24 +146,52 @@ __global__ __launch_bounds__(256) void asm_sort_incidence_kernel(AsmArgs a) {
   }
 }
 
+// COEF form: entry (i, j) of the cell matrix of `cell`, one sequential sum over the quadrature points in ascending order.  qw
+// and the scale of a level are uniform over the wavefront; G and the cell's coefficients come through the cache.
+template <bool LEVEL>
+__device__ __forceinline__ double asm_cell_k(const AsmArgs &a, int32_t cell, int i, int j) {
+  const int nv = a.nv;
+  const double *cc = a.cell_coef + (int64_t)cell * a.nq;
+  const double *g = a.G + i * nv + j;
+  double s;
+  if constexpr (LEVEL) s = a.scale[0];
+  else s = a.scale[a.cell_level[cell]];
+  double k = 0.0;
+  for (int q = 0; q < a.nq; ++q) k += ((cc[q] * g[q * nv * nv]) * a.qw[q]) * s;
+  return k;
+}
+
 // what the host loop adds to (r, c) for slot (cell, i), in its order of j, ri, rj
+template <bool COEF>
 __device__ __forceinline__ void asm_add_slot(const AsmArgs &a, int32_t slot, int32_t r, int32_t c, double &acc) {
   const int nv = a.nv;
   const int32_t cell = slot >> a.lg_nv;
   const int i = slot & (nv - 1);
   const int32_t *cd = a.cell_dofs + (int64_t)cell * nv;
-  const double *K = a.K + (int)a.cell_level[cell] * nv * nv;
+  const double *K = COEF ? nullptr : a.K + (int)a.cell_level[cell] * nv * nv;
   const int32_t di = cd[i], li = a.cons[di];
   int32_t i0 = 0, i1 = 0;
   if (li >= 0) {
     i0 = a.line_ptr[li]; i1 = a.line_ptr[li + 1];
-    if (di == r && c == r) acc += fabs(K[i * nv + i]);
+    if (di == r && c == r) {
+      if constexpr (COEF) acc += fabs(asm_cell_k<false>(a, cell, i, i));
+      else acc += fabs(K[i * nv + i]);
+    }
   }
   for (int j = 0; j < nv; ++j) {
     const int32_t dj = cd[j], lj = a.cons[dj];
-    const double kij = K[i * nv + j];
+    // (COEF: K_c[i][j] is formed once, by the first term of this j that needs it)
+    double kij = 0.0;
+    bool have = !COEF;
+    if constexpr (!COEF) kij = K[i * nv + j];
+    auto k = [&]() {
+      if constexpr (COEF) {
+        if (!have) { kij = asm_cell_k<false>(a, cell, i, j); have = true; }
+      }
+      return kij;
+    };
     if (li < 0 && lj < 0) {
-      if (di == r && dj == c) acc += kij;
+      if (di == r && dj == c) acc += k();
       continue;
     }
     if (li >= 0 && i0 == i1) continue;
@@ -160,41 +204,53 @@ __device__ __forceinline__ void asm_add_slot(const AsmArgs &a, int32_t slot, int
       for (int32_t ei = i0; ei < i1; ++ei) {
         if (a.line_master[ei] != r) continue;
         for (int32_t ej = j0; ej < j1; ++ej)
-          if (a.line_master[ej] == c) acc += (a.line_weight[ei] * a.line_weight[ej]) * kij;
+          if (a.line_master[ej] == c) acc += (a.line_weight[ei] * a.line_weight[ej]) * k();
       }
     } else if (li >= 0) {
       if (dj != c) continue;
       for (int32_t ei = i0; ei < i1; ++ei)
-        if (a.line_master[ei] == r) acc += a.line_weight[ei] * kij;
+        if (a.line_master[ei] == r) acc += a.line_weight[ei] * k();
     } else {
       if (di != r) continue;
       for (int32_t ej = j0; ej < j1; ++ej)
-        if (a.line_master[ej] == c) acc += a.line_weight[ej] * kij;
+        if (a.line_master[ej] == c) acc += a.line_weight[ej] * k();
     }
   }
 }
 
 // LEVEL form: what assemble_level adds to (r, c) of A_l for slot (cell, i) -- dofs[i] == r -- in its order of j
+template <bool COEF>
 __device__ __forceinline__ void asm_add_level_slot(const AsmArgs &a, int32_t slot, int32_t r, int32_t c, double &acc) {
   const int nv = a.nv;
   const int i = slot & (nv - 1);
-  const int32_t *cd = a.cell_dofs + (int64_t)(slot >> a.lg_nv) * nv;
+  const int32_t cell = slot >> a.lg_nv;
+  const int32_t *cd = a.cell_dofs + (int64_t)cell * nv;
   if (a.flags[r] != 0) {
-    if (c == r) acc += fabs(a.K[i * nv + i]);
+    if (c == r) {
+      if constexpr (COEF) acc += fabs(asm_cell_k<true>(a, cell, i, i));
+      else acc += fabs(a.K[i * nv + i]);
+    }
     return;
   }
   for (int j = 0; j < nv; ++j)
-    if (cd[j] == c && a.flags[c] == 0) acc += a.K[i * nv + j];
+    if (cd[j] == c && a.flags[c] == 0) {
+      if constexpr (COEF) acc += asm_cell_k<true>(a, cell, i, j);
+      else acc += a.K[i * nv + j];
+    }
 }
 
 // LEVEL form: what slot (cell, i) contributes to (r, c) of I_l (flag 2 on r, flag 0 on c): the sum starts from its first term
+template <bool COEF>
 __device__ __forceinline__ void asm_add_edge_slot(const AsmArgs &a, int32_t slot, int32_t c, double &acc, bool &any) {
   const int nv = a.nv;
   const int i = slot & (nv - 1);
-  const int32_t *cd = a.cell_dofs + (int64_t)(slot >> a.lg_nv) * nv;
+  const int32_t cell = slot >> a.lg_nv;
+  const int32_t *cd = a.cell_dofs + (int64_t)cell * nv;
   for (int j = 0; j < nv; ++j)
     if (cd[j] == c) {
-      const double v = a.K[i * nv + j];
+      double v;
+      if constexpr (COEF) v = asm_cell_k<true>(a, cell, i, j);
+      else v = a.K[i * nv + j];
       acc = any ? acc + v : v;
       any = true;
     }
@@ -203,8 +259,10 @@ __device__ __forceinline__ void asm_add_edge_slot(const AsmArgs &a, int32_t slot
 // One wavefront per row (workgroups of 64).  FILL = false: rowptr[r] = number of distinct columns.  FILL = true (rowptr
 // scanned): the columns in ascending order, the values, the Jacobi diagonal.  LEVEL: a cell's coupling list is its DoFs, the
 // values are assemble_level's, and the rows with flag 2 also form their interface-matrix sums (edge_val) and count them.
-template <bool FILL, bool LEVEL = false>
+// COEF (FILL pass only; the pattern needs no values): the cell matrices come from asm_cell_k instead of the table K.
+template <bool FILL, bool LEVEL = false, bool COEF = false>
 __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
+  static_assert(FILL || !COEF, "the pattern pass reads no cell matrix");
   __shared__ int32_t set[kAsmMaxRow + 64];
   __shared__ int32_t sorted[FILL ? kAsmMaxRow : 1];
   const int lane = threadIdx.x;
@@ -270,8 +328,8 @@ __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
         const int32_t c = sorted[k];
         double acc = 0.0;
         for (int32_t q = q0; q < q1; ++q) {
-          if constexpr (LEVEL) asm_add_level_slot(a, a.inc_slot[q], (int32_t)r, c, acc);
-          else asm_add_slot(a, a.inc_slot[q], (int32_t)r, c, acc);
+          if constexpr (LEVEL) asm_add_level_slot<COEF>(a, a.inc_slot[q], (int32_t)r, c, acc);
+          else asm_add_slot<COEF>(a, a.inc_slot[q], (int32_t)r, c, acc);
         }
         a.val[k0 + k] = acc;
         if (c == (int32_t)r) { a.invd[r] = 1.0 / acc; has_diag = true; }
@@ -279,7 +337,7 @@ __global__ __launch_bounds__(64) void asm_row_kernel(AsmArgs a) {
           double e = 0.0;
           if (a.flags[c] == 0) {
             bool any = false;
-            for (int32_t q = q0; q < q1; ++q) asm_add_edge_slot(a, a.inc_slot[q], c, e, any);
+            for (int32_t q = q0; q < q1; ++q) asm_add_edge_slot<COEF>(a, a.inc_slot[q], c, e, any);
           }
           a.edge_val[k0 + k] = e;
           n_edge += e != 0.0 ? 1 : 0;

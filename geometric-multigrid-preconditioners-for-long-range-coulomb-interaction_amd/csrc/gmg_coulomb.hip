@@ -2680,7 +2680,36 @@ int assemble_rows(gmg_context *ctx, const char *who, AsmArgs &a, AsmScratch &w, 
   HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
   a.col = m.col.get(); a.val = m.val.get();
   CHK(before_fill(nnz));
-  if (n_dofs) hipLaunchKernelGGL((asm_row_kernel<true, LEVEL>), g_rows, dim3(64), 0, ctx->stream, a);
+  if (n_dofs && a.nq > 0) hipLaunchKernelGGL((asm_row_kernel<true, LEVEL, true>), g_rows, dim3(64), 0, ctx->stream, a);
+  else if (n_dofs) hipLaunchKernelGGL((asm_row_kernel<true, LEVEL>), g_rows, dim3(64), 0, ctx->stream, a);
+  return GMG_OK;
+}
+
+// The coefficient form of the two assemblies (gmg_assemble_*_matrix_coef): values at the quadrature points of every cell, the
+// reference-cell products G, the weights and the scale(s) instead of cell matrices.
+struct AsmCoef {
+  int nq;
+  const double *cell_coef, *G, *qw, *scale;
+  int n_scale;  // 16 by cell level, or 1
+};
+struct AsmCoefDev {  // the uploaded tables; lives until the stream has run the kernels
+  DevPtr<double> cc, G, qw, scale;
+};
+
+// the argument checks of the coefficient form, on the host before any launch (0: fine)
+int check_coef(gmg_context *ctx, const char *who, const AsmCoef &k, int64_t n_cells) {
+  const std::string w(who);
+  if (k.nq < 1 || k.nq > kAsmMaxNq) return fail(ctx, GMG_ERR_INVALID, (w + ": nq must be in 1 .. 64").c_str());
+  if ((n_cells > 0 && !k.cell_coef) || !k.G || !k.qw || !k.scale) return fail(ctx, GMG_ERR_INVALID, (w + ": cell_coef, G, qw or the scale is NULL").c_str());
+  return GMG_OK;
+}
+
+int upload_coef(gmg_context *ctx, const AsmCoef &k, int64_t n_cells, int nv, AsmCoefDev &d, AsmArgs &a) {
+  HIPC(upload(d.cc, k.cell_coef, (size_t)n_cells * (size_t)k.nq, ctx->stream));
+  HIPC(upload(d.G, k.G, (size_t)k.nq * nv * nv, ctx->stream));
+  HIPC(upload(d.qw, k.qw, (size_t)k.nq, ctx->stream));
+  HIPC(upload(d.scale, k.scale, (size_t)k.n_scale, ctx->stream));
+  a.nq = k.nq; a.cell_coef = d.cc.get(); a.G = d.G.get(); a.qw = d.qw.get(); a.scale = d.scale.get();
   return GMG_OK;
 }
 
@@ -3809,45 +3838,52 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
 
 // ---- the active-mesh system matrix formed on the device (gmg_assemble.hpp) ----
 
-int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
-                               const double *K_of_level, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
-                               const int32_t *line_master, const double *line_weight, double *build_ms) {
+// both entries: coef == nullptr takes the per-level cell matrices K_of_level, otherwise K_of_level is unused
+static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                           const double *K_of_level, const AsmCoef *coef, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                           const int32_t *line_master, const double *line_weight, double *build_ms) {
   if (!ctx) return GMG_ERR_INVALID;
-  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: not on a communicator (rank-local assembly does not exist yet)");
-  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: dim must be 2 or 3");
-  if (n_dofs < 0 || n_cells < 0 || n_lines < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: negative size");
+  (void)hipSetDevice(ctx->device);
+  auto drop = [&] { reset_keep_halo(ctx->S); ctx->S_invd.reset(); ctx->S_tmp.reset(); };
+  // the coefficient form: whatever the context held goes first, so that after any failure it holds no system matrix (the
+  // cell-matrix form leaves the context untouched by arguments it refuses as invalid)
+  if (coef) drop();
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_dofs < 0 || n_cells < 0 || n_lines < 0) return bad(GMG_ERR_INVALID, "negative size");
   const int nv = 1 << dim;
-  if ((n_cells > 0 && (!cell_dofs || !cell_level || !K_of_level)) || (n_dofs > 0 && !constraint_of_dof) || (n_lines > 0 && !line_ptr))
-    return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: an array of nonzero length is NULL");
+  if ((n_cells > 0 && (!cell_dofs || !cell_level || (!coef && !K_of_level))) || (n_dofs > 0 && !constraint_of_dof) || (n_lines > 0 && !line_ptr))
+    return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
   if (n_dofs >= ((int64_t)1 << 31) || n_cells * nv >= ((int64_t)1 << 31) || n_lines >= ((int64_t)1 << 31))
-    return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 DoFs, slots or lines");
+    return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs, slots or lines");
   std::vector<int32_t> lp32((size_t)n_lines + 1, 0);
   int64_t max_line = 0;
   if (n_lines > 0) {
-    if (line_ptr[0] < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line_ptr starts below 0");
+    if (line_ptr[0] < 0) return bad(GMG_ERR_INVALID, "line_ptr starts below 0");
     for (int64_t l = 0; l < n_lines; ++l) {
-      if (line_ptr[l + 1] < line_ptr[l]) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line_ptr decreases");
+      if (line_ptr[l + 1] < line_ptr[l]) return bad(GMG_ERR_INVALID, "line_ptr decreases");
       max_line = std::max(max_line, line_ptr[l + 1] - line_ptr[l]);
     }
-    if (line_ptr[n_lines] >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 line entries");
+    if (line_ptr[n_lines] >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 line entries");
     for (int64_t l = 0; l <= n_lines; ++l) lp32[(size_t)l] = (int32_t)line_ptr[l];
   }
   const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
-  if (n_ent > 0 && (!line_master || !line_weight)) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: an array of nonzero length is NULL");
+  if (n_ent > 0 && (!line_master || !line_weight)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
   for (int64_t e = line_ptr && n_lines > 0 ? line_ptr[0] : 0; e < n_ent; ++e)
-    if (line_master[e] < 0 || line_master[e] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: master outside [0, n_dofs)");
+    if (line_master[e] < 0 || line_master[e] >= n_dofs) return bad(GMG_ERR_INVALID, "master outside [0, n_dofs)");
   for (int64_t d = 0; d < n_dofs; ++d)
-    if (constraint_of_dof[d] < -1 || constraint_of_dof[d] >= n_lines) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: line index outside [0, n_lines)");
+    if (constraint_of_dof[d] < -1 || constraint_of_dof[d] >= n_lines) return bad(GMG_ERR_INVALID, "line index outside [0, n_lines)");
   for (int64_t s = 0; s < n_slots; ++s)
-    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: DoF outside [0, n_dofs)");
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return bad(GMG_ERR_INVALID, "DoF outside [0, n_dofs)");
   for (int64_t c = 0; c < n_cells; ++c)
-    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_system_matrix: cell level of 16 or more");
+    if (cell_level[c] > 15) return bad(GMG_ERR_INVALID, "cell level of 16 or more");
   // (32-bit slot lists: every slot goes to its DoF and to at most max_line masters)
-  if (n_slots * (1 + max_line) >= ((int64_t)1 << 31)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_system_matrix: more than 2^31 (row, slot) pairs");
-  (void)hipSetDevice(ctx->device);
+  if (n_slots * (1 + max_line) >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 (row, slot) pairs");
+  if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
   DevCSR &m = ctx->S;
-  reset_keep_halo(m);
-  ctx->S_invd.reset(); ctx->S_tmp.reset();
+  drop();
+  AsmCoefDev d_coef;
   DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
   DevPtr<uint8_t> d_lv;
   DevPtr<double> d_K, d_lw;
@@ -3855,7 +3891,7 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
   Event e0, e1;
   HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
   HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
-  HIPC(upload(d_K, K_of_level, n_cells > 0 ? (size_t)16 * nv * nv : 0, ctx->stream));
+  if (!coef) HIPC(upload(d_K, K_of_level, n_cells > 0 ? (size_t)16 * nv * nv : 0, ctx->stream));
   HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
   HIPC(upload(d_lp, lp32, ctx->stream));
   HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
@@ -3870,17 +3906,18 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
   a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.K = d_K.get(); a.cons = d_cons.get();
   a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
   a.invd = ctx->S_invd.get();
+  if (coef) CHK(upload_coef(ctx, *coef, n_cells, nv, d_coef, a));
   std::vector<int32_t> rp;
   int64_t nnz = 0;
   int32_t n_inc = 0;
-  int rc = assemble_rows<false>(ctx, "gmg_assemble_system_matrix", a, w, m, rp, nnz, n_inc, [](int64_t) { return (int)GMG_OK; });
+  int rc = assemble_rows<false>(ctx, who, a, w, m, rp, nnz, n_inc, [](int64_t) { return (int)GMG_OK; });
   if (rc == GMG_OK) {
-    rc = hipEventRecord(e1.get(), ctx->stream) == hipSuccess ? GMG_OK : fail(ctx, GMG_ERR_HIP, "gmg_assemble_system_matrix: hipEventRecord");
+    rc = hipEventRecord(e1.get(), ctx->stream) == hipSuccess ? GMG_OK : bad(GMG_ERR_HIP, "hipEventRecord");
     if (rc == GMG_OK) rc = tile_device_csr(ctx, m, rp, n_dofs, n_dofs, nnz);
   }
   if (rc != GMG_OK) {  // (nothing half-built stays behind)
     (void)hipStreamSynchronize(ctx->stream);
-    reset_keep_halo(m); ctx->S_invd.reset(); ctx->S_tmp.reset();
+    drop();
     return rc;
   }
   float ms = 0.f;
@@ -3888,7 +3925,23 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
   if (build_ms) *build_ms = ms;
   if (ctx->debug_upload)
     std::fprintf(stderr, "[gmg] system matrix assembled on the device: %lld rows nnz %lld, %lld (row, slot) pairs, %.3f ms\n", (long long)n_dofs, (long long)nnz, (long long)n_inc, ms);
-  return GMG_OK;
+  return GMG_OK;  // (tile_device_csr has asked hipGetLastError after the last launch)
+}
+
+int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                               const double *K_of_level, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                               const int32_t *line_master, const double *line_weight, double *build_ms) {
+  return assemble_system(ctx, "gmg_assemble_system_matrix", dim, n_dofs, n_cells, cell_dofs, cell_level, K_of_level, nullptr, constraint_of_dof, n_lines,
+                         line_ptr, line_master, line_weight, build_ms);
+}
+
+int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level, int nq,
+                                    const double *cell_coef, const double *G, const double *qw, const double *scale_of_level,
+                                    const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master,
+                                    const double *line_weight, double *build_ms) {
+  const AsmCoef coef{nq, cell_coef, G, qw, scale_of_level, 16};
+  return assemble_system(ctx, "gmg_assemble_system_matrix_coef", dim, n_dofs, n_cells, cell_dofs, cell_level, nullptr, &coef, constraint_of_dof, n_lines,
+                         line_ptr, line_master, line_weight, build_ms);
 }
 
 int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
@@ -3940,35 +3993,38 @@ int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *
 
 // ---- the multigrid level and interface matrices formed on the device (gmg_assemble.hpp) ----
 
-static int assemble_level_checked(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
-                           const uint8_t *dof_flags, double *build_ms) {
-  const char *who = "gmg_assemble_level_matrix";
-  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: not on a communicator (rank-local assembly does not exist yet)");
-  if (level == 0 && l0_partitioned(ctx)) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: a row-partitioned level 0 takes its local rows as CSR (gmg_set_level_matrix)");
-  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: dim must be 2 or 3");
-  if (n_dofs < 0 || n_cells < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: negative size");
+// both entries: coef == nullptr takes the level's cell matrix K, otherwise K is unused
+static int assemble_level_checked(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                                  const double *K, const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
+  if (level == 0 && l0_partitioned(ctx)) return bad(GMG_ERR_UNSUPPORTED, "a row-partitioned level 0 takes its local rows as CSR (gmg_set_level_matrix)");
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_dofs < 0 || n_cells < 0) return bad(GMG_ERR_INVALID, "negative size");
   const int nv = 1 << dim;
-  if ((n_cells > 0 && (!cell_dofs || !K)) || (n_dofs > 0 && !dof_flags)) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: an array of nonzero length is NULL");
-  if (n_dofs >= ((int64_t)1 << 31) || n_cells >= ((int64_t)1 << 31) / nv) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_assemble_level_matrix: more than 2^31 DoFs or slots");
+  if ((n_cells > 0 && (!cell_dofs || (!coef && !K))) || (n_dofs > 0 && !dof_flags)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_dofs >= ((int64_t)1 << 31) || n_cells >= ((int64_t)1 << 31) / nv) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs or slots");
+  if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
   const int64_t n_slots = n_cells * nv;
   for (int64_t s = 0; s < n_slots; ++s)
-    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: DoF outside [0, n_dofs)");
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return bad(GMG_ERR_INVALID, "DoF outside [0, n_dofs)");
   for (int64_t d = 0; d < n_dofs; ++d)
-    if (dof_flags[d] > 3) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: flag bits above 1");
+    if (dof_flags[d] > 3) return bad(GMG_ERR_INVALID, "flag bits above 1");
   const auto ex = level > 0 ? ctx->ssor_block_rows.find(level) : ctx->ssor_block_rows.end();
   const std::vector<int64_t> *explicit_rows = ex == ctx->ssor_block_rows.end() ? nullptr : &ex->second;
   if (explicit_rows && explicit_rows->back() != n_dofs)
-    return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_dofs");
+    return bad(GMG_ERR_INVALID, "the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_dofs");
   Level &L = ctx->lv[(size_t)level];
   DevCSR &m = L.A;
   DevPtr<int32_t> d_cd;
   DevPtr<uint8_t> d_fl;
   DevPtr<double> d_K, d_eval;
+  AsmCoefDev d_coef;
   DevPtr<unsigned long long> d_lmax;
   AsmScratch w;
   Event e0, e1;
   HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
-  HIPC(upload(d_K, K, n_cells > 0 ? (size_t)nv * nv : 0, ctx->stream));
+  if (!coef) HIPC(upload(d_K, K, n_cells > 0 ? (size_t)nv * nv : 0, ctx->stream));
   HIPC(upload(d_fl, dof_flags, (size_t)n_dofs, ctx->stream));
   HIPC(L.I.rowptr.alloc((size_t)n_dofs + 1));  // (the row kernel counts I_l's entries into it)
   HIPC(d_lmax.alloc(1));
@@ -3981,6 +4037,7 @@ static int assemble_level_checked(gmg_context *ctx, int level, int dim, int64_t 
   AsmArgs a{};
   a.nv = nv; a.lg_nv = dim; a.max_line = 0; a.n_dofs = n_dofs; a.n_slots = n_slots;
   a.cell_dofs = d_cd.get(); a.K = d_K.get(); a.flags = d_fl.get(); a.invd = L.invd.get(); a.edge_cnt = L.I.rowptr.get();
+  if (coef) CHK(upload_coef(ctx, *coef, n_cells, nv, d_coef, a));
   std::vector<int32_t> rp;
   int64_t nnz = 0;
   int32_t n_inc = 0;
@@ -4027,7 +4084,7 @@ static int assemble_level_checked(gmg_context *ctx, int level, int dim, int64_t 
   HIPC(hipStreamSynchronize(ctx->stream));
   CHK(tile_device_csr(ctx, m, rp, n_dofs, n_dofs, nnz));
   if (n_edge > 0) {
-    if (trp[(size_t)n_dofs] != n_edge) return fail(ctx, GMG_ERR_HIP, "gmg_assemble_level_matrix: the transposed interface matrix lost entries");
+    if (trp[(size_t)n_dofs] != n_edge) return bad(GMG_ERR_HIP, "the transposed interface matrix lost entries");
     CHK(tile_device_csr(ctx, L.I, irp, n_dofs, n_dofs, n_edge));
     CHK(tile_device_csr(ctx, L.It, trp, n_dofs, n_dofs, n_edge));
     L.has_I = true;
@@ -4049,10 +4106,10 @@ static int assemble_level_checked(gmg_context *ctx, int level, int dim, int64_t 
   return finish_level(ctx, level, n_dofs, n_dofs, nnz);
 }
 
-int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
-                              const uint8_t *dof_flags, double *build_ms) {
+static int assemble_level(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
+                          const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms) {
   if (!ctx) return GMG_ERR_INVALID;
-  if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, "gmg_assemble_level_matrix: level outside the context");
+  if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": level outside the context").c_str());
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
   // whatever the level held goes first: after a failure it holds no operator
@@ -4066,12 +4123,23 @@ int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_do
   };
   clear();
   if (level == 0) drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
-  const int rc = assemble_level_checked(ctx, level, dim, n_dofs, n_cells, cell_dofs, K, dof_flags, build_ms);
+  const int rc = assemble_level_checked(ctx, who, level, dim, n_dofs, n_cells, cell_dofs, K, coef, dof_flags, build_ms);
   if (rc != GMG_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     clear();
   }
   return rc;
+}
+
+int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
+                              const uint8_t *dof_flags, double *build_ms) {
+  return assemble_level(ctx, "gmg_assemble_level_matrix", level, dim, n_dofs, n_cells, cell_dofs, K, nullptr, dof_flags, build_ms);
+}
+
+int gmg_assemble_level_matrix_coef(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, int nq,
+                                   const double *cell_coef, const double *G, const double *qw, double scale, const uint8_t *dof_flags, double *build_ms) {
+  const AsmCoef coef{nq, cell_coef, G, qw, &scale, 1};
+  return assemble_level(ctx, "gmg_assemble_level_matrix_coef", level, dim, n_dofs, n_cells, cell_dofs, nullptr, &coef, dof_flags, build_ms);
 }
 
 int gmg_get_level_matrix(gmg_context *ctx, int level, int which, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {

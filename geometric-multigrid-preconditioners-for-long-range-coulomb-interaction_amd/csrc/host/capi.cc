@@ -368,6 +368,47 @@ int step50_level_assembly_inputs(step50_problem *h, int level, int32_t *cell_dof
     return 0;
   });
 }
+// ---- the coefficient form: what the driver hands to gmg_assemble_system_matrix_coef /
+// gmg_assemble_level_matrix_coef beyond the arrays above.  sizes: nq, n_cells, 2^dim, number of scales (16 / 1)
+int step50_system_coefficient_sizes(step50_problem *h, int64_t sizes[4]) {
+  return guarded(h, [&] {
+    sizes[0] = (int64_t)DISPATCH(h, coefficient_tables().nq); sizes[1] = (int64_t)DISPATCH(h, active_cells.size());
+    sizes[2] = (int64_t)1 << h->dim; sizes[3] = 16;
+    return 0;
+  });
+}
+int step50_system_coefficient_inputs(step50_problem *h, double *cell_coef, double *G, double *qw, double *scale_of_level) {
+  return guarded(h, [&] {
+    auto fill = [&](auto &P) {
+      const auto in = P.system_coefficient_inputs();
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(in.cell_coef, cell_coef); put(in.G, G); put(in.qw, qw); put(in.scale, scale_of_level);
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
+int step50_level_coefficient_sizes(step50_problem *h, int level, int64_t sizes[4]) {
+  return guarded(h, [&] {
+    if (level < 0 || level >= step50_n_levels(h)) throw std::runtime_error("level_coefficient_inputs: no such level");
+    sizes[0] = (int64_t)DISPATCH(h, coefficient_tables().nq);
+    sizes[1] = (int64_t)DISPATCH(h, level_cell_dof_table)[(size_t)level].size() >> h->dim;
+    sizes[2] = (int64_t)1 << h->dim; sizes[3] = 1;
+    return 0;
+  });
+}
+int step50_level_coefficient_inputs(step50_problem *h, int level, double *cell_coef, double *G, double *qw, double *scale) {
+  return guarded(h, [&] {
+    if (level < 0 || level >= step50_n_levels(h)) throw std::runtime_error("level_coefficient_inputs: no such level");
+    auto fill = [&](auto &P) {
+      const auto in = P.level_coefficient_inputs(level);
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(in.cell_coef, cell_coef); put(in.G, G); put(in.qw, qw); put(in.scale, scale);
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
 // the refinement marks of the cycle just estimated, all levels concatenated; returns their number (out may be null)
 int64_t step50_refine_flags(step50_problem *h, uint8_t *out) {
   int64_t n = 0;

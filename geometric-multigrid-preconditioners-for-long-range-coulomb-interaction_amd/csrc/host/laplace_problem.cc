@@ -229,12 +229,12 @@ void ParameterReader::declare_parameters() {
             // as CSR (gmg_set_level_matrix_lattice; 3D constant-coefficient problems with a lexicographic, unpartitioned level 0)
             {"Level 0 matrix on device", "true"},
             // the active-mesh system matrix formed on the device from the cells' DoFs, the per-level cell matrix and the
-            // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; constant-coefficient
-            // problems on one rank, DESIGN.md section 12
+            // constraint lines (gmg_assemble_system_matrix) instead of assembled here and uploaded as CSR; one rank, DESIGN.md
+            // section 12 (Step16: the coefficient's values at the quadrature points instead of cell matrices, section 18)
             {"System matrix on device", "false"},
             // the level matrices A_l and the interface matrices I_l formed on the device from the levels' cell tables, one
             // cell matrix and the boundary / refinement-edge flags (gmg_assemble_level_matrix) instead of assembled here and
-            // uploaded as CSR; constant-coefficient problems on one rank, DESIGN.md section 17
+            // uploaded as CSR; one rank, DESIGN.md section 17 (Step16: section 18)
             {"Level matrices on device", "false"},
             // what stands behind mg_coarse: the reference's unpreconditioned CG (:962-967), or fast diagonalisation on the
             // level-0 lattice (gmg_set_coarse_solver; where level 0 does not qualify the CG stays), DESIGN.md section 15
@@ -899,25 +899,43 @@ void LaplaceProblem<dim>::compute_moments() {
 // ======================================================================== assembly
 
 namespace {
-template <int dim, class Coef>
-void cell_matrix(const Quadrature<dim> &q2, double h, const double x0[3], Coef coef, bool constant, double K[1 << dim][1 << dim]) {
+// sum_d d_d phi_i d_d phi_j at quadrature point q of the reference cell: the G[q][i][j] of gmg_assemble_*_matrix_coef
+template <int dim>
+inline double gradient_product(const Quadrature<dim> &q2, size_t q, int i, int j) {
+  double g = 0;
+  for (int d = 0; d < dim; ++d) g += q2.grad[q][(size_t)i][(size_t)d] * q2.grad[q][(size_t)j][(size_t)d];
+  return g;
+}
+
+// the cell matrix of a cell with edge h from the coefficient's values at its quadrature points (coef == nullptr: 1.0
+// everywhere); gmg_assemble_*_matrix_coef forms the same sums from the same values
+template <int dim>
+void cell_matrix(const Quadrature<dim> &q2, double h, const double *coef, double K[1 << dim][1 << dim]) {
   constexpr int nv = 1 << dim;
   for (int i = 0; i < nv; ++i)
     for (int j = 0; j < nv; ++j) K[i][j] = 0;
   const double scale = std::pow(h, dim - 2);  // JxW / h^2 from the two gradients
   for (size_t q = 0; q < q2.p.size(); ++q) {
-    double c = 1.0;
-    if (!constant) {
-      double x[3] = {0, 0, 0};
-      for (int d = 0; d < dim; ++d) x[d] = x0[d] + h * q2.p[q][(size_t)d];
-      c = coef(x);
-    }
+    const double c = coef ? coef[q] : 1.0;
     for (int i = 0; i < nv; ++i)
       for (int j = 0; j < nv; ++j) {
-        double g = 0;
-        for (int d = 0; d < dim; ++d) g += q2.grad[q][(size_t)i][(size_t)d] * q2.grad[q][(size_t)j][(size_t)d];
+        const double g = gradient_product<dim>(q2, q, i, j);
         K[i][j] += c * g * q2.w[q] * scale;
       }
+  }
+}
+
+constexpr int kMaxCoefficientPoints = 64;  // (degree 1: 2^dim points)
+
+// The coefficient at the quadrature points of a cell with origin x0 and edge h, q ascending.  The one text for these values:
+// the host's cell matrices and the tables of gmg_assemble_*_matrix_coef are made from it, so a point near the sphere is on
+// the same side for both.
+template <int dim>
+void coefficient_values(const LaplaceProblem<dim> &P, const Quadrature<dim> &q2, double h, const double x0[3], double *out) {
+  for (size_t q = 0; q < q2.p.size(); ++q) {
+    double x[3] = {0, 0, 0};
+    for (int d = 0; d < dim; ++d) x[d] = x0[d] + h * q2.p[q][(size_t)d];
+    out[q] = P.coefficient(x);
   }
 }
 
@@ -933,8 +951,7 @@ struct CellAssembly {
   const bool constant_coef;
   double Kc[nv][nv];  // constant coefficient: the cell matrix of the unit cell
   explicit CellAssembly(const LaplaceProblem<dim> &p) : P(p), q_laplace((int)p.par.degree + 1), constant_coef(p.par.Problemtype != "Step16") {
-    double x0[3] = {0, 0, 0};
-    if (constant_coef) cell_matrix<dim>(q_laplace, 1.0, x0, [](const double *) { return 1.0; }, true, Kc);
+    cell_matrix<dim>(q_laplace, 1.0, nullptr, Kc);
   }
   // constant coefficient: the cell matrix of a cell with edge h
   void scaled(double h, double (&K)[nv][nv]) const {
@@ -947,8 +964,10 @@ struct CellAssembly {
     const Cell &cell = P.triangulation.levels[(size_t)ac.level][(size_t)ac.index];
     h = P.triangulation.cell_size(ac.level);
     P.triangulation.cell_origin(ac.level, cell, x0);
-    if (constant_coef) scaled(h, K);
-    else cell_matrix<dim>(q_laplace, h, x0, [&](const double *x) { return P.coefficient(x); }, false, K);
+    if (constant_coef) { scaled(h, K); return; }
+    double c[kMaxCoefficientPoints];
+    coefficient_values<dim>(P, q_laplace, h, x0, c);
+    cell_matrix<dim>(q_laplace, h, c, K);
   }
   // ConstraintMatrix::distribute_local_to_global (:793-795, 825-828)
   void cell_lines(size_t ci, int32_t (&dofs)[nv], const Line *(&line)[nv]) const {
@@ -967,8 +986,7 @@ bool LaplaceProblem<dim>::decide_system_on_device() {
   if (!par.system_matrix_on_device) return false;
   const char *why = !solve_on_device_requested ? "the cycle does not run on the device"
                     : distributed              ? "the run is distributed"
-                    : par.Problemtype == "Step16" ? "the coefficient varies"
-                                                  : nullptr;
+                                               : nullptr;
   if (!why) return true;
   if (!system_fallback_reported) pcout(std::string("   System matrix on device: not applicable (") + why + "), assembled on the host");
   system_fallback_reported = true;
@@ -1007,6 +1025,62 @@ typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_a
     in.line_inhomogeneity.push_back(constraint_lines[l].inhomogeneity);
     for (auto &e : constraint_lines[l].entries) { in.line_master.push_back(e.first); in.line_weight.push_back(e.second); }
   }
+  return in;
+}
+
+// what the coefficient form takes beyond the cell tables: the quadrature's tables and, filled by the callers below, the
+// coefficient values and the scale(s)
+template <int dim>
+typename LaplaceProblem<dim>::CoefficientInputs LaplaceProblem<dim>::coefficient_tables() const {
+  constexpr int nv = 1 << dim;
+  const Quadrature<dim> q2((int)par.degree + 1);
+  CoefficientInputs in;
+  in.nq = (int)q2.p.size();
+  if (in.nq > kMaxCoefficientPoints) throw std::runtime_error("coefficient inputs: more than 64 quadrature points");
+  in.qw.assign(q2.w.begin(), q2.w.end());
+  in.G.resize((size_t)in.nq * nv * nv);
+  for (size_t q = 0; q < q2.p.size(); ++q)
+    for (int i = 0; i < nv; ++i)
+      for (int j = 0; j < nv; ++j) in.G[(q * nv + (size_t)i) * nv + (size_t)j] = gradient_product<dim>(q2, q, i, j);
+  return in;
+}
+
+// gmg_assemble_system_matrix_coef: the coefficient at the quadrature points of every active cell (the host's threads, one
+// cell per iteration: the values do not depend on their number) and pow(h, dim - 2) of every level, as cell_matrix scales
+template <int dim>
+typename LaplaceProblem<dim>::CoefficientInputs LaplaceProblem<dim>::system_coefficient_inputs() const {
+  const Quadrature<dim> q2((int)par.degree + 1);
+  CoefficientInputs in = coefficient_tables();
+  const int64_t nc = (int64_t)active_cells.size();
+  in.cell_coef.resize((size_t)nc * (size_t)in.nq);
+#pragma omp parallel for schedule(static)
+  for (int64_t ci = 0; ci < nc; ++ci) {
+    const auto &ac = active_cells[(size_t)ci];
+    double x0[3];
+    triangulation.cell_origin(ac.level, triangulation.levels[(size_t)ac.level][(size_t)ac.index], x0);
+    coefficient_values<dim>(*this, q2, triangulation.cell_size(ac.level), x0, &in.cell_coef[(size_t)ci * (size_t)in.nq]);
+  }
+  in.scale.resize(16);
+  for (int l = 0; l < 16; ++l) in.scale[(size_t)l] = std::pow(triangulation.cell_size(l), dim - 2);
+  return in;
+}
+
+// gmg_assemble_level_matrix_coef: likewise for all cells of level l, with the level's one scale
+template <int dim>
+typename LaplaceProblem<dim>::CoefficientInputs LaplaceProblem<dim>::level_coefficient_inputs(int l) const {
+  const Quadrature<dim> q2((int)par.degree + 1);
+  CoefficientInputs in = coefficient_tables();
+  const auto &cells = triangulation.levels[(size_t)l];
+  const int64_t nc = (int64_t)cells.size();
+  const double h = triangulation.cell_size(l);
+  in.cell_coef.resize((size_t)nc * (size_t)in.nq);
+#pragma omp parallel for schedule(static)
+  for (int64_t ci = 0; ci < nc; ++ci) {
+    double x0[3];
+    triangulation.cell_origin(l, cells[(size_t)ci], x0);
+    coefficient_values<dim>(*this, q2, h, x0, &in.cell_coef[(size_t)ci * (size_t)in.nq]);
+  }
+  in.scale.assign(1, std::pow(h, dim - 2));
   return in;
 }
 
@@ -1113,7 +1187,8 @@ void LaplaceProblem<dim>::assemble_system() {
     ca.cell_lines(ci, dofs, line);
     bool any_inhom = false;
     for (int a = 0; a < nv; ++a) any_inhom = any_inhom || (line[a] && line[a]->inhomogeneity != 0.0);
-    if (!rhs_dev || any_inhom) ca.cell_K(ci, K, x0, h);
+    // (the cell matrix only for the inhomogeneous Dirichlet terms below: with "System matrix on device" nobody else forms it)
+    if (any_inhom) ca.cell_K(ci, K, x0, h);
     else { h = triangulation.cell_size(active_cells[ci].level); }
     double F[nv];
     for (int i = 0; i < nv; ++i) F[i] = 0;
@@ -1188,10 +1263,7 @@ void LaplaceProblem<dim>::assemble_system() {
 
 template <int dim>
 void LaplaceProblem<dim>::assemble_multigrid() {
-  constexpr int nv = 1 << dim;
   const int L = triangulation.n_levels();
-  const Quadrature<dim> q_laplace((int)par.degree + 1);
-  const bool constant_coef = par.Problemtype != "Step16";
   mg_matrices.assign((size_t)L, {});
   mg_interface_matrices.assign((size_t)L, {});
   level0_on_device = decide_level0_on_device();
@@ -1209,8 +1281,7 @@ bool LaplaceProblem<dim>::decide_levels_on_device() {
   if (!par.level_matrices_on_device) return false;
   const char *why = !solve_on_device_requested ? "the cycle does not run on the device"
                     : distributed              ? "the run is distributed"
-                    : par.Problemtype == "Step16" ? "the coefficient varies"
-                                                  : nullptr;
+                                               : nullptr;
   if (!why) return true;
   if (!levels_fallback_reported) pcout(std::string("   Level matrices on device: not applicable (") + why + "), assembled on the host");
   levels_fallback_reported = true;
@@ -1225,8 +1296,7 @@ typename LaplaceProblem<dim>::LevelAssemblyInputs LaplaceProblem<dim>::level_ass
   LevelAssemblyInputs in;
   const Quadrature<dim> q_laplace((int)par.degree + 1);
   double Kc[nv][nv];
-  double x0[3] = {0, 0, 0};
-  cell_matrix<dim>(q_laplace, 1.0, x0, [&](const double *) { return 1.0; }, true, Kc);
+  cell_matrix<dim>(q_laplace, 1.0, nullptr, Kc);
   const double s = std::pow(triangulation.cell_size(l), dim - 2);
   in.K.resize((size_t)nv * nv);
   for (int i = 0; i < nv; ++i)
@@ -1259,8 +1329,7 @@ void LaplaceProblem<dim>::level0_cell_matrix(double *Ke) const {
   constexpr int nv = 1 << dim;
   const Quadrature<dim> q_laplace((int)par.degree + 1);
   double Kc[nv][nv];
-  double x0[3] = {0, 0, 0};
-  cell_matrix<dim>(q_laplace, 1.0, x0, [&](const double *) { return 1.0; }, true, Kc);
+  cell_matrix<dim>(q_laplace, 1.0, nullptr, Kc);
   const double s = std::pow(triangulation.cell_size(0), dim - 2);
   for (int i = 0; i < nv; ++i)
     for (int j = 0; j < nv; ++j) Ke[i * nv + j] = Kc[i][j] * s;
@@ -1277,10 +1346,7 @@ void LaplaceProblem<dim>::assemble_level(int l) {
   const Quadrature<dim> q_laplace((int)par.degree + 1);
   const bool constant_coef = par.Problemtype != "Step16";
   double Kc[nv][nv];
-  if (constant_coef) {
-    double x0[3] = {0, 0, 0};
-    cell_matrix<dim>(q_laplace, 1.0, x0, [&](const double *) { return 1.0; }, true, Kc);
-  }
+  if (constant_coef) cell_matrix<dim>(q_laplace, 1.0, nullptr, Kc);
   {
     const auto &cells = triangulation.levels[(size_t)l];
     const int64_t n = (int64_t)level_vertex_of_dof[(size_t)l].size();
@@ -1304,9 +1370,10 @@ void LaplaceProblem<dim>::assemble_level(int l) {
         for (int i = 0; i < nv; ++i)
           for (int j = 0; j < nv; ++j) K[i][j] = Kc[i][j] * s;
       } else {
-        double x0[3];
+        double x0[3], c[kMaxCoefficientPoints];
         triangulation.cell_origin(l, cells[ci], x0);
-        cell_matrix<dim>(q_laplace, h, x0, [&](const double *x) { return coefficient(x); }, false, K);
+        coefficient_values<dim>(*this, q_laplace, h, x0, c);
+        cell_matrix<dim>(q_laplace, h, c, K);
       }
       const int32_t *dofs = &citems[ci * nv];
       for (int i = 0; i < nv; ++i) {
@@ -1445,9 +1512,20 @@ int LaplaceProblem<dim>::upload() {
     const SystemAssemblyInputs in = system_assembly_inputs();
     sublap(nullptr);
     double build_ms = 0.0;
-    const int rc_asm = gmg_assemble_system_matrix(gmg, dim, n_system, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(),
-                                                  in.K_of_level.data(), constraint_of_dof.data(), (int64_t)constraint_lines.size(), in.line_ptr.data(),
-                                                  in.line_master.data(), in.line_weight.data(), &build_ms);
+    int rc_asm;
+    if (par.Problemtype == "Step16") {
+      // section 18: the coefficient varies -- its values at the cells' quadrature points instead of one cell matrix per level
+      const CoefficientInputs co = system_coefficient_inputs();
+      sublap("assemble: coefficient values");
+      rc_asm = gmg_assemble_system_matrix_coef(gmg, dim, n_system, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(), co.nq,
+                                               co.cell_coef.data(), co.G.data(), co.qw.data(), co.scale.data(), constraint_of_dof.data(),
+                                               (int64_t)constraint_lines.size(), in.line_ptr.data(), in.line_master.data(), in.line_weight.data(),
+                                               &build_ms);
+    } else {
+      rc_asm = gmg_assemble_system_matrix(gmg, dim, n_system, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(),
+                                          in.K_of_level.data(), constraint_of_dof.data(), (int64_t)constraint_lines.size(), in.line_ptr.data(),
+                                          in.line_master.data(), in.line_weight.data(), &build_ms);
+    }
     if (rc_asm == GMG_ERR_UNSUPPORTED) {
       // a mesh the device assembly does not take (a row wider than its limit, sizes beyond 32-bit indices): the host path
       if (!system_fallback_reported) pcout(std::string("   System matrix on device: not applicable (") + gmg_last_error(gmg) + "), assembled on the host");
@@ -1498,8 +1576,16 @@ int LaplaceProblem<dim>::upload() {
       const auto t_level = std::chrono::steady_clock::now();
       const LevelAssemblyInputs in = level_assembly_inputs(l);
       double build_ms = 0.0;
-      const int rc_asm = gmg_assemble_level_matrix(gmg, l, dim, (int64_t)level_vertex_of_dof[(size_t)l].size(), (int64_t)triangulation.levels[(size_t)l].size(),
-                                                   level_cell_dof_table[(size_t)l].data(), in.K.data(), in.dof_flags.data(), &build_ms);
+      const int64_t n_level = (int64_t)level_vertex_of_dof[(size_t)l].size(), n_level_cells = (int64_t)triangulation.levels[(size_t)l].size();
+      int rc_asm;
+      if (par.Problemtype == "Step16") {  // section 18
+        const CoefficientInputs co = level_coefficient_inputs(l);
+        rc_asm = gmg_assemble_level_matrix_coef(gmg, l, dim, n_level, n_level_cells, level_cell_dof_table[(size_t)l].data(), co.nq, co.cell_coef.data(),
+                                                co.G.data(), co.qw.data(), co.scale[0], in.dof_flags.data(), &build_ms);
+      } else {
+        rc_asm = gmg_assemble_level_matrix(gmg, l, dim, n_level, n_level_cells, level_cell_dof_table[(size_t)l].data(), in.K.data(), in.dof_flags.data(),
+                                           &build_ms);
+      }
       if (rc_asm == GMG_ERR_UNSUPPORTED) {
         // a level the device assembly does not take (a row wider than its limit, sizes beyond 32-bit indices): the host path
         if (!levels_fallback_reported) pcout(std::string("   Level matrices on device: not applicable (") + gmg_last_error(gmg) + "), assembled on the host");

@@ -78,8 +78,8 @@ struct Parameters {
   bool rhs_on_device = true;            // gmg_rhs_assemble: F integrated on the device from densities that stay there
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
-  bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (constant coefficient, one rank)
-  bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (constant coefficient, one rank)
+  bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (one rank; Step16: the _coef entry)
+  bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
@@ -144,6 +144,16 @@ class LaplaceProblem {
     std::vector<uint8_t> dof_flags;  // bit 0 level_boundary, bit 1 level_refinement_edge
   };
   LevelAssemblyInputs level_assembly_inputs(int l) const;
+  // what gmg_assemble_system_matrix_coef / gmg_assemble_level_matrix_coef take beyond the cell tables
+  struct CoefficientInputs {
+    int nq = 0;
+    std::vector<double> cell_coef;  // [n_cells][nq]: coefficient(x0 + h p_q), q ascending
+    std::vector<double> G, qw;      // [nq][nv][nv], [nq]
+    std::vector<double> scale;      // [16] by level (system) or [1] (one level): pow(h, dim - 2)
+  };
+  CoefficientInputs coefficient_tables() const;
+  CoefficientInputs system_coefficient_inputs() const;
+  CoefficientInputs level_coefficient_inputs(int l) const;
   bool decide_level0_on_device() const;                                  // level 0 formed on the device (gmg_set_level_matrix_lattice)?
   void level0_cell_matrix(double *Ke) const;
   void build_transfer();                                                 // mg_transfer.build_matrices, :957-958

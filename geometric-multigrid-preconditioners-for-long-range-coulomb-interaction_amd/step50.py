@@ -322,6 +322,31 @@ class Problem:
         return SimpleNamespace(dim=dim, n_dofs=n_dofs, cell_dofs=cd, cell_level=lv, K_of_level=K, constraint_of_dof=cons, line_ptr=lp,
                                line_master=lm, line_weight=lw, line_inhomogeneity=li)
 
+    def _coefficient_fields(self, sizes_call, inputs_call, what):
+        sz = (C.c_int64 * 4)()
+        self._chk(sizes_call(sz), what)
+        nq, n_cells, nv, n_scale = (int(v) for v in sz)
+        cc, G, qw, sc = np.zeros((n_cells, nq)), np.zeros((nq, nv, nv)), np.zeros(nq), np.zeros(n_scale)
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(inputs_call(P(cc), P(G), P(qw), P(sc)), what)
+        return dict(nq=nq, cell_coef=cc, G=G, qw=qw), sc
+
+    def system_coefficient_inputs(self):
+        """The arrays the driver hands to gmg_assemble_system_matrix_coef for the current mesh: the fields of
+        system_assembly_inputs() plus nq, cell_coef [n_cells, nq] (the coefficient at the quadrature points of every active
+        cell), G [nq, 2^dim, 2^dim], qw [nq] and scale_of_level [16] (pow(h, dim - 2))."""
+        new, sc = self._coefficient_fields(lambda sz: self.L.step50_system_coefficient_sizes(self.h, sz),
+                                           lambda *a: self.L.step50_system_coefficient_inputs(self.h, *a), "system_coefficient_inputs")
+        return SimpleNamespace(**vars(self.system_assembly_inputs()), **new, scale_of_level=sc)
+
+    def level_coefficient_inputs(self, level):
+        """The arrays the driver hands to gmg_assemble_level_matrix_coef for one level of the current mesh: the fields of
+        level_assembly_inputs(level) plus nq, cell_coef [n_cells, nq] (all cells of the level), G, qw and scale."""
+        new, sc = self._coefficient_fields(lambda sz: self.L.step50_level_coefficient_sizes(self.h, C.c_int(level), sz),
+                                           lambda *a: self.L.step50_level_coefficient_inputs(self.h, C.c_int(level), *a),
+                                           "level_coefficient_inputs")
+        return SimpleNamespace(**vars(self.level_assembly_inputs(level)), **new, scale=float(sc[0]))
+
     def device_system_matrix(self):
         """The system matrix as the device holds it after a cycle with "System matrix on device" (gmg_get_system_matrix)."""
         from . import capi

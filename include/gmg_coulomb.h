@@ -352,6 +352,24 @@ int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_
                                const uint8_t *cell_level, const double *K_of_level, const int32_t *constraint_of_dof,
                                int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master, const double *line_weight,
                                double *build_ms);
+/* gmg_assemble_system_matrix for a coefficient that varies in space: instead of one cell matrix per level the caller hands
+ * over the coefficient VALUES at the quadrature points of every cell, and the cell matrices are formed on the device where
+ * they are consumed (none is stored).  Inputs beyond those of gmg_assemble_system_matrix: nq (1 <= nq <= 64) quadrature
+ * points per cell; cell_coef [n_cells][nq], the coefficient at point q of cell c (a deal.II adapter passes
+ * coefficient.value_list(fe_values.get_quadrature_points(), ...) per cell); G [nq][2^dim][2^dim], the reference-cell
+ * products sum_d d_d phi_i d_d phi_j at each point -- the caller forms them, their bits are the caller's; qw [nq], the
+ * weights; scale_of_level [16], the factor of a cell of that level (the driver passes pow(h, dim - 2)).  The cell matrix of
+ * cell c is
+ *   K_c[i][j] = +0.0;   for q ascending:   K_c[i][j] += ((cell_coef[c][q] * G[q][i][j]) * qw[q]) * scale_of_level[cell_level[c]]
+ * in fp64 without contraction.  Everything else is word for word the definition of gmg_assemble_system_matrix with K_c in
+ * place of K[level]: the pattern, the order of the sums, |K_c[i][i]| for a constrained i, the Jacobi diagonal, the error
+ * codes and the state the context is left in (gmg_get_system_matrix, gmg_system_matrix_norms, gmg_spmv, gmg_cg_solve work on
+ * it).  GMG_ERR_INVALID -- found on the host, before anything is launched -- additionally for nq outside [1, 64], a NULL
+ * cell_coef with n_cells > 0 and a NULL G, qw or scale_of_level.  After ANY failure the context holds no system matrix. */
+int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                                    const uint8_t *cell_level, int nq, const double *cell_coef, const double *G, const double *qw,
+                                    const double *scale_of_level, const int32_t *constraint_of_dof, int64_t n_lines,
+                                    const int64_t *line_ptr, const int32_t *line_master, const double *line_weight, double *build_ms);
 /* The CSR of the system matrix as the device holds it (after gmg_assemble_system_matrix; gmg_set_system_matrix keeps no CSR
  * copy: GMG_ERR_UNSUPPORTED): with rowptr == NULL only the sizes are returned.                                         */
 int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val);
@@ -386,6 +404,18 @@ int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *
  * After any failure the level holds no operator.  Zero cells are valid: n_dofs empty rows.                              */
 int gmg_assemble_level_matrix(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
                               const double *K, const uint8_t *dof_flags, double *build_ms);
+/* gmg_assemble_level_matrix for a coefficient that varies in space: nq, cell_coef [n_cells][nq] (all cells of the level), G
+ * and qw as for gmg_assemble_system_matrix_coef, and ONE scale (the driver passes pow(h_l, dim - 2)); the cell matrix of cell
+ * c is
+ *   K_c[i][j] = +0.0;   for q ascending:   K_c[i][j] += ((cell_coef[c][q] * G[q][i][j]) * qw[q]) * scale
+ * in fp64 without contraction.  Everything else is word for word the definition of gmg_assemble_level_matrix with K_c in
+ * place of K: the patterns, the order of the sums, |K_c[i][i]| for a flagged i, the Jacobi diagonal, the Chebyshev bound, I_l
+ * with its dropped zeros, I_l^T, the SSOR plan, the error codes and the state the level is left in.  GMG_ERR_INVALID
+ * additionally for nq outside [1, 64], a NULL cell_coef with n_cells > 0 and a NULL G or qw.  After any failure the level
+ * holds no operator.                                                                                                    */
+int gmg_assemble_level_matrix_coef(gmg_context *ctx, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                                   int nq, const double *cell_coef, const double *G, const double *qw, double scale,
+                                   const uint8_t *dof_flags, double *build_ms);
 /* The CSR of a level's operators as the device holds them: which = GMG_LEVEL_A, GMG_LEVEL_EDGE (I_l) or GMG_LEVEL_EDGE_T
  * (I_l^T).  With rowptr == NULL only the sizes are returned.  GMG_ERR_UNSUPPORTED where the device keeps no CSR copy (a
  * lattice level 0, an operator stored in a SELL layout); an absent interface matrix returns nnz = 0.                       */
