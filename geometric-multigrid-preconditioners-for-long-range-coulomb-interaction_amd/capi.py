@@ -27,6 +27,7 @@ SYMBOLS = [
     "gmg_set_system_matrix", "gmg_set_level_matrix", "gmg_set_level_matrix_lattice", "gmg_set_edge_matrix", "gmg_set_prolongation", "gmg_build_transfer", "gmg_get_transfer",
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
     "gmg_assemble_level_matrix", "gmg_get_level_matrix", "gmg_assemble_system_matrix_coef", "gmg_assemble_level_matrix_coef",
+    "gmg_assemble_rhs", "gmg_distribute_constraints",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -440,6 +441,40 @@ class Context:
                                                     opt(lp, C.c_int64), opt(lm, C.c_int32), opt(lw, C.c_double), C.byref(ms)))
         self.n_system = int(n_dofs)
         return ms.value
+
+    def assemble_rhs(self, inp, rhs, source=True, K_of_level=True):
+        """The right-hand side formed on the device from the cell tables (gmg_assemble_rhs) into rhs (DeviceVector of inp.n_dofs
+        entries); returns the device time in ms.  inp: the fields of Problem.rhs_assembly_inputs() (dim, n_dofs, cell_dofs
+        [n_cells, 2^dim], cell_level, constraint_of_dof, line_ptr, line_master, line_weight, line_inhomogeneity, K_of_level, nq,
+        shape [nq, 2^dim], weight, jxw_of_level, source [n_cells, nq]).  source=None passes NULL: the densities
+        charge_density(..., dens=None) left on the device; K_of_level=None passes NULL.  Arrays of length 0 are passed as NULL;
+        the library checks everything."""
+        i32, u8, f64 = (lambda a, t=t: np.ascontiguousarray([] if a is None else a, dtype=t) for t in (np.int32, np.uint8, np.float64))
+        cd, lv, cons = i32(inp.cell_dofs), u8(inp.cell_level), i32(inp.constraint_of_dof)
+        lp, lm = np.ascontiguousarray([] if inp.line_ptr is None else inp.line_ptr, dtype=np.int64), i32(inp.line_master)
+        lw, li = f64(inp.line_weight), f64(inp.line_inhomogeneity)
+        K = f64(inp.K_of_level if K_of_level is True else K_of_level)
+        sh, w, jxw = f64(inp.shape), f64(inp.weight), f64(inp.jxw_of_level)
+        src = f64(inp.source if source is True else source)
+        opt = lambda a, t: _p(a, t) if a.size else None
+        D = lambda a: opt(a, C.c_double)
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_rhs(self.h, C.c_int(int(inp.dim)), C.c_int64(int(inp.n_dofs)), C.c_int64(len(lv)), opt(cd, C.c_int32),
+                                          opt(lv, C.c_uint8), opt(cons, C.c_int32), C.c_int64(max(len(lp) - 1, 0)), opt(lp, C.c_int64),
+                                          opt(lm, C.c_int32), D(lw), D(li), D(K), C.c_int(int(inp.nq)), D(sh), D(w), D(jxw), D(src),
+                                          None if rhs is None else rhs.ptr, C.byref(ms)))
+        return ms.value
+
+    def distribute_constraints(self, u, constraint_of_dof, line_ptr, line_master, line_weight, line_inhomogeneity):
+        """constraints.distribute in place on the DeviceVector u (gmg_distribute_constraints)."""
+        cons = np.ascontiguousarray(constraint_of_dof, dtype=np.int32)
+        lp = np.ascontiguousarray([] if line_ptr is None else line_ptr, dtype=np.int64)
+        lm = np.ascontiguousarray([] if line_master is None else line_master, dtype=np.int32)
+        lw = np.ascontiguousarray([] if line_weight is None else line_weight, dtype=np.float64)
+        li = np.ascontiguousarray([] if line_inhomogeneity is None else line_inhomogeneity, dtype=np.float64)
+        opt = lambda a, t: _p(a, t) if a.size else None
+        self._chk(self.L.gmg_distribute_constraints(self.h, C.c_int64(u.n), u.ptr, opt(cons, C.c_int32), C.c_int64(max(len(lp) - 1, 0)),
+                                                    opt(lp, C.c_int64), opt(lm, C.c_int32), opt(lw, C.c_double), opt(li, C.c_double)))
 
     def assemble_system_matrix_coef(self, dim, n_dofs, cell_dofs, cell_level, nq, cell_coef, G, qw, scale_of_level, constraint_of_dof, line_ptr,
                                     line_master, line_weight, validate=True):

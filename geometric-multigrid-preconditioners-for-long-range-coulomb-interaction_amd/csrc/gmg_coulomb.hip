@@ -20,6 +20,7 @@
 #include "gmg_forces.hpp"
 #include "gmg_exact.hpp"
 #include "gmg_assemble.hpp"
+#include "gmg_rhs_cells.hpp"
 #include "gmg_estimate.hpp"
 #include "gmg_fastdiag.hpp"
 #include "gmg_mem.hpp"
@@ -2634,22 +2635,17 @@ struct AsmScratch {  // lives until the stream has run the kernels
 // and the FILL pass of the row kernel.  a holds the inputs and the outputs the caller owns (invd, ...); m receives rowptr /
 // col / val, rp the row pointers on the host, n_inc the (row, slot) pairs.  before_fill(nnz) may point a at further outputs of
 // the FILL pass once their size is known.  The FILL pass is enqueued, not waited for.
-template <bool LEVEL, class BeforeFill>
-int assemble_rows(gmg_context *ctx, const char *who, AsmArgs &a, AsmScratch &w, DevCSR &m, std::vector<int32_t> &rp, int64_t &nnz, int32_t &n_inc,
-                  BeforeFill before_fill) {
+// The incidence lists (gmg_assemble.hpp, kernels 1 and 2): every row's (cell, vertex) slots in ascending order, from the inputs
+// in a into a.inc_ptr / a.inc_slot (owned by w); n_inc receives the (row, slot) pairs.  The sort is enqueued, not waited for.
+template <bool LEVEL>
+int assemble_incidence(gmg_context *ctx, AsmArgs &a, AsmScratch &w, int32_t &n_inc) {
   const int64_t n_dofs = a.n_dofs, n_slots = a.n_slots;
   HIPC(w.iptr.alloc((size_t)n_dofs + 1));
   HIPC(w.ipos.alloc((size_t)n_dofs + 1));
-  HIPC(m.rowptr.alloc((size_t)n_dofs + 1));
-  HIPC(w.total.alloc(1));
-  HIPC(w.over.alloc(1));
   HIPC(hipMemsetAsync(w.iptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
   HIPC(hipMemsetAsync(w.ipos.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
-  HIPC(hipMemsetAsync(m.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
-  HIPC(hipMemsetAsync(w.total.get(), 0, sizeof(unsigned long long), ctx->stream));
-  HIPC(hipMemsetAsync(w.over.get(), 0, sizeof(int), ctx->stream));
-  a.inc_ptr = w.iptr.get(); a.inc_pos = w.ipos.get(); a.rowptr = m.rowptr.get(); a.total = w.total.get(); a.overflow = w.over.get();
-  const dim3 g_slots = asm_blocks(ctx, n_slots, 256), g_dofs = asm_blocks(ctx, n_dofs, 256), g_rows = asm_blocks(ctx, n_dofs, 1);
+  a.inc_ptr = w.iptr.get(); a.inc_pos = w.ipos.get();
+  const dim3 g_slots = asm_blocks(ctx, n_slots, 256), g_dofs = asm_blocks(ctx, n_dofs, 256);
   if (n_slots) hipLaunchKernelGGL((asm_incidence_kernel<false, LEVEL>), g_slots, dim3(256), 0, ctx->stream, a);
   hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, w.iptr.get(), n_dofs);
   n_inc = 0;
@@ -2661,6 +2657,22 @@ int assemble_rows(gmg_context *ctx, const char *who, AsmArgs &a, AsmScratch &w, 
     hipLaunchKernelGGL((asm_incidence_kernel<true, LEVEL>), g_slots, dim3(256), 0, ctx->stream, a);
     hipLaunchKernelGGL(asm_sort_incidence_kernel, g_dofs, dim3(256), 0, ctx->stream, a);
   }
+  return GMG_OK;
+}
+
+template <bool LEVEL, class BeforeFill>
+int assemble_rows(gmg_context *ctx, const char *who, AsmArgs &a, AsmScratch &w, DevCSR &m, std::vector<int32_t> &rp, int64_t &nnz, int32_t &n_inc,
+                  BeforeFill before_fill) {
+  const int64_t n_dofs = a.n_dofs;
+  HIPC(m.rowptr.alloc((size_t)n_dofs + 1));
+  HIPC(w.total.alloc(1));
+  HIPC(w.over.alloc(1));
+  HIPC(hipMemsetAsync(m.rowptr.get(), 0, sizeof(int32_t) * ((size_t)n_dofs + 1), ctx->stream));
+  HIPC(hipMemsetAsync(w.total.get(), 0, sizeof(unsigned long long), ctx->stream));
+  HIPC(hipMemsetAsync(w.over.get(), 0, sizeof(int), ctx->stream));
+  a.rowptr = m.rowptr.get(); a.total = w.total.get(); a.overflow = w.over.get();
+  const dim3 g_rows = asm_blocks(ctx, n_dofs, 1);
+  CHK(assemble_incidence<LEVEL>(ctx, a, w, n_inc));
   if (n_dofs) hipLaunchKernelGGL((asm_row_kernel<false, LEVEL>), g_rows, dim3(64), 0, ctx->stream, a);
   hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, m.rowptr.get(), n_dofs);
   rp.assign((size_t)n_dofs + 1, 0);
@@ -3838,27 +3850,24 @@ int gmg_rhs_assemble(gmg_context *ctx, int64_t n_cells, int nq, int dim, const d
 
 // ---- the active-mesh system matrix formed on the device (gmg_assemble.hpp) ----
 
-// both entries: coef == nullptr takes the per-level cell matrices K_of_level, otherwise K_of_level is unused
-static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
-                           const double *K_of_level, const AsmCoef *coef, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
-                           const int32_t *line_master, const double *line_weight, double *build_ms) {
-  if (!ctx) return GMG_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  auto drop = [&] { reset_keep_halo(ctx->S); ctx->S_invd.reset(); ctx->S_tmp.reset(); };
-  // the coefficient form: whatever the context held goes first, so that after any failure it holds no system matrix (the
-  // cell-matrix form leaves the context untouched by arguments it refuses as invalid)
-  if (coef) drop();
+// The argument checks of everything that takes the cell tables and the constraint lines (gmg_assemble_system_matrix[_coef],
+// gmg_assemble_rhs), on the host before any launch: the communicator, dim, sizes, NULL arrays (other_null: one of the caller's
+// own arrays of nonzero length is NULL), 32-bit device indices, line_ptr, masters, line indices, DoFs and levels.  lp32
+// receives line_ptr in 32 bits, max_line the longest line.
+static int check_cell_tables(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                             bool other_null, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master,
+                             const double *line_weight, std::vector<int32_t> &lp32, int64_t &max_line) {
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
   if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
   if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
   if (n_dofs < 0 || n_cells < 0 || n_lines < 0) return bad(GMG_ERR_INVALID, "negative size");
   const int nv = 1 << dim;
-  if ((n_cells > 0 && (!cell_dofs || !cell_level || (!coef && !K_of_level))) || (n_dofs > 0 && !constraint_of_dof) || (n_lines > 0 && !line_ptr))
+  if ((n_cells > 0 && (!cell_dofs || !cell_level)) || other_null || (n_dofs > 0 && !constraint_of_dof) || (n_lines > 0 && !line_ptr))
     return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
   if (n_dofs >= ((int64_t)1 << 31) || n_cells * nv >= ((int64_t)1 << 31) || n_lines >= ((int64_t)1 << 31))
     return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs, slots or lines");
-  std::vector<int32_t> lp32((size_t)n_lines + 1, 0);
-  int64_t max_line = 0;
+  lp32.assign((size_t)n_lines + 1, 0);
+  max_line = 0;
   if (n_lines > 0) {
     if (line_ptr[0] < 0) return bad(GMG_ERR_INVALID, "line_ptr starts below 0");
     for (int64_t l = 0; l < n_lines; ++l) {
@@ -3880,6 +3889,26 @@ static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n
     if (cell_level[c] > 15) return bad(GMG_ERR_INVALID, "cell level of 16 or more");
   // (32-bit slot lists: every slot goes to its DoF and to at most max_line masters)
   if (n_slots * (1 + max_line) >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 (row, slot) pairs");
+  return GMG_OK;
+}
+
+// both entries: coef == nullptr takes the per-level cell matrices K_of_level, otherwise K_of_level is unused
+static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                           const double *K_of_level, const AsmCoef *coef, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                           const int32_t *line_master, const double *line_weight, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  auto drop = [&] { reset_keep_halo(ctx->S); ctx->S_invd.reset(); ctx->S_tmp.reset(); };
+  // the coefficient form: whatever the context held goes first, so that after any failure it holds no system matrix (the
+  // cell-matrix form leaves the context untouched by arguments it refuses as invalid)
+  if (coef) drop();
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  std::vector<int32_t> lp32;
+  int64_t max_line = 0;
+  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level, n_cells > 0 && !coef && !K_of_level, constraint_of_dof, n_lines, line_ptr,
+                        line_master, line_weight, lp32, max_line));
+  const int nv = 1 << dim;
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
   if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
   DevCSR &m = ctx->S;
   drop();
@@ -3942,6 +3971,128 @@ int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, i
   const AsmCoef coef{nq, cell_coef, G, qw, scale_of_level, 16};
   return assemble_system(ctx, "gmg_assemble_system_matrix_coef", dim, n_dofs, n_cells, cell_dofs, cell_level, nullptr, &coef, constraint_of_dof, n_lines,
                          line_ptr, line_master, line_weight, build_ms);
+}
+
+// ---- the right-hand side from the cell tables, and constraints.distribute on the same tables (gmg_rhs_cells.hpp, DESIGN.md
+// section 19)
+
+int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                     const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master, const double *line_weight,
+                     const double *line_inhomogeneity, const double *K_of_level, int nq, const double *shape, const double *weight,
+                     const double *jxw_of_level, const double *source, double *rhs, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_assemble_rhs";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  std::vector<int32_t> lp32;
+  int64_t max_line = 0;
+  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level,
+                        !shape || !weight || !jxw_of_level || (n_dofs > 0 && !rhs) || (n_lines > 0 && !line_inhomogeneity), constraint_of_dof, n_lines,
+                        line_ptr, line_master, line_weight, lp32, max_line));
+  if (nq < 1 || nq > 512) return bad(GMG_ERR_INVALID, "nq must be in 1 .. 512");
+  if (!source && n_cells > 0 && (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq))
+    return bad(GMG_ERR_INVALID, "source is NULL and the device holds no densities of n_cells x nq (gmg_charge_density with dens = NULL)");
+  bool any_inhom = false;
+  for (int64_t l = 0; l < n_lines; ++l) any_inhom = any_inhom || line_inhomogeneity[l] != 0.0;
+  if (any_inhom && !K_of_level) return bad(GMG_ERR_INVALID, "K_of_level is NULL while a line_inhomogeneity is not 0");
+  (void)hipSetDevice(ctx->device);
+  const int nv = 1 << dim;
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
+  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
+  DevPtr<uint8_t> d_lv;
+  DevPtr<double> d_K, d_lw, d_li, d_src, d_F;
+  DevPtr<RhsArgs> d_ra;  // (the argument block of rhs_cell_kernel is 39 KB: it travels through memory)
+  AsmScratch w;
+  Event e0, e1;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+  if (any_inhom) HIPC(upload(d_K, K_of_level, (size_t)16 * nv * nv, ctx->stream));
+  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
+  HIPC(upload(d_lp, lp32, ctx->stream));
+  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_li, line_inhomogeneity, (size_t)n_lines, ctx->stream));
+  if (source) HIPC(upload(d_src, source, (size_t)n_cells * (size_t)nq, ctx->stream));
+  HIPC(d_F.alloc((size_t)std::max<int64_t>(n_slots, 1)));
+  RhsArgs ra{};
+  ra.dens = source ? d_src.get() : ctx->dens_dev.get(); ra.n_cells = n_cells; ra.nq = nq; ra.nv = nv; ra.cell_level = d_lv.get(); ra.F = d_F.get();
+  for (int q = 0; q < nq; ++q) {
+    ra.weight[q] = weight[q];
+    for (int i = 0; i < nv; ++i) ra.shape[q * 8 + i] = shape[q * nv + i];
+  }
+  for (int l = 0; l < 16; ++l) ra.jxw[l] = jxw_of_level[l];
+  HIPC(d_ra.alloc(1));
+  HIPC(hipMemcpyAsync(d_ra.get(), &ra, sizeof(RhsArgs), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  AsmArgs a{};
+  a.nv = nv; a.lg_nv = dim; a.max_line = (int)max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
+  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.cons = d_cons.get();
+  a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
+  int32_t n_inc = 0;
+  int rc = assemble_incidence<false>(ctx, a, w, n_inc);
+  if (rc != GMG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+  RhsCellsArgs r{};
+  r.nv = nv; r.lg_nv = dim; r.n_dofs = n_dofs; r.n_slots = n_slots; r.cell_dofs = d_cd.get(); r.cell_level = d_lv.get(); r.K = d_K.get();
+  r.cons = d_cons.get(); r.line_ptr = d_lp.get(); r.line_master = d_lm.get(); r.line_weight = d_lw.get(); r.line_inhom = d_li.get();
+  r.inc_ptr = a.inc_ptr; r.inc_slot = a.inc_slot; r.F = d_F.get(); r.rhs = rhs;
+  if (n_cells) hipLaunchKernelGGL(rhs_cell_kernel, asm_blocks(ctx, n_cells, kThreads), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_ra.get());
+  if (n_slots && any_inhom) hipLaunchKernelGGL(rhs_cells_dirichlet_kernel, asm_blocks(ctx, n_slots, 256), dim3(256), 0, ctx->stream, r);
+  if (n_dofs) hipLaunchKernelGGL(rhs_cells_gather_kernel, asm_blocks(ctx, n_dofs, 256), dim3(256), 0, ctx->stream, r);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(e1.get(), ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (the tables above live until the stream has run the kernels)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) { ctx->err = std::string(who) + ": " + hipGetErrorString(e); return GMG_ERR_HIP; }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] right-hand side from cell tables: %lld DoFs, %lld cells x %d points, %lld (row, slot) pairs, %.3f ms\n", (long long)n_dofs,
+                 (long long)n_cells, nq, (long long)n_inc, ms);
+  return GMG_OK;
+}
+
+int gmg_distribute_constraints(gmg_context *ctx, int64_t n_dofs, double *u, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                               const int32_t *line_master, const double *line_weight, const double *line_inhomogeneity) {
+  if (!ctx) return GMG_ERR_INVALID;
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string("gmg_distribute_constraints: ") + msg).c_str()); };
+  if (n_dofs < 0 || n_lines < 0) return bad(GMG_ERR_INVALID, "negative size");
+  if ((n_dofs > 0 && (!u || !constraint_of_dof)) || (n_lines > 0 && (!line_ptr || !line_inhomogeneity))) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_dofs >= ((int64_t)1 << 31) || n_lines >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs or lines");
+  std::vector<int32_t> lp32((size_t)n_lines + 1, 0);
+  if (n_lines > 0) {
+    if (line_ptr[0] < 0) return bad(GMG_ERR_INVALID, "line_ptr starts below 0");
+    for (int64_t l = 0; l < n_lines; ++l)
+      if (line_ptr[l + 1] < line_ptr[l]) return bad(GMG_ERR_INVALID, "line_ptr decreases");
+    if (line_ptr[n_lines] >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 line entries");
+    for (int64_t l = 0; l <= n_lines; ++l) lp32[(size_t)l] = (int32_t)line_ptr[l];
+  }
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0;
+  if (n_ent > 0 && (!line_master || !line_weight)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  for (int64_t d = 0; d < n_dofs; ++d)
+    if (constraint_of_dof[d] < -1 || constraint_of_dof[d] >= n_lines) return bad(GMG_ERR_INVALID, "line index outside [0, n_lines)");
+  for (int64_t e = n_lines > 0 ? line_ptr[0] : 0; e < n_ent; ++e) {
+    if (line_master[e] < 0 || line_master[e] >= n_dofs) return bad(GMG_ERR_INVALID, "master outside [0, n_dofs)");
+    // (the host loop runs in place and ascending: one thread per constrained DoF agrees with it only when no master is constrained)
+    if (constraint_of_dof[line_master[e]] >= 0) return bad(GMG_ERR_INVALID, "a master is itself constrained");
+  }
+  if (n_dofs == 0) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  DevPtr<int32_t> d_cons, d_lp, d_lm;
+  DevPtr<double> d_lw, d_li;
+  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
+  HIPC(upload(d_lp, lp32, ctx->stream));
+  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_li, line_inhomogeneity, (size_t)n_lines, ctx->stream));
+  hipLaunchKernelGGL(distribute_constraints_kernel, asm_blocks(ctx, n_dofs, 256), dim3(256), 0, ctx->stream, n_dofs, (const int32_t *)d_cons.get(),
+                     (const int32_t *)d_lp.get(), (const int32_t *)d_lm.get(), (const double *)d_lw.get(), (const double *)d_li.get(), u);
+  hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) { ctx->err = std::string("gmg_distribute_constraints: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
+  return GMG_OK;
 }
 
 int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {

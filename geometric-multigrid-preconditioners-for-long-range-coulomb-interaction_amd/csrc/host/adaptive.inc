@@ -326,23 +326,26 @@ int LaplaceProblem<dim>::estimate_error_device() {
   const EstimatorInputs in = estimator_inputs();
   sublap("estimate: face table, inputs");
   if (ensure_context() != GMG_OK) return GMG_ERR_HIP;
+  // (the solution the device kept after gmg_distribute_constraints, "RHS from cell tables"; otherwise a copy of the host's)
+  const double *u_dev = device_solution();
   double *d_u = nullptr;
-  if (gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u) != GMG_OK) { last_error = std::string("gmg_vec_alloc: ") + gmg_last_error(gmg); return GMG_ERR_HIP; }
+  if (!u_dev && gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u) != GMG_OK) { last_error = std::string("gmg_vec_alloc: ") + gmg_last_error(gmg); return GMG_ERR_HIP; }
   std::vector<float> eta(nc, 0.f);
   std::vector<double> kelly(nc, 0.0), res(nc, 0.0), fi(nc * 2 * dim, 0.0);
   std::vector<uint8_t> mark(nc, 0);
   double threshold = 0.0, build_ms = 0.0;
   int64_t n_marked = 0;
-  int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+  int rc = u_dev ? GMG_OK : gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+  if (!u_dev) u_dev = d_u;
   sublap("estimate: upload of u");
   if (rc == GMG_OK)
     rc = gmg_estimate_error(gmg, dim, (int64_t)nc, in.cell_dofs.data(), in.cell_level.data(), in.face_kind.data(), in.face_cell.data(),
                             in.h_of_level.data(), in.face_measure_of_level.data(), in.diameter_of_level.data(), (int)in.gauss_x.size(),
-                            in.gauss_x.data(), in.gauss_w.data(), d_u, (int64_t)solution.size(), in.residual, in.nq, in.weight.data(),
+                            in.gauss_x.data(), in.gauss_w.data(), u_dev, (int64_t)solution.size(), in.residual, in.nq, in.weight.data(),
                             in.jxw_of_level.data(), in.dens_resident || in.dens.empty() ? nullptr : in.dens.data(), in.fraction, eta.data(),
                             kelly.data(), res.data(), fi.data(), &threshold, mark.data(), &n_marked, &build_ms);
   if (rc != GMG_OK) last_error = std::string("gmg_estimate_error: ") + gmg_last_error(gmg);
-  gmg_vec_free(gmg, d_u);
+  if (d_u) gmg_vec_free(gmg, d_u);
   if (rc != GMG_OK) return rc;
   sublap("estimate: on device");
   if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
@@ -410,6 +413,7 @@ void LaplaceProblem<dim>::refine_grid(unsigned int cycle) {
       }
     }
   solution.assign(vertex_of_dof.size(), 0.0);
+  solution_on_device = false;
   for (size_t i = 0; i < vertex_of_dof.size(); ++i) solution[i] = value_of_vertex.at(vertex_of_dof[i]);
   set_zero_constraints(solution);  // :1119
   initial_guess = solution;

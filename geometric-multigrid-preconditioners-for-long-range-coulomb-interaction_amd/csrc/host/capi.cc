@@ -344,6 +344,27 @@ int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t
     return 0;
   });
 }
+// ---- "RHS from cell tables" (DESIGN.md section 19): what the driver hands to gmg_assemble_rhs beyond the arrays above.
+// sizes: nq, n_cells, 2^dim.  source: the charge densities as the host holds them, or rhs_function at the quadrature points
+int step50_rhs_from_cell_tables(step50_problem *h) { return DISPATCH(h, rhs_from_cells) ? 1 : 0; }
+int step50_rhs_assembly_sizes(step50_problem *h, int64_t sizes[3]) {
+  return guarded(h, [&] {
+    sizes[0] = (int64_t)DISPATCH(h, rhs_assembly_inputs(false).nq); sizes[1] = (int64_t)DISPATCH(h, active_cells.size());
+    sizes[2] = (int64_t)1 << h->dim;
+    return 0;
+  });
+}
+int step50_rhs_assembly_inputs(step50_problem *h, double *shape, double *weight, double *jxw_of_level, double *source) {
+  return guarded(h, [&] {
+    auto fill = [&](auto &P) {
+      const auto in = P.rhs_assembly_inputs(true);
+      auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+      put(in.shape, shape); put(in.weight, weight); put(in.jxw_of_level, jxw_of_level); put(in.source, source);
+    };
+    if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+    return 0;
+  });
+}
 // ---- "Level matrices on device" (DESIGN.md section 17): what the driver hands to gmg_assemble_level_matrix for one level of
 // the current mesh.  sizes: dim, n_dofs, n_cells
 int step50_level_matrices_on_device(step50_problem *h) { return DISPATCH(h, levels_on_device) ? 1 : 0; }

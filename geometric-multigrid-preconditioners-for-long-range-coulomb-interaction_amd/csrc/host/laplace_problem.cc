@@ -247,6 +247,11 @@ void ParameterReader::declare_parameters() {
             {"Transfer matrices on device", "true"},
             // the right-hand side integrated on the device from densities that stay there (gmg_rhs_assemble)
             {"RHS on device", "true"},
+            // the right-hand side formed on the device from the cell tables the matrix assembly takes (gmg_assemble_rhs) instead
+            // of the sequential cell loop and its gather plan, and constraints.distribute of the solution on the device
+            // (gmg_distribute_constraints), whose vector the estimator, the forces and the error norm then take; cycles that
+            // run on the device, one rank, DESIGN.md section 19
+            {"RHS from cell tables", "false"},
             // the short-ranged pair sum over the pairs closer than this many smoothing lengths, found through
             // cell bins (erfc(6) = 2e-17: beyond 6 r_c a pair contributes nothing in double precision); 0 = all pairs as the
             // reference (:1325-1332).  With it the energy is also evaluated for the large systems the reference skips (:1554).
@@ -334,6 +339,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.estimator_on_device = prm.get_bool("Error estimator on device");
   p.transfer_on_device = prm.get_bool("Transfer matrices on device");
   p.rhs_on_device = prm.get_bool("RHS on device");
+  p.rhs_from_cell_tables = prm.get_bool("RHS from cell tables");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
   p.compute_forces = prm.get_bool("Compute forces");
@@ -793,6 +799,7 @@ void LaplaceProblem<dim>::setup_system(unsigned int cycle) {
   distribute_dofs();
   const int64_t n = (int64_t)vertex_of_dof.size();
   solution.assign((size_t)n, 0.0);
+  solution_on_device = false;
   system_rhs.assign((size_t)n, 0.0);
   if (cycle == 0 && par.flag_rhs_assembly && lammpsinput) rhs_assembly_optimization();
   sublap("rhs_assembly_optimization");
@@ -1019,13 +1026,21 @@ typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_a
     for (int i = 0; i < nv; ++i)
       for (int j = 0; j < nv; ++j) in.K_of_level[((size_t)l * nv + (size_t)i) * nv + (size_t)j] = K[i][j];
   }
-  in.line_ptr.assign(constraint_lines.size() + 1, 0);
-  for (size_t l = 0; l < constraint_lines.size(); ++l) {
-    in.line_ptr[l + 1] = in.line_ptr[l] + (int64_t)constraint_lines[l].entries.size();
-    in.line_inhomogeneity.push_back(constraint_lines[l].inhomogeneity);
-    for (auto &e : constraint_lines[l].entries) { in.line_master.push_back(e.first); in.line_weight.push_back(e.second); }
-  }
+  line_tables(in.line_ptr, in.line_master, in.line_weight, in.line_inhomogeneity);
   return in;
+}
+
+// the constraint lines in the CSR form the device entries take (a Dirichlet line has no entries)
+template <int dim>
+void LaplaceProblem<dim>::line_tables(std::vector<int64_t> &line_ptr, std::vector<int32_t> &line_master, std::vector<double> &line_weight,
+                                      std::vector<double> &line_inhomogeneity) const {
+  line_ptr.assign(constraint_lines.size() + 1, 0);
+  line_master.clear(); line_weight.clear(); line_inhomogeneity.clear();
+  for (size_t l = 0; l < constraint_lines.size(); ++l) {
+    line_ptr[l + 1] = line_ptr[l] + (int64_t)constraint_lines[l].entries.size();
+    line_inhomogeneity.push_back(constraint_lines[l].inhomogeneity);
+    for (auto &e : constraint_lines[l].entries) { line_master.push_back(e.first); line_weight.push_back(e.second); }
+  }
 }
 
 // what the coefficient form takes beyond the cell tables: the quadrature's tables and, filled by the callers below, the
@@ -1163,6 +1178,9 @@ void LaplaceProblem<dim>::assemble_system() {
   if (system_on_device) { system_matrix = CSRMatrix(); sublap(nullptr); }
   else assemble_system_matrix_host();
   system_rhs.assign((size_t)n, 0.0);
+  // "RHS from cell tables": no cell loop and no plan here, gmg_assemble_rhs forms the vector from the cell tables
+  rhs_from_cells = decide_rhs_from_cell_tables();
+  if (rhs_from_cells) { assemble_rhs_from_cell_tables(); return; }
   // "RHS on device": the cell loop records WHERE every F_i goes (DoF, slot = cell * 2^dim + i, weight) and which Dirichlet
   // terms it loses instead of forming F from densities the host does not have; gmg_rhs_assemble does the arithmetic
   const bool rhs_dev = lammpsinput && densities_device_resident;
@@ -1259,6 +1277,101 @@ void LaplaceProblem<dim>::assemble_system() {
     gmg_vec_free(gmg, d_out);
     sublap("assemble: rhs on device");
   }
+}
+
+// Is this cycle's right-hand side one gmg_assemble_rhs forms?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_rhs_from_cell_tables() {
+  if (!par.rhs_from_cell_tables) return false;
+  bool any_inhom = false;
+  for (auto &l : constraint_lines) any_inhom = any_inhom || l.inhomogeneity != 0.0;
+  const char *why = !solve_on_device_requested                    ? "the cycle does not run on the device"
+                    : distributed                                 ? "the run is distributed"
+                    : lammpsinput && !densities_device_resident   ? "the charge densities are not on the device"
+                    : par.Problemtype == "Step16" && any_inhom    ? "variable coefficient with a nonzero boundary value"
+                                                                  : nullptr;
+  if (!why) return true;
+  if (!rhs_cells_fallback_reported) pcout(std::string("   RHS from cell tables: not applicable (") + why + "), assembled on the host");
+  rhs_cells_fallback_reported = true;
+  return false;
+}
+
+// the tables of the right-hand side's quadrature as assemble_system uses them, and (with_source) the integrand per cell
+template <int dim>
+typename LaplaceProblem<dim>::RhsAssemblyInputs LaplaceProblem<dim>::rhs_assembly_inputs(bool with_source) {
+  constexpr int nv = 1 << dim;
+  const Quadrature<dim> q_rhs((int)(par.degree + par.quadrature_degree_rhs));
+  RhsAssemblyInputs in;
+  const size_t nq = q_rhs.p.size();
+  in.nq = (int)nq;
+  in.shape.resize(nq * nv);
+  in.weight.assign(q_rhs.w.begin(), q_rhs.w.end());
+  for (size_t q = 0; q < nq; ++q)
+    for (int i = 0; i < nv; ++i) in.shape[q * nv + (size_t)i] = q_rhs.shape[q][(size_t)i];
+  in.jxw_of_level.resize(16);
+  for (int l = 0; l < 16; ++l) in.jxw_of_level[(size_t)l] = std::pow(triangulation.cell_size(l), dim);
+  if (!with_source) return in;
+  const int64_t nc = (int64_t)active_cells.size();
+  in.source.resize((size_t)nc * nq);
+  if (lammpsinput) {
+    ensure_host_densities();
+    if (density_values_for_each_cell.size() != (size_t)nc) throw std::runtime_error("rhs_assembly_inputs: the charge densities are not those of this mesh");
+    for (int64_t ci = 0; ci < nc; ++ci)
+      if (density_values_for_each_cell[(size_t)ci].size() != nq) throw std::runtime_error("rhs_assembly_inputs: the charge densities are not those of this quadrature");
+    for (int64_t ci = 0; ci < nc; ++ci) std::copy(density_values_for_each_cell[(size_t)ci].begin(), density_values_for_each_cell[(size_t)ci].end(), in.source.begin() + (std::ptrdiff_t)((size_t)ci * nq));
+    return in;
+  }
+#pragma omp parallel for schedule(static)
+  for (int64_t ci = 0; ci < nc; ++ci) {
+    const auto &ac = active_cells[(size_t)ci];
+    const double h = triangulation.cell_size(ac.level);
+    double x0[3];
+    triangulation.cell_origin(ac.level, triangulation.levels[(size_t)ac.level][(size_t)ac.index], x0);
+    for (size_t q = 0; q < nq; ++q) {
+      double x[3] = {0, 0, 0};
+      for (int d = 0; d < dim; ++d) x[d] = x0[d] + h * q_rhs.p[q][(size_t)d];
+      in.source[(size_t)ci * nq + q] = rhs_function(x);
+    }
+  }
+  return in;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::assemble_rhs_from_cell_tables() {
+  auto chk = [&](int rc, const char *what) { if (rc != GMG_OK) throw std::runtime_error(std::string(what) + ": " + (gmg ? gmg_last_error(gmg) : last_error.c_str())); };
+  chk(ensure_context(), "RHS from cell tables");
+  const int64_t n = (int64_t)vertex_of_dof.size();
+  SystemAssemblyInputs in = system_assembly_inputs();
+  // GaussianCharges: the densities gmg_charge_density left on the device (source = NULL); otherwise the function's values
+  const RhsAssemblyInputs r = rhs_assembly_inputs(!lammpsinput);
+  const bool constant_coef = par.Problemtype != "Step16";  // (K_of_level is the constant-coefficient cell matrix: decide_rhs_from_cell_tables)
+  double *d_out = nullptr, build_ms = 0.0;
+  chk(gmg_vec_alloc(gmg, n, &d_out), "gmg_vec_alloc");
+  int rc = gmg_assemble_rhs(gmg, dim, n, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(), constraint_of_dof.data(),
+                            (int64_t)constraint_lines.size(), in.line_ptr.data(), in.line_master.data(), in.line_weight.data(),
+                            in.line_inhomogeneity.data(), constant_coef ? in.K_of_level.data() : nullptr, r.nq, r.shape.data(), r.weight.data(),
+                            r.jxw_of_level.data(), lammpsinput ? nullptr : r.source.data(), d_out, &build_ms);
+  if (rc == GMG_OK) rc = gmg_vec_download(gmg, system_rhs.data(), d_out, n);
+  gmg_vec_free(gmg, d_out);
+  chk(rc, "gmg_assemble_rhs");
+  // the line tables stay for gmg_distribute_constraints after this cycle's solves
+  cycle_line_tables = SystemAssemblyInputs();
+  cycle_line_tables.line_ptr.swap(in.line_ptr); cycle_line_tables.line_master.swap(in.line_master);
+  cycle_line_tables.line_weight.swap(in.line_weight); cycle_line_tables.line_inhomogeneity.swap(in.line_inhomogeneity);
+  sublap("assemble: rhs from cell tables");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+}
+
+// constraints.distribute of a device vector with this cycle's lines (gmg_distribute_constraints)
+template <int dim>
+int LaplaceProblem<dim>::distribute_constraints_on_device(double *d_u) {
+  // (the tables assemble_rhs_from_cell_tables kept for this cycle: repeated solves of one cycle build nothing)
+  const SystemAssemblyInputs &t = cycle_line_tables;
+  if (t.line_ptr.size() != constraint_lines.size() + 1) { last_error = "gmg_distribute_constraints: no line tables of this cycle"; return GMG_ERR_INVALID; }
+  const int rc = gmg_distribute_constraints(gmg, (int64_t)constraint_of_dof.size(), d_u, constraint_of_dof.data(), (int64_t)constraint_lines.size(),
+                                            t.line_ptr.data(), t.line_master.data(), t.line_weight.data(), t.line_inhomogeneity.data());
+  if (rc != GMG_OK) last_error = std::string("gmg_distribute_constraints: ") + gmg_last_error(gmg);
+  return rc;
 }
 
 template <int dim>
@@ -1495,6 +1608,7 @@ int LaplaceProblem<dim>::upload() {
     for (double *p : {d_solution, d_rhs, d_full})
       if (p) gmg_vec_free(gmg, p);
     d_solution = d_rhs = d_full = nullptr;
+    solution_on_device = false;
     GMGC(gmg_reset(gmg, L));
   } else {
     GMGC(gmg_reset(gmg, L));  // the context may have been created early (charge densities) with 1 level
@@ -1737,7 +1851,11 @@ int LaplaceProblem<dim>::solve_on_device(CycleReport &rep) {
   if (rc != GMG_OK) { last_error = std::string("solve: ") + gmg_last_error(gmg); return rc; }
   GMGC(gmg_vec_norms(gmg, d_solution, d_n, &rep.sol_l1, &rep.sol_l2, &rep.sol_linf));  // :1012-1014
   GMGC(gmg_vec_allgather(gmg, (int64_t)solution.size(), d_full, d_solution));  // every rank keeps the whole solution
+  // "RHS from cell tables": constraints.distribute (:1016) on the device before the one download; d_full then stays the
+  // solution for the estimator, the forces and the error norm (device_solution) until the next cycle
+  if (rhs_from_cells) GMGC(distribute_constraints_on_device(d_full));
   GMGC(gmg_vec_download(gmg, solution.data(), d_full, (int64_t)solution.size()));
+  solution_on_device = rhs_from_cells;
   return GMG_OK;
 }
 
@@ -1769,7 +1887,7 @@ int LaplaceProblem<dim>::solve() {
   pcout("   L1 solution norm " + fmt("%.10e", rep.sol_l1));
   pcout("   L2 solution norm " + fmt("%.10e", rep.sol_l2));
   pcout("   LInfinity solution norm " + fmt("%.10e", rep.sol_linf));
-  distribute_constraints(solution);  // :1016
+  if (!solution_on_device) distribute_constraints(solution);  // :1016 (else: done on the device before the download)
   return GMG_OK;
 }
 
@@ -1959,14 +2077,16 @@ int LaplaceProblem<dim>::atom_forces(bool on_device, double cutoff, std::vector<
     GMGC(ensure_context());
     GMGC(gmg_set_point_locator(gmg, n0, origin, triangulation.h0, (int64_t)node.size(), node.data(), (int64_t)active_cells.size(),
                                active_cell_dof_table.data()));
+    const double *u_dev = device_solution();  // ("RHS from cell tables": the device kept the distributed solution)
     double *d_u = nullptr;
-    GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
-    int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (!u_dev) GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
+    int rc = u_dev ? GMG_OK : gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (!u_dev) u_dev = d_u;
     if (rc == GMG_OK)
-      rc = gmg_atom_forces(gmg, n, atom_positions.data(), charges.data(), d_u, (int64_t)solution.size(), par.r_c, cutoff, data(phi),
+      rc = gmg_atom_forces(gmg, n, atom_positions.data(), charges.data(), u_dev, (int64_t)solution.size(), par.r_c, cutoff, data(phi),
                            data(field), data(force), data(force_short), data(e_short));
     if (rc != GMG_OK) last_error = std::string("gmg_atom_forces: ") + gmg_last_error(gmg);
-    gmg_vec_free(gmg, d_u);
+    if (d_u) gmg_vec_free(gmg, d_u);
     return rc;
   }
   // host mirror: the same per-atom functions (gmg_forces.hpp), one atom per iteration
@@ -2103,15 +2223,17 @@ int LaplaceProblem<dim>::energy_norm_error(bool on_device, double *error, std::v
     }
   if (on_device) {
     GMGC(ensure_context());
+    const double *u_dev = device_solution();  // ("RHS from cell tables": the device kept the distributed solution)
     double *d_u = nullptr;
-    GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
-    int rc = gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (!u_dev) GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
+    int rc = u_dev ? GMG_OK : gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
+    if (!u_dev) u_dev = d_u;
     if (rc == GMG_OK)
-      rc = gmg_energy_norm_error(gmg, nc, lo.data(), hh.data(), active_cell_dof_table.data(), d_u, (int64_t)solution.size(), n,
+      rc = gmg_energy_norm_error(gmg, nc, lo.data(), hh.data(), active_cell_dof_table.data(), u_dev, (int64_t)solution.size(), n,
                                  atom_positions.data(), charges.data(), par.r_c, nq, qp.data(), quad.w.data(), sg.data(), error,
                                  cell_err2 ? ce.data() : nullptr);
     if (rc != GMG_OK) last_error = std::string("gmg_energy_norm_error: ") + gmg_last_error(gmg);
-    gmg_vec_free(gmg, d_u);
+    if (d_u) gmg_vec_free(gmg, d_u);
     if (rc == GMG_OK && cell_err2) cell_err2->swap(ce);
     return rc;
   }
@@ -2312,6 +2434,7 @@ void LaplaceProblem<dim>::finish_cycle() {
 template <int dim>
 void LaplaceProblem<dim>::set_solution(const std::vector<double> &x) {
   solution = x;
+  solution_on_device = false;
   distribute_constraints(solution);
 }
 

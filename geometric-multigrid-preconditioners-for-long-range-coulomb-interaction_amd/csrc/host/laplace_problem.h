@@ -80,6 +80,7 @@ struct Parameters {
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (one rank; Step16: the _coef entry)
   bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
+  bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
@@ -134,6 +135,23 @@ class LaplaceProblem {
     std::vector<int64_t> line_ptr;
   };
   SystemAssemblyInputs system_assembly_inputs() const;
+  void line_tables(std::vector<int64_t> &line_ptr, std::vector<int32_t> &line_master, std::vector<double> &line_weight,
+                   std::vector<double> &line_inhomogeneity) const;  // the constraint lines in CSR form
+  SystemAssemblyInputs cycle_line_tables;  // "RHS from cell tables": the line tables of this cycle, kept for gmg_distribute_constraints
+  // what gmg_assemble_rhs takes beyond them: the tables of the right-hand side's quadrature and the
+  // integrand at the quadrature points of every active cell -- the charge densities as the host holds them, or
+  // rhs_function(x0 + h p_q) (filled one cell per iteration: the values do not depend on the number of threads)
+  struct RhsAssemblyInputs {
+    int nq = 0;
+    std::vector<double> shape, weight, jxw_of_level;  // [nq][nv], [nq], [16]
+    std::vector<double> source;                       // [n_cells][nq]
+  };
+  RhsAssemblyInputs rhs_assembly_inputs(bool with_source = true);
+  bool decide_rhs_from_cell_tables();                                    // right-hand side formed by gmg_assemble_rhs?
+  void assemble_rhs_from_cell_tables();                                  // system_rhs through gmg_assemble_rhs
+  int distribute_constraints_on_device(double *d_u);                     // gmg_distribute_constraints with this cycle's lines
+  // the distributed solution as the device holds it after a solve with "RHS from cell tables" (nullptr: upload `solution`)
+  const double *device_solution() const { return solution_on_device ? d_full : nullptr; }
   void assemble_multigrid();                                             // :835-933
   void assemble_level(int l);                                            // one level's matrix + interface matrix (:869-931)
   void ensure_level_matrix(int l);                                       // assemble a level that was left to the device, on demand
@@ -224,6 +242,9 @@ class LaplaceProblem {
   bool levels_on_device = false;           // this cycle's level and interface matrices are formed by gmg_assemble_level_matrix at upload()
   bool levels_fallback_reported = false;   // "Level matrices on device" was set but not applicable: said once
   bool system_fallback_reported = false;   // "System matrix on device" was set but not applicable: said once
+  bool rhs_from_cells = false;             // this cycle's right-hand side was formed by gmg_assemble_rhs
+  bool rhs_cells_fallback_reported = false;  // "RHS from cell tables" was set but not applicable: said once
+  bool solution_on_device = false;         // d_full holds `solution` as constraints.distribute left it (gmg_distribute_constraints)
   bool coarse_fallback_reported = false;   // "Coarse solver = direct" was set but not applicable: said once
   bool densities_device_resident = false;  // compute_charge_densities left them in HBM for gmg_rhs_assemble
   double build_matrices_ms = 0.0;  // device time of gmg_build_transfer for the current cycle's operators

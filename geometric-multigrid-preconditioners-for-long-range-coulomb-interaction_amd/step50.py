@@ -86,6 +86,7 @@ def prm_text(**kw) -> str:
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
         "system_matrix_on_device": ("Misc", "System matrix on device"),
         "level_matrices_on_device": ("Misc", "Level matrices on device"),
+        "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
@@ -346,6 +347,22 @@ class Problem:
                                            lambda *a: self.L.step50_level_coefficient_inputs(self.h, C.c_int(level), *a),
                                            "level_coefficient_inputs")
         return SimpleNamespace(**vars(self.level_assembly_inputs(level)), **new, scale=float(sc[0]))
+
+    def rhs_assembly_inputs(self):
+        """The arrays the driver hands to gmg_assemble_rhs for the current mesh: the fields of system_assembly_inputs() plus nq,
+        shape [nq, 2^dim], weight [nq], jxw_of_level [16] and source [n_cells, nq]: the integrand at the quadrature points of
+        every active cell -- the charge densities as the host forms them, or Step16's function values."""
+        sz = (C.c_int64 * 3)()
+        self._chk(self.L.step50_rhs_assembly_sizes(self.h, sz), "rhs_assembly_inputs")
+        nq, n_cells, nv = (int(v) for v in sz)
+        sh, w, jxw, src = np.zeros((nq, nv)), np.zeros(nq), np.zeros(16), np.zeros((n_cells, nq))
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self.L.step50_rhs_assembly_inputs(self.h, P(sh), P(w), P(jxw), P(src)), "rhs_assembly_inputs")
+        return SimpleNamespace(**vars(self.system_assembly_inputs()), nq=nq, shape=sh, weight=w, jxw_of_level=jxw, source=src)
+
+    def rhs_from_cell_tables(self) -> bool:
+        """Did the last assembly form the right-hand side through gmg_assemble_rhs?"""
+        return bool(self.L.step50_rhs_from_cell_tables(self.h))
 
     def device_system_matrix(self):
         """The system matrix as the device holds it after a cycle with "System matrix on device" (gmg_get_system_matrix)."""

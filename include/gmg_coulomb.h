@@ -370,6 +370,47 @@ int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, i
                                     const uint8_t *cell_level, int nq, const double *cell_coef, const double *G, const double *qw,
                                     const double *scale_of_level, const int32_t *constraint_of_dof, int64_t n_lines,
                                     const int64_t *line_ptr, const int32_t *line_master, const double *line_weight, double *build_ms);
+/* The right-hand side of LaplaceProblem::assemble_system formed on the device from the cell tables, without a host plan
+ * (gmg_rhs_assemble wants gather lists that the host walks every cell to build): cell_dofs, cell_level, constraint_of_dof and
+ * the lines are exactly what gmg_assemble_system_matrix takes, nv = 2^dim; new are line_inhomogeneity [n_lines], the
+ * quadrature's tables shape [nq][nv], weight [nq], jxw_of_level [16] and the integrand at the quadrature points, source
+ * [n_cells][nq] on the host (the driver's Step16 passes rhs_function(x0 + h p_q)), or source == NULL: the densities rho that
+ * gmg_charge_density(..., dens = NULL) left on the device, which must be n_cells x nq.  K_of_level [16][nv][nv] may be NULL
+ * when every line_inhomogeneity is 0.0.  rhs: a device vector of n_dofs entries.
+ * Definition -- fp64, no contraction into fused multiply-adds, no floating-point atomics: every output is one sequential sum
+ * formed by one lane, so the bits do not depend on the launch shape (option assemble_max_blocks).  With l = cell_level[c],
+ * d_i = cell_dofs[c][i] and line(i) the line of d_i or none:
+ *   1. per slot s = c * nv + i:   F[s] = +0.0;   for q ascending:   F[s] += ((shape[q][i] * rho[c][q]) * weight[q]) * jxw_of_level[l]
+ *      (the operand order of gmg_rhs_assemble);
+ *   2. then, for j ascending over the vertices of c whose line has line_inhomogeneity != 0.0:
+ *        F[s] = F[s] - K_of_level[l][i][j] * line_inhomogeneity[line(j)]      -- for every i, constrained or not;
+ *   3. per DoF d:   rhs[d] = +0.0;   over the slots s = (c, i) in ascending order:   if d_i is unconstrained and d_i == d:
+ *        rhs[d] += F[s];   if d_i has a line: for its entries e in stored order with line_master[e] == d:
+ *        rhs[d] += line_weight[e] * F[s].   A line without entries (Dirichlet) passes nothing on; a DoF that receives nothing
+ *      holds +0.0.
+ * These are the bits of system_rhs after LaplaceProblem::assemble_system on either of its paths (the per-DoF order is (cell,
+ * vertex, entry), what the stable counting sort of the gmg_rhs_assemble plan produces).  build_ms (may be NULL): device time.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a DoF or master outside
+ * [0, n_dofs), a line index outside [0, n_lines), a line_ptr that starts below 0 or decreases, a level of 16 or more, nq
+ * outside 1 .. 512, a NULL array of nonzero length, source == NULL without device densities of n_cells x nq, or K_of_level ==
+ * NULL while some line_inhomogeneity != 0.0.  GMG_ERR_UNSUPPORTED on a context with a communicator and for sizes beyond
+ * 32-bit device indices.  rhs is not touched after a refusal.  Zero cells are valid: rhs is all +0.0.                     */
+int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                     const uint8_t *cell_level, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                     const int32_t *line_master, const double *line_weight, const double *line_inhomogeneity,
+                     const double *K_of_level /* [16][nv][nv] or NULL */, int nq, const double *shape /* [nq][nv] */,
+                     const double *weight /* [nq] */, const double *jxw_of_level /* [16] */,
+                     const double *source /* [n_cells][nq] or NULL */, double *rhs /* device vector, n_dofs */, double *build_ms);
+/* constraints.distribute on the same constraint tables (LaplaceProblem::distribute_constraints), in place on the device vector
+ * u [n_dofs]: for every constrained d with line l
+ *   v = line_inhomogeneity[l];   for the entries e in stored order:   v += line_weight[e] * u[line_master[e]];   u[d] = v
+ * (fp64, no contraction), one thread per constrained DoF.  The host loop runs in place and ascending, so the two agree only
+ * when no master is itself constrained: the entry checks that on the host.  GMG_ERR_INVALID -- before anything is launched, u
+ * untouched -- for a constrained master, a master or line index out of range, a line_ptr that starts below 0 or decreases,
+ * or a NULL array of nonzero length; GMG_ERR_UNSUPPORTED beyond 32-bit device indices.                                  */
+int gmg_distribute_constraints(gmg_context *ctx, int64_t n_dofs, double *u /* device, in place */,
+                               const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                               const int32_t *line_master, const double *line_weight, const double *line_inhomogeneity);
 /* The CSR of the system matrix as the device holds it (after gmg_assemble_system_matrix; gmg_set_system_matrix keeps no CSR
  * copy: GMG_ERR_UNSUPPORTED): with rowptr == NULL only the sizes are returned.                                         */
 int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val);
