@@ -28,6 +28,7 @@ SYMBOLS = [
     "gmg_assemble_system_matrix", "gmg_get_system_matrix", "gmg_system_matrix_norms",
     "gmg_assemble_level_matrix", "gmg_get_level_matrix", "gmg_assemble_system_matrix_coef", "gmg_assemble_level_matrix_coef",
     "gmg_assemble_rhs", "gmg_distribute_constraints",
+    "gmg_build_mesh_tables", "gmg_get_mesh_tables", "gmg_get_mesh_level_tables",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -197,6 +198,56 @@ class Context:
         self._chk(self.L.gmg_get_transfer(self.h, C.c_int(level), C.c_int(1 if transposed else 0), C.byref(nr), C.byref(nc), C.byref(nz),
                                           _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double)))
         return SimpleNamespace(n_rows=nr.value, n_cols=nc.value, nnz=nz.value, rowptr=rp, col=col[:nz.value], val=val[:nz.value])
+
+    def build_mesh_tables(self, dim, n0, level_ptr, cell_coord, cell_first_child, level0_lexicographic=True, n_levels=None):
+        """DoF numbering, constraints and level flags from the forest (gmg_build_mesh_tables); the tables stay on the device
+        (get_mesh_tables, get_mesh_level_tables).  None for an array passes NULL.  Returns the device time in ms."""
+        def opt(a, dt, ct):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=dt)
+            return a, _p(a, ct)
+        lp, lp_p = opt(level_ptr, np.int64, C.c_int64)
+        cc, cc_p = opt(cell_coord, np.int32, C.c_int32)
+        fc, fc_p = opt(cell_first_child, np.int32, C.c_int32)
+        n03 = None if n0 is None else (C.c_int32 * 3)(*[int(v) for v in n0])
+        if n_levels is None:
+            n_levels = len(lp) - 1
+        ms = C.c_double(0)
+        self.mesh_dim = int(dim)
+        self._chk(self.L.gmg_build_mesh_tables(self.h, C.c_int(int(dim)), n03, C.c_int(int(n_levels)), lp_p, cc_p, fc_p, C.c_int(1 if level0_lexicographic else 0),
+                                               C.byref(ms)))
+        return ms.value
+
+    def _mesh_dim(self, dim):
+        dim = getattr(self, "mesh_dim", None) if dim is None else dim
+        if dim not in (2, 3):
+            raise ValueError("the dimension of the mesh tables is not known to this view: pass dim")
+        return dim
+
+    def get_mesh_tables(self, dim=None):
+        """The active-mesh tables of the last build_mesh_tables as numpy arrays (dim: only for a view of a context whose
+        tables were built elsewhere)"""
+        from types import SimpleNamespace
+        n = [C.c_int64(0) for _ in range(5)]
+        self._chk(self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], None, None, None, None, None, None, None, None))
+        nc, nd, nh, nl, ne = [v.value for v in n]
+        cd = np.zeros(nc << self._mesh_dim(dim), dtype=np.int32)
+        lv, vk, cons = np.zeros(nc, dtype=np.uint8), np.zeros(nd, dtype=np.uint64), np.zeros(nd, dtype=np.int32)
+        lp, lm, lw, ld = np.zeros(nl + 1, dtype=np.int64), np.zeros(ne, dtype=np.int32), np.zeros(ne), np.zeros(nl, dtype=np.int32)
+        self._chk(self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], _p(cd, C.c_int32), _p(lv, C.c_uint8), _p(vk, C.c_uint64), _p(cons, C.c_int32),
+                                             _p(lp, C.c_int64), _p(lm, C.c_int32), _p(lw, C.c_double), _p(ld, C.c_int32)))
+        return SimpleNamespace(n_cells=nc, n_dofs=nd, n_hanging=nh, n_lines=nl, n_entries=ne, cell_dofs=cd, cell_level=lv, vertex_of_dof=vk,
+                               constraint_of_dof=cons, line_ptr=lp, line_master=lm, line_weight=lw, line_dof=ld)
+
+    def get_mesh_level_tables(self, level, dim=None):
+        """One level's tables of the last build_mesh_tables as numpy arrays"""
+        from types import SimpleNamespace
+        nc, nd = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_mesh_level_tables(self.h, C.c_int(int(level)), C.byref(nc), C.byref(nd), None, None, None))
+        cd, vk, fl = np.zeros(nc.value << self._mesh_dim(dim), dtype=np.int32), np.zeros(nd.value, dtype=np.uint64), np.zeros(nd.value, dtype=np.uint8)
+        self._chk(self.L.gmg_get_mesh_level_tables(self.h, C.c_int(int(level)), C.byref(nc), C.byref(nd), _p(cd, C.c_int32), _p(vk, C.c_uint64), _p(fl, C.c_uint8)))
+        return SimpleNamespace(n_cells=nc.value, n_dofs=nd.value, cell_dofs=cd, vertex_of_dof=vk, dof_flags=fl)
 
     def set_copy_indices(self, level, global_idx, level_idx):
         g = np.ascontiguousarray(global_idx, dtype=np.int32)

@@ -23,6 +23,7 @@
 #include "gmg_rhs_cells.hpp"
 #include "gmg_estimate.hpp"
 #include "gmg_fastdiag.hpp"
+#include "gmg_mesh_tables.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -147,6 +148,24 @@ struct FastDiag {
   DevPtr<double> t1, t2;  // level-0 vectors between the passes
 };
 
+// what gmg_build_mesh_tables leaves on the device (gmg_mesh_tables.hpp): valid until the next build, gmg_reset or gmg_destroy
+struct MeshTables {
+  bool valid = false;
+  int dim = 0;
+  int64_t n_cells = 0, n_dofs = 0, n_hanging = 0, n_lines = 0, n_entries = 0;  // active cells, active DoFs, lines, line entries
+  DevPtr<int32_t> cell_dofs, constraint_of_dof, line_ptr, line_master, line_dof;
+  DevPtr<uint8_t> cell_level;
+  DevPtr<unsigned long long> vertex_of_dof;
+  DevPtr<double> line_weight;
+  struct PerLevel {
+    int64_t n_cells = 0, n_dofs = 0;
+    DevPtr<int32_t> cell_dofs;
+    DevPtr<unsigned long long> vertex_of_dof;
+    DevPtr<uint8_t> dof_flags;
+  };
+  std::vector<PerLevel> level;
+};
+
 }  // namespace
 
 struct gmg_context {
@@ -236,6 +255,7 @@ struct gmg_context {
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
+  MeshTables mesh;              // gmg_build_mesh_tables: the tables of the last build
   int estimate_max_blocks = 0;  // gmg_estimate.hpp: the same cap for the estimator's kernels (option "estimate_max_blocks"); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
@@ -2725,6 +2745,13 @@ int upload_coef(gmg_context *ctx, const AsmCoef &k, int64_t n_cells, int nv, Asm
   return GMG_OK;
 }
 
+// device -> host copy of n elements on the context's stream (not waited for); a null destination is skipped
+template <class T>
+hipError_t mesh_fetch(gmg_context *ctx, T *dst, const DevPtr<T> &src, int64_t n) {
+  if (!dst || n <= 0) return hipSuccess;
+  return hipMemcpyAsync(dst, src.get(), sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
+}
+
 DevCSR *which_matrix(gmg_context *ctx, int which) {
   if (which == GMG_SYSTEM) return &ctx->S;
   if (which < 0 || which >= ctx->n_levels) return nullptr;
@@ -2802,6 +2829,7 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   HIPC(hipStreamSynchronize(ctx->stream));
   release_operators(ctx);
   free_locator(ctx);
+  ctx->mesh = MeshTables();
   ctx->n_levels = n_levels;
   ctx->lv.clear();
   ctx->lv.resize((size_t)n_levels);
@@ -3971,6 +3999,267 @@ int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, i
   const AsmCoef coef{nq, cell_coef, G, qw, scale_of_level, 16};
   return assemble_system(ctx, "gmg_assemble_system_matrix_coef", dim, n_dofs, n_cells, cell_dofs, cell_level, nullptr, &coef, constraint_of_dof, n_lines,
                          line_ptr, line_master, line_weight, build_ms);
+}
+
+// ---- DoF numbering, constraints and level flags from the forest (gmg_mesh_tables.hpp)
+
+int gmg_build_mesh_tables(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                          const int32_t *cell_first_child, int level0_lexicographic, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  ctx->mesh = MeshTables();  // after any failure the context holds no mesh tables
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string("gmg_build_mesh_tables: ") + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_levels < 0 || n_levels > kMtShift + 1) return bad(GMG_ERR_INVALID, "between 0 and 13 levels");
+  if (!n0 || !level_ptr) return bad(GMG_ERR_INVALID, "n0 or level_ptr is NULL");
+  for (int d = 0; d < dim; ++d)
+    if (n0[d] < 1 || n0[d] > 511) return bad(GMG_ERR_INVALID, "n0 outside 1 .. 511");
+  if (level_ptr[0] != 0) return bad(GMG_ERR_INVALID, "level_ptr does not start at 0");
+  for (int l = 0; l < n_levels; ++l)
+    if (level_ptr[l + 1] < level_ptr[l]) return bad(GMG_ERR_INVALID, "level_ptr decreases");
+  const int nv = 1 << dim, nf = 2 * dim;
+  const int64_t n_all = level_ptr[n_levels];
+  if (n_all > 0 && (!cell_coord || !cell_first_child)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_all * nv >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 slots");
+  const int32_t lat[3] = {n0[0], n0[1], dim == 3 ? n0[2] : 1};
+  std::vector<uint8_t> level_of((size_t)n_all);
+  for (int l = 0; l < n_levels; ++l) {
+    const int64_t n_next = l + 1 < n_levels ? level_ptr[l + 2] - level_ptr[l + 1] : 0;
+    for (int64_t c = level_ptr[l]; c < level_ptr[l + 1]; ++c) {
+      level_of[(size_t)c] = (uint8_t)l;
+      for (int d = 0; d < 3; ++d) {
+        const int64_t x = cell_coord[3 * c + d], n = d < dim ? (int64_t)lat[d] << l : 1;
+        if (x < 0 || x >= n) return bad(GMG_ERR_INVALID, "a cell outside its level's lattice");
+      }
+      const int64_t fc = cell_first_child[c];
+      if (fc >= 0 && fc + nv > n_next) return bad(GMG_ERR_INVALID, "first_child points outside the next level");
+    }
+  }
+  const int64_t n_l0 = n_levels > 0 ? level_ptr[1] : 0;
+  const bool lattice0 = level0_lexicographic != 0 && n_all > 0;
+  if (lattice0) {  // level 0 must be the full lattice, x fastest
+    if (n_l0 != (int64_t)lat[0] * lat[1] * lat[2]) return bad(GMG_ERR_INVALID, "level0_lexicographic: level 0 is not the full lattice");
+    for (int64_t c = 0; c < n_l0; ++c)
+      if (cell_coord[3 * c] != c % lat[0] || cell_coord[3 * c + 1] != (c / lat[0]) % lat[1] || cell_coord[3 * c + 2] != c / ((int64_t)lat[0] * lat[1]))
+        return bad(GMG_ERR_INVALID, "level0_lexicographic: level 0 is not in lexicographic cell order");
+  }
+  // the scratch lives until the stream has run the kernels
+  DevPtr<int32_t> d_coord, d_fc, d_apos, d_active, d_rank, d_tdof, d_cidx, d_lbase, d_ebase, d_drank;
+  DevPtr<uint8_t> d_lvl, d_hangs, d_edge;
+  DevPtr<unsigned long long> d_akeys, d_vkeys, d_ckeys, d_visit;
+  DevPtr<unsigned int> d_afirst, d_vfirst, d_hpos;
+  DevPtr<int> d_err;
+  Event e0, e1;
+  MeshTables mt;
+  mt.dim = dim;
+  mt.level.resize((size_t)n_levels);
+  auto table_size = [](int64_t n) { unsigned long long t = 1024; while ((int64_t)t < 2 * n) t <<= 1; return t; };
+  HIPC(upload(d_coord, cell_coord, (size_t)n_all * 3, ctx->stream));
+  HIPC(upload(d_fc, cell_first_child, (size_t)n_all, ctx->stream));
+  HIPC(upload(d_lvl, level_of, ctx->stream));
+  HIPC(d_err.alloc(1));
+  HIPC(hipMemsetAsync(d_err.get(), 0, sizeof(int), ctx->stream));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  MtForest f{};
+  f.coord = d_coord.get(); f.first_child = d_fc.get(); f.level = d_lvl.get(); f.dim = dim; f.nv = nv; f.nf = nf;
+  for (int d = 0; d < 3; ++d) { f.n0[d] = lat[d]; f.hi[d] = (unsigned long long)lat[d] << kMtShift; }
+  const dim3 blk(kMtThreads);
+  // the flag word, and what it means once the stream has been waited for
+  auto flagged = [&](int &rc) -> int {
+    int err = 0;
+    HIPC(hipMemcpyAsync(&err, d_err.get(), sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    rc = err & kMtErrDuplicate    ? bad(GMG_ERR_INVALID, "the same cell appears twice")
+         : err & kMtErrUnbalanced ? bad(GMG_ERR_INVALID, "hanging node without a DoF: the mesh is not 2:1 balanced")
+         : err & kMtErrFull       ? bad(GMG_ERR_HIP, "a hash table filled up")
+                                  : (int)GMG_OK;
+    return GMG_OK;
+  };
+  // 1. the active cells, by (level, index)
+  HIPC(d_apos.alloc((size_t)n_all + 1));
+  if (n_all) hipLaunchKernelGGL(mt_active_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d_fc.get(), n_all, d_apos.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_apos.get(), n_all);
+  int32_t n_active32 = 0;
+  HIPC(hipMemcpyAsync(&n_active32, d_apos.get() + n_all, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const int64_t n_active = n_active32;
+  mt.n_cells = n_active;
+  HIPC(d_active.alloc((size_t)std::max<int64_t>(n_active, 1)));
+  HIPC(mt.cell_level.alloc((size_t)std::max<int64_t>(n_active, 1)));
+  HIPC(mt.cell_dofs.alloc((size_t)std::max<int64_t>(n_active * nv, 1)));
+  if (n_all) hipLaunchKernelGGL(mt_active_list_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, f, n_all, (const int32_t *)d_apos.get(), d_active.get(), mt.cell_level.get());
+  // first-touch numbering of a cell list (gmg_mesh_tables.hpp, kernels 1 - 3); keys / first: a table of `size` entries
+  int64_t max_slots = n_active * nv;
+  for (int l = 0; l < n_levels; ++l) max_slots = std::max(max_slots, (level_ptr[l + 1] - level_ptr[l]) * nv);
+  HIPC(d_rank.alloc((size_t)max_slots + 1));
+  HIPC(d_hpos.alloc((size_t)std::max<int64_t>(max_slots, 1)));
+  auto number = [&](const int32_t *cells, int64_t begin, int64_t n_slots, unsigned long long *keys, unsigned int *first, unsigned long long size, int32_t *tdof,
+                    DevPtr<int32_t> &cell_dofs, DevPtr<unsigned long long> &vertex_of_dof, int64_t &n_dofs, int &rc) -> int {
+    HIPC(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * size, ctx->stream));
+    HIPC(hipMemsetAsync(first, 0xff, sizeof(unsigned int) * size, ctx->stream));
+    const dim3 g = asm_blocks(ctx, n_slots, kMtThreads);
+    if (n_slots) {
+      hipLaunchKernelGGL(mt_vertex_insert_kernel, g, blk, 0, ctx->stream, f, cells, begin, n_slots, keys, first, d_hpos.get(), size - 1, d_err.get());
+      hipLaunchKernelGGL(mt_first_flag_kernel, g, blk, 0, ctx->stream, (const unsigned int *)first, (const unsigned int *)d_hpos.get(), n_slots, d_rank.get());
+    }
+    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_rank.get(), n_slots);
+    int32_t n32 = 0;
+    HIPC(hipMemcpyAsync(&n32, d_rank.get() + n_slots, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CHK(flagged(rc));  // (a full table leaves first slots unset: nothing may index through them)
+    if (rc != GMG_OK) return GMG_OK;
+    n_dofs = n32;
+    HIPC(vertex_of_dof.alloc((size_t)std::max<int64_t>(n_dofs, 1)));
+    if (n_slots)
+      hipLaunchKernelGGL(mt_number_kernel, g, blk, 0, ctx->stream, (const unsigned long long *)keys, (const unsigned int *)first, (const unsigned int *)d_hpos.get(),
+                         (const int32_t *)d_rank.get(), n_slots, cell_dofs.get(), vertex_of_dof.get(), tdof);
+    return GMG_OK;
+  };
+  int rc = GMG_OK;
+  // 2. the active numbering; its table stays for the hanging nodes
+  const unsigned long long a_size = table_size(n_active * nv);
+  HIPC(d_akeys.alloc(a_size));
+  HIPC(d_afirst.alloc(a_size));
+  HIPC(d_tdof.alloc(a_size));
+  CHK(number(d_active.get(), 0, n_active * nv, d_akeys.get(), d_afirst.get(), a_size, d_tdof.get(), mt.cell_dofs, mt.vertex_of_dof, mt.n_dofs, rc));
+  if (rc != GMG_OK) return rc;
+  // 3. level by level: the cells by coordinates, the level numbering, the faces (hanging faces of the active cells, the
+  // refinement edge), the flags
+  int64_t max_level_cells = 0;
+  for (int l = 0; l < n_levels; ++l) max_level_cells = std::max(max_level_cells, level_ptr[l + 1] - level_ptr[l]);
+  const unsigned long long v_size_max = table_size(max_level_cells * nv), c_size_max = table_size(max_level_cells);
+  HIPC(d_vkeys.alloc(v_size_max));
+  HIPC(d_vfirst.alloc(v_size_max));
+  HIPC(d_ckeys.alloc(c_size_max));
+  HIPC(d_cidx.alloc(c_size_max));
+  HIPC(d_hangs.alloc((size_t)std::max<int64_t>(n_active * nf, 1)));
+  HIPC(hipMemsetAsync(d_hangs.get(), 0, (size_t)std::max<int64_t>(n_active * nf, 1), ctx->stream));
+  for (int l = 0; l < n_levels; ++l) {
+    MeshTables::PerLevel &L = mt.level[(size_t)l];
+    const int64_t begin = level_ptr[l], n_cells = level_ptr[l + 1] - begin;
+    L.n_cells = n_cells;
+    HIPC(L.cell_dofs.alloc((size_t)std::max<int64_t>(n_cells * nv, 1)));
+    if (l == 0 && lattice0) {
+      L.n_dofs = (int64_t)(lat[0] + 1) * (lat[1] + 1) * (dim == 3 ? lat[2] + 1 : 1);
+      HIPC(L.vertex_of_dof.alloc((size_t)L.n_dofs));
+      hipLaunchKernelGGL(mt_lattice_kernel, asm_blocks(ctx, std::max(n_cells * nv, L.n_dofs), kMtThreads), blk, 0, ctx->stream, f, n_cells, L.n_dofs, L.cell_dofs.get(),
+                         L.vertex_of_dof.get());
+    } else {
+      CHK(number(nullptr, begin, n_cells * nv, d_vkeys.get(), d_vfirst.get(), table_size(n_cells * nv), nullptr, L.cell_dofs, L.vertex_of_dof, L.n_dofs, rc));
+      if (rc != GMG_OK) return rc;
+    }
+    const unsigned long long c_size = table_size(n_cells);
+    HIPC(hipMemsetAsync(d_ckeys.get(), 0xff, sizeof(unsigned long long) * c_size, ctx->stream));
+    HIPC(d_edge.alloc((size_t)std::max<int64_t>(L.n_dofs, 1)));
+    HIPC(hipMemsetAsync(d_edge.get(), 0, (size_t)std::max<int64_t>(L.n_dofs, 1), ctx->stream));
+    HIPC(L.dof_flags.alloc((size_t)std::max<int64_t>(L.n_dofs, 1)));
+    if (n_cells) {
+      hipLaunchKernelGGL(mt_cell_insert_kernel, asm_blocks(ctx, n_cells, kMtThreads), blk, 0, ctx->stream, f, begin, n_cells, d_ckeys.get(), d_cidx.get(), c_size - 1, d_err.get());
+      CHK(flagged(rc));  // (a cell met twice or a full table leaves positions without an index)
+      if (rc != GMG_OK) return rc;
+      hipLaunchKernelGGL(mt_level_face_kernel, asm_blocks(ctx, n_cells * nf, kMtThreads), blk, 0, ctx->stream, f, l, begin, n_cells, (const unsigned long long *)d_ckeys.get(),
+                         (const int32_t *)d_cidx.get(), c_size - 1, (const int32_t *)d_apos.get(), (const int32_t *)L.cell_dofs.get(), d_hangs.get(), d_edge.get());
+    }
+    if (L.n_dofs)
+      hipLaunchKernelGGL(mt_level_flags_kernel, asm_blocks(ctx, L.n_dofs, kMtThreads), blk, 0, ctx->stream, f, (const unsigned long long *)L.vertex_of_dof.get(),
+                         (const uint8_t *)d_edge.get(), L.n_dofs, L.dof_flags.get());
+    HIPC(hipStreamSynchronize(ctx->stream));  // (d_edge is allocated anew for the next level)
+  }
+  // 4. the hanging-node lines, then the Dirichlet lines behind them
+  const int64_t n_dofs = mt.n_dofs;
+  HIPC(d_visit.alloc((size_t)std::max<int64_t>(n_dofs, 1)));
+  HIPC(hipMemsetAsync(d_visit.get(), 0xff, sizeof(unsigned long long) * (size_t)std::max<int64_t>(n_dofs, 1), ctx->stream));
+  HIPC(d_lbase.alloc((size_t)n_active + 1));
+  HIPC(d_ebase.alloc((size_t)n_active + 1));
+  HIPC(d_drank.alloc((size_t)n_dofs + 1));
+  HIPC(mt.constraint_of_dof.alloc((size_t)std::max<int64_t>(n_dofs, 1)));
+  HIPC(hipMemsetAsync(mt.constraint_of_dof.get(), 0xff, sizeof(int32_t) * (size_t)std::max<int64_t>(n_dofs, 1), ctx->stream));
+  MtHang a{};
+  a.active_cell = d_active.get(); a.face_hangs = d_hangs.get(); a.cell_dofs = mt.cell_dofs.get(); a.keys = d_akeys.get(); a.tdof = d_tdof.get(); a.mask = a_size - 1;
+  a.visit = d_visit.get(); a.n_active = n_active; a.err = d_err.get(); a.line_base = d_lbase.get(); a.entry_base = d_ebase.get();
+  const dim3 g_cells = asm_blocks(ctx, n_active, kMtThreads), g_dofs = asm_blocks(ctx, n_dofs, kMtThreads);
+  if (n_active) {
+    hipLaunchKernelGGL(mt_hang_visit_kernel, asm_blocks(ctx, n_active * nf, kMtThreads), blk, 0, ctx->stream, f, a);
+    hipLaunchKernelGGL(mt_hang_lines_kernel<false>, g_cells, blk, 0, ctx->stream, f, a);
+  }
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_lbase.get(), n_active);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_ebase.get(), n_active);
+  if (n_dofs)
+    hipLaunchKernelGGL(mt_dirichlet_flag_kernel, g_dofs, blk, 0, ctx->stream, f, (const unsigned long long *)mt.vertex_of_dof.get(), (const unsigned long long *)d_visit.get(), n_dofs,
+                       d_drank.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_drank.get(), n_dofs);
+  int32_t n_hanging = 0, n_entries = 0, n_dirichlet = 0;
+  HIPC(hipMemcpyAsync(&n_hanging, d_lbase.get() + n_active, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&n_entries, d_ebase.get() + n_active, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&n_dirichlet, d_drank.get() + n_dofs, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  CHK(flagged(rc));
+  if (rc != GMG_OK) return rc;
+  mt.n_hanging = n_hanging; mt.n_entries = n_entries; mt.n_lines = (int64_t)n_hanging + n_dirichlet;
+  HIPC(mt.line_ptr.alloc((size_t)mt.n_lines + 1));
+  HIPC(mt.line_dof.alloc((size_t)std::max<int64_t>(mt.n_lines, 1)));
+  HIPC(mt.line_master.alloc((size_t)std::max<int64_t>(mt.n_entries, 1)));
+  HIPC(mt.line_weight.alloc((size_t)std::max<int64_t>(mt.n_entries, 1)));
+  a.constraint_of_dof = mt.constraint_of_dof.get(); a.line_dof = mt.line_dof.get(); a.line_ptr = mt.line_ptr.get(); a.line_master = mt.line_master.get();
+  a.line_weight = mt.line_weight.get();
+  if (n_active) hipLaunchKernelGGL(mt_hang_lines_kernel<true>, g_cells, blk, 0, ctx->stream, f, a);
+  hipLaunchKernelGGL(mt_dirichlet_lines_kernel, g_dofs, blk, 0, ctx->stream, f, (const unsigned long long *)mt.vertex_of_dof.get(), (const unsigned long long *)d_visit.get(),
+                     (const int32_t *)d_drank.get(), n_dofs, n_hanging, (int32_t)mt.n_lines, n_entries, mt.constraint_of_dof.get(), mt.line_dof.get(), mt.line_ptr.get());
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(launch_status(ctx));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  mt.valid = true;
+  ctx->mesh = std::move(mt);
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] mesh tables built on the device: %lld active cells, %lld DoFs, %lld hanging + %lld Dirichlet lines, %.3f ms\n", (long long)n_active,
+                 (long long)n_dofs, (long long)n_hanging, (long long)n_dirichlet, ms);
+  return GMG_OK;
+}
+
+int gmg_get_mesh_tables(gmg_context *ctx, int64_t *n_cells, int64_t *n_dofs, int64_t *n_hanging, int64_t *n_lines, int64_t *n_entries, int32_t *cell_dofs,
+                        uint8_t *cell_level, uint64_t *vertex_of_dof, int32_t *constraint_of_dof, int64_t *line_ptr, int32_t *line_master, double *line_weight,
+                        int32_t *line_dof) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_mesh_tables: the context holds no mesh tables");
+  (void)hipSetDevice(ctx->device);
+  if (n_cells) *n_cells = m.n_cells;
+  if (n_dofs) *n_dofs = m.n_dofs;
+  if (n_hanging) *n_hanging = m.n_hanging;
+  if (n_lines) *n_lines = m.n_lines;
+  if (n_entries) *n_entries = m.n_entries;
+  std::vector<int32_t> lp(line_ptr ? (size_t)m.n_lines + 1 : 0);
+  HIPC(mesh_fetch(ctx, cell_dofs, m.cell_dofs, m.n_cells << m.dim));
+  HIPC(mesh_fetch(ctx, cell_level, m.cell_level, m.n_cells));
+  HIPC(mesh_fetch(ctx, (unsigned long long *)vertex_of_dof, m.vertex_of_dof, m.n_dofs));
+  HIPC(mesh_fetch(ctx, constraint_of_dof, m.constraint_of_dof, m.n_dofs));
+  HIPC(mesh_fetch(ctx, line_ptr ? lp.data() : nullptr, m.line_ptr, m.n_lines + 1));
+  HIPC(mesh_fetch(ctx, line_master, m.line_master, m.n_entries));
+  HIPC(mesh_fetch(ctx, line_weight, m.line_weight, m.n_entries));
+  HIPC(mesh_fetch(ctx, line_dof, m.line_dof, m.n_lines));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < lp.size(); ++i) line_ptr[i] = lp[i];
+  return GMG_OK;
+}
+
+int gmg_get_mesh_level_tables(gmg_context *ctx, int level, int64_t *n_cells, int64_t *n_dofs, int32_t *cell_dofs, uint64_t *vertex_of_dof, uint8_t *dof_flags) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_mesh_level_tables: the context holds no mesh tables");
+  if (level < 0 || level >= (int)m.level.size()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_mesh_level_tables: no such level in the mesh tables");
+  (void)hipSetDevice(ctx->device);
+  const MeshTables::PerLevel &L = m.level[(size_t)level];
+  if (n_cells) *n_cells = L.n_cells;
+  if (n_dofs) *n_dofs = L.n_dofs;
+  HIPC(mesh_fetch(ctx, cell_dofs, L.cell_dofs, L.n_cells << m.dim));
+  HIPC(mesh_fetch(ctx, (unsigned long long *)vertex_of_dof, L.vertex_of_dof, L.n_dofs));
+  HIPC(mesh_fetch(ctx, dof_flags, L.dof_flags, L.n_dofs));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
 }
 
 // ---- the right-hand side from the cell tables, and constraints.distribute on the same tables (gmg_rhs_cells.hpp, DESIGN.md

@@ -344,6 +344,25 @@ int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t
     return 0;
   });
 }
+// ---- "Mesh tables on device" (DESIGN.md section 20): what the driver hands to gmg_build_mesh_tables for the current forest.
+// sizes: n_levels, cells of all levels, level0_lexicographic
+int step50_mesh_tables_on_device(step50_problem *h) { return DISPATCH(h, mesh_on_device) ? 1 : 0; }
+int step50_forest_sizes(step50_problem *h, int64_t sizes[3]) {
+  return guarded(h, [&] {
+    const auto fc = DISPATCH(h, forest_cells());
+    sizes[0] = (int64_t)fc.level_ptr.size() - 1; sizes[1] = fc.level_ptr.back(); sizes[2] = fc.level0_lexicographic;
+    return 0;
+  });
+}
+int step50_forest_cells(step50_problem *h, int32_t n0[3], int64_t *level_ptr, int32_t *cell_coord, int32_t *cell_first_child) {
+  return guarded(h, [&] {
+    const auto fc = DISPATCH(h, forest_cells());
+    auto put = [](const auto &v, auto *out) { if (!v.empty()) std::memcpy(out, v.data(), sizeof(v[0]) * v.size()); };
+    for (int d = 0; d < 3; ++d) n0[d] = fc.n0[d];
+    put(fc.level_ptr, level_ptr); put(fc.cell_coord, cell_coord); put(fc.cell_first_child, cell_first_child);
+    return 0;
+  });
+}
 // ---- "RHS from cell tables" (DESIGN.md section 19): what the driver hands to gmg_assemble_rhs beyond the arrays above.
 // sizes: nq, n_cells, 2^dim.  source: the charge densities as the host holds them, or rhs_function at the quadrature points
 int step50_rhs_from_cell_tables(step50_problem *h) { return DISPATCH(h, rhs_from_cells) ? 1 : 0; }

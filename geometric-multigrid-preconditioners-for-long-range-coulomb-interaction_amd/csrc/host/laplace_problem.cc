@@ -252,6 +252,10 @@ void ParameterReader::declare_parameters() {
             // (gmg_distribute_constraints), whose vector the estimator, the forces and the error norm then take; cycles that
             // run on the device, one rank, DESIGN.md section 19
             {"RHS from cell tables", "false"},
+            // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints: DoF numbering of the
+            // active mesh and of every level, hanging-node and Dirichlet lines, level flags; boundary values and close() stay
+            // here; cycles that run on the device, one rank, DESIGN.md section 20
+            {"Mesh tables on device", "false"},
             // the short-ranged pair sum over the pairs closer than this many smoothing lengths, found through
             // cell bins (erfc(6) = 2e-17: beyond 6 r_c a pair contributes nothing in double precision); 0 = all pairs as the
             // reference (:1325-1332).  With it the energy is also evaluated for the large systems the reference skips (:1554).
@@ -340,6 +344,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.transfer_on_device = prm.get_bool("Transfer matrices on device");
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.rhs_from_cell_tables = prm.get_bool("RHS from cell tables");
+  p.mesh_tables_on_device = prm.get_bool("Mesh tables on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
   p.compute_forces = prm.get_bool("Compute forces");
@@ -609,6 +614,9 @@ void LaplaceProblem<dim>::distribute_dofs() {
   dof_of_vertex.reset(kMaxLevelShift, lattice);
   vertex_of_dof.clear();
   sublap("dofs: active cell list");
+  mesh_on_device = decide_mesh_tables_on_device();
+  if (mesh_on_device) { distribute_dofs_on_device(); return; }
+  dof_maps_ready = true;
   dof_of_vertex.reserve_sparse(active_cells.size() - (size_t)std::min<int64_t>((int64_t)active_cells.size(), (int64_t)triangulation.levels[0].size()));
   active_cell_dof_table.resize(active_cells.size() * (size_t)(1 << dim));
   size_t slot = 0;
@@ -672,6 +680,113 @@ void LaplaceProblem<dim>::distribute_dofs() {
   sublap("dofs: level numbering");
 }
 
+// Is this cycle's mesh one whose tables gmg_build_mesh_tables forms?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_mesh_tables_on_device() {
+  if (!par.mesh_tables_on_device) return false;
+  const char *why = !solve_on_device_requested ? "the cycle does not run on the device"
+                    : distributed              ? "the run is distributed"
+                                               : nullptr;
+  if (!why) return true;
+  if (!mesh_fallback_reported) pcout(std::string("   Mesh tables on device: not applicable (") + why + "), formed on the host");
+  mesh_fallback_reported = true;
+  return false;
+}
+
+// what gmg_build_mesh_tables takes: the cells of every level in index order
+template <int dim>
+ForestCells LaplaceProblem<dim>::forest_cells() const {
+  ForestCells fc;
+  const int L = triangulation.n_levels();
+  fc.n0[0] = fc.n0[1] = triangulation.n0;
+  fc.n0[2] = dim == 3 ? triangulation.n0 : 1;
+  fc.level_ptr.assign((size_t)L + 1, 0);
+  for (int l = 0; l < L; ++l) fc.level_ptr[(size_t)l + 1] = fc.level_ptr[(size_t)l] + (int64_t)triangulation.levels[(size_t)l].size();
+  fc.cell_coord.resize((size_t)fc.level_ptr[(size_t)L] * 3);
+  fc.cell_first_child.resize((size_t)fc.level_ptr[(size_t)L]);
+  for (int l = 0; l < L; ++l) {
+    const auto &cells = triangulation.levels[(size_t)l];
+    const int64_t b = fc.level_ptr[(size_t)l];
+#pragma omp parallel for schedule(static)
+    for (int64_t c = 0; c < (int64_t)cells.size(); ++c) {
+      for (int d = 0; d < 3; ++d) fc.cell_coord[(size_t)(b + c) * 3 + (size_t)d] = cells[(size_t)c].c[d];
+      fc.cell_first_child[(size_t)(b + c)] = cells[(size_t)c].first_child;
+    }
+  }
+  fc.level0_lexicographic = par.level0_numbering == "lexicographic" ? 1 : 0;
+  return fc;
+}
+
+// distribute_dofs() through gmg_build_mesh_tables: one call, then the tables come back into the containers the host loops
+// fill; the lines and the level flags wait in device_mesh for make_constraints().  The vertex -> DoF hash tables are not
+// built here (ensure_dof_maps).
+template <int dim>
+void LaplaceProblem<dim>::distribute_dofs_on_device() {
+  auto chk = [&](int rc, const char *what) {
+    if (rc != GMG_OK) throw std::runtime_error(std::string("Mesh tables on device: ") + what + ": " + (gmg ? gmg_last_error(gmg) : last_error.c_str()));
+  };
+  chk(ensure_context(), "context");
+  constexpr int nv = 1 << dim;
+  const int L = triangulation.n_levels();
+  const ForestCells fc = forest_cells();
+  chk(gmg_build_mesh_tables(gmg, dim, fc.n0, L, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), fc.level0_lexicographic, &mesh_tables_ms),
+      "gmg_build_mesh_tables");
+  sublap("dofs + constraints on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     .   build_ms %.3f\n", mesh_tables_ms);
+  int64_t n_cells = 0, n_dofs = 0, n_lines = 0, n_entries = 0;
+  DeviceMeshTables &t = device_mesh;
+  chk(gmg_get_mesh_tables(gmg, &n_cells, &n_dofs, &t.n_hanging, &n_lines, &n_entries, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "sizes");
+  if (n_cells != (int64_t)active_cells.size()) throw std::logic_error("Mesh tables on device: the active cell lists differ");
+  active_cell_dof_table.resize((size_t)n_cells * nv);
+  vertex_of_dof.resize((size_t)n_dofs);
+  t.constraint_of_dof.resize((size_t)n_dofs);
+  t.line_ptr.resize((size_t)n_lines + 1);
+  t.line_master.resize((size_t)n_entries);
+  t.line_weight.resize((size_t)n_entries);
+  t.line_dof.resize((size_t)n_lines);
+  chk(gmg_get_mesh_tables(gmg, nullptr, nullptr, nullptr, nullptr, nullptr, active_cell_dof_table.data(), nullptr, vertex_of_dof.data(), t.constraint_of_dof.data(),
+                          t.line_ptr.data(), t.line_master.data(), t.line_weight.data(), t.line_dof.data()),
+      "download");
+  level_vertex_of_dof.assign((size_t)L, {});
+  level_cell_dof_table.assign((size_t)L, {});
+  t.dof_flags.assign((size_t)L, {});
+  for (int l = 0; l < L; ++l) {
+    int64_t nc = 0, nd = 0;
+    chk(gmg_get_mesh_level_tables(gmg, l, &nc, &nd, nullptr, nullptr, nullptr), "level sizes");
+    level_cell_dof_table[(size_t)l].resize((size_t)nc * nv);
+    level_vertex_of_dof[(size_t)l].resize((size_t)nd);
+    t.dof_flags[(size_t)l].resize((size_t)nd);
+    chk(gmg_get_mesh_level_tables(gmg, l, nullptr, nullptr, level_cell_dof_table[(size_t)l].data(), level_vertex_of_dof[(size_t)l].data(), t.dof_flags[(size_t)l].data()),
+        "level download");
+  }
+  dof_of_vertex.clear();
+  level_dof_of_vertex.assign((size_t)L, {});
+  dof_maps_ready = false;
+  sublap("dofs + constraints: download");
+}
+
+// dof_of_vertex and level_dof_of_vertex from vertex_of_dof / level_vertex_of_dof, on first use after "Mesh tables on device"
+// left them out (fe_value_at, the host path of make_constraints)
+template <int dim>
+void LaplaceProblem<dim>::ensure_dof_maps() {
+  if (dof_maps_ready) return;
+  const int L = triangulation.n_levels();
+  const int lattice[3] = {triangulation.n0 + 1, triangulation.n0 + 1, dim == 3 ? triangulation.n0 + 1 : 1};
+  const int none[3] = {0, 0, 0};
+  dof_of_vertex.reset(kMaxLevelShift, lattice);
+  dof_of_vertex.reserve_sparse(vertex_of_dof.size() - std::min(vertex_of_dof.size(), (size_t)lattice[0] * lattice[1] * lattice[2]));
+  for (size_t i = 0; i < vertex_of_dof.size(); ++i) dof_of_vertex.emplace(vertex_of_dof[i], (int32_t)i);
+  level_dof_of_vertex.assign((size_t)L, {});
+  for (int l = 0; l < L; ++l) {
+    auto &map = level_dof_of_vertex[(size_t)l];
+    const auto &vec = level_vertex_of_dof[(size_t)l];
+    map.reset(kMaxLevelShift, l == 0 ? lattice : none);
+    if (l > 0) map.reserve_sparse(vec.size());
+    for (size_t i = 0; i < vec.size(); ++i) map.emplace(vec[i], (int32_t)i);
+  }
+  dof_maps_ready = true;
+}
+
 template <int dim>
 void LaplaceProblem<dim>::make_constraints() {
   // DoFTools::make_hanging_node_constraints + VectorTools::interpolate_boundary_values +
@@ -680,7 +795,18 @@ void LaplaceProblem<dim>::make_constraints() {
   constraint_of_dof.assign((size_t)n, -1);
   constraint_lines.clear();
   const int shift0 = kMaxLevelShift;
-  for (const ActiveCell &ac : active_cells) {
+  if (mesh_on_device) {  // the hanging lines as gmg_build_mesh_tables numbered them (unclosed); the Dirichlet lines follow below
+    const DeviceMeshTables &t = device_mesh;
+    constraint_lines.resize((size_t)t.n_hanging);
+    for (int64_t l = 0; l < t.n_hanging; ++l) {
+      ConstraintLine &line = constraint_lines[(size_t)l];
+      line.hanging = true;
+      for (int64_t e = t.line_ptr[(size_t)l]; e < t.line_ptr[(size_t)l + 1]; ++e) line.entries.push_back({t.line_master[(size_t)e], t.line_weight[(size_t)e]});
+      constraint_of_dof[(size_t)t.line_dof[(size_t)l]] = (int32_t)l;
+    }
+  } else ensure_dof_maps();
+  static const std::vector<ActiveCell> no_cells;  // (the host's loop over the faces runs over no cell when the device formed the lines)
+  for (const ActiveCell &ac : mesh_on_device ? no_cells : active_cells) {
     const int l = ac.level;
     const Cell &c = triangulation.levels[(size_t)l][(size_t)ac.index];
     for (int d = 0; d < dim; ++d)
@@ -734,8 +860,13 @@ void LaplaceProblem<dim>::make_constraints() {
   const bool batch = par.analytical_on_device && dim == 3 && par.Boundary_conditions == "Exact" && par.Problemtype == "GaussianCharges";
   std::vector<int32_t> batch_line;
   std::vector<double> batch_x;
-  for (int64_t i = 0; i < n; ++i) {
-    if (!triangulation.vertex_on_boundary(vertex_of_dof[(size_t)i]) || constraint_of_dof[(size_t)i] >= 0) continue;
+  // (the device lists the DoFs of the Dirichlet lines in the same ascending order: line_dof behind the hanging lines)
+  std::vector<int32_t> dirichlet_dof;
+  if (mesh_on_device) dirichlet_dof.assign(device_mesh.line_dof.begin() + device_mesh.n_hanging, device_mesh.line_dof.end());
+  else
+    for (int64_t i = 0; i < n; ++i)
+      if (triangulation.vertex_on_boundary(vertex_of_dof[(size_t)i]) && constraint_of_dof[(size_t)i] < 0) dirichlet_dof.push_back((int32_t)i);
+  for (const int32_t i : dirichlet_dof) {
     double x[3];
     triangulation.vertex_coords(vertex_of_dof[(size_t)i], x);
     ConstraintLine line;
@@ -775,6 +906,11 @@ void LaplaceProblem<dim>::make_constraints() {
     const auto &vec = level_vertex_of_dof[(size_t)l];
     level_boundary[(size_t)l].assign(vec.size(), 0);
     level_refinement_edge[(size_t)l].assign(vec.size(), 0);
+    if (mesh_on_device) {
+      const auto &fl = device_mesh.dof_flags[(size_t)l];
+      for (size_t i = 0; i < vec.size(); ++i) { level_boundary[(size_t)l][i] = fl[i] & 1; level_refinement_edge[(size_t)l][i] = (fl[i] >> 1) & 1; }
+      continue;
+    }
     for (size_t i = 0; i < vec.size(); ++i) level_boundary[(size_t)l][i] = triangulation.vertex_on_boundary(vec[i]);
     if (l == 0) continue;
     const int nl = triangulation.n0 << l;
@@ -791,6 +927,10 @@ void LaplaceProblem<dim>::make_constraints() {
               level_refinement_edge[(size_t)l][(size_t)level_dof_of_vertex[(size_t)l].at(triangulation.vertex_key(l, c, a))] = 1;
         }
     }
+  }
+  if (mesh_on_device) {  // (the same lines, numbered the same: anything else is a defect of the entry, not of the mesh)
+    if (constraint_of_dof != device_mesh.constraint_of_dof) throw std::logic_error("Mesh tables on device: constraint_of_dof differs from the lines");
+    device_mesh = DeviceMeshTables();
   }
 }
 
@@ -1961,6 +2101,7 @@ double LaplaceProblem<dim>::fe_value_at(const std::vector<double> &u, const doub
   double t[3] = {0, 0, 0};
   for (int d = 0; d < dim; ++d) t[d] = (x[d] - x0[d]) / h;
   double v = 0;
+  const_cast<LaplaceProblem<dim> *>(this)->ensure_dof_maps();  // ("Mesh tables on device" leaves the hash tables to their first use; callers are sequential)
   for (int a = 0; a < (1 << dim); ++a) {
     double w = 1;
     for (int d = 0; d < dim; ++d) w *= ((a >> d) & 1) ? t[d] : 1.0 - t[d];

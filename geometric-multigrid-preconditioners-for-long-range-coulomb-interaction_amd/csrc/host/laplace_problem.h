@@ -81,6 +81,7 @@ struct Parameters {
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (one rank; Step16: the _coef entry)
   bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
   bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
+  bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
@@ -105,6 +106,14 @@ struct CycleReport {  // the values the reference prints per cycle (src/step-50.
   int coarse_solver = 0;  // GMG_COARSE_CG / GMG_COARSE_DIRECT: what the cycle's last coarse solve ran (gmg_stats.coarse_solver)
   bool has_forces = false;  // "Compute forces": sum_i F_i, max_i |F_i|, ||F - F^d|| / ||F^d|| ("Direct Coulomb check", else 0)
   double force_net[3] = {0, 0, 0}, force_max = 0, force_rel_error = 0;
+};
+
+// "Mesh tables on device" (DESIGN.md section 20): what gmg_build_mesh_tables takes, from the forest alone
+struct ForestCells {
+  int32_t n0[3] = {0, 0, 0};
+  std::vector<int64_t> level_ptr;
+  std::vector<int32_t> cell_coord, cell_first_child;  // [n][3], [n]: every cell of every level in index order
+  int level0_lexicographic = 0;
 };
 
 template <int dim>
@@ -284,6 +293,22 @@ class LaplaceProblem {
   bool estimated_on_device = false;        // the last estimate came from gmg_estimate_error
   bool estimator_fallback_reported = false;  // "Error estimator on device" was set but not applicable: said once
   int64_t host_density_copies = 0;         // how often ensure_host_densities() fetched device-resident densities
+
+  ForestCells forest_cells() const;     // "Mesh tables on device": the input of gmg_build_mesh_tables
+  bool decide_mesh_tables_on_device();  // this cycle's numbering, constraints and level flags formed by gmg_build_mesh_tables?
+  void distribute_dofs_on_device();     // the one call, and the download of the DoF tables
+  void ensure_dof_maps();               // the vertex -> DoF hash tables, built from vertex_of_dof on first use
+  bool mesh_on_device = false;            // this cycle's tables came from gmg_build_mesh_tables
+  bool mesh_fallback_reported = false;    // "Mesh tables on device" was set but not applicable: said once
+  bool dof_maps_ready = false;            // dof_of_vertex / level_dof_of_vertex match vertex_of_dof / level_vertex_of_dof
+  double mesh_tables_ms = 0.0;            // device time of gmg_build_mesh_tables for the current mesh
+  struct DeviceMeshTables {               // what make_constraints() takes from the same result
+    int64_t n_hanging = 0;
+    std::vector<int32_t> constraint_of_dof, line_master, line_dof;
+    std::vector<int64_t> line_ptr;
+    std::vector<double> line_weight;
+    std::vector<std::vector<uint8_t>> dof_flags;
+  } device_mesh;
 
   void pcout(const std::string &s);
   void distribute_dofs();

@@ -87,6 +87,7 @@ def prm_text(**kw) -> str:
         "system_matrix_on_device": ("Misc", "System matrix on device"),
         "level_matrices_on_device": ("Misc", "Level matrices on device"),
         "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
+        "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
@@ -363,6 +364,23 @@ class Problem:
     def rhs_from_cell_tables(self) -> bool:
         """Did the last assembly form the right-hand side through gmg_assemble_rhs?"""
         return bool(self.L.step50_rhs_from_cell_tables(self.h))
+
+    def forest_cells(self):
+        """The arrays the driver hands to gmg_build_mesh_tables for the current forest: namespace(dim, n0 [3], n_levels,
+        level_ptr [n_levels + 1], cell_coord [n, 3], cell_first_child [n], level0_lexicographic)."""
+        sz = (C.c_int64 * 3)()
+        self._chk(self.L.step50_forest_sizes(self.h, sz), "forest_cells")
+        n_levels, n, lex = (int(v) for v in sz)
+        n0, lp = np.zeros(3, dtype=np.int32), np.zeros(n_levels + 1, dtype=np.int64)
+        cc, fc = np.zeros((n, 3), dtype=np.int32), np.zeros(n, dtype=np.int32)
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        self._chk(self.L.step50_forest_cells(self.h, P(n0, C.c_int32), P(lp, C.c_int64), P(cc, C.c_int32), P(fc, C.c_int32)), "forest_cells")
+        return SimpleNamespace(dim=int(self.L.step50_dim(self.h)), n0=n0, n_levels=n_levels, level_ptr=lp, cell_coord=cc, cell_first_child=fc,
+                               level0_lexicographic=bool(lex))
+
+    def mesh_tables_on_device(self) -> bool:
+        """Did the last setup_system form the DoF numbering, the constraints and the level flags through gmg_build_mesh_tables?"""
+        return bool(self.L.step50_mesh_tables_on_device(self.h))
 
     def device_system_matrix(self):
         """The system matrix as the device holds it after a cycle with "System matrix on device" (gmg_get_system_matrix)."""

@@ -370,6 +370,55 @@ int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, i
                                     const uint8_t *cell_level, int nq, const double *cell_coef, const double *G, const double *qw,
                                     const double *scale_of_level, const int32_t *constraint_of_dof, int64_t n_lines,
                                     const int64_t *line_ptr, const int32_t *line_master, const double *line_weight, double *build_ms);
+/* The inputs of the entries above -- DoF numbering, constraints and level flags -- formed on the device from the forest alone
+ * (dof_handler.distribute_dofs / distribute_mg_dofs, make_hanging_node_constraints, interpolate_boundary_values' line list and
+ * MGConstrainedDoFs, src/step-50.cc:661-706; LaplaceProblem::distribute_dofs and make_constraints on the host).
+ * Input: dim (2 or 3); the root lattice n0[3] (cells per direction, 1 .. 511; n0[2] is not read in 2D); n_levels (0 .. 13) and
+ * level_ptr [n_levels + 1] (level l owns the cells level_ptr[l] .. level_ptr[l + 1] - 1, level_ptr[0] = 0); for every cell of
+ * every level, in the host's index order, cell_coord [n][3] (in units of that level's cell size; z = 0 in 2D) and
+ * cell_first_child [n] (the index of child 0 inside the next level, the 2^dim children contiguous, or negative for an active
+ * cell); level0_lexicographic (0 or 1).  Vertex keys are x | y << 21 | z << 42 with the vertex coordinates shifted by
+ * 12 - level (what gmg_build_transfer takes with fine_spacing = 1 << (12 - fine level)).
+ * Definitions -- integer work, the results equal the host's arrays exactly and do not depend on the launch shape (option
+ * assemble_max_blocks):
+ *   active cells     the cells with first_child < 0 ordered by (level, index); cell_level[a] is the level.
+ *   active numbering slot s = a * 2^dim + v, v = bx + 2 by + 4 bz; the DoF of a vertex is the number of distinct vertices whose
+ *                    first slot lies before its own first slot (first-touch order).  cell_dofs, n_dofs, vertex_of_dof [n_dofs].
+ *   level numbering  the same rule over all cells of level l in index order; level 0 with level0_lexicographic = 1 must be the
+ *                    full lattice in lexicographic cell order (x fastest) and gets dof = x + (n0[0] + 1) (y + (n0[1] + 1) z).
+ *   dof_flags of a level   bit 0: the vertex lies on the domain boundary (a coordinate is 0 or n0[d] << 12); bit 1: the vertex
+ *                    belongs to a face of a level-l cell (l >= 1) that lies inside the domain and has no level-l cell behind it.
+ *   hanging lines    visit the active cells a ascending, then the direction d ascending, then side 0 before side 1; a face
+ *                    qualifies when the same-level neighbour across it exists and is not active.  Its corners are the cell's
+ *                    vertices on the face in ascending v; in 3D the constrained vertices are the face centre (masters: the 4
+ *                    corners, weights 1.0 / 4), then the mid-points of the edges (0,1), (2,3), (0,2), (1,3) (masters: the 2
+ *                    corners, weights 1.0 / 2), in 2D the one edge mid-point.  A vertex gets its line from the first visit
+ *                    that reaches it; lines are numbered in that order and list their masters in corner order.
+ *   Dirichlet lines  every DoF in ascending order whose vertex has bit-0 geometry and no hanging line gets the next line index;
+ *                    such a line has no entries.
+ * The lines come back UNCLOSED and without inhomogeneities (a master may itself carry a Dirichlet line): boundary values and
+ * close() stay with the caller.  The tables stay on the device, owned by the context, until the next build, gmg_reset or
+ * gmg_destroy; nothing else in the context changes.  build_ms (may be NULL): device time of the build.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a NULL array of nonzero
+ * length, a level_ptr that does not start at 0 or decreases, more than 13 levels, n0[d] outside 1 .. 511, a coordinate outside
+ * its level's lattice, a first_child that points outside the next level, or level0_lexicographic = 1 with a level 0 that is
+ * not the full lattice in lexicographic order; found on the device: the same cell twice in a level, or a hanging vertex without
+ * a DoF (the mesh is not 2:1 balanced).  GMG_ERR_UNSUPPORTED on a context with a communicator and for 2^31 slots or more.
+ * After ANY failure the context holds no mesh tables and the getters return GMG_ERR_INVALID.  Zero cells are valid.      */
+int gmg_build_mesh_tables(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                          const int32_t *cell_coord, const int32_t *cell_first_child, int level0_lexicographic, double *build_ms);
+/* The tables of the last gmg_build_mesh_tables.  Sizes: n_cells (active cells), n_dofs, n_hanging (lines 0 .. n_hanging - 1 are
+ * the hanging lines), n_lines, n_entries (= line_ptr[n_lines]).  Arrays -- any may be NULL and is then skipped, so a first call
+ * with all of them NULL returns the sizes: cell_dofs [n_cells * 2^dim], cell_level [n_cells], vertex_of_dof [n_dofs],
+ * constraint_of_dof [n_dofs] (-1 or a line index), line_ptr [n_lines + 1], line_master / line_weight [n_entries] in the CSR
+ * form gmg_assemble_system_matrix takes, line_dof [n_lines] (the DoF each line constrains).                                */
+int gmg_get_mesh_tables(gmg_context *ctx, int64_t *n_cells, int64_t *n_dofs, int64_t *n_hanging, int64_t *n_lines,
+                        int64_t *n_entries, int32_t *cell_dofs, uint8_t *cell_level, uint64_t *vertex_of_dof,
+                        int32_t *constraint_of_dof, int64_t *line_ptr, int32_t *line_master, double *line_weight, int32_t *line_dof);
+/* One level of them: n_cells, n_dofs, cell_dofs [n_cells * 2^dim], vertex_of_dof [n_dofs], dof_flags [n_dofs] (what
+ * gmg_assemble_level_matrix takes); NULL arrays are skipped.  GMG_ERR_INVALID for a level the build did not have.          */
+int gmg_get_mesh_level_tables(gmg_context *ctx, int level, int64_t *n_cells, int64_t *n_dofs, int32_t *cell_dofs,
+                              uint64_t *vertex_of_dof, uint8_t *dof_flags);
 /* The right-hand side of LaplaceProblem::assemble_system formed on the device from the cell tables, without a host plan
  * (gmg_rhs_assemble wants gather lists that the host walks every cell to build): cell_dofs, cell_level, constraint_of_dof and
  * the lines are exactly what gmg_assemble_system_matrix takes, nv = 2^dim; new are line_inhomogeneity [n_lines], the
