@@ -29,6 +29,7 @@ SYMBOLS = [
     "gmg_assemble_level_matrix", "gmg_get_level_matrix", "gmg_assemble_system_matrix_coef", "gmg_assemble_level_matrix_coef",
     "gmg_assemble_rhs", "gmg_distribute_constraints",
     "gmg_build_mesh_tables", "gmg_get_mesh_tables", "gmg_get_mesh_level_tables",
+    "gmg_refine_forest", "gmg_get_refined_forest", "gmg_transfer_solution", "gmg_build_face_table",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -248,6 +249,76 @@ class Context:
         cd, vk, fl = np.zeros(nc.value << self._mesh_dim(dim), dtype=np.int32), np.zeros(nd.value, dtype=np.uint64), np.zeros(nd.value, dtype=np.uint8)
         self._chk(self.L.gmg_get_mesh_level_tables(self.h, C.c_int(int(level)), C.byref(nc), C.byref(nd), _p(cd, C.c_int32), _p(vk, C.c_uint64), _p(fl, C.c_uint8)))
         return SimpleNamespace(n_cells=nc.value, n_dofs=nd.value, cell_dofs=cd, vertex_of_dof=vk, dof_flags=fl)
+
+    @staticmethod
+    def _forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels):
+        """the forest as the entries take it; None for an array passes NULL.  Returns (ctypes arguments, arrays to keep alive)"""
+        def opt(a, dt, ct):
+            if a is None:
+                return None, None
+            a = np.ascontiguousarray(a, dtype=dt)
+            return a, _p(a, ct)
+        lp, lp_p = opt(level_ptr, np.int64, C.c_int64)
+        cc, cc_p = opt(cell_coord, np.int32, C.c_int32)
+        fc, fc_p = opt(cell_first_child, np.int32, C.c_int32)
+        n03 = None if n0 is None else (C.c_int32 * 3)(*[int(v) for v in n0])
+        if n_levels is None:
+            n_levels = len(lp) - 1
+        return (C.c_int(int(dim)), n03, C.c_int(int(n_levels)), lp_p, cc_p, fc_p), (lp, cc, fc, n03)
+
+    def refine_forest(self, dim, n0, level_ptr, cell_coord, cell_first_child, flag, n_levels=None):
+        """The 2:1 closure of the marks and the split (gmg_refine_forest); the new forest stays on the device
+        (get_refined_forest).  Returns namespace(n_levels, n_cells, n_split, build_ms)."""
+        from types import SimpleNamespace
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        fl = None if flag is None else np.ascontiguousarray(flag, dtype=np.uint8)
+        nl, nc, ns, ms = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
+        self._chk(self.L.gmg_refine_forest(self.h, *args, None if fl is None else _p(fl, C.c_uint8), C.byref(nl), C.byref(nc), C.byref(ns), C.byref(ms)))
+        return SimpleNamespace(n_levels=nl.value, n_cells=nc.value, n_split=ns.value, build_ms=ms.value)
+
+    def get_refined_forest(self):
+        """The forest of the last refine_forest as numpy arrays: namespace(n_levels, n_cells, n_split, level_ptr, cell_coord
+        [n, 3], cell_first_child, cell_parent, closed_flag [cells of the forest that went in])"""
+        from types import SimpleNamespace
+        nl, nc, nf, ns = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_refined_forest(self.h, C.byref(nl), C.byref(nc), C.byref(nf), C.byref(ns), None, None, None, None, None))
+        lp, cc = np.zeros(nl.value + 1, dtype=np.int64), np.zeros((nc.value, 3), dtype=np.int32)
+        fc, pa, cl = np.zeros(nc.value, dtype=np.int32), np.zeros(nc.value, dtype=np.int32), np.zeros(nf.value, dtype=np.uint8)
+        self._chk(self.L.gmg_get_refined_forest(self.h, None, None, None, None, _p(lp, C.c_int64), _p(cc, C.c_int32), _p(fc, C.c_int32), _p(pa, C.c_int32),
+                                                _p(cl, C.c_uint8)))
+        return SimpleNamespace(n_levels=nl.value, n_cells=nc.value, n_split=ns.value, level_ptr=lp, cell_coord=cc, cell_first_child=fc, cell_parent=pa,
+                               closed_flag=cl)
+
+    def transfer_solution(self, dim, n0, level_ptr, cell_coord, cell_first_child, old_vertex_of_dof, u_old, new_vertex_of_dof, constraint_of_dof, u_new,
+                          n_levels=None, n_old=None, n_new=None):
+        """SolutionTransfer::interpolate + constraints.set_zero on the new forest (gmg_transfer_solution): u_old and u_new are
+        DeviceVectors (or None: NULL), the vertex lists and constraint_of_dof host arrays (None: NULL).  Returns the device
+        time in ms."""
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        ov = None if old_vertex_of_dof is None else np.ascontiguousarray(old_vertex_of_dof, dtype=np.uint64)
+        nv = None if new_vertex_of_dof is None else np.ascontiguousarray(new_vertex_of_dof, dtype=np.uint64)
+        co = None if constraint_of_dof is None else np.ascontiguousarray(constraint_of_dof, dtype=np.int32)
+        n_old = (0 if ov is None else len(ov)) if n_old is None else n_old
+        n_new = (0 if nv is None else len(nv)) if n_new is None else n_new
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_transfer_solution(self.h, *args, C.c_int64(n_old), None if ov is None else _p(ov, C.c_uint64), None if u_old is None else u_old.ptr,
+                                               C.c_int64(n_new), None if nv is None else _p(nv, C.c_uint64), None if co is None else _p(co, C.c_int32),
+                                               None if u_new is None else u_new.ptr, C.byref(ms)))
+        return ms.value
+
+    def build_face_table(self, dim, n0, level_ptr, cell_coord, cell_first_child, n_levels=None):
+        """The estimator's face table from the forest (gmg_build_face_table): namespace(n_active, face_kind [n_active, 2 dim],
+        face_cell [n_active, 2 dim, 2^(dim-1)], build_ms)"""
+        from types import SimpleNamespace
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        na, ms = C.c_int64(0), C.c_double(0)
+        self._chk(self.L.gmg_build_face_table(self.h, *args, C.byref(na), None, None, None))
+        dim = int(dim)
+        fk, fcell = np.zeros((na.value, 2 * dim), dtype=np.uint8), np.zeros((na.value, 2 * dim, 1 << (dim - 1)), dtype=np.int32)
+        # (a buffer of one entry stands in for an empty array: the arrays' being NULL asks for the size alone)
+        k1, c1 = (fk, fcell) if na.value else (np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.int32))
+        self._chk(self.L.gmg_build_face_table(self.h, *args, C.byref(na), _p(k1, C.c_uint8), _p(c1, C.c_int32), C.byref(ms)))
+        return SimpleNamespace(n_active=na.value, face_kind=fk, face_cell=fcell, build_ms=ms.value)
 
     def set_copy_indices(self, level, global_idx, level_idx):
         g = np.ascontiguousarray(global_idx, dtype=np.int32)

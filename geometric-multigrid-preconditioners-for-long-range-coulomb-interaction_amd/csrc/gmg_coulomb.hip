@@ -24,6 +24,7 @@
 #include "gmg_estimate.hpp"
 #include "gmg_fastdiag.hpp"
 #include "gmg_mesh_tables.hpp"
+#include "gmg_refine.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -166,6 +167,16 @@ struct MeshTables {
   std::vector<PerLevel> level;
 };
 
+// what gmg_refine_forest leaves on the device (gmg_refine.hpp): valid until the next refinement, gmg_reset or gmg_destroy
+struct RefinedForest {
+  bool valid = false;
+  int n_levels = 0;
+  int64_t n_cells = 0, n_flags = 0, n_split = 0;  // new cells of all levels, cells of the forest that went in, cells split
+  std::vector<int64_t> level_ptr;
+  DevPtr<int32_t> coord, first_child, parent;
+  DevPtr<uint8_t> closed;  // [n_flags]
+};
+
 }  // namespace
 
 struct gmg_context {
@@ -256,6 +267,7 @@ struct gmg_context {
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
   MeshTables mesh;              // gmg_build_mesh_tables: the tables of the last build
+  RefinedForest refined;        // gmg_refine_forest: the forest of the last refinement
   int estimate_max_blocks = 0;  // gmg_estimate.hpp: the same cap for the estimator's kernels (option "estimate_max_blocks"); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
@@ -2752,6 +2764,40 @@ hipError_t mesh_fetch(gmg_context *ctx, T *dst, const DevPtr<T> &src, int64_t n)
   return hipMemcpyAsync(dst, src.get(), sizeof(T) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream);
 }
 
+// The host-side checks of every entry that takes the forest, before anything is launched (gmg_build_mesh_tables in
+// include/gmg_coulomb.h is the definition); level_of [cells of all levels]: the level of every cell
+int check_forest(gmg_context *ctx, const char *who, int dim, const int32_t *n0, int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                 const int32_t *cell_first_child, std::vector<uint8_t> &level_of) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_levels < 0 || n_levels > kMtShift + 1) return bad(GMG_ERR_INVALID, "between 0 and 13 levels");
+  if (!n0 || !level_ptr) return bad(GMG_ERR_INVALID, "n0 or level_ptr is NULL");
+  for (int d = 0; d < dim; ++d)
+    if (n0[d] < 1 || n0[d] > 511) return bad(GMG_ERR_INVALID, "n0 outside 1 .. 511");
+  if (level_ptr[0] != 0) return bad(GMG_ERR_INVALID, "level_ptr does not start at 0");
+  for (int l = 0; l < n_levels; ++l)
+    if (level_ptr[l + 1] < level_ptr[l]) return bad(GMG_ERR_INVALID, "level_ptr decreases");
+  const int nv = 1 << dim;
+  const int64_t n_all = level_ptr[n_levels];
+  if (n_all > 0 && (!cell_coord || !cell_first_child)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_all * nv >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 slots");
+  const int32_t lat[3] = {n0[0], n0[1], dim == 3 ? n0[2] : 1};
+  level_of.assign((size_t)n_all, 0);
+  for (int l = 0; l < n_levels; ++l) {
+    const int64_t n_next = l + 1 < n_levels ? level_ptr[l + 2] - level_ptr[l + 1] : 0;
+    for (int64_t c = level_ptr[l]; c < level_ptr[l + 1]; ++c) {
+      level_of[(size_t)c] = (uint8_t)l;
+      for (int d = 0; d < 3; ++d) {
+        const int64_t x = cell_coord[3 * c + d], n = d < dim ? (int64_t)lat[d] << l : 1;
+        if (x < 0 || x >= n) return bad(GMG_ERR_INVALID, "a cell outside its level's lattice");
+      }
+      const int64_t fc = cell_first_child[c];
+      if (fc >= 0 && fc + nv > n_next) return bad(GMG_ERR_INVALID, "first_child points outside the next level");
+    }
+  }
+  return GMG_OK;
+}
+
 DevCSR *which_matrix(gmg_context *ctx, int which) {
   if (which == GMG_SYSTEM) return &ctx->S;
   if (which < 0 || which >= ctx->n_levels) return nullptr;
@@ -2830,6 +2876,7 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   release_operators(ctx);
   free_locator(ctx);
   ctx->mesh = MeshTables();
+  ctx->refined = RefinedForest();
   ctx->n_levels = n_levels;
   ctx->lv.clear();
   ctx->lv.resize((size_t)n_levels);
@@ -4010,32 +4057,11 @@ int gmg_build_mesh_tables(gmg_context *ctx, int dim, const int32_t n0[3], int n_
   ctx->mesh = MeshTables();  // after any failure the context holds no mesh tables
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string("gmg_build_mesh_tables: ") + msg).c_str()); };
   if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
-  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
-  if (n_levels < 0 || n_levels > kMtShift + 1) return bad(GMG_ERR_INVALID, "between 0 and 13 levels");
-  if (!n0 || !level_ptr) return bad(GMG_ERR_INVALID, "n0 or level_ptr is NULL");
-  for (int d = 0; d < dim; ++d)
-    if (n0[d] < 1 || n0[d] > 511) return bad(GMG_ERR_INVALID, "n0 outside 1 .. 511");
-  if (level_ptr[0] != 0) return bad(GMG_ERR_INVALID, "level_ptr does not start at 0");
-  for (int l = 0; l < n_levels; ++l)
-    if (level_ptr[l + 1] < level_ptr[l]) return bad(GMG_ERR_INVALID, "level_ptr decreases");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, "gmg_build_mesh_tables", dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
   const int nv = 1 << dim, nf = 2 * dim;
   const int64_t n_all = level_ptr[n_levels];
-  if (n_all > 0 && (!cell_coord || !cell_first_child)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
-  if (n_all * nv >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 slots");
   const int32_t lat[3] = {n0[0], n0[1], dim == 3 ? n0[2] : 1};
-  std::vector<uint8_t> level_of((size_t)n_all);
-  for (int l = 0; l < n_levels; ++l) {
-    const int64_t n_next = l + 1 < n_levels ? level_ptr[l + 2] - level_ptr[l + 1] : 0;
-    for (int64_t c = level_ptr[l]; c < level_ptr[l + 1]; ++c) {
-      level_of[(size_t)c] = (uint8_t)l;
-      for (int d = 0; d < 3; ++d) {
-        const int64_t x = cell_coord[3 * c + d], n = d < dim ? (int64_t)lat[d] << l : 1;
-        if (x < 0 || x >= n) return bad(GMG_ERR_INVALID, "a cell outside its level's lattice");
-      }
-      const int64_t fc = cell_first_child[c];
-      if (fc >= 0 && fc + nv > n_next) return bad(GMG_ERR_INVALID, "first_child points outside the next level");
-    }
-  }
   const int64_t n_l0 = n_levels > 0 ? level_ptr[1] : 0;
   const bool lattice0 = level0_lexicographic != 0 && n_all > 0;
   if (lattice0) {  // level 0 must be the full lattice, x fastest
@@ -4259,6 +4285,302 @@ int gmg_get_mesh_level_tables(gmg_context *ctx, int level, int64_t *n_cells, int
   HIPC(mesh_fetch(ctx, (unsigned long long *)vertex_of_dof, L.vertex_of_dof, L.n_dofs));
   HIPC(mesh_fetch(ctx, dof_flags, L.dof_flags, L.n_dofs));
   HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+// ---- the step between two cycles from the forest alone (gmg_refine.hpp)
+
+namespace {
+
+// the forest on the device with every level's cells by coordinates (mt_cell_insert_kernel); level[l] for l = 0 .. n_levels - 1
+struct ForestDev {
+  DevPtr<int32_t> coord, fc, cidx;
+  DevPtr<uint8_t> lvl;
+  DevPtr<unsigned long long> ckeys;
+  DevPtr<int> err;
+  std::vector<RfLevel> level;
+  MtForest f{};
+  int64_t n_all = 0;
+};
+
+unsigned long long rf_table_size(int64_t n) { unsigned long long t = 1024; while ((int64_t)t < 2 * n) t <<= 1; return t; }
+
+// the flag word once the stream has been waited for; rc: what it means
+int rf_flagged(gmg_context *ctx, const char *who, const DevPtr<int> &d_err, int &rc) {
+  int err = 0;
+  HIPC(hipMemcpyAsync(&err, d_err.get(), sizeof err, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  const char *msg = err & kMtErrDuplicate    ? "the same cell or vertex appears twice"
+                    : err & kMtErrUnbalanced ? "a neighbour position without a cell on the level below: the forest is not vertex-balanced"
+                    : err & kRfErrOrphan     ? "a cell without a parent"
+                    : err & kRfErrMissing    ? "a vertex without a value: the old vertices do not cover the parents of the new ones"
+                    : err & kRfErrFace       ? "mesh not 2:1 balanced across a face"
+                    : err & kMtErrFull       ? "a hash table filled up"
+                                             : nullptr;
+  rc = msg ? fail(ctx, err & ~(kMtErrFull) ? GMG_ERR_INVALID : GMG_ERR_HIP, (std::string(who) + ": " + msg).c_str()) : (int)GMG_OK;
+  return GMG_OK;
+}
+
+int forest_to_device(gmg_context *ctx, const char *who, int dim, const int32_t *n0, int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                     const int32_t *cell_first_child, const std::vector<uint8_t> &level_of, ForestDev &d, int &rc) {
+  const int64_t n_all = level_ptr[n_levels];
+  d.n_all = n_all;
+  HIPC(upload(d.coord, cell_coord, (size_t)n_all * 3, ctx->stream));
+  HIPC(upload(d.fc, cell_first_child, (size_t)n_all, ctx->stream));
+  HIPC(upload(d.lvl, level_of, ctx->stream));
+  HIPC(d.err.alloc(1));
+  HIPC(hipMemsetAsync(d.err.get(), 0, sizeof(int), ctx->stream));
+  MtForest &f = d.f;
+  f.coord = d.coord.get(); f.first_child = d.fc.get(); f.level = d.lvl.get(); f.dim = dim; f.nv = 1 << dim; f.nf = 2 * dim;
+  for (int e = 0; e < 3; ++e) { f.n0[e] = e < dim ? n0[e] : 1; f.hi[e] = (unsigned long long)f.n0[e] << kMtShift; }
+  std::vector<unsigned long long> off((size_t)n_levels + 1, 0);
+  for (int l = 0; l < n_levels; ++l) off[(size_t)l + 1] = off[(size_t)l] + rf_table_size(level_ptr[l + 1] - level_ptr[l]);
+  const size_t total = (size_t)std::max<unsigned long long>(off[(size_t)n_levels], 1);
+  HIPC(d.ckeys.alloc(total));
+  HIPC(d.cidx.alloc(total));
+  HIPC(hipMemsetAsync(d.ckeys.get(), 0xff, sizeof(unsigned long long) * total, ctx->stream));
+  d.level.resize((size_t)n_levels);
+  for (int l = 0; l < n_levels; ++l) {
+    RfLevel &L = d.level[(size_t)l];
+    L.keys = d.ckeys.get() + off[(size_t)l]; L.index = d.cidx.get() + off[(size_t)l]; L.mask = off[(size_t)l + 1] - off[(size_t)l] - 1;
+    L.begin = level_ptr[l]; L.n = level_ptr[l + 1] - level_ptr[l];
+    if (L.n)
+      hipLaunchKernelGGL(mt_cell_insert_kernel, asm_blocks(ctx, L.n, kMtThreads), dim3(kMtThreads), 0, ctx->stream, f, L.begin, L.n, d.ckeys.get() + off[(size_t)l],
+                         d.cidx.get() + off[(size_t)l], L.mask, d.err.get());
+  }
+  CHK(rf_flagged(ctx, who, d.err, rc));  // (a cell met twice or a full table leaves positions without an index)
+  return GMG_OK;
+}
+
+float rf_elapsed(Event &e0, Event &e1) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  return ms;
+}
+
+}  // namespace
+
+int gmg_refine_forest(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                      const int32_t *cell_first_child, const uint8_t *flag, int *new_n_levels, int64_t *new_n_cells, int64_t *n_split, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_refine_forest";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  const int nv = 1 << dim;
+  const int64_t n_all = level_ptr[n_levels];
+  if (n_all > 0 && !flag) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  ForestDev d;
+  DevPtr<uint8_t> d_flag, d_F;
+  DevPtr<int32_t> d_rank;
+  Event e0, e1;
+  RefinedForest out;
+  int rc = GMG_OK;
+  HIPC(upload(d_flag, flag, (size_t)n_all, ctx->stream));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  CHK(forest_to_device(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of, d, rc));
+  if (rc != GMG_OK) return rc;
+  const dim3 blk(kMtThreads);
+  // 1. the closure, from the finest level down to level 1
+  HIPC(d_F.alloc((size_t)std::max<int64_t>(n_all, 1)));
+  HIPC(d_rank.alloc((size_t)n_all + 1));
+  if (n_all) hipLaunchKernelGGL(rf_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d.fc.get(), (const uint8_t *)d_flag.get(), n_all, d_F.get());
+  for (int l = n_levels - 1; l >= 1; --l) {
+    const RfLevel &cur = d.level[(size_t)l];
+    if (cur.n)
+      hipLaunchKernelGGL(rf_closure_kernel, asm_blocks(ctx, cur.n * (dim == 3 ? 27 : 9), kMtThreads), blk, 0, ctx->stream, d.f, l, cur, d.level[(size_t)l - 1], d_F.get(), d.err.get());
+  }
+  // 2. the rank of every split cell, and with it the sizes
+  if (n_all) hipLaunchKernelGGL(rf_split_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const uint8_t *)d_F.get(), n_all, d_rank.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_rank.get(), n_all);
+  std::vector<int32_t> rank_at((size_t)n_levels + 1, 0);
+  for (int l = 0; l <= n_levels; ++l)
+    HIPC(hipMemcpyAsync(&rank_at[(size_t)l], d_rank.get() + level_ptr[l], sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  CHK(rf_flagged(ctx, who, d.err, rc));  // (before anything is sized by the ranks)
+  if (rc != GMG_OK) return rc;
+  const int64_t split_last = n_levels > 0 ? rank_at[(size_t)n_levels] - rank_at[(size_t)n_levels - 1] : 0;
+  out.n_levels = n_levels + (split_last > 0 ? 1 : 0);
+  if (out.n_levels > kMtShift + 1) return bad(GMG_ERR_UNSUPPORTED, "a split on level 12: no level beyond 12");
+  out.n_flags = n_all;
+  out.n_split = rank_at[(size_t)n_levels];
+  out.n_cells = n_all + (int64_t)nv * out.n_split;
+  if (out.n_cells * nv >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 slots");
+  out.level_ptr.assign((size_t)out.n_levels + 1, 0);
+  std::vector<int64_t> old_size((size_t)out.n_levels + 1, 0);
+  for (int l = 0; l < n_levels; ++l) old_size[(size_t)l] = level_ptr[l + 1] - level_ptr[l];
+  for (int l = 0; l < out.n_levels; ++l)
+    out.level_ptr[(size_t)l + 1] = out.level_ptr[(size_t)l] + old_size[(size_t)l] + (l > 0 ? (int64_t)nv * (rank_at[(size_t)l] - rank_at[(size_t)l - 1]) : 0);
+  // 3. the new forest
+  HIPC(out.coord.alloc((size_t)std::max<int64_t>(out.n_cells * 3, 1)));
+  HIPC(out.first_child.alloc((size_t)std::max<int64_t>(out.n_cells, 1)));
+  HIPC(out.parent.alloc((size_t)std::max<int64_t>(out.n_cells, 1)));
+  for (int l = 0; l < n_levels; ++l) {
+    const RfLevel &cur = d.level[(size_t)l];
+    if (!cur.n) continue;
+    RfSplit s{};
+    s.F = d_F.get(); s.rank = d_rank.get(); s.rank_base = rank_at[(size_t)l];
+    s.new_begin = out.level_ptr[(size_t)l];
+    s.new_begin_next = l + 1 < out.n_levels ? out.level_ptr[(size_t)l + 1] : out.n_cells;  // (no next level: nothing of this one is split)
+    s.old_size_next = old_size[(size_t)l + 1];
+    s.coord = out.coord.get(); s.first_child = out.first_child.get(); s.parent = out.parent.get();
+    hipLaunchKernelGGL(rf_split_kernel, asm_blocks(ctx, cur.n, kMtThreads), blk, 0, ctx->stream, d.f, l, cur, l > 0 ? d.level[(size_t)l - 1] : RfLevel{}, s, d.err.get());
+  }
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  CHK(rf_flagged(ctx, who, d.err, rc));
+  if (rc != GMG_OK) return rc;
+  CHK(launch_status(ctx));
+  out.closed = std::move(d_F);
+  out.valid = true;
+  if (new_n_levels) *new_n_levels = out.n_levels;
+  if (new_n_cells) *new_n_cells = out.n_cells;
+  if (n_split) *n_split = out.n_split;
+  if (build_ms) *build_ms = rf_elapsed(e0, e1);
+  ctx->refined = std::move(out);
+  return GMG_OK;
+}
+
+int gmg_get_refined_forest(gmg_context *ctx, int *n_levels, int64_t *n_cells, int64_t *n_flags, int64_t *n_split, int64_t *level_ptr, int32_t *cell_coord,
+                           int32_t *cell_first_child, int32_t *cell_parent, uint8_t *closed_flag) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const RefinedForest &r = ctx->refined;
+  if (!r.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_refined_forest: the context holds no refined forest");
+  (void)hipSetDevice(ctx->device);
+  if (n_levels) *n_levels = r.n_levels;
+  if (n_cells) *n_cells = r.n_cells;
+  if (n_flags) *n_flags = r.n_flags;
+  if (n_split) *n_split = r.n_split;
+  if (level_ptr) std::copy(r.level_ptr.begin(), r.level_ptr.end(), level_ptr);
+  HIPC(mesh_fetch(ctx, cell_coord, r.coord, r.n_cells * 3));
+  HIPC(mesh_fetch(ctx, cell_first_child, r.first_child, r.n_cells));
+  HIPC(mesh_fetch(ctx, cell_parent, r.parent, r.n_cells));
+  HIPC(mesh_fetch(ctx, closed_flag, r.closed, r.n_flags));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+int gmg_transfer_solution(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                          const int32_t *cell_first_child, int64_t n_old, const uint64_t *old_vertex_of_dof, const double *u_old, int64_t n_new,
+                          const uint64_t *new_vertex_of_dof, const int32_t *constraint_of_dof, double *u_new, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_transfer_solution";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  if (n_old < 0 || n_new < 0) return bad(GMG_ERR_INVALID, "a negative number of DoFs");
+  if ((n_old > 0 && (!old_vertex_of_dof || !u_old)) || (n_new > 0 && (!new_vertex_of_dof || !u_new))) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_old >= ((int64_t)1 << 31) || n_new >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs");
+  const int nv = 1 << dim;
+  const int64_t n_all = level_ptr[n_levels], begin1 = n_levels > 0 ? level_ptr[1] : 0;
+  DevPtr<int32_t> d_coord, d_fc, d_oidx, d_nidx, d_cons;
+  DevPtr<uint8_t> d_lvl, d_have;
+  DevPtr<unsigned long long> d_overt, d_nvert, d_okeys, d_nkeys;
+  DevPtr<double> d_u;
+  DevPtr<int> d_err;
+  Event e0, e1;
+  int rc = GMG_OK;
+  HIPC(upload(d_coord, cell_coord, (size_t)n_all * 3, ctx->stream));
+  HIPC(upload(d_fc, cell_first_child, (size_t)n_all, ctx->stream));
+  HIPC(upload(d_lvl, level_of, ctx->stream));
+  HIPC(upload(d_overt, (const unsigned long long *)old_vertex_of_dof, (size_t)n_old, ctx->stream));
+  HIPC(upload(d_nvert, (const unsigned long long *)new_vertex_of_dof, (size_t)n_new, ctx->stream));
+  if (constraint_of_dof) HIPC(upload(d_cons, constraint_of_dof, (size_t)n_new, ctx->stream));
+  HIPC(d_err.alloc(1));
+  HIPC(hipMemsetAsync(d_err.get(), 0, sizeof(int), ctx->stream));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  MtForest f{};
+  f.coord = d_coord.get(); f.first_child = d_fc.get(); f.level = d_lvl.get(); f.dim = dim; f.nv = nv; f.nf = 2 * dim;
+  for (int e = 0; e < 3; ++e) { f.n0[e] = e < dim ? n0[e] : 1; f.hi[e] = (unsigned long long)f.n0[e] << kMtShift; }
+  const unsigned long long o_size = rf_table_size(n_old), n_size = rf_table_size(n_new);
+  HIPC(d_okeys.alloc(o_size));
+  HIPC(d_oidx.alloc(o_size));
+  HIPC(d_nkeys.alloc(n_size));
+  HIPC(d_nidx.alloc(n_size));
+  HIPC(d_have.alloc((size_t)std::max<int64_t>(n_new, 1)));
+  HIPC(d_u.alloc((size_t)std::max<int64_t>(n_new, 1)));
+  HIPC(hipMemsetAsync(d_okeys.get(), 0xff, sizeof(unsigned long long) * o_size, ctx->stream));
+  HIPC(hipMemsetAsync(d_nkeys.get(), 0xff, sizeof(unsigned long long) * n_size, ctx->stream));
+  const dim3 blk(kMtThreads);
+  if (n_old) hipLaunchKernelGGL(rf_vertex_insert_kernel, asm_blocks(ctx, n_old, kMtThreads), blk, 0, ctx->stream, (const unsigned long long *)d_overt.get(), n_old, d_okeys.get(), d_oidx.get(), o_size - 1, d_err.get());
+  if (n_new) hipLaunchKernelGGL(rf_vertex_insert_kernel, asm_blocks(ctx, n_new, kMtThreads), blk, 0, ctx->stream, (const unsigned long long *)d_nvert.get(), n_new, d_nkeys.get(), d_nidx.get(), n_size - 1, d_err.get());
+  CHK(rf_flagged(ctx, who, d_err, rc));  // (a vertex met twice or a full table leaves positions without an index)
+  if (rc != GMG_OK) return rc;
+  RfTransfer t{};
+  t.okeys = d_okeys.get(); t.nkeys = d_nkeys.get(); t.oidx = d_oidx.get(); t.nidx = d_nidx.get(); t.omask = o_size - 1; t.nmask = n_size - 1;
+  t.u_old = u_old; t.u_new = d_u.get(); t.have = d_have.get(); t.err = d_err.get();
+  const int64_t n_slots = (n_all - begin1) * nv;
+  if (n_new) hipLaunchKernelGGL(rf_transfer_old_kernel, asm_blocks(ctx, n_new, kMtThreads), blk, 0, ctx->stream, t, (const unsigned long long *)d_nvert.get(), n_new);
+  if (n_slots) hipLaunchKernelGGL(rf_transfer_interp_kernel, asm_blocks(ctx, n_slots, kMtThreads), blk, 0, ctx->stream, f, begin1, n_slots, t);
+  if (n_new) hipLaunchKernelGGL(rf_transfer_finish_kernel, asm_blocks(ctx, n_new, kMtThreads), blk, 0, ctx->stream, t, (const int32_t *)d_cons.get(), n_new);
+  CHK(rf_flagged(ctx, who, d_err, rc));
+  if (rc != GMG_OK) return rc;
+  CHK(launch_status(ctx));
+  if (n_new) HIPC(hipMemcpyAsync(u_new, d_u.get(), sizeof(double) * (size_t)n_new, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (build_ms) *build_ms = rf_elapsed(e0, e1);
+  return GMG_OK;
+}
+
+int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                         const int32_t *cell_first_child, int64_t *n_active, uint8_t *face_kind, int32_t *face_cell, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_build_face_table";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  const int nv = 1 << dim, nf = 2 * dim, nfc = nv / 2;
+  const int64_t n_all = level_ptr[n_levels];
+  int64_t na = 0;
+  for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
+  if (!face_kind && !face_cell) {  // the size alone
+    if (n_active) *n_active = na;
+    return GMG_OK;
+  }
+  if (na > 0 && (!face_kind || !face_cell)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  ForestDev d;
+  DevPtr<int32_t> d_apos, d_cell;
+  DevPtr<uint8_t> d_kind;
+  Event e0, e1;
+  int rc = GMG_OK;
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  CHK(forest_to_device(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of, d, rc));
+  if (rc != GMG_OK) return rc;
+  const dim3 blk(kMtThreads);
+  const size_t nk = (size_t)std::max<int64_t>(na * nf, 1), ncell = nk * (size_t)nfc;
+  HIPC(d_apos.alloc((size_t)n_all + 1));
+  HIPC(d_kind.alloc(nk));
+  HIPC(d_cell.alloc(ncell));
+  HIPC(hipMemsetAsync(d_kind.get(), 0, nk, ctx->stream));
+  HIPC(hipMemsetAsync(d_cell.get(), 0, sizeof(int32_t) * ncell, ctx->stream));
+  if (n_all) hipLaunchKernelGGL(mt_active_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d.fc.get(), n_all, d_apos.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_apos.get(), n_all);
+  for (int l = 0; l < n_levels; ++l) {
+    const RfLevel &cur = d.level[(size_t)l];
+    if (cur.n)
+      hipLaunchKernelGGL(rf_face_kernel, asm_blocks(ctx, cur.n * nf, kMtThreads), blk, 0, ctx->stream, d.f, l, cur, l > 0 ? d.level[(size_t)l - 1] : RfLevel{}, level_ptr[l + 1],
+                         (const int32_t *)d_apos.get(), d_kind.get(), d_cell.get(), d.err.get());
+  }
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  CHK(rf_flagged(ctx, who, d.err, rc));
+  if (rc != GMG_OK) return rc;
+  CHK(launch_status(ctx));
+  HIPC(mesh_fetch(ctx, face_kind, d_kind, na * nf));
+  HIPC(mesh_fetch(ctx, face_cell, d_cell, na * nf * nfc));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (n_active) *n_active = na;
+  if (build_ms) *build_ms = rf_elapsed(e0, e1);
   return GMG_OK;
 }
 

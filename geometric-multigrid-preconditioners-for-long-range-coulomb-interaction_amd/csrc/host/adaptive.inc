@@ -263,7 +263,8 @@ typename LaplaceProblem<dim>::EstimatorInputs LaplaceProblem<dim>::estimator_inp
     if (active_cells[a].level > 15) throw std::runtime_error("Error estimator on device: more than 16 levels");
     in.cell_level[a] = (uint8_t)active_cells[a].level;
   }
-  face_table(in.face_kind, in.face_cell);
+  if (decide_refinement_on_device()) face_table_on_device(in.face_kind, in.face_cell);
+  else face_table(in.face_kind, in.face_cell);
   // the per-level factors exactly as the host loop forms them
   for (int l = 0; l < 16; ++l) {
     const double h = triangulation.cell_size(l);
@@ -377,13 +378,21 @@ template <int dim>
 void LaplaceProblem<dim>::refine_grid(unsigned int cycle) {
   constexpr int nv = 1 << dim;
   if (refine_flags.empty()) throw std::runtime_error("refine_grid: no cells were marked (run the estimator first)");
+  refined_on_device = decide_refinement_on_device();
+  if (refined_on_device) { refine_grid_on_device(cycle); return; }
   // values of the previous (distributed) solution by vertex
   FlatMap<double> value_of_vertex;
   value_of_vertex.reserve(vertex_of_dof.size() * 2);
   sublap(nullptr);
   for (size_t i = 0; i < vertex_of_dof.size(); ++i) value_of_vertex.emplace(vertex_of_dof[i], solution[i]);
   sublap("refine: values by vertex");
+  // (a mark counts only on an active cell: refine_flagged skips the others, the record of the closure leaves them out)
+  for (size_t l = 0; l < refine_flags.size() && l < triangulation.levels.size(); ++l)
+    for (size_t c = 0; c < refine_flags[l].size() && c < triangulation.levels[l].size(); ++c)
+      if (triangulation.levels[l][c].first_child >= 0) refine_flags[l][c] = 0;
   triangulation.refine_flagged(refine_flags);
+  closed_refine_flags.clear();
+  for (const auto &lv : refine_flags) closed_refine_flags.insert(closed_refine_flags.end(), lv.begin(), lv.end());
   refine_flags.clear();
   sublap("refine: refine_flagged");
   setup_system(cycle);
@@ -418,6 +427,100 @@ void LaplaceProblem<dim>::refine_grid(unsigned int cycle) {
   set_zero_constraints(solution);  // :1119
   initial_guess = solution;
   sublap("refine: interpolate");
+}
+
+// ---- "Refinement on device" (DESIGN.md section 21)
+
+// Is this cycle one whose refinement, transfer and face table the device forms?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_refinement_on_device() {
+  if (!par.refinement_on_device) return false;
+  const char *why = !solve_on_device_requested ? "the cycle does not run on the device" : distributed ? "the run is distributed" : nullptr;
+  if (!why) return true;
+  if (!refinement_fallback_reported) pcout(std::string("   Refinement on device: not applicable (") + why + "), refined on the host");
+  refinement_fallback_reported = true;
+  return false;
+}
+
+template <int dim>
+void LaplaceProblem<dim>::face_table_on_device(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) {
+  constexpr int nfc = 1 << (dim - 1);
+  if (ensure_context() != GMG_OK) throw std::runtime_error("Refinement on device: context: " + last_error);
+  const ForestCells fc = forest_cells();
+  const size_t nc = active_cells.size();
+  face_kind.assign(nc * 2 * dim, 0);
+  face_cell.assign(nc * 2 * dim * nfc, 0);
+  int64_t n_active = 0;
+  double build_ms = 0.0;
+  sublap(nullptr);
+  if (gmg_build_face_table(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), &n_active,
+                           face_kind.data(), face_cell.data(), &build_ms) != GMG_OK)
+    throw std::logic_error(gmg_last_error(gmg));
+  if (n_active != (int64_t)nc) throw std::logic_error("Refinement on device: the active cell lists differ");
+  sublap("estimate: face table on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+}
+
+// refine_grid through gmg_refine_forest and gmg_transfer_solution: the marks go up with the forest, the new forest comes back
+// into `triangulation` (Forest::install), setup_system runs as before, and the old solution -- the vector the device kept
+// where "RHS from cell tables" left one, otherwise an upload -- is carried over on the device and downloaded once.
+template <int dim>
+void LaplaceProblem<dim>::refine_grid_on_device(unsigned int cycle) {
+  auto chk = [&](int rc, const char *what) {
+    if (rc != GMG_OK) throw std::runtime_error(std::string("Refinement on device: ") + what + ": " + (gmg ? gmg_last_error(gmg) : last_error.c_str()));
+  };
+  chk(ensure_context(), "context");
+  sublap(nullptr);
+  ForestCells fc = forest_cells();
+  std::vector<uint8_t> flag;
+  flag.reserve(fc.cell_first_child.size());
+  for (const auto &lv : refine_flags)
+    for (char f : lv) flag.push_back((uint8_t)(f != 0));
+  flag.resize(fc.cell_first_child.size(), 0);
+  int L = 0;
+  int64_t n_cells = 0, n_flags = 0, n_split = 0;
+  double refine_ms = 0.0, transfer_ms = 0.0;
+  chk(gmg_refine_forest(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), flag.data(), &L, &n_cells,
+                        &n_split, &refine_ms),
+      "gmg_refine_forest");
+  std::vector<int32_t> parent((size_t)n_cells);
+  fc.level_ptr.assign((size_t)L + 1, 0);
+  fc.cell_coord.resize((size_t)n_cells * 3);
+  fc.cell_first_child.resize((size_t)n_cells);
+  closed_refine_flags.assign(flag.size(), 0);
+  chk(gmg_get_refined_forest(gmg, nullptr, nullptr, &n_flags, nullptr, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), parent.data(),
+                             closed_refine_flags.data()),
+      "download");
+  triangulation.install(L, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), parent.data());
+  refine_flags.clear();
+  sublap("refine: forest on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", refine_ms);
+  // the old solution by vertex: setup_system replaces both containers and leaves d_full alone
+  const std::vector<uint64_t> old_vertex = std::move(vertex_of_dof);
+  const std::vector<double> old_solution = std::move(solution);
+  const double *u_old = device_solution();
+  setup_system(cycle);
+  const int64_t n_old = (int64_t)old_vertex.size(), n_new = (int64_t)vertex_of_dof.size();
+  double *d_old = nullptr, *d_new = nullptr;
+  int rc = gmg_vec_alloc(gmg, n_new, &d_new);
+  if (rc == GMG_OK && !u_old) {
+    rc = gmg_vec_alloc(gmg, n_old, &d_old);
+    if (rc == GMG_OK) rc = gmg_vec_upload(gmg, d_old, old_solution.data(), n_old);
+    u_old = d_old;
+  }
+  if (rc == GMG_OK)
+    rc = gmg_transfer_solution(gmg, dim, fc.n0, L, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), n_old, old_vertex.data(), u_old, n_new,
+                               vertex_of_dof.data(), constraint_of_dof.data(), d_new, &transfer_ms);
+  solution.assign((size_t)n_new, 0.0);
+  solution_on_device = false;
+  if (rc == GMG_OK) rc = gmg_vec_download(gmg, solution.data(), d_new, n_new);
+  const std::string why = rc != GMG_OK ? gmg_last_error(gmg) : "";
+  if (d_old) gmg_vec_free(gmg, d_old);
+  if (d_new) gmg_vec_free(gmg, d_new);
+  if (rc != GMG_OK) throw std::runtime_error("Refinement on device: gmg_transfer_solution: " + why);
+  initial_guess = solution;
+  sublap("refine: transfer on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", transfer_ms);
 }
 
 }  // namespace step50

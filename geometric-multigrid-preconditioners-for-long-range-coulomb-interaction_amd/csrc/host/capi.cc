@@ -363,6 +363,49 @@ int step50_forest_cells(step50_problem *h, int32_t n0[3], int64_t *level_ptr, in
     return 0;
   });
 }
+// ---- "Refinement on device" (DESIGN.md section 21): did the last refine_grid go through the device entries; the parents of
+// the forest's cells and the vertex keys of the active DoFs (beside step50_forest_cells); the marks of the last refine_grid after
+// the 2:1 closure (returns their number, out may be null); and refine_grid on a given flag array [cells of all levels] -- the
+// path the prm selects, the next cycle's setup_system and solution transfer included, without the cycle's assembly and solve
+int step50_refined_on_device(step50_problem *h) { return DISPATCH(h, refined_on_device) ? 1 : 0; }
+int step50_forest_parents(step50_problem *h, int32_t *parent) {
+  auto fill = [&](auto &P) {
+    size_t n = 0;
+    for (const auto &lv : P.triangulation.levels)
+      for (const auto &c : lv) parent[n++] = c.parent;
+  };
+  if (h->dim == 2) fill(*h->p2); else fill(*h->p3);
+  return 0;
+}
+int step50_vertex_keys(step50_problem *h, uint64_t *key) {
+  const auto &v = DISPATCH(h, vertex_of_dof);
+  if (!v.empty()) std::memcpy(key, v.data(), sizeof(uint64_t) * v.size());
+  return 0;
+}
+int64_t step50_closed_flags(step50_problem *h, uint8_t *out) {
+  const auto &f = DISPATCH(h, closed_refine_flags);
+  if (out && !f.empty()) std::memcpy(out, f.data(), f.size());
+  return (int64_t)f.size();
+}
+int step50_refine_with_flags(step50_problem *h, const uint8_t *flag, int64_t n, int on_device) {
+  return guarded(h, [&] {
+    auto run = [&](auto &P) {
+      if (P.reports.empty()) throw std::runtime_error("step50_refine_with_flags: no cycle has run");
+      int64_t k = 0;
+      P.refine_flags.assign(P.triangulation.levels.size(), {});
+      for (size_t l = 0; l < P.triangulation.levels.size(); ++l) {
+        P.refine_flags[l].assign(P.triangulation.levels[l].size(), 0);
+        for (auto &f : P.refine_flags[l]) f = k < n ? (char)(flag[k] != 0) : 0, ++k;
+      }
+      if (k != n) throw std::runtime_error("step50_refine_with_flags: one flag per cell of every level");
+      P.solve_on_device_requested = on_device != 0;
+      P.densities_on_device = on_device != 0 && P.par.densities_on_device;
+      P.refine_grid((unsigned)P.reports.size());
+    };
+    if (h->dim == 2) run(*h->p2); else run(*h->p3);
+    return 0;
+  });
+}
 // ---- "RHS from cell tables" (DESIGN.md section 19): what the driver hands to gmg_assemble_rhs beyond the arrays above.
 // sizes: nq, n_cells, 2^dim.  source: the charge densities as the host holds them, or rhs_function at the quadrature points
 int step50_rhs_from_cell_tables(step50_problem *h) { return DISPATCH(h, rhs_from_cells) ? 1 : 0; }

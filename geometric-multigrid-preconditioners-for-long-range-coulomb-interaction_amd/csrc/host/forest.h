@@ -123,6 +123,26 @@ class Forest {
     for (int d = 0; d < 3; ++d) x[d] = d < dim ? origin + h * c.c[d] : 0.0;
   }
 
+  // Take over a forest given as flat arrays (gmg_refine_forest / gmg_get_refined_forest): level_ptr
+  // [n_levels + 1], coord [n][3], first_child [n], parent [n] over the cells of all levels in index order.  `levels` and
+  // `index` are rebuilt at once -- one hash insertion per cell of level >= 1, what split() pays for the same cells, the levels
+  // in parallel -- so that find() stays a const look-up for the loops that call it from several threads.
+  void install(int n_levels_new, const int64_t *level_ptr, const int32_t *coord, const int32_t *first_child, const int32_t *parent) {
+    levels.assign((size_t)n_levels_new, {});
+    index.assign((size_t)n_levels_new, {});
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int l = 0; l < n_levels_new; ++l) {
+      const int64_t b = level_ptr[l], n = level_ptr[l + 1] - b;
+      auto &lv = levels[(size_t)l];
+      lv.resize((size_t)n);
+      for (int64_t c = 0; c < n; ++c) lv[(size_t)c] = Cell{{coord[3 * (b + c)], coord[3 * (b + c) + 1], coord[3 * (b + c) + 2]}, parent[b + c], first_child[b + c]};
+      if (l == 0) continue;
+      auto &map = index[(size_t)l];
+      map.reserve((size_t)n);
+      for (int64_t c = 0; c < n; ++c) map[pack3((uint64_t)lv[(size_t)c].c[0], (uint64_t)lv[(size_t)c].c[1], (uint64_t)lv[(size_t)c].c[2])] = (int32_t)c;
+    }
+  }
+
   // Refine the flagged active cells, then restore the 2:1 balance over vertices (deal.II
   // limit_level_difference_at_vertices == p4est full-connectivity balance).  flags[level][cell].
   // Returns the number of cells split.

@@ -256,6 +256,10 @@ void ParameterReader::declare_parameters() {
             // active mesh and of every level, hanging-node and Dirichlet lines, level flags; boundary values and close() stay
             // here; cycles that run on the device, one rank, DESIGN.md section 20
             {"Mesh tables on device", "false"},
+            // gmg_refine_forest (2:1 closure of the marks and the split), gmg_transfer_solution (SolutionTransfer::interpolate
+            // and constraints.set_zero) and gmg_build_face_table (the estimator's face table) instead of Forest::refine_flagged,
+            // the interpolation loop of refine_grid and face_table; cycles that run on the device, one rank, DESIGN.md section 21
+            {"Refinement on device", "false"},
             // the short-ranged pair sum over the pairs closer than this many smoothing lengths, found through
             // cell bins (erfc(6) = 2e-17: beyond 6 r_c a pair contributes nothing in double precision); 0 = all pairs as the
             // reference (:1325-1332).  With it the energy is also evaluated for the large systems the reference skips (:1554).
@@ -345,6 +349,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.rhs_from_cell_tables = prm.get_bool("RHS from cell tables");
   p.mesh_tables_on_device = prm.get_bool("Mesh tables on device");
+  p.refinement_on_device = prm.get_bool("Refinement on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
   p.compute_forces = prm.get_bool("Compute forces");

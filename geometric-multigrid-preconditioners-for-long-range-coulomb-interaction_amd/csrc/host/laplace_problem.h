@@ -82,6 +82,7 @@ struct Parameters {
   bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
   bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
   bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
+  bool refinement_on_device = false;     // gmg_refine_forest, gmg_transfer_solution and gmg_build_face_table instead of refine_flagged, the interpolation loop of refine_grid and face_table (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
@@ -205,6 +206,14 @@ class LaplaceProblem {
   EstimatorInputs estimator_inputs();
   void face_table(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) const;  // the forest's faces by kind
   void refine_grid(unsigned int cycle);                                  // :1095-1121
+  // "Refinement on device" 
+  bool refinement_applies() const { return par.refinement_on_device && solve_on_device_requested && !distributed; }
+  bool decide_refinement_on_device();                                    // set and applicable to this cycle?  Says so once when not
+  void refine_grid_on_device(unsigned int cycle);                        // refine_grid through gmg_refine_forest and gmg_transfer_solution
+  void face_table_on_device(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell);  // face_table through gmg_build_face_table
+  bool refined_on_device = false;              // the last refine_grid went through the device entries
+  bool refinement_fallback_reported = false;   // "Refinement on device" was set but not applicable: said once
+  std::vector<uint8_t> closed_refine_flags;    // the marks of the last refine_grid after the 2:1 closure, all levels of the old forest (tests)
   void postprocess_electrostatic_energy();                               // :1310-1420
   void postprocess_error_in_energy_norm();                               // :1423-1461
   void postprocess_forces();                                             // forces on the atoms (no counterpart in the reference)

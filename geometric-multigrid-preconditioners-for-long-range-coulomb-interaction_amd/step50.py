@@ -88,6 +88,7 @@ def prm_text(**kw) -> str:
         "level_matrices_on_device": ("Misc", "Level matrices on device"),
         "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
         "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
+        "refinement_on_device": ("Misc", "Refinement on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
         "transfer_on_device": ("Misc", "Transfer matrices on device"),
@@ -381,6 +382,37 @@ class Problem:
     def mesh_tables_on_device(self) -> bool:
         """Did the last setup_system form the DoF numbering, the constraints and the level flags through gmg_build_mesh_tables?"""
         return bool(self.L.step50_mesh_tables_on_device(self.h))
+
+    def refined_on_device(self) -> bool:
+        """Did the last refine_grid go through gmg_refine_forest and gmg_transfer_solution ("Refinement on device")?"""
+        return bool(self.L.step50_refined_on_device(self.h))
+
+    def forest_parents(self):
+        """cell_parent of every cell of forest_cells(): the index inside the previous level, -1 on level 0."""
+        out = np.zeros(len(self.forest_cells().cell_first_child), dtype=np.int32)
+        self.L.step50_forest_parents(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    def vertex_keys(self):
+        """The vertex key of every active DoF (x | y << 21 | z << 42 on the level-12 lattice)."""
+        out = np.zeros(self.n_dofs(), dtype=np.uint64)
+        self.L.step50_vertex_keys(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return out
+
+    def closed_flags(self):
+        """The marks of the last refine_grid after the 2:1 closure, over the cells of all levels of the forest it refined."""
+        self.L.step50_closed_flags.restype = C.c_int64
+        out = np.zeros(max(self.L.step50_closed_flags(self.h, None), 1), dtype=np.uint8)
+        n = self.L.step50_closed_flags(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out[:n]
+
+    def refine_with_flags(self, flags, on_device: bool = False):
+        """refine_grid on a given flag array (one per cell of every level of forest_cells()): the closure, the split, the next
+        cycle's setup_system and the solution transfer, on the path the prm selects for a cycle that runs on the device
+        (on_device) or not.  forest_cells(), forest_parents(), closed_flags() and vector("solution") show the result."""
+        f = np.ascontiguousarray(flags, dtype=np.uint8)
+        self._chk(self.L.step50_refine_with_flags(self.h, f.ctypes.data_as(C.POINTER(C.c_uint8)), C.c_int64(len(f)), C.c_int(1 if on_device else 0)),
+                  "refine_with_flags")
 
     def device_system_matrix(self):
         """The system matrix as the device holds it after a cycle with "System matrix on device" (gmg_get_system_matrix)."""

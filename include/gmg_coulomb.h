@@ -419,6 +419,81 @@ int gmg_get_mesh_tables(gmg_context *ctx, int64_t *n_cells, int64_t *n_dofs, int
  * gmg_assemble_level_matrix takes); NULL arrays are skipped.  GMG_ERR_INVALID for a level the build did not have.          */
 int gmg_get_mesh_level_tables(gmg_context *ctx, int level, int64_t *n_cells, int64_t *n_dofs, int32_t *cell_dofs,
                               uint64_t *vertex_of_dof, uint8_t *dof_flags);
+/* The step between two cycles, formed on the device from the forest alone.  The three entries below take
+ * the forest exactly as gmg_build_mesh_tables does -- dim, n0, n_levels, level_ptr, cell_coord, cell_first_child -- and run
+ * the same checks on the host before anything is launched, with the same codes: GMG_ERR_INVALID for dim other than 2 or 3, a
+ * NULL array of nonzero length, a level_ptr that does not start at 0 or decreases, more than 13 levels, n0[d] outside 1 .. 511,
+ * a coordinate outside its level's lattice or a first_child that points outside the next level; GMG_ERR_UNSUPPORTED on a context
+ * with a communicator and for 2^31 slots or more; found on the device by the two entries that look cells up (gmg_refine_forest,
+ * gmg_build_face_table), GMG_ERR_INVALID for the same cell twice in a level.
+ * Zero cells are valid.  After ANY failure the outputs are not written and the context is what it was.  Integer work and
+ * look-ups: the results do not depend on the launch shape (option assemble_max_blocks).  build_ms (may be NULL): device time.
+ *
+ * gmg_refine_forest -- Forest::refine_flagged (csrc/host/forest.h; p4est refine + balance over vertices, deal.II's
+ * limit_level_difference_at_vertices, src/step-50.cc:1095-1100).  Input beyond the forest: flag [cells of all levels], in index
+ * order.
+ *   closure  A flag counts only on an active cell (first_child < 0).  F is the smallest set of cells that holds the counted
+ *            flags and is closed under: for an active cell c of level l >= 1 in F and each of its 3^dim - 1 neighbour positions
+ *            c + {-1, 0, 1}^dim that lies inside the level-l lattice (0 <= x_d < n0[d] << l): if no level-l cell sits there, the
+ *            level-(l - 1) cell at (x >> 1, y >> 1, z >> 1) is in F (it has no children, so it is active).  If that cell does
+ *            not exist either the forest is not vertex-balanced: GMG_ERR_INVALID (the host calls abort()).  A flag on level
+ *            l - 1 is caused only by level l: one pass from the finest level down to level 1 is the fixed point.
+ *   split    Every cell of F is split, the levels independently: the new level l + 1 is the old cells of level l + 1 in
+ *            their old order and, behind them, the 2^dim children of the split cells of level l in ascending cell index; child
+ *            a sits at 2 c + (a & 1, (a >> 1) & 1, (a >> 2) & 1) (z = 0 in 2D), is active, and its parent's first_child becomes
+ *            old_size(l + 1) + 2^dim * (number of split cells of level l before the parent).  Level 0 keeps its cells.  A split
+ *            on the finest level adds a level; a new level beyond 12 is GMG_ERR_UNSUPPORTED.
+ *   parent   cell_parent of a cell of level l >= 1 is the index inside level l - 1 of the cell at (x >> 1, y >> 1, z >> 1), -1
+ *            on level 0; a cell of the input without one is GMG_ERR_INVALID.
+ * Every cell of the old forest keeps its index inside its level.  The result stays on the device, owned by the context, until
+ * the next gmg_refine_forest that succeeds, gmg_reset or gmg_destroy; new_n_levels, new_n_cells (all levels) and n_split (any may
+ * be NULL) return its sizes.                                                                                                  */
+int gmg_refine_forest(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                      const int32_t *cell_coord, const int32_t *cell_first_child, const uint8_t *flag, int *new_n_levels,
+                      int64_t *new_n_cells, int64_t *n_split, double *build_ms);
+/* The forest of the last gmg_refine_forest.  Sizes: n_levels, n_cells (all levels), n_flags (the cells of the forest that went
+ * in), n_split.  Arrays -- any may be NULL and is then skipped, so a first call with all of them NULL returns the sizes:
+ * level_ptr [n_levels + 1], cell_coord [n_cells][3], cell_first_child [n_cells], cell_parent [n_cells], closed_flag [n_flags]
+ * (the set F over the cells that went in).  GMG_ERR_INVALID when the context holds no refined forest.                       */
+int gmg_get_refined_forest(gmg_context *ctx, int *n_levels, int64_t *n_cells, int64_t *n_flags, int64_t *n_split,
+                           int64_t *level_ptr, int32_t *cell_coord, int32_t *cell_first_child, int32_t *cell_parent,
+                           uint8_t *closed_flag);
+/* gmg_transfer_solution -- SolutionTransfer::interpolate and constraints.set_zero (src/step-50.cc:1101-1121; the loop of
+ * LaplaceProblem::refine_grid).  Input beyond the NEW forest: old_vertex_of_dof [n_old] and the device vector u_old [n_old]
+ * (the distributed solution of the old mesh), new_vertex_of_dof [n_new], constraint_of_dof [n_new] (may be NULL: nothing is
+ * zeroed).  Output: the device vector u_new [n_new].  Vertex keys as in gmg_build_mesh_tables.
+ *   A new DoF whose key occurs among the old vertices takes that old value.  Any other new vertex is vertex a of some cell of
+ *   level l >= 1 at c; with child = the parity bits of c and pv[p] the old value at vertex p of the cell c >> 1 of level l - 1,
+ *       v = 0.0;   for p ascending:   v += w_p * pv[p]
+ *       w_p = 1.0;   for d ascending:   pos_d = 0.5 * (bit_d(child) + bit_d(a));   w_p *= bit_d(p) ? pos_d : 1.0 - pos_d
+ *   in fp64 without contraction into fused multiply-adds -- the host's loop verbatim.  Then u_new[i] = 0.0 wherever
+ *   constraint_of_dof[i] >= 0.
+ * The host takes the value from the first (level, cell, vertex) slot that finds the vertex missing; here every such slot
+ * computes it and stores it, by EQUAL plain stores, no supplier is chosen.  They are equal because the value does not depend on
+ * the slot: a new vertex is the mid-point of an edge, the centre of a face or the centre of a cell of level l - 1.  Its nonzero
+ * weights are 0.5 on the edge's two corners, 0.25 on the face's four, 0.125 on the cell's eight; every cell that shares the edge
+ * or face meets those corners in the same ascending order (vertex numbers ascend with (z, y, x) in every cell), and the other
+ * addends are w_p * pv[p] = +-0.0 added to a sum that starts at +0.0 and stays the same for finite pv.  The tests hold this.
+ * GMG_ERR_INVALID, found on the device, for a vertex that occurs twice in a list, a parent vertex without an old value, a
+ * vertex of a cell that is not among the new vertices, or a new DoF that neither had a value nor belongs to a cell of level
+ * >= 1; GMG_ERR_UNSUPPORTED for 2^31 DoFs or more.  u_new is written only on success.                                         */
+int gmg_transfer_solution(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                          const int32_t *cell_coord, const int32_t *cell_first_child, int64_t n_old,
+                          const uint64_t *old_vertex_of_dof, const double *u_old /* device */, int64_t n_new,
+                          const uint64_t *new_vertex_of_dof, const int32_t *constraint_of_dof /* or NULL */,
+                          double *u_new /* device */, double *build_ms);
+/* gmg_build_face_table -- LaplaceProblem::face_table: face_kind [n_active * 2 dim] and face_cell [n_active * 2 dim * 2^(dim-1)]
+ * exactly as gmg_estimate_error takes them.  Active cells are numbered by (level, index); face = 2 d + side.  Per slot, with nb
+ * the position across the face on the cell's level l: outside the lattice: kind 0.  A level-l cell N there: active -> kind 1,
+ * face_cell[0] = N's active number; refined -> kind 2, face_cell[k] = the active numbers of the children first_child(N) + ch for
+ * the ch whose bit d faces this cell (bit d of ch = 0 for side 1, 1 for side 0), ascending.  No level-l cell there: kind 3,
+ * face_cell[0] = the active number of the level-(l - 1) cell at nb >> 1, face_cell[1] = this cell's quadrant of that face: the
+ * parity of the cell's own in-face coordinates, lower direction in bit 0.  Unused entries are 0.  GMG_ERR_INVALID "mesh not 2:1
+ * balanced across a face" for a kind-3 neighbour that is missing or not active and for a kind-2 child that is not active.
+ * n_active (may be NULL) returns the number of active cells; with face_kind and face_cell both NULL nothing else is done.   */
+int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                         const int32_t *cell_coord, const int32_t *cell_first_child, int64_t *n_active, uint8_t *face_kind,
+                         int32_t *face_cell, double *build_ms);
 /* The right-hand side of LaplaceProblem::assemble_system formed on the device from the cell tables, without a host plan
  * (gmg_rhs_assemble wants gather lists that the host walks every cell to build): cell_dofs, cell_level, constraint_of_dof and
  * the lines are exactly what gmg_assemble_system_matrix takes, nv = 2^dim; new are line_inhomogeneity [n_lines], the
