@@ -29,6 +29,9 @@ SYMBOLS = [
     "gmg_assemble_level_matrix", "gmg_get_level_matrix", "gmg_assemble_system_matrix_coef", "gmg_assemble_level_matrix_coef",
     "gmg_assemble_rhs", "gmg_distribute_constraints",
     "gmg_build_mesh_tables", "gmg_get_mesh_tables", "gmg_get_mesh_level_tables",
+    "gmg_close_constraints", "gmg_get_closed_constraints",
+    "gmg_assemble_system_matrix_resident", "gmg_assemble_system_matrix_coef_resident", "gmg_assemble_level_matrix_resident",
+    "gmg_assemble_level_matrix_coef_resident", "gmg_assemble_rhs_resident", "gmg_distribute_constraints_resident",
     "gmg_refine_forest", "gmg_get_refined_forest", "gmg_transfer_solution", "gmg_build_face_table",
     "gmg_estimate_error",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
@@ -249,6 +252,80 @@ class Context:
         cd, vk, fl = np.zeros(nc.value << self._mesh_dim(dim), dtype=np.int32), np.zeros(nd.value, dtype=np.uint64), np.zeros(nd.value, dtype=np.uint8)
         self._chk(self.L.gmg_get_mesh_level_tables(self.h, C.c_int(int(level)), C.byref(nc), C.byref(nd), _p(cd, C.c_int32), _p(vk, C.c_uint64), _p(fl, C.c_uint8)))
         return SimpleNamespace(n_cells=nc.value, n_dofs=nd.value, cell_dofs=cd, vertex_of_dof=vk, dof_flags=fl)
+
+    # ---- boundary values and close() on the resident tables, and the entries that read the tables where they lie
+    def close_constraints(self, dirichlet_value=None, n_values=None):
+        """Boundary values and close() on the tables of the last build_mesh_tables (gmg_close_constraints); returns the device
+        time in ms.  dirichlet_value: one value per Dirichlet line, in line order; None passes NULL (all +0.0), with n_values
+        (default: the number of Dirichlet lines of the tables)."""
+        ms = C.c_double(0)
+        if dirichlet_value is None:
+            if n_values is None:
+                n = [C.c_int64(0) for _ in range(5)]
+                self._chk(self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], None, None, None, None, None, None, None, None))
+                n_values = n[3].value - n[2].value
+            self._chk(self.L.gmg_close_constraints(self.h, C.c_int64(int(n_values)), None, C.byref(ms)))
+            return ms.value
+        v = np.ascontiguousarray(dirichlet_value, dtype=np.float64)
+        self._chk(self.L.gmg_close_constraints(self.h, C.c_int64(len(v) if n_values is None else int(n_values)), _p(v, C.c_double), C.byref(ms)))
+        return ms.value
+
+    def get_closed_constraints(self):
+        """The closed lines of the last close_constraints as numpy arrays"""
+        from types import SimpleNamespace
+        nl, ne = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_closed_constraints(self.h, C.byref(nl), C.byref(ne), None, None, None, None))
+        lp, lm, lw, li = np.zeros(nl.value + 1, dtype=np.int64), np.zeros(ne.value, dtype=np.int32), np.zeros(ne.value), np.zeros(nl.value)
+        self._chk(self.L.gmg_get_closed_constraints(self.h, C.byref(nl), C.byref(ne), _p(lp, C.c_int64), _p(lm, C.c_int32), _p(lw, C.c_double), _p(li, C.c_double)))
+        return SimpleNamespace(n_lines=nl.value, n_entries=ne.value, line_ptr=lp, line_master=lm, line_weight=lw, line_inhomogeneity=li)
+
+    def assemble_system_matrix_resident(self, K_of_level):
+        """gmg_assemble_system_matrix on the resident tables and closed lines; returns the device time in ms"""
+        K = np.ascontiguousarray([] if K_of_level is None else K_of_level, dtype=np.float64)
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_system_matrix_resident(self.h, _p(K, C.c_double) if K.size else None, C.byref(ms)))
+        return ms.value
+
+    def assemble_system_matrix_coef_resident(self, nq, cell_coef, G, qw, scale_of_level):
+        """gmg_assemble_system_matrix_coef on the resident tables and closed lines; returns the device time in ms"""
+        cc, g, w, sc = (np.ascontiguousarray([] if a is None else a, dtype=np.float64) for a in (cell_coef, G, qw, scale_of_level))
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_system_matrix_coef_resident(self.h, C.c_int(int(nq)), D(cc), D(g), D(w), D(sc), C.byref(ms)))
+        return ms.value
+
+    def assemble_level_matrix_resident(self, level, K):
+        """gmg_assemble_level_matrix on the level's resident cell table and flags; returns the device time in ms"""
+        k = np.ascontiguousarray([] if K is None else K, dtype=np.float64)
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_level_matrix_resident(self.h, C.c_int(int(level)), _p(k, C.c_double) if k.size else None, C.byref(ms)))
+        return ms.value
+
+    def assemble_level_matrix_coef_resident(self, level, nq, cell_coef, G, qw, scale):
+        """gmg_assemble_level_matrix_coef on the level's resident cell table and flags; returns the device time in ms"""
+        cc, g, w = (np.ascontiguousarray([] if a is None else a, dtype=np.float64) for a in (cell_coef, G, qw))
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_level_matrix_coef_resident(self.h, C.c_int(int(level)), C.c_int(int(nq)), D(cc), D(g), D(w), C.c_double(float(scale)),
+                                                                 C.byref(ms)))
+        return ms.value
+
+    def assemble_rhs_resident(self, inp, rhs, source=True, K_of_level=True):
+        """gmg_assemble_rhs on the resident tables and closed lines into rhs (DeviceVector); of inp (see assemble_rhs) only
+        K_of_level, nq, shape, weight, jxw_of_level and source are read.  Returns the device time in ms."""
+        f64 = lambda a: np.ascontiguousarray([] if a is None else a, dtype=np.float64)
+        K = f64(inp.K_of_level if K_of_level is True else K_of_level)
+        sh, w, jxw = f64(inp.shape), f64(inp.weight), f64(inp.jxw_of_level)
+        src = f64(inp.source if source is True else source)
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_assemble_rhs_resident(self.h, D(K), C.c_int(int(inp.nq)), D(sh), D(w), D(jxw), D(src), None if rhs is None else rhs.ptr,
+                                                   C.byref(ms)))
+        return ms.value
+
+    def distribute_constraints_resident(self, u, n_dofs=None):
+        """constraints.distribute in place on the DeviceVector u with the resident closed lines"""
+        self._chk(self.L.gmg_distribute_constraints_resident(self.h, C.c_int64(u.n if n_dofs is None else int(n_dofs)), None if u is None else u.ptr))
 
     @staticmethod
     def _forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels):

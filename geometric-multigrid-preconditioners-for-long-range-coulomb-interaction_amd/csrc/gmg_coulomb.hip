@@ -24,6 +24,7 @@
 #include "gmg_estimate.hpp"
 #include "gmg_fastdiag.hpp"
 #include "gmg_mesh_tables.hpp"
+#include "gmg_close.hpp"
 #include "gmg_refine.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
@@ -165,6 +166,15 @@ struct MeshTables {
     DevPtr<uint8_t> dof_flags;
   };
   std::vector<PerLevel> level;
+  // what gmg_close_constraints adds (gmg_close.hpp): the closed lines of these tables, dropped with them
+  struct Closed {
+    bool valid = false;
+    int64_t n_entries = 0;
+    int max_line = 0;        // entries of the longest closed line
+    bool any_inhom = false;  // some line_inhomogeneity is not 0
+    DevPtr<int32_t> line_ptr, line_master;
+    DevPtr<double> line_weight, line_inhom;
+  } closed;
 };
 
 // what gmg_refine_forest leaves on the device (gmg_refine.hpp): valid until the next refinement, gmg_reset or gmg_destroy
@@ -265,6 +275,7 @@ struct gmg_context {
   int64_t loc_max_dof = -1;  // -1: no locator set
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
+  bool reset_keeps_mesh_tables = false;  // option "reset_keeps_mesh_tables": gmg_reset leaves the mesh tables and their closed lines alone
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
   MeshTables mesh;              // gmg_build_mesh_tables: the tables of the last build
   RefinedForest refined;        // gmg_refine_forest: the forest of the last refinement
@@ -2875,7 +2886,7 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   HIPC(hipStreamSynchronize(ctx->stream));
   release_operators(ctx);
   free_locator(ctx);
-  ctx->mesh = MeshTables();
+  if (!ctx->reset_keeps_mesh_tables) ctx->mesh = MeshTables();
   ctx->refined = RefinedForest();
   ctx->n_levels = n_levels;
   ctx->lv.clear();
@@ -3967,48 +3978,42 @@ static int check_cell_tables(gmg_context *ctx, const char *who, int dim, int64_t
   return GMG_OK;
 }
 
-// both entries: coef == nullptr takes the per-level cell matrices K_of_level, otherwise K_of_level is unused
-static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
-                           const double *K_of_level, const AsmCoef *coef, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
-                           const int32_t *line_master, const double *line_weight, double *build_ms) {
-  if (!ctx) return GMG_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  auto drop = [&] { reset_keep_halo(ctx->S); ctx->S_invd.reset(); ctx->S_tmp.reset(); };
-  // the coefficient form: whatever the context held goes first, so that after any failure it holds no system matrix (the
-  // cell-matrix form leaves the context untouched by arguments it refuses as invalid)
-  if (coef) drop();
+// The mesh arrays of the assemblies on the device: uploaded by the host-array entries (which own the copies until the stream
+// has run the kernels), or the context's resident tables (the _resident entries)
+struct CellTablesDev {
+  const int32_t *cell_dofs = nullptr;  // [n_cells * 2^dim]
+  const uint8_t *cell_level = nullptr;  // [n_cells]
+  const int32_t *cons = nullptr, *line_ptr = nullptr, *line_master = nullptr;
+  const double *line_weight = nullptr, *line_inhom = nullptr;
+  int max_line = 0;
+};
+
+static void drop_system(gmg_context *ctx) { reset_keep_halo(ctx->S); ctx->S_invd.reset(); ctx->S_tmp.reset(); }
+
+// the second half of both forms and both sources of the tables: everything after the argument checks and the uploads of the
+// mesh arrays.  coef == nullptr takes the per-level cell matrices K_of_level, otherwise K_of_level is unused
+static int assemble_system_device(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const CellTablesDev &t, const double *K_of_level,
+                                  const AsmCoef *coef, double *build_ms) {
+  auto drop = [&] { drop_system(ctx); };
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
-  std::vector<int32_t> lp32;
-  int64_t max_line = 0;
-  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level, n_cells > 0 && !coef && !K_of_level, constraint_of_dof, n_lines, line_ptr,
-                        line_master, line_weight, lp32, max_line));
   const int nv = 1 << dim;
-  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
-  if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
+  const int64_t n_slots = n_cells * nv;
   DevCSR &m = ctx->S;
   drop();
   AsmCoefDev d_coef;
-  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
-  DevPtr<uint8_t> d_lv;
-  DevPtr<double> d_K, d_lw;
+  DevPtr<double> d_K;
   AsmScratch w;
   Event e0, e1;
-  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
-  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
   if (!coef) HIPC(upload(d_K, K_of_level, n_cells > 0 ? (size_t)16 * nv * nv : 0, ctx->stream));
-  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
-  HIPC(upload(d_lp, lp32, ctx->stream));
-  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
-  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
   CHK(alloc_vec(ctx, ctx->S_invd, n_dofs));
   CHK(alloc_vec(ctx, ctx->S_tmp, n_dofs));
   HIPC(e0.create());
   HIPC(e1.create());
   HIPC(hipEventRecord(e0.get(), ctx->stream));
   AsmArgs a{};
-  a.nv = nv; a.lg_nv = dim; a.max_line = (int)max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
-  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.K = d_K.get(); a.cons = d_cons.get();
-  a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
+  a.nv = nv; a.lg_nv = dim; a.max_line = t.max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
+  a.cell_dofs = t.cell_dofs; a.cell_level = t.cell_level; a.K = d_K.get(); a.cons = t.cons;
+  a.line_ptr = t.line_ptr; a.line_master = t.line_master; a.line_weight = t.line_weight;
   a.invd = ctx->S_invd.get();
   if (coef) CHK(upload_coef(ctx, *coef, n_cells, nv, d_coef, a));
   std::vector<int32_t> rp;
@@ -4030,6 +4035,39 @@ static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n
   if (ctx->debug_upload)
     std::fprintf(stderr, "[gmg] system matrix assembled on the device: %lld rows nnz %lld, %lld (row, slot) pairs, %.3f ms\n", (long long)n_dofs, (long long)nnz, (long long)n_inc, ms);
   return GMG_OK;  // (tile_device_csr has asked hipGetLastError after the last launch)
+}
+
+// the first half of the host-array entries: the argument checks, then the mesh arrays go up into copies of this call
+static int assemble_system(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                           const double *K_of_level, const AsmCoef *coef, const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr,
+                           const int32_t *line_master, const double *line_weight, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  // the coefficient form: whatever the context held goes first, so that after any failure it holds no system matrix (the
+  // cell-matrix form leaves the context untouched by arguments it refuses as invalid)
+  if (coef) drop_system(ctx);
+  std::vector<int32_t> lp32;
+  int64_t max_line = 0;
+  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level, n_cells > 0 && !coef && !K_of_level, constraint_of_dof, n_lines, line_ptr,
+                        line_master, line_weight, lp32, max_line));
+  const int nv = 1 << dim;
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
+  if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
+  drop_system(ctx);
+  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
+  DevPtr<uint8_t> d_lv;
+  DevPtr<double> d_lw;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
+  HIPC(upload(d_lp, lp32, ctx->stream));
+  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
+  CellTablesDev t;
+  t.cell_dofs = d_cd.get(); t.cell_level = d_lv.get(); t.cons = d_cons.get(); t.line_ptr = d_lp.get(); t.line_master = d_lm.get(); t.line_weight = d_lw.get();
+  t.max_line = (int)max_line;
+  // (the copies are released when this returns, as they were: hipFree waits for the kernels that read them)
+  return assemble_system_device(ctx, who, dim, n_dofs, n_cells, t, K_of_level, coef, build_ms);
 }
 
 int gmg_assemble_system_matrix(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
@@ -4587,45 +4625,33 @@ int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_l
 // ---- the right-hand side from the cell tables, and constraints.distribute on the same tables (gmg_rhs_cells.hpp, DESIGN.md
 // section 19)
 
-int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
-                     const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master, const double *line_weight,
-                     const double *line_inhomogeneity, const double *K_of_level, int nq, const double *shape, const double *weight,
-                     const double *jxw_of_level, const double *source, double *rhs, double *build_ms) {
-  if (!ctx) return GMG_ERR_INVALID;
-  const char *who = "gmg_assemble_rhs";
+// the checks of the right-hand side's own arguments, shared by both entries (after the checks of the mesh arrays)
+static int check_rhs_args(gmg_context *ctx, const char *who, int64_t n_cells, bool any_inhom, const double *K_of_level, int nq, const double *source) {
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
-  std::vector<int32_t> lp32;
-  int64_t max_line = 0;
-  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level,
-                        !shape || !weight || !jxw_of_level || (n_dofs > 0 && !rhs) || (n_lines > 0 && !line_inhomogeneity), constraint_of_dof, n_lines,
-                        line_ptr, line_master, line_weight, lp32, max_line));
   if (nq < 1 || nq > 512) return bad(GMG_ERR_INVALID, "nq must be in 1 .. 512");
   if (!source && n_cells > 0 && (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq))
     return bad(GMG_ERR_INVALID, "source is NULL and the device holds no densities of n_cells x nq (gmg_charge_density with dens = NULL)");
-  bool any_inhom = false;
-  for (int64_t l = 0; l < n_lines; ++l) any_inhom = any_inhom || line_inhomogeneity[l] != 0.0;
   if (any_inhom && !K_of_level) return bad(GMG_ERR_INVALID, "K_of_level is NULL while a line_inhomogeneity is not 0");
+  return GMG_OK;
+}
+
+// the second half of gmg_assemble_rhs and gmg_assemble_rhs_resident: everything after the argument checks and the uploads of
+// the mesh arrays
+static int assemble_rhs_device(gmg_context *ctx, const char *who, int dim, int64_t n_dofs, int64_t n_cells, const CellTablesDev &t, bool any_inhom,
+                               const double *K_of_level, int nq, const double *shape, const double *weight, const double *jxw_of_level, const double *source,
+                               double *rhs, double *build_ms) {
   (void)hipSetDevice(ctx->device);
   const int nv = 1 << dim;
-  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
-  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
-  DevPtr<uint8_t> d_lv;
-  DevPtr<double> d_K, d_lw, d_li, d_src, d_F;
+  const int64_t n_slots = n_cells * nv;
+  DevPtr<double> d_K, d_src, d_F;
   DevPtr<RhsArgs> d_ra;  // (the argument block of rhs_cell_kernel is 39 KB: it travels through memory)
   AsmScratch w;
   Event e0, e1;
-  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
-  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
   if (any_inhom) HIPC(upload(d_K, K_of_level, (size_t)16 * nv * nv, ctx->stream));
-  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
-  HIPC(upload(d_lp, lp32, ctx->stream));
-  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
-  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
-  HIPC(upload(d_li, line_inhomogeneity, (size_t)n_lines, ctx->stream));
   if (source) HIPC(upload(d_src, source, (size_t)n_cells * (size_t)nq, ctx->stream));
   HIPC(d_F.alloc((size_t)std::max<int64_t>(n_slots, 1)));
   RhsArgs ra{};
-  ra.dens = source ? d_src.get() : ctx->dens_dev.get(); ra.n_cells = n_cells; ra.nq = nq; ra.nv = nv; ra.cell_level = d_lv.get(); ra.F = d_F.get();
+  ra.dens = source ? d_src.get() : ctx->dens_dev.get(); ra.n_cells = n_cells; ra.nq = nq; ra.nv = nv; ra.cell_level = t.cell_level; ra.F = d_F.get();
   for (int q = 0; q < nq; ++q) {
     ra.weight[q] = weight[q];
     for (int i = 0; i < nv; ++i) ra.shape[q * 8 + i] = shape[q * nv + i];
@@ -4637,15 +4663,15 @@ int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells,
   HIPC(e1.create());
   HIPC(hipEventRecord(e0.get(), ctx->stream));
   AsmArgs a{};
-  a.nv = nv; a.lg_nv = dim; a.max_line = (int)max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
-  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.cons = d_cons.get();
-  a.line_ptr = d_lp.get(); a.line_master = d_lm.get(); a.line_weight = d_lw.get();
+  a.nv = nv; a.lg_nv = dim; a.max_line = t.max_line; a.n_dofs = n_dofs; a.n_slots = n_slots;
+  a.cell_dofs = t.cell_dofs; a.cell_level = t.cell_level; a.cons = t.cons;
+  a.line_ptr = t.line_ptr; a.line_master = t.line_master; a.line_weight = t.line_weight;
   int32_t n_inc = 0;
   int rc = assemble_incidence<false>(ctx, a, w, n_inc);
   if (rc != GMG_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }
   RhsCellsArgs r{};
-  r.nv = nv; r.lg_nv = dim; r.n_dofs = n_dofs; r.n_slots = n_slots; r.cell_dofs = d_cd.get(); r.cell_level = d_lv.get(); r.K = d_K.get();
-  r.cons = d_cons.get(); r.line_ptr = d_lp.get(); r.line_master = d_lm.get(); r.line_weight = d_lw.get(); r.line_inhom = d_li.get();
+  r.nv = nv; r.lg_nv = dim; r.n_dofs = n_dofs; r.n_slots = n_slots; r.cell_dofs = t.cell_dofs; r.cell_level = t.cell_level; r.K = d_K.get();
+  r.cons = t.cons; r.line_ptr = t.line_ptr; r.line_master = t.line_master; r.line_weight = t.line_weight; r.line_inhom = t.line_inhom;
   r.inc_ptr = a.inc_ptr; r.inc_slot = a.inc_slot; r.F = d_F.get(); r.rhs = rhs;
   if (n_cells) hipLaunchKernelGGL(rhs_cell_kernel, asm_blocks(ctx, n_cells, kThreads), dim3(kThreads), 0, ctx->stream, (const RhsArgs *)d_ra.get());
   if (n_slots && any_inhom) hipLaunchKernelGGL(rhs_cells_dirichlet_kernel, asm_blocks(ctx, n_slots, 256), dim3(256), 0, ctx->stream, r);
@@ -4661,6 +4687,50 @@ int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells,
   if (ctx->debug_upload)
     std::fprintf(stderr, "[gmg] right-hand side from cell tables: %lld DoFs, %lld cells x %d points, %lld (row, slot) pairs, %.3f ms\n", (long long)n_dofs,
                  (long long)n_cells, nq, (long long)n_inc, ms);
+  return GMG_OK;
+}
+
+int gmg_assemble_rhs(gmg_context *ctx, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                     const int32_t *constraint_of_dof, int64_t n_lines, const int64_t *line_ptr, const int32_t *line_master, const double *line_weight,
+                     const double *line_inhomogeneity, const double *K_of_level, int nq, const double *shape, const double *weight,
+                     const double *jxw_of_level, const double *source, double *rhs, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_assemble_rhs";
+  std::vector<int32_t> lp32;
+  int64_t max_line = 0;
+  CHK(check_cell_tables(ctx, who, dim, n_dofs, n_cells, cell_dofs, cell_level,
+                        !shape || !weight || !jxw_of_level || (n_dofs > 0 && !rhs) || (n_lines > 0 && !line_inhomogeneity), constraint_of_dof, n_lines,
+                        line_ptr, line_master, line_weight, lp32, max_line));
+  bool any_inhom = false;
+  for (int64_t l = 0; l < n_lines; ++l) any_inhom = any_inhom || line_inhomogeneity[l] != 0.0;
+  CHK(check_rhs_args(ctx, who, n_cells, any_inhom, K_of_level, nq, source));
+  (void)hipSetDevice(ctx->device);
+  const int nv = 1 << dim;
+  const int64_t n_ent = n_lines > 0 ? line_ptr[n_lines] : 0, n_slots = n_cells * nv;
+  DevPtr<int32_t> d_cd, d_cons, d_lp, d_lm;
+  DevPtr<uint8_t> d_lv;
+  DevPtr<double> d_lw, d_li;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+  HIPC(upload(d_cons, constraint_of_dof, (size_t)n_dofs, ctx->stream));
+  HIPC(upload(d_lp, lp32, ctx->stream));
+  HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
+  HIPC(upload(d_li, line_inhomogeneity, (size_t)n_lines, ctx->stream));
+  CellTablesDev t;
+  t.cell_dofs = d_cd.get(); t.cell_level = d_lv.get(); t.cons = d_cons.get(); t.line_ptr = d_lp.get(); t.line_master = d_lm.get(); t.line_weight = d_lw.get();
+  t.line_inhom = d_li.get(); t.max_line = (int)max_line;
+  return assemble_rhs_device(ctx, who, dim, n_dofs, n_cells, t, any_inhom, K_of_level, nq, shape, weight, jxw_of_level, source, rhs, build_ms);
+}
+
+// the launch of constraints.distribute, shared by gmg_distribute_constraints and gmg_distribute_constraints_resident
+static int distribute_device(gmg_context *ctx, const char *who, int64_t n_dofs, double *u, const CellTablesDev &t) {
+  hipLaunchKernelGGL(distribute_constraints_kernel, asm_blocks(ctx, n_dofs, 256), dim3(256), 0, ctx->stream, n_dofs, t.cons, t.line_ptr, t.line_master, t.line_weight,
+                     t.line_inhom, u);
+  hipError_t e = hipGetLastError();
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) { ctx->err = std::string(who) + ": " + hipGetErrorString(e); return GMG_ERR_HIP; }
   return GMG_OK;
 }
 
@@ -4697,13 +4767,9 @@ int gmg_distribute_constraints(gmg_context *ctx, int64_t n_dofs, double *u, cons
   HIPC(upload(d_lm, line_master, (size_t)n_ent, ctx->stream));
   HIPC(upload(d_lw, line_weight, (size_t)n_ent, ctx->stream));
   HIPC(upload(d_li, line_inhomogeneity, (size_t)n_lines, ctx->stream));
-  hipLaunchKernelGGL(distribute_constraints_kernel, asm_blocks(ctx, n_dofs, 256), dim3(256), 0, ctx->stream, n_dofs, (const int32_t *)d_cons.get(),
-                     (const int32_t *)d_lp.get(), (const int32_t *)d_lm.get(), (const double *)d_lw.get(), (const double *)d_li.get(), u);
-  hipError_t e = hipGetLastError();
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) { ctx->err = std::string("gmg_distribute_constraints: ") + hipGetErrorString(e); return GMG_ERR_HIP; }
-  return GMG_OK;
+  CellTablesDev t;
+  t.cons = d_cons.get(); t.line_ptr = d_lp.get(); t.line_master = d_lm.get(); t.line_weight = d_lw.get(); t.line_inhom = d_li.get();
+  return distribute_device(ctx, "gmg_distribute_constraints", n_dofs, u, t);
 }
 
 int gmg_get_system_matrix(gmg_context *ctx, int64_t *n_rows, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
@@ -4755,39 +4821,40 @@ int gmg_system_matrix_norms(gmg_context *ctx, double *l1, double *linf, double *
 
 // ---- the multigrid level and interface matrices formed on the device (gmg_assemble.hpp) ----
 
-// both entries: coef == nullptr takes the level's cell matrix K, otherwise K is unused
-static int assemble_level_checked(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
-                                  const double *K, const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms) {
+// the checks of a level assembly that do not read the mesh arrays (both forms, both sources of the tables)
+static int check_level_args(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, bool mesh_null, const double *K,
+                            const AsmCoef *coef) {
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
   if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
   if (level == 0 && l0_partitioned(ctx)) return bad(GMG_ERR_UNSUPPORTED, "a row-partitioned level 0 takes its local rows as CSR (gmg_set_level_matrix)");
   if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
   if (n_dofs < 0 || n_cells < 0) return bad(GMG_ERR_INVALID, "negative size");
   const int nv = 1 << dim;
-  if ((n_cells > 0 && (!cell_dofs || (!coef && !K))) || (n_dofs > 0 && !dof_flags)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (mesh_null || (n_cells > 0 && !coef && !K)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
   if (n_dofs >= ((int64_t)1 << 31) || n_cells >= ((int64_t)1 << 31) / nv) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs or slots");
   if (coef) CHK(check_coef(ctx, who, *coef, n_cells));
+  return GMG_OK;
+}
+
+// the second half of a level assembly: d_cell_dofs [n_cells * 2^dim] and d_flags [n_dofs] are on the device, uploaded by the
+// host-array entries or resident (the _resident entries).  coef == nullptr takes the level's cell matrix K, otherwise K is unused
+static int assemble_level_device(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *d_cell_dofs,
+                                 const double *K, const AsmCoef *coef, const uint8_t *d_flags, double *build_ms) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  const int nv = 1 << dim;
   const int64_t n_slots = n_cells * nv;
-  for (int64_t s = 0; s < n_slots; ++s)
-    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return bad(GMG_ERR_INVALID, "DoF outside [0, n_dofs)");
-  for (int64_t d = 0; d < n_dofs; ++d)
-    if (dof_flags[d] > 3) return bad(GMG_ERR_INVALID, "flag bits above 1");
   const auto ex = level > 0 ? ctx->ssor_block_rows.find(level) : ctx->ssor_block_rows.end();
   const std::vector<int64_t> *explicit_rows = ex == ctx->ssor_block_rows.end() ? nullptr : &ex->second;
   if (explicit_rows && explicit_rows->back() != n_dofs)
     return bad(GMG_ERR_INVALID, "the SSOR block boundaries of this level (gmg_set_ssor_block_rows) do not end at n_dofs");
   Level &L = ctx->lv[(size_t)level];
   DevCSR &m = L.A;
-  DevPtr<int32_t> d_cd;
-  DevPtr<uint8_t> d_fl;
   DevPtr<double> d_K, d_eval;
   AsmCoefDev d_coef;
   DevPtr<unsigned long long> d_lmax;
   AsmScratch w;
   Event e0, e1;
-  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
   if (!coef) HIPC(upload(d_K, K, n_cells > 0 ? (size_t)nv * nv : 0, ctx->stream));
-  HIPC(upload(d_fl, dof_flags, (size_t)n_dofs, ctx->stream));
   HIPC(L.I.rowptr.alloc((size_t)n_dofs + 1));  // (the row kernel counts I_l's entries into it)
   HIPC(d_lmax.alloc(1));
   CHK(alloc_vec(ctx, L.invd, n_dofs));
@@ -4798,7 +4865,7 @@ static int assemble_level_checked(gmg_context *ctx, const char *who, int level, 
   HIPC(hipMemsetAsync(d_lmax.get(), 0, sizeof(unsigned long long), ctx->stream));
   AsmArgs a{};
   a.nv = nv; a.lg_nv = dim; a.max_line = 0; a.n_dofs = n_dofs; a.n_slots = n_slots;
-  a.cell_dofs = d_cd.get(); a.K = d_K.get(); a.flags = d_fl.get(); a.invd = L.invd.get(); a.edge_cnt = L.I.rowptr.get();
+  a.cell_dofs = d_cell_dofs; a.K = d_K.get(); a.flags = d_flags; a.invd = L.invd.get(); a.edge_cnt = L.I.rowptr.get();
   if (coef) CHK(upload_coef(ctx, *coef, n_cells, nv, d_coef, a));
   std::vector<int32_t> rp;
   int64_t nnz = 0;
@@ -4868,8 +4935,39 @@ static int assemble_level_checked(gmg_context *ctx, const char *who, int level, 
   return finish_level(ctx, level, n_dofs, n_dofs, nnz);
 }
 
+// the first half of the host-array entries: the argument checks, then the mesh arrays go up into copies of this call
+static int assemble_level_checked(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs,
+                                  const double *K, const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  CHK(check_level_args(ctx, who, level, dim, n_dofs, n_cells, (n_cells > 0 && !cell_dofs) || (n_dofs > 0 && !dof_flags), K, coef));
+  const int64_t n_slots = n_cells << dim;
+  for (int64_t s = 0; s < n_slots; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return bad(GMG_ERR_INVALID, "DoF outside [0, n_dofs)");
+  for (int64_t d = 0; d < n_dofs; ++d)
+    if (dof_flags[d] > 3) return bad(GMG_ERR_INVALID, "flag bits above 1");
+  DevPtr<int32_t> d_cd;
+  DevPtr<uint8_t> d_fl;
+  HIPC(upload(d_cd, cell_dofs, (size_t)n_slots, ctx->stream));
+  HIPC(upload(d_fl, dof_flags, (size_t)n_dofs, ctx->stream));
+  return assemble_level_device(ctx, who, level, dim, n_dofs, n_cells, d_cd.get(), K, coef, d_fl.get(), build_ms);
+}
+
+// The resident form's first half (gmg_assemble_level_matrix[_coef]_resident): the level's cell table and
+// flags are the ones gmg_build_mesh_tables left on the device, in range by construction, so only their presence is checked.
+static int assemble_level_resident(gmg_context *ctx, const char *who, int level, const double *K, const AsmCoef *coef, double *build_ms) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
+  const MeshTables &mt = ctx->mesh;
+  if (!mt.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  if (level >= (int)mt.level.size()) return bad(GMG_ERR_INVALID, "no such level in the mesh tables");
+  const MeshTables::PerLevel &T = mt.level[(size_t)level];
+  CHK(check_level_args(ctx, who, level, mt.dim, T.n_dofs, T.n_cells, false, K, coef));
+  return assemble_level_device(ctx, who, level, mt.dim, T.n_dofs, T.n_cells, T.cell_dofs.get(), K, coef, T.dof_flags.get(), build_ms);
+}
+
+// the host-array entries (resident = false: the mesh arguments are used) and the resident ones (they are ignored)
 static int assemble_level(gmg_context *ctx, const char *who, int level, int dim, int64_t n_dofs, int64_t n_cells, const int32_t *cell_dofs, const double *K,
-                          const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms) {
+                          const AsmCoef *coef, const uint8_t *dof_flags, double *build_ms, bool resident = false) {
   if (!ctx) return GMG_ERR_INVALID;
   if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": level outside the context").c_str());
   (void)hipSetDevice(ctx->device);
@@ -4885,7 +4983,8 @@ static int assemble_level(gmg_context *ctx, const char *who, int level, int dim,
   };
   clear();
   if (level == 0) drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
-  const int rc = assemble_level_checked(ctx, who, level, dim, n_dofs, n_cells, cell_dofs, K, coef, dof_flags, build_ms);
+  const int rc = resident ? assemble_level_resident(ctx, who, level, K, coef, build_ms)
+                          : assemble_level_checked(ctx, who, level, dim, n_dofs, n_cells, cell_dofs, K, coef, dof_flags, build_ms);
   if (rc != GMG_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     clear();
@@ -4902,6 +5001,164 @@ int gmg_assemble_level_matrix_coef(gmg_context *ctx, int level, int dim, int64_t
                                    const double *cell_coef, const double *G, const double *qw, double scale, const uint8_t *dof_flags, double *build_ms) {
   const AsmCoef coef{nq, cell_coef, G, qw, &scale, 1};
   return assemble_level(ctx, "gmg_assemble_level_matrix_coef", level, dim, n_dofs, n_cells, cell_dofs, nullptr, &coef, dof_flags, build_ms);
+}
+
+// ---- boundary values and close() on the resident mesh tables, and the consumers that read the tables where they lie
+// (gmg_close.hpp)
+
+int gmg_close_constraints(gmg_context *ctx, int64_t n_values, const double *dirichlet_value, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  ctx->mesh.closed = MeshTables::Closed();  // after any failure the context holds no closed constraints
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string("gmg_close_constraints: ") + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  const MeshTables &mt = ctx->mesh;
+  if (!mt.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  const int64_t H = mt.n_hanging, L = mt.n_lines;
+  if (n_values != L - H) return bad(GMG_ERR_INVALID, "n_values is not the number of Dirichlet lines (n_lines - n_hanging)");
+  MeshTables::Closed c;
+  DevPtr<int> d_flag;
+  Event e0, e1;
+  HIPC(c.line_ptr.alloc((size_t)L + 1));
+  HIPC(c.line_inhom.alloc((size_t)std::max<int64_t>(L, 1)));
+  HIPC(d_flag.alloc(1));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(hipMemsetAsync(c.line_ptr.get(), 0, sizeof(int32_t) * ((size_t)L + 1), ctx->stream));
+  HIPC(hipMemsetAsync(d_flag.get(), 0, sizeof(int), ctx->stream));
+  // the Dirichlet lines' values (NULL: +0.0, which is all bits 0)
+  if (n_values > 0 && dirichlet_value) {
+    HIPC(hipMemcpyAsync(c.line_inhom.get() + H, dirichlet_value, sizeof(double) * (size_t)n_values, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t i = 0; i < n_values; ++i) c.any_inhom = c.any_inhom || dirichlet_value[i] != 0.0;  // (a hanging line's sum is 0 unless one of these is not)
+  } else if (n_values > 0) {
+    HIPC(hipMemsetAsync(c.line_inhom.get() + H, 0, sizeof(double) * (size_t)n_values, ctx->stream));
+  }
+  ClArgs a{};
+  a.cons = mt.constraint_of_dof.get(); a.line_ptr = mt.line_ptr.get(); a.line_master = mt.line_master.get(); a.line_weight = mt.line_weight.get();
+  a.n_hanging = H; a.ptr = c.line_ptr.get(); a.inhom = c.line_inhom.get(); a.flag = d_flag.get();
+  const dim3 g = asm_blocks(ctx, H, kClThreads);
+  if (H) hipLaunchKernelGGL(cl_close_kernel<false>, g, dim3(kClThreads), 0, ctx->stream, a);
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, c.line_ptr.get(), L);
+  int flag = 0;
+  int32_t total = 0;
+  HIPC(hipMemcpyAsync(&flag, d_flag.get(), sizeof flag, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipMemcpyAsync(&total, c.line_ptr.get() + L, sizeof total, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (flag & kClErrHanging) return bad(GMG_ERR_INVALID, "hanging node constrained to a hanging node");
+  c.n_entries = total;
+  for (int k = 0; k <= kClKeptMax; ++k)
+    if (flag & (1 << (kClKeptShift + k))) c.max_line = k;
+  if (c.max_line >= kClKeptMax) return bad(GMG_ERR_UNSUPPORTED, "a line with 16 or more entries");
+  HIPC(c.line_master.alloc((size_t)std::max<int64_t>(c.n_entries, 1)));
+  HIPC(c.line_weight.alloc((size_t)std::max<int64_t>(c.n_entries, 1)));
+  a.master = c.line_master.get(); a.weight = c.line_weight.get();
+  if (H) hipLaunchKernelGGL(cl_close_kernel<true>, g, dim3(kClThreads), 0, ctx->stream, a);
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(launch_status(ctx));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  c.valid = true;
+  ctx->mesh.closed = std::move(c);
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] constraints closed on the device: %lld hanging + %lld Dirichlet lines, %lld of %lld entries kept, %.3f ms\n", (long long)H,
+                 (long long)(L - H), (long long)total, (long long)mt.n_entries, ms);
+  return GMG_OK;
+}
+
+int gmg_get_closed_constraints(gmg_context *ctx, int64_t *n_lines, int64_t *n_entries, int64_t *line_ptr, int32_t *line_master, double *line_weight,
+                               double *line_inhomogeneity) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid || !m.closed.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_closed_constraints: the context holds no closed constraints");
+  (void)hipSetDevice(ctx->device);
+  if (n_lines) *n_lines = m.n_lines;
+  if (n_entries) *n_entries = m.closed.n_entries;
+  std::vector<int32_t> lp(line_ptr ? (size_t)m.n_lines + 1 : 0);
+  HIPC(mesh_fetch(ctx, line_ptr ? lp.data() : nullptr, m.closed.line_ptr, m.n_lines + 1));
+  HIPC(mesh_fetch(ctx, line_master, m.closed.line_master, m.closed.n_entries));
+  HIPC(mesh_fetch(ctx, line_weight, m.closed.line_weight, m.closed.n_entries));
+  HIPC(mesh_fetch(ctx, line_inhomogeneity, m.closed.line_inhom, m.n_lines));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < lp.size(); ++i) line_ptr[i] = lp[i];
+  return GMG_OK;
+}
+
+// What the resident entries check instead of the siblings' host loops over the mesh arrays (the tables were produced by the
+// library and are in range by construction): no communicator, tables, and (need_closed) their closed lines.  t receives the
+// device pointers.
+static int resident_tables(gmg_context *ctx, const char *who, bool need_closed, CellTablesDev &t) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator (rank-local assembly does not exist yet)");
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  if (need_closed && !m.closed.valid) return bad(GMG_ERR_INVALID, "the context holds no closed constraints (gmg_close_constraints)");
+  t.cell_dofs = m.cell_dofs.get(); t.cell_level = m.cell_level.get(); t.cons = m.constraint_of_dof.get();
+  t.line_ptr = m.closed.line_ptr.get(); t.line_master = m.closed.line_master.get(); t.line_weight = m.closed.line_weight.get();
+  t.line_inhom = m.closed.line_inhom.get(); t.max_line = m.closed.max_line;
+  // (32-bit slot lists: every slot goes to its DoF and to at most max_line masters)
+  if ((m.n_cells << m.dim) * (1 + (int64_t)t.max_line) >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 (row, slot) pairs");
+  return GMG_OK;
+}
+
+static int assemble_system_resident(gmg_context *ctx, const char *who, const double *K_of_level, const AsmCoef *coef, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  if (coef) drop_system(ctx);  // (as the sibling: after any failure of the coefficient form the context holds no system matrix)
+  CellTablesDev t;
+  CHK(resident_tables(ctx, who, true, t));
+  const MeshTables &m = ctx->mesh;
+  if (m.n_cells > 0 && !coef && !K_of_level) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": an array of nonzero length is NULL").c_str());
+  if (coef) CHK(check_coef(ctx, who, *coef, m.n_cells));
+  return assemble_system_device(ctx, who, m.dim, m.n_dofs, m.n_cells, t, K_of_level, coef, build_ms);
+}
+
+int gmg_assemble_system_matrix_resident(gmg_context *ctx, const double *K_of_level, double *build_ms) {
+  return assemble_system_resident(ctx, "gmg_assemble_system_matrix_resident", K_of_level, nullptr, build_ms);
+}
+
+int gmg_assemble_system_matrix_coef_resident(gmg_context *ctx, int nq, const double *cell_coef, const double *G, const double *qw, const double *scale_of_level,
+                                             double *build_ms) {
+  const AsmCoef coef{nq, cell_coef, G, qw, scale_of_level, 16};
+  return assemble_system_resident(ctx, "gmg_assemble_system_matrix_coef_resident", nullptr, &coef, build_ms);
+}
+
+int gmg_assemble_level_matrix_resident(gmg_context *ctx, int level, const double *K, double *build_ms) {
+  return assemble_level(ctx, "gmg_assemble_level_matrix_resident", level, 0, 0, 0, nullptr, K, nullptr, nullptr, build_ms, true);
+}
+
+int gmg_assemble_level_matrix_coef_resident(gmg_context *ctx, int level, int nq, const double *cell_coef, const double *G, const double *qw, double scale,
+                                            double *build_ms) {
+  const AsmCoef coef{nq, cell_coef, G, qw, &scale, 1};
+  return assemble_level(ctx, "gmg_assemble_level_matrix_coef_resident", level, 0, 0, 0, nullptr, nullptr, &coef, nullptr, build_ms, true);
+}
+
+int gmg_assemble_rhs_resident(gmg_context *ctx, const double *K_of_level, int nq, const double *shape, const double *weight, const double *jxw_of_level,
+                              const double *source, double *rhs, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_assemble_rhs_resident";
+  CellTablesDev t;
+  CHK(resident_tables(ctx, who, true, t));
+  const MeshTables &m = ctx->mesh;
+  if (!shape || !weight || !jxw_of_level || (m.n_dofs > 0 && !rhs)) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": an array of nonzero length is NULL").c_str());
+  CHK(check_rhs_args(ctx, who, m.n_cells, m.closed.any_inhom, K_of_level, nq, source));
+  return assemble_rhs_device(ctx, who, m.dim, m.n_dofs, m.n_cells, t, m.closed.any_inhom, K_of_level, nq, shape, weight, jxw_of_level, source, rhs, build_ms);
+}
+
+// (the closed lines never have a constrained master -- gmg_close_constraints drops or refuses every such entry -- so what
+// gmg_distribute_constraints checks on the host, "no master is itself constrained", holds by construction)
+int gmg_distribute_constraints_resident(gmg_context *ctx, int64_t n_dofs, double *u) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_distribute_constraints_resident";
+  CellTablesDev t;
+  CHK(resident_tables(ctx, who, true, t));
+  if (n_dofs != ctx->mesh.n_dofs) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": n_dofs differs from the mesh tables'").c_str());
+  if (n_dofs > 0 && !u) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": an array of nonzero length is NULL").c_str());
+  if (n_dofs == 0) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  return distribute_device(ctx, who, n_dofs, u, t);
 }
 
 int gmg_get_level_matrix(gmg_context *ctx, int level, int which, int64_t *n_rows, int64_t *n_cols, int64_t *nnz, int64_t *rowptr, int32_t *col, double *val) {
@@ -5249,6 +5506,7 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
     if (value != 64 && value != 128 && value != 256) return fail(ctx, GMG_ERR_INVALID, "force_block: 64, 128 or 256");
     ctx->force_block = (int)value;
   }
+  else if (k == "reset_keeps_mesh_tables") ctx->reset_keeps_mesh_tables = on;
   else if (k == "assemble_max_blocks") {
     if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "assemble_max_blocks: an integer in 0 .. 65536");
     ctx->assemble_max_blocks = (int)value;

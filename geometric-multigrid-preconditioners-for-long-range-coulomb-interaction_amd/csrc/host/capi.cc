@@ -347,6 +347,8 @@ int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t
 // ---- "Mesh tables on device" (DESIGN.md section 20): what the driver hands to gmg_build_mesh_tables for the current forest.
 // sizes: n_levels, cells of all levels, level0_lexicographic
 int step50_mesh_tables_on_device(step50_problem *h) { return DISPATCH(h, mesh_on_device) ? 1 : 0; }
+// "Operators from resident tables" (DESIGN.md section 22): did the key take effect in the last setup_system?
+int step50_operators_resident(step50_problem *h) { return DISPATCH(h, operators_resident) ? 1 : 0; }
 int step50_forest_sizes(step50_problem *h, int64_t sizes[3]) {
   return guarded(h, [&] {
     const auto fc = DISPATCH(h, forest_cells());

@@ -256,6 +256,11 @@ void ParameterReader::declare_parameters() {
             // active mesh and of every level, hanging-node and Dirichlet lines, level flags; boundary values and close() stay
             // here; cycles that run on the device, one rank, DESIGN.md section 20
             {"Mesh tables on device", "false"},
+            // gmg_close_constraints and the _resident entries: the system matrix, the level matrices, the right-hand side and
+            // constraints.distribute read the tables gmg_build_mesh_tables left on the device instead of taking them back as
+            // host arrays; cycles in which "Mesh tables on device" took effect, with "System matrix on device", "Level matrices
+            // on device" and "RHS from cell tables" set, DESIGN.md section 22
+            {"Operators from resident tables", "false"},
             // gmg_refine_forest (2:1 closure of the marks and the split), gmg_transfer_solution (SolutionTransfer::interpolate
             // and constraints.set_zero) and gmg_build_face_table (the estimator's face table) instead of Forest::refine_flagged,
             // the interpolation loop of refine_grid and face_table; cycles that run on the device, one rank, DESIGN.md section 21
@@ -349,6 +354,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.rhs_on_device = prm.get_bool("RHS on device");
   p.rhs_from_cell_tables = prm.get_bool("RHS from cell tables");
   p.mesh_tables_on_device = prm.get_bool("Mesh tables on device");
+  p.operators_from_resident_tables = prm.get_bool("Operators from resident tables");
   p.refinement_on_device = prm.get_bool("Refinement on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
@@ -935,8 +941,56 @@ void LaplaceProblem<dim>::make_constraints() {
   }
   if (mesh_on_device) {  // (the same lines, numbered the same: anything else is a defect of the entry, not of the mesh)
     if (constraint_of_dof != device_mesh.constraint_of_dof) throw std::logic_error("Mesh tables on device: constraint_of_dof differs from the lines");
-    device_mesh = DeviceMeshTables();
+    device_mesh = DeviceMeshTables();  // (the host copy; the context keeps its tables until the next build, gmg_reset or gmg_destroy)
   }
+  operators_resident = decide_operators_resident();
+  if (operators_resident) close_constraints_on_device();
+}
+
+// Do this cycle's device entries read the context's mesh tables?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_operators_resident() {
+  if (!par.operators_from_resident_tables) return false;
+  const char *why = distributed                      ? "the run is distributed"
+                    : !mesh_on_device                ? "the mesh tables were not formed on the device"
+                    : !par.system_matrix_on_device   ? "System matrix on device is not set"
+                    : !par.level_matrices_on_device  ? "Level matrices on device is not set"
+                    : !par.rhs_from_cell_tables      ? "RHS from cell tables is not set"
+                                                     : nullptr;
+  if (!why) return true;
+  if (!resident_fallback_reported) pcout(std::string("   Operators from resident tables: not applicable (") + why + "), host arrays");
+  resident_fallback_reported = true;
+  return false;
+}
+
+// The boundary values make_constraints computed (boundary_value, or the gmg_gaussian_potential batch) go to the Dirichlet
+// lines of the resident tables, in line order, and close() runs there.  The host's closed constraint_lines stay: other host
+// loops read them.  STEP50_CHECK_RESIDENT=1 holds the device's closed lines against them.
+template <int dim>
+void LaplaceProblem<dim>::close_constraints_on_device() {
+  auto chk = [&](int rc, const char *what) { if (rc != GMG_OK) throw std::runtime_error(std::string("Operators from resident tables: ") + what + ": " + gmg_last_error(gmg)); };
+  sublap("make_constraints: host");  // (everything before this call; setup_system's lap "make_constraints" then holds the tail only)
+  size_t H = 0;
+  while (H < constraint_lines.size() && constraint_lines[H].hanging) ++H;
+  std::vector<double> value(constraint_lines.size() - H);
+  for (size_t l = H; l < constraint_lines.size(); ++l) value[l - H] = constraint_lines[l].inhomogeneity;
+  double build_ms = 0.0;
+  chk(gmg_close_constraints(gmg, (int64_t)value.size(), value.data(), &build_ms), "gmg_close_constraints");
+  sublap("constraints: close on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+  const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+  if (!check || std::atoi(check) == 0) return;
+  int64_t n_lines = 0, n_entries = 0;
+  chk(gmg_get_closed_constraints(gmg, &n_lines, &n_entries, nullptr, nullptr, nullptr, nullptr), "sizes");
+  std::vector<int64_t> lp((size_t)n_lines + 1), h_lp;
+  std::vector<int32_t> lm((size_t)n_entries), h_lm;
+  std::vector<double> lw((size_t)n_entries), li((size_t)n_lines), h_lw, h_li;
+  chk(gmg_get_closed_constraints(gmg, nullptr, nullptr, lp.data(), lm.data(), lw.data(), li.data()), "gmg_get_closed_constraints");
+  line_tables(h_lp, h_lm, h_lw, h_li);
+  if (lp != h_lp || lm != h_lm || lw.size() != h_lw.size() || li.size() != h_li.size() ||
+      (!lw.empty() && std::memcmp(lw.data(), h_lw.data(), sizeof(double) * lw.size()) != 0) ||
+      (!li.empty() && std::memcmp(li.data(), h_li.data(), sizeof(double) * li.size()) != 0))
+    throw std::logic_error("Operators from resident tables: the device's closed lines differ from the host's");
 }
 
 template <int dim>
@@ -1153,12 +1207,12 @@ void LaplaceProblem<dim>::ensure_system_matrix() {
 
 // the arrays of gmg_assemble_system_matrix: cell DoFs and levels, the cell matrix as cell_K scales it per level, the lines
 template <int dim>
-typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_assembly_inputs() const {
+typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_assembly_inputs(bool mesh_arrays) const {
   constexpr int nv = 1 << dim;
   SystemAssemblyInputs in;
-  in.cell_dofs.resize(active_cells.size() * nv);
-  in.cell_level.resize(active_cells.size());
-  for (size_t ci = 0; ci < active_cells.size(); ++ci) {
+  in.cell_dofs.resize(mesh_arrays ? active_cells.size() * nv : 0);
+  in.cell_level.resize(mesh_arrays ? active_cells.size() : 0);
+  for (size_t ci = 0; mesh_arrays && ci < active_cells.size(); ++ci) {
     cell_dofs(active_cells[ci], &in.cell_dofs[ci * nv]);
     if (active_cells[ci].level > 15) throw std::runtime_error("System matrix on device: more than 16 levels");
     in.cell_level[ci] = (uint8_t)active_cells[ci].level;
@@ -1171,7 +1225,7 @@ typename LaplaceProblem<dim>::SystemAssemblyInputs LaplaceProblem<dim>::system_a
     for (int i = 0; i < nv; ++i)
       for (int j = 0; j < nv; ++j) in.K_of_level[((size_t)l * nv + (size_t)i) * nv + (size_t)j] = K[i][j];
   }
-  line_tables(in.line_ptr, in.line_master, in.line_weight, in.line_inhomogeneity);
+  if (mesh_arrays) line_tables(in.line_ptr, in.line_master, in.line_weight, in.line_inhomogeneity);
   return in;
 }
 
@@ -1486,16 +1540,21 @@ void LaplaceProblem<dim>::assemble_rhs_from_cell_tables() {
   auto chk = [&](int rc, const char *what) { if (rc != GMG_OK) throw std::runtime_error(std::string(what) + ": " + (gmg ? gmg_last_error(gmg) : last_error.c_str())); };
   chk(ensure_context(), "RHS from cell tables");
   const int64_t n = (int64_t)vertex_of_dof.size();
-  SystemAssemblyInputs in = system_assembly_inputs();
+  SystemAssemblyInputs in = system_assembly_inputs(!operators_resident);
   // GaussianCharges: the densities gmg_charge_density left on the device (source = NULL); otherwise the function's values
   const RhsAssemblyInputs r = rhs_assembly_inputs(!lammpsinput);
   const bool constant_coef = par.Problemtype != "Step16";  // (K_of_level is the constant-coefficient cell matrix: decide_rhs_from_cell_tables)
   double *d_out = nullptr, build_ms = 0.0;
   chk(gmg_vec_alloc(gmg, n, &d_out), "gmg_vec_alloc");
-  int rc = gmg_assemble_rhs(gmg, dim, n, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(), constraint_of_dof.data(),
-                            (int64_t)constraint_lines.size(), in.line_ptr.data(), in.line_master.data(), in.line_weight.data(),
-                            in.line_inhomogeneity.data(), constant_coef ? in.K_of_level.data() : nullptr, r.nq, r.shape.data(), r.weight.data(),
-                            r.jxw_of_level.data(), lammpsinput ? nullptr : r.source.data(), d_out, &build_ms);
+  int rc;
+  if (operators_resident)  // the cell tables and the closed lines are the context's
+    rc = gmg_assemble_rhs_resident(gmg, constant_coef ? in.K_of_level.data() : nullptr, r.nq, r.shape.data(), r.weight.data(), r.jxw_of_level.data(),
+                                   lammpsinput ? nullptr : r.source.data(), d_out, &build_ms);
+  else
+    rc = gmg_assemble_rhs(gmg, dim, n, (int64_t)active_cells.size(), in.cell_dofs.data(), in.cell_level.data(), constraint_of_dof.data(),
+                          (int64_t)constraint_lines.size(), in.line_ptr.data(), in.line_master.data(), in.line_weight.data(),
+                          in.line_inhomogeneity.data(), constant_coef ? in.K_of_level.data() : nullptr, r.nq, r.shape.data(), r.weight.data(),
+                          r.jxw_of_level.data(), lammpsinput ? nullptr : r.source.data(), d_out, &build_ms);
   if (rc == GMG_OK) rc = gmg_vec_download(gmg, system_rhs.data(), d_out, n);
   gmg_vec_free(gmg, d_out);
   chk(rc, "gmg_assemble_rhs");
@@ -1511,6 +1570,11 @@ void LaplaceProblem<dim>::assemble_rhs_from_cell_tables() {
 template <int dim>
 int LaplaceProblem<dim>::distribute_constraints_on_device(double *d_u) {
   // (the tables assemble_rhs_from_cell_tables kept for this cycle: repeated solves of one cycle build nothing)
+  if (operators_resident) {  // the closed lines are the context's
+    const int rc = gmg_distribute_constraints_resident(gmg, (int64_t)constraint_of_dof.size(), d_u);
+    if (rc != GMG_OK) last_error = std::string("gmg_distribute_constraints_resident: ") + gmg_last_error(gmg);
+    return rc;
+  }
   const SystemAssemblyInputs &t = cycle_line_tables;
   if (t.line_ptr.size() != constraint_lines.size() + 1) { last_error = "gmg_distribute_constraints: no line tables of this cycle"; return GMG_ERR_INVALID; }
   const int rc = gmg_distribute_constraints(gmg, (int64_t)constraint_of_dof.size(), d_u, constraint_of_dof.data(), (int64_t)constraint_lines.size(),
@@ -1549,7 +1613,7 @@ bool LaplaceProblem<dim>::decide_levels_on_device() {
 // the arrays of gmg_assemble_level_matrix besides the cell table: the cell matrix exactly as assemble_level scales it (the
 // device's matrices have the host's bits only as long as both scale it the same way) and the two flags of every DoF
 template <int dim>
-typename LaplaceProblem<dim>::LevelAssemblyInputs LaplaceProblem<dim>::level_assembly_inputs(int l) const {
+typename LaplaceProblem<dim>::LevelAssemblyInputs LaplaceProblem<dim>::level_assembly_inputs(int l, bool flags) const {
   constexpr int nv = 1 << dim;
   LevelAssemblyInputs in;
   const Quadrature<dim> q_laplace((int)par.degree + 1);
@@ -1559,6 +1623,7 @@ typename LaplaceProblem<dim>::LevelAssemblyInputs LaplaceProblem<dim>::level_ass
   in.K.resize((size_t)nv * nv);
   for (int i = 0; i < nv; ++i)
     for (int j = 0; j < nv; ++j) in.K[(size_t)i * nv + (size_t)j] = Kc[i][j] * s;
+  if (!flags) return in;
   const auto &bnd = level_boundary[(size_t)l];
   const auto &edge = level_refinement_edge[(size_t)l];
   in.dof_flags.resize(bnd.size());
@@ -1754,10 +1819,13 @@ int LaplaceProblem<dim>::upload() {
       if (p) gmg_vec_free(gmg, p);
     d_solution = d_rhs = d_full = nullptr;
     solution_on_device = false;
-    GMGC(gmg_reset(gmg, L));
-  } else {
-    GMGC(gmg_reset(gmg, L));  // the context may have been created early (charge densities) with 1 level
   }
+  // (first upload: the context may have been created early (charge densities) with 1 level.)  gmg_reset drops the mesh
+  // tables; with "Operators from resident tables" they are this cycle's and the entries below read them
+  if (operators_resident) GMGC(gmg_set_option(gmg, "reset_keeps_mesh_tables", 1.0));
+  const int rc_reset = gmg_reset(gmg, L);
+  if (operators_resident) GMGC(gmg_set_option(gmg, "reset_keeps_mesh_tables", 0.0));
+  GMGC(rc_reset);
   operators_uploaded = true;
   build_matrices_ms = 0.0;
   // before the level matrices: sizes the SGS schedule.  0 = one block per rank: the reference's smoother on that many ranks
@@ -1768,11 +1836,17 @@ int LaplaceProblem<dim>::upload() {
   const int64_t n_system = (int64_t)vertex_of_dof.size();
   if (system_on_device) {
     // the active-mesh matrix is formed on the device from the cells' DoFs and the constraint lines
-    const SystemAssemblyInputs in = system_assembly_inputs();
+    const SystemAssemblyInputs in = system_assembly_inputs(!operators_resident);
     sublap(nullptr);
     double build_ms = 0.0;
     int rc_asm;
-    if (par.Problemtype == "Step16") {
+    if (operators_resident && par.Problemtype == "Step16") {  // section 22: the cell tables and the closed lines are the context's
+      const CoefficientInputs co = system_coefficient_inputs();
+      sublap("assemble: coefficient values");
+      rc_asm = gmg_assemble_system_matrix_coef_resident(gmg, co.nq, co.cell_coef.data(), co.G.data(), co.qw.data(), co.scale.data(), &build_ms);
+    } else if (operators_resident) {
+      rc_asm = gmg_assemble_system_matrix_resident(gmg, in.K_of_level.data(), &build_ms);
+    } else if (par.Problemtype == "Step16") {
       // section 18: the coefficient varies -- its values at the cells' quadrature points instead of one cell matrix per level
       const CoefficientInputs co = system_coefficient_inputs();
       sublap("assemble: coefficient values");
@@ -1833,11 +1907,16 @@ int LaplaceProblem<dim>::upload() {
     } else if (levels_on_device) {
       // the level's operators are formed on the device from its cell table and the DoF flags
       const auto t_level = std::chrono::steady_clock::now();
-      const LevelAssemblyInputs in = level_assembly_inputs(l);
+      const LevelAssemblyInputs in = level_assembly_inputs(l, !operators_resident);
       double build_ms = 0.0;
       const int64_t n_level = (int64_t)level_vertex_of_dof[(size_t)l].size(), n_level_cells = (int64_t)triangulation.levels[(size_t)l].size();
       int rc_asm;
-      if (par.Problemtype == "Step16") {  // section 18
+      if (operators_resident && par.Problemtype == "Step16") {  // section 22: the level's cell table and flags are the context's
+        const CoefficientInputs co = level_coefficient_inputs(l);
+        rc_asm = gmg_assemble_level_matrix_coef_resident(gmg, l, co.nq, co.cell_coef.data(), co.G.data(), co.qw.data(), co.scale[0], &build_ms);
+      } else if (operators_resident) {
+        rc_asm = gmg_assemble_level_matrix_resident(gmg, l, in.K.data(), &build_ms);
+      } else if (par.Problemtype == "Step16") {  // section 18
         const CoefficientInputs co = level_coefficient_inputs(l);
         rc_asm = gmg_assemble_level_matrix_coef(gmg, l, dim, n_level, n_level_cells, level_cell_dof_table[(size_t)l].data(), co.nq, co.cell_coef.data(),
                                                 co.G.data(), co.qw.data(), co.scale[0], in.dof_flags.data(), &build_ms);
@@ -1998,7 +2077,11 @@ int LaplaceProblem<dim>::solve_on_device(CycleReport &rep) {
   GMGC(gmg_vec_allgather(gmg, (int64_t)solution.size(), d_full, d_solution));  // every rank keeps the whole solution
   // "RHS from cell tables": constraints.distribute (:1016) on the device before the one download; d_full then stays the
   // solution for the estimator, the forces and the error norm (device_solution) until the next cycle
-  if (rhs_from_cells) GMGC(distribute_constraints_on_device(d_full));
+  if (rhs_from_cells) {
+    sublap("solve: up to the distribution");  // (a labelled lap, not a restart: whatever a caller's next lap covers, it covers with the key off and on)
+    GMGC(distribute_constraints_on_device(d_full));
+    sublap("solve: distribute on device");
+  }
   GMGC(gmg_vec_download(gmg, solution.data(), d_full, (int64_t)solution.size()));
   solution_on_device = rhs_from_cells;
   return GMG_OK;

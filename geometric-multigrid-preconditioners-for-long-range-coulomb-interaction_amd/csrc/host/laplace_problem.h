@@ -82,6 +82,7 @@ struct Parameters {
   bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
   bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
   bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
+  bool operators_from_resident_tables = false;  // gmg_close_constraints and the _resident entries: operators, right-hand side and distribution read the tables gmg_build_mesh_tables left on the device
   bool refinement_on_device = false;     // gmg_refine_forest, gmg_transfer_solution and gmg_build_face_table instead of refine_flagged, the interpolation loop of refine_grid and face_table (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
@@ -144,7 +145,7 @@ class LaplaceProblem {
     std::vector<double> K_of_level, line_weight, line_inhomogeneity;
     std::vector<int64_t> line_ptr;
   };
-  SystemAssemblyInputs system_assembly_inputs() const;
+  SystemAssemblyInputs system_assembly_inputs(bool mesh_arrays = true) const;  // (false: K_of_level alone, what the resident entries take)
   void line_tables(std::vector<int64_t> &line_ptr, std::vector<int32_t> &line_master, std::vector<double> &line_weight,
                    std::vector<double> &line_inhomogeneity) const;  // the constraint lines in CSR form
   SystemAssemblyInputs cycle_line_tables;  // "RHS from cell tables": the line tables of this cycle, kept for gmg_distribute_constraints
@@ -171,7 +172,7 @@ class LaplaceProblem {
     std::vector<double> K;           // [nv][nv]: the cell matrix as assemble_level scales it
     std::vector<uint8_t> dof_flags;  // bit 0 level_boundary, bit 1 level_refinement_edge
   };
-  LevelAssemblyInputs level_assembly_inputs(int l) const;
+  LevelAssemblyInputs level_assembly_inputs(int l, bool flags = true) const;  // (false: K alone, what the resident entry takes)
   // what gmg_assemble_system_matrix_coef / gmg_assemble_level_matrix_coef take beyond the cell tables
   struct CoefficientInputs {
     int nq = 0;
@@ -308,6 +309,11 @@ class LaplaceProblem {
   void distribute_dofs_on_device();     // the one call, and the download of the DoF tables
   void ensure_dof_maps();               // the vertex -> DoF hash tables, built from vertex_of_dof on first use
   bool mesh_on_device = false;            // this cycle's tables came from gmg_build_mesh_tables
+  // "Operators from resident tables" (DESIGN.md section 22): this cycle's device entries read the context's tables
+  bool decide_operators_resident();       // says so once when the key asks for it in vain
+  void close_constraints_on_device();     // gmg_close_constraints with the Dirichlet values of constraint_lines
+  bool operators_resident = false;        // the context holds this cycle's tables and their closed lines
+  bool resident_fallback_reported = false;
   bool mesh_fallback_reported = false;    // "Mesh tables on device" was set but not applicable: said once
   bool dof_maps_ready = false;            // dof_of_vertex / level_dof_of_vertex match vertex_of_dof / level_vertex_of_dof
   double mesh_tables_ms = 0.0;            // device time of gmg_build_mesh_tables for the current mesh

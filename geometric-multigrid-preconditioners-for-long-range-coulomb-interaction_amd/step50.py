@@ -88,6 +88,7 @@ def prm_text(**kw) -> str:
         "level_matrices_on_device": ("Misc", "Level matrices on device"),
         "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
         "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
+        "operators_from_resident_tables": ("Misc", "Operators from resident tables"),
         "refinement_on_device": ("Misc", "Refinement on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
@@ -382,6 +383,10 @@ class Problem:
     def mesh_tables_on_device(self) -> bool:
         """Did the last setup_system form the DoF numbering, the constraints and the level flags through gmg_build_mesh_tables?"""
         return bool(self.L.step50_mesh_tables_on_device(self.h))
+
+    def operators_resident(self) -> bool:
+        """Do this cycle's device entries read the context's mesh tables ("Operators from resident tables" took effect)?"""
+        return bool(self.L.step50_operators_resident(self.h))
 
     def refined_on_device(self) -> bool:
         """Did the last refine_grid go through gmg_refine_forest and gmg_transfer_solution ("Refinement on device")?"""

@@ -397,8 +397,8 @@ int gmg_assemble_system_matrix_coef(gmg_context *ctx, int dim, int64_t n_dofs, i
  *   Dirichlet lines  every DoF in ascending order whose vertex has bit-0 geometry and no hanging line gets the next line index;
  *                    such a line has no entries.
  * The lines come back UNCLOSED and without inhomogeneities (a master may itself carry a Dirichlet line): boundary values and
- * close() stay with the caller.  The tables stay on the device, owned by the context, until the next build, gmg_reset or
- * gmg_destroy; nothing else in the context changes.  build_ms (may be NULL): device time of the build.
+ * close() stay with the caller.  The tables stay on the device, owned by the context, until the next build, gmg_reset
+ * (unless the option reset_keeps_mesh_tables is set, see gmg_set_option) or gmg_destroy; nothing else in the context changes.  build_ms (may be NULL): device time of the build.
  * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a NULL array of nonzero
  * length, a level_ptr that does not start at 0 or decreases, more than 13 levels, n0[d] outside 1 .. 511, a coordinate outside
  * its level's lattice, a first_child that points outside the next level, or level0_lexicographic = 1 with a level 0 that is
@@ -419,6 +419,52 @@ int gmg_get_mesh_tables(gmg_context *ctx, int64_t *n_cells, int64_t *n_dofs, int
  * gmg_assemble_level_matrix takes); NULL arrays are skipped.  GMG_ERR_INVALID for a level the build did not have.          */
 int gmg_get_mesh_level_tables(gmg_context *ctx, int level, int64_t *n_cells, int64_t *n_dofs, int32_t *cell_dofs,
                               uint64_t *vertex_of_dof, uint8_t *dof_flags);
+/* Boundary values and constraints.close() on the tables of the last gmg_build_mesh_tables, where they lie (DESIGN.md section
+ * 22; the loop "close()" of LaplaceProblem::make_constraints on the host).  With H = n_hanging and L = n_lines of the tables:
+ *   Dirichlet lines  l in [H, L) have no entries; inhom[l] = dirichlet_value[l - H] (host array, in line order: the DoF of
+ *                    value i is line_dof[H + i]).  dirichlet_value == NULL means all values are +0.0, for any n_values.
+ *   hanging lines    l < H start from inhom[l] = +0.0 and visit their stored entries e in ascending order, with
+ *                    m = constraint_of_dof[line_master[e]]:  m < 0: the entry is kept, and kept entries retain their relative
+ *                    order;  m >= H: the entry is dropped and inhom[l] = inhom[l] + line_weight[e] * inhom[m], in fp64 with a
+ *                    rounded product and a rounded sum (no fused multiply-add);  0 <= m < H: a hanging node constrained to a
+ *                    hanging node, GMG_ERR_INVALID (found on the device).
+ * The closed lines -- line_ptr [L + 1], line_master / line_weight [line_ptr[L]], line_inhomogeneity [L] -- stay on the device,
+ * owned by the context next to the mesh tables, until the next gmg_close_constraints (which replaces them), the next
+ * gmg_build_mesh_tables, gmg_reset (unless the option reset_keeps_mesh_tables is set) or gmg_destroy.  The unclosed tables are not modified: gmg_get_mesh_tables returns what it
+ * returned before.  The results do not depend on the launch shape (option assemble_max_blocks).  build_ms (may be NULL):
+ * device time.  GMG_ERR_INVALID -- found on the host, before anything is launched -- without mesh tables and for
+ * n_values != L - H; GMG_ERR_UNSUPPORTED on a context with a communicator.  After ANY failure the context holds no closed
+ * constraints.  Zero lines are valid.                                                                                       */
+int gmg_close_constraints(gmg_context *ctx, int64_t n_values, const double *dirichlet_value /* host, or NULL = all +0.0 */,
+                          double *build_ms);
+/* The closed lines of the last gmg_close_constraints: n_lines, n_entries (= line_ptr[n_lines]) and the arrays in the form
+ * gmg_assemble_system_matrix / gmg_assemble_rhs take; NULL arrays are skipped, so a first call with all of them NULL returns
+ * the sizes.  GMG_ERR_INVALID when the context holds no closed constraints.                                                */
+int gmg_get_closed_constraints(gmg_context *ctx, int64_t *n_lines, int64_t *n_entries, int64_t *line_ptr,
+                               int32_t *line_master, double *line_weight, double *line_inhomogeneity);
+/* The resident forms of the assemblies, the right-hand side and the distribution.  Each one is, word for
+ * word, its host-array sibling -- gmg_assemble_system_matrix[_coef], gmg_assemble_level_matrix[_coef], gmg_assemble_rhs,
+ * gmg_distribute_constraints -- applied to dim, n_dofs, n_cells, cell_dofs and cell_level of the resident mesh tables (the
+ * level entries: to the level's n_dofs, n_cells, cell_dofs and dof_flags), and, for the system matrix, the right-hand side and
+ * the distribution, to constraint_of_dof and the CLOSED lines of gmg_close_constraints: the same pattern, the same order of
+ * every sum, the same bits, the same state left in the context or the level.  No mesh array crosses the bus.  The remaining
+ * arguments are the sibling's small host arrays and the per-cell values the host evaluates (cell_coef, source), checked as
+ * the sibling checks them.  The sibling's host loops over the mesh arrays are not repeated: the tables were produced by the
+ * library and are in range by construction (in particular no master of a closed line is constrained, which is what
+ * gmg_distribute_constraints verifies).  Instead, on the host before anything is launched: GMG_ERR_UNSUPPORTED on a context
+ * with a communicator; GMG_ERR_INVALID without mesh tables, without closed constraints (system matrix, right-hand side,
+ * distribution), for a level the build did not have, for n_dofs other than the tables' (distribution), and for source == NULL
+ * without device densities of n_cells x nq.  After a refusal the context or level is as the sibling leaves it (the cell-matrix
+ * system form: untouched; the _coef system form and both level forms: no operator), and rhs / u are untouched.              */
+int gmg_assemble_system_matrix_resident(gmg_context *ctx, const double *K_of_level, double *build_ms);
+int gmg_assemble_system_matrix_coef_resident(gmg_context *ctx, int nq, const double *cell_coef, const double *G, const double *qw,
+                                             const double *scale_of_level, double *build_ms);
+int gmg_assemble_level_matrix_resident(gmg_context *ctx, int level, const double *K, double *build_ms);
+int gmg_assemble_level_matrix_coef_resident(gmg_context *ctx, int level, int nq, const double *cell_coef, const double *G,
+                                            const double *qw, double scale, double *build_ms);
+int gmg_assemble_rhs_resident(gmg_context *ctx, const double *K_of_level, int nq, const double *shape, const double *weight,
+                              const double *jxw_of_level, const double *source, double *rhs /* device */, double *build_ms);
+int gmg_distribute_constraints_resident(gmg_context *ctx, int64_t n_dofs, double *u /* device, in place */);
 /* The step between two cycles, formed on the device from the forest alone.  The three entries below take
  * the forest exactly as gmg_build_mesh_tables does -- dim, n0, n_levels, level_ptr, cell_coord, cell_first_child -- and run
  * the same checks on the host before anything is launched, with the same codes: GMG_ERR_INVALID for dim other than 2 or 3, a
@@ -687,7 +733,11 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
  * 256: workgroup size of the force kernels and of the exact-potential kernels; the results do not depend on it),
  * exact_chunk_log2 (0 .. 35, default 35: gmg_gaussian_potential and gmg_energy_norm_error do at most 2^k point-atom
- * evaluations per launch; tests force many launches on small inputs, the results do not depend on it).  Options that shape a device
+ * evaluations per launch; tests force many launches on small inputs, the results do not depend on it), reset_keeps_mesh_tables
+ * (0 / 1, default 0: while it is 1, gmg_reset leaves the tables of gmg_build_mesh_tables and the closed lines of
+ * gmg_close_constraints in the context instead of dropping them -- for a caller that resets the context between the build and
+ * the resident assemblies; the caller must set it back to 0 after that reset, or every later gmg_reset keeps the tables too;
+ * the next gmg_build_mesh_tables and gmg_destroy drop them regardless).  Options that shape a device
  * layout take effect at the next gmg_set_*_matrix.  The same keys are read once from the environment
  * variable GMG_OPTIONS="key=value,..." at gmg_create (for profiling scripts around bench.py).        */
 int gmg_set_option(gmg_context *ctx, const char *key, double value);
