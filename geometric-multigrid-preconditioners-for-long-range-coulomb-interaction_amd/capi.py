@@ -44,6 +44,7 @@ SYMBOLS = [
     "gmg_vec_allgather",
     "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks",
     "gmg_set_ssor_block_rows", "gmg_set_ssor_partition", "gmg_get_ssor_partition", "gmg_ssor_balance_rows", "gmg_calibrate_hbm", "gmg_charge_density", "gmg_get_charge_density", "gmg_rhs_assemble",
+    "gmg_charge_density_resident", "gmg_get_resident_cell_geometry",
     "gmg_set_point_locator", "gmg_atom_forces", "gmg_direct_coulomb",
     "gmg_gaussian_potential", "gmg_energy_norm_error",
     "gmg_get_ssor_plan", "gmg_get_ssor_backward_rows", "gmg_ssor_slot_plan",
@@ -581,6 +582,44 @@ class Context:
                                             D(xyz), D(q), C.c_double(r_c), C.c_double(cutoff), C.c_int(1 if use_lists else 0),
                                             C.c_int(len(qp)), D(qp), None if out is None else D(out)))
         return out
+
+    def charge_density_resident(self, origin, h0, atom_xyz, atom_q, r_c, cutoff, use_lists, quadrature_points, dens=True, n_cells=None, nq=None,
+                                n_atoms=None):
+        """rho [n_cells, nq] for the active cells of the resident mesh tables (gmg_charge_density_resident): (rho, device time in
+        ms).  dens=None keeps the densities on the device and returns (None, ms).  None for an array passes NULL (with n_atoms /
+        nq); n_cells: the cells of the tables when this view did not build them."""
+        xyz = None if atom_xyz is None else np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        q = None if atom_q is None else np.ascontiguousarray(atom_q, dtype=np.float64)
+        qp = None if quadrature_points is None else np.ascontiguousarray(quadrature_points, dtype=np.float64).reshape(-1, 3)
+        if n_atoms is None:
+            n_atoms = len(q) if q is not None else len(xyz) if xyz is not None else 0
+        if nq is None:
+            nq = len(qp)
+        D = lambda a: None if a is None else _p(a, C.c_double)
+        out = None
+        if dens is not None:
+            if n_cells is None:
+                n = [C.c_int64(0) for _ in range(5)]
+                rc = self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], None, None, None, None, None, None, None, None)
+                n_cells = n[0].value if rc == OK else 0
+            out = np.zeros((int(n_cells), max(int(nq), 0)))
+        ms = C.c_double(0)
+        self._chk(self.L.gmg_charge_density_resident(self.h, C.c_double(origin), C.c_double(h0), C.c_int64(int(n_atoms)), D(xyz), D(q), C.c_double(r_c),
+                                                     C.c_double(cutoff), C.c_int(1 if use_lists else 0), C.c_int(int(nq)), D(qp), D(out), C.byref(ms)))
+        return out, ms.value
+
+    def get_resident_cell_geometry(self, origin, h0, want=(True, True, True)):
+        """(cell_lo [n_cells, 3], cell_h [n_cells], root_lo [n_cells, 3]) as gmg_charge_density_resident forms them from the
+        resident mesh tables; want: which of the three to fetch (the others are None)"""
+        n = [C.c_int64(0) for _ in range(5)]
+        rc = self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], None, None, None, None, None, None, None, None)
+        nc = n[0].value if rc == OK else 0
+        lo = np.zeros((nc, 3)) if want[0] else None
+        hh = np.zeros(nc) if want[1] else None
+        rlo = np.zeros((nc, 3)) if want[2] else None
+        D = lambda a: None if a is None else _p(a, C.c_double)
+        self._chk(self.L.gmg_get_resident_cell_geometry(self.h, C.c_double(origin), C.c_double(h0), D(lo), D(hh), D(rlo)))
+        return lo, hh, rlo
 
     def get_charge_density(self, n_cells, nq):
         """the densities charge_density(..., dens=None) left on the device: [n_cells, nq]"""

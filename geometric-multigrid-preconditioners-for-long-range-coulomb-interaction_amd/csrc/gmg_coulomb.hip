@@ -26,6 +26,7 @@
 #include "gmg_mesh_tables.hpp"
 #include "gmg_close.hpp"
 #include "gmg_refine.hpp"
+#include "gmg_density.hpp"
 #include "gmg_mem.hpp"
 #include <hip/hip_ext.h>
 
@@ -279,6 +280,7 @@ struct gmg_context {
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
   MeshTables mesh;              // gmg_build_mesh_tables: the tables of the last build
   RefinedForest refined;        // gmg_refine_forest: the forest of the last refinement
+  int density_segment = 0;      // gmg_density.hpp: atoms per LDS segment of a cell's lane group (option "density_segment"; 0: by group size); results do not depend on it
   int estimate_max_blocks = 0;  // gmg_estimate.hpp: the same cap for the estimator's kernels (option "estimate_max_blocks"); results do not depend on it
   Comm comm;
   bool dist = false;             // communicator initialised: level 0 + system rows are partitioned
@@ -3612,6 +3614,111 @@ int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *de
   return GMG_OK;
 }
 
+// ---- charge densities from the resident mesh tables (gmg_density.hpp)
+
+// what both entries check first: no communicator, 3D tables, a root lattice
+static int density_resident_tables(gmg_context *ctx, const char *who, double h0) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  if (!ctx->mesh.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  if (ctx->mesh.dim != 3) return bad(GMG_ERR_UNSUPPORTED, "the mesh tables are not 3D");
+  if (!(h0 > 0.0)) return bad(GMG_ERR_INVALID, "h0 must be positive");
+  return GMG_OK;
+}
+
+int gmg_charge_density_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c,
+                                double cutoff, int use_lists, int nq, const double *quadrature_points, double *dens, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_charge_density_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  ctx->dens_dev.reset(); ctx->dens_cells = 0; ctx->dens_nq = 0;  // after any failure the context holds no densities
+  if (build_ms) *build_ms = 0.0;
+  CHK(density_resident_tables(ctx, who, h0));
+  if (nq < 1) return bad(GMG_ERR_INVALID, "nq must be at least 1");
+  if (!(r_c > 0.0)) return bad(GMG_ERR_INVALID, "r_c must be positive");
+  if (!(cutoff >= 0.0)) return bad(GMG_ERR_INVALID, "cutoff must not be negative");
+  if (n_atoms < 0 || n_atoms >= ((int64_t)1 << 31)) return bad(GMG_ERR_INVALID, "n_atoms outside [0, 2^31)");
+  if (!quadrature_points || (n_atoms > 0 && (!atom_xyz || !atom_q))) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  const MeshTables &m = ctx->mesh;
+  const int64_t n_cells = m.n_cells;
+  gmg_forces::Bins B;  // (host; 64 k atoms: microseconds)
+  const double bs = std::max(cutoff, 1e-12);
+  if (use_lists && !gmg_forces::bin_atoms(n_atoms, atom_xyz, bs, (int64_t)1 << 28, B)) return bad(GMG_ERR_UNSUPPORTED, "atom bin grid too large");
+  if (n_cells == 0) return GMG_OK;
+  DevPtr<double> d_xyz, d_q, d_qp, d_dens;
+  DevPtr<int32_t> d_bptr, d_bitems;
+  Event e0, e1;
+  HIPC(upload(d_xyz, atom_xyz, 3 * (size_t)n_atoms, ctx->stream));
+  HIPC(upload(d_q, atom_q, (size_t)n_atoms, ctx->stream));
+  HIPC(upload(d_qp, quadrature_points, 3 * (size_t)nq, ctx->stream));
+  HIPC(upload(d_bptr, B.ptr, ctx->stream, 2));
+  HIPC(upload(d_bitems, B.items, ctx->stream, 2));
+  HIPC(d_dens.alloc((size_t)n_cells * (size_t)nq));
+  HIPC(e0.create());
+  HIPC(e1.create());
+  DensityResArgs a{};
+  a.cell_dofs = m.cell_dofs.get(); a.cell_level = m.cell_level.get(); a.vertex_of_dof = m.vertex_of_dof.get(); a.n_cells = n_cells;
+  a.origin = origin; a.h0 = h0;
+  a.atom_xyz = d_xyz.get(); a.atom_q = d_q.get(); a.n_atoms = (int)n_atoms;
+  a.bin_lo0 = B.lo[0]; a.bin_lo1 = B.lo[1]; a.bin_lo2 = B.lo[2]; a.bin_size = bs;
+  a.bin_n0 = B.n[0]; a.bin_n1 = B.n[1]; a.bin_n2 = B.n[2];
+  a.bin_ptr = d_bptr.get(); a.bin_items = d_bitems.get();
+  a.cutoff = cutoff; a.r_c = r_c; a.use_lists = use_lists ? 1 : 0;
+  a.qp = d_qp.get(); a.nq = nq; a.dens = d_dens.get();
+  // a cell's lane group: the smallest power of two >= min(nq, 64); its LDS segment: 4 g - 1 atoms, at most 127 (32 KB per
+  // workgroup: measured faster than 8 g - 1, which halves the workgroups a CU holds), or option
+  // density_segment made odd, no shorter than the group and within 64 KB per workgroup
+  while ((1 << a.lg_g) < std::min(nq, 64)) ++a.lg_g;
+  const int g = 1 << a.lg_g, groups = kDrThreads / g;
+  a.cap = std::max(std::min(4 * g - 1, 127), g | 1);
+  if (ctx->density_segment > 0) a.cap = std::min(std::max(ctx->density_segment | 1, g | 1), ((int)(65536 / (32 * groups)) - 1) | 1);
+  if (a.cap < g) a.cap = g | 1;
+  const size_t lds = (size_t)groups * (size_t)a.cap * 4 * sizeof(double);
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  hipLaunchKernelGGL(density_resident_kernel, asm_blocks(ctx, n_cells, groups), dim3(kDrThreads), lds, ctx->stream, a);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(e1.get(), ctx->stream);
+  if (e == hipSuccess && dens) e = hipMemcpyAsync(dens, d_dens.get(), sizeof(double) * (size_t)n_cells * (size_t)nq, hipMemcpyDeviceToHost, ctx->stream);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (the uploads above live until the stream has run the kernel)
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) { ctx->err = std::string(who) + ": " + hipGetErrorString(e); return GMG_ERR_HIP; }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
+  if (!dens) {  // the densities stay in HBM, as gmg_charge_density leaves them
+    ctx->dens_dev = std::move(d_dens); ctx->dens_cells = n_cells; ctx->dens_nq = nq;
+  }
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] charge densities from resident tables: %lld cells x %d points, %lld atoms, groups of %d lanes, segments of %d atoms, %.3f ms\n",
+                 (long long)n_cells, nq, (long long)n_atoms, g, a.cap, ms);
+  return GMG_OK;
+}
+
+int gmg_get_resident_cell_geometry(gmg_context *ctx, double origin, double h0, double *cell_lo, double *cell_h, double *root_lo) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  CHK(density_resident_tables(ctx, "gmg_get_resident_cell_geometry", h0));
+  const MeshTables &m = ctx->mesh;
+  const int64_t n = m.n_cells;
+  if (n == 0 || (!cell_lo && !cell_h && !root_lo)) return GMG_OK;
+  DevPtr<double> d_lo, d_h, d_root;
+  if (cell_lo) HIPC(d_lo.alloc(3 * (size_t)n));
+  if (cell_h) HIPC(d_h.alloc((size_t)n));
+  if (root_lo) HIPC(d_root.alloc(3 * (size_t)n));
+  DensityResArgs a{};
+  a.cell_dofs = m.cell_dofs.get(); a.cell_level = m.cell_level.get(); a.vertex_of_dof = m.vertex_of_dof.get(); a.n_cells = n;
+  a.origin = origin; a.h0 = h0;
+  a.cell_lo = d_lo.get(); a.cell_h = d_h.get(); a.root_lo = d_root.get();
+  hipLaunchKernelGGL(dr_geometry_kernel, asm_blocks(ctx, n, kDrThreads), dim3(kDrThreads), 0, ctx->stream, a);
+  HIPC(hipGetLastError());
+  HIPC(mesh_fetch(ctx, cell_lo, d_lo, 3 * n));
+  HIPC(mesh_fetch(ctx, cell_h, d_h, n));
+  HIPC(mesh_fetch(ctx, root_lo, d_root, 3 * n));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
 // ---- atom forces (gmg_forces.hpp) ----
 
 }  // extern "C"
@@ -5507,7 +5614,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
     ctx->force_block = (int)value;
   }
   else if (k == "reset_keeps_mesh_tables") ctx->reset_keeps_mesh_tables = on;
-  else if (k == "assemble_max_blocks") {
+  else if (k == "density_segment") {
+    if (!(value >= 0 && value <= 2047) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "density_segment: an integer in 0 .. 2047");
+    ctx->density_segment = (int)value;
+  } else if (k == "assemble_max_blocks") {
     if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "assemble_max_blocks: an integer in 0 .. 65536");
     ctx->assemble_max_blocks = (int)value;
   }

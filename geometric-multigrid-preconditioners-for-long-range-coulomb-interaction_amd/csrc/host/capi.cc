@@ -349,6 +349,8 @@ int step50_system_assembly_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t
 int step50_mesh_tables_on_device(step50_problem *h) { return DISPATCH(h, mesh_on_device) ? 1 : 0; }
 // "Operators from resident tables" (DESIGN.md section 22): did the key take effect in the last setup_system?
 int step50_operators_resident(step50_problem *h) { return DISPATCH(h, operators_resident) ? 1 : 0; }
+// "Charge densities from resident tables" (DESIGN.md section 23): did the key take effect in the last setup_system?
+int step50_densities_resident(step50_problem *h) { return DISPATCH(h, densities_resident) ? 1 : 0; }
 int step50_forest_sizes(step50_problem *h, int64_t sizes[3]) {
   return guarded(h, [&] {
     const auto fc = DISPATCH(h, forest_cells());

@@ -261,6 +261,10 @@ void ParameterReader::declare_parameters() {
             // host arrays; cycles in which "Mesh tables on device" took effect, with "System matrix on device", "Level matrices
             // on device" and "RHS from cell tables" set, DESIGN.md section 22
             {"Operators from resident tables", "false"},
+            // gmg_charge_density_resident: the densities of the active cells from the tables gmg_build_mesh_tables left on the
+            // device instead of per-cell corner / edge / root arrays built here and uploaded; cycles in which "Mesh tables on
+            // device" took effect, with "Charge densities on device" set, 3D LAMMPS input, one rank, DESIGN.md section 23
+            {"Charge densities from resident tables", "false"},
             // gmg_refine_forest (2:1 closure of the marks and the split), gmg_transfer_solution (SolutionTransfer::interpolate
             // and constraints.set_zero) and gmg_build_face_table (the estimator's face table) instead of Forest::refine_flagged,
             // the interpolation loop of refine_grid and face_table; cycles that run on the device, one rank, DESIGN.md section 21
@@ -355,6 +359,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.rhs_from_cell_tables = prm.get_bool("RHS from cell tables");
   p.mesh_tables_on_device = prm.get_bool("Mesh tables on device");
   p.operators_from_resident_tables = prm.get_bool("Operators from resident tables");
+  p.densities_from_resident_tables = prm.get_bool("Charge densities from resident tables");
   p.refinement_on_device = prm.get_bool("Refinement on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
@@ -1002,10 +1007,28 @@ void LaplaceProblem<dim>::setup_system(unsigned int cycle) {
   system_rhs.assign((size_t)n, 0.0);
   if (cycle == 0 && par.flag_rhs_assembly && lammpsinput) rhs_assembly_optimization();
   sublap("rhs_assembly_optimization");
+  densities_resident = decide_densities_resident();
   if (lammpsinput) compute_charge_densities();
   sublap("compute_charge_densities");
+  if (densities_resident && sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", densities_resident_ms);
   make_constraints();  // calls compute_moments() first when atoms are present (:675-679)
   sublap("make_constraints");
+}
+
+// Does this cycle's compute_charge_densities read the context's mesh tables?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_densities_resident() {
+  if (!par.densities_from_resident_tables) return false;
+  const char *why = distributed                 ? "the run is distributed"
+                    : dim != 3                  ? "the problem is not 3D"
+                    : !lammpsinput              ? "no LAMMPS input"
+                    : !mesh_on_device           ? "the mesh tables were not formed on the device"
+                    : !par.densities_on_device  ? "Charge densities on device is not set"
+                                                : nullptr;
+  if (!why) return true;
+  if (!densities_fallback_reported) pcout(std::string("   Charge densities from resident tables: not applicable (") + why + "), per-cell arrays from the host");
+  densities_fallback_reported = true;
+  return false;
 }
 
 template <int dim>
@@ -1019,8 +1042,11 @@ void LaplaceProblem<dim>::compute_charge_densities() {
     // the same sums on the MI355X (gmg_charge_density), cell geometry in, rho out
     if (ensure_context() != GMG_OK) throw std::runtime_error("charge densities on the device: " + last_error);
     const size_t nc = active_cells.size();
-    std::vector<double> lo(3 * nc), hh(nc), rlo(3 * nc), qp(3 * nq), dens(nc * nq);
-    for (size_t ci = 0; ci < nc; ++ci) {
+    const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+    const bool hold = densities_resident && check && std::atoi(check) != 0;  // the device's geometry against the loop below
+    const size_t ng = densities_resident && !hold ? 0 : nc;                  // (resident: no per-cell array is built)
+    std::vector<double> lo(3 * ng), hh(ng), rlo(3 * ng), qp(3 * nq), dens(densities_resident && par.rhs_on_device ? 0 : nc * nq);
+    for (size_t ci = 0; ci < ng; ++ci) {
       const ActiveCell &ac = active_cells[ci];
       const Cell &cell = triangulation.levels[(size_t)ac.level][(size_t)ac.index];
       double x0[3];
@@ -1036,6 +1062,24 @@ void LaplaceProblem<dim>::compute_charge_densities() {
     // "RHS on device": the densities stay in HBM (dens = NULL) and gmg_rhs_assemble integrates them there; the host gets a
     // copy only if something asks for it (HEAD's residual estimator, the rc_variation check vector): ensure_host_densities()
     densities_device_resident = par.rhs_on_device;
+    if (densities_resident) {
+      // "Charge densities from resident tables": the cells' geometry follows from cell_level and vertex_of_dof where they lie
+      int rc = gmg_charge_density_resident(gmg, triangulation.origin, triangulation.h0, (int64_t)number_of_atoms, atom_positions.data(), charges.data(),
+                                           par.r_c, par.nonzero_density_radius_parameter * par.r_c, par.flag_rhs_assembly ? 1 : 0, (int)nq, qp.data(),
+                                           densities_device_resident ? nullptr : dens.data(), &densities_resident_ms);
+      if (rc != GMG_OK) throw std::runtime_error(std::string("gmg_charge_density_resident: ") + gmg_last_error(gmg));
+      if (hold) {
+        std::vector<double> d_lo(3 * nc), d_hh(nc), d_rlo(3 * nc);
+        rc = gmg_get_resident_cell_geometry(gmg, triangulation.origin, triangulation.h0, d_lo.data(), d_hh.data(), d_rlo.data());
+        if (rc != GMG_OK) throw std::runtime_error(std::string("gmg_get_resident_cell_geometry: ") + gmg_last_error(gmg));
+        if (nc && (std::memcmp(d_lo.data(), lo.data(), sizeof(double) * 3 * nc) != 0 || std::memcmp(d_hh.data(), hh.data(), sizeof(double) * nc) != 0 ||
+                   std::memcmp(d_rlo.data(), rlo.data(), sizeof(double) * 3 * nc) != 0))
+          throw std::logic_error("Charge densities from resident tables: the device's cell geometry differs from the host's");
+      }
+      if (densities_device_resident) { density_values_for_each_cell.clear(); return; }
+      for (size_t ci = 0; ci < nc; ++ci) density_values_for_each_cell[ci].assign(dens.begin() + (std::ptrdiff_t)(ci * nq), dens.begin() + (std::ptrdiff_t)((ci + 1) * nq));
+      return;
+    }
     const int rc = gmg_charge_density(gmg, (int64_t)nc, lo.data(), hh.data(), rlo.data(), triangulation.h0, (int64_t)number_of_atoms,
                                       atom_positions.data(), charges.data(), par.r_c, par.nonzero_density_radius_parameter * par.r_c,
                                       par.flag_rhs_assembly ? 1 : 0, (int)nq, qp.data(), densities_device_resident ? nullptr : dens.data());

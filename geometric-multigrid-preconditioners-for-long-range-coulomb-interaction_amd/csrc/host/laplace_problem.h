@@ -83,6 +83,7 @@ struct Parameters {
   bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
   bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
   bool operators_from_resident_tables = false;  // gmg_close_constraints and the _resident entries: operators, right-hand side and distribution read the tables gmg_build_mesh_tables left on the device
+  bool densities_from_resident_tables = false;  // gmg_charge_density_resident: the densities read the cells' geometry from the tables gmg_build_mesh_tables left on the device
   bool refinement_on_device = false;     // gmg_refine_forest, gmg_transfer_solution and gmg_build_face_table instead of refine_flagged, the interpolation loop of refine_grid and face_table (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
@@ -314,6 +315,11 @@ class LaplaceProblem {
   void close_constraints_on_device();     // gmg_close_constraints with the Dirichlet values of constraint_lines
   bool operators_resident = false;        // the context holds this cycle's tables and their closed lines
   bool resident_fallback_reported = false;
+  // "Charge densities from resident tables" 
+  bool decide_densities_resident();       // says so once when the key asks for it in vain
+  bool densities_resident = false;        // this cycle's densities came from gmg_charge_density_resident
+  bool densities_fallback_reported = false;
+  double densities_resident_ms = 0.0;     // device time of that call
   bool mesh_fallback_reported = false;    // "Mesh tables on device" was set but not applicable: said once
   bool dof_maps_ready = false;            // dof_of_vertex / level_dof_of_vertex match vertex_of_dof / level_vertex_of_dof
   double mesh_tables_ms = 0.0;            // device time of gmg_build_mesh_tables for the current mesh

@@ -89,6 +89,7 @@ def prm_text(**kw) -> str:
         "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
         "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
         "operators_from_resident_tables": ("Misc", "Operators from resident tables"),
+        "densities_from_resident_tables": ("Misc", "Charge densities from resident tables"),
         "refinement_on_device": ("Misc", "Refinement on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
@@ -387,6 +388,11 @@ class Problem:
     def operators_resident(self) -> bool:
         """Do this cycle's device entries read the context's mesh tables ("Operators from resident tables" took effect)?"""
         return bool(self.L.step50_operators_resident(self.h))
+
+    def densities_resident(self) -> bool:
+        """Did the last setup_system form the densities through gmg_charge_density_resident ("Charge densities from resident
+        tables" took effect)?"""
+        return bool(self.L.step50_densities_resident(self.h))
 
     def refined_on_device(self) -> bool:
         """Did the last refine_grid go through gmg_refine_forest and gmg_transfer_solution ("Refinement on device")?"""

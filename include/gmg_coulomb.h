@@ -196,6 +196,36 @@ int gmg_charge_density(gmg_context *ctx, int64_t n_cells, const double *cell_lo,
                        const double *quadrature_points, double *dens);
 /* the densities gmg_charge_density kept on the device (dens == NULL), copied out: [n_cells * nq]                        */
 int gmg_get_charge_density(gmg_context *ctx, int64_t n_cells, int nq, double *dens);
+/* The same densities for the active cells of the 3D tables the last gmg_build_mesh_tables left on the device: no per-cell
+ * array crosses the bus.  With n_cells, cell_dofs, cell_level and vertex_of_dof of those tables, active cell a of level l has
+ *   k = vertex_of_dof[cell_dofs[8 a]],   c[d] = ((k >> 21 d) & 0x1fffff) >> (12 - l),   h = h0 / 2^l,
+ *   cell_lo[d] = origin + h * c[d],   root_lo[d] = origin + h0 * (c[d] >> l),
+ * each a rounded product followed by a rounded sum (no fused multiply-add): what Forest::cell_origin and the driver's loop
+ * give for origin and h0 of the root lattice.  The definition of gmg_charge_density then applies word for word to this
+ * geometry with cell_h = h and root_h = h0: rho, the points cell_lo + h * quadrature_points[q], the list predicate on the
+ * nearest root vertex with a strict <, use_lists = 0 meaning all atoms, exactly +0.0 for an empty list or n_atoms = 0.
+ * One point is tighter than there: every output value is ONE sequential sum from +0.0 by a single lane, without a
+ * cross-lane reduction, of the addends (constant * exp(-(r * r) * (1 / r_c^2))) * q_k, r = sqrt(dx dx + dy dy + dz dz), in
+ * an order that depends only on the atoms and on the cell's root: with B = gmg_forces::bin_atoms(atoms, edge max(cutoff,
+ * 1e-12)), the candidate bins floor((root_lo[d] - cutoff - B.lo[d]) / edge) .. floor((root_lo[d] + h0 + cutoff - B.lo[d]) /
+ * edge), clipped to the grid, ascending with x fastest, a bin's atoms in the bin's stored order (ascending atom index), the
+ * atoms that fail the predicate left out; with use_lists = 0 all atoms in index order.  The bits therefore do not depend on
+ * the launch shape (option assemble_max_blocks caps the workgroups; option density_segment, diagnostic, sets the atoms a
+ * cell's lanes stage in LDS at a time, 0 = by nq).
+ * dens == NULL leaves the densities on the device exactly as gmg_charge_density does (gmg_get_charge_density,
+ * gmg_rhs_assemble, gmg_assemble_rhs_resident with source = NULL and gmg_estimate_error find n_cells x nq of them); a host
+ * dens [n_cells * nq] receives them and none are kept.  The atoms are host arguments and are binned on the host.  build_ms
+ * (may be NULL): device time of the kernel.  Zero cells and zero atoms are valid.
+ * Found on the host before anything is launched: GMG_ERR_UNSUPPORTED on a communicator, for 2D tables and for a bin grid
+ * of more than 2^28 bins (use_lists != 0); GMG_ERR_INVALID without mesh tables, for nq < 1, r_c <= 0, h0 <= 0, a negative
+ * cutoff, n_atoms outside [0, 2^31), or a NULL input of nonzero length.  After any failure the context holds no densities. */
+int gmg_charge_density_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz,
+                                const double *atom_q, double r_c, double cutoff, int use_lists, int nq,
+                                const double *quadrature_points, double *dens /* host [n_cells*nq] or NULL */, double *build_ms);
+/* cell_lo [3 n_cells], cell_h [n_cells], root_lo [3 n_cells] as gmg_charge_density_resident forms them (the same device
+ * function), copied out so that they can be held against the host's bit for bit; an array passed as NULL is skipped.  The
+ * same refusals for the communicator, the tables and h0.  The context's densities are left alone.                        */
+int gmg_get_resident_cell_geometry(gmg_context *ctx, double origin, double h0, double *cell_lo, double *cell_h, double *root_lo);
 /* The right-hand side of assemble_system (src/step-50.cc:813-828) from the densities the preceding
  * gmg_charge_density(..., dens = NULL) left on the device -- they never cross PCIe:
  *   per cell   F_i = sum_q shape[q][i] * rho_q * weight[q] * jxw_of_level[level]      (:813-820, the reference's operand order)
@@ -733,7 +763,9 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
  * 256: workgroup size of the force kernels and of the exact-potential kernels; the results do not depend on it),
  * exact_chunk_log2 (0 .. 35, default 35: gmg_gaussian_potential and gmg_energy_norm_error do at most 2^k point-atom
- * evaluations per launch; tests force many launches on small inputs, the results do not depend on it), reset_keeps_mesh_tables
+ * evaluations per launch; tests force many launches on small inputs, the results do not depend on it), density_segment
+ * (0 .. 2047, default 0 = by nq: atoms per LDS segment of gmg_charge_density_resident, made odd and fitted to the group size
+ * and to 64 KB per workgroup; the results do not depend on it), reset_keeps_mesh_tables
  * (0 / 1, default 0: while it is 1, gmg_reset leaves the tables of gmg_build_mesh_tables and the closed lines of
  * gmg_close_constraints in the context instead of dropping them -- for a caller that resets the context between the build and
  * the resident assemblies; the caller must set it back to 0 after that reset, or every later gmg_reset keeps the tables too;
