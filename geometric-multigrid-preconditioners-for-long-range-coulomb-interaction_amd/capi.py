@@ -34,6 +34,8 @@ SYMBOLS = [
     "gmg_assemble_level_matrix_coef_resident", "gmg_assemble_rhs_resident", "gmg_distribute_constraints_resident",
     "gmg_refine_forest", "gmg_get_refined_forest", "gmg_transfer_solution", "gmg_build_face_table",
     "gmg_estimate_error",
+    "gmg_build_face_table_resident", "gmg_get_face_table", "gmg_estimate_error_resident", "gmg_get_marks", "gmg_refine_forest_marked",
+    "gmg_energy_norm_error_resident",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
@@ -871,6 +873,93 @@ class Context:
                                             C.byref(nm), C.byref(ms)))
         return SimpleNamespace(eta=eta, kelly_sq=ksq, residual_sq=rsq, face_int=fi, threshold=thr.value, mark=mark, n_marked=nm.value,
                                build_ms=ms.value)
+
+    # ---- the end of a cycle on the resident mesh tables: face table, estimator and marks, refinement, error norm
+    def _mesh_sizes(self):
+        """(n_cells, n_dofs) of the resident mesh tables, (0, 0) when the context holds none"""
+        n = [C.c_int64(0) for _ in range(5)]
+        rc = self.L.gmg_get_mesh_tables(self.h, *[C.byref(v) for v in n], None, None, None, None, None, None, None, None)
+        return (n[0].value, n[1].value) if rc == OK else (0, 0)
+
+    def build_face_table_resident(self, dim, n0, level_ptr, cell_coord, cell_first_child, n_levels=None):
+        """gmg_build_face_table with the table kept in the context (gmg_build_face_table_resident; get_face_table copies it
+        out): namespace(n_active, build_ms)"""
+        from types import SimpleNamespace
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        na, ms = C.c_int64(0), C.c_double(0)
+        self._chk(self.L.gmg_build_face_table_resident(self.h, *args, C.byref(na), C.byref(ms)))
+        return SimpleNamespace(n_active=na.value, build_ms=ms.value)
+
+    def get_face_table(self, dim=None):
+        """The kept face table as numpy arrays: namespace(n_active, face_kind [n_active, 2 dim], face_cell [n_active, 2 dim,
+        2^(dim-1)])"""
+        from types import SimpleNamespace
+        na = C.c_int64(0)
+        self._chk(self.L.gmg_get_face_table(self.h, C.byref(na), None, None))
+        dim = self._mesh_dim(dim)
+        fk, fcell = np.zeros((na.value, 2 * dim), dtype=np.uint8), np.zeros((na.value, 2 * dim, 1 << (dim - 1)), dtype=np.int32)
+        self._chk(self.L.gmg_get_face_table(self.h, C.byref(na), _p(fk, C.c_uint8) if fk.size else None, _p(fcell, C.c_int32) if fcell.size else None))
+        return SimpleNamespace(n_active=na.value, face_kind=fk, face_cell=fcell)
+
+    def estimate_error_resident(self, h_of_level, face_measure_of_level, diameter_of_level, gauss_x, gauss_w, u, residual=0, weight=None,
+                                jxw_of_level=None, dens=None, fraction=0.6, n_u=None, dim=None):
+        """gmg_estimate_error on the resident mesh tables and the kept face table (gmg_estimate_error_resident): the namespace
+        of estimate_error.  The marks also stay in the context (get_marks, refine_forest_marked)."""
+        from types import SimpleNamespace
+        n_cells, _ = self._mesh_sizes()
+        dim = getattr(self, "mesh_dim", 3) if dim is None else dim
+        nf = 2 * int(dim)
+        tabs = [np.ascontiguousarray([] if t is None else t, dtype=np.float64) for t in (h_of_level, face_measure_of_level, diameter_of_level)]
+        gx = np.ascontiguousarray([] if gauss_x is None else gauss_x, dtype=np.float64)
+        gw = np.ascontiguousarray([] if gauss_w is None else gauss_w, dtype=np.float64)
+        w = np.ascontiguousarray([] if weight is None else weight, dtype=np.float64)
+        jxw = np.ascontiguousarray([] if jxw_of_level is None else jxw_of_level, dtype=np.float64)
+        de = None if dens is None else np.ascontiguousarray(dens, dtype=np.float64)
+        eta, mark = np.zeros(n_cells, dtype=np.float32), np.zeros(n_cells, dtype=np.uint8)
+        ksq, rsq, fi = np.zeros(n_cells), np.zeros(n_cells), np.zeros((n_cells, nf))
+        thr, ms, nm = C.c_double(0), C.c_double(0), C.c_int64(0)
+        opt = lambda a, t: _p(a, t) if a is not None and a.size else None
+        D = C.c_double
+        self._chk(self.L.gmg_estimate_error_resident(self.h, opt(tabs[0], D), opt(tabs[1], D), opt(tabs[2], D), C.c_int(len(gx)), opt(gx, D), opt(gw, D),
+                                                     u.ptr if u is not None else None,
+                                                     C.c_int64(int(u.n if n_u is None else n_u) if u is not None else int(n_u or 0)),
+                                                     C.c_int(int(residual)), C.c_int(len(w)), opt(w, D), opt(jxw, D), opt(de, D), C.c_double(fraction),
+                                                     opt(eta, C.c_float), opt(ksq, D), opt(rsq, D), opt(fi, D), C.byref(thr), opt(mark, C.c_uint8),
+                                                     C.byref(nm), C.byref(ms)))
+        return SimpleNamespace(eta=eta, kelly_sq=ksq, residual_sq=rsq, face_int=fi, threshold=thr.value, mark=mark, n_marked=nm.value,
+                               build_ms=ms.value)
+
+    def get_marks(self):
+        """The marks the last estimate_error_resident kept: namespace(n_cells, mark [n_cells] uint8, n_marked)"""
+        from types import SimpleNamespace
+        nc, nm = C.c_int64(0), C.c_int64(0)
+        self._chk(self.L.gmg_get_marks(self.h, C.byref(nc), None, C.byref(nm)))
+        mark = np.zeros(nc.value, dtype=np.uint8)
+        self._chk(self.L.gmg_get_marks(self.h, C.byref(nc), _p(mark, C.c_uint8) if mark.size else None, C.byref(nm)))
+        return SimpleNamespace(n_cells=nc.value, mark=mark, n_marked=nm.value)
+
+    def refine_forest_marked(self, dim, n0, level_ptr, cell_coord, cell_first_child, n_levels=None):
+        """refine_forest with the flags formed on the device from the kept marks (gmg_refine_forest_marked)"""
+        from types import SimpleNamespace
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        nl, nc, ns, ms = C.c_int(0), C.c_int64(0), C.c_int64(0), C.c_double(0)
+        self._chk(self.L.gmg_refine_forest_marked(self.h, *args, C.byref(nl), C.byref(nc), C.byref(ns), C.byref(ms)))
+        return SimpleNamespace(n_levels=nl.value, n_cells=nc.value, n_split=ns.value, build_ms=ms.value)
+
+    def energy_norm_error_resident(self, origin, h0, u, atom_xyz, atom_q, r_c, quadrature_points, weights, shape_grad, n_u=None):
+        """energy_norm_error on the resident mesh tables (gmg_energy_norm_error_resident) -> (error, cell_err2 [n_cells])."""
+        n_cells, _ = self._mesh_sizes()
+        xyz = np.ascontiguousarray(atom_xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(atom_q, dtype=np.float64)
+        qp = np.ascontiguousarray(quadrature_points, dtype=np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        sg = np.ascontiguousarray(shape_grad, dtype=np.float64).reshape(len(w), 8, 3)
+        err, ce = C.c_double(0), np.zeros(n_cells)
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        self._chk(self.L.gmg_energy_norm_error_resident(self.h, C.c_double(origin), C.c_double(h0), u.ptr, C.c_int64(u.n if n_u is None else int(n_u)),
+                                                        C.c_int64(len(q)), D(xyz), D(q), C.c_double(r_c), C.c_int(len(w)), D(qp), D(w), D(sg),
+                                                        C.byref(err), D(ce)))
+        return err.value, ce
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

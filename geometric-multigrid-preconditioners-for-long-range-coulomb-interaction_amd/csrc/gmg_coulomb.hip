@@ -176,6 +176,18 @@ struct MeshTables {
     DevPtr<int32_t> line_ptr, line_master;
     DevPtr<double> line_weight, line_inhom;
   } closed;
+  // what gmg_build_face_table_resident adds (gmg_refine.hpp): the face table of these tables' active cells, dropped with them
+  struct Faces {
+    bool valid = false;
+    DevPtr<uint8_t> kind;   // [n_cells * 2 dim]
+    DevPtr<int32_t> cell;   // [n_cells * 2 dim * 2^(dim-1)]
+  } faces;
+  // what gmg_estimate_error_resident adds (gmg_estimate.hpp): the marks of these tables' active cells, dropped with them
+  struct Marks {
+    bool valid = false;
+    int64_t n_marked = 0;
+    DevPtr<uint8_t> mark;   // [n_cells]
+  } marks;
 };
 
 // what gmg_refine_forest leaves on the device (gmg_refine.hpp): valid until the next refinement, gmg_reset or gmg_destroy
@@ -3922,37 +3934,30 @@ int gmg_gaussian_potential(gmg_context *ctx, int64_t n_atoms, const double *atom
   return GMG_OK;
 }
 
-int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_lo, const double *cell_h, const int32_t *cell_dofs,
-                          const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, int nq,
-                          const double *quadrature_points, const double *weights, const double *shape_grad, double *error,
-                          double *cell_err2) {
-  if (!ctx) return GMG_ERR_INVALID;
+// The two halves of gmg_energy_norm_error's front.  energy_error_check_args: the arguments that are not mesh arrays.
+// energy_error_device: the kernels on cell_lo, cell_h and cell_dofs that lie on the device.
+static int energy_error_check_args(gmg_context *ctx, const char *who, int64_t n_cells, const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz,
+                                   const double *atom_q, double r_c, int nq, const double *quadrature_points, const double *weights, const double *shape_grad,
+                                   bool mesh_null = false) {
   if (n_cells < 0 || n_cells >= ((int64_t)1 << 28) || n_u < 0 || !atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || nq < 1 ||
-      (n_cells > 0 && (!cell_lo || !cell_h || !cell_dofs || !u || !quadrature_points || !weights || !shape_grad)))
-    return fail(ctx, GMG_ERR_INVALID, "gmg_energy_norm_error: bad arguments");
-  if (nq > 64) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_energy_norm_error: more than 64 quadrature points per cell");
-  for (int64_t i = 0; i < 8 * n_cells; ++i)
-    if (cell_dofs[i] < 0 || cell_dofs[i] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_energy_norm_error: a DoF of a cell lies beyond the end of u");
-  if (n_cells == 0) {
-    if (error) *error = 0.0;
-    return GMG_OK;
-  }
-  (void)hipSetDevice(ctx->device);
+      (n_cells > 0 && (mesh_null || !u || !quadrature_points || !weights || !shape_grad)))
+    return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": bad arguments").c_str());
+  if (nq > 64) return fail(ctx, GMG_ERR_UNSUPPORTED, (std::string(who) + ": more than 64 quadrature points per cell").c_str());
+  return GMG_OK;
+}
+
+static int energy_error_device(gmg_context *ctx, const char *who, int64_t n_cells, const double *d_lo, const double *d_h, const int32_t *d_dofs, const double *u,
+                               int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, int nq, const double *quadrature_points,
+                               const double *weights, const double *shape_grad, double *error, double *cell_err2) {
   const std::vector<double> xq = pack_xq(n_atoms, atom_xyz, atom_q);
   const size_t nc = (size_t)n_cells;
-  DevPtr<double> xq_own, lo_own, h_own, err_own, qp_own, w_own, sg_own;
-  DevPtr<int32_t> dofs_own;
-  if (xq_own.alloc(xq.size()) != hipSuccess || lo_own.alloc(3 * nc) != hipSuccess || h_own.alloc(nc) != hipSuccess || err_own.alloc(nc) != hipSuccess ||
-      qp_own.alloc(3 * (size_t)nq) != hipSuccess || w_own.alloc((size_t)nq) != hipSuccess || sg_own.alloc(24 * (size_t)nq) != hipSuccess ||
-      dofs_own.alloc(8 * nc) != hipSuccess)
-    return fail(ctx, GMG_ERR_HIP, "gmg_energy_norm_error: out of memory");
-  double *const d_xq = xq_own.get(), *const d_lo = lo_own.get(), *const d_h = h_own.get(), *const d_err = err_own.get();
+  DevPtr<double> xq_own, err_own, qp_own, w_own, sg_own;
+  if (xq_own.alloc(xq.size()) != hipSuccess || err_own.alloc(nc) != hipSuccess || qp_own.alloc(3 * (size_t)nq) != hipSuccess ||
+      w_own.alloc((size_t)nq) != hipSuccess || sg_own.alloc(24 * (size_t)nq) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, (std::string(who) + ": out of memory").c_str());
+  double *const d_xq = xq_own.get(), *const d_err = err_own.get();
   double *const d_qp = qp_own.get(), *const d_w = w_own.get(), *const d_sg = sg_own.get();
-  int32_t *const d_dofs = dofs_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * xq.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_lo, cell_lo, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_h, cell_h, sizeof(double) * nc, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(d_dofs, cell_dofs, sizeof(int32_t) * 8 * nc, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_qp, quadrature_points, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_w, weights, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipMemcpyAsync(d_sg, shape_grad, sizeof(double) * 24 * (size_t)nq, hipMemcpyHostToDevice, ctx->stream));
@@ -3975,6 +3980,33 @@ int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_
   CHK(fetch_scalars(ctx, 1));
   if (error) *error = std::sqrt(ctx->scal_host.get()[0]);
   return GMG_OK;
+}
+
+int gmg_energy_norm_error(gmg_context *ctx, int64_t n_cells, const double *cell_lo, const double *cell_h, const int32_t *cell_dofs,
+                          const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, int nq,
+                          const double *quadrature_points, const double *weights, const double *shape_grad, double *error,
+                          double *cell_err2) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_energy_norm_error";
+  CHK(energy_error_check_args(ctx, who, n_cells, u, n_u, n_atoms, atom_xyz, atom_q, r_c, nq, quadrature_points, weights, shape_grad,
+                              !cell_lo || !cell_h || !cell_dofs));
+  for (int64_t i = 0; i < 8 * n_cells; ++i)
+    if (cell_dofs[i] < 0 || cell_dofs[i] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_energy_norm_error: a DoF of a cell lies beyond the end of u");
+  if (n_cells == 0) {
+    if (error) *error = 0.0;
+    return GMG_OK;
+  }
+  (void)hipSetDevice(ctx->device);
+  const size_t nc = (size_t)n_cells;
+  DevPtr<double> lo_own, h_own;
+  DevPtr<int32_t> dofs_own;
+  if (lo_own.alloc(3 * nc) != hipSuccess || h_own.alloc(nc) != hipSuccess || dofs_own.alloc(8 * nc) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, "gmg_energy_norm_error: out of memory");
+  HIPC(hipMemcpyAsync(lo_own.get(), cell_lo, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(h_own.get(), cell_h, sizeof(double) * nc, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dofs_own.get(), cell_dofs, sizeof(int32_t) * 8 * nc, hipMemcpyHostToDevice, ctx->stream));
+  return energy_error_device(ctx, who, n_cells, lo_own.get(), h_own.get(), dofs_own.get(), u, n_atoms, atom_xyz, atom_q, r_c, nq, quadrature_points, weights,
+                             shape_grad, error, cell_err2);
 }
 
 // assemble_system's right-hand side (src/step-50.cc:813-828) from densities that never left the device: per cell
@@ -4505,31 +4537,50 @@ float rf_elapsed(Event &e0, Event &e1) {
 
 }  // namespace
 
-int gmg_refine_forest(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
-                      const int32_t *cell_first_child, const uint8_t *flag, int *new_n_levels, int64_t *new_n_cells, int64_t *n_split, double *build_ms) {
+// Both refinement entries.  marked = false: flag [cells of all levels] is the host's; marked = true (gmg_refine_forest_marked):
+// the flags are formed on the device from the marks gmg_estimate_error_resident left in the context, by the active numbers
+// (the scan gmg_build_face_table forms).  Everything after the flags is the same code.
+static int refine_forest(gmg_context *ctx, const char *who, bool marked, int dim, const int32_t *n0, int n_levels, const int64_t *level_ptr,
+                         const int32_t *cell_coord, const int32_t *cell_first_child, const uint8_t *flag, int *new_n_levels, int64_t *new_n_cells,
+                         int64_t *n_split, double *build_ms) {
   if (!ctx) return GMG_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
-  const char *who = "gmg_refine_forest";
   auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
   if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  if (marked && !ctx->mesh.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
   std::vector<uint8_t> level_of;
   CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
   const int nv = 1 << dim;
   const int64_t n_all = level_ptr[n_levels];
-  if (n_all > 0 && !flag) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (!marked && n_all > 0 && !flag) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (marked) {
+    if (!ctx->mesh.marks.valid) return bad(GMG_ERR_INVALID, "the context holds no marks (gmg_estimate_error_resident)");
+    int64_t na = 0;
+    for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
+    if (na != ctx->mesh.n_cells) return bad(GMG_ERR_INVALID, "the forest's active cells are not as many as the marks");
+  }
   ForestDev d;
   DevPtr<uint8_t> d_flag, d_F;
-  DevPtr<int32_t> d_rank;
+  DevPtr<int32_t> d_rank, d_apos;
   Event e0, e1;
   RefinedForest out;
   int rc = GMG_OK;
-  HIPC(upload(d_flag, flag, (size_t)n_all, ctx->stream));
+  if (!marked) HIPC(upload(d_flag, flag, (size_t)n_all, ctx->stream));
   HIPC(e0.create());
   HIPC(e1.create());
   HIPC(hipEventRecord(e0.get(), ctx->stream));
   CHK(forest_to_device(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of, d, rc));
   if (rc != GMG_OK) return rc;
   const dim3 blk(kMtThreads);
+  if (marked) {  // flag[c] = the mark of c's active number (every active number is below n_cells: counted above)
+    HIPC(d_flag.alloc((size_t)std::max<int64_t>(n_all, 1)));
+    HIPC(d_apos.alloc((size_t)n_all + 1));
+    if (n_all) hipLaunchKernelGGL(mt_active_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d.fc.get(), n_all, d_apos.get());
+    hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_apos.get(), n_all);
+    if (n_all)
+      hipLaunchKernelGGL(rf_mark_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d.fc.get(), (const int32_t *)d_apos.get(),
+                         (const uint8_t *)ctx->mesh.marks.mark.get(), n_all, d_flag.get());
+  }
   // 1. the closure, from the finest level down to level 1
   HIPC(d_F.alloc((size_t)std::max<int64_t>(n_all, 1)));
   HIPC(d_rank.alloc((size_t)n_all + 1));
@@ -4586,6 +4637,18 @@ int gmg_refine_forest(gmg_context *ctx, int dim, const int32_t n0[3], int n_leve
   if (build_ms) *build_ms = rf_elapsed(e0, e1);
   ctx->refined = std::move(out);
   return GMG_OK;
+}
+
+int gmg_refine_forest(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                      const int32_t *cell_first_child, const uint8_t *flag, int *new_n_levels, int64_t *new_n_cells, int64_t *n_split, double *build_ms) {
+  return refine_forest(ctx, "gmg_refine_forest", false, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, flag, new_n_levels, new_n_cells, n_split,
+                       build_ms);
+}
+
+int gmg_refine_forest_marked(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                             const int32_t *cell_first_child, int *new_n_levels, int64_t *new_n_cells, int64_t *n_split, double *build_ms) {
+  return refine_forest(ctx, "gmg_refine_forest_marked", true, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, nullptr, new_n_levels, new_n_cells,
+                       n_split, build_ms);
 }
 
 int gmg_get_refined_forest(gmg_context *ctx, int *n_levels, int64_t *n_cells, int64_t *n_flags, int64_t *n_split, int64_t *level_ptr, int32_t *cell_coord,
@@ -4674,27 +4737,14 @@ int gmg_transfer_solution(gmg_context *ctx, int dim, const int32_t n0[3], int n_
   return GMG_OK;
 }
 
-int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
-                         const int32_t *cell_first_child, int64_t *n_active, uint8_t *face_kind, int32_t *face_cell, double *build_ms) {
-  if (!ctx) return GMG_ERR_INVALID;
-  (void)hipSetDevice(ctx->device);
-  const char *who = "gmg_build_face_table";
-  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
-  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
-  std::vector<uint8_t> level_of;
-  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+// the device half of both face-table entries: the forest's faces by kind for its na active cells, left in d_kind / d_cell
+static int face_table_device(gmg_context *ctx, const char *who, int dim, const int32_t *n0, int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                             const int32_t *cell_first_child, const std::vector<uint8_t> &level_of, int64_t na, DevPtr<uint8_t> &d_kind, DevPtr<int32_t> &d_cell,
+                             float &ms) {
   const int nv = 1 << dim, nf = 2 * dim, nfc = nv / 2;
   const int64_t n_all = level_ptr[n_levels];
-  int64_t na = 0;
-  for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
-  if (!face_kind && !face_cell) {  // the size alone
-    if (n_active) *n_active = na;
-    return GMG_OK;
-  }
-  if (na > 0 && (!face_kind || !face_cell)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
   ForestDev d;
-  DevPtr<int32_t> d_apos, d_cell;
-  DevPtr<uint8_t> d_kind;
+  DevPtr<int32_t> d_apos;
   Event e0, e1;
   int rc = GMG_OK;
   HIPC(e0.create());
@@ -4721,11 +4771,80 @@ int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_l
   CHK(rf_flagged(ctx, who, d.err, rc));
   if (rc != GMG_OK) return rc;
   CHK(launch_status(ctx));
+  ms = rf_elapsed(e0, e1);
+  return GMG_OK;
+}
+
+int gmg_build_face_table(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                         const int32_t *cell_first_child, int64_t *n_active, uint8_t *face_kind, int32_t *face_cell, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_build_face_table";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  const int nv = 1 << dim, nf = 2 * dim, nfc = nv / 2;
+  const int64_t n_all = level_ptr[n_levels];
+  int64_t na = 0;
+  for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
+  if (!face_kind && !face_cell) {  // the size alone
+    if (n_active) *n_active = na;
+    return GMG_OK;
+  }
+  if (na > 0 && (!face_kind || !face_cell)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  DevPtr<int32_t> d_cell;
+  DevPtr<uint8_t> d_kind;
+  float ms = 0.f;
+  CHK(face_table_device(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of, na, d_kind, d_cell, ms));
   HIPC(mesh_fetch(ctx, face_kind, d_kind, na * nf));
   HIPC(mesh_fetch(ctx, face_cell, d_cell, na * nf * nfc));
   HIPC(hipStreamSynchronize(ctx->stream));
   if (n_active) *n_active = na;
-  if (build_ms) *build_ms = rf_elapsed(e0, e1);
+  if (build_ms) *build_ms = ms;
+  return GMG_OK;
+}
+
+// gmg_build_face_table with the table left in the context, next to the mesh tables whose active cells it numbers (DESIGN.md
+// section 24).  The marks of an earlier estimate belong to the table they were formed with and leave with it.
+int gmg_build_face_table_resident(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                                  const int32_t *cell_first_child, int64_t *n_active, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_build_face_table_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  ctx->mesh.faces = MeshTables::Faces();  // after any failure the context holds no face table
+  ctx->mesh.marks = MeshTables::Marks();
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  if (!ctx->mesh.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  if (dim != ctx->mesh.dim) return bad(GMG_ERR_INVALID, "dim differs from the mesh tables'");
+  const int64_t n_all = level_ptr[n_levels];
+  int64_t na = 0;
+  for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
+  if (na != ctx->mesh.n_cells) return bad(GMG_ERR_INVALID, "the forest's active cells are not as many as the mesh tables' n_cells");
+  MeshTables::Faces faces;
+  float ms = 0.f;
+  CHK(face_table_device(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of, na, faces.kind, faces.cell, ms));
+  faces.valid = true;
+  ctx->mesh.faces = std::move(faces);  // (nothing after this can fail)
+  if (n_active) *n_active = na;
+  if (build_ms) *build_ms = ms;
+  return GMG_OK;
+}
+
+int gmg_get_face_table(gmg_context *ctx, int64_t *n_active, uint8_t *face_kind, int32_t *face_cell) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_face_table: not on a communicator");
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid || !m.faces.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_face_table: the context holds no face table (gmg_build_face_table_resident)");
+  (void)hipSetDevice(ctx->device);
+  const int64_t nf = 2 * m.dim, nfc = (int64_t)1 << (m.dim - 1);
+  if (n_active) *n_active = m.n_cells;
+  HIPC(mesh_fetch(ctx, face_kind, m.faces.kind, m.n_cells * nf));
+  HIPC(mesh_fetch(ctx, face_cell, m.faces.cell, m.n_cells * nf * nfc));
+  HIPC(hipStreamSynchronize(ctx->stream));
   return GMG_OK;
 }
 
@@ -5302,61 +5421,48 @@ int gmg_get_level_matrix(gmg_context *ctx, int level, int which, int64_t *n_rows
 
 // ---- error estimator and refinement marks formed on the device (gmg_estimate.hpp) ----
 
-int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level, const uint8_t *face_kind,
-                       const int32_t *face_cell, const double *h_of_level, const double *face_measure_of_level, const double *diameter_of_level,
-                       int ng, const double *gauss_x, const double *gauss_w, const double *u, int64_t n_u, int residual, int nq,
-                       const double *weight, const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq,
-                       double *residual_sq, double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked, double *build_ms) {
-  if (!ctx) return GMG_ERR_INVALID;
-  if (dim != 2 && dim != 3) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: dim must be 2 or 3");
-  if (n_cells < 0 || n_u < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: negative size");
-  if (ng < 1 || ng > kEstMaxGauss) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: ng must be in 1 .. 8");
-  if (residual < 0 || residual > 2) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: residual must be 0, 1 or 2");
-  if (residual && (nq < 1 || nq > 512)) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: nq must be in 1 .. 512");
-  if (!std::isfinite(fraction) || fraction < 0.0) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: fraction must be finite and not negative");
-  const int nv = 1 << dim, nfc = 1 << (dim - 1), nf = 2 * dim;
-  if (!gauss_x || !gauss_w || !h_of_level || !face_measure_of_level || !diameter_of_level || (residual && (!weight || !jxw_of_level)) ||
-      (n_cells > 0 && (!cell_dofs || !cell_level || !face_kind || !face_cell)) || (n_u > 0 && !u))
-    return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: an array of nonzero length is NULL");
-  if (n_cells * nf * nfc >= ((int64_t)1 << 31) || n_cells * (residual ? nq : 1) >= ((int64_t)1 << 40))
-    return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_estimate_error: more than 2^31 face entries");
+// The two halves of the estimator's front (as section 22 split the assemblies).  estimate_check_args: what both entries check of
+// the small arguments, before anything is launched.  estimate_device: the three kernels on cell and face tables that lie on the
+// device, and the downloads.  keep (may be NULL) receives the marks and their number instead of leaving them to the call.
+static int estimate_check_args(gmg_context *ctx, const char *who, int dim, int64_t n_cells, int64_t n_u, bool mesh_null, const double *h_of_level,
+                               const double *face_measure_of_level, const double *diameter_of_level, int ng, const double *gauss_x, const double *gauss_w,
+                               const double *u, int residual, int nq, const double *weight, const double *jxw_of_level, const double *dens, double fraction) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_cells < 0 || n_u < 0) return bad(GMG_ERR_INVALID, "negative size");
+  if (ng < 1 || ng > kEstMaxGauss) return bad(GMG_ERR_INVALID, "ng must be in 1 .. 8");
+  if (residual < 0 || residual > 2) return bad(GMG_ERR_INVALID, "residual must be 0, 1 or 2");
+  if (residual && (nq < 1 || nq > 512)) return bad(GMG_ERR_INVALID, "nq must be in 1 .. 512");
+  if (!std::isfinite(fraction) || fraction < 0.0) return bad(GMG_ERR_INVALID, "fraction must be finite and not negative");
+  const int nfc = 1 << (dim - 1), nf = 2 * dim;
+  if (!gauss_x || !gauss_w || !h_of_level || !face_measure_of_level || !diameter_of_level || (residual && (!weight || !jxw_of_level)) || mesh_null || (n_u > 0 && !u))
+    return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_cells * nf * nfc >= ((int64_t)1 << 31) || n_cells * (residual ? nq : 1) >= ((int64_t)1 << 40)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 face entries");
   if (residual && !dens && n_cells > 0 && (!ctx->dens_dev.get() || ctx->dens_cells != n_cells || ctx->dens_nq != nq))
-    return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: no densities of this shape on the device (gmg_charge_density(..., dens = NULL))");
-  for (int64_t c = 0; c < n_cells; ++c)
-    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: cell level of 16 or more");
-  for (int64_t s = 0; s < n_cells * nv; ++s)
-    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: DoF outside [0, n_u)");
-  for (int64_t c = 0; c < n_cells; ++c)
-    for (int f = 0; f < nf; ++f) {
-      const int64_t slot = c * nf + f;
-      const int kind = face_kind[slot], l = cell_level[c];
-      const int32_t *fc = face_cell + slot * nfc;
-      if (kind > 3) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face kind above 3");
-      const int n_idx = kind == 0 ? 0 : kind == 2 ? nfc : 1, want = kind == 1 ? l : kind == 2 ? l + 1 : l - 1;
-      for (int k = 0; k < n_idx; ++k) {
-        if (fc[k] < 0 || fc[k] >= n_cells) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face_cell index outside [0, n_cells)");
-        if ((int)cell_level[fc[k]] != want) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: the level of a face neighbour does not fit the kind of its face");
-      }
-      if (kind == 3 && (fc[1] < 0 || fc[1] >= nfc)) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: quadrant outside [0, 2^(dim-1))");
-    }
+    return bad(GMG_ERR_INVALID, "no densities of this shape on the device (gmg_charge_density(..., dens = NULL))");
+  return GMG_OK;
+}
+
+static int estimate_device(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *d_cell_dofs, const uint8_t *d_cell_level, const uint8_t *d_face_kind,
+                           const int32_t *d_face_cell, const double *h_of_level, const double *face_measure_of_level, const double *diameter_of_level, int ng,
+                           const double *gauss_x, const double *gauss_w, const double *u, int residual, int nq, const double *weight,
+                           const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq, double *residual_sq, double *face_int,
+                           double *threshold, uint8_t *mark, int64_t *n_marked, double *build_ms, MeshTables::Marks *keep) {
+  const int nv = 1 << dim, nfc = 1 << (dim - 1), nf = 2 * dim;
   if (n_cells == 0) {  // as the host: the maximum over nothing is 0
     if (threshold) *threshold = fraction * 0.0;
     if (n_marked) *n_marked = 0;
     if (build_ms) *build_ms = 0.0;
+    if (keep) { keep->n_marked = 0; keep->valid = true; }
     return GMG_OK;
   }
   (void)hipSetDevice(ctx->device);
   const size_t nc = (size_t)n_cells;
-  DevPtr<int32_t> d_cd, d_fc;
-  DevPtr<uint8_t> d_lv, d_fk, d_mark;
+  DevPtr<uint8_t> d_mark;
   DevPtr<double> d_dens, d_w, d_fi, d_k, d_r, d_thr;
   DevPtr<float> d_eta, d_part;
   DevPtr<unsigned long long> d_count;
   Event e0, e1;
-  HIPC(upload(d_cd, cell_dofs, nc * nv, ctx->stream));
-  HIPC(upload(d_lv, cell_level, nc, ctx->stream));
-  HIPC(upload(d_fk, face_kind, nc * nf, ctx->stream));
-  HIPC(upload(d_fc, face_cell, nc * nf * nfc, ctx->stream));
   if (residual) {
     HIPC(upload(d_w, weight, (size_t)nq, ctx->stream));
     if (dens) HIPC(upload(d_dens, dens, nc * (size_t)nq, ctx->stream));
@@ -5378,7 +5484,7 @@ int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t
   HIPC(d_part.alloc(g_cells));
   EstArgs a{};
   a.dim = dim; a.nv = nv; a.nfc = nfc; a.nf = nf; a.ng = ng; a.nq = residual ? nq : 0; a.residual = residual; a.n_cells = n_cells;
-  a.cell_dofs = d_cd.get(); a.cell_level = d_lv.get(); a.face_kind = d_fk.get(); a.face_cell = d_fc.get(); a.u = u;
+  a.cell_dofs = d_cell_dofs; a.cell_level = d_cell_level; a.face_kind = d_face_kind; a.face_cell = d_face_cell; a.u = u;
   a.dens = !residual ? nullptr : dens ? d_dens.get() : ctx->dens_dev.get();
   a.weight = d_w.get();
   for (int l = 0; l < 16; ++l) {
@@ -5414,7 +5520,117 @@ int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
   if (build_ms) *build_ms = ms;
+  if (keep) { keep->mark = std::move(d_mark); keep->n_marked = (int64_t)count; keep->valid = true; }  // (the caller installs them on GMG_OK alone)
   RETURN_LAUNCHED(ctx);
+}
+
+int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level, const uint8_t *face_kind,
+                       const int32_t *face_cell, const double *h_of_level, const double *face_measure_of_level, const double *diameter_of_level,
+                       int ng, const double *gauss_x, const double *gauss_w, const double *u, int64_t n_u, int residual, int nq,
+                       const double *weight, const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq,
+                       double *residual_sq, double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_estimate_error";
+  CHK(estimate_check_args(ctx, who, dim, n_cells, n_u, n_cells > 0 && (!cell_dofs || !cell_level || !face_kind || !face_cell), h_of_level, face_measure_of_level,
+                          diameter_of_level, ng, gauss_x, gauss_w, u, residual, nq, weight, jxw_of_level, dens, fraction));
+  const int nv = 1 << dim, nfc = 1 << (dim - 1), nf = 2 * dim;
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cell_level[c] > 15) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: cell level of 16 or more");
+  for (int64_t s = 0; s < n_cells * nv; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_u) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: DoF outside [0, n_u)");
+  for (int64_t c = 0; c < n_cells; ++c)
+    for (int f = 0; f < nf; ++f) {
+      const int64_t slot = c * nf + f;
+      const int kind = face_kind[slot], l = cell_level[c];
+      const int32_t *fc = face_cell + slot * nfc;
+      if (kind > 3) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face kind above 3");
+      const int n_idx = kind == 0 ? 0 : kind == 2 ? nfc : 1, want = kind == 1 ? l : kind == 2 ? l + 1 : l - 1;
+      for (int k = 0; k < n_idx; ++k) {
+        if (fc[k] < 0 || fc[k] >= n_cells) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: face_cell index outside [0, n_cells)");
+        if ((int)cell_level[fc[k]] != want) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: the level of a face neighbour does not fit the kind of its face");
+      }
+      if (kind == 3 && (fc[1] < 0 || fc[1] >= nfc)) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_error: quadrant outside [0, 2^(dim-1))");
+    }
+  DevPtr<int32_t> d_cd, d_fc;
+  DevPtr<uint8_t> d_lv, d_fk;
+  if (n_cells > 0) {
+    (void)hipSetDevice(ctx->device);
+    const size_t nc = (size_t)n_cells;
+    HIPC(upload(d_cd, cell_dofs, nc * nv, ctx->stream));
+    HIPC(upload(d_lv, cell_level, nc, ctx->stream));
+    HIPC(upload(d_fk, face_kind, nc * nf, ctx->stream));
+    HIPC(upload(d_fc, face_cell, nc * nf * nfc, ctx->stream));
+  }
+  return estimate_device(ctx, dim, n_cells, d_cd.get(), d_lv.get(), d_fk.get(), d_fc.get(), h_of_level, face_measure_of_level, diameter_of_level, ng, gauss_x,
+                         gauss_w, u, residual, nq, weight, jxw_of_level, dens, fraction, eta, kelly_sq, residual_sq, face_int, threshold, mark, n_marked,
+                         build_ms, nullptr);
+}
+
+// gmg_estimate_error on the resident tables and the kept face table; the marks stay in the context
+int gmg_estimate_error_resident(gmg_context *ctx, const double *h_of_level, const double *face_measure_of_level, const double *diameter_of_level, int ng,
+                                const double *gauss_x, const double *gauss_w, const double *u, int64_t n_u, int residual, int nq, const double *weight,
+                                const double *jxw_of_level, const double *dens, double fraction, float *eta, double *kelly_sq, double *residual_sq,
+                                double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_estimate_error_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  ctx->mesh.marks = MeshTables::Marks();  // after any failure the context holds no marks
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  MeshTables &m = ctx->mesh;
+  if (!m.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  if (!m.faces.valid) return bad(GMG_ERR_INVALID, "the context holds no face table (gmg_build_face_table_resident)");
+  if (n_u != m.n_dofs) return bad(GMG_ERR_INVALID, "n_u differs from the mesh tables' n_dofs");
+  CHK(estimate_check_args(ctx, who, m.dim, m.n_cells, n_u, false, h_of_level, face_measure_of_level, diameter_of_level, ng, gauss_x, gauss_w, u, residual, nq, weight,
+                          jxw_of_level, dens, fraction));
+  MeshTables::Marks keep;
+  CHK(estimate_device(ctx, m.dim, m.n_cells, m.cell_dofs.get(), m.cell_level.get(), m.faces.kind.get(), m.faces.cell.get(), h_of_level, face_measure_of_level,
+                      diameter_of_level, ng, gauss_x, gauss_w, u, residual, nq, weight, jxw_of_level, dens, fraction, eta, kelly_sq, residual_sq, face_int,
+                      threshold, mark, n_marked, build_ms, &keep));
+  m.marks = std::move(keep);
+  return GMG_OK;
+}
+
+int gmg_get_marks(gmg_context *ctx, int64_t *n_cells, uint8_t *mark, int64_t *n_marked) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (ctx->dist) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_get_marks: not on a communicator");
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid || !m.marks.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_marks: the context holds no marks (gmg_estimate_error_resident)");
+  (void)hipSetDevice(ctx->device);
+  if (n_cells) *n_cells = m.n_cells;
+  if (n_marked) *n_marked = m.marks.n_marked;
+  HIPC(mesh_fetch(ctx, mark, m.marks.mark, m.n_cells));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+// gmg_energy_norm_error on the resident cell_dofs and on the geometry dr_geometry_kernel forms (DESIGN.md sections 23, 24)
+int gmg_energy_norm_error_resident(gmg_context *ctx, double origin, double h0, const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz,
+                                   const double *atom_q, double r_c, int nq, const double *quadrature_points, const double *weights,
+                                   const double *shape_grad, double *error, double *cell_err2) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_energy_norm_error_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  CHK(density_resident_tables(ctx, who, h0));  // no communicator, 3D tables, h0 > 0
+  const MeshTables &m = ctx->mesh;
+  const int64_t n_cells = m.n_cells;
+  if (n_u != m.n_dofs) return bad(GMG_ERR_INVALID, "n_u differs from the mesh tables' n_dofs");
+  CHK(energy_error_check_args(ctx, who, n_cells, u, n_u, n_atoms, atom_xyz, atom_q, r_c, nq, quadrature_points, weights, shape_grad));
+  if (n_cells == 0) {
+    if (error) *error = 0.0;
+    return GMG_OK;
+  }
+  DevPtr<double> d_lo, d_h;
+  HIPC(d_lo.alloc(3 * (size_t)n_cells));
+  HIPC(d_h.alloc((size_t)n_cells));
+  DensityResArgs a{};
+  a.cell_dofs = m.cell_dofs.get(); a.cell_level = m.cell_level.get(); a.vertex_of_dof = m.vertex_of_dof.get(); a.n_cells = n_cells;
+  a.origin = origin; a.h0 = h0;
+  a.cell_lo = d_lo.get(); a.cell_h = d_h.get(); a.root_lo = nullptr;
+  hipLaunchKernelGGL(dr_geometry_kernel, asm_blocks(ctx, n_cells, kDrThreads), dim3(kDrThreads), 0, ctx->stream, a);
+  HIPC(hipGetLastError());
+  return energy_error_device(ctx, who, n_cells, d_lo.get(), d_h.get(), m.cell_dofs.get(), u, n_atoms, atom_xyz, atom_q, r_c, nq, quadrature_points, weights,
+                             shape_grad, error, cell_err2);
 }
 
 // ---- distributed ----

@@ -3,6 +3,8 @@
 //   gmg_transfer_solution SolutionTransfer::interpolate + constraints.set_zero (src/step-50.cc:1095-1121;
 //                         LaplaceProblem::refine_grid in csrc/host/adaptive.inc);
 //   gmg_build_face_table  LaplaceProblem::face_table, the input of gmg_estimate_error.
+// gmg_build_face_table_resident and gmg_refine_forest_marked run the same kernels on a face table and on
+// marks that stay in the context; rf_mark_flag_kernel forms the latter's flags.
 // The host restates p4est's refine + balance and deal.II's transfer as sequential loops over hash maps; the kernels here restate
 // those loops order-free, with the tools of gmg_mesh_tables.hpp (mt_insert / mt_find, the cell table by coordinates, the
 // one-workgroup scan, the flag word):
@@ -44,6 +46,11 @@ __device__ __forceinline__ int64_t rf_cell(const RfLevel &L, int32_t x, int32_t 
 // a flag counts only on an active cell
 __global__ __launch_bounds__(kMtThreads) void rf_flag_kernel(const int32_t *first_child, const uint8_t *flag, int64_t n_cells, uint8_t *F) {
   MT_FOR(c, n_cells) F[c] = flag[c] && first_child[c] < 0 ? 1 : 0;
+}
+// gmg_refine_forest_marked: the flags of the forest's cells from the marks of its active cells; apos is the exclusive scan of
+// mt_active_flag_kernel, so apos[c] is the active number of an active cell c (below the number of marks: the entry counts)
+__global__ __launch_bounds__(kMtThreads) void rf_mark_flag_kernel(const int32_t *first_child, const int32_t *apos, const uint8_t *mark, int64_t n_cells, uint8_t *flag) {
+  MT_FOR(c, n_cells) flag[c] = first_child[c] < 0 ? mark[apos[c]] : 0;
 }
 // one thread per (cell of the level, neighbour position): reads F on this level, writes F on the level below
 __global__ __launch_bounds__(kMtThreads) void rf_closure_kernel(MtForest f, int level, RfLevel cur, RfLevel coarse, uint8_t *F, int *err) {

@@ -185,6 +185,7 @@ void LaplaceProblem<dim>::estimate_error_host() {
   error_per_cell = estimated_error_per_cell;
   face_integrals.swap(face_int);
   estimated_on_device = false;
+  estimator_resident = marks_resident = false;  // (marks the context may still hold are not these)
   refine_flags.assign(triangulation.levels.size(), {});
   for (size_t l = 0; l < triangulation.levels.size(); ++l) refine_flags[l].assign(triangulation.levels[l].size(), 0);
   for (size_t a = 0; a < nc; ++a)
@@ -254,17 +255,19 @@ void LaplaceProblem<dim>::face_table(std::vector<uint8_t> &face_kind, std::vecto
 }
 
 template <int dim>
-typename LaplaceProblem<dim>::EstimatorInputs LaplaceProblem<dim>::estimator_inputs() {
+typename LaplaceProblem<dim>::EstimatorInputs LaplaceProblem<dim>::estimator_inputs(bool mesh_arrays) {
   EstimatorInputs in;
   const size_t nc = active_cells.size();
-  in.cell_dofs = active_cell_dof_table;
-  in.cell_level.resize(nc);
-  for (size_t a = 0; a < nc; ++a) {
-    if (active_cells[a].level > 15) throw std::runtime_error("Error estimator on device: more than 16 levels");
-    in.cell_level[a] = (uint8_t)active_cells[a].level;
+  if (mesh_arrays) {  // (otherwise the context's tables and its face table stand for them, DESIGN.md section 24)
+    in.cell_dofs = active_cell_dof_table;
+    in.cell_level.resize(nc);
+    for (size_t a = 0; a < nc; ++a) {
+      if (active_cells[a].level > 15) throw std::runtime_error("Error estimator on device: more than 16 levels");
+      in.cell_level[a] = (uint8_t)active_cells[a].level;
+    }
+    if (decide_refinement_on_device()) face_table_on_device(in.face_kind, in.face_cell);
+    else face_table(in.face_kind, in.face_cell);
   }
-  if (decide_refinement_on_device()) face_table_on_device(in.face_kind, in.face_cell);
-  else face_table(in.face_kind, in.face_cell);
   // the per-level factors exactly as the host loop forms them
   for (int l = 0; l < 16; ++l) {
     const double h = triangulation.cell_size(l);
@@ -319,12 +322,56 @@ bool LaplaceProblem<dim>::decide_estimator_on_device() {
   return false;
 }
 
+// Does this cycle's estimate read the context's mesh tables?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_estimator_resident() {
+  if (!par.estimator_from_resident_tables) return false;
+  const char *why = distributed                  ? "the run is distributed"
+                    : !operators_resident        ? "Operators from resident tables did not take effect"
+                    : !par.estimator_on_device   ? "Error estimator on device is not set"
+                    : !par.refinement_on_device  ? "Refinement on device is not set"
+                                                 : nullptr;
+  if (!why) return true;
+  if (!estimator_resident_fallback_reported) pcout(std::string("   Estimator from resident tables: not applicable (") + why + "), host arrays");
+  estimator_resident_fallback_reported = true;
+  return false;
+}
+
+// gmg_build_face_table_resident: the face table stays in the context.  STEP50_CHECK_RESIDENT=1 holds it against face_table().
+template <int dim>
+void LaplaceProblem<dim>::face_table_resident() {
+  if (ensure_context() != GMG_OK) throw std::runtime_error("Estimator from resident tables: context: " + last_error);
+  const ForestCells fc = forest_cells();
+  const size_t nc = active_cells.size();
+  int64_t n_active = 0;
+  double build_ms = 0.0;
+  sublap(nullptr);
+  if (gmg_build_face_table_resident(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), &n_active,
+                                    &build_ms) != GMG_OK)
+    throw std::logic_error(gmg_last_error(gmg));
+  if (n_active != (int64_t)nc) throw std::logic_error("Estimator from resident tables: the active cell lists differ");
+  sublap("estimate: face table on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+  const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+  if (!check || std::atoi(check) == 0) return;
+  std::vector<uint8_t> h_kind, d_kind;
+  std::vector<int32_t> h_cell, d_cell;
+  face_table(h_kind, h_cell);
+  d_kind.assign(h_kind.size(), 0);
+  d_cell.assign(h_cell.size(), 0);
+  if (gmg_get_face_table(gmg, &n_active, d_kind.data(), d_cell.data()) != GMG_OK) throw std::runtime_error(std::string("gmg_get_face_table: ") + gmg_last_error(gmg));
+  if (n_active != (int64_t)nc || d_kind != h_kind || d_cell != h_cell) throw std::logic_error("Estimator from resident tables: the device's face table differs from the host's");
+}
+
 template <int dim>
 int LaplaceProblem<dim>::estimate_error_device() {
   if (solution.size() != vertex_of_dof.size()) { last_error = "error estimator: no solution of this mesh"; return GMG_ERR_INVALID; }
   const size_t nc = active_cells.size();
+  estimator_resident = decide_estimator_resident();
+  marks_resident = false;
   sublap(nullptr);
-  const EstimatorInputs in = estimator_inputs();
+  const EstimatorInputs in = estimator_inputs(!estimator_resident);
+  if (estimator_resident) face_table_resident();
   sublap("estimate: face table, inputs");
   if (ensure_context() != GMG_OK) return GMG_ERR_HIP;
   // (the solution the device kept after gmg_distribute_constraints, "RHS from cell tables"; otherwise a copy of the host's)
@@ -339,13 +386,18 @@ int LaplaceProblem<dim>::estimate_error_device() {
   int rc = u_dev ? GMG_OK : gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
   if (!u_dev) u_dev = d_u;
   sublap("estimate: upload of u");
-  if (rc == GMG_OK)
+  if (rc == GMG_OK && estimator_resident)  // DESIGN.md section 24: the cell tables and the face table are the context's; the marks stay there too
+    rc = gmg_estimate_error_resident(gmg, in.h_of_level.data(), in.face_measure_of_level.data(), in.diameter_of_level.data(), (int)in.gauss_x.size(),
+                                     in.gauss_x.data(), in.gauss_w.data(), u_dev, (int64_t)solution.size(), in.residual, in.nq, in.weight.data(),
+                                     in.jxw_of_level.data(), in.dens_resident || in.dens.empty() ? nullptr : in.dens.data(), in.fraction, eta.data(),
+                                     kelly.data(), res.data(), fi.data(), &threshold, mark.data(), &n_marked, &build_ms);
+  else if (rc == GMG_OK)
     rc = gmg_estimate_error(gmg, dim, (int64_t)nc, in.cell_dofs.data(), in.cell_level.data(), in.face_kind.data(), in.face_cell.data(),
                             in.h_of_level.data(), in.face_measure_of_level.data(), in.diameter_of_level.data(), (int)in.gauss_x.size(),
                             in.gauss_x.data(), in.gauss_w.data(), u_dev, (int64_t)solution.size(), in.residual, in.nq, in.weight.data(),
                             in.jxw_of_level.data(), in.dens_resident || in.dens.empty() ? nullptr : in.dens.data(), in.fraction, eta.data(),
                             kelly.data(), res.data(), fi.data(), &threshold, mark.data(), &n_marked, &build_ms);
-  if (rc != GMG_OK) last_error = std::string("gmg_estimate_error: ") + gmg_last_error(gmg);
+  if (rc != GMG_OK) last_error = std::string(estimator_resident ? "gmg_estimate_error_resident: " : "gmg_estimate_error: ") + gmg_last_error(gmg);
   if (d_u) gmg_vec_free(gmg, d_u);
   if (rc != GMG_OK) return rc;
   sublap("estimate: on device");
@@ -361,6 +413,7 @@ int LaplaceProblem<dim>::estimate_error_device() {
   for (size_t l = 0; l < triangulation.levels.size(); ++l) refine_flags[l].assign(triangulation.levels[l].size(), 0);
   for (size_t a = 0; a < nc; ++a)
     if (mark[a]) refine_flags[(size_t)active_cells[a].level][(size_t)active_cells[a].index] = 1;
+  marks_resident = estimator_resident;
   sublap("estimate: marks");
   return GMG_OK;
 }
@@ -370,6 +423,7 @@ void LaplaceProblem<dim>::estimate_error_and_mark_cells() {
   if (decide_estimator_on_device()) {
     if (estimate_error_device() != GMG_OK) throw std::runtime_error(last_error);
   } else {
+    (void)decide_estimator_resident();  // (says why the key has no effect here; estimate_error_host clears the rest)
     estimate_error_host();
   }
 }
@@ -472,25 +526,56 @@ void LaplaceProblem<dim>::refine_grid_on_device(unsigned int cycle) {
   chk(ensure_context(), "context");
   sublap(nullptr);
   ForestCells fc = forest_cells();
-  std::vector<uint8_t> flag;
-  flag.reserve(fc.cell_first_child.size());
-  for (const auto &lv : refine_flags)
-    for (char f : lv) flag.push_back((uint8_t)(f != 0));
-  flag.resize(fc.cell_first_child.size(), 0);
+  // "Estimator from resident tables" (DESIGN.md section 24): the marks of the last estimate lie in the context and the flags are
+  // formed from them there.  STEP50_CHECK_RESIDENT=1: the marks come back once more, the flags are formed here as below and go
+  // through gmg_refine_forest first; the closed flags of both refinements must agree.
+  int64_t n_held = -1;
+  const bool marked = marks_resident && estimator_resident_applies() && gmg_get_marks(gmg, &n_held, nullptr, nullptr) == GMG_OK && n_held == (int64_t)active_cells.size();
+  const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+  const bool hold = marked && check && std::atoi(check) != 0;
+  std::vector<uint8_t> flag, held_closed;
+  if (hold) {
+    std::vector<uint8_t> mark(active_cells.size(), 0);
+    int64_t n_marks = 0;
+    chk(gmg_get_marks(gmg, &n_marks, mark.data(), nullptr), "gmg_get_marks");
+    if (n_marks != (int64_t)active_cells.size()) throw std::logic_error("Estimator from resident tables: the marks are not this mesh's");
+    refine_flags.assign(triangulation.levels.size(), {});
+    for (size_t l = 0; l < triangulation.levels.size(); ++l) refine_flags[l].assign(triangulation.levels[l].size(), 0);
+    for (size_t a = 0; a < active_cells.size(); ++a)
+      if (mark[a]) refine_flags[(size_t)active_cells[a].level][(size_t)active_cells[a].index] = 1;
+  }
+  if (!marked || hold) {
+    flag.reserve(fc.cell_first_child.size());
+    for (const auto &lv : refine_flags)
+      for (char f : lv) flag.push_back((uint8_t)(f != 0));
+    flag.resize(fc.cell_first_child.size(), 0);
+  }
   int L = 0;
   int64_t n_cells = 0, n_flags = 0, n_split = 0;
   double refine_ms = 0.0, transfer_ms = 0.0;
-  chk(gmg_refine_forest(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), flag.data(), &L, &n_cells,
-                        &n_split, &refine_ms),
-      "gmg_refine_forest");
+  if (!marked || hold)
+    chk(gmg_refine_forest(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), flag.data(), &L, &n_cells,
+                          &n_split, &refine_ms),
+        "gmg_refine_forest");
+  if (hold) {
+    held_closed.assign(flag.size(), 0);
+    chk(gmg_get_refined_forest(gmg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, held_closed.data()), "download");
+  }
+  if (marked)
+    chk(gmg_refine_forest_marked(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), &L, &n_cells,
+                                 &n_split, &refine_ms),
+        "gmg_refine_forest_marked");
+  marks_resident = false;
   std::vector<int32_t> parent((size_t)n_cells);
+  const size_t n_old_cells = fc.cell_first_child.size();
   fc.level_ptr.assign((size_t)L + 1, 0);
   fc.cell_coord.resize((size_t)n_cells * 3);
   fc.cell_first_child.resize((size_t)n_cells);
-  closed_refine_flags.assign(flag.size(), 0);
+  closed_refine_flags.assign(n_old_cells, 0);
   chk(gmg_get_refined_forest(gmg, nullptr, nullptr, &n_flags, nullptr, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), parent.data(),
                              closed_refine_flags.data()),
       "download");
+  if (hold && closed_refine_flags != held_closed) throw std::logic_error("Estimator from resident tables: the flags formed from the marks on the device differ from the host's");
   triangulation.install(L, fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), parent.data());
   refine_flags.clear();
   sublap("refine: forest on device");

@@ -351,6 +351,8 @@ int step50_mesh_tables_on_device(step50_problem *h) { return DISPATCH(h, mesh_on
 int step50_operators_resident(step50_problem *h) { return DISPATCH(h, operators_resident) ? 1 : 0; }
 // "Charge densities from resident tables" (DESIGN.md section 23): did the key take effect in the last setup_system?
 int step50_densities_resident(step50_problem *h) { return DISPATCH(h, densities_resident) ? 1 : 0; }
+// "Estimator from resident tables" (DESIGN.md section 24): did the key take effect in the last estimate?
+int step50_estimator_resident(step50_problem *h) { return DISPATCH(h, estimator_resident) ? 1 : 0; }
 int step50_forest_sizes(step50_problem *h, int64_t sizes[3]) {
   return guarded(h, [&] {
     const auto fc = DISPATCH(h, forest_cells());
@@ -402,6 +404,7 @@ int step50_refine_with_flags(step50_problem *h, const uint8_t *flag, int64_t n, 
         for (auto &f : P.refine_flags[l]) f = k < n ? (char)(flag[k] != 0) : 0, ++k;
       }
       if (k != n) throw std::runtime_error("step50_refine_with_flags: one flag per cell of every level");
+      P.marks_resident = false;  // (the caller's flags, not the marks the context may hold)
       P.solve_on_device_requested = on_device != 0;
       P.densities_on_device = on_device != 0 && P.par.densities_on_device;
       P.refine_grid((unsigned)P.reports.size());

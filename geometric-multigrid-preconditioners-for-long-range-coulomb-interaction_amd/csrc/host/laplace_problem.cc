@@ -265,6 +265,11 @@ void ParameterReader::declare_parameters() {
             // device instead of per-cell corner / edge / root arrays built here and uploaded; cycles in which "Mesh tables on
             // device" took effect, with "Charge densities on device" set, 3D LAMMPS input, one rank, DESIGN.md section 23
             {"Charge densities from resident tables", "false"},
+            // gmg_build_face_table_resident, gmg_estimate_error_resident, gmg_refine_forest_marked and
+            // gmg_energy_norm_error_resident: the face table, the marks and the cells of the error norm stay on the device next
+            // to the tables; cycles in which "Operators from resident tables" took effect, with "Error estimator on device" and
+            // "Refinement on device" set, one rank, DESIGN.md section 24
+            {"Estimator from resident tables", "false"},
             // gmg_refine_forest (2:1 closure of the marks and the split), gmg_transfer_solution (SolutionTransfer::interpolate
             // and constraints.set_zero) and gmg_build_face_table (the estimator's face table) instead of Forest::refine_flagged,
             // the interpolation loop of refine_grid and face_table; cycles that run on the device, one rank, DESIGN.md section 21
@@ -360,6 +365,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.mesh_tables_on_device = prm.get_bool("Mesh tables on device");
   p.operators_from_resident_tables = prm.get_bool("Operators from resident tables");
   p.densities_from_resident_tables = prm.get_bool("Charge densities from resident tables");
+  p.estimator_from_resident_tables = prm.get_bool("Estimator from resident tables");
   p.refinement_on_device = prm.get_bool("Refinement on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
@@ -2481,8 +2487,11 @@ int LaplaceProblem<dim>::energy_norm_error(bool on_device, double *error, std::v
   const Quadrature<dim> quad((int)par.degree + 1);  // QGauss(degree + 1), :1427
   const int nq = (int)quad.p.size();
   const int64_t nc = (int64_t)active_cells.size(), n = number_of_atoms;
-  std::vector<double> lo((size_t)(3 * nc)), hh((size_t)nc), qp((size_t)(3 * nq)), sg((size_t)(24 * nq), 0.0), ce((size_t)nc, 0.0);
-  for (int64_t ci = 0; ci < nc; ++ci) {
+  // ("Estimator from resident tables": the device forms the cells' corners and edges from its own tables, section 24)
+  const bool resident = on_device && lammpsinput && estimator_resident_applies();
+  const int64_t ng = resident ? 0 : nc;
+  std::vector<double> lo((size_t)(3 * ng)), hh((size_t)ng), qp((size_t)(3 * nq)), sg((size_t)(24 * nq), 0.0), ce((size_t)nc, 0.0);
+  for (int64_t ci = 0; ci < ng; ++ci) {
     const ActiveCell &ac = active_cells[(size_t)ci];
     double x0[3];
     triangulation.cell_origin(ac.level, triangulation.levels[(size_t)ac.level][(size_t)ac.index], x0);
@@ -2501,11 +2510,14 @@ int LaplaceProblem<dim>::energy_norm_error(bool on_device, double *error, std::v
     if (!u_dev) GMGC(gmg_vec_alloc(gmg, (int64_t)solution.size(), &d_u));
     int rc = u_dev ? GMG_OK : gmg_vec_upload(gmg, d_u, solution.data(), (int64_t)solution.size());
     if (!u_dev) u_dev = d_u;
-    if (rc == GMG_OK)
+    if (rc == GMG_OK && resident)
+      rc = gmg_energy_norm_error_resident(gmg, triangulation.origin, triangulation.h0, u_dev, (int64_t)solution.size(), n, atom_positions.data(),
+                                          charges.data(), par.r_c, nq, qp.data(), quad.w.data(), sg.data(), error, cell_err2 ? ce.data() : nullptr);
+    else if (rc == GMG_OK)
       rc = gmg_energy_norm_error(gmg, nc, lo.data(), hh.data(), active_cell_dof_table.data(), u_dev, (int64_t)solution.size(), n,
                                  atom_positions.data(), charges.data(), par.r_c, nq, qp.data(), quad.w.data(), sg.data(), error,
                                  cell_err2 ? ce.data() : nullptr);
-    if (rc != GMG_OK) last_error = std::string("gmg_energy_norm_error: ") + gmg_last_error(gmg);
+    if (rc != GMG_OK) last_error = std::string(resident ? "gmg_energy_norm_error_resident: " : "gmg_energy_norm_error: ") + gmg_last_error(gmg);
     if (d_u) gmg_vec_free(gmg, d_u);
     if (rc == GMG_OK && cell_err2) cell_err2->swap(ce);
     return rc;

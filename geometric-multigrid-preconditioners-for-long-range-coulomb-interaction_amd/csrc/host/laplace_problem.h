@@ -84,6 +84,7 @@ struct Parameters {
   bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
   bool operators_from_resident_tables = false;  // gmg_close_constraints and the _resident entries: operators, right-hand side and distribution read the tables gmg_build_mesh_tables left on the device
   bool densities_from_resident_tables = false;  // gmg_charge_density_resident: the densities read the cells' geometry from the tables gmg_build_mesh_tables left on the device
+  bool estimator_from_resident_tables = false;  // gmg_build_face_table_resident, gmg_estimate_error_resident, gmg_refine_forest_marked and gmg_energy_norm_error_resident: the end of the cycle reads the tables, the face table and the marks where they lie
   bool refinement_on_device = false;     // gmg_refine_forest, gmg_transfer_solution and gmg_build_face_table instead of refine_flagged, the interpolation loop of refine_grid and face_table (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
@@ -205,7 +206,16 @@ class LaplaceProblem {
     bool dens_resident = false;  // dens stays NULL: the densities gmg_charge_density left on the device
     double fraction = 0.6;       // :1084
   };
-  EstimatorInputs estimator_inputs();
+  EstimatorInputs estimator_inputs(bool mesh_arrays = true);  // (false: no cell_dofs, cell_level or face table, what the resident entry takes)
+  // "Estimator from resident tables" (DESIGN.md section 24): face table, estimate, marks and error norm on the context's tables
+  bool decide_estimator_resident();       // says so once when the key asks for it in vain
+  bool estimator_resident_applies() const {
+    return par.estimator_from_resident_tables && operators_resident && par.estimator_on_device && par.refinement_on_device && !distributed;
+  }
+  void face_table_resident();             // gmg_build_face_table_resident for the current forest
+  bool estimator_resident = false;        // the last estimate went through gmg_estimate_error_resident
+  bool marks_resident = false;            // the context holds the marks of refine_flags (until the next estimate or mesh)
+  bool estimator_resident_fallback_reported = false;
   void face_table(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) const;  // the forest's faces by kind
   void refine_grid(unsigned int cycle);                                  // :1095-1121
   // "Refinement on device" 

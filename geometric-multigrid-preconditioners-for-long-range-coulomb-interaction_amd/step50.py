@@ -90,6 +90,7 @@ def prm_text(**kw) -> str:
         "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
         "operators_from_resident_tables": ("Misc", "Operators from resident tables"),
         "densities_from_resident_tables": ("Misc", "Charge densities from resident tables"),
+        "estimator_from_resident_tables": ("Misc", "Estimator from resident tables"),
         "refinement_on_device": ("Misc", "Refinement on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
@@ -393,6 +394,11 @@ class Problem:
         """Did the last setup_system form the densities through gmg_charge_density_resident ("Charge densities from resident
         tables" took effect)?"""
         return bool(self.L.step50_densities_resident(self.h))
+
+    def estimator_resident(self) -> bool:
+        """Did the last estimate go through gmg_build_face_table_resident and gmg_estimate_error_resident ("Estimator from
+        resident tables" took effect)?"""
+        return bool(self.L.step50_estimator_resident(self.h))
 
     def refined_on_device(self) -> bool:
         """Did the last refine_grid go through gmg_refine_forest and gmg_transfer_solution ("Refinement on device")?"""

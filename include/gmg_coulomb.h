@@ -715,6 +715,58 @@ int gmg_estimate_error(gmg_context *ctx, int dim, int64_t n_cells, const int32_t
                        double *residual_sq, double *face_int, double *threshold, uint8_t *mark, int64_t *n_marked,
                        double *build_ms);
 
+/* The step that ends an adaptive cycle on the tables the last gmg_build_mesh_tables left on the device:
+ * face table, estimator and marks, the refinement from those marks, and the error norm, without a mesh array crossing the bus.
+ * What the six entries below share: GMG_ERR_UNSUPPORTED on a context with a communicator; GMG_ERR_INVALID when the context
+ * holds no mesh tables; zero cells are valid.  The face table and the marks are owned by the context INSIDE the mesh tables, as
+ * the closed lines of gmg_close_constraints are: the next gmg_build_mesh_tables, gmg_reset (unless the option
+ * reset_keeps_mesh_tables is set) and gmg_destroy drop them with the tables.
+ *
+ * gmg_build_face_table_resident -- gmg_build_face_table word for word (the same forest checks with the same codes, the same
+ * kernels, the same integers), but face_kind and face_cell are not downloaded: they stay on the device, moved into the context
+ * after the last step that can fail.  The forest must be the one the tables were built from: GMG_ERR_INVALID if dim differs
+ * from the tables' dim or the forest's number of active cells is not the tables' n_cells.  The call first drops the face table
+ * and the marks the context holds (marks belong to the table they were formed with), so the table of the last successful call
+ * is the one kept and after ANY failure the context holds no face table.  Device memory kept: 28 bytes per (cell, face) slot
+ * in 3D (1 byte of kind, 4 integers), 9 in 2D -- 168 bytes per active cell in 3D.  n_active, build_ms: may be NULL.          */
+int gmg_build_face_table_resident(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                                  const int32_t *cell_coord, const int32_t *cell_first_child, int64_t *n_active, double *build_ms);
+/* The kept face table copied out: n_active (= the tables' n_cells), face_kind [n_active * 2 dim], face_cell [n_active * 2 dim *
+ * 2^(dim-1)]; NULL arrays are skipped.  GMG_ERR_INVALID when the context holds none.                                        */
+int gmg_get_face_table(gmg_context *ctx, int64_t *n_active, uint8_t *face_kind, int32_t *face_cell);
+/* gmg_estimate_error_resident -- gmg_estimate_error applied to dim, n_cells, cell_dofs and cell_level of the resident tables and
+ * to the kept face table: the same three kernels, the same order of every sum, the same bits in every output, for any launch
+ * shape (option estimate_max_blocks).  The remaining arguments are the sibling's and are checked as the sibling checks them;
+ * the sibling's host loops over the mesh arrays are not repeated (the tables and the face table were produced by the library
+ * and are in range by construction).  Instead: GMG_ERR_INVALID without a face table, for n_u other than the tables' n_dofs,
+ * and, with residual != 0 and dens == NULL, for device densities that are missing or not n_cells x nq.
+ * New: on success the marks (uint8_t [n_cells]) and n_marked stay on the device in the context, with the lifetime of the face
+ * table, for gmg_refine_forest_marked.  They are dropped first thing in the call: after ANY failure the context holds no marks.
+ * The host outputs are the sibling's and any may be NULL.                                                                   */
+int gmg_estimate_error_resident(gmg_context *ctx, const double *h_of_level, const double *face_measure_of_level,
+                                const double *diameter_of_level, int ng, const double *gauss_x, const double *gauss_w, const double *u,
+                                int64_t n_u, int residual, int nq, const double *weight, const double *jxw_of_level, const double *dens,
+                                double fraction, float *eta, double *kelly_sq, double *residual_sq, double *face_int, double *threshold,
+                                uint8_t *mark, int64_t *n_marked, double *build_ms);
+/* The kept marks copied out: n_cells, mark [n_cells] (NULL is skipped), n_marked.  GMG_ERR_INVALID when the context holds none. */
+int gmg_get_marks(gmg_context *ctx, int64_t *n_cells, uint8_t *mark, int64_t *n_marked);
+/* gmg_refine_forest_marked -- gmg_refine_forest with flag[c] = first_child[c] < 0 ? mark[active number of c] : 0, formed on the
+ * device from the kept marks.  The active number of a cell is the number of active cells before it in (level, index) order
+ * (the scan gmg_build_face_table forms), which is how the tables number their cells.  Closure, split, parents, the result read
+ * by gmg_get_refined_forest (closed_flag included) and every refusal are the sibling's.  GMG_ERR_INVALID when the context holds
+ * no marks or the forest's number of active cells is not the marks' length.  The marks are left in place.                    */
+int gmg_refine_forest_marked(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                             const int32_t *cell_coord, const int32_t *cell_first_child, int *new_n_levels, int64_t *new_n_cells,
+                             int64_t *n_split, double *build_ms);
+/* gmg_energy_norm_error_resident -- gmg_energy_norm_error applied to n_cells and cell_dofs of the resident tables and to
+ * cell_lo / cell_h as gmg_charge_density_resident defines them from origin and h0 (the same device function, written into
+ * temporaries of the call; gmg_get_resident_cell_geometry copies the same values out): the same kernel, the same bits in error
+ * and cell_err2.  3D tables only: GMG_ERR_UNSUPPORTED for 2D tables and, as in the sibling, for nq > 64.  GMG_ERR_INVALID for
+ * h0 <= 0, for n_u other than the tables' n_dofs, and for what the sibling refuses of the remaining arguments.               */
+int gmg_energy_norm_error_resident(gmg_context *ctx, double origin, double h0, const double *u, int64_t n_u, int64_t n_atoms,
+                                   const double *atom_xyz, const double *atom_q, double r_c, int nq, const double *quadrature_points,
+                                   const double *weights, const double *shape_grad, double *error, double *cell_err2);
+
 /* ---- measurement -------------------------------------------------------------------- */
 typedef struct gmg_stats {
   int64_t coarse_solves;        /* calls of the coarse solver since the last reset           */
