@@ -36,6 +36,7 @@ SYMBOLS = [
     "gmg_estimate_error",
     "gmg_build_face_table_resident", "gmg_get_face_table", "gmg_estimate_error_resident", "gmg_get_marks", "gmg_refine_forest_marked",
     "gmg_energy_norm_error_resident",
+    "gmg_build_point_locator_resident", "gmg_get_point_locator", "gmg_atom_forces_resident", "gmg_electrostatic_energy_resident",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
@@ -900,6 +901,50 @@ class Context:
         fk, fcell = np.zeros((na.value, 2 * dim), dtype=np.uint8), np.zeros((na.value, 2 * dim, 1 << (dim - 1)), dtype=np.int32)
         self._chk(self.L.gmg_get_face_table(self.h, C.byref(na), _p(fk, C.c_uint8) if fk.size else None, _p(fcell, C.c_int32) if fcell.size else None))
         return SimpleNamespace(n_active=na.value, face_kind=fk, face_cell=fcell)
+
+    # ---- energy and forces at the atoms on the resident mesh tables
+    def build_point_locator_resident(self, dim, n0, level_ptr, cell_coord, cell_first_child, n_levels=None):
+        """The node array of set_point_locator formed on the device from the forest the tables were built from and kept in the
+        context next to them (gmg_build_point_locator_resident; get_point_locator copies it out): namespace(n_nodes, build_ms)"""
+        from types import SimpleNamespace
+        args, keep = self._forest_args(dim, n0, level_ptr, cell_coord, cell_first_child, n_levels)
+        nn, ms = C.c_int64(0), C.c_double(0)
+        self._chk(self.L.gmg_build_point_locator_resident(self.h, *args, C.byref(nn), C.byref(ms)))
+        return SimpleNamespace(n_nodes=nn.value, build_ms=ms.value)
+
+    def get_point_locator(self):
+        """The kept node array [cells of all levels] (int32)"""
+        nn = C.c_int64(0)
+        self._chk(self.L.gmg_get_point_locator(self.h, C.byref(nn), None))
+        node = np.zeros(nn.value, dtype=np.int32)
+        self._chk(self.L.gmg_get_point_locator(self.h, C.byref(nn), _p(node, C.c_int32) if node.size else None))
+        return node
+
+    def atom_forces_resident(self, origin, h0, xyz, q, u, r_c, cutoff=0.0, n_u=None):
+        """atom_forces on the resident locator and the tables' cell_dofs (gmg_atom_forces_resident): the same dict"""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        n = len(q)
+        out = dict(phi=np.zeros(n), field=np.zeros((n, 3)), force=np.zeros((n, 3)), force_short=np.zeros((n, 3)), e_short=np.zeros(n))
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        self._chk(self.L.gmg_atom_forces_resident(self.h, C.c_double(origin), C.c_double(h0), C.c_int64(n), D(xyz), D(q), u.ptr if u is not None else None,
+                                                  C.c_int64(int((u.n if u is not None else 0) if n_u is None else n_u)), C.c_double(r_c), C.c_double(cutoff),
+                                                  D(out["phi"]), D(out["field"]), D(out["force"]), D(out["force_short"]), D(out["e_short"])))
+        return out
+
+    def electrostatic_energy_resident(self, origin, h0, xyz, q, u, r_c, cutoff=0.0, n_u=None):
+        """The three ascending sums of the electrostatic energy formed on the device (gmg_electrostatic_energy_resident):
+        namespace(short, fe_long, self_energy, build_ms)"""
+        from types import SimpleNamespace
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        D = lambda a: _p(a, C.c_double) if a.size else None
+        out, ms = np.zeros(3), C.c_double(0)
+        self._chk(self.L.gmg_electrostatic_energy_resident(self.h, C.c_double(origin), C.c_double(h0), C.c_int64(len(q)), D(xyz), D(q),
+                                                           u.ptr if u is not None else None,
+                                                           C.c_int64(int((u.n if u is not None else 0) if n_u is None else n_u)), C.c_double(r_c),
+                                                           C.c_double(cutoff), _p(out, C.c_double), C.byref(ms)))
+        return SimpleNamespace(short=out[0], fe_long=out[1], self_energy=out[2], build_ms=ms.value)
 
     def estimate_error_resident(self, h_of_level, face_measure_of_level, diameter_of_level, gauss_x, gauss_w, u, residual=0, weight=None,
                                 jxw_of_level=None, dens=None, fraction=0.6, n_u=None, dim=None):

@@ -188,6 +188,14 @@ struct MeshTables {
     int64_t n_marked = 0;
     DevPtr<uint8_t> mark;   // [n_cells]
   } marks;
+  // what gmg_build_point_locator_resident adds (gmg_forces.hpp): the forest flattened for locate(); the cells' DoFs are
+  // cell_dofs above, so 4 bytes per forest cell are all it keeps.  Dropped with the tables.
+  struct PointLocator {
+    bool valid = false;
+    int64_t n_nodes = 0;
+    int32_t n0[3] = {0, 0, 0};
+    DevPtr<int32_t> node;   // [n_nodes]
+  } locator;
 };
 
 // what gmg_refine_forest leaves on the device (gmg_refine.hpp): valid until the next refinement, gmg_reset or gmg_destroy
@@ -3830,13 +3838,17 @@ int gmg_set_point_locator(gmg_context *ctx, const int32_t n0[3], const double or
   return GMG_OK;
 }
 
-int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u, int64_t n_u,
-                    double r_c, double cutoff, double *phi, double *field, double *force, double *force_short, double *e_short) {
-  if (!ctx) return GMG_ERR_INVALID;
-  if (!atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || !(cutoff >= 0.0)) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: bad arguments");
-  if (ctx->loc_max_dof < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: call gmg_set_point_locator first");
-  if (!u || n_u <= ctx->loc_max_dof) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: u is shorter than the locator's DoFs");
-  if (n_atoms == 0) return GMG_OK;
+// The two halves of gmg_atom_forces' front.  atom_forces_check_args: the arguments that are not the locator.
+// atom_forces_device: the kernels on a locator whose arrays lie on the device (located == false: a mesh without cells, phi and
+// the field are 0).
+static int atom_forces_check_args(gmg_context *ctx, const char *who, int64_t n_atoms, const double *atom_xyz, const double *atom_q, double r_c, double cutoff) {
+  if (!atoms_ok(n_atoms, atom_xyz, atom_q) || !(r_c > 0.0) || !(cutoff >= 0.0)) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": bad arguments").c_str());
+  return GMG_OK;
+}
+
+static int atom_forces_device(gmg_context *ctx, const char *who, const gmg_forces::Locator &L, bool located, int64_t n_atoms, const double *atom_xyz,
+                              const double *atom_q, const double *u, double r_c, double cutoff, double *phi, double *field, double *force, double *force_short,
+                              double *e_short) {
   (void)hipSetDevice(ctx->device);
   const int64_t n = n_atoms;
   const bool want_field = phi || field || force, want_pairs = force || force_short || e_short;
@@ -3844,13 +3856,17 @@ int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, c
   DevPtr<double> xq_own, phi_own, E_own, pair_own;
   if (xq_own.alloc((size_t)n * 4) != hipSuccess || phi_own.alloc((size_t)n) != hipSuccess || E_own.alloc((size_t)n * 3) != hipSuccess ||
       pair_own.alloc((size_t)n * 4) != hipSuccess)
-    return fail(ctx, GMG_ERR_HIP, "gmg_atom_forces: out of memory");
+    return fail(ctx, GMG_ERR_HIP, (std::string(who) + ": out of memory").c_str());
   double *const d_xq = xq_own.get(), *const d_phi = phi_own.get(), *const d_E = E_own.get(), *const d_pair = pair_own.get();
   HIPC(hipMemcpyAsync(d_xq, xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   const int bs = ctx->force_block;
-  if (want_field)
-    hipLaunchKernelGGL(gmg_forces::atom_field_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, ctx->stream, ctx->loc, u, d_xq, (int)n,
+  if (want_field && located)
+    hipLaunchKernelGGL(gmg_forces::atom_field_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, ctx->stream, L, u, d_xq, (int)n,
                        d_phi, d_E);
+  if (want_field && !located) {
+    HIPC(hipMemsetAsync(d_phi, 0, sizeof(double) * (size_t)n, ctx->stream));
+    HIPC(hipMemsetAsync(d_E, 0, sizeof(double) * 3 * (size_t)n, ctx->stream));
+  }
   if (want_pairs) CHK(launch_pairs(ctx, gmg_forces::ShortLaw::make(r_c), cutoff > 0.0 ? cutoff * r_c : INFINITY, n, atom_xyz,
                                    xq.data(), d_xq, d_pair));
   HIPC(hipGetLastError());
@@ -3867,6 +3883,156 @@ int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, c
     }
     if (e_short) e_short[i] = pair[(size_t)(4 * i + 3)];
   }
+  return GMG_OK;
+}
+
+int gmg_atom_forces(gmg_context *ctx, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u, int64_t n_u,
+                    double r_c, double cutoff, double *phi, double *field, double *force, double *force_short, double *e_short) {
+  if (!ctx) return GMG_ERR_INVALID;
+  CHK(atom_forces_check_args(ctx, "gmg_atom_forces", n_atoms, atom_xyz, atom_q, r_c, cutoff));
+  if (ctx->loc_max_dof < 0) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: call gmg_set_point_locator first");
+  if (!u || n_u <= ctx->loc_max_dof) return fail(ctx, GMG_ERR_INVALID, "gmg_atom_forces: u is shorter than the locator's DoFs");
+  if (n_atoms == 0) return GMG_OK;
+  return atom_forces_device(ctx, "gmg_atom_forces", ctx->loc, true, n_atoms, atom_xyz, atom_q, u, r_c, cutoff, phi, field, force, force_short, e_short);
+}
+
+// ---- energy and forces at the atoms from the resident mesh tables
+
+// what the entries on the resident locator check first: no communicator, tables, 3D
+static int locator_resident_tables(gmg_context *ctx, const char *who) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  if (!ctx->mesh.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  if (ctx->mesh.dim != 3) return bad(GMG_ERR_UNSUPPORTED, "the mesh tables are not 3D");
+  return GMG_OK;
+}
+
+// the resident locator as locate() takes it, after the checks both consumers share
+static int resident_locator(gmg_context *ctx, const char *who, double origin, double h0, const double *u, int64_t n_u, gmg_forces::Locator &L) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  CHK(locator_resident_tables(ctx, who));
+  const MeshTables &m = ctx->mesh;
+  if (!m.locator.valid) return bad(GMG_ERR_INVALID, "the context holds no point locator (gmg_build_point_locator_resident)");
+  if (!(h0 > 0.0)) return bad(GMG_ERR_INVALID, "h0 must be positive");
+  if (n_u != m.n_dofs || (n_u > 0 && !u)) return bad(GMG_ERR_INVALID, "u does not have the mesh tables' n_dofs entries");
+  L = gmg_forces::Locator{{m.locator.n0[0], m.locator.n0[1], m.locator.n0[2]}, {origin, origin, origin}, h0, m.locator.node.get(), m.cell_dofs.get()};
+  return GMG_OK;
+}
+
+int gmg_build_point_locator_resident(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr, const int32_t *cell_coord,
+                                     const int32_t *cell_first_child, int64_t *n_nodes, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const char *who = "gmg_build_point_locator_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  ctx->mesh.locator = MeshTables::PointLocator();  // after any failure the context holds no resident locator
+  if (build_ms) *build_ms = 0.0;
+  CHK(locator_resident_tables(ctx, who));
+  std::vector<uint8_t> level_of;
+  CHK(check_forest(ctx, who, dim, n0, n_levels, level_ptr, cell_coord, cell_first_child, level_of));
+  if (dim != ctx->mesh.dim) return bad(GMG_ERR_INVALID, "dim differs from the mesh tables'");
+  const int64_t n_all = level_ptr[n_levels];
+  int64_t na = 0;
+  for (int64_t c = 0; c < n_all; ++c) na += cell_first_child[c] < 0;
+  if (na != ctx->mesh.n_cells) return bad(GMG_ERR_INVALID, "the forest's active cells are not as many as the mesh tables' n_cells");
+  if (n_all > 0) {  // locate() indexes the roots by coordinate: level 0 must be the full lattice, x fastest
+    if (level_ptr[1] != (int64_t)n0[0] * n0[1] * n0[2]) return bad(GMG_ERR_INVALID, "level 0 is not the full lattice");
+    for (int64_t c = 0; c < level_ptr[1]; ++c)
+      if (cell_coord[3 * c] != c % n0[0] || cell_coord[3 * c + 1] != (c / n0[0]) % n0[1] || cell_coord[3 * c + 2] != c / ((int64_t)n0[0] * n0[1]))
+        return bad(GMG_ERR_INVALID, "level 0 is not in lexicographic cell order");
+  }
+  MeshTables::PointLocator loc;
+  loc.n_nodes = n_all;
+  for (int d = 0; d < 3; ++d) loc.n0[d] = n0[d];
+  DevPtr<int32_t> d_fc, d_apos;  // the scratch lives until the stream has run the kernels
+  Event e0, e1;
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  HIPC(upload(d_fc, cell_first_child, (size_t)n_all, ctx->stream));
+  HIPC(d_apos.alloc((size_t)n_all + 1));
+  HIPC(loc.node.alloc((size_t)std::max<int64_t>(n_all, 1)));
+  gmg_forces::LocLevels lv{};
+  lv.n_levels = n_levels;
+  for (int l = 0; l < 14; ++l) lv.ptr[l] = level_ptr[std::min(l, n_levels)];
+  const dim3 blk(kMtThreads);
+  if (n_all) hipLaunchKernelGGL(mt_active_flag_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d_fc.get(), n_all, d_apos.get());
+  hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_apos.get(), n_all);
+  if (n_all)
+    hipLaunchKernelGGL(gmg_forces::loc_node_kernel, asm_blocks(ctx, n_all, kMtThreads), blk, 0, ctx->stream, (const int32_t *)d_fc.get(), (const int32_t *)d_apos.get(), lv,
+                       n_all, loc.node.get());
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  CHK(launch_status(ctx));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  loc.valid = true;
+  ctx->mesh.locator = std::move(loc);  // (nothing after this can fail)
+  if (n_nodes) *n_nodes = n_all;
+  if (build_ms) *build_ms = ms;
+  return GMG_OK;
+}
+
+int gmg_get_point_locator(gmg_context *ctx, int64_t *n_nodes, int32_t *node) {
+  if (!ctx) return GMG_ERR_INVALID;
+  CHK(locator_resident_tables(ctx, "gmg_get_point_locator"));
+  const MeshTables &m = ctx->mesh;
+  if (!m.locator.valid) return fail(ctx, GMG_ERR_INVALID, "gmg_get_point_locator: the context holds no point locator (gmg_build_point_locator_resident)");
+  (void)hipSetDevice(ctx->device);
+  if (n_nodes) *n_nodes = m.locator.n_nodes;
+  HIPC(mesh_fetch(ctx, node, m.locator.node, m.locator.n_nodes));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+int gmg_atom_forces_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u,
+                             int64_t n_u, double r_c, double cutoff, double *phi, double *field, double *force, double *force_short, double *e_short) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_atom_forces_resident";
+  gmg_forces::Locator L{};
+  CHK(resident_locator(ctx, who, origin, h0, u, n_u, L));
+  CHK(atom_forces_check_args(ctx, who, n_atoms, atom_xyz, atom_q, r_c, cutoff));
+  if (n_atoms == 0) return GMG_OK;
+  return atom_forces_device(ctx, who, L, ctx->mesh.n_cells > 0, n_atoms, atom_xyz, atom_q, u, r_c, cutoff, phi, field, force, force_short, e_short);
+}
+
+int gmg_electrostatic_energy_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz, const double *atom_q, const double *u,
+                                      int64_t n_u, double r_c, double cutoff, double out[3], double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_electrostatic_energy_resident";
+  if (build_ms) *build_ms = 0.0;
+  gmg_forces::Locator L{};
+  CHK(resident_locator(ctx, who, origin, h0, u, n_u, L));
+  CHK(atom_forces_check_args(ctx, who, n_atoms, atom_xyz, atom_q, r_c, cutoff));
+  if (!out) return fail(ctx, GMG_ERR_INVALID, (std::string(who) + ": out is NULL").c_str());
+  out[0] = out[1] = out[2] = 0.0;
+  if (n_atoms == 0) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  const int64_t n = n_atoms;
+  const std::vector<double> xq = pack_xq(n, atom_xyz, atom_q);
+  DevPtr<double> d_xq, d_pair, d_fe, d_self, d_out;
+  Event e0, e1;
+  if (d_xq.alloc((size_t)n * 4) != hipSuccess || d_pair.alloc((size_t)n * 4) != hipSuccess || d_fe.alloc((size_t)n) != hipSuccess ||
+      d_self.alloc((size_t)n) != hipSuccess || d_out.alloc(3) != hipSuccess)
+    return fail(ctx, GMG_ERR_HIP, (std::string(who) + ": out of memory").c_str());
+  HIPC(e0.create());
+  HIPC(e1.create());
+  HIPC(hipMemcpyAsync(d_xq.get(), xq.data(), sizeof(double) * 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipEventRecord(e0.get(), ctx->stream));
+  const int bs = ctx->force_block;
+  hipLaunchKernelGGL(gmg_forces::atom_energy_terms_kernel, dim3((unsigned)((n + bs - 1) / bs)), dim3(bs), 0, ctx->stream, L, ctx->mesh.n_cells > 0 ? 1 : 0, u,
+                     (const double *)d_xq.get(), (int)n, std::sqrt(M_PI) * r_c, d_fe.get(), d_self.get());
+  CHK(launch_pairs(ctx, gmg_forces::ShortLaw::make(r_c), cutoff > 0.0 ? cutoff * r_c : INFINITY, n, atom_xyz, xq.data(), d_xq.get(), d_pair.get()));
+  gmg_forces::EnergySumArgs a{{d_pair.get() + 3, d_fe.get(), d_self.get()}, {4, 1, 1}, (int)n, d_out.get()};
+  hipLaunchKernelGGL(gmg_forces::energy_sum_kernel, dim3(3), dim3(256), 0, ctx->stream, a);
+  HIPC(hipGetLastError());
+  HIPC(hipEventRecord(e1.get(), ctx->stream));
+  HIPC(hipMemcpyAsync(out, d_out.get(), sizeof(double) * 3, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
+  if (build_ms) *build_ms = ms;
   return GMG_OK;
 }
 

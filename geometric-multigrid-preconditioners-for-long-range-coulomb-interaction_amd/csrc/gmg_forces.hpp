@@ -118,6 +118,24 @@ GMG_FHD inline void atom_field(const Locator &L, const double *u, const double x
   phi = v;
 }
 
+// phi_h(x) alone: the cell of octant 7 with clamp and the trilinear sum, in fe_value_at's operation order -- one descent per atom,
+// where atom_field makes nine (the electrostatic energy needs no field: gmg_electrostatic_energy_resident)
+GMG_FHD inline double atom_phi(const Locator &L, const double *u, const double x[3]) {
+  int32_t cell;
+  int c[3], level;
+  locate(L, x, 7, true, cell, c, level);
+  const double h = L.h0 / double(1 << level);
+  double t[3];
+  for (int d = 0; d < 3; ++d) t[d] = (x[d] - (L.origin[d] + h * c[d])) / h;
+  double v = 0.0;
+  for (int a = 0; a < 8; ++a) {
+    double w = 1.0;
+    for (int d = 0; d < 3; ++d) w *= ((a >> d) & 1) ? t[d] : 1.0 - t[d];
+    v += w * u[L.active_dofs[8 * (int64_t)cell + a]];
+  }
+  return v;
+}
+
 // pair laws: scalar force f (F_i += f (x_i - x_j)) and energy e of one pair at distance r, r2 = r * r as summed
 struct ShortLaw {  // erfc(r / r_c) / r and its derivative
   double r_c, c2, rc2;  // c2 = 2 / (sqrt(pi) r_c), rc2 = r_c^2
@@ -218,6 +236,66 @@ __global__ __launch_bounds__(256) void atom_field_kernel(Locator L, const double
   atom_field(L, u, x, p, e);
   phi[i] = p;
   for (int d = 0; d < 3; ++d) E[3 * (int64_t)i + d] = e[d];
+}
+
+// ---- the resident point locator (gmg_build_point_locator_resident): the forest's first_child array turned into Locator::node.
+// level_ptr by value: at most 13 levels, so the level of a cell is a search over constants held in scalar registers.
+struct LocLevels {
+  int n_levels;
+  int64_t ptr[14];  // ptr[l] .. ptr[l + 1]: the cells of level l; entries past n_levels repeat the last one
+};
+// one thread per forest cell k (grid-stride): node[k] = ptr[level + 1] + first_child[k] for a refined cell, -(active number) - 1
+// for an active one; apos[k]: the exclusive count of active cells before k (mt_active_flag_kernel scanned)
+__global__ __launch_bounds__(256) void loc_node_kernel(const int32_t *first_child, const int32_t *apos, LocLevels lv, int64_t n_all, int32_t *node) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_all; k += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t fc = first_child[k];
+    if (fc < 0) {
+      node[k] = -apos[k] - 1;
+      continue;
+    }
+    int64_t next = lv.ptr[1];  // the start of the level after k's: the last l < n_levels with ptr[l] <= k is k's level
+#pragma unroll
+    for (int l = 1; l < 13; ++l)
+      if (l < lv.n_levels && lv.ptr[l] <= k) next = lv.ptr[l + 1];
+    node[k] = (int32_t)(next + fc);
+  }
+}
+
+// the per-atom terms of the electrostatic energy, one lane per atom: fe[i] = (0.5 q_i) phi_h(x_i) (phi = 0 where the mesh has
+// no cell: located == 0), self[i] = q_i q_i / self_denom with self_denom = sqrt(pi) r_c formed by the caller
+__global__ __launch_bounds__(256) void atom_energy_terms_kernel(Locator L, int located, const double *u, const double *xq, int n, double self_denom,
+                                                                double *fe, double *self) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x[3] = {xq[4 * (int64_t)i], xq[4 * (int64_t)i + 1], xq[4 * (int64_t)i + 2]};
+  const double q = xq[4 * (int64_t)i + 3];
+  const double phi = located ? atom_phi(L, u, x) : 0.0;
+  fe[i] = (0.5 * q) * phi;
+  self[i] = q * q / self_denom;
+}
+
+// out[b] = src_b[0] + src_b[stride_b] + ... in ascending index, one sequential fp64 sum per workgroup b = 0, 1, 2: the
+// workgroup stages a tile of blockDim.x values in LDS, lane 0 adds them in order.  The bits are those of a host loop over i.
+struct EnergySumArgs {
+  const double *src[3];
+  int stride[3];
+  int n;
+  double *out;  // [3]
+};
+__global__ __launch_bounds__(256) void energy_sum_kernel(EnergySumArgs a) {
+  __shared__ double tile[256];
+  const double *src = blockIdx.x == 0 ? a.src[0] : blockIdx.x == 1 ? a.src[1] : a.src[2];
+  const int stride = blockIdx.x == 0 ? a.stride[0] : blockIdx.x == 1 ? a.stride[1] : a.stride[2];
+  double sum = 0.0;
+  for (int t0 = 0; t0 < a.n; t0 += blockDim.x) {
+    const int m = min((int)blockDim.x, a.n - t0);
+    __syncthreads();
+    if ((int)threadIdx.x < m) tile[threadIdx.x] = src[(int64_t)stride * (t0 + threadIdx.x)];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int j = 0; j < m; ++j) sum += tile[j];
+  }
+  if (threadIdx.x == 0) a.out[blockIdx.x] = sum;
 }
 
 // stage slots [t0, t0 + m) of xq in LDS (m <= blockDim.x); every lane then reads the same word: broadcast, no bank conflict

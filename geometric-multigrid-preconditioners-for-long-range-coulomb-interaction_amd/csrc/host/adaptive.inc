@@ -337,6 +337,47 @@ bool LaplaceProblem<dim>::decide_estimator_resident() {
   return false;
 }
 
+// Do this cycle's energy and forces read the context's mesh tables?  Says so once when the key asks for it in vain.
+template <int dim>
+bool LaplaceProblem<dim>::decide_energy_forces_resident() {
+  if (!par.energy_forces_from_resident_tables) return false;
+  const char *why = distributed                    ? "the run is distributed"
+                    : !operators_resident          ? "Operators from resident tables did not take effect"
+                    : device_solution() == nullptr ? "the solution is not on the device"
+                    : (dim != 3 || !lammpsinput)   ? "not a 3D problem with LAMMPS input"
+                                                   : nullptr;
+  if (!why) return true;
+  if (!energy_forces_fallback_reported) pcout(std::string("   Energy and forces from resident tables: not applicable (") + why + "), host arrays");
+  energy_forces_fallback_reported = true;
+  return false;
+}
+
+// gmg_build_point_locator_resident, once per mesh: the context drops the locator with the tables it belongs to, so a kept one
+// with this forest's number of cells is this mesh's.  STEP50_CHECK_RESIDENT=1 holds it against point_locator().
+template <int dim>
+void LaplaceProblem<dim>::ensure_point_locator_resident() {
+  if (ensure_context() != GMG_OK) throw std::runtime_error("Energy and forces from resident tables: context: " + last_error);
+  int64_t n_all = 0, n_nodes = -1;
+  for (const auto &lv : triangulation.levels) n_all += (int64_t)lv.size();
+  if (gmg_get_point_locator(gmg, &n_nodes, nullptr) == GMG_OK && n_nodes == n_all) return;
+  const ForestCells fc = forest_cells();
+  double build_ms = 0.0;
+  sublap(nullptr);
+  if (gmg_build_point_locator_resident(gmg, dim, fc.n0, triangulation.n_levels(), fc.level_ptr.data(), fc.cell_coord.data(), fc.cell_first_child.data(), &n_nodes,
+                                       &build_ms) != GMG_OK)
+    throw std::logic_error(gmg_last_error(gmg));
+  sublap("point locator on device");
+  if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+  const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+  if (!check || std::atoi(check) == 0) return;
+  std::vector<int32_t> h_node, d_node;
+  point_locator(h_node);
+  d_node.assign(h_node.size(), 0);
+  if (n_nodes != (int64_t)h_node.size()) throw std::logic_error("Energy and forces from resident tables: the forests differ in size");
+  if (gmg_get_point_locator(gmg, &n_nodes, d_node.data()) != GMG_OK) throw std::runtime_error(std::string("gmg_get_point_locator: ") + gmg_last_error(gmg));
+  if (d_node != h_node) throw std::logic_error("Energy and forces from resident tables: the device's point locator differs from the host's");
+}
+
 // gmg_build_face_table_resident: the face table stays in the context.  STEP50_CHECK_RESIDENT=1 holds it against face_table().
 template <int dim>
 void LaplaceProblem<dim>::face_table_resident() {

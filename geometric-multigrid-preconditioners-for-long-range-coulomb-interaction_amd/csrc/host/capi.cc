@@ -353,6 +353,27 @@ int step50_operators_resident(step50_problem *h) { return DISPATCH(h, operators_
 int step50_densities_resident(step50_problem *h) { return DISPATCH(h, densities_resident) ? 1 : 0; }
 // "Estimator from resident tables" (DESIGN.md section 24): did the key take effect in the last estimate?
 int step50_estimator_resident(step50_problem *h) { return DISPATCH(h, estimator_resident) ? 1 : 0; }
+// "Energy and forces from resident tables" (DESIGN.md section 25): did the key take effect in the last finish_cycle?
+int step50_energy_forces_resident(step50_problem *h) { return DISPATCH(h, energy_forces_resident) ? 1 : 0; }
+// postprocess_electrostatic_energy() of the current solution once more: the path the cycle took (its six lines are appended to the
+// log, the energies of the last report are overwritten with the same values)
+int step50_electrostatic_energy(step50_problem *h) {
+  return guarded(h, [&] {
+    auto run = [&](auto &P) {
+      if (P.reports.empty() || !P.lammpsinput) throw std::runtime_error("step50_electrostatic_energy: no cycle with atoms has run");
+      P.postprocess_electrostatic_energy();
+    };
+    if (h->dim == 2) run(*h->p2); else run(*h->p3);
+    return 0;
+  });
+}
+// the host's point_locator() of the current forest: returns its length (cells of all levels), node may be null
+int64_t step50_point_locator(step50_problem *h, int32_t *node) {
+  std::vector<int32_t> v;
+  DISPATCH(h, point_locator(v));
+  if (node && !v.empty()) std::memcpy(node, v.data(), sizeof(int32_t) * v.size());
+  return (int64_t)v.size();
+}
 int step50_forest_sizes(step50_problem *h, int64_t sizes[3]) {
   return guarded(h, [&] {
     const auto fc = DISPATCH(h, forest_cells());
@@ -520,6 +541,8 @@ int step50_estimate(step50_problem *h, int where) {
 }
 int step50_estimated_on_device(step50_problem *h) { return DISPATCH(h, estimated_on_device) ? 1 : 0; }
 int64_t step50_host_density_copies(step50_problem *h) { return DISPATCH(h, host_density_copies); }
+// how often ensure_dof_maps() built the vertex -> DoF hash tables ("Mesh tables on device" leaves them to their first use)
+int64_t step50_dof_map_builds(step50_problem *h) { return DISPATCH(h, dof_map_builds); }
 int step50_error_per_cell(step50_problem *h, float *eta) {
   const auto &e = DISPATCH(h, error_per_cell);
   if (!e.empty()) std::memcpy(eta, e.data(), sizeof(float) * e.size());

@@ -270,6 +270,11 @@ void ParameterReader::declare_parameters() {
             // to the tables; cycles in which "Operators from resident tables" took effect, with "Error estimator on device" and
             // "Refinement on device" set, one rank, DESIGN.md section 24
             {"Estimator from resident tables", "false"},
+            // gmg_build_point_locator_resident, gmg_electrostatic_energy_resident and gmg_atom_forces_resident: the point
+            // locator is formed on the device next to the tables, the energy's three sums and the forces at the atoms read
+            // cell_dofs and the solution there; cycles in which "Operators from resident tables" took effect with the solution
+            // on the device ("RHS from cell tables"), 3D LAMMPS input, one rank, DESIGN.md section 25
+            {"Energy and forces from resident tables", "false"},
             // gmg_refine_forest (2:1 closure of the marks and the split), gmg_transfer_solution (SolutionTransfer::interpolate
             // and constraints.set_zero) and gmg_build_face_table (the estimator's face table) instead of Forest::refine_flagged,
             // the interpolation loop of refine_grid and face_table; cycles that run on the device, one rank, DESIGN.md section 21
@@ -366,6 +371,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.operators_from_resident_tables = prm.get_bool("Operators from resident tables");
   p.densities_from_resident_tables = prm.get_bool("Charge densities from resident tables");
   p.estimator_from_resident_tables = prm.get_bool("Estimator from resident tables");
+  p.energy_forces_from_resident_tables = prm.get_bool("Energy and forces from resident tables");
   p.refinement_on_device = prm.get_bool("Refinement on device");
   p.short_range_cutoff = prm.get_double("Short-range cutoff in smoothing lengths");
   p.energy_for_large_systems = prm.get_bool("Energy for large systems");
@@ -792,6 +798,7 @@ void LaplaceProblem<dim>::distribute_dofs_on_device() {
 template <int dim>
 void LaplaceProblem<dim>::ensure_dof_maps() {
   if (dof_maps_ready) return;
+  ++dof_map_builds;
   const int L = triangulation.n_levels();
   const int lattice[3] = {triangulation.n0 + 1, triangulation.n0 + 1, dim == 3 ? triangulation.n0 + 1 : 1};
   const int none[3] = {0, 0, 0};
@@ -2255,6 +2262,8 @@ void LaplaceProblem<dim>::postprocess_electrostatic_energy() {
   double analytical = 0, shortr = 0, fe = 0, self = 0;
   const bool large = number_of_atoms >= 300;  // the reference's gate (:1554): the all-pairs sums are O(N^2)
   const double rcut = par.short_range_cutoff * par.r_c;
+  // "Energy and forces from resident tables" (DESIGN.md section 25): the three sums come back from the device, 24 bytes
+  const bool resident = energy_forces_resident_applies() && gmg != nullptr;
   if (!large)
     for (unsigned i = 0; i < number_of_atoms; ++i)
       for (unsigned j = i + 1; j < number_of_atoms; ++j) {
@@ -2262,7 +2271,31 @@ void LaplaceProblem<dim>::postprocess_electrostatic_energy() {
         for (int d = 0; d < 3; ++d) { const double t = atom_positions[3 * i + (size_t)d] - atom_positions[3 * j + (size_t)d]; r2 += t * t; }
         analytical += charges[i] * charges[j] / std::sqrt(r2);
       }
-  if (rcut <= 0.0) {  // the reference's loop (:1325-1332)
+  if (resident) {
+    ensure_point_locator_resident();
+    double sums[3] = {0, 0, 0}, build_ms = 0.0;
+    sublap(nullptr);
+    if (gmg_electrostatic_energy_resident(gmg, triangulation.origin, triangulation.h0, (int64_t)number_of_atoms, atom_positions.data(), charges.data(),
+                                          device_solution(), (int64_t)solution.size(), par.r_c, std::max(par.short_range_cutoff, 0.0), sums, &build_ms) != GMG_OK)
+      throw std::runtime_error(std::string("gmg_electrostatic_energy_resident: ") + gmg_last_error(gmg));
+    sublap("energy: sums on device");
+    if (sublap_on()) std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", build_ms);
+    shortr = sums[0]; fe = sums[1]; self = sums[2];
+    const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+    if (check && std::atoi(check) != 0) {  // fe and self by the host's loops (phi_h through the host mirror of atom_phi: no hash tables)
+      std::vector<int32_t> node;
+      point_locator(node);
+      const gmg_forces::Locator L{{triangulation.n0, triangulation.n0, triangulation.n0}, {triangulation.origin, triangulation.origin, triangulation.origin},
+                                  triangulation.h0, node.data(), active_cell_dof_table.data()};
+      double h_fe = 0, h_self = 0;
+      for (unsigned i = 0; i < number_of_atoms; ++i) {
+        h_fe += 0.5 * charges[i] * gmg_forces::atom_phi(L, solution.data(), &atom_positions[3 * i]);
+        h_self += charges[i] * charges[i] / (std::sqrt(M_PI) * par.r_c);
+      }
+      if (std::memcmp(&h_fe, &fe, sizeof(double)) != 0 || std::memcmp(&h_self, &self, sizeof(double)) != 0)
+        throw std::logic_error("Energy and forces from resident tables: the device's fe or self sum differs from the host's");
+    }
+  } else if (rcut <= 0.0) {  // the reference's loop (:1325-1332)
     for (unsigned i = 0; i < number_of_atoms; ++i)
       for (unsigned j = i + 1; j < number_of_atoms; ++j) {
         double r2 = 0;
@@ -2305,10 +2338,11 @@ void LaplaceProblem<dim>::postprocess_electrostatic_energy() {
     }
     for (unsigned i = 0; i < number_of_atoms; ++i) shortr += part[i];  // fixed order: deterministic
   }
-  for (unsigned i = 0; i < number_of_atoms; ++i) {
-    fe += 0.5 * charges[i] * fe_value_at(solution, &atom_positions[3 * i]);
-    self += charges[i] * charges[i] / (std::sqrt(M_PI) * par.r_c);
-  }
+  if (!resident)
+    for (unsigned i = 0; i < number_of_atoms; ++i) {
+      fe += 0.5 * charges[i] * fe_value_at(solution, &atom_positions[3 * i]);
+      self += charges[i] * charges[i] / (std::sqrt(M_PI) * par.r_c);
+    }
   rep.has_energy = true;
   rep.energy_analytical = analytical; rep.energy_short = shortr; rep.energy_fe_long = fe; rep.energy_self = self;
   rep.energy_total = shortr + fe - self;
@@ -2347,11 +2381,18 @@ int LaplaceProblem<dim>::atom_forces(bool on_device, double cutoff, std::vector<
     if (v) v->assign((size_t)n, 0.0);
   for (std::vector<double> *v : {field, force, force_short})
     if (v) v->assign((size_t)n * 3, 0.0);
+  auto data = [](std::vector<double> *v) { return v ? v->data() : nullptr; };
+  if (on_device && gmg != nullptr && energy_forces_resident_applies()) {  // no node array, no cell table crosses the bus
+    ensure_point_locator_resident();
+    const int rc = gmg_atom_forces_resident(gmg, triangulation.origin, triangulation.h0, n, atom_positions.data(), charges.data(), device_solution(),
+                                            (int64_t)solution.size(), par.r_c, cutoff, data(phi), data(field), data(force), data(force_short), data(e_short));
+    if (rc != GMG_OK) last_error = std::string("gmg_atom_forces_resident: ") + gmg_last_error(gmg);
+    return rc;
+  }
   std::vector<int32_t> node;
   point_locator(node);
   const int32_t n0[3] = {triangulation.n0, triangulation.n0, triangulation.n0};
   const double origin[3] = {triangulation.origin, triangulation.origin, triangulation.origin};
-  auto data = [](std::vector<double> *v) { return v ? v->data() : nullptr; };
   if (on_device) {
     GMGC(ensure_context());
     GMGC(gmg_set_point_locator(gmg, n0, origin, triangulation.h0, (int64_t)node.size(), node.data(), (int64_t)active_cells.size(),
@@ -2704,6 +2745,7 @@ std::vector<double> LaplaceProblem<dim>::total_charge_density_vector() const {
 template <int dim>
 void LaplaceProblem<dim>::finish_cycle() {
   estimate_error_and_mark_cells();                                               // :1552
+  energy_forces_resident = decide_energy_forces_resident();
   if (lammpsinput && (number_of_atoms < 300 || (par.energy_for_large_systems && par.short_range_cutoff > 0.0))) {
     postprocess_electrostatic_energy();     // :1554-1555
     if (number_of_atoms < 300) postprocess_error_in_energy_norm();  // :1556 (O(cells x atoms): under the reference's small-system gate only)

@@ -85,6 +85,7 @@ struct Parameters {
   bool operators_from_resident_tables = false;  // gmg_close_constraints and the _resident entries: operators, right-hand side and distribution read the tables gmg_build_mesh_tables left on the device
   bool densities_from_resident_tables = false;  // gmg_charge_density_resident: the densities read the cells' geometry from the tables gmg_build_mesh_tables left on the device
   bool estimator_from_resident_tables = false;  // gmg_build_face_table_resident, gmg_estimate_error_resident, gmg_refine_forest_marked and gmg_energy_norm_error_resident: the end of the cycle reads the tables, the face table and the marks where they lie
+  bool energy_forces_from_resident_tables = false;  // gmg_build_point_locator_resident, gmg_electrostatic_energy_resident and gmg_atom_forces_resident: the energy's sums and the forces read the tables and the solution where they lie
   bool refinement_on_device = false;     // gmg_refine_forest, gmg_transfer_solution and gmg_build_face_table instead of refine_flagged, the interpolation loop of refine_grid and face_table (cycle on the device, one rank)
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
@@ -236,6 +237,15 @@ class LaplaceProblem {
   int direct_coulomb(bool on_device, std::vector<double> *force, std::vector<double> *energy);  // exact all-pairs sum
   bool forces_on_device() const { return solve_on_device_requested && gmg != nullptr; }  // where the cycle's solve ran
   void point_locator(std::vector<int32_t> &node) const;  // the forest flattened for gmg_set_point_locator
+  // "Energy and forces from resident tables" (DESIGN.md section 25): the locator is formed on the device next to the tables,
+  // the energy's three sums and the forces read cell_dofs and the solution there
+  bool decide_energy_forces_resident();   // says so once when the key asks for it in vain
+  bool energy_forces_resident_applies() const {
+    return par.energy_forces_from_resident_tables && operators_resident && device_solution() != nullptr && dim == 3 && lammpsinput && !distributed;
+  }
+  void ensure_point_locator_resident();   // gmg_build_point_locator_resident for the current forest, once per mesh
+  bool energy_forces_resident = false;    // the last finish_cycle took energy and forces from the resident entries
+  bool energy_forces_fallback_reported = false;
   // The exact free-space potential of all atoms (Analytical_Solution, include/step_50.h:338-369) and / or its gradient at
   // n_points points [3 n] (3D): through gmg_gaussian_potential, or by the host mirror of the same text (gmg_exact.hpp).
   int gaussian_potential(bool on_device, int64_t n_points, const double *points, double *phi, double *grad);
@@ -314,6 +324,7 @@ class LaplaceProblem {
   bool estimated_on_device = false;        // the last estimate came from gmg_estimate_error
   bool estimator_fallback_reported = false;  // "Error estimator on device" was set but not applicable: said once
   int64_t host_density_copies = 0;         // how often ensure_host_densities() fetched device-resident densities
+  int64_t dof_map_builds = 0;              // how often ensure_dof_maps() built the vertex -> DoF hash tables
 
   ForestCells forest_cells() const;     // "Mesh tables on device": the input of gmg_build_mesh_tables
   bool decide_mesh_tables_on_device();  // this cycle's numbering, constraints and level flags formed by gmg_build_mesh_tables?

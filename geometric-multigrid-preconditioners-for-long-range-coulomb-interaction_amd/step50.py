@@ -91,6 +91,7 @@ def prm_text(**kw) -> str:
         "operators_from_resident_tables": ("Misc", "Operators from resident tables"),
         "densities_from_resident_tables": ("Misc", "Charge densities from resident tables"),
         "estimator_from_resident_tables": ("Misc", "Estimator from resident tables"),
+        "energy_forces_from_resident_tables": ("Misc", "Energy and forces from resident tables"),
         "refinement_on_device": ("Misc", "Refinement on device"),
         "coarse_solver": ("Solver input data", "Coarse solver"),
         "estimator_on_device": ("Misc", "Error estimator on device"),
@@ -400,6 +401,11 @@ class Problem:
         resident tables" took effect)?"""
         return bool(self.L.step50_estimator_resident(self.h))
 
+    def energy_forces_resident(self) -> bool:
+        """Did the last finish_cycle take the energy's sums and the forces from gmg_electrostatic_energy_resident and
+        gmg_atom_forces_resident ("Energy and forces from resident tables" took effect)?"""
+        return bool(self.L.step50_energy_forces_resident(self.h))
+
     def refined_on_device(self) -> bool:
         """Did the last refine_grid go through gmg_refine_forest and gmg_transfer_solution ("Refinement on device")?"""
         return bool(self.L.step50_refined_on_device(self.h))
@@ -508,6 +514,26 @@ class Problem:
         """How often device-resident charge densities were copied to the host (ensure_host_densities)."""
         self.L.step50_host_density_copies.restype = C.c_int64
         return int(self.L.step50_host_density_copies(self.h))
+
+    def electrostatic_energy(self):
+        """The electrostatic energy of the current solution once more, by the path the cycle took (host loops, or
+        gmg_electrostatic_energy_resident where "Energy and forces from resident tables" took effect): the report."""
+        self._chk(self.L.step50_electrostatic_energy(self.h), "electrostatic_energy")
+        return self.report(-1)
+
+    def point_locator(self):
+        """The host's flattened forest as gmg_set_point_locator takes it (LaplaceProblem::point_locator): node [cells of all
+        levels], >= 0 the flat index of child 0, < 0 the active cell -node - 1."""
+        self.L.step50_point_locator.restype = C.c_int64
+        out = np.zeros(self.L.step50_point_locator(self.h, None), dtype=np.int32)
+        if out.size:
+            self.L.step50_point_locator(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        return out
+
+    def dof_map_builds(self) -> int:
+        """How often the host built its vertex -> DoF hash tables (ensure_dof_maps)."""
+        self.L.step50_dof_map_builds.restype = C.c_int64
+        return int(self.L.step50_dof_map_builds(self.h))
 
     def error_per_cell(self):
         """eta per active cell of the last estimate (float32)."""

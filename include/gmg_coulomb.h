@@ -767,6 +767,48 @@ int gmg_energy_norm_error_resident(gmg_context *ctx, double origin, double h0, c
                                    const double *atom_xyz, const double *atom_q, double r_c, int nq, const double *quadrature_points,
                                    const double *weights, const double *shape_grad, double *error, double *cell_err2);
 
+/* Energy and forces at the atoms on the tables the last gmg_build_mesh_tables left on the device.  What
+ * the four entries below share: GMG_ERR_UNSUPPORTED on a context with a communicator and for 2D tables; GMG_ERR_INVALID when
+ * the context holds no mesh tables; zero cells and zero atoms are valid (without cells phi_h and the field are 0).  The
+ * resident locator is owned by the context INSIDE the mesh tables, as the face table is: the next gmg_build_mesh_tables,
+ * gmg_reset (unless the option reset_keeps_mesh_tables is set) and gmg_destroy drop it with the tables.  It is separate from
+ * the locator of gmg_set_point_locator: neither form sees the other's.
+ *
+ * gmg_build_point_locator_resident -- the node array of gmg_set_point_locator formed on the device from the forest the tables
+ * were built from (arguments and host checks of gmg_build_face_table_resident, with its codes).  With k = level_ptr[l] + c:
+ *   node[k] = level_ptr[l + 1] + first_child[k]        where first_child[k] >= 0,
+ *   node[k] = -(active number of k) - 1                otherwise,
+ * the active number being the number of active cells before k in (level, index) order, which is how the tables number their
+ * cells.  GMG_ERR_INVALID, found on the host before anything is launched, if dim differs from the tables' dim, the forest's
+ * number of active cells is not the tables' n_cells, or level 0 is not the full n0 lattice in lexicographic cell order (x
+ * fastest; the check of gmg_build_mesh_tables with level0_lexicographic = 1): the roots are indexed by coordinate.  The
+ * cells' DoFs are not copied: the locator reads the tables' cell_dofs.  Device memory kept: 4 bytes per forest cell.  The call
+ * first drops the locator the context holds, so after ANY failure none is held.  n_nodes, build_ms: may be NULL.            */
+int gmg_build_point_locator_resident(gmg_context *ctx, int dim, const int32_t n0[3], int n_levels, const int64_t *level_ptr,
+                                     const int32_t *cell_coord, const int32_t *cell_first_child, int64_t *n_nodes, double *build_ms);
+/* The kept node array copied out: n_nodes (cells of all levels), node [n_nodes]; NULL is skipped.  GMG_ERR_INVALID when the
+ * context holds none.                                                                                                      */
+int gmg_get_point_locator(gmg_context *ctx, int64_t *n_nodes, int32_t *node);
+/* gmg_atom_forces_resident -- gmg_atom_forces on the resident locator: root lattice n0 of the forest the locator was built from,
+ * origin (the same in every direction) and h0 as gmg_charge_density_resident takes them.  The same kernels, the same bins, the
+ * same bits in every output.  GMG_ERR_INVALID without a resident locator, for h0 <= 0, for n_u other than the tables' n_dofs
+ * (which covers every DoF of cell_dofs), and for what the sibling refuses of the remaining arguments.                       */
+int gmg_atom_forces_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz, const double *atom_q,
+                             const double *u, int64_t n_u, double r_c, double cutoff, double *phi, double *field, double *force,
+                             double *force_short, double *e_short);
+/* gmg_electrostatic_energy_resident -- the three sums of the electrostatic energy (src/step-50.cc:1310-1420), formed on the
+ * device; 24 bytes return.  out = {short, fe_long, self}, each ONE sequential sum over the atoms in ascending index, fp64, no
+ * contraction into fused multiply-adds:
+ *   short   = sum_i e_i                               e_i exactly as gmg_atom_forces returns it in e_short (same kernels)
+ *   fe_long = sum_i (0.5 * q_i) * phi_i               phi_i = phi_h(x_i) of octant 7 with clamp, as gmg_atom_forces returns phi
+ *   self    = sum_i q_i * q_i / (sqrt(pi) * r_c)      the divisor formed once
+ * total = short + fe_long - self is left to the caller.  The sums do not depend on the launch shape (options force_block,
+ * assemble_max_blocks).  Arguments and refusals of gmg_atom_forces_resident; out must not be NULL; build_ms (may be NULL):
+ * device time from the first kernel to the last.                                                                           */
+int gmg_electrostatic_energy_resident(gmg_context *ctx, double origin, double h0, int64_t n_atoms, const double *atom_xyz,
+                                      const double *atom_q, const double *u, int64_t n_u, double r_c, double cutoff, double out[3],
+                                      double *build_ms);
+
 /* ---- measurement -------------------------------------------------------------------- */
 typedef struct gmg_stats {
   int64_t coarse_solves;        /* calls of the coarse solver since the last reset           */
