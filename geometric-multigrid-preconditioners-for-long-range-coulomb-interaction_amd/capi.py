@@ -51,6 +51,7 @@ SYMBOLS = [
     "gmg_set_point_locator", "gmg_atom_forces", "gmg_direct_coulomb",
     "gmg_gaussian_potential", "gmg_energy_norm_error",
     "gmg_get_ssor_plan", "gmg_get_ssor_backward_rows", "gmg_ssor_slot_plan",
+    "gmg_get_ssor_plan_array", "gmg_get_ssor_plan_origin",
 ]
 
 
@@ -1100,7 +1101,24 @@ class Context:
         self._chk(self.L.gmg_get_ssor_backward_rows(self.h, C.c_int(level), C.byref(cnt), _p(rows, C.c_int32)))
         return rows[:cnt.value]
 
+    def get_ssor_plan_array(self, level, which):
+        """gmg_get_ssor_plan_array: one array of the level's four-wave plan as raw bytes (which: a name of SSOR_PLAN_ARRAYS or its index)."""
+        w = SSOR_PLAN_ARRAYS.index(which) if isinstance(which, str) else int(which)
+        nbytes = C.c_int64(0)
+        self._chk(self.L.gmg_get_ssor_plan_array(self.h, C.c_int(level), C.c_int(w), C.byref(nbytes), None))
+        out = np.zeros(max(nbytes.value, 1), dtype=np.uint8)
+        self._chk(self.L.gmg_get_ssor_plan_array(self.h, C.c_int(level), C.c_int(w), C.byref(nbytes), out.ctypes.data_as(C.c_void_p)))
+        return out[:nbytes.value]
 
+    def get_ssor_plan_origin(self, level):
+        """gmg_get_ssor_plan_origin: (on_device, bytes of col / val downloaded for the plan, why the host built it or '')."""
+        on_dev, moved, why = C.c_int(0), C.c_int64(0), C.c_char_p()
+        self._chk(self.L.gmg_get_ssor_plan_origin(self.h, C.c_int(level), C.byref(on_dev), C.byref(moved), C.byref(why)))
+        return bool(on_dev.value), int(moved.value), (why.value or b"").decode()
+
+
+# gmg_get_ssor_plan_array: the values of GMG_SSOR_PLAN_* in order
+SSOR_PLAN_ARRAYS = ("stream", "ranges", "blk_tab", "block_rng", "row_ci", "ci_row", "rpos_f", "rpos_b", "iso_diag", "iso_invd")
 SSOR_PLAN_KEYS = ("forward_ranges", "backward_ranges", "self_contained_ranges", "y_slots", "max_live_forward", "max_live_backward", "steps", "stream_bytes")
 
 

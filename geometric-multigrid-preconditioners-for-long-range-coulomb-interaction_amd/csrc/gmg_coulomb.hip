@@ -12,6 +12,7 @@
 #include "gmg_sgs_phase.hpp"
 #include "gmg_sgs_dep.hpp"
 #include "gmg_sgs_reg.hpp"
+#include "gmg_sgs_plan.hpp"
 #ifdef GMG_EXPERIMENTS
 #include "gmg_sgs_chain.hpp"  // hand-over through an LDS word instead of s_barrier: measured slower, kept as an experiment
 #endif
@@ -94,7 +95,8 @@ struct DevCSR {
 };
 
 struct SgsPlan {
-  // generic level-scheduled sweep straight from the CSR copy (fallback: rows with unsorted columns)
+  // generic level-scheduled sweep straight from the CSR copy (fallback: rows with unsorted columns).  Read only when !wave:
+  // a plan built on the device (gmg_sgs_plan.hpp) always has wave set and leaves these four tables and n_stages_max empty
   DevPtr<int32_t> stage_ptr, stage_rows, block_row, block_stage;
   int n_blocks = 0;
   int n_stages_max = 0;
@@ -122,6 +124,11 @@ struct SgsPlan {
   DevPtr<PhRange> p_ranges;
   DevPtr<uint4> p_blk_tab;
   std::vector<PhRange> host_pranges;
+  // who built the plan (gmg_get_ssor_plan_origin): the kernels of gmg_sgs_plan.hpp or the host; the bytes of col / val that came
+  // back to the host for it; with option ssor_plan_device set and a host-built plan, why (a fixed text)
+  bool on_device = false;
+  int64_t csr_bytes_down = 0;
+  const char *host_reason = "";
 };
 
 struct Level {
@@ -257,6 +264,7 @@ struct gmg_context {
   int coarse_chunk = 0;
   // diagnostic options (gmg_set_option / GMG_OPTIONS); the defaults are the fast paths
   int sgs_y_slots = 0;      // 0 = kSwYSlots; tests shrink it to force several LDS ranges
+  bool ssor_plan_device = false;  // option "ssor_plan_device": the default four-wave plan of a level is formed by kernels (gmg_sgs_plan.hpp) where it applies
   bool sgs_sliding = true;  // four-wave sweep: one self-contained range per direction where a block's live rows fit the y slots
   bool sgs_disable_wave = false, sgs_disable_phase = false, sgs_chain = false, sgs_dep = false, sgs_reg = false, debug_upload = false, sgs_profile = false;
   int sgs_profile_mode = 0;
@@ -1953,6 +1961,43 @@ void ssor_slot_alloc(int m, const std::vector<int32_t> &prp, const std::vector<i
   }
 }
 
+// What both plan builders end with: the sweep kernels may use the whole LDS, and, since the records carry absolute LDS
+// addresses, their dynamic LDS must start at 0 (no static __shared__) -- else the level keeps the generic sweep (G.wave unset).
+int sgs_wave_tail(gmg_context *ctx, SgsPlan &G, bool ph, bool dep, bool reg) {
+  HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_phase_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_phase_profile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_dep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPC(hipFuncSetAttribute((const void *)sgs_regs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#ifdef GMG_EXPERIMENTS
+  HIPC(hipFuncSetAttribute((const void *)sgs_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+#endif
+  // the sweep bakes absolute LDS addresses into its records: its dynamic LDS must start at 0 (no static __shared__)
+  hipFuncAttributes fa{};
+  HIPC(hipFuncGetAttributes(&fa, ph ? (const void *)sgs_phase_kernel : (const void *)sgs_wave_kernel<false>));
+  G.wave = fa.sharedSizeBytes == 0;
+  if (ph) {
+    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_phase_profile_kernel));
+    G.wave = G.wave && fa.sharedSizeBytes == 0;
+  }
+  if (dep) {
+    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_dep_kernel));
+    G.wave = G.wave && fa.sharedSizeBytes == 0;
+  }
+  if (reg) {
+    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_regs_kernel));
+    G.wave = G.wave && fa.sharedSizeBytes == 0;
+  }
+#ifdef GMG_EXPERIMENTS
+  if (ph) {
+    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_chain_kernel));
+    G.wave = G.wave && fa.sharedSizeBytes == 0;
+  }
+#endif
+  return GMG_OK;
+}
+
 // Plan of the wavefront sweep (gmg_sgs.hpp): per block the pruned rows, the dependency stages, the steps of both
 // sweep directions, their grouping into LDS-sized ranges (or one self-contained range per direction where the live
 // rows fit), and the record stream in consumption order.
@@ -1992,6 +2037,14 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   // before the plan is accepted (the one fault this code ever produced was a store through an aux field).
   uint64_t max_aux = 0, max_lds_addr = 0;
   std::vector<int64_t> blk_steps0((size_t)n_blocks + 1, 0), blk_bytes0((size_t)n_blocks + 1, 0);  // tallies at each block's start
+  // debug_upload: where the host spends the plan's time (seconds): block graph, steps + slots, shapes, record fill, upload
+  double laps[5] = {0, 0, 0, 0, 0};
+  auto lap_t = std::chrono::steady_clock::now();
+  auto lap = [&](int k) {
+    const auto t = std::chrono::steady_clock::now();
+    laps[k] += std::chrono::duration<double>(t - lap_t).count();
+    lap_t = t;
+  };
   for (int b = 0; b < n_blocks; ++b) {
     const int64_t rb = block_row[(size_t)b], re = block_row[(size_t)b + 1];
     const int m = (int)(re - rb);
@@ -2013,6 +2066,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
       iso_diag[(size_t)(rb + i)] = dstored;
       iso_invd[(size_t)(rb + i)] = 1.0 / aii;
     }
+    lap(0);
     const size_t ci_base = ci_row.size();
     ci_row.resize(ci_base + crow.size());
     rpos_f.resize(ci_row.size(), 0);
@@ -2047,6 +2101,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
         if (((slide[dir].n_slots + 1) & ~1) > y_cap) sliding = false;
       }
     }
+    lap(1);
     for (int dir = 1; dir >= 0; --dir) {  // backward first: the forward records point into the backward ones
       // entries of a row in this direction: forward = the columns j < i (y_j = 0 for j >= i); backward = the columns
       // j >= i, continuing the forward sum
@@ -2175,10 +2230,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
           // behind the last late column, products formed ahead).  A row may give the end of its head and the start of its T2 to
           // T1; of the shapes every row of the step fits, the one with the cheapest phase (measured costs, cycles) is taken.
           auto fits = [&](const RowCut &rc, int g, int l1, int l2, int *h0o, int *h1o) {
-            const int h1 = std::max(rc.last + 1, rc.ne - l2), h0 = std::max(std::min(rc.first, 8 * g), h1 - l1);
-            if (h0 > rc.first || h0 > 8 * g || h0 < 0) return false;
-            if (h0o) { *h0o = h0; *h1o = h1; }
-            return true;
+            return sp::fits(rc.ne, rc.first, rc.last, g, l1, l2, h0o, h1o);  // (shared with the device builder, gmg_sgs_plan.hpp)
           };
           struct Shape { int g, l1, l2; };
           std::vector<Shape> shape_of;
@@ -2195,15 +2247,18 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
                     bool ok = true;
                     for (int u = 0; u < nr && ok; ++u) ok = fits(cut[c0 + (size_t)u], g, l1, l2, nullptr, nullptr);
                     if (!ok) continue;
-                    const int ent = 8 * g + l1 + l2;
-                    const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, copy = 45.0 * (16.0 + (double)nr * ph_stride(g, l1 + l2)) / 1024.0,
-                                 p1 = 150.0 + 8.0 * (2.0 + 0.75 * ent), p2 = 100.0 + 11.0 * (8 * g + l2);
+                    // default: the measured phase costs (sp::shape_cost, shared with the device builder)
                     // (dep: the dependent wave's step is what counts -- ~20 cycles per T1 slot, ~8 per T2 add; the rest is the prep waves')
                     // (reg: no copy, no read-back; the record is 2 + 6 g + 0.75 (l1 + l2) load instructions of ~20 cycles)
-                    const double load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
-                    const double cost = dep ? 20.0 * l1 + 8.0 * l2 + 2.0 * g
-                                        : reg ? std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2)
-                                              : std::max(std::max(crit, copy), std::max(p1, p2)) + 0.1 * (crit + copy + p1 + p2);
+                    double cost;
+                    if (dep) {
+                      cost = 20.0 * l1 + 8.0 * l2 + 2.0 * g;
+                    } else if (reg) {
+                      const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, p2 = 100.0 + 11.0 * (8 * g + l2), load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
+                      cost = std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2);
+                    } else {
+                      cost = sp::shape_cost(g, l1, l2, (double)nr);
+                    }
                     if (cost < best) { best = cost; bs = Shape{g, l1, l2}; }
                   }
               if (bs.g < 0) return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row, false);
@@ -2227,20 +2282,25 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
                     bool ok = true;
                     for (size_t u = cpos[q0]; u < cpos[q1] && ok; ++u) ok = fits(cut[u], g, l1, l2, nullptr, nullptr);
                     if (!ok) continue;
-                    const int ent = 8 * g + l1 + l2;
-                    const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, copy = 45.0 * (16.0 + avg_rows * ph_stride(g, l1 + l2)) / 1024.0,
-                                 p1 = 150.0 + 8.0 * (2.0 + 0.75 * ent), p2 = 100.0 + 11.0 * (8 * g + l2);
+                    // default: the measured phase costs (sp::shape_cost, shared with the device builder)
+                    // (dep: the dependent wave's step is what counts -- ~20 cycles per T1 slot, ~8 per T2 add; the rest is the prep waves')
                     // (reg: no copy, no read-back; the record is 2 + 6 g + 0.75 (l1 + l2) load instructions of ~20 cycles)
-                    const double load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
-                    const double cost = dep ? 20.0 * l1 + 8.0 * l2 + 2.0 * g
-                                        : reg ? std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2)
-                                              : std::max(std::max(crit, copy), std::max(p1, p2)) + 0.1 * (crit + copy + p1 + p2);
+                    double cost;
+                    if (dep) {
+                      cost = 20.0 * l1 + 8.0 * l2 + 2.0 * g;
+                    } else if (reg) {
+                      const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, p2 = 100.0 + 11.0 * (8 * g + l2), load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
+                      cost = std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2);
+                    } else {
+                      cost = sp::shape_cost(g, l1, l2, avg_rows);
+                    }
                     if (cost < best) { best = cost; bs = Shape{g, l1, l2}; }
                   }
               if (bs.g < 0) return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row, false);
               for (size_t q = q0; q < q1; ++q) shape_of[q] = bs;
             }
           }
+          lap(2);
           PhRange P{};
           P.ws_off = R.ws_off; P.n_own = R.n_own; P.n_ws = R.n_ws; P.backward = dir;
           // the rows updated here as a piece of ycur (sweep-order numbering): first index and direction, if they are one
@@ -2355,6 +2415,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
           if (ctx->sgs_pf_lead_kb < 0 || (ctx->sgs_pf_lead_kb == 0 && !fieldmajor)) P.pf_step = P.pf_lead = 0;
           total_steps += P.n_steps;
           dir_pranges[dir].push_back(P);
+          lap(3);
           s0 = s1;
           continue;
         }
@@ -2436,6 +2497,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   block_rng[(size_t)n_blocks] = (int32_t)(ph ? pranges.size() : ranges.size());
   blk_steps0[(size_t)n_blocks] = total_steps; blk_bytes0[(size_t)n_blocks] = (int64_t)stream.size();
   const int y_slots = std::max(2, (max_ws + 1) & ~1);
+  lap(3);
   // ---- the plan is memory-safe by construction, and checked: every address a record carries lies inside what is allocated
   if (!stream.empty() && (max_aux * 8 + 8 > stream.size() || max_lds_addr + 8 > (uint64_t)y_slots * 8))
     return fail(ctx, GMG_ERR_INVALID, "SSOR plan: a record addresses memory outside the stream / the LDS slots (internal error)");
@@ -2460,6 +2522,10 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   // (every range self-contained: nobody reads or writes ycur -- it is not allocated and the pre-pass gets a null pointer)
   if (!(ph && n_self == (int)pranges.size())) HIPC(G.w_ycur.alloc(std::max<size_t>(ci_row.size(), 1)));
   HIPC(hipStreamSynchronize(ctx->stream));
+  lap(4);
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] SGS plan laps (host, %lld rows): block graph %.4f s, steps + slots %.4f s, shapes %.4f s, record fill %.4f s, upload %.4f s\n", (long long)n,
+                 laps[0], laps[1], laps[2], laps[3], laps[4]);
   G.host_bwd_rows = bwd_rows;
   G.n_self = n_self; G.live_max[0] = live_max[0]; G.live_max[1] = live_max[1];
   G.host_block_row = block_row;
@@ -2490,37 +2556,7 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
   G.w_n_coupled = (int64_t)ci_row.size();
   G.w_stream_bytes = (int64_t)stream.size();
   G.w_steps = total_steps; G.w_stages = total_stages;
-  HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPC(hipFuncSetAttribute((const void *)sgs_wave_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPC(hipFuncSetAttribute((const void *)sgs_phase_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPC(hipFuncSetAttribute((const void *)sgs_phase_profile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPC(hipFuncSetAttribute((const void *)sgs_dep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPC(hipFuncSetAttribute((const void *)sgs_regs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#ifdef GMG_EXPERIMENTS
-  HIPC(hipFuncSetAttribute((const void *)sgs_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#endif
-  // the sweep bakes absolute LDS addresses into its records: its dynamic LDS must start at 0 (no static __shared__)
-  hipFuncAttributes fa{};
-  HIPC(hipFuncGetAttributes(&fa, ph ? (const void *)sgs_phase_kernel : (const void *)sgs_wave_kernel<false>));
-  G.wave = fa.sharedSizeBytes == 0;
-  if (ph) {
-    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_phase_profile_kernel));
-    G.wave = G.wave && fa.sharedSizeBytes == 0;
-  }
-  if (dep) {
-    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_dep_kernel));
-    G.wave = G.wave && fa.sharedSizeBytes == 0;
-  }
-  if (reg) {
-    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_regs_kernel));
-    G.wave = G.wave && fa.sharedSizeBytes == 0;
-  }
-#ifdef GMG_EXPERIMENTS
-  if (ph) {
-    HIPC(hipFuncGetAttributes(&fa, (const void *)sgs_chain_kernel));
-    G.wave = G.wave && fa.sharedSizeBytes == 0;
-  }
-#endif
+  CHK(sgs_wave_tail(ctx, G, ph, dep, reg));
   if (ctx->debug_upload && ph)
     std::fprintf(stderr, "[gmg] SGS step shapes: G %lld %lld %lld %lld | L1/4 %lld %lld %lld %lld %lld %lld %lld %lld | L2/8 %lld %lld %lld %lld\n", (long long)hist_g[0], (long long)hist_g[1],
                  (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
@@ -2539,6 +2575,31 @@ int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, con
 }
 
 
+// debug_upload: the partition -- per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
+void sgs_partition_log(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val, const std::vector<int32_t> &block_row,
+                     bool explicit_rows) {
+  const int n_blocks = (int)block_row.size() - 1;
+  // the partition: per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
+  const std::vector<double> cost = ssor_block_costs(SsorPattern(n, rp, col, val), block_row);
+  double c_max = 0, c_sum = 0;
+  int64_t s_max = 0, s_sum = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    std::fprintf(stderr, "[gmg]   SSOR block %3d: rows [%lld, %lld) %lld, sub-steps %lld, stream %.2f MB, model %.1f us\n", b, (long long)block_row[(size_t)b],
+                 (long long)block_row[(size_t)b + 1], (long long)(block_row[(size_t)b + 1] - block_row[(size_t)b]), (long long)L.sgs.host_block_steps[(size_t)b],
+                 (double)L.sgs.host_block_bytes[(size_t)b] / 1e6, cost[(size_t)b]);
+    c_max = std::max(c_max, cost[(size_t)b]); c_sum += cost[(size_t)b];
+    s_max = std::max(s_max, L.sgs.host_block_steps[(size_t)b]); s_sum += L.sgs.host_block_steps[(size_t)b];
+  }
+  std::fprintf(stderr, "[gmg]   SSOR partition (%s): %d blocks, longest / mean: model %.2f, sub-steps %.2f\n",
+               explicit_rows ? "caller's" : ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED ? "balanced" : "equal rows", n_blocks,
+               c_sum > 0 ? c_max * n_blocks / c_sum : 1.0, s_sum > 0 ? (double)s_max * n_blocks / (double)s_sum : 1.0);
+  if (L.sgs.w_stage.get()) {
+    const int n_ranks = ctx->comm.n_ranks;
+    std::fprintf(stderr, "[gmg]   SSOR all-gather: %d ranks x %lld doubles (largest piece) = %.2f MB moved per sweep for %.2f MB of y\n", n_ranks,
+                 (long long)L.sgs.w_stage_len, 8e-6 * (double)L.sgs.w_stage_len * n_ranks, 8e-6 * (double)n);
+  }
+}
+
 // SGS level schedule on the symmetrised pattern, per block of consecutive rows:
 // stage(i) = 1 + max stage(j) over the coupled j < i of the same block.
 // The boundaries: the caller's (explicit_rows, checked by gmg_set_level_matrix), else the balanced cuts if that mode is on,
@@ -2551,7 +2612,7 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
   transpose_host(n, n, rp, col, ones.data(), trp, tcol, tval);
   std::vector<int32_t> block_row;
   if (explicit_rows) {
-    block_row.assign(explicit_rows->begin(), explicit_rows->end());
+    block_row.assign(explicit_rows->begin(), explicit_rows->end());  // (setup_sgs_device below: the same case and the equal runs)
   } else if (ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED) {
     std::vector<int64_t> br;
     std::vector<double> cost;
@@ -2606,27 +2667,327 @@ int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const in
   for (int b = 0; b < n_blocks; ++b) L.sgs.host_block_steps[(size_t)b] = 2 * (int64_t)(block_stage[(size_t)b + 1] - block_stage[(size_t)b]);
   L.sgs.host_block_bytes.assign((size_t)n_blocks, 0);
   CHK(setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row));
-  if (ctx->debug_upload) {
-    // the partition: per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
-    const std::vector<double> cost = ssor_block_costs(SsorPattern(n, rp, col, val), block_row);
-    double c_max = 0, c_sum = 0;
-    int64_t s_max = 0, s_sum = 0;
-    for (int b = 0; b < n_blocks; ++b) {
-      std::fprintf(stderr, "[gmg]   SSOR block %3d: rows [%lld, %lld) %lld, sub-steps %lld, stream %.2f MB, model %.1f us\n", b, (long long)block_row[(size_t)b],
-                   (long long)block_row[(size_t)b + 1], (long long)(block_row[(size_t)b + 1] - block_row[(size_t)b]), (long long)L.sgs.host_block_steps[(size_t)b],
-                   (double)L.sgs.host_block_bytes[(size_t)b] / 1e6, cost[(size_t)b]);
-      c_max = std::max(c_max, cost[(size_t)b]); c_sum += cost[(size_t)b];
-      s_max = std::max(s_max, L.sgs.host_block_steps[(size_t)b]); s_sum += L.sgs.host_block_steps[(size_t)b];
-    }
-    std::fprintf(stderr, "[gmg]   SSOR partition (%s): %d blocks, longest / mean: model %.2f, sub-steps %.2f\n",
-                 explicit_rows ? "caller's" : ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED ? "balanced" : "equal rows", n_blocks,
-                 c_sum > 0 ? c_max * n_blocks / c_sum : 1.0, s_sum > 0 ? (double)s_max * n_blocks / (double)s_sum : 1.0);
-    if (L.sgs.w_stage.get()) {
-      const int n_ranks = ctx->comm.n_ranks;
-      std::fprintf(stderr, "[gmg]   SSOR all-gather: %d ranks x %lld doubles (largest piece) = %.2f MB moved per sweep for %.2f MB of y\n", n_ranks,
-                   (long long)L.sgs.w_stage_len, 8e-6 * (double)L.sgs.w_stage_len * n_ranks, 8e-6 * (double)n);
+  if (ctx->debug_upload) sgs_partition_log(ctx, L, n, rp, col, val, block_row, explicit_rows != nullptr);
+  return GMG_OK;
+}
+
+// grid of an assembly kernel: by size, at most `most` workgroups, capped by option assemble_max_blocks
+dim3 asm_blocks(const gmg_context *ctx, int64_t n, int per_block, int most = 1 << 16) {
+  int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + per_block - 1) / per_block));
+  if (ctx->assemble_max_blocks > 0) g = std::min<int64_t>(g, ctx->assemble_max_blocks);
+  return dim3((unsigned)g);
+}
+
+// ---- the same plan formed on the device (option ssor_plan_device; gmg_sgs_plan.hpp) ----------------------------------------
+// Why the device builder does not apply to this context (nullptr: it may); one fixed text per cause.
+const char *sgs_device_refusal(const gmg_context *ctx, bool explicit_rows) {
+  if (ctx->dist) return "communicator";
+  if (!explicit_rows && ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED) return "balanced partition";
+  if (!ctx->sgs_sliding) return "option sgs_sliding unset";
+  if (ctx->sgs_disable_wave) return "option sgs_disable_wave set";
+  if (ctx->sgs_disable_phase) return "option sgs_disable_phase set";
+  if (ctx->sgs_profile) return "option sgs_profile set";
+  if (ctx->sgs_dep) return "option sgs_dep set";
+  if (ctx->sgs_reg) return "option sgs_reg set";
+  if (ctx->sgs_chain) return "option sgs_chain set";
+  if (ctx->sgs_groups) return "option sgs_groups set";
+  if (ctx->sgs_phase_chunk) return "option sgs_phase_chunk set";
+  if (ctx->sgs_phase_nosplit) return "option sgs_phase_nosplit set";
+  if (ctx->sgs_phase_nocascade) return "option sgs_phase_nocascade set";
+  if (ctx->sgs_pf_lead_kb) return "option sgs_pf_lead_kb set";
+  return nullptr;
+}
+
+// The plan of level L from its CSR on the device (rp: n + 1 row pointers, col, val).  *reason == nullptr on return: L.sgs holds
+// the plan setup_sgs would have made, byte for byte.  Else nothing of L.sgs was touched and *reason says why the host builder
+// has to run (decided after the kernels found the condition, before anything is kept).  A plan that fails its own checks is an
+// error (GMG_ERR_INVALID): no sweep runs on it.
+int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, const int32_t *col, const double *val,
+                     const std::vector<int64_t> *explicit_rows, const char **reason) {
+  *reason = sgs_device_refusal(ctx, explicit_rows != nullptr);
+  if (*reason) return GMG_OK;
+  if (n <= 0) { *reason = "empty level"; return GMG_OK; }
+  std::vector<int32_t> block_row;
+  if (explicit_rows) {
+    block_row.assign(explicit_rows->begin(), explicit_rows->end());
+  } else {
+    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64));
+    block_row.resize((size_t)nb + 1);
+    for (int b = 0; b <= nb; ++b) block_row[(size_t)b] = (int32_t)(n * b / nb);
+  }
+  const int n_blocks = (int)block_row.size() - 1;
+  int y_cap = ctx->sgs_y_slots > 0 ? ctx->sgs_y_slots : kPhYSlots;
+  y_cap = std::max(64, std::min(y_cap, kPhYSlots)) & ~1;
+  hipStream_t st = ctx->stream;
+  const size_t N = (size_t)n, NB = (size_t)n_blocks;
+  // debug_upload: wall time (seconds) up to each of the builder's host synchronisations: graph, stages, order .. offsets, records + check
+  double laps[4] = {0, 0, 0, 0};
+  auto lap_t = std::chrono::steady_clock::now();
+  auto lap = [&](int k) {
+    const auto t = std::chrono::steady_clock::now();
+    laps[k] += std::chrono::duration<double>(t - lap_t).count();
+    lap_t = t;
+  };
+  auto grid = [&](int64_t cnt) { return asm_blocks(ctx, cnt, 256); };
+  auto scan = [&](int32_t *p, int64_t cnt) { hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, st, p, cnt); };
+  sp::Args a{};
+  a.n = n; a.n_blocks = n_blocks; a.y_cap = y_cap; a.rp = rp; a.col = col; a.val = val;
+  // ---- 1. pruned graph
+  DevPtr<int32_t> d_brow, d_prp, d_indeg, d_upptr, d_upfill, d_ccnt, d_stage, d_pcol, d_uplist, d_row_ci;
+  DevPtr<uint8_t> d_coupled;
+  DevPtr<uint32_t> d_flags;
+  DevPtr<double> d_pval, d_iso_diag, d_iso_invd;
+  DevPtr<sp::Block> d_blk;
+  HIPC(upload(d_brow, block_row, st));
+  HIPC(d_prp.alloc(N + 1)); HIPC(d_indeg.alloc(N)); HIPC(d_upptr.alloc(N + 1)); HIPC(d_upfill.alloc(N)); HIPC(d_ccnt.alloc(NB));
+  HIPC(d_stage.alloc(N)); HIPC(d_coupled.alloc(N)); HIPC(d_flags.alloc(1)); HIPC(d_iso_diag.alloc(N)); HIPC(d_iso_invd.alloc(N)); HIPC(d_row_ci.alloc(N));
+  HIPC(hipMemsetAsync(d_indeg.get(), 0, 4 * N, st)); HIPC(hipMemsetAsync(d_upptr.get(), 0, 4 * (N + 1), st)); HIPC(hipMemsetAsync(d_upfill.get(), 0, 4 * N, st));
+  HIPC(hipMemsetAsync(d_ccnt.get(), 0, 4 * NB, st)); HIPC(hipMemsetAsync(d_coupled.get(), 0, N, st)); HIPC(hipMemsetAsync(d_flags.get(), 0, 4, st));
+  HIPC(hipMemsetAsync(d_row_ci.get(), 0xff, 4 * N, st));
+  a.brow = d_brow.get(); a.prp = d_prp.get(); a.indeg = d_indeg.get(); a.upptr = d_upptr.get(); a.upfill = d_upfill.get(); a.ccnt = d_ccnt.get();
+  a.stage = d_stage.get(); a.coupled = d_coupled.get(); a.flags = d_flags.get(); a.iso_diag = d_iso_diag.get(); a.iso_invd = d_iso_invd.get(); a.row_ci = d_row_ci.get();
+  hipLaunchKernelGGL(sp::graph_kernel<false>, grid(n), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(sp::coupled_count_kernel, grid(n), dim3(256), 0, st, a);
+  scan(d_prp.get(), n);
+  scan(d_upptr.get(), n);
+  uint32_t flags = 0;
+  int32_t n_pruned = 0, n_up = 0;
+  std::vector<int32_t> ccnt(NB, 0);
+  HIPC(hipMemcpyAsync(&flags, d_flags.get(), 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(&n_pruned, d_prp.get() + n, 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(&n_up, d_upptr.get() + n, 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(ccnt.data(), d_ccnt.get(), 4 * NB, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  CHK(launch_status(ctx));
+  lap(0);
+  if (flags & sp::kUnsorted) { *reason = "unsorted columns"; return GMG_OK; }
+  if (flags & sp::kWide) { *reason = "row too wide"; return GMG_OK; }
+  std::vector<sp::Block> blk(NB);
+  std::vector<int32_t> block_rng(NB + 1, 0);
+  int64_t nct = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    sp::Block &B = blk[(size_t)b];
+    B = sp::Block{block_row[(size_t)b], block_row[(size_t)b + 1], (int32_t)nct, ccnt[(size_t)b], 0, 0, block_rng[(size_t)b], 0};
+    nct += ccnt[(size_t)b];
+    block_rng[(size_t)b + 1] = block_rng[(size_t)b] + (ccnt[(size_t)b] > 0 ? 2 : 0);
+  }
+  const int n_ranges = block_rng[NB];
+  const size_t NC = (size_t)nct;
+  a.n_coupled = (int32_t)nct;
+  HIPC(upload(d_blk, blk, st));
+  a.blk = d_blk.get();
+  HIPC(d_pcol.alloc(std::max<size_t>((size_t)n_pruned, 1))); HIPC(d_pval.alloc(std::max<size_t>((size_t)n_pruned, 1))); HIPC(d_uplist.alloc(std::max<size_t>((size_t)n_up, 1)));
+  a.pcol = d_pcol.get(); a.pval = d_pval.get(); a.uplist = d_uplist.get();
+  hipLaunchKernelGGL(sp::graph_kernel<true>, grid(n), dim3(256), 0, st, a);
+  // ---- 2. stages
+  DevPtr<int32_t> d_queue, d_sptr, d_stepbase, d_nstages, d_nsteps, d_ci_row, d_spos;
+  HIPC(d_queue.alloc(std::max<size_t>(NC, 1))); HIPC(d_ci_row.alloc(std::max<size_t>(NC, 1)));
+  HIPC(d_sptr.alloc(NC + NB + 1)); HIPC(d_stepbase.alloc(NC + NB + 1)); HIPC(d_spos.alloc(NC + NB + 1)); HIPC(d_nstages.alloc(NB)); HIPC(d_nsteps.alloc(NB));
+  a.queue = d_queue.get(); a.ci_row = d_ci_row.get(); a.sptr = d_sptr.get(); a.spos = d_spos.get(); a.stepbase = d_stepbase.get(); a.nstages = d_nstages.get(); a.nsteps = d_nsteps.get();
+  hipLaunchKernelGGL(sp::stage_kernel, asm_blocks(ctx, n_blocks, 1), dim3(1024), 0, st, a);
+  std::vector<int32_t> nstages(NB, 0), nsteps(NB, 0);
+  HIPC(hipMemcpyAsync(nstages.data(), d_nstages.get(), 4 * NB, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(nsteps.data(), d_nsteps.get(), 4 * NB, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(&flags, d_flags.get(), 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  CHK(launch_status(ctx));
+  lap(1);
+  if (flags & sp::kInternal) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: the stage propagation did not reach every coupled row (internal error)");
+  int64_t n_steps = 0, total_stages = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    blk[(size_t)b].S = nsteps[(size_t)b]; blk[(size_t)b].g0 = (int32_t)n_steps;
+    n_steps += 2 * (int64_t)nsteps[(size_t)b];
+    total_stages += nstages[(size_t)b];
+  }
+  if (n_steps >= INT32_MAX / kPhMaxRows) { *reason = "stream positions beyond 2^31"; return GMG_OK; }
+  const size_t NS = (size_t)n_steps;
+  a.n_steps = (int32_t)n_steps;
+  HIPC(hipMemcpyAsync(d_blk.get(), blk.data(), sizeof(sp::Block) * NB, hipMemcpyHostToDevice, st));
+  // ---- 3. - 6. order, steps, slots, shapes, offsets
+  DevPtr<int32_t> d_su, d_st_bd, d_st_nrows, d_st_row, d_last, d_dueptr, d_duefill, d_duelist, d_slot, d_nslots, d_cut, d_shape, d_word, d_bytes, d_off16, d_rbytes;
+  DevPtr<unsigned long long> d_mask;
+  HIPC(d_su.alloc(2 * N)); HIPC(d_last.alloc(2 * N)); HIPC(d_slot.alloc(2 * N));
+  HIPC(d_st_bd.alloc(NS + 1)); HIPC(d_st_nrows.alloc(NS + 1)); HIPC(d_st_row.alloc(NS * kPhMaxRows + 1)); HIPC(d_dueptr.alloc(NS + 1)); HIPC(d_duefill.alloc(NS + 1));
+  HIPC(d_duelist.alloc(2 * NC + 1)); HIPC(d_nslots.alloc(2 * NB)); HIPC(d_cut.alloc(NS * kPhMaxRows + 1)); HIPC(d_shape.alloc(NS + 1)); HIPC(d_word.alloc(NS + 1));
+  HIPC(d_bytes.alloc(NS + 1)); HIPC(d_off16.alloc(NS + 1)); HIPC(d_mask.alloc(2 * NS + 1)); HIPC(d_rbytes.alloc(2 * NB));
+  HIPC(hipMemsetAsync(d_last.get(), 0xff, 8 * N, st)); HIPC(hipMemsetAsync(d_dueptr.get(), 0, 4 * (NS + 1), st)); HIPC(hipMemsetAsync(d_duefill.get(), 0, 4 * (NS + 1), st));
+  HIPC(hipMemsetAsync(d_nslots.get(), 0, 8 * NB, st)); HIPC(hipMemsetAsync(d_off16.get(), 0, 4 * (NS + 1), st));
+  a.su = d_su.get(); a.last = d_last.get(); a.slot = d_slot.get(); a.st_bd = d_st_bd.get(); a.st_nrows = d_st_nrows.get(); a.st_row = d_st_row.get();
+  a.dueptr = d_dueptr.get(); a.duefill = d_duefill.get(); a.duelist = d_duelist.get(); a.nslots = d_nslots.get(); a.cut = d_cut.get(); a.shape = d_shape.get();
+  a.word = d_word.get(); a.bytes = d_bytes.get(); a.off16 = d_off16.get(); a.mask = d_mask.get();
+  if (nct > 0) {
+    // (only now: the stage propagation was found complete above, so every coupled row has a stage and every stage its place)
+    hipLaunchKernelGGL(sp::rank_kernel, asm_blocks(ctx, n_blocks, 1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(sp::order_kernel, grid(nct), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::last_kernel, grid(2 * nct), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::due_kernel<false>, grid(2 * nct), dim3(256), 0, st, a);
+    scan(d_dueptr.get(), n_steps);
+    hipLaunchKernelGGL(sp::due_kernel<true>, grid(2 * nct), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::slot_kernel, asm_blocks(ctx, 2 * n_blocks, 1), dim3(sp::kSlotThreads), 0, st, a);
+    hipLaunchKernelGGL(sp::cut_kernel, grid(n_steps), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::chunk_kernel, grid(n_steps), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::word_kernel, grid(n_steps), dim3(256), 0, st, a);
+    scan(d_off16.get(), n_steps);
+  }
+  hipLaunchKernelGGL(sp::range_bytes_kernel, grid(2 * n_blocks), dim3(256), 0, st, a, d_rbytes.get());
+  std::vector<int32_t> nslots(2 * NB, 0), rbytes(2 * NB, 0);
+  HIPC(hipMemcpyAsync(nslots.data(), d_nslots.get(), 8 * NB, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(rbytes.data(), d_rbytes.get(), 8 * NB, hipMemcpyDeviceToHost, st));
+  HIPC(hipMemcpyAsync(&flags, d_flags.get(), 4, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  CHK(launch_status(ctx));
+  lap(2);
+  if (flags & sp::kNoFit) { *reason = "block does not fit"; return GMG_OK; }
+  if (flags & sp::kNoShape) { *reason = "no shape"; return GMG_OK; }
+  // ---- 7. the ranges: inside a block the backward one first in the stream, the forward one first in the table
+  std::vector<PhRange> pranges((size_t)n_ranges);
+  std::vector<int64_t> rbase((size_t)n_ranges + 1, 0), blk_bytes0(NB + 1, 0);
+  int64_t stream_size = 0;
+  int live_max[2] = {0, 0}, max_ws = 0;
+  for (int b = 0; b < n_blocks; ++b) {
+    blk_bytes0[(size_t)b] = stream_size;
+    const sp::Block &B = blk[(size_t)b];
+    if (B.nc == 0) continue;
+    for (int dir = 1; dir >= 0; --dir) {
+      const int ns = nslots[2 * (size_t)b + dir];
+      live_max[dir] = std::max(live_max[dir], ns);
+      max_ws = std::max(max_ws, ns);
+      PhRange P{};
+      P.backward = dir; P.pad0[0] = 1; P.pad0[1] = ns;
+      P.n_steps = B.S;
+      const int64_t base = (stream_size + 1023) / 1024 * 1024, off = (int64_t)rbytes[2 * (size_t)b + dir] * 16;
+      P.stream_off = base;
+      P.blk_tab = (uint32_t)(B.g0 + (dir ? 0 : B.S));
+      const int64_t padded = (off + 2048 + 1023) / 1024 * 1024;
+      if (padded >= ((int64_t)1 << 31) || (base + padded) / 8 >= ((int64_t)1 << 31)) { *reason = "stream positions beyond 2^31"; return GMG_OK; }
+      P.stream_bytes = (uint32_t)padded;
+      stream_size = base + padded;
+      pranges[(size_t)(B.rng + dir)] = P;
+      rbase[(size_t)(B.rng + dir)] = base;
     }
   }
+  blk_bytes0[NB] = stream_size;
+  const int y_slots = std::max(2, (max_ws + 1) & ~1);
+  // ---- 8. records
+  DevPtr<int64_t> d_rbase;
+  DevPtr<char> d_stream;
+  DevPtr<uint4> d_blk_tab;
+  DevPtr<PhRange> d_pranges;
+  DevPtr<int32_t> d_rpos, d_block_rng;
+  DevPtr<unsigned long long> d_chk;
+  HIPC(upload(d_rbase, rbase, st));
+  HIPC(upload(d_pranges, pranges, st));
+  HIPC(upload(d_block_rng, block_rng, st));
+  HIPC(d_stream.alloc(std::max<size_t>((size_t)stream_size, 1))); HIPC(d_blk_tab.alloc(std::max<size_t>(NS, 1))); HIPC(d_rpos.alloc(std::max<size_t>(2 * NC, 1))); HIPC(d_chk.alloc(8));
+  HIPC(hipMemsetAsync(d_stream.get(), 0, std::max<size_t>((size_t)stream_size, 1), st));
+  HIPC(hipMemsetAsync(d_chk.get(), 0, 64, st));
+  a.rbase = d_rbase.get(); a.stream = d_stream.get(); a.blk_tab = d_blk_tab.get(); a.rpos = d_rpos.get();
+  if (nct > 0) {
+    hipLaunchKernelGGL(sp::record_kernel, grid(2 * nct), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sp::header_kernel, grid(n_steps), dim3(256), 0, st, a);
+  }
+  // ---- the finished plan is checked from its own arrays before it is accepted
+  sp::CheckArgs c{};
+  c.ranges = d_pranges.get(); c.blk_tab = d_blk_tab.get(); c.stream = d_stream.get(); c.rpos_f = d_rpos.get(); c.rpos_b = d_rpos.get() + NC;
+  c.n_ranges = n_ranges; c.n_coupled = (int32_t)nct; c.y_slots = y_slots; c.stream_bytes = stream_size; c.out = d_chk.get();
+  hipLaunchKernelGGL(sp::check_kernel, asm_blocks(ctx, std::max(n_ranges, 1), 1, 1024), dim3(256), 0, st, c);
+  unsigned long long chk[8] = {};
+  std::vector<int32_t> ci_row(NC);
+  std::vector<uint4> blk_tab_h;
+  HIPC(hipMemcpyAsync(chk, d_chk.get(), 64, hipMemcpyDeviceToHost, st));
+  if (NC) HIPC(hipMemcpyAsync(ci_row.data(), d_ci_row.get(), 4 * NC, hipMemcpyDeviceToHost, st));
+  if (ctx->debug_upload && NS) {
+    blk_tab_h.resize(NS);
+    HIPC(hipMemcpyAsync(blk_tab_h.data(), d_blk_tab.get(), 16 * NS, hipMemcpyDeviceToHost, st));
+  }
+  HIPC(hipStreamSynchronize(st));
+  CHK(launch_status(ctx));
+  if (chk[0]) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: the block table, a header or a record fails the plan's checks (internal error)");
+  if (stream_size > 0 && (chk[1] * 8 + 8 > (uint64_t)stream_size || chk[2] + 8 > (uint64_t)y_slots * 8))
+    return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: a record addresses memory outside the stream / the LDS slots (internal error)");
+  if (chk[3] >= (uint64_t)n) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: a backward record stores outside the level vector (internal error)");
+  if (NC && chk[4] * 8 + 8 > (uint64_t)stream_size) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: rhs position outside the stream (internal error)");
+  // ---- 9. accepted: the plan and its host-side members, as setup_sgs + setup_sgs_wave leave them
+  L.sgs = SgsPlan();
+  SgsPlan &G = L.sgs;
+  G.n_blocks = n_blocks;
+  HIPC(upload(G.w_ranges, std::vector<SwRange>(), st));
+  HIPC(upload(G.w_ws_ci, std::vector<int32_t>(), st));
+  G.p_ranges = std::move(d_pranges); G.p_blk_tab = std::move(d_blk_tab); G.w_block_rng = std::move(d_block_rng);
+  G.w_ci_row = std::move(d_ci_row); G.w_row_ci = std::move(d_row_ci); G.w_stream = std::move(d_stream);
+  G.w_iso_diag = std::move(d_iso_diag); G.w_iso_invd = std::move(d_iso_invd);
+  HIPC(G.w_rpos_f.alloc(std::max<size_t>(NC, 1))); HIPC(G.w_rpos_b.alloc(std::max<size_t>(NC, 1)));
+  if (NC) {
+    HIPC(hipMemcpyAsync(G.w_rpos_f.get(), d_rpos.get(), 4 * NC, hipMemcpyDeviceToDevice, st));
+    HIPC(hipMemcpyAsync(G.w_rpos_b.get(), d_rpos.get() + NC, 4 * NC, hipMemcpyDeviceToDevice, st));
+  }
+  HIPC(hipStreamSynchronize(st));
+  for (int b = 0; b < n_blocks; ++b)  // (the aux words of the backward records in stream order: each block's coupled rows, last first)
+    for (int q = blk[(size_t)b].nc - 1; q >= 0; --q) G.host_bwd_rows.push_back(ci_row[(size_t)(blk[(size_t)b].q0 + q)]);
+  G.n_self = n_ranges; G.live_max[0] = live_max[0]; G.live_max[1] = live_max[1];
+  G.host_block_row = block_row;
+  G.host_block_rng = block_rng;
+  G.host_block_steps.assign(NB, 0);
+  G.host_block_bytes.assign(NB, 0);
+  for (int b = 0; b < n_blocks; ++b) {
+    G.host_block_steps[(size_t)b] = blk[(size_t)b].nc > 0 ? 2 * (int64_t)blk[(size_t)b].S : 0;
+    G.host_block_bytes[(size_t)b] = blk_bytes0[(size_t)b + 1] - blk_bytes0[(size_t)b];
+  }
+  G.w_y_slots = y_slots;
+  G.w_lds_bytes = y_slots * 8 + kPhWaves * kPhRegion + kPhJunk;
+  G.w_n_ranges = n_ranges;
+  G.phased = true;
+  G.host_pranges = pranges;
+  G.w_n_coupled = nct;
+  G.w_stream_bytes = stream_size;
+  G.w_steps = n_steps; G.w_stages = total_stages;
+  G.n_bwd = n_ranges / 2;
+  G.on_device = true;
+  CHK(sgs_wave_tail(ctx, G, true, false, false));
+  if (!G.wave) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: the sweep kernel has static LDS (internal error)");
+  lap(3);
+  if (ctx->debug_upload) {
+    std::fprintf(stderr, "[gmg] SGS plan laps (device, %lld rows): graph %.4f s, stages %.4f s, order + slots + shapes + offsets %.4f s, records + check %.4f s\n", (long long)n,
+                 laps[0], laps[1], laps[2], laps[3]);
+    std::vector<int64_t> hist_l1(8, 0), hist_l2(4, 0), hist_g(4, 0);
+    for (const uint4 &e : blk_tab_h) {
+      int g, l1, l2;
+      sp::key_shape((int)(e.z & 255u), &g, &l1, &l2);
+      hist_l1[(size_t)std::min(7, l1 / 4)]++; hist_l2[(size_t)(l2 / 8)]++; hist_g[(size_t)g]++;
+    }
+    std::fprintf(stderr, "[gmg] SGS step shapes: G %lld %lld %lld %lld | L1/4 %lld %lld %lld %lld %lld %lld %lld %lld | L2/8 %lld %lld %lld %lld\n", (long long)hist_g[0], (long long)hist_g[1],
+                 (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
+                 (long long)hist_l1[5], (long long)hist_l1[6], (long long)hist_l1[7], (long long)hist_l2[0], (long long)hist_l2[1], (long long)hist_l2[2], (long long)hist_l2[3]);
+    std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
+                 "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
+                 "four-wave", (long long)n, (long long)G.w_n_coupled, n_blocks, (long long)total_stages, (long long)n_steps, G.w_n_ranges,
+                 G.w_n_ranges - G.n_bwd, G.n_bwd, G.n_self, y_slots, live_max[0], live_max[1], (double)stream_size / 1e6);
+  }
+  return GMG_OK;
+}
+
+// The SSOR plan of a level whose CSR lies on the device (d_*) -- and, for gmg_set_level_matrix, on the host as well (rp64 / col /
+// val; col == nullptr: fetch() brings col and val back when the host builder needs them and returns the bytes it moved).
+template <class Fetch>
+int setup_sgs_any(gmg_context *ctx, Level &L, int64_t n, const int32_t *d_rp, const int32_t *d_col, const double *d_val, const int64_t *rp64,
+                  const int32_t *col, const double *val, const std::vector<int64_t> *explicit_rows, Fetch fetch) {
+  const char *reason = "";
+  int64_t moved = 0;
+  if (ctx->ssor_plan_device) {
+    CHK(setup_sgs_device(ctx, L, n, d_rp, d_col, d_val, explicit_rows, &reason));
+    if (!reason) {
+      if (ctx->debug_upload) {  // (the log's modelled block costs come from the host's cost model: the CSR comes back for that line alone)
+        if (!col) CHK(fetch(&col, &val, &moved));
+        L.sgs.csr_bytes_down = moved;
+        sgs_partition_log(ctx, L, n, rp64, col, val, L.sgs.host_block_row, explicit_rows != nullptr);
+      }
+      return GMG_OK;
+    }
+  }
+  if (!col) CHK(fetch(&col, &val, &moved));
+  CHK(setup_sgs(ctx, L, n, rp64, col, val, explicit_rows));
+  L.sgs.csr_bytes_down = moved;
+  L.sgs.host_reason = reason;
   return GMG_OK;
 }
 
@@ -2681,13 +3042,6 @@ int tile_device_csr(gmg_context *ctx, DevCSR &m, const std::vector<int32_t> &rp,
   CHK(launch_status(ctx));
   m.valid = true;
   return GMG_OK;
-}
-
-// grid of an assembly kernel: by size, at most `most` workgroups, capped by option assemble_max_blocks
-dim3 asm_blocks(const gmg_context *ctx, int64_t n, int per_block, int most = 1 << 16) {
-  int64_t g = std::max<int64_t>(1, std::min<int64_t>(most, (n + per_block - 1) / per_block));
-  if (ctx->assemble_max_blocks > 0) g = std::min<int64_t>(g, ctx->assemble_max_blocks);
-  return dim3((unsigned)g);
 }
 
 struct AsmScratch {  // lives until the stream has run the kernels
@@ -3008,7 +3362,30 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
   CHK(setup_diag(ctx, n_rows, rowptr, col, val, L.invd, &L.cheb_lmax));
   if (level > 0) {
     L.n = n_rows;  // (the SGS plan reads it)
-    CHK(setup_sgs(ctx, L, n_rows, rowptr, col, val, explicit_rows));
+    if (ctx->ssor_plan_device) {
+      // the device builder reads an int32 CSR: a copy of this call's arrays (upload_csr may have kept another layout)
+      DevPtr<int32_t> d_rp, d_col;
+      DevPtr<double> d_val;
+      if (!sgs_device_refusal(ctx, explicit_rows != nullptr) && n_rows > 0) {
+        if (rowptr[n_rows] > INT32_MAX) return fail(ctx, GMG_ERR_INVALID, "gmg_set_level_matrix: more than 2^31 entries");
+        const std::vector<int32_t> rp32(rowptr, rowptr + n_rows + 1);
+        HIPC(upload(d_rp, rp32, ctx->stream));
+        HIPC(upload(d_col, col, (size_t)rowptr[n_rows], ctx->stream));
+        HIPC(upload(d_val, val, (size_t)rowptr[n_rows], ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));  // (rp32 leaves scope)
+      }
+      const int rc_plan = setup_sgs_any(ctx, L, n_rows, d_rp.get(), d_col.get(), d_val.get(), rowptr, col, val, explicit_rows,
+                                        [](const int32_t **, const double **, int64_t *) { return (int)GMG_OK; });
+      if (rc_plan != GMG_OK) {  // (a plan that failed its checks, or a HIP error on the way: the level is left without an operator, never a new matrix with an old plan)
+        reset_keep_halo(L.A);
+        L.invd.reset();
+        L.cheb_lmax = 0.0;
+        L.sgs = SgsPlan();
+        return rc_plan;
+      }
+    } else {
+      CHK(setup_sgs(ctx, L, n_rows, rowptr, col, val, explicit_rows));
+    }
   }
   return finish_level(ctx, level, n_rows, n_cols, rowptr[n_rows]);
 }
@@ -5271,9 +5648,12 @@ static int assemble_level_device(gmg_context *ctx, const char *who, int level, i
   const int32_t *c_rp = m.rowptr.get(), *c_col = m.col.get();
   if (n_dofs) hipLaunchKernelGGL(asm_gershgorin_kernel, g_dofs, dim3(256), 0, ctx->stream, c_rp, c_col, (const double *)m.val.get(), n_dofs, d_lmax.get());
   hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, L.I.rowptr.get(), n_dofs);
-  // the host needs the CSR for the SSOR plan (setup_sgs) and the row pointers for the tilings
-  std::vector<int32_t> col_h((size_t)nnz), irp((size_t)n_dofs + 1), trp;
-  std::vector<double> val_h((size_t)nnz);
+  // the host needs the row pointers for the tilings and, unless the SSOR plan is formed on the device (option ssor_plan_device),
+  // the CSR for setup_sgs
+  std::vector<int32_t> col_h, irp((size_t)n_dofs + 1), trp;
+  std::vector<double> val_h;
+  const bool plan_on_host = level > 0 && !ctx->ssor_plan_device;
+  if (plan_on_host) { col_h.resize((size_t)nnz); val_h.resize((size_t)nnz); }
   unsigned long long lmax_bits = 0;
   HIPC(hipMemcpyAsync(irp.data(), L.I.rowptr.get(), sizeof(int32_t) * irp.size(), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipMemcpyAsync(&lmax_bits, d_lmax.get(), sizeof lmax_bits, hipMemcpyDeviceToHost, ctx->stream));
@@ -5298,7 +5678,7 @@ static int assemble_level_device(gmg_context *ctx, const char *who, int level, i
     HIPC(hipMemcpyAsync(trp.data(), L.It.rowptr.get(), sizeof(int32_t) * trp.size(), hipMemcpyDeviceToHost, ctx->stream));
   }
   HIPC(hipEventRecord(e1.get(), ctx->stream));
-  if (level > 0 && nnz) {
+  if (plan_on_host && nnz) {
     HIPC(hipMemcpyAsync(col_h.data(), m.col.get(), sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipMemcpyAsync(val_h.data(), m.val.get(), sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -5316,7 +5696,22 @@ static int assemble_level_device(gmg_context *ctx, const char *who, int level, i
   if (level > 0) {
     L.n = n_dofs;  // (the SGS plan reads it)
     const std::vector<int64_t> rp64(rp.begin(), rp.end());
-    CHK(setup_sgs(ctx, L, n_dofs, rp64.data(), col_h.data(), val_h.data(), explicit_rows));
+    if (plan_on_host) {
+      CHK(setup_sgs(ctx, L, n_dofs, rp64.data(), col_h.data(), val_h.data(), explicit_rows));
+      L.sgs.csr_bytes_down = 12 * nnz;
+    } else {
+      CHK(setup_sgs_any(ctx, L, n_dofs, m.rowptr.get(), m.col.get(), m.val.get(), rp64.data(), nullptr, nullptr, explicit_rows,
+                        [&](const int32_t **c, const double **v, int64_t *moved) {
+                          col_h.resize((size_t)nnz); val_h.resize((size_t)nnz);
+                          if (nnz) {
+                            HIPC(hipMemcpyAsync(col_h.data(), m.col.get(), sizeof(int32_t) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+                            HIPC(hipMemcpyAsync(val_h.data(), m.val.get(), sizeof(double) * (size_t)nnz, hipMemcpyDeviceToHost, ctx->stream));
+                            HIPC(hipStreamSynchronize(ctx->stream));
+                          }
+                          *c = col_h.data(); *v = val_h.data(); *moved = 12 * nnz;
+                          return (int)GMG_OK;
+                        }));
+    }
   }
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, e0.get(), e1.get()) != hipSuccess) ms = 0.f;
@@ -5973,6 +6368,7 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "ssor_balanced") ctx->ssor_partition = on ? GMG_SSOR_PARTITION_BALANCED : GMG_SSOR_PARTITION_ROWS;
   else if (k == "sgs_y_slots") ctx->sgs_y_slots = (int)value;
   else if (k == "sgs_sliding") ctx->sgs_sliding = on;
+  else if (k == "ssor_plan_device") ctx->ssor_plan_device = on;
   else if (k == "sgs_disable_wave") ctx->sgs_disable_wave = on;
   else if (k == "sgs_disable_phase") ctx->sgs_disable_phase = on;
   else if (k == "sgs_dep") ctx->sgs_dep = on;
@@ -6110,6 +6506,45 @@ int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int3
   if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_backward_rows: the level matrix has not been set");
   *count = G.wave ? (int64_t)G.host_bwd_rows.size() : 0;
   if (rows && G.wave) std::copy(G.host_bwd_rows.begin(), G.host_bwd_rows.end(), rows);
+  return GMG_OK;
+}
+
+int gmg_get_ssor_plan_array(gmg_context *ctx, int level, int which, int64_t *bytes, void *out) {
+  if (!ctx || !bytes || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const Level &L = ctx->lv[(size_t)level];
+  const SgsPlan &G = L.sgs;
+  if (G.host_block_row.empty() || !G.wave || !G.phased) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_plan_array: the level has no four-wave plan");
+  const void *src = nullptr;
+  int64_t len = 0;
+  switch (which) {
+    case GMG_SSOR_PLAN_STREAM: src = G.w_stream.get(); len = G.w_stream_bytes; break;
+    case GMG_SSOR_PLAN_RANGES: src = G.p_ranges.get(); len = (int64_t)sizeof(PhRange) * G.w_n_ranges; break;
+    case GMG_SSOR_PLAN_BLK_TAB: src = G.p_blk_tab.get(); len = 16 * G.w_steps; break;
+    case GMG_SSOR_PLAN_BLOCK_RNG: src = G.w_block_rng.get(); len = 4 * (int64_t)G.host_block_row.size(); break;
+    case GMG_SSOR_PLAN_ROW_CI: src = G.w_row_ci.get(); len = 4 * L.n; break;
+    case GMG_SSOR_PLAN_CI_ROW: src = G.w_ci_row.get(); len = 4 * G.w_n_coupled; break;
+    case GMG_SSOR_PLAN_RPOS_F: src = G.w_rpos_f.get(); len = 4 * G.w_n_coupled; break;
+    case GMG_SSOR_PLAN_RPOS_B: src = G.w_rpos_b.get(); len = 4 * G.w_n_coupled; break;
+    case GMG_SSOR_PLAN_ISO_DIAG: src = G.w_iso_diag.get(); len = 8 * L.n; break;
+    case GMG_SSOR_PLAN_ISO_INVD: src = G.w_iso_invd.get(); len = 8 * L.n; break;
+    default: return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_plan_array: unknown array");
+  }
+  if (!out) { *bytes = len; return GMG_OK; }
+  if (*bytes < len) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_plan_array: the buffer is too small");
+  *bytes = len;
+  (void)hipSetDevice(ctx->device);
+  if (len) HIPC(hipMemcpyAsync(out, src, (size_t)len, hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return GMG_OK;
+}
+
+int gmg_get_ssor_plan_origin(gmg_context *ctx, int level, int *on_device, int64_t *csr_bytes_downloaded, const char **reason) {
+  if (!ctx || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const SgsPlan &G = ctx->lv[(size_t)level].sgs;
+  if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_plan_origin: the level matrix has not been set");
+  if (on_device) *on_device = G.on_device ? 1 : 0;
+  if (csr_bytes_downloaded) *csr_bytes_downloaded = G.csr_bytes_down;
+  if (reason) *reason = G.host_reason;
   return GMG_OK;
 }
 

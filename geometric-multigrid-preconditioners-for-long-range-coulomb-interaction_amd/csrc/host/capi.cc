@@ -458,6 +458,11 @@ int step50_rhs_assembly_inputs(step50_problem *h, double *shape, double *weight,
 // ---- "Level matrices on device" (DESIGN.md section 17): what the driver hands to gmg_assemble_level_matrix for one level of
 // the current mesh.  sizes: dim, n_dofs, n_cells
 int step50_level_matrices_on_device(step50_problem *h) { return DISPATCH(h, levels_on_device) ? 1 : 0; }
+// "SSOR plan on device" (DESIGN.md section 26): gmg_get_ssor_plan_origin of the driver's context for one level >= 1
+int step50_ssor_plan_origin(step50_problem *h, int level, int *on_device, int64_t *csr_bytes_downloaded, const char **reason) {
+  gmg_context *g = DISPATCH(h, gmg);
+  return g ? gmg_get_ssor_plan_origin(g, level, on_device, csr_bytes_downloaded, reason) : GMG_ERR_INVALID;
+}
 int step50_level_assembly_sizes(step50_problem *h, int level, int64_t sizes[3]) {
   return guarded(h, [&] {
     if (level < 0 || level >= step50_n_levels(h)) throw std::runtime_error("level_assembly_inputs: no such level");

@@ -236,6 +236,9 @@ void ParameterReader::declare_parameters() {
             // cell matrix and the boundary / refinement-edge flags (gmg_assemble_level_matrix) instead of assembled here and
             // uploaded as CSR; one rank, DESIGN.md section 17 (Step16: section 18)
             {"Level matrices on device", "false"},
+            // the SSOR plan of every level >= 1 formed on the device from the level's CSR (option ssor_plan_device of the context)
+            // where the default four-wave plan applies, else by the host as without the key; DESIGN.md section 26
+            {"SSOR plan on device", "false"},
             // what stands behind mg_coarse: the reference's unpreconditioned CG (:962-967), or fast diagonalisation on the
             // level-0 lattice (gmg_set_coarse_solver; where level 0 does not qualify the CG stays), DESIGN.md section 15
             {"Coarse solver", "CG"},
@@ -361,6 +364,7 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.level0_matrix_on_device = prm.get_bool("Level 0 matrix on device");
   p.system_matrix_on_device = prm.get_bool("System matrix on device");
   p.level_matrices_on_device = prm.get_bool("Level matrices on device");
+  p.ssor_plan_on_device = prm.get_bool("SSOR plan on device");
   p.coarse_solver = prm.get("Coarse solver");
   if (p.coarse_solver != "CG" && p.coarse_solver != "direct") throw std::runtime_error("Coarse solver must be <CG> or <direct>");
   p.estimator_on_device = prm.get_bool("Error estimator on device");
@@ -1865,6 +1869,43 @@ int LaplaceProblem<dim>::ensure_context() {
   return GMG_OK;
 }
 
+// "SSOR plan on device": why the host planned a level after all, once per run and cause.  STEP50_CHECK_RESIDENT=1 holds the
+// eight numbers of gmg_get_ssor_plan of a device-planned level against a second, host-planned build of the same level.
+template <int dim>
+int LaplaceProblem<dim>::report_ssor_plan_origin(int l) {
+  int on_device = 0;
+  const char *why = "";
+  GMGC(gmg_get_ssor_plan_origin(gmg, l, &on_device, nullptr, &why));
+  if (!on_device) {
+    if (why[0] && ssor_plan_reasons_reported.insert(why).second) pcout(std::string("   SSOR plan on device: not applicable (") + why + "), planned on the host");
+    return GMG_OK;
+  }
+  const char *check = std::getenv("STEP50_CHECK_RESIDENT");
+  if (!check || check[0] != '1') return GMG_OK;
+  int64_t n_rows = 0, n_cols = 0, nnz = 0, dev_plan[8], host_plan[8];
+  GMGC(gmg_get_level_matrix(gmg, l, GMG_LEVEL_A, &n_rows, &n_cols, &nnz, nullptr, nullptr, nullptr));
+  std::vector<int64_t> rp((size_t)n_rows + 1);
+  std::vector<int32_t> col((size_t)std::max<int64_t>(nnz, 1));
+  std::vector<double> val((size_t)std::max<int64_t>(nnz, 1));
+  GMGC(gmg_get_level_matrix(gmg, l, GMG_LEVEL_A, &n_rows, &n_cols, &nnz, rp.data(), col.data(), val.data()));
+  GMGC(gmg_get_ssor_plan(gmg, l, dev_plan));
+  // (a context of its own: the level of this run keeps the operator and the plan it has)
+  gmg_context *second = nullptr;
+  const char *dev_env = std::getenv("STEP50_DEVICE");
+  if (gmg_create(&second, dev_env ? std::atoi(dev_env) : 0, l + 1) != GMG_OK) { last_error = "STEP50_CHECK_RESIDENT: no second context"; return GMG_ERR_HIP; }
+  int rc2 = gmg_set_option(second, "ssor_plan_device", 0.0);
+  if (rc2 == GMG_OK) rc2 = gmg_set_ssor_blocks(second, par.ssor_blocks > 0 ? par.ssor_blocks : 1);
+  if (rc2 == GMG_OK) rc2 = gmg_set_level_matrix(second, l, n_rows, n_cols, rp.data(), col.data(), val.data());
+  if (rc2 == GMG_OK) rc2 = gmg_get_ssor_plan(second, l, host_plan);
+  gmg_destroy(second);
+  if (rc2 != GMG_OK) { last_error = "STEP50_CHECK_RESIDENT: the host-planned second build of a level failed"; return rc2; }
+  for (int k = 0; k < 8; ++k)
+    if (dev_plan[k] != host_plan[k])
+      throw std::runtime_error("STEP50_CHECK_RESIDENT: the SSOR plan of level " + std::to_string(l) + " formed on the device differs from the host's (number " +
+                               std::to_string(k) + ": " + std::to_string(dev_plan[k]) + " against " + std::to_string(host_plan[k]) + ")");
+  return GMG_OK;
+}
+
 template <int dim>
 int LaplaceProblem<dim>::upload() {
   const int L = triangulation.n_levels();
@@ -1889,6 +1930,7 @@ int LaplaceProblem<dim>::upload() {
   GMGC(gmg_set_ssor_blocks(gmg, par.ssor_blocks > 0 ? par.ssor_blocks : std::max(1, distributed ? n_ranks : 1)));
   // (the default leaves the context's own setting: GMG_OPTIONS=ssor_balanced=1 measures the unchanged driver)
   if (par.ssor_partition == "balanced") GMGC(gmg_set_ssor_partition(gmg, GMG_SSOR_PARTITION_BALANCED));
+  if (par.ssor_plan_on_device) GMGC(gmg_set_option(gmg, "ssor_plan_device", 1.0));  // (unset: the context's own setting, as above)
   const CSRMatrix &S = system_matrix;
   const int64_t n_system = (int64_t)vertex_of_dof.size();
   if (system_on_device) {
@@ -2011,6 +2053,7 @@ int LaplaceProblem<dim>::upload() {
     const CSRMatrix &I = mg_interface_matrices[(size_t)l];
     if (!level_formed && I.nnz() > 0) GMGC(gmg_set_edge_matrix(gmg, l, I.n_rows, I.n_cols, I.rowptr.data(), I.col.data(), I.val.data()));
     GMGC(gmg_set_copy_indices(gmg, l, (int64_t)copy_global[(size_t)l].size(), copy_global[(size_t)l].data(), copy_level[(size_t)l].data()));
+    if (par.ssor_plan_on_device && l > 0) GMGC(report_ssor_plan_origin(l));
     if (l + 1 < L && transfer_on_device) {
       // P_l and its transpose are formed on the device from the vertex tables of the two levels
       std::vector<uint8_t> bnd(level_boundary[(size_t)l].begin(), level_boundary[(size_t)l].end());

@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <map>
 #include <memory>
+#include <set>
 #include <string>
 #include <unordered_map>
 
@@ -79,6 +80,7 @@ struct Parameters {
   bool transfer_on_device = true;       // gmg_build_transfer instead of building P_l here and uploading it
   bool level0_matrix_on_device = true;  // gmg_set_level_matrix_lattice instead of assembling + uploading level 0 (3D, constant coefficient, lexicographic, unpartitioned)
   bool system_matrix_on_device = false;  // gmg_assemble_system_matrix instead of assembling + uploading the active-mesh matrix (one rank; Step16: the _coef entry)
+  bool ssor_plan_on_device = false;  // option ssor_plan_device of the context: the SSOR plans of the levels >= 1 formed by kernels where that applies
   bool level_matrices_on_device = false;  // gmg_assemble_level_matrix instead of assembling + uploading A_l and I_l (one rank; Step16: the _coef entry)
   bool rhs_from_cell_tables = false;     // gmg_assemble_rhs instead of the sequential cell loop (and its gather plan), and constraints.distribute on the device (one rank)
   bool mesh_tables_on_device = false;    // gmg_build_mesh_tables instead of the sequential loops of distribute_dofs and make_constraints (cycle on the device, one rank)
@@ -192,6 +194,7 @@ class LaplaceProblem {
   void build_prolongation(int l);                                        // P_l on the host (the device builds it otherwise)
   void ensure_prolongation(int l);
   int ensure_context();                                                  // gmg_create (+ communicator) on first use
+  int report_ssor_plan_origin(int level);                                // "SSOR plan on device": the fallback line, the check against a host plan
   int upload();                                                          // hand the operators over the C-ABI
   int solve();                                                           // :938-1017
   void estimate_error_and_mark_cells();                                  // :1020-1090
@@ -280,6 +283,7 @@ class LaplaceProblem {
   bool solve_on_device_requested = false, level0_on_device = false, transfer_on_device = false;
   bool system_on_device = false;           // this cycle's system matrix is formed by gmg_assemble_system_matrix at upload()
   bool levels_on_device = false;           // this cycle's level and interface matrices are formed by gmg_assemble_level_matrix at upload()
+  std::set<std::string> ssor_plan_reasons_reported;  // "SSOR plan on device": the causes of host-built plans said so far (once per run and cause)
   bool levels_fallback_reported = false;   // "Level matrices on device" was set but not applicable: said once
   bool system_fallback_reported = false;   // "System matrix on device" was set but not applicable: said once
   bool rhs_from_cells = false;             // this cycle's right-hand side was formed by gmg_assemble_rhs

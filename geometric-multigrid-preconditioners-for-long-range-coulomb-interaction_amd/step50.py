@@ -86,6 +86,7 @@ def prm_text(**kw) -> str:
         "level0_on_device": ("Misc", "Level 0 matrix on device"),
         "system_matrix_on_device": ("Misc", "System matrix on device"),
         "level_matrices_on_device": ("Misc", "Level matrices on device"),
+        "ssor_plan_on_device": ("Misc", "SSOR plan on device"),
         "rhs_from_cell_tables": ("Misc", "RHS from cell tables"),
         "mesh_tables_on_device": ("Misc", "Mesh tables on device"),
         "operators_from_resident_tables": ("Misc", "Operators from resident tables"),
@@ -469,6 +470,14 @@ class Problem:
     def level_matrices_on_device(self) -> bool:
         """Did the last upload form the level and interface matrices on the device?"""
         return bool(self.L.step50_level_matrices_on_device(self.h))
+
+    def ssor_plan_origin(self, level):
+        """gmg_get_ssor_plan_origin of the last upload: (built on the device?, bytes of col / val downloaded for it, why the host built it or '')."""
+        on_dev, moved, why = C.c_int(0), C.c_int64(0), C.c_char_p()
+        rc = self.L.step50_ssor_plan_origin(self.h, C.c_int(level), C.byref(on_dev), C.byref(moved), C.byref(why))
+        if rc != 0:
+            raise RuntimeError(f"step50_ssor_plan_origin: level {level} has no plan (error {rc})")
+        return bool(on_dev.value), int(moved.value), (why.value or b"").decode()
 
     def refine_flags(self):
         """The refinement marks of the cycle just estimated, all levels concatenated (uint8)."""

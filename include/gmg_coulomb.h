@@ -910,6 +910,38 @@ int gmg_get_ssor_plan(gmg_context *ctx, int level, int64_t out[8]);
  * (0 without self-contained ranges); rows: count entries, may be NULL (call twice).  Each coupled row of each
  * self-contained block appears exactly once.                                                                       */
 int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int32_t *rows);
+/* Option ssor_plan_device (gmg_set_option / GMG_OPTIONS, default 0): the plan of a level >= 1 is formed by kernels from the
+ * level's CSR as it lies on the device, where the default four-wave plan with one self-contained range per direction in every
+ * block applies -- and is then the host builder's plan byte for byte (every array, header word and padding byte).  Where it
+ * does not apply (a communicator, the balanced partition, one of the sgs_* diagnostic options, unsorted columns, a row with
+ * more than 72 stored entries, a step no shape holds, a block whose live rows exceed the y slots, stream positions beyond
+ * 2^31) the WHOLE level is planned by the host builder as without the option; never a mix inside a level.  Both
+ * gmg_set_level_matrix and every gmg_assemble_level_matrix* take part; the latter then no longer copy col / val of the level
+ * matrix back to the host (except with option debug_upload, for the modelled block costs of its log).  A device-built plan is
+ * checked from its own arrays before it is accepted (block table inside the ranges, rows per step, shape keys, header links,
+ * LDS addresses below the y slots, aux words and rhs positions inside the stream / the level vector): on a miss the entry
+ * returns GMG_ERR_INVALID, the level is left without an operator and no sweep runs on that plan.
+ *   gmg_get_ssor_plan_array: one array of a level's four-wave plan as it lies on the device, host-built or device-built.
+ *     which: GMG_SSOR_PLAN_*.  out == NULL: *bytes <- the array's size.  Else *bytes is the capacity of out on entry
+ *     (GMG_ERR_INVALID if too small) and the size copied on return.  GMG_ERR_INVALID for a level without a four-wave plan.
+ *   gmg_get_ssor_plan_origin: who built the level's plan (*on_device 1 / 0), how many bytes of col / val came back to the host
+ *     for it (0 for a device-built plan from gmg_assemble_level_matrix*, and for gmg_set_level_matrix, whose caller holds
+ *     them), and, where the option was set and the host built it anyway, why -- one fixed text per cause: "communicator",
+ *     "balanced partition", "option <key> set" ("option sgs_sliding unset"), "unsorted columns", "row too wide", "no shape",
+ *     "block does not fit", "stream positions beyond 2^31", "empty level"; "" otherwise.  Any pointer may be NULL; the text
+ *     is static.                                                                                                          */
+#define GMG_SSOR_PLAN_STREAM 0
+#define GMG_SSOR_PLAN_RANGES 1
+#define GMG_SSOR_PLAN_BLK_TAB 2
+#define GMG_SSOR_PLAN_BLOCK_RNG 3
+#define GMG_SSOR_PLAN_ROW_CI 4
+#define GMG_SSOR_PLAN_CI_ROW 5
+#define GMG_SSOR_PLAN_RPOS_F 6
+#define GMG_SSOR_PLAN_RPOS_B 7
+#define GMG_SSOR_PLAN_ISO_DIAG 8
+#define GMG_SSOR_PLAN_ISO_INVD 9
+int gmg_get_ssor_plan_array(gmg_context *ctx, int level, int which, int64_t *bytes, void *out);
+int gmg_get_ssor_plan_origin(gmg_context *ctx, int level, int *on_device, int64_t *csr_bytes_downloaded, const char **reason);
 /* The slot allocator of the self-contained ranges for ONE block [row_begin, row_end) and one direction (backward: 0 / 1) of
  * a level matrix (host CSR, ascending columns, values required: stored zeros do not couple), without a context or a device:
  * the routine the plan uses.  Per row of the block (row_end - row_begin entries each, any may be NULL; -1 for a row without
