@@ -1023,6 +1023,10 @@ class Context:
         buf = C.create_string_buffer(uid, UNIQUE_ID_BYTES)
         self._chk(self.L.gmg_comm_init(self.h, C.c_int(rank), C.c_int(n_ranks), buf))
 
+    def comm_barrier(self):
+        """the ranks meet on the host: when the operators are set, before the first solve (gmg_comm_barrier)"""
+        self._chk(self.L.gmg_comm_barrier(self.h))
+
     def comm_info(self) -> dict:
         out = (C.c_int64 * 8)()
         self._chk(self.L.gmg_comm_info(self.h, out))

@@ -180,6 +180,25 @@ SSOR_VARIANTS = {"default": (), "sgs_reg": (("sgs_reg", 1),), "sgs_dep": (("sgs_
 VCYCLE_CONFIGS = [R.Config(kind=k, steps=s, degree=2 + (s % 2)) for k in (R.JACOBI, R.SSOR, R.CHEBYSHEV) for s in (1, 2, 3)]
 VCYCLE_CONFIGS.append(R.Config(kind=R.SSOR, steps=0))   # no smoothing at all: restrict, solve level 0, prolongate
 
+# tests/test_gpu_ranks_reference.py: on N ranks the SSOR sweep is split among the ranks where N divides the
+# number of blocks.  B = N and 2 N for N = 2, 3, a caller-given partition of N blocks with an empty block or a block of one row
+# (tests/rank_cases.given_bounds), and the V-cycle with one block per rank.
+RANK_BLOCKS = (2, 3, 4, 6)
+RANK_SMOOTH_LEVELS = [("A3", 1), ("A3", 2), ("B3", 1), ("B3", 2)]
+RANK_VCYCLE_CONFIGS = [R.Config(kind=R.SSOR, steps=s, degree=2 + (s % 2), blocks=b) for b in (2, 3) for s in (1, 2, 3)]
+
+
+def rank_smoother_configs(name, level):
+    import rank_cases as RC
+
+    n = hierarchy(name)[1].rows[level]
+    out = [R.Config(kind=R.SSOR, steps=s, blocks=b) for b in (1,) + RANK_BLOCKS for s in RC.MG_STEPS]
+    for n_ranks in RC.MG_RANKS:
+        out += [R.Config(kind=R.SSOR, steps=s, blocks=n_ranks, bounds=((level, bounds),)) for bounds in RC.given_bounds(n_ranks, n)
+                for s in RC.MG_STEPS]
+    return out
+
+
 # bits of gmg_stats.spmv0_layout that a switch takes away from an operator that has them all (include/gmg_coulomb.h).  The
 # lattice kernel needs the nine-run pattern and the value codes, not the pattern-run kernel: disable_sellp leaves it.
 LAYOUT_CLEARS = {"disable_sell": 63, "disable_patterns": 8 + 16 + 32, "disable_compression": 2 + 4 + 8 + 16 + 32, "disable_sellp": 8 + 16,

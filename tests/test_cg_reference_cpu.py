@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import cg_reference as R
+import rank_cases as RC
 from oracle import gmg_oracle as go
 from oracle import step50_oracle as so
 
@@ -108,6 +109,30 @@ def test_every_gpu_case_is_targetable_and_sensitive(case):
     scale = np.abs(ref.x).max()
     smallest = min(np.abs(s).max() for s in ref.steps)
     assert smallest > R.SENSITIVITY * tol_x * scale, (smallest / (tol_x * scale))
+
+
+@pytest.mark.parametrize("name,k", RC.coarse_pairs(), ids=lambda v: str(v))
+def test_every_rank_case_is_targetable_and_sensitive(name, k):
+    """the (operator, k) pairs tests/test_gpu_ranks_reference.py solves on a partitioned level 0 and gpu_cases() does not hold:
+    the same proof, with the same tolerance on x and the same SENSITIVITY (the spread S stays that of gpu_cases())"""
+    tol_x = RC.x_tolerance(name)
+    tol, ref = RC.stop_case(name, k)
+    for tier in R.TIERS:
+        r = RC.stop_case(name, k, tier)[1]
+        assert r.iterations == k and r.status == R.OK, (tier, r.iterations, r.status)
+        assert r.history[k] <= tol / R.MARGIN and r.history[:k].min() >= R.MARGIN * tol
+        assert np.abs(r.history - ref.history).max() <= 1e-9 * ref.history[0]
+        assert np.abs(r.x - ref.x).max() <= tol_x / R.X_TOL_FACTOR * np.abs(ref.x).max()
+    scale = np.abs(ref.x).max()
+    smallest = min(np.abs(s).max() for s in ref.steps)
+    assert smallest > R.SENSITIVITY * tol_x * scale, (smallest / (tol_x * scale))
+
+
+def test_rank_sequence_cases_are_those_of_gpu_cases():
+    """the sequence and the refused solve the ranks run on "csr" are cases of gpu_cases() already"""
+    have = set(R.gpu_cases())
+    for kind, k in R.SEQUENCE:
+        assert kind == "zero" or (kind, "csr", k, "identity", "zero") in have
 
 
 def test_converged_start_vector_case():

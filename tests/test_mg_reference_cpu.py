@@ -269,3 +269,47 @@ def test_vcycle_sensitivity(name):
             assert ratio >= R.SENSITIVITY, (cfg.label(), mut, ratio)
     print(f"\n[mg] V-cycle sensitivity {name} (difference / tolerance, best source, min over the configurations): "
           + ", ".join(f"{m} {v:.1e}" for m, v in sorted(low.items())))
+
+
+@pytest.mark.parametrize("name,level", K.RANK_SMOOTH_LEVELS)
+def test_rank_smoother_sensitivity(name, level):
+    """the SSOR partitions tests/test_gpu_ranks_reference.py sweeps on N ranks (B = N, 2 N, caller-given partitions with an empty
+    and a one-row block): the same mutations at the same SENSITIVITY.  A partition whose reference decouples nothing (one block
+    holds every row but one, or the level is too small for more than one block) cannot show ssor_coupled and is not asked to."""
+    H = K.hierarchy(name)[1]
+    u0, rhs = K.smoother_vectors(name, level)
+    low = {}
+    for cfg in K.rank_smoother_configs(name, level):
+        for from_zero in (True, False):
+            ref = K.smoother_reference(name, level, cfg, from_zero)
+            true = H.smooth("f64", cfg, level, u0, rhs, from_zero)
+            for mut in smoother_mutations(cfg, from_zero):
+                ratio = float(np.linalg.norm(H.smooth("f64", cfg.with_mut(mut), level, u0, rhs, from_zero) - true)) / ref.tol
+                low[mut] = min(low.get(mut, np.inf), ratio)
+                assert ratio >= R.SENSITIVITY, (cfg.label(), from_zero, mut, ratio)
+    print(f"\n[mg] rank smoother sensitivity {name} level {level} (difference / tolerance, min over the cases): "
+          + ", ".join(f"{m} {v:.1e}" for m, v in sorted(low.items())))
+
+
+@pytest.mark.parametrize("name", ["A3", "B3"])
+def test_rank_vcycle_sensitivity(name):
+    """the V-cycle with one SSOR block per rank (B = 2, 3): the oracle within tolerance and every mutation seen"""
+    h, H = K.hierarchy(name)
+    src, labels, dst0 = K.vcycle_sources(name)
+    low, worst = {}, 0.0
+    for cfg in K.RANK_VCYCLE_CONFIGS:
+        ref = K.vcycle_reference(name, cfg)
+        tol = ref.tol + H.cg_allowance(cfg, TAU)
+        o = oracle_mg(h, cfg)
+        for j, lab in enumerate(labels):
+            got, rc = o.vcycle(src[:, j])
+            err = float(np.linalg.norm(got - ref.ref[:, j]))
+            assert rc == 0 and err <= tol[j], (cfg.label(), lab, err, tol[j])
+            worst = max(worst, err / tol[j] if tol[j] > 0 else 0.0)
+        true = H.precondition("f64", cfg, src, dst0)
+        for mut in vcycle_mutations(name, cfg):
+            ratio = float((R.norm2(H.precondition("f64", cfg.with_mut(mut), src, dst0) - true) / tol).max())
+            low[mut] = min(low.get(mut, np.inf), ratio)
+            assert ratio >= R.SENSITIVITY, (cfg.label(), mut, ratio)
+    print(f"\n[mg] rank V-cycle {name}: oracle error / tolerance max {worst:.3f}; sensitivity (difference / tolerance, best source, min): "
+          + ", ".join(f"{m} {v:.1e}" for m, v in sorted(low.items())))
