@@ -42,7 +42,7 @@ SYMBOLS = [
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
     "gmg_vec_add", "gmg_vec_sadd", "gmg_vec_dot", "gmg_vec_norms", "gmg_vec_all_zero",
     "gmg_spmv", "gmg_precondition", "gmg_precondition_jacobi", "gmg_coarse_solve", "gmg_smoother_step",
-    "gmg_prolongate", "gmg_restrict_and_add", "gmg_cg_solve",
+    "gmg_prolongate", "gmg_restrict_and_add", "gmg_cg_solve", "gmg_cg_direction_step", "gmg_cg_update_step",
     "gmg_comm_unique_id", "gmg_comm_init", "gmg_comm_barrier", "gmg_comm_info", "gmg_set_halo_plan", "gmg_set_global_sizes", "gmg_partition_range",
     "gmg_vec_allgather",
     "gmg_stats_reset", "gmg_stats_get", "gmg_set_profiling", "gmg_set_tuning", "gmg_set_option", "gmg_set_ssor_blocks",
@@ -505,6 +505,16 @@ class Context:
         rc = self.L.gmg_cg_solve(self.h, x.ptr, b.ptr, C.c_double(rel_tol), C.c_int(max_it), C.c_int(precond),
                                  C.byref(it), C.byref(r0), C.byref(r))
         return {"iterations": it.value, "starting_value": r0.value, "convergence_value": r.value, "status": rc}
+
+    def cg_direction_step(self, d, g, h, first):
+        """first: d = -h; else d = beta d - h with beta = g.h / (the g.h of the previous call).  g.h stays in the context."""
+        self._chk(self.L.gmg_cg_direction_step(self.h, d.ptr, g.ptr, h.ptr, C.c_int64(d.n), C.c_int(1 if first else 0)))
+
+    def cg_update_step(self, x, g, d, h):
+        """alpha = (kept g.h) / d.h; x += alpha d; g += alpha h; returns g.g."""
+        gg = C.c_double(0)
+        self._chk(self.L.gmg_cg_update_step(self.h, x.ptr, g.ptr, d.ptr, h.ptr, C.c_int64(x.n), C.byref(gg)))
+        return gg.value
 
     # ---- forces on the atoms (gmg_forces.hpp)
     def set_point_locator(self, n0, origin, h0, node, active_dofs):

@@ -90,6 +90,14 @@ struct DevCSR {
   int64_t lat_fast_rows = 0;
   int lat_classes = 0, lat_nx = 0, lat_nxy = 0, lat_R0 = 0, lat_R1 = 0, lat_C = 0, lat_K = 0, lat_S = 0, lat_fast_blocks = 0, lat_n_gen = 0, lat_grid = 0;
   int64_t lat_gen_bytes = 0;  // stream bytes of the slices outside the interior
+  // hybrid layout (build_hybrid): y = A x reads the regular slices from SELL streams of their own and the rows of the other
+  // slices from the CSR copy above, in one launch (spmv_hybrid_kernel); every other mode uses the CSR copy
+  bool hyb = false, hyb_val8 = false;
+  DevPtr<int32_t> hyb_qptr, hyb_spat, hyb_pat, hyb_tiles, hyb_reg;
+  DevPtr<void> hyb_vals, hyb_cols;
+  DevPtr<double> hyb_dict;
+  int hyb_n_slices = 0, hyb_n_reg = 0, hyb_n_pattern_slices = 0, hyb_n_tiles = 0, hyb_tile_blocks = 0, hyb_grid = 0;
+  int64_t hyb_stream_bytes = 0, hyb_csr_bytes = 0;  // bytes one product streams: SELL part, CSR part
   int lat_nv[3] = {0, 0, 0};  // lat_only: what gmg_set_level_matrix_lattice was given (the direct coarse solver reads them)
   double lat_Ke[64] = {};
 };
@@ -138,6 +146,8 @@ struct Level {
   int64_t n_vec = 0;   // owned + ghost entries of a level vector
   int64_t n_copy = 0;
   DevPtr<int32_t> copy_g, copy_l;
+  std::vector<int32_t> host_copy_g, host_copy_l;  // the same lists on the host (mg_copy_tables)
+  int copy_version = 0;                           // counts gmg_set_copy_indices calls
   DevPtr<double> sol, def, t, w1, w2, w3;
   // distributed runs keep levels >= 1 replicated and level 0 row-partitioned: the V-cycle sees
   // level 0 through these full-length replicas: views of sol/def on a single GPU, of the two owners below when
@@ -259,6 +269,19 @@ struct gmg_context {
   DevPtr<double> part_a, part_b;  // reduction partials (4 * kMaxPartials each)
   DevPtr<double> scal_dev;        // 8 doubles
   HostPtr<double> scal_host;      // pinned, 8 doubles
+  // outer CG steps (gmg_cg_direction_step / gmg_cg_update_step): g.h stays on the device between the steps
+  DevPtr<double> ocg_dev;         // [0], [1]: g.h of this and of the previous iteration (ocg_cur names this one's); [2]: d.h
+  int ocg_cur = 0;
+  double ocg_gh = 0.0;            // g.h on the host (option disable_outer_cg_fused, several ranks)
+  // copy_to_mg / copy_from_mg as one kernel each (mg_copy_tables); option "disable_vcycle_fused": the memsets, gathers and the
+  // separate t = def - t of the coarse-level residual, as before
+  bool disable_vcycle_fused = false;
+  DevPtr<int32_t> mgcopy_to, mgcopy_from_level, mgcopy_from_row;
+  std::vector<int64_t> mgcopy_sig;  // what the tables were built for: n_sys, then (n_vec, n_copy, copy_version) per level
+  bool mgcopy_ok = false;
+  bool hybrid_two_launches = false;  // option "hybrid_two_launches": the CSR tiles and the SELL slices of a hybrid operator as two kernels (measured slower or equal: DESIGN.md section 28)
+  bool disable_hybrid = false;  // option "disable_hybrid": operators the SELL rule refuses stay on the CSR row-window kernel for y = A x too (checked at upload and at launch)
+  bool disable_outer_cg_fused = false;  // option "disable_outer_cg_fused": three host waits and six kernels per iteration, as before the fused steps
   HostPtr<int> sgs_abort;         // pinned, device-visible: set by the SSOR sweep if its wave protocol broke
   // tuning / measurement
   int coarse_chunk = 0;
@@ -428,8 +451,201 @@ int lattice_grid(const gmg_context *ctx, DevCSR &m, size_t n_gen) {
 // the lattice interior only needs the rows whose columns are owned (< n_rows): any n_cols >= n_rows qualifies
 inline int64_t n_cols_owned(int64_t n_rows, int64_t n_cols) { return n_cols >= n_rows ? n_rows : -1; }
 
+// Hybrid layout for an operator the SELL rule below refuses as a whole: slice by slice, a slice is
+// regular when its own padding passes the same 12 % bound (padded entries <= 1.12 x its entries; the width is that of its
+// column pattern where it has one).  Regular slices go into SELL streams -- 8-bit value codes if the REGULAR slices hold
+// <= 256 distinct values, no columns for pattern slices, 32-bit columns otherwise --, the rows of the other slices are
+// cut into row-window tiles of the CSR copy.  Not built (the operator stays as it is) when the regular slices hold less
+// than half of the entries: the product then streams more than 3/4 of the CSR bytes anyway.
+int build_hybrid(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val,
+                 const std::vector<int32_t> &slice_w, const std::vector<std::vector<int32_t>> &slice_delta) {
+  const int64_t n_slices = (n_rows + 63) / 64, nnz = rowptr[n_rows];
+  std::vector<int32_t> qp((size_t)n_slices + 1, 0), spat((size_t)n_slices, -1), reg;
+  std::vector<char> regular((size_t)n_slices, 0);
+  int64_t quads = 0, nnz_reg = 0, n_irr = 0;
+  for (int64_t sl = 0; sl < n_slices; ++sl) {
+    const int64_t rb = sl * 64, re = std::min<int64_t>(n_rows, rb + 64), ent = rowptr[re] - rowptr[rb];
+    const int64_t w = slice_delta[(size_t)sl].empty() ? slice_w[(size_t)sl] : (int64_t)slice_delta[(size_t)sl].size();
+    const int64_t nq = (w + 3) / 4;
+    if ((double)(nq * 256) <= 1.12 * (double)ent) {
+      regular[(size_t)sl] = 1;
+      reg.push_back((int32_t)sl);
+      quads += nq;
+      nnz_reg += ent;
+    } else {
+      ++n_irr;
+    }
+    qp[(size_t)sl + 1] = (int32_t)quads;
+  }
+  if (reg.empty() || n_irr == 0 || 2 * nnz_reg < nnz || quads == 0 || quads * 256 >= ((int64_t)1 << 31)) {
+    if (ctx->debug_upload)
+      std::fprintf(stderr, "[gmg]   hybrid not built: %lld of %lld slices regular, %lld of %lld entries in them\n", (long long)reg.size(), (long long)n_slices,
+                   (long long)nnz_reg, (long long)nnz);
+    return GMG_OK;
+  }
+  // column patterns of the regular slices
+  std::vector<std::vector<int32_t>> patterns;
+  std::map<std::vector<int32_t>, int> pattern_id;
+  int n_pattern_slices = 0;
+  for (int32_t sl : reg) {
+    if (slice_delta[(size_t)sl].empty()) continue;
+    auto ins = pattern_id.emplace(slice_delta[(size_t)sl], (int)patterns.size());
+    if (ins.second) patterns.push_back(slice_delta[(size_t)sl]);
+    spat[(size_t)sl] = ins.first->second;
+    ++n_pattern_slices;
+  }
+  // value dictionary over the regular slices (bit patterns; +0.0, the padding, is code 0): per chunk of slices in parallel
+  const int nt = host_threads();
+  std::vector<std::vector<uint64_t>> firsts((size_t)nt);
+  std::vector<char> overflow((size_t)nt, 0);
+  bool val8 = !ctx->disable_compression;
+  if (val8)
+    parallel_chunks((int64_t)reg.size(), [&](int64_t ib, int64_t ie, int t) {
+      std::unordered_map<uint64_t, int> seen;
+      uint64_t last = ~0ull;
+      for (int64_t i = ib; i < ie; ++i) {
+        const int64_t rb = (int64_t)reg[(size_t)i] * 64, re = std::min<int64_t>(n_rows, rb + 64);
+        for (int64_t k = rowptr[rb]; k < rowptr[re]; ++k) {
+          uint64_t bits;
+          std::memcpy(&bits, &val[k], 8);
+          if (bits == last) continue;
+          last = bits;
+          if (seen.emplace(bits, 0).second) {
+            firsts[(size_t)t].push_back(bits);
+            if (firsts[(size_t)t].size() > 256) { overflow[(size_t)t] = 1; return; }
+          }
+        }
+      }
+    });
+  std::vector<double> dict(1, 0.0);
+  std::unordered_map<uint64_t, int> code_of;
+  code_of.emplace(0ull, 0);
+  for (size_t t = 0; t < firsts.size() && val8; ++t) {
+    if (overflow[t]) val8 = false;
+    for (uint64_t bits : firsts[t]) {
+      if (!val8) break;
+      if (code_of.emplace(bits, (int)dict.size()).second) {
+        double v;
+        std::memcpy(&v, &bits, 8);
+        dict.push_back(v);
+        if (dict.size() > 256) val8 = false;
+      }
+    }
+  }
+  std::vector<uint64_t> ht_key(1024, 0);
+  std::vector<int16_t> ht_code(1024, -1);
+  auto ht_slot = [](uint64_t bits) { return (size_t)((bits * 0x9E3779B97F4A7C15ull) >> 54); };
+  if (val8)
+    for (const auto &kv : code_of) {
+      size_t h = ht_slot(kv.first);
+      while (ht_code[h] >= 0) h = (h + 1) & 1023;
+      ht_key[h] = kv.first; ht_code[h] = (int16_t)kv.second;
+    }
+  auto code_lookup = [&](uint64_t bits) -> uint8_t {
+    size_t h = ht_slot(bits);
+    while (ht_key[h] != bits || ht_code[h] < 0) h = (h + 1) & 1023;
+    return (uint8_t)ht_code[h];
+  };
+  // pack (the layouts of spmv_sell_kernel: values in double2 pairs or one code per entry, columns four per lane)
+  const size_t n_ent = (size_t)quads * 256;
+  std::vector<double> v2(val8 ? 0 : n_ent, 0.0);
+  std::vector<uint8_t> v1(val8 ? n_ent : 0, 0);
+  std::vector<int32_t> c4(n_ent, 0);
+  parallel_chunks((int64_t)reg.size(), [&](int64_t ib, int64_t ie, int) {
+    for (int64_t i = ib; i < ie; ++i) {
+      const int64_t sl = reg[(size_t)i], q0 = qp[(size_t)sl], nq = qp[(size_t)sl + 1] - q0;
+      const int64_t rb = sl * 64, re = std::min<int64_t>(n_rows, rb + 64);
+      const int32_t first_col = rowptr[re] > rowptr[rb] ? col[rowptr[rb]] : 0;  // (padding of lanes without a row: any valid column)
+      const int pidx = spat[(size_t)sl];
+      for (int lane = 0; lane < 64; ++lane) {
+        const int64_t r2 = rb + lane;
+        const int64_t k0 = r2 < n_rows ? rowptr[r2] : 0, len = r2 < n_rows ? rowptr[r2 + 1] - k0 : 0;
+        const int32_t padcol = r2 < std::min(n_rows, n_cols) ? (int32_t)r2 : first_col;
+        int64_t kk = 0;
+        for (int64_t j = 0; j < 4 * nq; ++j) {
+          const int64_t qq = q0 + j / 4, e = j & 3;
+          const size_t ov = (size_t)(((2 * qq + (e >> 1)) * 64 + lane) * 2 + (e & 1));
+          const size_t oc = (size_t)((qq * 64 + lane) * 4 + e);
+          int32_t cj;
+          double vj;
+          if (pidx >= 0) {
+            const auto &dl = patterns[(size_t)pidx];
+            if (j < (int64_t)dl.size() && kk < len && col[k0 + kk] - r2 == dl[(size_t)j]) { cj = col[k0 + kk]; vj = val[k0 + kk]; ++kk; }
+            else { cj = (int32_t)(j < (int64_t)dl.size() ? r2 + dl[(size_t)j] : r2); vj = 0.0; }
+          } else {
+            cj = j < len ? col[k0 + j] : padcol;
+            vj = j < len ? val[k0 + j] : 0.0;
+          }
+          if (val8) { uint64_t bits; std::memcpy(&bits, &vj, 8); v1[oc] = code_lookup(bits); }
+          else v2[ov] = vj;
+          c4[oc] = cj;
+        }
+      }
+    }
+  });
+  // row-window tiles over the runs of irregular slices (the rule of upload_csr's tiles)
+  std::vector<int32_t> tiles;
+  for (int64_t sl = 0; sl < n_slices;) {
+    if (regular[(size_t)sl]) { ++sl; continue; }
+    int64_t se = sl;
+    while (se < n_slices && !regular[(size_t)se]) ++se;
+    const int64_t run_end = std::min<int64_t>(n_rows, se * 64);
+    for (int64_t r = sl * 64; r < run_end;) {
+      const int64_t ka = rowptr[r] & ~(int64_t)3;
+      int64_t e = r + 1;
+      while (e < run_end && rowptr[e + 1] - ka <= kTileNnz && e - r < kTileMaxRowsEarly) ++e;
+      if (rowptr[e] - ka > kTileNnz) e = r + 1;
+      tiles.push_back((int32_t)r);
+      tiles.push_back((int32_t)e);
+      r = e;
+    }
+    sl = se;
+  }
+  dict.resize(256, 0.0);
+  std::vector<int32_t> table(std::max<size_t>(patterns.size(), 1) * 32, 0);
+  for (size_t pi = 0; pi < patterns.size(); ++pi)
+    for (size_t j = 0; j < patterns[pi].size(); ++j) table[pi * 32 + j] = patterns[pi][j];
+  const size_t vbytes = val8 ? v1.size() : v2.size() * 8, cbytes = c4.size() * 4;
+  HIPC(m.hyb_qptr.alloc(qp.size()));
+  HIPC(m.hyb_spat.alloc(spat.size()));
+  HIPC(m.hyb_pat.alloc(table.size()));
+  HIPC(m.hyb_tiles.alloc(tiles.size()));
+  HIPC(m.hyb_reg.alloc(reg.size()));
+  HIPC(m.hyb_dict.alloc(256));
+  HIPC(m.hyb_vals.alloc_bytes(vbytes + 64));
+  HIPC(m.hyb_cols.alloc_bytes(cbytes + 64));
+  HIPC(hipMemcpyAsync(m.hyb_qptr.get(), qp.data(), sizeof(int32_t) * qp.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_spat.get(), spat.data(), sizeof(int32_t) * spat.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_pat.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_tiles.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_reg.get(), reg.data(), sizeof(int32_t) * reg.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_dict.get(), dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_vals.get(), val8 ? (const void *)v1.data() : (const void *)v2.data(), vbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(m.hyb_cols.get(), c4.data(), cbytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  m.hyb_val8 = val8;
+  m.hyb_n_slices = (int)n_slices; m.hyb_n_reg = (int)reg.size(); m.hyb_n_pattern_slices = n_pattern_slices;
+  m.hyb_n_tiles = (int)(tiles.size() / 2);
+  // as many workgroups of each kind as are resident at 4 per CU (the 32 KiB row window): two rounds at the most
+  m.hyb_tile_blocks = 8 * (int)std::min<int64_t>(128, std::max<int64_t>(1, (m.hyb_n_tiles + 7) / 8));
+  const int sell_blocks = 8 * (int)std::min<int64_t>(128, std::max<int64_t>(1, ((int64_t)reg.size() + 63) / 64));
+  m.hyb_grid = m.hyb_tile_blocks + sell_blocks;
+  int64_t streamed_cols = 0;
+  for (int32_t sl : reg)
+    if (spat[(size_t)sl] < 0) streamed_cols += (int64_t)(qp[(size_t)sl + 1] - qp[(size_t)sl]) * 256;
+  m.hyb_stream_bytes = (int64_t)n_ent * (val8 ? 1 : 8) + 4 * streamed_cols + 12 * (int64_t)reg.size();
+  m.hyb_csr_bytes = 12 * (nnz - nnz_reg) + 8 * (int64_t)m.hyb_n_tiles + 4 * ((int64_t)n_irr * 64 + m.hyb_n_tiles);
+  m.hyb = true;
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg]   layout hybrid: %d of %d slices regular (%d pattern slices, %zu patterns), %lld of %lld entries in them padded to %lld, val8 %d (%zu values); "
+                 "%d csr tiles; bytes per product: sell %lld + csr %lld (csr alone %lld); grid %d + %d\n", m.hyb_n_reg, m.hyb_n_slices, n_pattern_slices, patterns.size(),
+                 (long long)nnz_reg, (long long)nnz, (long long)n_ent, (int)val8, code_of.size(), m.hyb_n_tiles, (long long)m.hyb_stream_bytes, (long long)m.hyb_csr_bytes,
+                 (long long)(12 * nnz + 4 * (n_rows + 1)), m.hyb_tile_blocks, sell_blocks);
+  return GMG_OK;
+}
+
 int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col,
-               const double *val, bool keep_csr = false) {
+               const double *val, bool keep_csr = false, bool allow_hybrid = false) {
   if (n_rows < 0 || n_cols < 0 || !rowptr) return fail(ctx, GMG_ERR_INVALID, "upload_csr: bad arguments");
   const int64_t nnz = rowptr[n_rows];
   if (nnz >= (int64_t)1 << 31 || n_rows >= (int64_t)1 << 31 || n_cols >= (int64_t)1 << 31)
@@ -537,8 +753,8 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
       quads += (w + 3) / 4;
       sp[(size_t)sidx + 1] = (int32_t)quads;
     }
-    slice_delta.clear();
     if (quads * 256 <= (int64_t)(1.12 * (double)nnz) && quads * 256 < ((int64_t)1 << 31)) {
+      slice_delta.clear();
       phase("patterns");
       // --- value dictionary (bit patterns, so -0.0 / NaN payloads survive)
       const bool allow_comp = !ctx->disable_compression;
@@ -945,6 +1161,10 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
       if (!keep_csr) {  // the CSR copy is only kept where the SGS sweeps need it (levels >= 1)
         m.col.reset(); m.val.reset(); m.tile_row.reset();
       }
+    } else if (allow_hybrid && !ctx->disable_hybrid && !m.halo.active) {  // (the system matrix only: its product is the one that is HBM bound)
+      phase("patterns");
+      CHK(build_hybrid(ctx, m, n_rows, n_cols, rowptr, col, val, slice_w, slice_delta));
+      phase("hybrid pack+copy");
     }
   }
   phase("finish");
@@ -952,6 +1172,7 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
     std::fprintf(stderr, "[gmg] operator %lld x %lld nnz %lld: tiles %d grid %d sell %d val8 %d col16 %d sell_grid %d patterns %d pattern_slices %d/%d\n", (long long)n_rows,
                  (long long)n_cols, (long long)nnz, m.n_tiles, m.grid, (int)m.sell, (int)m.val8, (int)m.col16, m.sell_grid, m.n_patterns, m.n_pattern_slices, m.n_slices);
   if (ctx->debug_upload && m.rowclass) std::fprintf(stderr, "[gmg]   row classes of the run-pattern slices: %d\n", m.n_classes);
+  if (ctx->debug_upload && !m.hyb) std::fprintf(stderr, "[gmg]   layout %s\n", m.sell ? "sell" : "csr");
   return GMG_OK;
 }
 
@@ -1033,6 +1254,24 @@ int launch_op(gmg_context *ctx, const DevCSR &m, const SpmvArgs &a) {
     else if (m.col16) launch_timed(ctx, spmv_sell_kernel<MODE, CG, false, true>, dim3(m.sell_grid), dim3(kThreads), 0, sa);
     else launch_timed(ctx, spmv_sell_kernel<MODE, CG, false, false>, dim3(m.sell_grid), dim3(kThreads), 0, sa);
     return m.sell_grid;
+  }
+  if constexpr (MODE == kStore && CG == 0) {
+    if (m.hyb && !a.init && !ctx->disable_hybrid) {
+      HybArgs h{};
+      h.sa = SellArgs{m.hyb_qptr.get(), nullptr, m.hyb_vals.get(), m.hyb_cols.get(), m.hyb_dict.get(), m.hyb_spat.get(), m.hyb_pat.get(), m.hyb_n_slices, (int)m.n_rows, a};
+      h.tiles = m.hyb_tiles.get(); h.reg = m.hyb_reg.get(); h.n_tiles = m.hyb_n_tiles; h.n_reg = m.hyb_n_reg; h.tile_blocks = m.hyb_tile_blocks;
+      if (ctx->hybrid_two_launches) {  // (measurement: the SELL workgroups without the row window's 32 KiB of LDS)
+        HybArgs t = h, q = h;
+        q.tile_blocks = 0;
+        launch_timed(ctx, spmv_hybrid_kernel<true, 1>, dim3(m.hyb_tile_blocks), dim3(kThreads), 0, t);
+        if (m.hyb_val8) hipLaunchKernelGGL((spmv_hybrid_kernel<true, 2>), dim3(m.hyb_grid - m.hyb_tile_blocks), dim3(kThreads), 0, ctx->stream, q);
+        else hipLaunchKernelGGL((spmv_hybrid_kernel<false, 2>), dim3(m.hyb_grid - m.hyb_tile_blocks), dim3(kThreads), 0, ctx->stream, q);
+        return m.hyb_grid;
+      }
+      if (m.hyb_val8) launch_timed(ctx, spmv_hybrid_kernel<true, 0>, dim3(m.hyb_grid), dim3(kThreads), 0, h);
+      else launch_timed(ctx, spmv_hybrid_kernel<false, 0>, dim3(m.hyb_grid), dim3(kThreads), 0, h);
+      return m.hyb_grid;
+    }
   }
   launch_timed(ctx, spmv_tile_kernel<MODE, CG>, dim3(m.grid), dim3(kThreads), 0, a);
   return m.grid;
@@ -1135,14 +1374,24 @@ int sgs_profile_launch(gmg_context *ctx, Level &L, SgsWaveArgs p) {
   return GMG_OK;
 }
 
-int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r) {
+// the pre-pass operands of a level's sweep for the epilogue of its residual product (spmv_tile_kernel<kResidPre, 0>)
+SgsPreArgs sgs_pre_args(const gmg_context *ctx, const Level &L, double *y) {
+  SgsPreArgs q{};
+  q.row_ci = L.sgs.w_row_ci.get(); q.rpos_f = L.sgs.w_rpos_f.get(); q.rpos_b = L.sgs.w_rpos_b.get();
+  q.iso_diag = L.sgs.w_iso_diag.get(); q.iso_invd = L.sgs.w_iso_invd.get();
+  q.stream = reinterpret_cast<double *>(L.sgs.w_stream.get()); q.ycur = L.sgs.w_ycur.get(); q.y = y; q.omega = ctx->omega;
+  return q;
+}
+
+// prepass_done: r was produced by the level's residual product with the pre-pass in its epilogue (smooth_level)
+int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r, bool prepass_done = false) {
   if (L.sgs.wave) {
     SgsWaveArgs p{};
     p.ranges = L.sgs.w_ranges.get(); p.block_rng = L.sgs.w_block_rng.get(); p.stream = L.sgs.w_stream.get(); p.ws_ci = L.sgs.w_ws_ci.get();
     p.ci_row = L.sgs.w_ci_row.get(); p.ycur = L.sgs.w_ycur.get(); p.y = y; p.omega = ctx->omega; p.y_slots = L.sgs.w_y_slots;
     p.row_ci = L.sgs.w_row_ci.get(); p.rpos_f = L.sgs.w_rpos_f.get(); p.rpos_b = L.sgs.w_rpos_b.get(); p.iso_diag = L.sgs.w_iso_diag.get();
     p.iso_invd = L.sgs.w_iso_invd.get(); p.r = r; p.n_rows = L.n; p.abort_flag = ctx->sgs_abort.get();
-    hipLaunchKernelGGL(sgs_wave_prepass_kernel, dim3(grid_for(L.n)), dim3(256), 0, ctx->stream, p);
+    if (!prepass_done) hipLaunchKernelGGL(sgs_wave_prepass_kernel, dim3(grid_for(L.n)), dim3(256), 0, ctx->stream, p);
     // one process per GPU: the blocks are what the reference's ranks sweep -- each rank sweeps its share of them and
     // the pieces of y are all-gathered (levels >= 1 are replicated: every rank needs the whole vector)
     const int n_ranks = ctx->dist ? ctx->comm.n_ranks : 1;
@@ -1328,9 +1577,20 @@ int smooth_level(gmg_context *ctx, int l, DevPtr<double> &u_io, const double *rh
       launch_spmv_mode<kJacobi>(ctx, L.A, a);
       std::swap(u, spare);
     } else {
-      CHK(spmv(ctx, L.A, kResid, u, L.t.get(), nullptr, rhs));  // r = rhs - A u
+      // SSOR on the row-window kernel: the sweep's pre-pass (r into the record stream, the closed form of rows without
+      // couplings) rides in the epilogue of the product that forms r
+      const bool pre = ctx->smoother == GMG_SMOOTHER_SSOR && L.sgs.wave && !ctx->dist && !ctx->disable_vcycle_fused && L.A.valid && !L.A.sell &&
+                       !L.A.lat_only && !L.A.halo.active && L.A.n_rows == L.n;
+      if (pre) {
+        SpmvArgs a = base_args(L.A, u, L.t.get());
+        a.b = rhs; a.pre = sgs_pre_args(ctx, L, L.w1.get());
+        launch_timed(ctx, spmv_tile_kernel<kResidPre, 0>, dim3(L.A.grid), dim3(kThreads), 0, a);
+        CHK(launch_status(ctx));
+      } else {
+        CHK(spmv(ctx, L.A, kResid, u, L.t.get(), nullptr, rhs));  // r = rhs - A u
+      }
       if (ctx->smoother == GMG_SMOOTHER_SSOR) {
-        CHK(sgs_apply(ctx, L, L.w1.get(), L.t.get()));
+        CHK(sgs_apply(ctx, L, L.w1.get(), L.t.get(), pre));
         hipLaunchKernelGGL(vec_add_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, u, 1.0, (const double *)L.w1.get(), L.n);
       } else {
         double *y = nullptr;
@@ -1621,8 +1881,14 @@ int level_v_step(gmg_context *ctx, int l) {
   CHK(smooth_level(ctx, l, L.sol, L.def.get(), true, L.w1));  // pre_smooth->apply (Jacobi may swap sol <-> w1)
   if (L.has_I) {
     CHK(spmv(ctx, L.A, kStore, L.sol.get(), L.t.get()));                 // t = A u
-    CHK(spmv(ctx, L.I, kStore, L.sol.get(), L.t.get(), L.t.get()));            // edge_out->vmult_add
-    hipLaunchKernelGGL(vec_sadd_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, L.t.get(), -1.0, 1.0, (const double *)L.def.get(), L.n);
+    if (!ctx->dist && !ctx->disable_vcycle_fused) {
+      // edge_out->vmult_add and t.sadd(-1, 1, defect) in the product's epilogue: row by row t = defect - (t + I u), the same
+      // two additions in the same order (-t + defect and defect - t are the same IEEE operation)
+      CHK(spmv(ctx, L.I, kResid, L.sol.get(), L.t.get(), L.t.get(), L.def.get()));
+    } else {
+      CHK(spmv(ctx, L.I, kStore, L.sol.get(), L.t.get(), L.t.get()));            // edge_out->vmult_add
+      hipLaunchKernelGGL(vec_sadd_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, L.t.get(), -1.0, 1.0, (const double *)L.def.get(), L.n);
+    }
   } else {
     CHK(spmv(ctx, L.A, kResid, L.sol.get(), L.t.get(), nullptr, L.def.get()));  // t = defect - A u
   }
@@ -1637,6 +1903,44 @@ int level_v_step(gmg_context *ctx, int l) {
   return GMG_OK;
 }
 
+// Inverse indices of the levels' copy lists for mg_copy_to_kernel / mg_copy_from_kernel, rebuilt when a list, a level size or
+// the system size changed.  mgcopy_ok stays false (the V-cycle then copies list by list) when an index lies outside its
+// vector or there are more than kMgMaxLevels levels.
+int mg_copy_tables(gmg_context *ctx) {
+  std::vector<int64_t> sig{ctx->S.n_rows};
+  for (const Level &L : ctx->lv) { sig.push_back(L.n_vec); sig.push_back(L.n_copy); sig.push_back(L.copy_version); }
+  if (sig == ctx->mgcopy_sig) return GMG_OK;
+  ctx->mgcopy_sig = sig;
+  ctx->mgcopy_ok = false;
+  const int64_t n_sys = ctx->S.n_rows;
+  if (ctx->n_levels > kMgMaxLevels) return GMG_OK;
+  int64_t total = 0;
+  for (const Level &L : ctx->lv) total += L.n_vec;
+  std::vector<int32_t> to((size_t)std::max<int64_t>(total, 1), -1), from_level((size_t)std::max<int64_t>(n_sys, 1), -1), from_row((size_t)std::max<int64_t>(n_sys, 1), 0);
+  int64_t off = 0;
+  for (int l = 0; l < ctx->n_levels; ++l) {  // (ascending, as the loops of vcycle: a system DoF on two levels takes the later one)
+    const Level &L = ctx->lv[(size_t)l];
+    if ((int64_t)L.host_copy_g.size() != L.n_copy) return GMG_OK;
+    for (int64_t k = 0; k < L.n_copy; ++k) {
+      const int64_t g = L.host_copy_g[(size_t)k], r = L.host_copy_l[(size_t)k];
+      if (g < 0 || g >= n_sys || r < 0 || r >= L.n_vec) return GMG_OK;
+      to[(size_t)(off + r)] = (int32_t)g;
+      from_level[(size_t)g] = l;
+      from_row[(size_t)g] = (int32_t)r;
+    }
+    off += L.n_vec;
+  }
+  HIPC(ctx->mgcopy_to.alloc(to.size()));
+  HIPC(ctx->mgcopy_from_level.alloc(from_level.size()));
+  HIPC(ctx->mgcopy_from_row.alloc(from_row.size()));
+  HIPC(hipMemcpyAsync(ctx->mgcopy_to.get(), to.data(), sizeof(int32_t) * to.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(ctx->mgcopy_from_level.get(), from_level.data(), sizeof(int32_t) * from_level.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(ctx->mgcopy_from_row.get(), from_row.data(), sizeof(int32_t) * from_row.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));  // (the host tables die here)
+  ctx->mgcopy_ok = true;
+  return GMG_OK;
+}
+
 int vcycle(gmg_context *ctx, double *dst, const double *src) {
   if (!ctx->S.valid) return fail(ctx, GMG_ERR_INVALID, "system matrix not set");
   const double *src_v = src;
@@ -1648,7 +1952,25 @@ int vcycle(gmg_context *ctx, double *dst, const double *src) {
     dst_v = ctx->sys_full_b.get();
     n_sys = ctx->sys_global;
   }
-  for (int l = 0; l < ctx->n_levels; ++l) {  // copy_to_mg
+  bool fused = !ctx->dist && !ctx->disable_vcycle_fused;
+  if (fused) {
+    CHK(mg_copy_tables(ctx));
+    fused = ctx->mgcopy_ok;
+  }
+  MgCopyArgs mc{};
+  if (fused) {
+    mc.n_levels = ctx->n_levels; mc.to = ctx->mgcopy_to.get(); mc.src = src_v;
+    mc.from_level = ctx->mgcopy_from_level.get(); mc.from_row = ctx->mgcopy_from_row.get(); mc.dst = dst_v; mc.n_sys = n_sys;
+    for (int l = 0; l < ctx->n_levels; ++l) {
+      Level &L = ctx->lv[(size_t)l];
+      if (!L.A.valid) return fail(ctx, GMG_ERR_INVALID, "level matrix not set");
+      mc.def[l] = (l == 0) ? L.def_full : L.def.get();
+      mc.sol[l] = L.sol.get();
+      mc.off[l + 1] = mc.off[l] + L.n_vec;
+    }
+    if (mc.off[ctx->n_levels] > 0) hipLaunchKernelGGL(mg_copy_to_kernel, dim3(grid_for(mc.off[ctx->n_levels])), dim3(kThreads), 0, ctx->stream, mc);
+  }
+  for (int l = 0; l < ctx->n_levels && !fused; ++l) {  // copy_to_mg
     Level &L = ctx->lv[(size_t)l];
     if (!L.A.valid) return fail(ctx, GMG_ERR_INVALID, "level matrix not set");
     double *def = (l == 0) ? L.def_full : L.def.get();
@@ -1660,8 +1982,13 @@ int vcycle(gmg_context *ctx, double *dst, const double *src) {
                          (const int32_t *)L.copy_l.get(), src_v, (const int32_t *)L.copy_g.get(), L.n_copy);
   }
   CHK(level_v_step(ctx, ctx->n_levels - 1));
-  HIPC(hipMemsetAsync(dst_v, 0, sizeof(double) * (size_t)n_sys, ctx->stream));  // copy_from_mg: dst = 0
-  for (int l = 0; l < ctx->n_levels; ++l) {
+  if (fused) {  // (the levels' solutions: read after the cycle, Jacobi swaps sol <-> w1)
+    for (int l = 0; l < ctx->n_levels; ++l) mc.sol[l] = (l == 0) ? ctx->lv[0].sol_full : ctx->lv[(size_t)l].sol.get();
+    if (n_sys > 0) hipLaunchKernelGGL(mg_copy_from_kernel, dim3(grid_for(n_sys)), dim3(kThreads), 0, ctx->stream, mc);
+  } else {
+    HIPC(hipMemsetAsync(dst_v, 0, sizeof(double) * (size_t)n_sys, ctx->stream));  // copy_from_mg: dst = 0
+  }
+  for (int l = 0; l < ctx->n_levels && !fused; ++l) {
     Level &L = ctx->lv[(size_t)l];
     const double *sol = (l == 0) ? L.sol_full : L.sol.get();
     if (L.n_copy)
@@ -3220,6 +3547,7 @@ int gmg_create(gmg_context **out, int device_id, int n_levels) {
   if (ctx->part_b.alloc(4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->scal_dev.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->scal_host.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->ocg_dev.alloc(4) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->sgs_abort.alloc(1) != hipSuccess) return bail(GMG_ERR_HIP);
   *ctx->sgs_abort.get() = 0;
   (void)hipMemsetAsync(ctx->st.get(), 0, sizeof(CGState), ctx->stream);
@@ -3285,7 +3613,7 @@ int gmg_set_system_matrix(gmg_context *ctx, int64_t n_rows, int64_t n_cols, cons
                           const double *val) {
   if (!ctx) return GMG_ERR_INVALID;
   (void)hipSetDevice(ctx->device);
-  CHK(upload_csr(ctx, ctx->S, n_rows, n_cols, rowptr, col, val));
+  CHK(upload_csr(ctx, ctx->S, n_rows, n_cols, rowptr, col, val, false, true));
   CHK(setup_diag(ctx, n_rows, rowptr, col, val, ctx->S_invd, nullptr));
   CHK(alloc_vec(ctx, ctx->S_tmp, n_cols));
   if (ctx->dist) {
@@ -3657,12 +3985,23 @@ int gmg_set_copy_indices(gmg_context *ctx, int level, int64_t n, const int32_t *
   Level &L = ctx->lv[(size_t)level];
   L.copy_g.reset(); L.copy_l.reset();
   L.n_copy = n;
-  if (n == 0) return GMG_OK;
-  HIPC(L.copy_g.alloc((size_t)n));
-  HIPC(L.copy_l.alloc((size_t)n));
-  HIPC(hipMemcpyAsync(L.copy_g.get(), global_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.copy_l.get(), level_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
+  L.copy_version++;
+  L.host_copy_g.assign(global_idx, global_idx + (n ? n : 0));
+  L.host_copy_l.assign(level_idx, level_idx + (n ? n : 0));
+  if (n > 0) {
+    HIPC(L.copy_g.alloc((size_t)n));
+    HIPC(L.copy_l.alloc((size_t)n));
+    HIPC(hipMemcpyAsync(L.copy_g.get(), global_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(L.copy_l.get(), level_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+  }
+  // the inverse indices of the fused copies are part of the upload: built with the finest level's list, the last one a
+  // hierarchy is given (any other order: the first V-cycle builds them)
+  if (level == ctx->n_levels - 1 && ctx->S.valid && !ctx->dist) {
+    bool complete = true;
+    for (const Level &K : ctx->lv) complete = complete && K.A.valid;
+    if (complete) CHK(mg_copy_tables(ctx));
+  }
   return GMG_OK;
 }
 
@@ -3887,6 +4226,62 @@ int gmg_restrict_and_add(gmg_context *ctx, int level, double *dst_coarse, const 
   return spmv(ctx, L.Pt, kStore, src_fine, dst_coarse, dst_coarse);
 }
 
+// ---- the two steps of one outer CG iteration around the preconditioner ----
+// One rank, option disable_outer_cg_fused off: g.h lives in ocg_dev between the steps, alpha and beta are formed on the
+// device, and only |g|^2 (SolverControl's check) comes back to the host.  Otherwise: the calls these steps replace.
+
+int gmg_cg_direction_step(gmg_context *ctx, double *d, const double *g, const double *h, int64_t n, int first) {
+  if (!ctx || !d || !g || !h || n < 0) return GMG_ERR_INVALID;
+  const int gr = grid_for(n);
+  if (ctx->dist || ctx->comm.n_ranks > 1 || ctx->disable_outer_cg_fused) {
+    if (first) {
+      hipLaunchKernelGGL(vec_equ_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, d, -1.0, h, n);
+      return dot_host(ctx, g, h, n, &ctx->ocg_gh);
+    }
+    double beta = ctx->ocg_gh;
+    CHK(dot_host(ctx, g, h, n, &ctx->ocg_gh));
+    beta = ctx->ocg_gh / beta;
+    hipLaunchKernelGGL(vec_sadd_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, d, beta, -1.0, h, n);
+    RETURN_LAUNCHED(ctx);
+  }
+  double *const s = ctx->ocg_dev.get();
+  if (first) {
+    hipLaunchKernelGGL(vec_equ_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, d, -1.0, h, n);
+    ctx->ocg_cur = 0;
+  } else {
+    ctx->ocg_cur ^= 1;
+  }
+  hipLaunchKernelGGL(dot_partial_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, g, h, n, ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), gr, 1, 0u, s + ctx->ocg_cur);
+  if (!first)
+    hipLaunchKernelGGL(cg_outer_direction_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, d, h, n, (const double *)(s + ctx->ocg_cur),
+                       (const double *)(s + (ctx->ocg_cur ^ 1)), -1.0);
+  RETURN_LAUNCHED(ctx);
+}
+
+int gmg_cg_update_step(gmg_context *ctx, double *x, double *g, const double *d, const double *h, int64_t n, double *gg) {
+  if (!ctx || !x || !g || !d || !h || !gg || n < 0) return GMG_ERR_INVALID;
+  const int gr = grid_for(n);
+  if (ctx->dist || ctx->comm.n_ranks > 1 || ctx->disable_outer_cg_fused) {
+    double alpha = 0.0;
+    CHK(dot_host(ctx, d, h, n, &alpha));
+    alpha = ctx->ocg_gh / alpha;
+    hipLaunchKernelGGL(vec_add_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, x, alpha, d, n);
+    hipLaunchKernelGGL(vec_add_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, g, alpha, h, n);
+    return dot_host(ctx, g, g, n, gg);
+  }
+  double *const s = ctx->ocg_dev.get();
+  hipLaunchKernelGGL(dot_partial_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, d, h, n, ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), gr, 1, 0u, s + 2);
+  hipLaunchKernelGGL(cg_outer_update_kernel, dim3(gr), dim3(kThreads), 0, ctx->stream, x, g, d, h, n, (const double *)(s + ctx->ocg_cur),
+                     (const double *)(s + 2), ctx->part_a.get());
+  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, (const double *)ctx->part_a.get(), gr, 1, 0u, ctx->scal_dev.get());
+  CHK(launch_status(ctx));
+  CHK(fetch_scalars(ctx, 1));
+  *gg = ctx->scal_host.get()[0];
+  return GMG_OK;
+}
+
 // SolverCG<vector_t>::solve, deal.II operation order (see oracle/gmg_oracle.c:cg_solve).
 int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, int max_it, int precond, int *iterations,
                  double *starting_value, double *convergence_value) {
@@ -3921,8 +4316,7 @@ int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, i
     if (res <= tol) break;
     if (precond != GMG_PRECOND_IDENTITY) {
       if ((rc = apply_precond(h, g))) break;
-      gmg_vec_equ(ctx, d, -1.0, h, n);
-      if ((rc = dot_host(ctx, g, h, n, &gh))) break;
+      if ((rc = gmg_cg_direction_step(ctx, d, g, h, n, 1))) break;  // d = -h, g.h
     } else {
       gmg_vec_equ(ctx, d, -1.0, g, n);
       gh = res * res;
@@ -3930,20 +4324,21 @@ int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, i
     for (;;) {
       ++it;
       if ((rc = gmg_spmv(ctx, GMG_SYSTEM, h, d))) break;
-      if ((rc = dot_host(ctx, d, h, n, &alpha))) break;
-      alpha = gh / alpha;
-      gmg_vec_add(ctx, x, alpha, d, n);
-      gmg_vec_add(ctx, g, alpha, h, n);
-      if ((rc = dot_host(ctx, g, g, n, &tmp))) break;
+      if (precond != GMG_PRECOND_IDENTITY) {
+        if ((rc = gmg_cg_update_step(ctx, x, g, d, h, n, &tmp))) break;  // alpha = g.h / d.h; x += alpha d; g += alpha h; |g|^2
+      } else {  // (g.h is res * res on the host)
+        if ((rc = dot_host(ctx, d, h, n, &alpha))) break;
+        alpha = gh / alpha;
+        gmg_vec_add(ctx, x, alpha, d, n);
+        gmg_vec_add(ctx, g, alpha, h, n);
+        if ((rc = dot_host(ctx, g, g, n, &tmp))) break;
+      }
       res = std::sqrt(tmp);
       if (res <= tol) break;
       if (it >= max_it || res != res) { rc = GMG_ERR_OUTER_NOCONV; ctx->err = "outer CG did not converge within max_it"; break; }
       if (precond != GMG_PRECOND_IDENTITY) {
         if ((rc = apply_precond(h, g))) break;
-        beta = gh;
-        if ((rc = dot_host(ctx, g, h, n, &gh))) break;
-        beta = gh / beta;
-        gmg_vec_sadd(ctx, d, beta, -1.0, h, n);
+        if ((rc = gmg_cg_direction_step(ctx, d, g, h, n, 0))) break;  // beta = g.h / (the previous g.h); d = beta d - h
       } else {
         beta = gh;
         gh = res * res;
@@ -6348,6 +6743,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   if (k == "host_threads") g_host_threads = (int)value;
   else if (k == "debug_upload") ctx->debug_upload = on;
   else if (k == "disable_sell") ctx->disable_sell = on;
+  else if (k == "disable_outer_cg_fused") ctx->disable_outer_cg_fused = on;
+  else if (k == "disable_hybrid") ctx->disable_hybrid = on;
+  else if (k == "hybrid_two_launches") ctx->hybrid_two_launches = on;
+  else if (k == "disable_vcycle_fused") ctx->disable_vcycle_fused = on;
   else if (k == "disable_patterns") ctx->disable_patterns = on;
   else if (k == "disable_compression") ctx->disable_compression = on;
   else if (k == "disable_sellp") ctx->disable_sellp = on;

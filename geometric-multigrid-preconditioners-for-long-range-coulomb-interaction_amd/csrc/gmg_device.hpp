@@ -142,7 +142,30 @@ enum SpmvMode : int {
   kAddTo = 2,   // y = b + acc                       (u += P u_c)
   kJacobi = 3,  // y = x_i + (omega (b - acc)) invd  (one damped-Jacobi smoothing step)
   kCheb = 4,    // w = c1 w + omega ((b - acc) invd) ; y = x_i + w   (Chebyshev recurrence step)
+  kResidPre = 5,  // kResid, and the SSOR sweep's pre-pass on r_i = y_i (row-window kernel only)
 };
+
+// What sgs_wave_prepass_kernel (gmg_sgs.hpp) does with r_i, for the epilogue of the product that forms r
+struct SgsPreArgs {
+  const int32_t *row_ci;           // level row -> compact id, -1: row without couplings
+  const int32_t *rpos_f, *rpos_b;  // compact id -> index (in doubles) of its rhs field in the record stream
+  const double *iso_diag, *iso_invd;
+  double *stream, *ycur, *y;       // record stream, latest values (may be null), the sweep's output vector
+  double omega;
+};
+__device__ __forceinline__ void sgs_pre_row(const SgsPreArgs &p, int i, double ri) {
+  const int ci = p.row_ci[i];
+  if (ci < 0) {
+    const double invd = p.iso_invd[i];
+    const double y1 = 0.0 + (p.omega * (ri - 0.0)) * invd;
+    const double acc = 0.0 + p.iso_diag[i] * y1;
+    p.y[i] = y1 + (p.omega * (ri - acc)) * invd;
+  } else {
+    p.stream[p.rpos_f[ci]] = ri;
+    p.stream[p.rpos_b[ci]] = ri;
+    if (p.ycur) p.ycur[ci] = 0.0;
+  }
+}
 
 struct SpmvArgs {
   const int32_t *rowptr;
@@ -167,6 +190,7 @@ struct SpmvArgs {
   double *part_out;       // partials of d.h, one per workgroup
   double tol;
   int maxit;
+  SgsPreArgs pre;         // kResidPre
 };
 
 // SolverCG between two iterations: res = |g| ; SolverControl::check ; beta = gh_new / gh_old.
@@ -204,28 +228,12 @@ __device__ __forceinline__ bool cg_open_iteration(CGState *st, const double *par
 // CG = 0: plain operator application with epilogue MODE
 // CG = 1: single-GPU coarse CG, direction update fused in: x_j := beta d_old[j] - g[j]
 // CG = 2: distributed coarse CG: x is the already exchanged direction d; emits partial d.h
+// rows [r0, r1) of one tile (the whole workgroup): products into the LDS window, then one lane per row
 template <int MODE, int CG>
-__global__ __launch_bounds__(kThreads) void spmv_tile_kernel(SpmvArgs a) {
-  __shared__ __attribute__((aligned(16))) double prod[kTileNnz + 8];
-  __shared__ double red[4];
+__device__ __forceinline__ void spmv_tile_rows(const SpmvArgs &a, int r0, int r1, double beta, double *prod, double *red, double &dot_acc) {
   const int tid = threadIdx.x;
   constexpr bool XFORM = (CG == 1);
-
-  double beta = 0.0;
-  if constexpr (CG == 1) {
-    if (!cg_open_iteration(a.st, a.part_in, a.n_part_in, a.tol, a.maxit, red, &beta)) return;
-  }
-  if constexpr (CG == 2) {
-    if (a.st->done) return;
-  }
-
-  const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, nb = gridDim.x >> 3;
-  const int t_begin = xcd * a.tiles_per_xcd;
-  const int t_end = min(t_begin + a.tiles_per_xcd, a.n_tiles);
-  double dot_acc = 0.0;
-
-  for (int t = t_begin + lb; t < t_end; t += nb) {
-    const int r0 = a.tile_row[t], r1 = a.tile_row[t + 1];
+  {
     const int k0 = a.rowptr[r0], k1 = a.rowptr[r1];
     const int ka = k0 & ~3;
     if (k1 - ka <= kTileNnz) {
@@ -280,6 +288,10 @@ __global__ __launch_bounds__(kThreads) void spmv_tile_kernel(SpmvArgs a) {
           a.y[r] = acc;
         } else if constexpr (MODE == kResid) {
           a.y[r] = a.b[r] - acc;
+        } else if constexpr (MODE == kResidPre) {
+          const double ri = a.b[r] - acc;
+          a.y[r] = ri;
+          sgs_pre_row(a.pre, r, ri);
         } else if constexpr (MODE == kAddTo) {
           a.y[r] = a.b[r] + acc;
         } else if constexpr (MODE == kJacobi) {
@@ -310,6 +322,7 @@ __global__ __launch_bounds__(kThreads) void spmv_tile_kernel(SpmvArgs a) {
         } else if constexpr (CG == 2) { a.y[r] = acc; dot_acc += a.x[r] * acc; }
         else if constexpr (MODE == kStore) a.y[r] = acc;
         else if constexpr (MODE == kResid) a.y[r] = a.b[r] - acc;
+        else if constexpr (MODE == kResidPre) { const double ri = a.b[r] - acc; a.y[r] = ri; sgs_pre_row(a.pre, r, ri); }
         else if constexpr (MODE == kAddTo) a.y[r] = a.b[r] + acc;
         else if constexpr (MODE == kJacobi) a.y[r] = a.x[r] + (a.omega * (a.b[r] - acc)) * a.invd[r];
         else if constexpr (MODE == kCheb) {
@@ -320,6 +333,28 @@ __global__ __launch_bounds__(kThreads) void spmv_tile_kernel(SpmvArgs a) {
       __syncthreads();
     }
   }
+}
+
+template <int MODE, int CG>
+__global__ __launch_bounds__(kThreads) void spmv_tile_kernel(SpmvArgs a) {
+  __shared__ __attribute__((aligned(16))) double prod[kTileNnz + 8];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+
+  double beta = 0.0;
+  if constexpr (CG == 1) {
+    if (!cg_open_iteration(a.st, a.part_in, a.n_part_in, a.tol, a.maxit, red, &beta)) return;
+  }
+  if constexpr (CG == 2) {
+    if (a.st->done) return;
+  }
+
+  const int xcd = blockIdx.x & 7, lb = blockIdx.x >> 3, nb = gridDim.x >> 3;
+  const int t_begin = xcd * a.tiles_per_xcd;
+  const int t_end = min(t_begin + a.tiles_per_xcd, a.n_tiles);
+  double dot_acc = 0.0;
+
+  for (int t = t_begin + lb; t < t_end; t += nb) spmv_tile_rows<MODE, CG>(a, a.tile_row[t], a.tile_row[t + 1], beta, prod, red, dot_acc);
   if constexpr (CG != 0) {
     const double s = block_sum(dot_acc, red);
     if (tid == 0) a.part_out[blockIdx.x] = s;
@@ -502,6 +537,87 @@ __global__ __launch_bounds__(kThreads) void spmv_sell_kernel(SellArgs sa) {
     const double sblock = block_sum(dot_acc, red);
     if (threadIdx.x == 0) a.part_out[blockIdx.x] = sblock;
   }
+}
+
+// ---------------------------------------------------------------- hybrid: SELL slices + CSR row windows in one launch
+//
+// An operator most of whose slices are regular while a few hold much wider rows (the active-mesh system matrix: rows of
+// hanging-node neighbours carry up to three times the 27 entries of the others) is refused by the SELL rule as a whole.
+// Its regular slices are kept in the SELL streams above (value codes from a dictionary over those slices only, column
+// patterns where a slice qualifies, 32-bit columns otherwise, zero quads for the other slices); the rows of the other
+// slices are read from the CSR copy by the row-window code.  y = A x only.  Workgroups [0, tile_blocks) take the CSR
+// tiles, the others one SELL slice per wave at a time; both kinds own an XCD-contiguous share, as the kernels above.
+struct HybArgs {
+  SellArgs sa;             // streams of the regular slices (qptr over all slices); sa.a: the CSR copy and the vectors
+  const int32_t *tiles;    // [n_tiles][2]: rows [begin, end) of the CSR tiles
+  const int32_t *reg;      // [n_reg]: the regular slices
+  int n_tiles, n_reg, tile_blocks;
+};
+
+template <bool VAL8>
+__device__ __forceinline__ void hybrid_sell_slice(const SellArgs &sa, int s, int lane, const double *dict) {
+  const SpmvArgs &a = sa.a;
+  const int qb = __builtin_amdgcn_readfirstlane(sa.qptr[s]), qe = __builtin_amdgcn_readfirstlane(sa.qptr[s + 1]);
+  const int pid = sa.spat ? __builtin_amdgcn_readfirstlane(sa.spat[s]) : -1;
+  const int row = s * 64 + lane;
+  const uchar4 *kbase = reinterpret_cast<const uchar4 *>(sa.vals) + lane;
+  const double2 *vbase = reinterpret_cast<const double2 *>(sa.vals) + lane;
+  const int4 *cbase = reinterpret_cast<const int4 *>(sa.cols) + lane;
+  const int32_t *pat = pid >= 0 ? sa.pat + (size_t)pid * 32 : nullptr;
+  auto load = [&](int q, SellVals<VAL8> &V, int4 &C) {
+    if constexpr (VAL8) V.code = kbase[(size_t)q * 64];
+    else { V.v0 = vbase[(size_t)(2 * q) * 64]; V.v1 = vbase[(size_t)(2 * q + 1) * 64]; }
+    if (pat) {
+      const int4 dl = *reinterpret_cast<const int4 *>(pat + 4 * (q - qb));
+      C = int4{row + dl.x, row + dl.y, row + dl.z, row + dl.w};
+    } else {
+      C = cbase[(size_t)q * 64];
+    }
+  };
+  double acc = 0.0;
+  SellVals<VAL8> v0{}, v1{};
+  int4 c0{0, 0, 0, 0}, c1{0, 0, 0, 0};
+  if (qb < qe) load(qb, v0, c0);
+  if (qb + 1 < qe) load(qb + 1, v1, c1);
+  for (int q = qb; q < qe; ++q) {
+    const double x0 = a.x[c0.x], x1 = a.x[c0.y], x2 = a.x[c0.z], x3 = a.x[c0.w];
+    double w0, w1, w2, w3;
+    if constexpr (VAL8) { w0 = dict[v0.code.x]; w1 = dict[v0.code.y]; w2 = dict[v0.code.z]; w3 = dict[v0.code.w]; }
+    else { w0 = v0.v0.x; w1 = v0.v0.y; w2 = v0.v1.x; w3 = v0.v1.y; }
+    v0 = v1; c0 = c1;
+    if (q + 2 < qe) load(q + 2, v1, c1);
+    acc += w0 * x0; acc += w1 * x1; acc += w2 * x2; acc += w3 * x3;
+  }
+  if (row < sa.n_rows) a.y[row] = acc;
+}
+
+// PART 0: both kinds of workgroup in one launch; 1: the tiles alone; 2: the slices alone (tile_blocks = 0, no row window)
+template <bool VAL8, int PART>
+__global__ __launch_bounds__(kThreads) void spmv_hybrid_kernel(HybArgs h) {
+  __shared__ __attribute__((aligned(16))) double prod[PART == 2 ? 2 : kTileNnz + 8];
+  __shared__ double red[4];
+  __shared__ double dict[VAL8 && PART != 1 ? 256 : 1];
+  const int xcd = blockIdx.x & 7;  // (tile_blocks and the grid are multiples of 8)
+  if (PART != 2 && (int)blockIdx.x < h.tile_blocks) {
+    const int lb = blockIdx.x >> 3, nb = h.tile_blocks >> 3;
+    const int per_xcd = (h.n_tiles + 7) >> 3;
+    const int t_end = min((xcd + 1) * per_xcd, h.n_tiles);
+    double unused = 0.0;
+    for (int t = xcd * per_xcd + lb; t < t_end; t += nb)
+      spmv_tile_rows<kStore, 0>(h.sa.a, h.tiles[2 * t], h.tiles[2 * t + 1], 0.0, prod, red, unused);
+    return;
+  }
+  if constexpr (PART == 1) return;
+  if constexpr (VAL8) {
+    dict[threadIdx.x] = h.sa.dict[threadIdx.x];
+    __syncthreads();
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int lb = ((int)blockIdx.x - h.tile_blocks) >> 3, nb = ((int)gridDim.x - h.tile_blocks) >> 3;
+  const int per_xcd = (h.n_reg + 7) >> 3;
+  const int i_end = min((xcd + 1) * per_xcd, h.n_reg);
+  for (int i = xcd * per_xcd + lb * 4 + wid; i < i_end; i += nb * 4)
+    hybrid_sell_slice<VAL8>(h.sa, __builtin_amdgcn_readfirstlane(h.reg[i]), lane, dict);
 }
 
 // ---------------------------------------------------------------- SELL-64 pattern kernel (lattice fast path)
@@ -1169,6 +1285,41 @@ __global__ __launch_bounds__(kThreads) void gather_scatter_kernel(double *dst, c
   }
 }
 
+// copy_to_mg / copy_from_mg of one V-cycle over all levels at once, driven by inverse indices built from the levels' copy
+// lists (mg_copy_tables): `to` holds, level after level, the system index a level row is filled from, or -1 (+0.0).
+constexpr int kMgMaxLevels = 12;
+struct MgCopyArgs {
+  double *def[kMgMaxLevels];
+  double *sol[kMgMaxLevels];
+  int64_t off[kMgMaxLevels + 1];  // first entry of each level in `to`
+  int n_levels;
+  const int32_t *to;
+  const double *src;
+  // copy_from_mg: system row -> level (-1: in no copy list, +0.0) and row on it
+  const int32_t *from_level, *from_row;
+  double *dst;
+  int64_t n_sys;
+};
+// def_l = src at the level's copy indices, +0.0 elsewhere; sol_l = 0 on the levels above the coarsest
+__global__ __launch_bounds__(kThreads) void mg_copy_to_kernel(MgCopyArgs a) {
+  const int64_t total = a.off[a.n_levels];
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
+    int l = 0;
+    while (i >= a.off[l + 1]) ++l;
+    const int64_t r = i - a.off[l];
+    const int32_t g = a.to[i];
+    a.def[l][r] = g >= 0 ? a.src[g] : 0.0;
+    if (l > 0) a.sol[l][r] = 0.0;
+  }
+}
+// dst = the level solutions at the copy indices (a DoF on two levels: the later level of the V-cycle's loop), +0.0 elsewhere
+__global__ __launch_bounds__(kThreads) void mg_copy_from_kernel(MgCopyArgs a) {
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < a.n_sys; i += (int64_t)gridDim.x * kThreads) {
+    const int l = a.from_level[i];
+    a.dst[i] = l >= 0 ? a.sol[l][a.from_row[i]] : 0.0;
+  }
+}
+
 // partial dot: out[blockIdx] ; finalised by reduce_final_kernel
 __global__ __launch_bounds__(kThreads) void dot_partial_kernel(const double *x, const double *y, int64_t n, double *part) {
   __shared__ double red[4];
@@ -1219,6 +1370,31 @@ __global__ __launch_bounds__(kThreads) void reduce_final_kernel(const double *pa
     }
     if (threadIdx.x == 0) out[j] = r;
   }
+}
+
+// Outer CG, update step (gmg_cg_update_step): alpha = gh / d.h from the two device scalars (the IEEE division the host
+// did), x += alpha d, g += alpha h, and the partials of |g|^2 as dot_partial_kernel(g, g) forms them: launched on the
+// same grid, every thread sums the same elements in the same order, and block_sum combines them the same way.
+__global__ __launch_bounds__(kThreads) void cg_outer_update_kernel(double *x, double *g, const double *d, const double *h, int64_t n,
+                                                                  const double *gh, const double *dh, double *part) {
+  __shared__ double red[4];
+  const double alpha = *gh / *dh;
+  double acc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+    x[i] += alpha * d[i];
+    const double gi = g[i] + alpha * h[i];
+    g[i] = gi;
+    acc += gi * gi;
+  }
+  const double s = block_sum(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// Outer CG, direction step (gmg_cg_direction_step): beta = gh_new / gh_old on the device, d.sadd(beta, a, h) with a = -1
+__global__ __launch_bounds__(kThreads) void cg_outer_direction_kernel(double *d, const double *h, int64_t n, const double *gh_new,
+                                                                     const double *gh_old, double a) {
+  const double beta = *gh_new / *gh_old;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads)
+    d[i] = beta * d[i] + a * h[i];
 }
 
 // ---------------------------------------------------------------- Gaussian charge density

@@ -2103,7 +2103,7 @@ int SolverCG_solve(gmg_context *ctx, SolverControl &control, int64_t n, int64_t 
     return preconditioner == "GMG" ? gmg_precondition(ctx, dst, src) : gmg_precondition_jacobi(ctx, 0.6, dst, src);
   };
   int it = 0, zero = 0;
-  double res = 0, gh = 0, alpha = 0, beta = 0, tmp = 0;
+  double res = 0, tmp = 0;
   do {
     if ((rc = gmg_vec_all_zero(ctx, x, n, &zero))) break;
     if (!zero) {
@@ -2117,24 +2117,17 @@ int SolverCG_solve(gmg_context *ctx, SolverControl &control, int64_t n, int64_t 
     control.initial_value = res;
     if (res <= control.tolerance) break;
     if ((rc = precondition(h, g))) break;
-    gmg_vec_equ(ctx, d, -1.0, h, n);
-    if ((rc = gmg_vec_dot(ctx, g, h, n, &gh))) break;
+    if ((rc = gmg_cg_direction_step(ctx, d, g, h, n, 1))) break;  // d = -h; gh = g.h, kept by the library
     for (;;) {
       ++it;
       if ((rc = gmg_spmv(ctx, GMG_SYSTEM, h, d))) break;
-      if ((rc = gmg_vec_dot(ctx, d, h, n, &alpha))) break;
-      alpha = gh / alpha;
-      gmg_vec_add(ctx, x, alpha, d, n);
-      gmg_vec_add(ctx, g, alpha, h, n);
-      if ((rc = gmg_vec_dot(ctx, g, g, n, &tmp))) break;
+      // alpha = gh / d.h; x += alpha d; g += alpha h; |g|^2: the one value SolverControl needs on the host
+      if ((rc = gmg_cg_update_step(ctx, x, g, d, h, n, &tmp))) break;
       res = std::sqrt(tmp);
       if (res <= control.tolerance) break;
       if (it >= control.max_steps || res != res) { rc = GMG_ERR_OUTER_NOCONV; break; }
       if ((rc = precondition(h, g))) break;
-      beta = gh;
-      if ((rc = gmg_vec_dot(ctx, g, h, n, &gh))) break;
-      beta = gh / beta;
-      gmg_vec_sadd(ctx, d, beta, -1.0, h, n);
+      if ((rc = gmg_cg_direction_step(ctx, d, g, h, n, 0))) break;  // beta = g.h / gh; d = beta d - h; gh = g.h
     }
   } while (0);
   control.last_step = it;

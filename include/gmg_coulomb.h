@@ -175,6 +175,18 @@ int gmg_restrict_and_add(gmg_context *ctx, int level, double *dst_coarse, const 
 int gmg_cg_solve(gmg_context *ctx, double *x, const double *b, double rel_tol, int max_it, int precond,
                  int *iterations, double *starting_value, double *convergence_value);
 
+/* The two steps of one SolverCG iteration around the preconditioner (src/step-50.cc:991-992), for a caller that keeps the
+ * loop itself (csrc/host/laplace_problem.cc) and for gmg_cg_solve.  g.h stays inside the context between the steps: on one
+ * rank in device memory, where alpha = g.h / d.h and beta = g.h / (the previous g.h) are formed by the same IEEE divisions
+ * the host did, so an iteration waits for the device once (|g|^2, which SolverControl checks) instead of three times.
+ * Vectors, partial sums and their order are those of gmg_vec_dot / gmg_vec_add / gmg_vec_sadd: results are bit for bit
+ * the same.  Several ranks, or option disable_outer_cg_fused: the steps run exactly those calls.
+ *   direction step: first != 0: d = -h, g.h kept; first == 0: beta = g.h / (kept g.h), d.sadd(beta, -1, h), g.h kept.
+ *                   Asynchronous on one rank.
+ *   update step:    alpha = (kept g.h) / d.h, x.add(alpha, d), g.add(alpha, h), *gg = g.g.  Blocks.                        */
+int gmg_cg_direction_step(gmg_context *ctx, double *d, const double *g, const double *h, int64_t n, int first);
+int gmg_cg_update_step(gmg_context *ctx, double *x, double *g, const double *d, const double *h, int64_t n, double *gg);
+
 /* ---- next row N1: Gaussian charge density at the quadrature points -------- */
 /* compute_charge_densities() (src/step-50.cc:509-575) with the atom lists of
  * rhs_assembly_optimization() (:260-306) evaluated on the fly: for every cell, rho at its nq
