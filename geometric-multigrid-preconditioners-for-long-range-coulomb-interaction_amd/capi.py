@@ -160,6 +160,12 @@ class Context:
         if rc != OK:
             raise GMGError(rc, self.L.gmg_last_error(self.h).decode())
 
+    def reset(self, n_levels: int):
+        """gmg_reset: drops every operator and every table derived from one; the context then has n_levels empty levels"""
+        self._chk(self.L.gmg_reset(self.h, C.c_int(n_levels)))
+        self.n_levels = n_levels
+        self.n_system = 0
+
     # ---- operators
     def set_system_matrix(self, m):
         rp, c, v = _csr(m)

@@ -3595,6 +3595,8 @@ int gmg_reset(gmg_context *ctx, int n_levels) {
   ctx->n_levels = n_levels;
   ctx->lv.clear();
   ctx->lv.resize((size_t)n_levels);
+  // the levels' copy_version restart at 0: a hierarchy of the same sizes would repeat the signature of the fused copies' tables
+  ctx->mgcopy_sig.clear(); ctx->mgcopy_ok = false;
   ctx->last_coarse_iters = 0;
   ctx->stats = gmg_stats{};
   ctx->ev3_used = 0;

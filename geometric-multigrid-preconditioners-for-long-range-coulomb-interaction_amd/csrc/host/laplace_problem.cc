@@ -1921,7 +1921,10 @@ int LaplaceProblem<dim>::upload() {
   // (first upload: the context may have been created early (charge densities) with 1 level.)  gmg_reset drops the mesh
   // tables; with "Operators from resident tables" they are this cycle's and the entries below read them
   if (operators_resident) GMGC(gmg_set_option(gmg, "reset_keeps_mesh_tables", 1.0));
-  const int rc_reset = gmg_reset(gmg, L);
+  // "Preconditioner = Jacobi" (:996-1004) needs the system matrix alone: run_cycle assembles no level operator for it, and none
+  // is uploaded.  The context is then reset to one (empty) level, the smallest count gmg_reset takes.
+  const bool with_levels = par.PreconditionerType == "GMG";
+  const int rc_reset = gmg_reset(gmg, with_levels ? L : 1);
   if (operators_resident) GMGC(gmg_set_option(gmg, "reset_keeps_mesh_tables", 0.0));
   GMGC(rc_reset);
   operators_uploaded = true;
@@ -1994,7 +1997,7 @@ int LaplaceProblem<dim>::upload() {
     d_begin = 0; d_n = d_nvec = S.n_rows;
   }
   double levels_build_ms = 0.0, levels_wall_s = 0.0;  // (STEP50_TIMING=2: the device-formed levels, inputs included)
-  for (int l = 0; l < L; ++l) {
+  for (int l = 0; with_levels && l < L; ++l) {
     const bool lattice0 = l == 0 && level0_on_device && !(distributed && level0_partitioned);
     bool level_formed = false;  // A_l and I_l by gmg_assemble_level_matrix
     if (lattice0) {
@@ -2067,14 +2070,14 @@ int LaplaceProblem<dim>::upload() {
       GMGC(gmg_set_prolongation(gmg, l, P.n_rows, P.n_cols, P.rowptr.data(), P.col.data(), P.val.data()));
     }
   }
-  if (levels_on_device && sublap_on()) {
+  if (with_levels && levels_on_device && sublap_on()) {
     std::fprintf(stderr, "[step50]     . %-32s %8.3f s\n", "level matrices on device", levels_wall_s);
     std::fprintf(stderr, "[step50]     . %-32s %8.3f ms\n", "  of it on the device (build_ms)", levels_build_ms);
   }
   const int kind = par.smoother == "Jacobi" ? GMG_SMOOTHER_JACOBI : par.smoother == "Chebyshev" ? GMG_SMOOTHER_CHEBYSHEV : GMG_SMOOTHER_SSOR;
-  GMGC(gmg_set_smoother(gmg, kind, par.smoother_omega, par.smoother_steps, par.chebyshev_degree, 0.0, 0.0));
-  GMGC(gmg_set_coarse(gmg, 1e-10, 1000));  // :962
-  if (par.coarse_solver == "direct") {
+  if (with_levels) GMGC(gmg_set_smoother(gmg, kind, par.smoother_omega, par.smoother_steps, par.chebyshev_degree, 0.0, 0.0));
+  if (with_levels) GMGC(gmg_set_coarse(gmg, 1e-10, 1000));  // :962
+  if (with_levels && par.coarse_solver == "direct") {
     const int rc_cs = gmg_set_coarse_solver(gmg, GMG_COARSE_DIRECT);
     if (rc_cs == GMG_ERR_UNSUPPORTED) {
       if (!coarse_fallback_reported) pcout(std::string("   Coarse solver direct: not applicable (") + gmg_last_error(gmg) + "), coarse CG");

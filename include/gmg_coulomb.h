@@ -60,7 +60,8 @@ typedef struct gmg_context gmg_context;
  * n_levels = triangulation.n_global_levels() (:709).                                      */
 int gmg_create(gmg_context **ctx, int device_id, int n_levels);
 int gmg_destroy(gmg_context *ctx);
-/* New adaptive cycle (src/step-50.cc:1484): drops every operator, keeps stream + communicator. */
+/* New adaptive cycle (src/step-50.cc:1484): drops every operator, keeps stream + communicator; no table derived from an
+ * operator or a copy list survives it (the inverse indices of the fused copies included).   */
 int gmg_reset(gmg_context *ctx, int n_levels);
 const char *gmg_last_error(const gmg_context *ctx);
 int gmg_synchronize(gmg_context *ctx);
@@ -69,7 +70,10 @@ int gmg_synchronize(gmg_context *ctx);
 /* system_matrix (include/step_50.h:156; filled src/step-50.cc:793-795, 831).              */
 int gmg_set_system_matrix(gmg_context *ctx, int64_t n_rows, int64_t n_cols, const int64_t *rowptr,
                           const int32_t *col, const double *val);
-/* mg_matrices[level] (include/step_50.h:168; filled src/step-50.cc:869-889, 930).         */
+/* mg_matrices[level] (include/step_50.h:168; filled src/step-50.cc:869-889, 930).
+ * A call refused with GMG_ERR_INVALID for its rowptr or col (found on the host, before any launch) leaves the level WITHOUT
+ * an operator, not with the previous one: gmg_precondition then returns GMG_ERR_INVALID ("level matrix not set") until a
+ * valid matrix is set for the level, after which the context is as if the refused call had not been made.              */
 int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_cols, const int64_t *rowptr,
                          const int32_t *col, const double *val);
 /* mg_matrices[0] of the undivided lattice (Triangulation::subdivided_hyper_rectangle, src/step-50.cc:1526; assembled

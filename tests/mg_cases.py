@@ -95,6 +95,71 @@ def _synthetic(k=3):
                            copy_global=[g0.astype(np.int32), g1.astype(np.int32)], copy_level=[v0.astype(np.int32), v1.astype(np.int32)])
 
 
+# tests/test_gpu_context_reuse.py: hierarchies that differ from SYN in ONE thing a context derives
+# tables from, and agree with it in every size -- what a context that kept a table of SYN's would not notice by a fault.
+REUSE_TWIN = "SYN-T"
+REUSE_SUBSTITUTIONS = ("SYN-A1", "SYN-A0", "SYN-I", "SYN-P")
+REUSE_NAMES = (REUSE_TWIN,) + REUSE_SUBSTITUTIONS
+
+
+def _respd(m, seed):
+    """m's pattern with other values: the off-diagonal a_ij times s_i s_j, s_i in [0.5, 1) drawn per row (symmetric, and no
+    entry grows), then the diagonal set as spd() of _synthetic sets it, sum_j |a_ij| times a factor in [1.02, 1.3) per row:
+    symmetric and strictly diagonally dominant with a positive diagonal, hence SPD"""
+    import scipy.sparse as sp
+
+    rng = np.random.default_rng(seed)
+    a = R._scipy_csr(m).tocoo()
+    s = rng.uniform(0.5, 1.0, a.shape[0])
+    off = a.row != a.col
+    val = np.where(off, a.data * s[a.row] * s[a.col], 0.0)
+    rowsum = np.bincount(a.row, weights=np.abs(val), minlength=a.shape[0])
+    diag = rowsum * rng.uniform(1.02, 1.3, a.shape[0])
+    val = np.where(off, val, diag[a.row])
+    out = _csr_ns(sp.csr_matrix((val, (a.row, a.col)), shape=a.shape))
+    assert np.array_equal(out.rowptr, m.rowptr) and np.array_equal(out.col, m.col)   # the pattern is m's
+    return out
+
+
+def _reuse_case(name):
+    """SYN with one thing replaced (the sizes, and with them everything the signature of the fused copies' tables holds, are SYN's):
+    SYN-T   both copy lists redrawn: another assignment of the system entries to level 1 / level 0 / no list, another order
+    SYN-A1  A_1 of the same pattern with other values (_respd): invd, the Gershgorin bound and the SSOR records must follow
+    SYN-A0  the same on level 0: the coarse CG's operator
+    SYN-I   the edge matrix of another pattern
+    SYN-P   the prolongation with the weights 0.25 / 1 / 0.25 in place of 0.5 / 1 / 0.5: P^T must follow"""
+    import scipy.sparse as sp
+
+    h = SimpleNamespace(**vars(hierarchy("SYN")[0]))
+    n0, n1 = (m.n_rows for m in h.level_matrices)
+    n_sys = h.system_matrix.n_rows
+    if name == "SYN-T":
+        rng = np.random.default_rng(7919 + n_sys)
+        perm = rng.permutation(n_sys)
+        g1, v1 = perm[:n1], rng.permutation(n1)
+        g0, v0 = perm[n1:n1 + 12], rng.permutation(n0)[:12]
+        h.constrained = np.zeros(n_sys, dtype=bool)
+        h.constrained[perm[n1 + 12:]] = True
+        h.copy_global, h.copy_level = [g0.astype(np.int32), g1.astype(np.int32)], [v0.astype(np.int32), v1.astype(np.int32)]
+    elif name == "SYN-A1":
+        h.level_matrices = [h.level_matrices[0], _respd(h.level_matrices[1], 1)]
+    elif name == "SYN-A0":
+        h.level_matrices = [_respd(h.level_matrices[0], 2), h.level_matrices[1]]
+    elif name == "SYN-I":
+        rng = np.random.default_rng(3)
+        ei, ej = rng.integers(0, n1, 60), rng.integers(0, n1, 60)
+        I1 = sp.csr_matrix((rng.uniform(-0.3, 0.3, 60), (ei, ej)), shape=(n1, n1))
+        I1.sum_duplicates()
+        h.edge_matrices = [None, _csr_ns(I1)]
+    elif name == "SYN-P":
+        P = R._scipy_csr(h.prolongations[0]).copy()
+        P.data = np.where(P.data == 0.5, 0.25, P.data)
+        h.prolongations = [_csr_ns(P)]
+    else:
+        raise KeyError(name)
+    return h
+
+
 LAT_CELLS = (10, 28)   # cells per direction of LAT's level 0 and level 1
 
 
@@ -150,6 +215,8 @@ def hierarchy(name):
         h = _synthetic()
     elif name == LAT:
         h = _lattice_case()
+    elif name in REUSE_NAMES:
+        h = _reuse_case(name)
     else:
         h = _adaptive(name)
     return h, R.Hierarchy(h, name)

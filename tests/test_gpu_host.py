@@ -193,3 +193,25 @@ def test_short_range_energy_with_cutoff_and_for_large_systems(golden_dir):
     assert big["has_energy"] and np.isfinite(big["energy_total"]) and big["energy_short"] < 0.0
     # NaCl lattice: the short-ranged energy per ion of 1000 atoms is that of 216 atoms up to the surface share (measured: 5.1 %)
     assert abs(big["energy_short"] / 1000 - a["energy_short"] / 216) <= 0.10 * abs(a["energy_short"] / 216)
+
+
+@pytest.mark.parametrize("device_cg", [False, True])
+def test_preconditioner_jacobi_through_the_driver(golden_dir, device_cg):
+    """Preconditioner = Jacobi on the device: upload() hands over the system matrix, the vectors and the rhs and no level (the
+    levels are not assembled for it), SolverCG_solve (device_cg false) and gmg_cg_solve (true) run gmg_precondition_jacobi.
+    Two adaptive cycles with the geometry of case B3 of tests/mg_cases.py, each against tests/cg_reference.py on the cycle's
+    own system matrix, rhs and initial guess; tests/test_host.py (test_preconditioner_jacobi_host_cycles) shows that no
+    rounding moves the iteration count on these cycles."""
+    from test_host import check_jacobi_cycle, jacobi_references, preconditioner_problem
+
+    p = preconditioner_problem(golden_dir, preconditioner="Jacobi", device_cg=device_cg)
+    worst = 0.0
+    for cycle in range(2):
+        rep = p.run_cycle(cycle, on_device=True)
+        refs, tol, spread = jacobi_references(p)
+        worst = max(worst, check_jacobi_cycle(rep, p.vector("solution"), p, refs, spread))
+        assert rep["coarse_iterations"] == 0
+        with pytest.raises(RuntimeError):   # (no level matrix exists, on the host or on the device: none is read)
+            p.hierarchy()
+    p.close()
+    print(f"\n[host-gpu] Jacobi through the driver, device_cg {device_cg}: |x - ref| / tolerance max {worst:.3f}")

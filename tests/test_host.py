@@ -182,3 +182,99 @@ def test_rhs_cutoff_lists_match_reference_error_table(golden, golden_dir):
     (src/step-50.cc:260-306) as tabulated in Plotting/RHS_Norm_value_comparison_{L2,Linf}.dat, and of the l2 norm of the per-DoF
     integrated charge density (Plotting/Total_charge_density_AbsErr_L2.dat)."""
     check_rc_variation(golden, golden_dir, on_device=False)
+
+
+# ------------------------------------------------------------------------------------------------ Preconditioner = Jacobi / GMG
+
+# the geometry of case B3 of tests/mg_cases.py (8 atoms, two adaptive cycles)
+PRECONDITIONER_PRM = dict(left=0, right=1, mesh_size=0.5, vacuum=2, problem="GaussianCharges", dim=3, bc="Inhomogeneous", cycles=2, r_c=0.5,
+                          cutoff=3.5, rhs_optimization=True, quad_rhs=1, global_refinement=0, smoother="SSOR")
+
+
+def preconditioner_problem(golden_dir, **kw):
+    p = S().Problem(S().prm_text(**dict(PRECONDITIONER_PRM, **kw)))
+    p.read_lammps(os.path.join(golden_dir, "atom_n1_2.data"))
+    return p
+
+
+def jacobi_references(p):
+    """SolverCG with PreconditionJacobi(0.6) as LaplaceProblem::solve runs it (tolerance 1e-8 |b|, 500 steps, from the cycle's
+    initial guess) on the system matrix and rhs of the cycle p is in, in the three tiers of tests/cg_reference.py -> ({tier:
+    result}, tol, S): S is the spread of the tiers' x on this system relative to max|x|, the S of cg_reference.x_tolerance
+    measured here instead of on its "csr" operator"""
+    import itertools
+
+    import cg_reference as CG
+
+    A, b, x0 = p.matrix("system"), p.vector("rhs"), p.vector("initial_guess")
+    tol = 1e-8 * float(np.linalg.norm(b))
+    refs = {t: CG.cg(A, b, tol, 500, x0=x0, precond=CG.jacobi, tier=t, keep_steps=False) for t in CG.TIERS}
+    scale = np.abs(refs["seq"].x).max()
+    spread = max(float(np.abs(refs[a].x - refs[b_].x).max() / scale) for a, b_ in itertools.combinations(CG.TIERS, 2))
+    return refs, tol, spread
+
+
+def check_jacobi_cycle(rep, x, p, refs, spread):
+    """a cycle's report and solution against the reference: the iteration count, the two residuals to 1e-9 relative, the
+    unconstrained entries of x within X_TOL_FACTOR S max|x|"""
+    import cg_reference as CG
+
+    ref = refs["seq"]
+    assert rep["cg_iterations"] == ref.iterations, (rep["cg_iterations"], ref.iterations)
+    assert abs(rep["starting_value"] - ref.history[0]) <= 1e-9 * ref.history[0]
+    assert abs(rep["convergence_value"] - ref.res) <= 1e-9 * ref.res
+    free = ~p.constrained_mask()
+    err, tol = float(np.abs(x - ref.x)[free].max()), CG.X_TOL_FACTOR * spread * float(np.abs(ref.x).max())
+    assert err <= tol, (err, tol)
+    return err / tol
+
+
+def test_preconditioner_jacobi_host_cycles(golden_dir):
+    """Preconditioner = Jacobi: run_cycle assembles no level operator, and nothing reads one -- two adaptive cycles on the
+    host, solved by the reference CG.  hierarchy() has no level matrices to hand out and says so instead of reading them.
+    What tests/test_gpu_host.py relies on is settled here: on both cycles the tiers stop at the same iteration, under 500,
+    and no residual lies within cg_reference.MARGIN of the tolerance, so no rounding moves the device's count."""
+    import cg_reference as CG
+
+    p = preconditioner_problem(golden_dir, preconditioner="Jacobi")
+    for cycle in range(2):
+        rep = p.run_cycle(cycle, on_device=False)
+        assert rep["dofs"] == p.n_dofs() > 0
+        with pytest.raises(RuntimeError):
+            p.hierarchy()
+        assert p.matrix("system").n_rows == p.n_dofs() and len(p.copy_indices(0)[0]) > 0   # (the lists and transfers are built all the same)
+        refs, tol, spread = jacobi_references(p)
+        its = {t: r.iterations for t, r in refs.items()}
+        hist = refs["seq"].history
+        print(f"\n[host] Jacobi cycle {cycle}: {p.n_dofs()} DoFs, iterations {its}, residual before / at the stop over tol "
+              f"{hist[:-1].min() / tol:.3f} / {hist[-1] / tol:.3f}, tier spread {spread:.2e}")
+        assert all(r.status == CG.OK for r in refs.values()) and len(set(its.values())) == 1 and its["seq"] < 500
+        assert hist[-1] <= tol / CG.MARGIN and hist[:-1].min() >= CG.MARGIN * tol
+        p.finish_cycle_with(refs["seq"].x)
+    assert p.n_levels() == 2
+    p.close()
+
+
+def test_preconditioner_gmg_spelled_out_equals_default(golden_dir):
+    """one prm with Preconditioner = GMG written out runs as the default does: the same log and the same operators, bit for bit"""
+    runs = []
+    for kw in ({}, {"preconditioner": "GMG"}):
+        p = preconditioner_problem(golden_dir, **kw)
+        hs = []
+        for cycle in range(2):
+            p.run_cycle(cycle, on_device=False)
+            h = p.hierarchy()
+            hs.append(h)
+            p.finish_cycle_with(go.OracleMG(h, smoother=go.SSOR).solve(h.system_rhs, x0=p.vector("initial_guess"))["x"])
+        runs.append((hs, p.log(), p.vector("solution")))
+        p.close()
+    (ha, la, xa), (hb, lb, xb) = runs
+    assert la == lb and np.array_equal(xa, xb)
+    for a, b in zip(ha, hb):
+        assert np.array_equal(a.system_rhs, b.system_rhs) and np.array_equal(a.constrained, b.constrained)
+        ms = [(a.system_matrix, b.system_matrix)] + list(zip(a.level_matrices + a.edge_matrices + a.prolongations,
+                                                              b.level_matrices + b.edge_matrices + b.prolongations))
+        for ma, mb in ms:
+            assert all(np.array_equal(getattr(ma, k), getattr(mb, k)) for k in ("rowptr", "col", "val"))
+        for k in ("copy_global", "copy_level"):
+            assert all(np.array_equal(u, v) for u, v in zip(getattr(a, k), getattr(b, k)))

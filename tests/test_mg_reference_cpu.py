@@ -313,3 +313,88 @@ def test_rank_vcycle_sensitivity(name):
             assert ratio >= R.SENSITIVITY, (cfg.label(), mut, ratio)
     print(f"\n[mg] rank V-cycle {name}: oracle error / tolerance max {worst:.3f}; sensitivity (difference / tolerance, best source, min): "
           + ", ".join(f"{m} {v:.1e}" for m, v in sorted(low.items())))
+
+
+# ------------------------------------------------------------------------------------------------ context reuse: twins and substitutions
+
+REUSE_SOURCES = ("random", "random-free-x", "random-free-y")
+
+
+def reuse_visible(name, cfg):
+    """Without smoothing the cycle is u_1 = P A_0^-1 P^T d_1: u = 0 meets A_1 and I_1, and nothing reads d_1 after I_1^T (the
+    reason vcycle_mutations gives for the edge mutations).  M then holds neither operator, no substitution of either can show,
+    and the proof below asserts that instead: the two references are equal to the bit"""
+    return cfg.steps > 0 or name not in ("SYN-A1", "SYN-I")
+
+
+@pytest.mark.parametrize("name", K.REUSE_NAMES)
+def test_reuse_case_discriminates(name):
+    """tests/test_gpu_context_reuse.py loads SYN and then `name` into one context.  A context that kept
+    a table derived from what `name` replaces computes SYN's M.  Per configuration and on each of the random source and the two
+    random-free ones, SYN's M and `name`'s M are SENSITIVITY tolerances of `name` apart (the coarse allowance of tau = 1e-10
+    included), so check_vcycle against `name`'s reference fails for such a context.  The sizes are SYN's: what the signature
+    of the fused copies' tables holds is equal, and no stale index leaves its vector."""
+    h, H = K.hierarchy(name)
+    h0, H0 = K.hierarchy("SYN")
+    assert H.n_sys == H0.n_sys and H.rows == H0.rows and [len(g) for g in H.copy_global] == [len(g) for g in H0.copy_global]
+    src, labels, dst0 = K.vcycle_sources(name)
+    cols = [labels.index(s) for s in REUSE_SOURCES]
+    low = np.inf
+    for cfg in K.VCYCLE_CONFIGS:
+        ref = K.vcycle_reference(name, cfg)
+        tol = (ref.tol + H.cg_allowance(cfg, TAU))[cols]
+        other = H0.precondition("f64", cfg, src[:, cols], dst0)
+        diff = R.norm2(other - ref.ref[:, cols])
+        if not reuse_visible(name, cfg):
+            assert np.array_equal(other, H.precondition("f64", cfg, src[:, cols], dst0)), cfg.label()   # (tier against the same tier)
+            continue
+        ratio = float((diff / tol).min())
+        low = min(low, ratio)
+        assert ratio >= R.SENSITIVITY, (cfg.label(), ratio)
+    print(f"\n[mg] reuse {name} against SYN (difference / tolerance, worst of {', '.join(REUSE_SOURCES)}, min over the configurations): {low:.1e}")
+
+
+def test_reuse_twin_stale_tables():
+    """the defect itself, built explicitly: copy_to_mg and copy_from_mg through SYN's lists, everything else SYN-T's.  The
+    operators are equal, so this is SYN's M (to the bit), and it is SENSITIVITY tolerances from SYN-T's M on SYN-T's sources"""
+    from types import SimpleNamespace
+
+    h, H = K.hierarchy(K.REUSE_TWIN)
+    h0, H0 = K.hierarchy("SYN")
+    assert not np.array_equal(np.sort(h.copy_global[1]), np.sort(h0.copy_global[1]))   # another assignment, not only another order
+    assert not np.array_equal(np.sort(h.copy_global[0]), np.sort(h0.copy_global[0]))
+    stale = SimpleNamespace(**vars(h))
+    stale.copy_global, stale.copy_level = h0.copy_global, h0.copy_level
+    Hs = R.Hierarchy(stale, "SYN-T with SYN's lists")
+    src, labels, dst0 = K.vcycle_sources(K.REUSE_TWIN)
+    cols = [labels.index(s) for s in REUSE_SOURCES]
+    low = np.inf
+    for cfg in K.VCYCLE_CONFIGS:
+        ref = K.vcycle_reference(K.REUSE_TWIN, cfg)
+        tol = (ref.tol + H.cg_allowance(cfg, TAU))[cols]
+        got = Hs.precondition("f64", cfg, src[:, cols], dst0)
+        assert np.array_equal(got, H0.precondition("f64", cfg, src[:, cols], dst0)), cfg.label()
+        ratio = float((R.norm2(got - ref.ref[:, cols]) / tol).min())
+        low = min(low, ratio)
+        assert ratio >= R.SENSITIVITY, (cfg.label(), ratio)
+    print(f"\n[mg] reuse SYN-T through SYN's copy tables (difference / tolerance, worst source, min over the configurations): {low:.1e}")
+
+
+@pytest.mark.parametrize("name", ["SYN-A1", "SYN-I"])
+def test_reuse_smoother_discriminates(name):
+    """the smoother steps on level 1 that sequence 4 runs after each replacement: A_1's substitution is seen by every smoother
+    with a step to run at SENSITIVITY tolerances; the edge matrix is no part of a smoother step (equal to the bit)"""
+    H, H0 = K.hierarchy(name)[1], K.hierarchy("SYN")[1]
+    u0, rhs = K.smoother_vectors(name, 1)
+    low = np.inf
+    for cfg in [c for c in K.VCYCLE_CONFIGS if c.steps > 0]:
+        for from_zero in (True, False):
+            ref = K.smoother_reference(name, 1, cfg, from_zero)
+            diff = float(np.linalg.norm(H0.smooth("f64", cfg, 1, u0, rhs, from_zero) - ref.ref))
+            if name == "SYN-I":
+                assert diff <= ref.tol
+                continue
+            low = min(low, diff / ref.tol)
+            assert diff / ref.tol >= R.SENSITIVITY, (cfg.label(), from_zero, diff / ref.tol)
+    if name == "SYN-A1":
+        print(f"\n[mg] reuse smoother SYN-A1 against SYN on level 1 (difference / tolerance, min): {low:.1e}")
