@@ -90,7 +90,7 @@ struct DevCSR {
   int64_t lat_fast_rows = 0;
   int lat_classes = 0, lat_nx = 0, lat_nxy = 0, lat_R0 = 0, lat_R1 = 0, lat_C = 0, lat_K = 0, lat_S = 0, lat_fast_blocks = 0, lat_n_gen = 0, lat_grid = 0;
   int64_t lat_gen_bytes = 0;  // stream bytes of the slices outside the interior
-  // hybrid layout (build_hybrid): y = A x reads the regular slices from SELL streams of their own and the rows of the other
+  // hybrid layout (plan_hybrid, gmg_layout.hpp): y = A x reads the regular slices from SELL streams of their own and the rows of the other
   // slices from the CSR copy above, in one launch (spmv_hybrid_kernel); every other mode uses the CSR copy
   bool hyb = false, hyb_val8 = false;
   DevPtr<int32_t> hyb_qptr, hyb_spat, hyb_pat, hyb_tiles, hyb_reg;
@@ -389,8 +389,6 @@ inline hipError_t stream_wait(hipStream_t s) {
   }
 }
 
-constexpr int64_t kTileMaxRowsEarly = 1024;
-
 // level 0 (matrix, coarse CG vectors) is row-partitioned over the ranks
 inline bool l0_partitioned(const gmg_context *ctx) { return ctx->dist && ctx->l0_global > 0; }
 
@@ -408,242 +406,105 @@ void reset_keep_halo(DevCSR &m) {
   m.halo = std::move(keep);
 }
 
-// Host CSR -> device CSR + LDS-window tiling.
-// Host-side setup loops (layout conversion of 10^7..10^8 nonzeros) run on a few threads: f(begin, end, chunk)
-int g_host_threads = 0;  // option "host_threads" (process-wide); 0 = hardware concurrency, at most 16
-inline int host_threads() {
-  const int t = g_host_threads > 0 ? g_host_threads : (int)std::thread::hardware_concurrency();
-  return std::max(1, std::min(16, t));
-}
-template <class F>
-void parallel_chunks(int64_t n, F f) {
-  const int nt = host_threads();
-  if (n < 2048 || nt <= 1) { f((int64_t)0, n, 0); return; }
-  const int64_t per = (n + nt - 1) / nt;
-  std::vector<std::thread> th;
-  for (int t = 0; t < nt; ++t) {
-    const int64_t b = t * per, e = std::min(n, b + per);
-    if (b < e) th.emplace_back(f, b, e, t);
-  }
-  for (auto &x : th) x.join();
+// the options of the context that steer an operator's layout
+LayoutOptions layout_options(const gmg_context *ctx) {
+  LayoutOptions o;
+  o.disable_sell = ctx->disable_sell; o.disable_patterns = ctx->disable_patterns; o.disable_compression = ctx->disable_compression;
+  o.disable_sellp = ctx->disable_sellp; o.disable_rowclass = ctx->disable_rowclass; o.disable_lattice = ctx->disable_lattice;
+  o.disable_hybrid = ctx->disable_hybrid;
+  o.sell_grid = ctx->sell_grid; o.sellp_cost = ctx->sellp_cost; o.sellp_rr = ctx->sellp_rr;
+  o.lattice_segments = ctx->lattice_segments; o.lattice_max_blocks = ctx->lattice_max_blocks;
+  o.debug = ctx->debug_upload;
+  return o;
 }
 
-// Grid of spmv_lattice_kernel: m.lat_C columns x m.lat_K plane steps are cut into S segments per XCD slab -- 2.5 - 3 marching
-// waves per SIMD (measured at 121^3: 2 segments 13.0 us, 3 segments 11.8 us on a pure lattice) as long as a wave keeps >= 4
-// steps; the register budget admits four waves per SIMD = 1024 workgroups: what the marching waves leave free goes to the
-// rows outside the interior (per-entry gathers, ~10 x the cost of an interior row: about one chunk of 64 rows per wave).
-// Returns the number of workgroups for those rows.
-int lattice_grid(const gmg_context *ctx, DevCSR &m, size_t n_gen) {
-  const int slab = std::max(1, m.lat_K / 8);
-  int S = (int)std::max<int64_t>(1, (2816 / 8 + m.lat_C / 2) / m.lat_C);
-  S = std::min(S, std::max(1, slab / 4));
-  if (ctx->lattice_segments > 0) S = std::min(ctx->lattice_segments, slab);
-  m.lat_S = S;
-  m.lat_fast_blocks = 8 * ((S * m.lat_C + 3) / 4);
-  const int n_gen_blocks = n_gen == 0 ? 0 : (int)std::min<size_t>((size_t)std::max(64, 256 * kLatWavesPerSimd - m.lat_fast_blocks), (n_gen + 3) / 4);
-  // every workgroup writes one reduction partial: beyond kMaxPartials (lattices above ~360^3) the marching waves take
-  // several (segment, column) pairs each
-  m.lat_fast_blocks = std::min(m.lat_fast_blocks, (kMaxPartials - n_gen_blocks) / 8 * 8);
-  if (ctx->lattice_max_blocks >= 8) m.lat_fast_blocks = std::min(m.lat_fast_blocks, ctx->lattice_max_blocks / 8 * 8);  // (tests: the multi-pass form on a small lattice)
-  return n_gen_blocks;
-}
+static_assert(sizeof(WaveRR) == sizeof(int4) && alignof(WaveRR) <= alignof(int4),
+              "the round-robin descriptors are read as int4 by spmv_sellp_kernel");
 
-// the lattice interior only needs the rows whose columns are owned (< n_rows): any n_cols >= n_rows qualifies
-inline int64_t n_cols_owned(int64_t n_rows, int64_t n_cols) { return n_cols >= n_rows ? n_rows : -1; }
+void set_tiles(DevCSR &m, const TilePlan &T) { m.n_tiles = T.n_tiles; m.tiles_per_xcd = T.tiles_per_xcd; m.grid = T.grid; }
 
-// Hybrid layout for an operator the SELL rule below refuses as a whole: slice by slice, a slice is
-// regular when its own padding passes the same 12 % bound (padded entries <= 1.12 x its entries; the width is that of its
-// column pattern where it has one).  Regular slices go into SELL streams -- 8-bit value codes if the REGULAR slices hold
-// <= 256 distinct values, no columns for pattern slices, 32-bit columns otherwise --, the rows of the other slices are
-// cut into row-window tiles of the CSR copy.  Not built (the operator stays as it is) when the regular slices hold less
-// than half of the entries: the product then streams more than 3/4 of the CSR bytes anyway.
-int build_hybrid(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col, const double *val,
-                 const std::vector<int32_t> &slice_w, const std::vector<std::vector<int32_t>> &slice_delta) {
-  const int64_t n_slices = (n_rows + 63) / 64, nnz = rowptr[n_rows];
-  std::vector<int32_t> qp((size_t)n_slices + 1, 0), spat((size_t)n_slices, -1), reg;
-  std::vector<char> regular((size_t)n_slices, 0);
-  int64_t quads = 0, nnz_reg = 0, n_irr = 0;
-  for (int64_t sl = 0; sl < n_slices; ++sl) {
-    const int64_t rb = sl * 64, re = std::min<int64_t>(n_rows, rb + 64), ent = rowptr[re] - rowptr[rb];
-    const int64_t w = slice_delta[(size_t)sl].empty() ? slice_w[(size_t)sl] : (int64_t)slice_delta[(size_t)sl].size();
-    const int64_t nq = (w + 3) / 4;
-    if ((double)(nq * 256) <= 1.12 * (double)ent) {
-      regular[(size_t)sl] = 1;
-      reg.push_back((int32_t)sl);
-      quads += nq;
-      nnz_reg += ent;
-    } else {
-      ++n_irr;
-    }
-    qp[(size_t)sl + 1] = (int32_t)quads;
-  }
-  if (reg.empty() || n_irr == 0 || 2 * nnz_reg < nnz || quads == 0 || quads * 256 >= ((int64_t)1 << 31)) {
-    if (ctx->debug_upload)
-      std::fprintf(stderr, "[gmg]   hybrid not built: %lld of %lld slices regular, %lld of %lld entries in them\n", (long long)reg.size(), (long long)n_slices,
-                   (long long)nnz_reg, (long long)nnz);
-    return GMG_OK;
-  }
-  // column patterns of the regular slices
-  std::vector<std::vector<int32_t>> patterns;
-  std::map<std::vector<int32_t>, int> pattern_id;
-  int n_pattern_slices = 0;
-  for (int32_t sl : reg) {
-    if (slice_delta[(size_t)sl].empty()) continue;
-    auto ins = pattern_id.emplace(slice_delta[(size_t)sl], (int)patterns.size());
-    if (ins.second) patterns.push_back(slice_delta[(size_t)sl]);
-    spat[(size_t)sl] = ins.first->second;
-    ++n_pattern_slices;
-  }
-  // value dictionary over the regular slices (bit patterns; +0.0, the padding, is code 0): per chunk of slices in parallel
-  const int nt = host_threads();
-  std::vector<std::vector<uint64_t>> firsts((size_t)nt);
-  std::vector<char> overflow((size_t)nt, 0);
-  bool val8 = !ctx->disable_compression;
-  if (val8)
-    parallel_chunks((int64_t)reg.size(), [&](int64_t ib, int64_t ie, int t) {
-      std::unordered_map<uint64_t, int> seen;
-      uint64_t last = ~0ull;
-      for (int64_t i = ib; i < ie; ++i) {
-        const int64_t rb = (int64_t)reg[(size_t)i] * 64, re = std::min<int64_t>(n_rows, rb + 64);
-        for (int64_t k = rowptr[rb]; k < rowptr[re]; ++k) {
-          uint64_t bits;
-          std::memcpy(&bits, &val[k], 8);
-          if (bits == last) continue;
-          last = bits;
-          if (seen.emplace(bits, 0).second) {
-            firsts[(size_t)t].push_back(bits);
-            if (firsts[(size_t)t].size() > 256) { overflow[(size_t)t] = 1; return; }
-          }
-        }
-      }
-    });
-  std::vector<double> dict(1, 0.0);
-  std::unordered_map<uint64_t, int> code_of;
-  code_of.emplace(0ull, 0);
-  for (size_t t = 0; t < firsts.size() && val8; ++t) {
-    if (overflow[t]) val8 = false;
-    for (uint64_t bits : firsts[t]) {
-      if (!val8) break;
-      if (code_of.emplace(bits, (int)dict.size()).second) {
-        double v;
-        std::memcpy(&v, &bits, 8);
-        dict.push_back(v);
-        if (dict.size() > 256) val8 = false;
-      }
-    }
-  }
-  std::vector<uint64_t> ht_key(1024, 0);
-  std::vector<int16_t> ht_code(1024, -1);
-  auto ht_slot = [](uint64_t bits) { return (size_t)((bits * 0x9E3779B97F4A7C15ull) >> 54); };
-  if (val8)
-    for (const auto &kv : code_of) {
-      size_t h = ht_slot(kv.first);
-      while (ht_code[h] >= 0) h = (h + 1) & 1023;
-      ht_key[h] = kv.first; ht_code[h] = (int16_t)kv.second;
-    }
-  auto code_lookup = [&](uint64_t bits) -> uint8_t {
-    size_t h = ht_slot(bits);
-    while (ht_key[h] != bits || ht_code[h] < 0) h = (h + 1) & 1023;
-    return (uint8_t)ht_code[h];
-  };
-  // pack (the layouts of spmv_sell_kernel: values in double2 pairs or one code per entry, columns four per lane)
-  const size_t n_ent = (size_t)quads * 256;
-  std::vector<double> v2(val8 ? 0 : n_ent, 0.0);
-  std::vector<uint8_t> v1(val8 ? n_ent : 0, 0);
-  std::vector<int32_t> c4(n_ent, 0);
-  parallel_chunks((int64_t)reg.size(), [&](int64_t ib, int64_t ie, int) {
-    for (int64_t i = ib; i < ie; ++i) {
-      const int64_t sl = reg[(size_t)i], q0 = qp[(size_t)sl], nq = qp[(size_t)sl + 1] - q0;
-      const int64_t rb = sl * 64, re = std::min<int64_t>(n_rows, rb + 64);
-      const int32_t first_col = rowptr[re] > rowptr[rb] ? col[rowptr[rb]] : 0;  // (padding of lanes without a row: any valid column)
-      const int pidx = spat[(size_t)sl];
-      for (int lane = 0; lane < 64; ++lane) {
-        const int64_t r2 = rb + lane;
-        const int64_t k0 = r2 < n_rows ? rowptr[r2] : 0, len = r2 < n_rows ? rowptr[r2 + 1] - k0 : 0;
-        const int32_t padcol = r2 < std::min(n_rows, n_cols) ? (int32_t)r2 : first_col;
-        int64_t kk = 0;
-        for (int64_t j = 0; j < 4 * nq; ++j) {
-          const int64_t qq = q0 + j / 4, e = j & 3;
-          const size_t ov = (size_t)(((2 * qq + (e >> 1)) * 64 + lane) * 2 + (e & 1));
-          const size_t oc = (size_t)((qq * 64 + lane) * 4 + e);
-          int32_t cj;
-          double vj;
-          if (pidx >= 0) {
-            const auto &dl = patterns[(size_t)pidx];
-            if (j < (int64_t)dl.size() && kk < len && col[k0 + kk] - r2 == dl[(size_t)j]) { cj = col[k0 + kk]; vj = val[k0 + kk]; ++kk; }
-            else { cj = (int32_t)(j < (int64_t)dl.size() ? r2 + dl[(size_t)j] : r2); vj = 0.0; }
-          } else {
-            cj = j < len ? col[k0 + j] : padcol;
-            vj = j < len ? val[k0 + j] : 0.0;
-          }
-          if (val8) { uint64_t bits; std::memcpy(&bits, &vj, 8); v1[oc] = code_lookup(bits); }
-          else v2[ov] = vj;
-          c4[oc] = cj;
-        }
-      }
-    }
-  });
-  // row-window tiles over the runs of irregular slices (the rule of upload_csr's tiles)
-  std::vector<int32_t> tiles;
-  for (int64_t sl = 0; sl < n_slices;) {
-    if (regular[(size_t)sl]) { ++sl; continue; }
-    int64_t se = sl;
-    while (se < n_slices && !regular[(size_t)se]) ++se;
-    const int64_t run_end = std::min<int64_t>(n_rows, se * 64);
-    for (int64_t r = sl * 64; r < run_end;) {
-      const int64_t ka = rowptr[r] & ~(int64_t)3;
-      int64_t e = r + 1;
-      while (e < run_end && rowptr[e + 1] - ka <= kTileNnz && e - r < kTileMaxRowsEarly) ++e;
-      if (rowptr[e] - ka > kTileNnz) e = r + 1;
-      tiles.push_back((int32_t)r);
-      tiles.push_back((int32_t)e);
-      r = e;
-    }
-    sl = se;
-  }
-  dict.resize(256, 0.0);
-  std::vector<int32_t> table(std::max<size_t>(patterns.size(), 1) * 32, 0);
-  for (size_t pi = 0; pi < patterns.size(); ++pi)
-    for (size_t j = 0; j < patterns[pi].size(); ++j) table[pi * 32 + j] = patterns[pi][j];
-  const size_t vbytes = val8 ? v1.size() : v2.size() * 8, cbytes = c4.size() * 4;
-  HIPC(m.hyb_qptr.alloc(qp.size()));
-  HIPC(m.hyb_spat.alloc(spat.size()));
-  HIPC(m.hyb_pat.alloc(table.size()));
-  HIPC(m.hyb_tiles.alloc(tiles.size()));
-  HIPC(m.hyb_reg.alloc(reg.size()));
-  HIPC(m.hyb_dict.alloc(256));
-  HIPC(m.hyb_vals.alloc_bytes(vbytes + 64));
-  HIPC(m.hyb_cols.alloc_bytes(cbytes + 64));
-  HIPC(hipMemcpyAsync(m.hyb_qptr.get(), qp.data(), sizeof(int32_t) * qp.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_spat.get(), spat.data(), sizeof(int32_t) * spat.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_pat.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_tiles.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_reg.get(), reg.data(), sizeof(int32_t) * reg.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_dict.get(), dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_vals.get(), val8 ? (const void *)v1.data() : (const void *)v2.data(), vbytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(m.hyb_cols.get(), c4.data(), cbytes, hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  m.hyb_val8 = val8;
-  m.hyb_n_slices = (int)n_slices; m.hyb_n_reg = (int)reg.size(); m.hyb_n_pattern_slices = n_pattern_slices;
-  m.hyb_n_tiles = (int)(tiles.size() / 2);
-  // as many workgroups of each kind as are resident at 4 per CU (the 32 KiB row window): two rounds at the most
-  m.hyb_tile_blocks = 8 * (int)std::min<int64_t>(128, std::max<int64_t>(1, (m.hyb_n_tiles + 7) / 8));
-  const int sell_blocks = 8 * (int)std::min<int64_t>(128, std::max<int64_t>(1, ((int64_t)reg.size() + 63) / 64));
-  m.hyb_grid = m.hyb_tile_blocks + sell_blocks;
-  int64_t streamed_cols = 0;
-  for (int32_t sl : reg)
-    if (spat[(size_t)sl] < 0) streamed_cols += (int64_t)(qp[(size_t)sl + 1] - qp[(size_t)sl]) * 256;
-  m.hyb_stream_bytes = (int64_t)n_ent * (val8 ? 1 : 8) + 4 * streamed_cols + 12 * (int64_t)reg.size();
-  m.hyb_csr_bytes = 12 * (nnz - nnz_reg) + 8 * (int64_t)m.hyb_n_tiles + 4 * ((int64_t)n_irr * 64 + m.hyb_n_tiles);
-  m.hyb = true;
-  if (ctx->debug_upload)
-    std::fprintf(stderr, "[gmg]   layout hybrid: %d of %d slices regular (%d pattern slices, %zu patterns), %lld of %lld entries in them padded to %lld, val8 %d (%zu values); "
-                 "%d csr tiles; bytes per product: sell %lld + csr %lld (csr alone %lld); grid %d + %d\n", m.hyb_n_reg, m.hyb_n_slices, n_pattern_slices, patterns.size(),
-                 (long long)nnz_reg, (long long)nnz, (long long)n_ent, (int)val8, code_of.size(), m.hyb_n_tiles, (long long)m.hyb_stream_bytes, (long long)m.hyb_csr_bytes,
-                 (long long)(12 * nnz + 4 * (n_rows + 1)), m.hyb_tile_blocks, sell_blocks);
+// Host CSR -> device: upload_csr plans the layouts (gmg_layout.hpp) and the copy_* functions below enqueue the plan's
+// vectors as they are; they wait for nothing, so every plan has to outlive the stream's copies.
+
+// the CSR copy, with a zeroed 8-entry pad behind col and val, and the row-window tiles
+int copy_csr(gmg_context *ctx, DevCSR &m, const CsrView &A, const std::vector<int32_t> &rp, const TilePlan &T) {
+  const size_t nnz = (size_t)A.nnz(), pad = 8;
+  HIPC(upload(m.rowptr, rp, ctx->stream));
+  HIPC(upload(m.col, A.col, nnz, ctx->stream, nnz + pad));
+  HIPC(upload(m.val, A.val, nnz, ctx->stream, nnz + pad));
+  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
+  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
+  HIPC(upload(m.tile_row, T.tile_row, ctx->stream));
+  set_tiles(m, T);
   return GMG_OK;
 }
 
+// value and column streams, with 64 bytes of slack behind each (the kernels' 16-byte loads past the last quad)
+int copy_streams(gmg_context *ctx, const SellStreams &s, DevPtr<void> &vals, DevPtr<void> &cols) {
+  HIPC(vals.alloc_bytes(s.val_bytes() + 64));
+  HIPC(cols.alloc_bytes(s.col_bytes() + 64));
+  HIPC(hipMemcpyAsync(vals.get(), s.vals(), s.val_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(cols.get(), s.cols(), s.col_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  return GMG_OK;
+}
+
+int copy_sell(gmg_context *ctx, DevCSR &m, const StreamPlan &P) {
+  const SellPlan &s = P.sell;
+  const SellpPlan &w = P.sellp;
+  const LatticePlan &L = P.lat;
+  hipStream_t st = ctx->stream;
+  HIPC(upload(m.slice_ptr, s.slice_ptr, st));
+  HIPC(upload(m.slice_base, s.slice_base, st));
+  HIPC(upload(m.sell_dict, s.vd.dict, st));
+  CHK(copy_streams(ctx, s.s, m.sell_vals, m.sell_cols));
+  m.sell = true; m.val8 = s.s.val8; m.col16 = s.s.col16;
+  m.n_slices = (int)s.n_slices; m.sell_quads = s.quads; m.sell_grid = s.sell_grid;
+  if (s.pat.n_pattern_slices > 0) {
+    HIPC(upload(m.sell_spat, s.pat.spat, st));
+    HIPC(upload(m.sell_pat, s.pat.table, st));
+    m.n_patterns = (int)s.pat.list.size(); m.n_pattern_slices = s.pat.n_pattern_slices;
+    m.sellp_pid = s.sellp_pid; m.use_sellp = s.use_sellp;
+    std::copy(s.sellp_centre, s.sellp_centre + 9, m.sellp_centre);
+  }
+  if (!w.wave_ptr.empty()) HIPC(upload(m.sellp_wave_ptr, w.wave_ptr, st));
+  if (w.rowclass) {
+    HIPC(upload(m.sellp_rowcls, w.rowcls, st));
+    HIPC(upload(m.sellp_ctab, w.ctab, st));
+    if (!w.wave_rr.empty()) HIPC(upload(m.sellp_wave_rr, reinterpret_cast<const int4 *>(w.wave_rr.data()), w.wave_rr.size(), st));
+    m.rowclass = true; m.n_classes = w.n_classes;
+  }
+  m.lat_classes = L.classes;
+  if (L.planned) {
+    m.lat_nx = (int)L.nx; m.lat_nxy = (int)L.nxy; m.lat_R0 = (int)L.R0; m.lat_R1 = (int)L.R1; m.lat_W = (int)L.W;
+    m.lat_C = L.C; m.lat_K = L.K; m.lat_S = L.S; m.lat_fast_blocks = L.fast_blocks; m.lat_grid = L.grid;
+    m.lat_fast_rows = L.fast_rows; m.lat_n_gen = (int)L.gen.size(); m.lat_gen_bytes = L.gen_bytes;
+  }
+  if (L.built) {
+    HIPC(upload(m.lat_rowcls, L.rowcls, st, L.rowcls.size() + 64));
+    HIPC(upload(m.lat_ctab, L.ctab, st));
+    HIPC(upload(m.lat_gen, L.gen, st));
+    m.lattice = true;
+  }
+  return GMG_OK;
+}
+
+int copy_hybrid(gmg_context *ctx, DevCSR &m, const HybridPlan &H) {
+  hipStream_t st = ctx->stream;
+  HIPC(upload(m.hyb_qptr, H.qptr, st));
+  HIPC(upload(m.hyb_spat, H.pat.spat, st));
+  HIPC(upload(m.hyb_pat, H.pat.table, st));
+  HIPC(upload(m.hyb_tiles, H.tiles, st));
+  HIPC(upload(m.hyb_reg, H.reg, st));
+  HIPC(upload(m.hyb_dict, H.vd.dict, st));
+  CHK(copy_streams(ctx, H.s, m.hyb_vals, m.hyb_cols));
+  m.hyb = true; m.hyb_val8 = H.vd.val8;
+  m.hyb_n_slices = H.n_slices; m.hyb_n_reg = (int)H.reg.size(); m.hyb_n_pattern_slices = H.pat.n_pattern_slices;
+  m.hyb_n_tiles = H.n_tiles; m.hyb_tile_blocks = H.tile_blocks; m.hyb_grid = H.grid;
+  m.hyb_stream_bytes = H.stream_bytes; m.hyb_csr_bytes = H.csr_bytes;
+  return GMG_OK;
+}
+
+// keep_csr: the CSR copy of a SELL operator is only kept where the SGS sweeps need it (levels >= 1).  allow_hybrid: see plan_streams
 int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, const int64_t *rowptr, const int32_t *col,
                const double *val, bool keep_csr = false, bool allow_hybrid = false) {
   if (n_rows < 0 || n_cols < 0 || !rowptr) return fail(ctx, GMG_ERR_INVALID, "upload_csr: bad arguments");
@@ -652,527 +513,30 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
     return fail(ctx, GMG_ERR_UNSUPPORTED, "operator needs 64-bit device indices (nnz >= 2^31)");
   reset_keep_halo(m);
   m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
-  const bool dbg_upload = ctx->debug_upload;
-  auto t_phase = std::chrono::steady_clock::now();
-  auto phase = [&](const char *what) {
-    if (!dbg_upload) return;
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "[gmg]   upload %-14s %7.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_phase).count());
-    t_phase = now;
-  };
-  std::vector<int32_t> rp((size_t)n_rows + 1);
-  for (int64_t i = 0; i <= n_rows; ++i) {
-    if (i && rowptr[i] < rowptr[i - 1]) return fail(ctx, GMG_ERR_INVALID, "rowptr not monotone");
-    rp[(size_t)i] = (int32_t)rowptr[i];
-  }
-  for (int64_t k = 0; k < nnz; ++k)
-    if (col[k] < 0 || col[k] >= n_cols) return fail(ctx, GMG_ERR_INVALID, "column index out of range");
-  // tiles: consecutive rows whose nonzeros fit the LDS window (window start rounded down to 4)
-  std::vector<int32_t> tiles;
-  tiles.push_back(0);
-  int64_t r = 0;
-  while (r < n_rows) {
-    const int64_t ka = rowptr[r] & ~(int64_t)3;
-    int64_t e = r + 1;  // a tile always holds at least one row (possibly a "long row")
-    // rows are capped too: operators with long runs of empty rows (P^T onto the level-0 lattice)
-    // would otherwise put 10^5 rows into one workgroup
-    while (e < n_rows && rowptr[e + 1] - ka <= kTileNnz && e - r < kTileMaxRowsEarly) ++e;
-    if (rowptr[e] - ka > kTileNnz) e = r + 1;
-    tiles.push_back((int32_t)e);
-    r = e;
-  }
-  m.n_tiles = (int)tiles.size() - 1;
-  m.tiles_per_xcd = (m.n_tiles + 7) / 8;
-  int per_xcd = std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
-  m.grid = 8 * per_xcd;
-  const size_t pad = 8;
-  HIPC(m.rowptr.alloc(((size_t)n_rows + 1)));
-  HIPC(m.col.alloc(((size_t)nnz + pad)));
-  HIPC(m.val.alloc(((size_t)nnz + pad)));
-  HIPC(m.tile_row.alloc(tiles.size()));
-  HIPC(hipMemsetAsync(m.col.get() + nnz, 0, sizeof(int32_t) * pad, ctx->stream));
-  HIPC(hipMemsetAsync(m.val.get() + nnz, 0, sizeof(double) * pad, ctx->stream));
-  HIPC(hipMemcpyAsync(m.rowptr.get(), rp.data(), sizeof(int32_t) * rp.size(), hipMemcpyHostToDevice, ctx->stream));
-  if (nnz) {
-    HIPC(hipMemcpyAsync(m.col.get(), col, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipMemcpyAsync(m.val.get(), val, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-  }
-  HIPC(hipMemcpyAsync(m.tile_row.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipStreamSynchronize(ctx->stream));  // host staging buffers die here
-  m.valid = true;
+  const LayoutOptions opt = layout_options(ctx);
+  PhaseLog phase{opt.debug};
+  const CsrView A{n_rows, n_cols, rowptr, col, val};
+  if (const char *wrong = check_csr(A)) return fail(ctx, GMG_ERR_INVALID, wrong);
+  const std::vector<int32_t> rp(rowptr, rowptr + n_rows + 1);
+  const TilePlan T = plan_tiles(rowptr, n_rows);
+  StreamPlan P;
+  int rc = copy_csr(ctx, m, A, rp, T);
   phase("csr copy");
-  // SELL-64 copy when the rows are regular enough (level-0 lattice, active-mesh matrix)
-  // the SELL kernels gather through 32-bit byte offsets (c << 3 into a 2 GiB buffer descriptor): columns beyond 2^28
-  // stay on the CSR row-window kernel
-  if (n_rows >= 1024 && !ctx->disable_sell && n_cols < ((int64_t)1 << 28)) {
-    const int64_t n_slices = (n_rows + 63) / 64;
-    std::vector<int32_t> sp((size_t)n_slices + 1, 0);
-    // column patterns: a slice qualifies when all 64 rows exist and the union of (col - row) over
-    // its rows has <= 32 members that are valid columns for every row; rows lacking a member get an
-    // explicit +0.0 there (exact: x is finite), which keeps the CSR summation order
-    // (a row-partitioned operator has its ghost columns behind the owned ones, n_cols > n_rows: the slices whose columns are all
-    // owned still follow the lattice's patterns -- without them the distributed coarse CG ran on per-entry gathers, 99 us per
-    // iteration on two ranks against 34 us on one)
-    const bool allow_pat = !ctx->disable_patterns && n_cols >= n_rows;
-    std::vector<int32_t> spat((size_t)n_slices, -1);
-    std::vector<std::vector<int32_t>> patterns;
-    std::map<std::vector<int32_t>, int> pattern_id;
-    int64_t quads = 0;
-    // per slice (parallel): widest row, and the sorted union of (col - row) when the slice qualifies
-    std::vector<int32_t> slice_w((size_t)n_slices, 0);
-    std::vector<std::vector<int32_t>> slice_delta((size_t)n_slices);
-    parallel_chunks(n_slices, [&](int64_t sb, int64_t se, int) {
-      for (int64_t sidx = sb; sidx < se; ++sidx) {
-        int64_t w = 0;
-        for (int64_t r2 = sidx * 64; r2 < std::min<int64_t>(n_rows, sidx * 64 + 64); ++r2) w = std::max(w, rowptr[r2 + 1] - rowptr[r2]);
-        slice_w[(size_t)sidx] = (int32_t)w;
-        if (!(allow_pat && sidx * 64 + 64 <= n_rows)) continue;
-        std::vector<int32_t> delta;
-        for (int64_t r2 = sidx * 64; r2 < sidx * 64 + 64 && delta.size() <= 32; ++r2)
-          for (int64_t k = rowptr[r2]; k < rowptr[r2 + 1]; ++k) {
-            const int32_t d = (int32_t)(col[k] - r2);
-            auto it = std::lower_bound(delta.begin(), delta.end(), d);
-            if (it == delta.end() || *it != d) delta.insert(it, d);
-          }
-        bool ok = !delta.empty() && delta.size() <= 32;
-        if (ok) ok = sidx * 64 + delta.front() >= 0 && sidx * 64 + 63 + delta.back() < n_cols;
-        // columns must be strictly ascending inside each row for the positions to be well defined
-        for (int64_t r2 = sidx * 64; ok && r2 < sidx * 64 + 64; ++r2)
-          for (int64_t k = rowptr[r2] + 1; k < rowptr[r2 + 1]; ++k) ok = ok && col[k] > col[k - 1];
-        if (ok && (int64_t)delta.size() <= ((w + 3) / 4) * 4 + 4) slice_delta[(size_t)sidx] = std::move(delta);
-      }
-    });
-    for (int64_t sidx = 0; sidx < n_slices; ++sidx) {  // pattern ids in slice order
-      int64_t w = slice_w[(size_t)sidx];
-      if (!slice_delta[(size_t)sidx].empty()) {
-        auto ins = pattern_id.emplace(slice_delta[(size_t)sidx], (int)patterns.size());
-        if (ins.second) patterns.push_back(slice_delta[(size_t)sidx]);
-        spat[(size_t)sidx] = ins.first->second;
-        w = (int64_t)slice_delta[(size_t)sidx].size();
-      }
-      quads += (w + 3) / 4;
-      sp[(size_t)sidx + 1] = (int32_t)quads;
-    }
-    if (quads * 256 <= (int64_t)(1.12 * (double)nnz) && quads * 256 < ((int64_t)1 << 31)) {
-      slice_delta.clear();
-      phase("patterns");
-      // --- value dictionary (bit patterns, so -0.0 / NaN payloads survive)
-      const bool allow_comp = !ctx->disable_compression;
-      std::vector<double> dict;
-      std::unordered_map<uint64_t, int> code_of;
-      bool val8 = allow_comp;
-      code_of.emplace(0ull, 0);  // +0.0 is the padding value: always code 0
-      dict.push_back(0.0);
-      if (val8) {
-        // distinct bit patterns in order of first occurrence: per chunk in parallel, merged in chunk order
-        std::vector<std::vector<uint64_t>> firsts((size_t)host_threads());
-        std::vector<char> overflow((size_t)host_threads(), 0);
-        parallel_chunks(nnz, [&](int64_t kb, int64_t ke, int t) {
-          std::unordered_map<uint64_t, int> seen;
-          uint64_t last = ~0ull;
-          for (int64_t k = kb; k < ke; ++k) {
-            uint64_t bits;
-            std::memcpy(&bits, &val[k], 8);
-            if (bits == last) continue;
-            last = bits;
-            if (seen.emplace(bits, 0).second) {
-              firsts[(size_t)t].push_back(bits);
-              if (firsts[(size_t)t].size() > 256) { overflow[(size_t)t] = 1; return; }
-            }
-          }
-        });
-        for (size_t t = 0; t < firsts.size() && val8; ++t) {
-          if (overflow[t]) val8 = false;
-          for (uint64_t bits : firsts[t]) {
-            if (!val8) break;
-            if (code_of.emplace(bits, (int)dict.size()).second) {
-              double v;
-              std::memcpy(&v, &bits, 8);
-              dict.push_back(v);
-              if (dict.size() > 256) val8 = false;
-            }
-          }
-        }
-      }
-      // read-only open-addressing table for the packing threads
-      std::vector<uint64_t> ht_key(1024, 0);
-      std::vector<int16_t> ht_code(1024, -1);
-      auto ht_slot = [](uint64_t bits) { return (size_t)((bits * 0x9E3779B97F4A7C15ull) >> 54); };
-      if (val8)
-        for (const auto &kv : code_of) {
-          size_t h = ht_slot(kv.first);
-          while (ht_code[h] >= 0) h = (h + 1) & 1023;
-          ht_key[h] = kv.first; ht_code[h] = (int16_t)kv.second;
-        }
-      auto code_lookup = [&](uint64_t bits) -> uint8_t {
-        size_t h = ht_slot(bits);
-        while (ht_key[h] != bits || ht_code[h] < 0) h = (h + 1) & 1023;
-        return (uint8_t)ht_code[h];
-      };
-      phase("dictionary");
-      // --- per-slice column base, 16-bit offsets if every slice spans < 65536 columns
-      std::vector<int32_t> sbase((size_t)n_slices, 0);
-      std::vector<char> wide((size_t)host_threads(), 0);
-      parallel_chunks(n_slices, [&](int64_t sb, int64_t se, int t) {
-        for (int64_t sidx = sb; sidx < se; ++sidx) {
-          int64_t lo = INT64_MAX, hi = -1;
-          const int64_t rend = std::min<int64_t>(n_rows, sidx * 64 + 64);
-          for (int64_t r2 = sidx * 64; r2 < rend; ++r2) {
-            lo = std::min(lo, r2 < n_cols ? r2 : lo);  // the padding column is the row itself
-            hi = std::max(hi, r2 < n_cols ? r2 : hi);
-            for (int64_t k = rowptr[r2]; k < rowptr[r2 + 1]; ++k) { lo = std::min<int64_t>(lo, col[k]); hi = std::max<int64_t>(hi, col[k]); }
-          }
-          if (hi < 0) { lo = hi = 0; }
-          sbase[(size_t)sidx] = (int32_t)lo;
-          if (hi - lo > 65535) wide[(size_t)t] = 1;
-        }
-      });
-      bool col16 = allow_comp;
-      for (char wflag : wide) col16 = col16 && !wflag;
-      const size_t n_ent = (size_t)quads * 256;
-      int n_pattern_slices = 0;
-      for (int32_t v : spat) n_pattern_slices += v >= 0;
-      std::vector<double> v2(val8 ? 0 : n_ent, 0.0);
-      std::vector<uint8_t> v1(val8 ? n_ent : 0, 0);
-      std::vector<int32_t> c4(col16 ? 0 : n_ent, 0);
-      std::vector<uint16_t> c2(col16 ? n_ent : 0, 0);
-      parallel_chunks(n_slices, [&](int64_t sb, int64_t se, int) {
-      for (int64_t sidx = sb; sidx < se; ++sidx) {
-        const int64_t q0 = sp[(size_t)sidx], nq = sp[(size_t)sidx + 1] - q0;
-        for (int lane = 0; lane < 64; ++lane) {
-          const int64_t r2 = sidx * 64 + lane;
-          const int64_t k0 = r2 < n_rows ? rowptr[r2] : 0, len = r2 < n_rows ? rowptr[r2 + 1] - k0 : 0;
-          const int32_t padcol = r2 < std::min(n_rows, n_cols) ? (int32_t)r2 : sbase[(size_t)sidx];
-          const int pidx = spat[(size_t)sidx];
-          int64_t kk = 0;  // next CSR entry of this row (pattern slices walk the pattern positions)
-          for (int64_t j = 0; j < 4 * nq; ++j) {
-            const int64_t qq = q0 + j / 4, e = j & 3;
-            const size_t ov = (size_t)(((2 * qq + (e >> 1)) * 64 + lane) * 2 + (e & 1));  // double2-pair layout
-            const size_t oc = (size_t)((qq * 64 + lane) * 4 + e);                          // 4-per-lane layout
-            int32_t cj;
-            double vj;
-            if (pidx >= 0) {
-              const auto &dl = patterns[(size_t)pidx];
-              if (j < (int64_t)dl.size() && kk < len && col[k0 + kk] - r2 == dl[(size_t)j]) { cj = col[k0 + kk]; vj = val[k0 + kk]; ++kk; }
-              else { cj = (int32_t)(j < (int64_t)dl.size() ? r2 + dl[(size_t)j] : r2); vj = 0.0; }
-            } else {
-              cj = j < len ? col[k0 + j] : padcol;
-              vj = j < len ? val[k0 + j] : 0.0;
-            }
-            if (val8) { uint64_t bits; std::memcpy(&bits, &vj, 8); v1[oc] = code_lookup(bits); }
-            else v2[ov] = vj;
-            if (col16) c2[oc] = (uint16_t)(cj - sbase[(size_t)sidx]);
-            else c4[oc] = cj;
-          }
-        }
-      }
-      });
-      dict.resize(256, 0.0);
-      HIPC(m.slice_ptr.alloc(sp.size()));
-      HIPC(m.slice_base.alloc(sbase.size()));
-      HIPC(m.sell_dict.alloc(256));
-      const size_t vbytes = val8 ? v1.size() : v2.size() * 8, cbytes = col16 ? c2.size() * 2 : c4.size() * 4;
-      HIPC(m.sell_vals.alloc_bytes(vbytes + 64));
-      HIPC(m.sell_cols.alloc_bytes(cbytes + 64));
-      HIPC(hipMemcpyAsync(m.slice_ptr.get(), sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.slice_base.get(), sbase.data(), sizeof(int32_t) * sbase.size(), hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_dict.get(), dict.data(), sizeof(double) * 256, hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_vals.get(), val8 ? (const void *)v1.data() : (const void *)v2.data(), vbytes, hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipMemcpyAsync(m.sell_cols.get(), col16 ? (const void *)c2.data() : (const void *)c4.data(), cbytes, hipMemcpyHostToDevice, ctx->stream));
-      HIPC(hipStreamSynchronize(ctx->stream));
-      m.val8 = val8; m.col16 = col16;
-      if (n_pattern_slices > 0) {
-        std::vector<int32_t> table(patterns.size() * 32, 0);
-        for (size_t pi = 0; pi < patterns.size(); ++pi)
-          for (size_t j = 0; j < 32; ++j) table[pi * 32 + j] = j < patterns[pi].size() ? patterns[pi][j] : 0;  // padding: own row, value +0.0
-        HIPC(m.sell_spat.alloc(spat.size()));
-        HIPC(m.sell_pat.alloc(table.size()));
-        HIPC(hipMemcpyAsync(m.sell_spat.get(), spat.data(), sizeof(int32_t) * spat.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPC(hipMemcpyAsync(m.sell_pat.get(), table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIPC(hipStreamSynchronize(ctx->stream));
-        m.n_patterns = (int)patterns.size();
-        m.n_pattern_slices = n_pattern_slices;
-        // the most frequent pattern made of nine runs of three consecutive columns (the x-1, x, x+1
-        // neighbours of a 27-point lattice row) is served by spmv_sellp_kernel
-        std::vector<size_t> uses(patterns.size(), 0);
-        for (size_t sl = 0; sl < n_slices; ++sl)
-          if (spat[sl] >= 0) ++uses[(size_t)spat[sl]];
-        size_t n_run_slices = 0;
-        m.sellp_pid = -1;
-        for (size_t pi = 0; pi < patterns.size(); ++pi) {
-          const auto &dl = patterns[pi];
-          bool ok = dl.size() == 27;
-          for (size_t j = 0; ok && j < dl.size(); j += 3) ok = dl[j + 1] == dl[j] + 1 && dl[j + 2] == dl[j] + 2;
-          if (!ok || uses[pi] <= n_run_slices) continue;
-          n_run_slices = uses[pi];
-          m.sellp_pid = (int)pi;
-          for (size_t u = 0; u < 9; ++u) m.sellp_centre[u] = dl[3 * u + 1];
-        }
-        // a streamed slice costs ~4 pattern slices here against ~2.2 in the per-entry kernel: worth it up to ~40 % streamed slices
-        m.use_sellp = val8 && !ctx->disable_sellp && n_run_slices * 10 >= n_slices * 7;
-      }
-      m.sell = true;
-      m.n_slices = (int)n_slices;
-      m.sell_quads = quads;
-      phase("sell pack+copy");
-      // one wave per >= 1 slice; at most kMaxPartials workgroups (one reduction partial each)
-      const int per_xcd = (int)((n_slices + 7) / 8);
-      m.sell_grid = 8 * std::min(kMaxPartials / 8, std::max(1, (per_xcd + 3) / 4));
-      if (ctx->sell_grid > 0) m.sell_grid = std::max(8, ctx->sell_grid / 8 * 8);
-      if (m.use_sellp) {
-        // as many workgroups as are resident at the kernel's register budget: one round
-        if (ctx->sell_grid <= 0) m.sell_grid = std::min(m.sell_grid, 256 * kSellpWaves);
-        // contiguous slice ranges per wave, balanced by cost: a streamed slice (one memory round trip
-        // per quad) costs about four pattern slices
-        const double other_cost = ctx->sellp_cost;
-        const int n_waves = m.sell_grid * 4;
-        std::vector<double> cost(n_slices + 1, 0.0);
-        for (size_t sl = 0; sl < n_slices; ++sl)
-          cost[sl + 1] = cost[sl] + (spat[sl] == m.sellp_pid ? 1.0 : std::max(0.25, other_cost * (double)(sp[sl + 1] - sp[sl]) / 7.0));
-        std::vector<int32_t> wp((size_t)n_waves + 1, 0);
-        size_t sl = 0;
-        int longest = 0;
-        for (int wv = 1; wv <= n_waves; ++wv) {
-          const double target = cost[n_slices] * (double)wv / (double)n_waves;
-          while (sl < n_slices && cost[sl + 1] <= target + 1e-9) ++sl;
-          if (wv == n_waves) sl = n_slices;
-          wp[(size_t)wv] = (int32_t)sl;
-          longest = std::max(longest, wp[(size_t)wv] - wp[(size_t)wv - 1]);
-        }
-        if (longest > 64) m.use_sellp = false;  // slice metadata lives in the 64 lanes
-        else {
-          // ---- row classes of the run-pattern slices (N4): the 27-tuple of value codes of a row; a lattice operator
-          // has a few dozen of them.  Too many classes (> kSellpMaxClasses): the per-entry codes stay in use.
-          if (!ctx->disable_rowclass) {
-            std::vector<uint8_t> rowcls((size_t)n_rows, 0);
-            std::map<std::array<uint8_t, 27>, int> cls_of;
-            std::vector<double> ctab;
-            bool ok = true;
-            for (size_t s2 = 0; s2 < (size_t)n_slices && ok; ++s2) {
-              if (spat[s2] != m.sellp_pid) continue;
-              for (int lane = 0; lane < 64 && ok; ++lane) {
-                std::array<uint8_t, 27> key;
-                for (int j = 0; j < 27; ++j) key[(size_t)j] = v1[(size_t)((((int64_t)sp[s2] + j / 4) * 64 + lane) * 4 + (j & 3))];
-                auto ins = cls_of.emplace(key, (int)cls_of.size());
-                if (ins.second) {
-                  if ((int)cls_of.size() > kSellpMaxClasses) { ok = false; break; }
-                  for (int j = 0; j < 27; ++j) ctab.push_back(dict[key[(size_t)j]]);
-                }
-                rowcls[s2 * 64 + (size_t)lane] = (uint8_t)ins.first->second;
-              }
-            }
-            if (ok && !cls_of.empty()) {
-              HIPC(m.sellp_rowcls.alloc_bytes(rowcls.size()));
-              HIPC(m.sellp_ctab.alloc(ctab.size()));
-              HIPC(hipMemcpyAsync(m.sellp_rowcls.get(), rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
-              HIPC(hipMemcpyAsync(m.sellp_ctab.get(), ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
-              HIPC(hipStreamSynchronize(ctx->stream));
-              m.rowclass = true;
-              m.n_classes = (int)cls_of.size();
-              // waves whose slices are all run-pattern slices need no slice metadata (flag in their wave_ptr entry)
-              for (int wv = 0; wv < n_waves; ++wv) {
-                bool all = wp[(size_t)wv] < wp[(size_t)wv + 1];
-                for (int32_t s2 = wp[(size_t)wv]; s2 < wp[(size_t)wv + 1] && all; ++s2) all = spat[(size_t)s2] == m.sellp_pid;
-                if (all) wp[(size_t)wv] |= kSellpFastWave;
-              }
-              // Large operators: the slices of consecutive fast waves of one XCD are dealt round-robin in pairs, so that at
-              // any time the XCD's waves sit inside a window of ~2 W slices (their x working set: three lattice planes
-              // instead of the XCD's whole eighth of x, which is then fetched once).  The threshold is a MEASURED
-              // crossover in rows, not the L2 size: an XCD's eighth of x leaves its 4 MiB L2 at 4 Mi rows (8 x 4 MiB / 8 B),
-              // and below ~3 Mi rows the contiguous order was never slower (121^3 = 1.77 M rows: x/8 = 1.8 MB per XCD stays
-              // L2-resident, 17.0 us either way; 5.18 M rows: 50.7 -> 41.0 us; 201^3: PMC traffic 454 -> 197 MB).
-              const bool rr = ctx->sellp_rr == 1 || (ctx->sellp_rr == 0 && n_rows > (int64_t)(3 << 20));
-              if (rr) {
-                const int per_xcd = n_waves / 8;
-                std::vector<int4> desc((size_t)n_waves, int4{0, 0, 0, -1});
-                for (int x = 0; x < 8; ++x) {
-                  int a0 = x * per_xcd;
-                  while (a0 < (x + 1) * per_xcd) {
-                    if (!(wp[(size_t)a0] & kSellpFastWave)) { ++a0; continue; }
-                    int b0 = a0;
-                    while (b0 + 1 < (x + 1) * per_xcd && (wp[(size_t)b0 + 1] & kSellpFastWave)) ++b0;
-                    const int wn = b0 - a0 + 1;
-                    const int32_t S0 = wp[(size_t)a0] & (kSellpFastWave - 1), S1 = wp[(size_t)b0 + 1] & (kSellpFastWave - 1);
-                    const int n_pairs = (S1 - S0) / 2;
-                    if (wn >= 2 && n_pairs >= wn) {
-                      for (int r = 0; r < wn; ++r) {
-                        desc[(size_t)(a0 + r)] = int4{S0 + 2 * r, 2 * wn, (n_pairs - r + wn - 1) / wn, -1};
-                        wp[(size_t)(a0 + r)] |= kSellpStrided;
-                      }
-                      if ((S1 - S0) & 1) desc[(size_t)b0].w = S1 - 1;
-                    }
-                    a0 = b0 + 1;
-                  }
-                }
-                HIPC(m.sellp_wave_rr.alloc(desc.size()));
-                HIPC(hipMemcpyAsync(m.sellp_wave_rr.get(), desc.data(), sizeof(int4) * desc.size(), hipMemcpyHostToDevice, ctx->stream));
-              }
-            }
-          }
-          HIPC(m.sellp_wave_ptr.alloc(wp.size()));
-          HIPC(hipMemcpyAsync(m.sellp_wave_ptr.get(), wp.data(), sizeof(int32_t) * wp.size(), hipMemcpyHostToDevice, ctx->stream));
-          HIPC(hipStreamSynchronize(ctx->stream));
-        }
-      }
-      // ---- lattice interior (gmg_lattice.hpp): the nine runs are the (dz, dy) lines of an nx x ny x nz vertex lattice
-      // numbered lexicographically -> the rows whose columns are all owned lattice neighbours are walked plane by plane
-      // from a class table; everything else stays on the SELL streams.
-      if (val8 && !ctx->disable_lattice && m.sellp_pid >= 0 && n_rows == n_cols_owned(n_rows, n_cols) && n_rows < ((int64_t)1 << 28)) {
-        const int64_t nx = m.sellp_centre[5] - m.sellp_centre[4], nxy = m.sellp_centre[7] - m.sellp_centre[4];
-        bool lat_ok = nx >= 3 && nxy >= 3 * nx;
-        for (int u = 0; u < 9 && lat_ok; ++u) lat_ok = m.sellp_centre[u] == (u / 3 - 1) * nxy + (u % 3 - 1) * nx;
-        const int64_t reach = nxy + nx + 1;
-        if (lat_ok && n_rows > 4 * reach + 256) {
-          // per row: are all stored columns owned lattice neighbours (27 offsets), and is every offset in range?
-          std::vector<char> row_ok((size_t)n_rows, 0);
-          parallel_chunks(n_rows, [&](int64_t rb2, int64_t re2, int) {
-            for (int64_t r2 = rb2; r2 < re2; ++r2) {
-              // (lane 0 of a unit holds the two rows in front of the unit's first row: their lowest neighbour is row - 2 - reach;
-              // the highest index read is n_rows + 1: every vector has two spare entries)
-              bool ok = r2 >= reach + 2 && r2 + reach < n_rows;
-              for (int64_t k = rowptr[r2]; k < rowptr[r2 + 1] && ok; ++k) {
-                const int64_t t = (int64_t)col[k] - r2 + reach;
-                ok = col[k] < n_rows && t >= 0 && t / nxy <= 2 && (t % nxy) / nx <= 2 && (t % nxy) % nx <= 2;
-              }
-              row_ok[(size_t)r2] = ok ? 1 : 0;
-            }
-          });
-          // longest run of good rows.  A lexicographic numbering gives one run over the whole interior; deal.II's
-          // cell-by-cell numbering (the host side's) breaks it at every plane: the first three lines of a plane (and the
-          // first three planes) are numbered in first-touch order.  So the interior is a WINDOW of W rows that repeats with
-          // the plane stride: rows R0 + k nxy + [0, W), k < K.
-          int64_t best_b = 0, best_e = 0, cur_b = -1;
-          for (int64_t r2 = 0; r2 <= n_rows; ++r2) {
-            const bool ok = r2 < n_rows && row_ok[(size_t)r2];
-            if (ok && cur_b < 0) cur_b = r2;
-            if (!ok && cur_b >= 0) {
-              if (r2 - cur_b > best_e - best_b) { best_b = cur_b; best_e = r2; }
-              cur_b = -1;
-            }
-          }
-          int64_t R0 = best_b, R1 = best_e, Wd = std::min<int64_t>(best_e - best_b, nxy), Kp = 0;
-          if (best_e - best_b >= nxy) {
-            Kp = (best_e - best_b + nxy - 1) / nxy;  // the last plane step may be cut by R1
-          } else if (Wd > 0) {
-            std::vector<int32_t> bad_before((size_t)n_rows + 1, 0);  // prefix count of bad rows
-            for (int64_t r2 = 0; r2 < n_rows; ++r2) bad_before[(size_t)r2 + 1] = bad_before[(size_t)r2] + (row_ok[(size_t)r2] ? 0 : 1);
-            auto window_ok = [&](int64_t b2) { return b2 >= 0 && b2 + Wd <= n_rows && bad_before[(size_t)(b2 + Wd)] == bad_before[(size_t)b2]; };
-            int64_t lo = best_b, hi = best_b;
-            while (window_ok(lo - nxy)) lo -= nxy;
-            while (window_ok(hi + nxy)) hi += nxy;
-            R0 = lo; Kp = (hi - lo) / nxy + 1; R1 = hi + Wd;
-          }
-          const int64_t n_fast = Wd == nxy ? R1 - R0 : Kp * Wd;
-          if (ctx->debug_upload)
-            std::fprintf(stderr, "[gmg]   lattice rows: longest run [%lld, %lld) -> window of %lld rows x %lld planes from row %lld: %lld of %lld rows\n", (long long)best_b, (long long)best_e,
-                         (long long)Wd, (long long)Kp, (long long)R0, (long long)n_fast, (long long)n_rows);
-          auto is_fast = [&](int64_t r2) { return r2 >= R0 && r2 < R1 && (r2 - R0) % nxy < Wd; };
-          // what the marching waves read: rows R0 - 2 - reach .. R1 + 1 + reach - 1 of x (lane 0 / lane 63 of a unit sit two
-          // rows outside it): checked here, once, instead of trusting the row test above
-          const bool reads_inside = R0 - 2 - reach >= 0 && R1 + reach <= n_rows;
-          if (n_fast >= n_rows / 2 && Wd >= 2 && reads_inside) {
-            // classes: the 27 value codes of a row by offset position (0 = +0.0 where the row stores nothing)
-            std::vector<uint8_t> rowcls((size_t)n_rows, 0);
-            const int nt = host_threads();
-            std::vector<std::map<std::array<uint8_t, 27>, int>> local_cls((size_t)nt);
-            std::vector<std::vector<std::array<uint8_t, 27>>> local_keys((size_t)nt);
-            std::vector<std::array<int64_t, 2>> local_rng((size_t)nt, {0, 0});
-            std::vector<std::vector<int32_t>> local_id((size_t)nt);
-            parallel_chunks(R1 - R0, [&](int64_t cb, int64_t ce, int t) {
-              auto &M = local_cls[(size_t)t];
-              local_rng[(size_t)t] = {R0 + cb, R0 + ce};
-              local_id[(size_t)t].resize((size_t)(ce - cb));
-              for (int64_t r2 = R0 + cb; r2 < R0 + ce; ++r2) {
-                std::array<uint8_t, 27> key;
-                key.fill(0);
-                if (!is_fast(r2)) { local_id[(size_t)t][(size_t)(r2 - R0 - cb)] = -1; continue; }
-                for (int64_t k = rowptr[r2]; k < rowptr[r2 + 1]; ++k) {
-                  const int64_t t2 = (int64_t)col[k] - r2 + reach;
-                  const int pos = (int)((t2 / nxy) * 9 + ((t2 % nxy) / nx) * 3 + (t2 % nxy) % nx);
-                  uint64_t bits;
-                  std::memcpy(&bits, &val[k], 8);
-                  key[(size_t)pos] = code_lookup(bits);
-                }
-                auto ins = M.emplace(key, (int)M.size());
-                if (ins.second) local_keys[(size_t)t].push_back(key);
-                local_id[(size_t)t][(size_t)(r2 - R0 - cb)] = ins.first->second;
-              }
-            });
-            std::map<std::array<uint8_t, 27>, int> cls_of;
-            std::vector<double> ctab;
-            bool cls_ok = true;
-            for (int t = 0; t < nt && cls_ok; ++t) {
-              std::vector<int> remap(local_keys[(size_t)t].size(), 0);
-              for (size_t q = 0; q < local_keys[(size_t)t].size() && cls_ok; ++q) {
-                auto ins = cls_of.emplace(local_keys[(size_t)t][q], (int)cls_of.size());
-                if (ins.second) {
-                  if ((int)cls_of.size() > kLatMaxClasses) { cls_ok = false; m.lat_classes = -(int)cls_of.size(); break; }
-                  for (int j = 0; j < 27; ++j) ctab.push_back(dict[local_keys[(size_t)t][q][(size_t)j]]);
-                }
-                remap[q] = ins.first->second;
-              }
-              if (!cls_ok) break;
-              for (int64_t r2 = local_rng[(size_t)t][0]; r2 < local_rng[(size_t)t][1]; ++r2) {
-                const int32_t id = local_id[(size_t)t][(size_t)(r2 - local_rng[(size_t)t][0])];
-                if (id >= 0) rowcls[(size_t)r2] = (uint8_t)remap[(size_t)id];
-              }
-            }
-            if (cls_ok && !cls_of.empty()) {
-              std::vector<int32_t> gen;
-              int64_t gen_bytes = 0;
-              for (int64_t sl = 0; sl < n_slices; ++sl) {
-                bool all_fast = true;  // a slice with any row outside the interior is served from the streams (its interior rows masked)
-                for (int64_t r2 = sl * 64; r2 < std::min<int64_t>(n_rows, sl * 64 + 64) && all_fast; ++r2) all_fast = is_fast(r2);
-                if (!all_fast) {
-                  gen.push_back((int32_t)sl);
-                  gen_bytes += (int64_t)(sp[(size_t)sl + 1] - sp[(size_t)sl]) * 256 * (1 + (spat[(size_t)sl] >= 0 ? 0 : (col16 ? 2 : 4))) + 8;
-                }
-              }
-              m.lat_nx = (int)nx; m.lat_nxy = (int)nxy; m.lat_R0 = (int)R0; m.lat_R1 = (int)R1; m.lat_W = (int)Wd;
-              m.lat_C = (int)((Wd + kLatRowsPerUnit - 1) / kLatRowsPerUnit);
-              m.lat_K = (int)Kp;
-              m.lat_fast_rows = n_fast;
-              const int gen_blocks = lattice_grid(ctx, m, gen.size());
-              m.lat_grid = m.lat_fast_blocks + gen_blocks;
-              m.lat_n_gen = (int)gen.size();
-              m.lat_gen_bytes = gen_bytes;
-              m.lat_classes = (int)cls_of.size();
-              if (m.lat_grid <= kMaxPartials) {
-                HIPC(m.lat_rowcls.alloc_bytes(rowcls.size() + 64));
-                HIPC(m.lat_ctab.alloc(ctab.size()));
-                HIPC(m.lat_gen.alloc(std::max<size_t>(gen.size(), 1)));
-                HIPC(hipMemcpyAsync(m.lat_rowcls.get(), rowcls.data(), rowcls.size(), hipMemcpyHostToDevice, ctx->stream));
-                HIPC(hipMemcpyAsync(m.lat_ctab.get(), ctab.data(), sizeof(double) * ctab.size(), hipMemcpyHostToDevice, ctx->stream));
-                if (!gen.empty()) HIPC(hipMemcpyAsync(m.lat_gen.get(), gen.data(), sizeof(int32_t) * gen.size(), hipMemcpyHostToDevice, ctx->stream));
-                HIPC(hipStreamSynchronize(ctx->stream));
-                m.lattice = true;
-                if (ctx->debug_upload)
-                  std::fprintf(stderr, "[gmg]   lattice interior: nx %d nxy %d rows [%d, %d) of %lld, %d classes, %d columns x %d steps, %d segments per XCD slab, grid %d + %d, %d slices outside\n",
-                               m.lat_nx, m.lat_nxy, m.lat_R0, m.lat_R1, (long long)n_rows, m.lat_classes, m.lat_C, m.lat_K, m.lat_S, m.lat_fast_blocks, gen_blocks, m.lat_n_gen);
-              }
-            }
-          }
-        }
-        if (ctx->debug_upload && !m.lattice)
-          std::fprintf(stderr, "[gmg]   lattice interior not used: nx %lld nxy %lld lattice-shaped %d rows %lld reach %lld classes %d\n", (long long)nx, (long long)nxy, (int)lat_ok,
-                       (long long)n_rows, (long long)reach, m.lat_classes);
-        phase("lattice plan");
-      }
-      if (!keep_csr) {  // the CSR copy is only kept where the SGS sweeps need it (levels >= 1)
-        m.col.reset(); m.val.reset(); m.tile_row.reset();
-      }
-    } else if (allow_hybrid && !ctx->disable_hybrid && !m.halo.active) {  // (the system matrix only: its product is the one that is HBM bound)
-      phase("patterns");
-      CHK(build_hybrid(ctx, m, n_rows, n_cols, rowptr, col, val, slice_w, slice_delta));
-      phase("hybrid pack+copy");
-    }
+  if (rc == GMG_OK) {
+    P = plan_streams(A, opt, allow_hybrid && !m.halo.active, phase);
+    rc = P.sell.built ? copy_sell(ctx, m, P) : P.hyb.built ? copy_hybrid(ctx, m, P.hyb) : GMG_OK;
   }
+  const hipError_t waited = hipStreamSynchronize(ctx->stream);  // rp, T and P are read by the copies until here
+  if (rc != GMG_OK) return rc;
+  HIPC(waited);
+  m.valid = true;
+  if (m.sell && !keep_csr) { m.col.reset(); m.val.reset(); m.tile_row.reset(); }
   phase("finish");
-  if (ctx->debug_upload)
+  if (opt.debug)
     std::fprintf(stderr, "[gmg] operator %lld x %lld nnz %lld: tiles %d grid %d sell %d val8 %d col16 %d sell_grid %d patterns %d pattern_slices %d/%d\n", (long long)n_rows,
                  (long long)n_cols, (long long)nnz, m.n_tiles, m.grid, (int)m.sell, (int)m.val8, (int)m.col16, m.sell_grid, m.n_patterns, m.n_pattern_slices, m.n_slices);
-  if (ctx->debug_upload && m.rowclass) std::fprintf(stderr, "[gmg]   row classes of the run-pattern slices: %d\n", m.n_classes);
-  if (ctx->debug_upload && !m.hyb) std::fprintf(stderr, "[gmg]   layout %s\n", m.sell ? "sell" : "csr");
+  if (opt.debug && m.rowclass) std::fprintf(stderr, "[gmg]   row classes of the run-pattern slices: %d\n", m.n_classes);
+  if (opt.debug && !m.hyb) std::fprintf(stderr, "[gmg]   layout %s\n", m.sell ? "sell" : "csr");
   return GMG_OK;
 }
 
@@ -3340,31 +2704,12 @@ void release_operators(gmg_context *ctx) {
   drop_coarse_direct(ctx);
 }
 
-// tiles of the CSR row-window kernel: consecutive rows whose nonzeros fit the LDS window (as in upload_csr)
-template <class RP>
-std::vector<int32_t> window_tiles(const RP *rowptr, int64_t n_rows) {
-  std::vector<int32_t> tiles;
-  tiles.push_back(0);
-  int64_t r = 0;
-  while (r < n_rows) {
-    const int64_t ka = (int64_t)rowptr[r] & ~(int64_t)3;
-    int64_t e = r + 1;
-    while (e < n_rows && (int64_t)rowptr[e + 1] - ka <= kTileNnz && e - r < kTileMaxRowsEarly) ++e;
-    if ((int64_t)rowptr[e] - ka > kTileNnz) e = r + 1;
-    tiles.push_back((int32_t)e);
-    r = e;
-  }
-  return tiles;
-}
-
 // a CSR the device formed in place (rowptr / col / val of m): its sizes and the row-window tiling from the row pointers
 int tile_device_csr(gmg_context *ctx, DevCSR &m, const std::vector<int32_t> &rp, int64_t n_rows, int64_t n_cols, int64_t nnz) {
-  const std::vector<int32_t> tiles = window_tiles(rp.data(), n_rows);
+  const TilePlan T = plan_tiles(rp.data(), n_rows);
   m.n_rows = n_rows; m.n_cols = n_cols; m.nnz = nnz;
-  m.n_tiles = (int)tiles.size() - 1;
-  m.tiles_per_xcd = (m.n_tiles + 7) / 8;
-  m.grid = 8 * std::min(kMaxPartials / 8, std::max(1, m.tiles_per_xcd));
-  HIPC(upload(m.tile_row, tiles, ctx->stream));
+  set_tiles(m, T);
+  HIPC(upload(m.tile_row, T.tile_row, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   CHK(launch_status(ctx));
   m.valid = true;
@@ -3815,7 +3160,10 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   m.lat_fast_rows = m.lat_R1 - m.lat_R0;
   m.lat_n_gen = (m.lat_R0 + 63) / 64 + (int)((n - m.lat_R1 + 63) / 64);
   m.lat_gen_bytes = (int64_t)m.lat_n_gen * 64;
-  m.lat_grid = lattice_grid(ctx, m, (size_t)m.lat_n_gen);
+  LatticePlan grid;
+  grid.C = m.lat_C; grid.K = m.lat_K;
+  m.lat_grid = lattice_grid(layout_options(ctx), grid, (size_t)m.lat_n_gen);
+  m.lat_S = grid.S; m.lat_fast_blocks = grid.fast_blocks;
   m.lat_grid += m.lat_fast_blocks;
   if (m.lat_grid > kMaxPartials) return fail(ctx, GMG_ERR_UNSUPPORTED, "gmg_set_level_matrix_lattice: grid exceeds the reduction partials");
   m.valid = true;
@@ -3940,12 +3288,9 @@ int gmg_build_transfer(gmg_context *ctx, int level, int dim, int64_t n_coarse, c
     std::vector<int32_t> rp((size_t)m->n_rows + 1);
     if (hipMemcpyAsync(rp.data(), m->rowptr.get(), sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = GMG_ERR_HIP; break; }
-    const std::vector<int32_t> tiles = window_tiles(rp.data(), m->n_rows);
-    m->n_tiles = (int)tiles.size() - 1;
-    m->tiles_per_xcd = (m->n_tiles + 7) / 8;
-    m->grid = 8 * std::min(kMaxPartials / 8, std::max(1, m->tiles_per_xcd));
-    if (m->tile_row.alloc(tiles.size()) != hipSuccess ||
-        hipMemcpyAsync(m->tile_row.get(), tiles.data(), sizeof(int32_t) * tiles.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+    const TilePlan T = plan_tiles(rp.data(), m->n_rows);
+    set_tiles(*m, T);
+    if (upload(m->tile_row, T.tile_row, ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess) { rc = GMG_ERR_HIP; break; }
     m->valid = true;
   }

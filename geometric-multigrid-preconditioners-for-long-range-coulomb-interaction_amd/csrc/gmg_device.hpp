@@ -18,12 +18,12 @@
 
 #include <type_traits>
 
+#include "gmg_layout.hpp"  // the layout constants the kernels share with the host-side planner
+
 namespace gmg {
 
 constexpr int kThreads = 256;      // 4 waves
-constexpr int kTileNnz = 4096;     // LDS row window, doubles (32 KiB) -> 4 workgroups / CU
 constexpr int kPasses = kTileNnz / (kThreads * 4);
-constexpr int kMaxPartials = 2048; // upper bound of any grid that emits reduction partials
 
 // ---------------------------------------------------------------- reductions
 
@@ -631,7 +631,6 @@ __global__ __launch_bounds__(kThreads) void spmv_hybrid_kernel(HybArgs h) {
 // scalar load: nine vector loads per slice instead of 27.  Products are still added in CSR order
 // with the exact dictionary values, so the result is bit-identical.  Slices with any other pattern
 // (the boundary of the numbering) take a plain streamed loop.
-constexpr int kSellpMaxClasses = 96;  // row classes (27 coefficients each) the pattern-run kernel keeps in LDS: 20 KB, 6 workgroups / CU
 
 struct SellPatArgs {
   SellArgs sa;
@@ -675,9 +674,6 @@ __device__ __forceinline__ double lane_double(double v, int l) {  // l: wave-uni
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
-constexpr int kSellpWaves = 4;  // resident waves per SIMD (= workgroups per CU) the register budget of the kernel is set for
-constexpr int kSellpStrided = 0x20000000;   // flag in wave_ptr[w]: the wave's pairs of slices are described by wave_rr[w]
-constexpr int kSellpFastWave = 0x40000000;  // flag in wave_ptr[w]: every slice of wave w is a run-pattern slice with row classes
 
 // RC (row classes): on a lattice the rows of the run-pattern slices have few distinct coefficient
 // vectors (interior, next to a boundary face / edge / corner, Dirichlet rows).  Instead of one 8-bit code per ENTRY

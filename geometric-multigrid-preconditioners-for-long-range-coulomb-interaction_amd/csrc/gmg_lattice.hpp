@@ -30,10 +30,7 @@
 
 namespace gmg {
 
-constexpr int kLatMaxClasses = 128;  // 27 doubles each in LDS: 27.6 KB (125 = the position types of gmg_set_level_matrix_lattice)
-constexpr int kLatRowsPerUnit = 124;
 constexpr int kLatAhead = 1;         // plane steps of loads in flight beyond the one being summed
-constexpr int kLatWavesPerSimd = 4;  // register budget of the kernel (128 VGPRs): the window of planes lives in registers
 
 struct LatArgs {
   SellPatArgs pa;         // SELL streams + vectors (pa.sa.a): the slices outside [R0, R1) are served from them
