@@ -8,6 +8,7 @@
 // :938-1017 as restated in SURVEY.md 3.2.
 #include "../../include/gmg_coulomb.h"
 #include "gmg_device.hpp"
+#include "gmg_sgs_layout.hpp"
 #include "gmg_sgs.hpp"
 #include "gmg_sgs_phase.hpp"
 #include "gmg_sgs_dep.hpp"
@@ -538,25 +539,6 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
   if (opt.debug && m.rowclass) std::fprintf(stderr, "[gmg]   row classes of the run-pattern slices: %d\n", m.n_classes);
   if (opt.debug && !m.hyb) std::fprintf(stderr, "[gmg]   layout %s\n", m.sell ? "sell" : "csr");
   return GMG_OK;
-}
-
-// stable transpose: row j of A^T lists the entries of column j in ascending source row,
-// i.e. the order in which the sequential scatter of Tvmult / restrict_and_add adds them.
-void transpose_host(int64_t n_rows, int64_t n_cols, const int64_t *rp, const int32_t *col, const double *val,
-                    std::vector<int64_t> &trp, std::vector<int32_t> &tcol, std::vector<double> &tval) {
-  const int64_t nnz = rp[n_rows];
-  trp.assign((size_t)n_cols + 1, 0);
-  for (int64_t k = 0; k < nnz; ++k) trp[(size_t)col[k] + 1]++;
-  for (int64_t j = 0; j < n_cols; ++j) trp[(size_t)j + 1] += trp[(size_t)j];
-  tcol.resize((size_t)nnz);
-  tval.resize((size_t)nnz);
-  std::vector<int64_t> pos(trp.begin(), trp.end() - 1);
-  for (int64_t i = 0; i < n_rows; ++i)
-    for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
-      const int64_t p = pos[(size_t)col[k]]++;
-      tcol[(size_t)p] = (int32_t)i;
-      tval[(size_t)p] = val[k];
-    }
 }
 
 int alloc_vec(gmg_context *ctx, DevPtr<double> &p, int64_t n) {
@@ -1389,268 +1371,6 @@ int setup_diag(gmg_context *ctx, int64_t n, const int64_t *rp, const int32_t *co
   return GMG_OK;
 }
 
-// ---- where the SSOR blocks are cut ("Block boundaries").  Modelled sweep time of a block of consecutive rows:
-//   cost = kSsorStepNs * sub-steps + stream bytes / kSsorBytesPerNs
-// sub-steps: both directions walk the stages of the block's recurrence stage(i) = 1 + max stage(j) over the coupled j in
-// [rb, i), at most kPhMaxRows rows of one stage per step -- the count setup_sgs_wave makes for the four-wave sweep.  Stream:
-// the records scale with rows x width, kSsorRowBytes per coupled row plus kSsorEntryBytes per in-block entry of it (both
-// directions; 73 MB for the 92 164 coupled rows of the 64 k-atom level 1).  Uncoupled rows (the prepass) cost nothing.
-constexpr double kSsorStepNs = 240.0;     // one dependent step of the four-wave sweep
-constexpr double kSsorBytesPerNs = 48.0;  // one CU streams ~20 B per clock at 2.4 GHz
-constexpr int64_t kSsorRowBytes = 64, kSsorEntryBytes = 28;
-
-// Pattern of the entries that couple (stored value != 0, or every stored entry without values) and its transpose.
-struct SsorPattern {
-  int64_t n = 0;
-  std::vector<int64_t> rp, trp;
-  std::vector<int32_t> col, tcol;
-  SsorPattern(int64_t n_, const int64_t *rp_, const int32_t *col_, const double *val) : n(n_) {
-    rp.assign((size_t)n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-      for (int64_t k = rp_[i]; k < rp_[i + 1]; ++k)
-        if (!val || val[k] != 0.0) col.push_back(col_[k]);
-      rp[(size_t)i + 1] = (int64_t)col.size();
-    }
-    std::vector<double> ones(col.size(), 1.0), tval;
-    transpose_host(n, n, rp.data(), col.data(), ones.data(), trp, tcol, tval);
-  }
-};
-
-// The model of one block, grown a row at a time (add() never lowers the cost: the greedy cut below relies on it).
-struct SsorBlockModel {
-  const SsorPattern &P;
-  std::vector<int32_t> stage, ent;  // per row of the block: stage, in-block entries so far
-  std::vector<char> coupled;
-  std::vector<int64_t> cnt;          // coupled rows per stage
-  int64_t rb = 0, steps = 0, bytes = 0;
-  explicit SsorBlockModel(const SsorPattern &p) : P(p), stage((size_t)p.n, 0), ent((size_t)p.n, 0), coupled((size_t)p.n, 0) {}
-  void reset(int64_t r) { rb = r; steps = bytes = 0; cnt.clear(); }
-  double cost_ns() const { return kSsorStepNs * (double)steps + (double)bytes / kSsorBytesPerNs; }
-  void put(int32_t s) {
-    if ((size_t)s >= cnt.size()) cnt.resize((size_t)s + 1, 0);
-    if (cnt[(size_t)s]++ % kPhMaxRows == 0) steps += 2;
-  }
-  void add(int64_t i) {
-    int32_t st = 0;
-    bool low = false;
-    auto touch = [&](int64_t j) {  // j in [rb, i) coupled to i
-      low = true;
-      if (!coupled[(size_t)j]) {  // coupled only to rows after it: stage 0
-        coupled[(size_t)j] = 1; stage[(size_t)j] = 0; put(0);
-        bytes += kSsorRowBytes + kSsorEntryBytes * ent[(size_t)j];
-      }
-      st = std::max(st, stage[(size_t)j] + 1);
-    };
-    int32_t e = 0;
-    for (int64_t k = P.rp[(size_t)i]; k < P.rp[(size_t)i + 1]; ++k) {
-      const int64_t c = P.col[(size_t)k];
-      if (c < rb || c > i) continue;
-      ++e;
-      if (c < i) touch(c);
-    }
-    for (int64_t k = P.trp[(size_t)i]; k < P.trp[(size_t)i + 1]; ++k) {  // entries (j, i) of the earlier rows
-      const int64_t j = P.tcol[(size_t)k];
-      if (j < rb || j >= i) continue;
-      ent[(size_t)j]++;
-      if (coupled[(size_t)j]) bytes += kSsorEntryBytes;
-      touch(j);
-    }
-    ent[(size_t)i] = e;
-    coupled[(size_t)i] = low;
-    stage[(size_t)i] = low ? st : 0;
-    if (low) { put(st); bytes += kSsorRowBytes + kSsorEntryBytes * e; }
-  }
-};
-
-// B - 1 cuts that make the blocks' modelled costs about equal: the greedy pass fills each block up to a target T (the
-// fewest blocks for that T), a bisection finds the smallest T that needs at most B of them.  O(nnz) per pass, the same
-// arithmetic in the same order on every rank.  B is clamped to (n + 63) / 64 like the equal runs; the boundaries behind
-// the last block used are n (empty blocks).  cost_us: each block's modelled time.
-void ssor_balance(const SsorPattern &P, int n_blocks, std::vector<int64_t> &block_row, std::vector<double> &cost_us) {
-  const int64_t n = P.n;
-  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(n_blocks, (n + 63) / 64));
-  SsorBlockModel M(P);
-  auto greedy = [&](double T, std::vector<int64_t> *cuts) {
-    int count = 1;
-    M.reset(0);
-    for (int64_t i = 0; i < n; ++i) {
-      M.add(i);
-      if (M.cost_ns() > T && i > M.rb) {
-        if (++count > nb) return count;
-        if (cuts) cuts->push_back(i);
-        M.reset(i);
-        M.add(i);
-      }
-    }
-    return count;
-  };
-  M.reset(0);
-  for (int64_t i = 0; i < n; ++i) M.add(i);
-  double lo = 0.0, hi = M.cost_ns();
-  while (hi - lo > 1e-4 * hi) {
-    const double mid = 0.5 * (lo + hi);
-    if (greedy(mid, nullptr) <= nb) hi = mid;
-    else lo = mid;
-  }
-  std::vector<int64_t> cuts;
-  greedy(hi, &cuts);
-  block_row.assign((size_t)n_blocks + 1, n);
-  block_row[0] = 0;
-  for (size_t c = 0; c < cuts.size(); ++c) block_row[c + 1] = cuts[c];
-  cost_us.assign((size_t)n_blocks, 0.0);
-  for (int b = 0; b < n_blocks; ++b) {
-    M.reset(block_row[(size_t)b]);
-    for (int64_t i = block_row[(size_t)b]; i < block_row[(size_t)b + 1]; ++i) M.add(i);
-    cost_us[(size_t)b] = M.cost_ns() * 1e-3;
-  }
-}
-
-// modelled cost (us) of every block of a partition (the plan log prints it beside what the plan really holds)
-std::vector<double> ssor_block_costs(const SsorPattern &P, const std::vector<int32_t> &block_row) {
-  SsorBlockModel M(P);
-  std::vector<double> c(block_row.size() - 1, 0.0);
-  for (size_t b = 0; b + 1 < block_row.size(); ++b) {
-    M.reset(block_row[b]);
-    for (int64_t i = block_row[b]; i < block_row[b + 1]; ++i) M.add(i);
-    c[b] = M.cost_ns() * 1e-3;
-  }
-  return c;
-}
-
-// The part of a level matrix one SSOR block [rb, re) sweeps: its pruned entries (stored value != 0, column inside the
-// block; local column numbers), which rows couple at all, and the dependency stages
-// stage(i) = 1 + max stage(j) over the j < i coupled to i through a_ij or a_ji.  false: a row's columns do not ascend.
-struct SsorBlockGraph {
-  std::vector<int32_t> prp, pcol, stage, crow, sptr, by_stage;  // crow: coupled rows, ascending; by_stage[sptr[t] .. sptr[t + 1]): those of stage t
-  std::vector<double> pval;
-  std::vector<char> coupled;
-  int n_stages = 0;
-};
-bool ssor_block_graph(int64_t rb, int64_t re, const int64_t *rp, const int32_t *col, const double *val, SsorBlockGraph &B) {
-  const int m = (int)(re - rb);
-  B.prp.assign((size_t)m + 1, 0); B.pcol.clear(); B.pval.clear();
-  B.coupled.assign((size_t)m, 0);
-  std::vector<int32_t> low_cnt((size_t)m + 1, 0);
-  for (int i = 0; i < m; ++i) {
-    for (int64_t k = rp[rb + i]; k < rp[rb + i + 1]; ++k) {
-      const int64_t c = col[k];
-      if (k > rp[rb + i] && c <= col[k - 1]) return false;
-      if (c < rb || c >= re || val[k] == 0.0) continue;
-      B.pcol.push_back((int32_t)(c - rb));
-      B.pval.push_back(val[k]);
-      if (c != rb + i) {
-        B.coupled[(size_t)i] = 1; B.coupled[(size_t)(c - rb)] = 1;
-        low_cnt[(size_t)std::max<int64_t>(i, c - rb) + 1]++;
-      }
-    }
-    B.prp[(size_t)i + 1] = (int32_t)B.pcol.size();
-  }
-  for (int i = 0; i < m; ++i) low_cnt[(size_t)i + 1] += low_cnt[(size_t)i];
-  std::vector<int32_t> low((size_t)low_cnt[(size_t)m]), fill(low_cnt.begin(), low_cnt.end() - 1);
-  for (int i = 0; i < m; ++i)
-    for (int32_t k = B.prp[(size_t)i]; k < B.prp[(size_t)i + 1]; ++k)
-      if (B.pcol[(size_t)k] != i) low[(size_t)fill[(size_t)std::max(i, B.pcol[(size_t)k])]++] = std::min(i, B.pcol[(size_t)k]);
-  B.stage.assign((size_t)m, 0);
-  B.n_stages = 0;
-  B.crow.clear();
-  for (int i = 0; i < m; ++i) {
-    if (!B.coupled[(size_t)i]) continue;
-    int st = 0;
-    for (int32_t k = low_cnt[(size_t)i]; k < low_cnt[(size_t)i + 1]; ++k) st = std::max(st, B.stage[(size_t)low[(size_t)k]] + 1);
-    B.stage[(size_t)i] = st;
-    B.n_stages = std::max(B.n_stages, st + 1);
-    B.crow.push_back(i);
-  }
-  B.sptr.assign((size_t)B.n_stages + 1, 0);
-  B.by_stage.assign(B.crow.size(), 0);
-  for (int32_t i : B.crow) B.sptr[(size_t)B.stage[(size_t)i] + 1]++;
-  for (int t = 0; t < B.n_stages; ++t) B.sptr[(size_t)t + 1] += B.sptr[(size_t)t];
-  if (B.n_stages > 0) {
-    std::vector<int32_t> pos(B.sptr.begin(), B.sptr.end() - 1);
-    for (int32_t i : B.crow) B.by_stage[(size_t)pos[(size_t)B.stage[(size_t)i]]++] = i;
-  }
-  return true;
-}
-
-// ---- steps of one sweep direction of a block, and the y slots of a self-contained range (gmg_sgs_phase.hpp) ----------
-// prp / pcol: the block's pruned entries (stored value != 0, column inside the block; local numbers, ascending);
-// sptr / by_stage: its coupled rows stage by stage, ascending inside a stage.  dir 0 = forward, 1 = backward.
-struct SsorStep { int32_t first, nrows, len; };  // rows seq[first, first + nrows) of one stage; len: entries of its widest row
-
-inline int ssor_dir_entries(const std::vector<int32_t> &prp, const std::vector<int32_t> &pcol, int dir, int i) {
-  int c = 0;
-  for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) c += dir == 0 ? pcol[(size_t)k] < i : pcol[(size_t)k] >= i;
-  return c;
-}
-
-// The steps: the stages in sweep order, at most max_rows rows of a stage per step (one-wave sweep: records of a step
-// <= kSwMaxBlock bytes), a step's rows and columns <= y_cap slots.  Rows of a stage are independent: the backward sweep
-// takes them in descending order, so that the rows a backward range updates are a DEscending contiguous piece of ycur,
-// as those of a forward range are an ascending one.
-void ssor_build_steps(int dir, int n_stages, const std::vector<int32_t> &sptr, const std::vector<int32_t> &by_stage, const std::vector<int32_t> &prp,
-                      const std::vector<int32_t> &pcol, int max_rows, bool ph, int stride, int y_cap, std::vector<int32_t> &seq, std::vector<SsorStep> &steps) {
-  seq.clear(); steps.clear();
-  seq.reserve(by_stage.size());
-  for (int t = 0; t < n_stages; ++t) {
-    const int tt = dir == 0 ? t : n_stages - 1 - t;
-    SsorStep cur{(int32_t)seq.size(), 0, 0};
-    for (int32_t qq = sptr[(size_t)tt]; qq < sptr[(size_t)tt + 1]; ++qq) {
-      const int32_t q = dir == 0 ? qq : sptr[(size_t)tt] + sptr[(size_t)tt + 1] - 1 - qq;
-      const int i = by_stage[(size_t)q];
-      const int li = ssor_dir_entries(prp, pcol, dir, i);
-      const int nl = std::max(cur.len, li);
-      const int64_t raw = 16 + (int64_t)(cur.nrows + 1) * stride;
-      if (cur.nrows > 0 && (cur.nrows == max_rows || (!ph && raw > kSwMaxBlock) || (cur.nrows + 1) * (nl + 1) > y_cap)) {
-        steps.push_back(cur);
-        cur = SsorStep{(int32_t)seq.size(), 0, 0};
-      }
-      cur.len = std::max(cur.len, li);
-      cur.nrows++;
-      seq.push_back(i);
-    }
-    if (cur.nrows) steps.push_back(cur);
-  }
-}
-
-// y slots of a whole sweep direction as ONE range: a row owns a slot from its step to the step of its last reader (a
-// row i of this direction with a pruned entry a_ic it gathers: c < i forward, c > i backward; the row itself counts).
-// Walking the steps in order, the slots of the rows whose last reader is behind are returned to a free list before the
-// step's rows take theirs, lowest free slot first -- deterministic.  A slot is free for step s when its owner's last
-// reader is < s - 1: a step touches its rows' slots one phase before its dependent phase already (backward, it puts the
-// row's forward value there; forward, the padding entries of a record read it), while the step before may still
-// read or write (gmg_sgs_phase.hpp).
-// A row nobody reads still gets a slot (the step stores to it).  n_slots = the most slots ever live = the highest + 1.
-struct SsorSlotPlan {
-  std::vector<int32_t> step, last, slot;  // per row of the block; -1: a row without couplings
-  int n_slots = 0;
-};
-void ssor_slot_alloc(int m, const std::vector<int32_t> &prp, const std::vector<int32_t> &pcol, int dir, const std::vector<int32_t> &seq,
-                     const std::vector<SsorStep> &steps, SsorSlotPlan &out) {
-  out.step.assign((size_t)m, -1); out.last.assign((size_t)m, -1); out.slot.assign((size_t)m, -1);
-  out.n_slots = 0;
-  for (size_t s = 0; s < steps.size(); ++s)
-    for (int u = 0; u < steps[s].nrows; ++u) out.step[(size_t)seq[(size_t)(steps[s].first + u)]] = (int32_t)s;
-  for (int32_t i : seq) {
-    out.last[(size_t)i] = std::max(out.last[(size_t)i], out.step[(size_t)i]);
-    for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-      const int c = pcol[(size_t)k];
-      if (dir == 0 ? c < i : c > i) out.last[(size_t)c] = std::max(out.last[(size_t)c], out.step[(size_t)i]);
-    }
-  }
-  const int hold = 2;  // steps behind the last reader before the slot changes hands
-  std::vector<std::vector<int32_t>> due(steps.size() + 1);  // rows whose slot is free from step s on
-  std::priority_queue<int32_t, std::vector<int32_t>, std::greater<int32_t>> free_slots;
-  for (size_t s = 0; s < steps.size(); ++s) {
-    for (int32_t i : due[s]) free_slots.push(out.slot[(size_t)i]);
-    for (int u = 0; u < steps[s].nrows; ++u) {
-      const int i = seq[(size_t)(steps[s].first + u)];
-      if (free_slots.empty()) out.slot[(size_t)i] = out.n_slots++;
-      else { out.slot[(size_t)i] = free_slots.top(); free_slots.pop(); }
-      const size_t rel = (size_t)out.last[(size_t)i] + (size_t)hold;
-      if (rel < steps.size()) due[rel].push_back(i);
-    }
-  }
-}
 
 // What both plan builders end with: the sweep kernels may use the whole LDS, and, since the records carry absolute LDS
 // addresses, their dynamic LDS must start at 0 (no static __shared__) -- else the level keeps the generic sweep (G.wave unset).
@@ -1689,582 +1409,42 @@ int sgs_wave_tail(gmg_context *ctx, SgsPlan &G, bool ph, bool dep, bool reg) {
   return GMG_OK;
 }
 
-// Plan of the wavefront sweep (gmg_sgs.hpp): per block the pruned rows, the dependency stages, the steps of both
-// sweep directions, their grouping into LDS-sized ranges (or one self-contained range per direction where the live
-// rows fit), and the record stream in consumption order.
-int setup_sgs_wave(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val, int n_blocks,
-                   const std::vector<int32_t> &block_row, bool allow_phase = true) {
-  SgsPlan &G = L.sgs;
-  G.wave = false;
-  if (n <= 0 || ctx->sgs_disable_wave) return GMG_OK;
-  // four waves in turn (gmg_sgs_phase.hpp) unless switched off; rows wider than its records hold fall back to one wave
-  bool ph = allow_phase && !ctx->sgs_disable_phase && !ctx->sgs_profile;
-  if (ph) {
-    for (int64_t i = 0; i < n && ph; ++i) ph = rp[i + 1] - rp[i] <= 2 * kPhMaxEntries;  // (cheap pre-check; the exact one is per range)
-  }
-  const bool dep = ph && ctx->sgs_dep;  // one dependent wave + three preparing waves (gmg_sgs_dep.hpp)
-  const bool reg = ph && !dep && ctx->sgs_reg && !ctx->sgs_chain;  // four waves, records global -> registers (gmg_sgs_reg.hpp)
-  const bool fieldmajor = dep || reg;
-  // one self-contained range per direction (gmg_sgs_phase.hpp) where a block's live rows fit: the default four-wave sweep only
-  const bool slide_ok = ph && !dep && !reg && !ctx->sgs_chain && ctx->sgs_sliding;
-  int n_self = 0, live_max[2] = {0, 0};
-  uint64_t max_yrow = 0;  // largest level row number a self-contained backward record stores through
-  std::vector<int32_t> bwd_rows;  // the aux words of the self-contained backward records, in stream order
-  const int late_steps = dep ? kDpLate : 1;
-  const int y_max = dep ? kDpYSlots : reg ? kRgYSlots : ph ? kPhYSlots : kSwYSlots;
-  int y_cap = ctx->sgs_y_slots > 0 ? ctx->sgs_y_slots : y_max;
-  y_cap = std::max(64, std::min(y_cap, y_max)) & ~1;
-  std::vector<PhRange> pranges;
-  std::vector<uint4> blk_tab;
-  std::vector<int64_t> hist_l1(8, 0), hist_l2(4, 0), hist_g(4, 0);  // shapes of the steps (debug print)
-  std::vector<int32_t> row_ci((size_t)n, -1), ci_row, rpos_f, rpos_b, ws_ci, block_rng((size_t)n_blocks + 1, 0);
-  std::vector<double> iso_diag((size_t)n, 0.0), iso_invd((size_t)n, 1.0);
-  std::vector<SwRange> ranges;
-  std::vector<char> stream;
-  int max_ws = 0;
-  int64_t total_steps = 0, total_stages = 0;
-  // what the kernels take from the records as ADDRESSES: the forward sweep's global store index (aux, in doubles into the
-  // stream) and the LDS byte addresses of y slots.  Their maxima are checked against the allocation / the LDS budget
-  // before the plan is accepted (the one fault this code ever produced was a store through an aux field).
-  uint64_t max_aux = 0, max_lds_addr = 0;
-  std::vector<int64_t> blk_steps0((size_t)n_blocks + 1, 0), blk_bytes0((size_t)n_blocks + 1, 0);  // tallies at each block's start
-  // debug_upload: where the host spends the plan's time (seconds): block graph, steps + slots, shapes, record fill, upload
-  double laps[5] = {0, 0, 0, 0, 0};
-  auto lap_t = std::chrono::steady_clock::now();
-  auto lap = [&](int k) {
-    const auto t = std::chrono::steady_clock::now();
-    laps[k] += std::chrono::duration<double>(t - lap_t).count();
-    lap_t = t;
-  };
-  for (int b = 0; b < n_blocks; ++b) {
-    const int64_t rb = block_row[(size_t)b], re = block_row[(size_t)b + 1];
-    const int m = (int)(re - rb);
-    block_rng[(size_t)b] = (int32_t)(ph ? pranges.size() : ranges.size());
-    blk_steps0[(size_t)b] = total_steps; blk_bytes0[(size_t)b] = (int64_t)stream.size();
-    if (m == 0) continue;
-    // ---- in-block nonzero entries of every row (local column numbers), stages; 1 / a_ii as in setup_diag
-    SsorBlockGraph BG;
-    if (!ssor_block_graph(rb, re, rp, col, val, BG)) return GMG_OK;  // the prefix hand-over needs ascending columns: generic sweep
-    const std::vector<int32_t> &prp = BG.prp, &pcol = BG.pcol, &stage = BG.stage, &crow = BG.crow, &sptr = BG.sptr, &by_stage = BG.by_stage;
-    const std::vector<double> &pval = BG.pval;
-    const int n_stages = BG.n_stages;
-    std::vector<double> invd((size_t)m, 1.0);
-    for (int i = 0; i < m; ++i) {
-      double aii = 1.0, dstored = 0.0;
-      for (int64_t k = rp[rb + i]; k < rp[rb + i + 1]; ++k)
-        if (col[k] == rb + i) { aii = val[k]; dstored = val[k]; }
-      invd[(size_t)i] = 1.0 / aii;
-      iso_diag[(size_t)(rb + i)] = dstored;
-      iso_invd[(size_t)(rb + i)] = 1.0 / aii;
-    }
-    lap(0);
-    const size_t ci_base = ci_row.size();
-    ci_row.resize(ci_base + crow.size());
-    rpos_f.resize(ci_row.size(), 0);
-    rpos_b.resize(ci_row.size(), 0);
-    if (crow.empty()) continue;
-    total_stages += n_stages;
-    // The compact copy ycur is numbered in SWEEP order (stage by stage): the rows a forward range updates are one contiguous
-    // piece of it, those of a backward range a run of stage-long pieces -- the working-set loads and write-backs at the range
-    // boundaries (a tenth of the sweep) then touch consecutive addresses instead of one cache line per row.
-    for (size_t q = 0; q < by_stage.size(); ++q) {
-      row_ci[(size_t)(rb + by_stage[q])] = (int32_t)(ci_base + q);
-      ci_row[ci_base + q] = (int32_t)(rb + by_stage[q]);
-    }
-    std::vector<int32_t> ws_stamp((size_t)m, -1), own_stamp((size_t)m, -1), tmp_stamp((size_t)m, -1), slot_of((size_t)m, 0);
-    std::vector<int32_t> prefix_pos((size_t)m, 0);  // index (doubles) of the row's prefix field in the backward records
-    std::vector<SwRange> dir_ranges[2];
-    std::vector<PhRange> dir_pranges[2];
-    std::vector<int32_t> step_of((size_t)m, -1);
-    std::vector<int32_t> upd_stamp((size_t)m, -1);  // == stamp_id: the row is updated in the current range
-    int stamp_id = 0, tmp_id = 0;
-    // ---- self-contained ranges: both directions of the block must fit; else the ranged plan, unchanged
-    SsorSlotPlan slide[2];
-    std::vector<int32_t> slide_seq[2];  // the steps the slots were handed out for: the records below are built from these very lists
-    std::vector<SsorStep> slide_steps[2];
-    bool sliding = false;
-    if (slide_ok) {
-      sliding = true;
-      for (int dir = 0; dir < 2; ++dir) {
-        ssor_build_steps(dir, n_stages, sptr, by_stage, prp, pcol, kPhMaxRows, true, 0, y_max, slide_seq[dir], slide_steps[dir]);
-        ssor_slot_alloc(m, prp, pcol, dir, slide_seq[dir], slide_steps[dir], slide[dir]);
-        live_max[dir] = std::max(live_max[dir], slide[dir].n_slots);
-        if (((slide[dir].n_slots + 1) & ~1) > y_cap) sliding = false;
-      }
-    }
-    lap(1);
-    for (int dir = 1; dir >= 0; --dir) {  // backward first: the forward records point into the backward ones
-      // entries of a row in this direction: forward = the columns j < i (y_j = 0 for j >= i); backward = the columns
-      // j >= i, continuing the forward sum
-      auto in_dir = [&](int i, int c) { return dir == 0 ? c < i : c >= i; };
-      auto n_ent = [&](int i) {
-        int c = 0;
-        for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) c += in_dir(i, pcol[(size_t)k]);
-        return c;
-      };
-      // ---- groups per sub-step for this direction: every step needs ceil(widest row / 8 g) sub-steps, a sub-step of g
-      // groups costs about 3 + g units (measured: ~300 + 100 g cycles); steps are roughly the stages
-      int g_dir = 2;
-      {
-        std::vector<int> stage_len((size_t)n_stages, 0);
-        for (int32_t i : crow) stage_len[(size_t)stage[(size_t)i]] = std::max(stage_len[(size_t)stage[(size_t)i]], n_ent(i));
-        double best = 1e300;
-        for (int gg = 1; gg <= 4; ++gg) {
-          double cost = 0;
-          for (int t = 0; t < n_stages; ++t) cost += (double)std::max(1, (stage_len[(size_t)t] + 8 * gg - 1) / (8 * gg)) * (3.0 + gg);
-          if (cost < best) { best = cost; g_dir = gg; }
-        }
-        if (ctx->sgs_groups > 0) g_dir = std::min(4, ctx->sgs_groups);
-      }
-      const int w_dir = 8 * g_dir, stride = ph ? ph_stride(3, 12) : sw_stride(g_dir);
-      const int max_rows = ph ? kPhMaxRows : 64;
-      // ---- steps: <= 64 rows of one stage, records of a sub-step <= kSwMaxBlock bytes, working set <= y_cap
-      // (self-contained: the allocator's own lists -- the LDS bound is the allocator's, not the step's)
-      using Step = SsorStep;
-      std::vector<int32_t> seq;
-      std::vector<Step> steps;
-      if (sliding) { seq.swap(slide_seq[dir]); steps.swap(slide_steps[dir]); }
-      else ssor_build_steps(dir, n_stages, sptr, by_stage, prp, pcol, max_rows, ph, stride, y_cap, seq, steps);
-      // ---- ranges: greedy runs of steps whose rows + referenced rows fit y_cap
-      size_t s0 = 0;
-      while (s0 < steps.size()) {
-        ++stamp_id;
-        size_t s1 = s0;
-        SwRange R{};
-        R.ws_off = (int32_t)ws_ci.size();
-        int n_slot = 0;
-        if (sliding) {
-          // the whole direction is the range: the allocator's slots, no working-set list (n_own = n_ws = 0)
-          s1 = steps.size();
-          for (int32_t i : seq) slot_of[(size_t)i] = slide[dir].slot[(size_t)i];
-          max_ws = std::max(max_ws, slide[dir].n_slots);
-        } else {
-          int ws = 0;
-          while (s1 < steps.size()) {
-            ++tmp_id;
-            int add = 0;
-            const Step &S = steps[s1];
-            for (int u = 0; u < S.nrows; ++u) {
-              const int i = seq[(size_t)(S.first + u)];
-              if (ws_stamp[(size_t)i] != stamp_id && tmp_stamp[(size_t)i] != tmp_id) { tmp_stamp[(size_t)i] = tmp_id; ++add; }
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-                const int c = pcol[(size_t)k];
-                if (!in_dir(i, c)) continue;
-                if (ws_stamp[(size_t)c] != stamp_id && tmp_stamp[(size_t)c] != tmp_id) { tmp_stamp[(size_t)c] = tmp_id; ++add; }
-              }
-            }
-            if (ws + add > y_cap && s1 > s0) break;
-            if (ws + add > y_cap) return fail(ctx, GMG_ERR_UNSUPPORTED, "SGS plan: one step exceeds the LDS working set");
-            ws += add;
-            for (int u = 0; u < S.nrows; ++u) {
-              const int i = seq[(size_t)(S.first + u)];
-              ws_stamp[(size_t)i] = stamp_id;
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k)
-                if (in_dir(i, pcol[(size_t)k])) ws_stamp[(size_t)pcol[(size_t)k]] = stamp_id;
-            }
-            ++s1;
-          }
-          // slots: rows updated here first (step order), then the rows only read (first touch)
-          for (size_t st = s0; st < s1; ++st)
-            for (int u = 0; u < steps[st].nrows; ++u) {
-              const int i = seq[(size_t)(steps[st].first + u)];
-              own_stamp[(size_t)i] = stamp_id;
-              slot_of[(size_t)i] = n_slot++;
-              ws_ci.push_back(row_ci[(size_t)(rb + i)]);
-            }
-          R.n_own = n_slot;
-          for (size_t st = s0; st < s1; ++st)
-            for (int u = 0; u < steps[st].nrows; ++u) {
-              const int i = seq[(size_t)(steps[st].first + u)];
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-                const int c = pcol[(size_t)k];
-                if (!in_dir(i, c) || own_stamp[(size_t)c] == stamp_id) continue;
-                own_stamp[(size_t)c] = stamp_id;  // now "has a slot"
-                slot_of[(size_t)c] = n_slot++;
-                ws_ci.push_back(row_ci[(size_t)(rb + c)]);
-              }
-            }
-          R.n_ws = n_slot;
-          max_ws = std::max(max_ws, n_slot);
-        }
-        R.backward = dir;
-        R.groups = g_dir;
-        R.n_steps = 0;
-        if (ph) {
-          // ---- four-wave records.  step_of: the step (of this range) that updates a row; a row's TAIL starts at its first
-          // column updated by the step right before its own
-          for (size_t st = s0; st < s1; ++st)
-            for (int u = 0; u < steps[st].nrows; ++u) {
-              step_of[(size_t)seq[(size_t)(steps[st].first + u)]] = (int32_t)(st - s0);
-              upd_stamp[(size_t)seq[(size_t)(steps[st].first + u)]] = stamp_id;
-            }
-          // per row (in step order): entries, index of the first and of the last late column (ne: none)
-          struct RowCut { int32_t ne, first, last; };
-          std::vector<RowCut> cut;
-          for (size_t st = s0; st < s1; ++st)
-            for (int u = 0; u < steps[st].nrows; ++u) {
-              const int i = seq[(size_t)(steps[st].first + u)];
-              int ne = 0, first_late = -1, last_late = -1;
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-                const int c = pcol[(size_t)k];
-                if (!in_dir(i, c)) continue;
-                if (c != i && upd_stamp[(size_t)c] == stamp_id && step_of[(size_t)c] >= (int32_t)(st - s0) - late_steps && step_of[(size_t)c] < (int32_t)(st - s0)) {
-                  if (first_late < 0) first_late = ne;
-                  last_late = ne;
-                }
-                ++ne;
-              }
-              if (first_late < 0) { first_late = ne; last_late = ne - 1; }
-              cut.push_back(RowCut{ne, first_late, last_late});
-            }
-          // shape of a step: head (8 G) | T1 (L1: from the first late column to the last, gathered in the dependent phase) | T2 (L2:
-          // behind the last late column, products formed ahead).  A row may give the end of its head and the start of its T2 to
-          // T1; of the shapes every row of the step fits, the one with the cheapest phase (measured costs, cycles) is taken.
-          auto fits = [&](const RowCut &rc, int g, int l1, int l2, int *h0o, int *h1o) {
-            return sp::fits(rc.ne, rc.first, rc.last, g, l1, l2, h0o, h1o);  // (shared with the device builder, gmg_sgs_plan.hpp)
-          };
-          struct Shape { int g, l1, l2; };
-          std::vector<Shape> shape_of;
-          {
-            size_t c0 = 0;
-            for (size_t st = s0; st < s1; ++st) {
-              const int nr = steps[st].nrows;
-              double best = 1e300;
-              Shape bs{-1, 0, 0};
-              for (int g = 0; g <= 3; ++g)
-                for (int l1 = 4; l1 <= 28; l1 += 4)
-                  for (int l2 = 0; l2 <= 24; l2 += 8) {
-                    if (!ph_shape_ok(g, l1, l2) || (ctx->sgs_phase_nosplit && l2 > 0) || (dep && l1 > kDpMaxL1)) continue;
-                    bool ok = true;
-                    for (int u = 0; u < nr && ok; ++u) ok = fits(cut[c0 + (size_t)u], g, l1, l2, nullptr, nullptr);
-                    if (!ok) continue;
-                    // default: the measured phase costs (sp::shape_cost, shared with the device builder)
-                    // (dep: the dependent wave's step is what counts -- ~20 cycles per T1 slot, ~8 per T2 add; the rest is the prep waves')
-                    // (reg: no copy, no read-back; the record is 2 + 6 g + 0.75 (l1 + l2) load instructions of ~20 cycles)
-                    double cost;
-                    if (dep) {
-                      cost = 20.0 * l1 + 8.0 * l2 + 2.0 * g;
-                    } else if (reg) {
-                      const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, p2 = 100.0 + 11.0 * (8 * g + l2), load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
-                      cost = std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2);
-                    } else {
-                      cost = sp::shape_cost(g, l1, l2, (double)nr);
-                    }
-                    if (cost < best) { best = cost; bs = Shape{g, l1, l2}; }
-                  }
-              if (bs.g < 0) return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row, false);
-              shape_of.push_back(bs);
-              c0 += (size_t)nr;
-            }
-            // A wave pays ~400 cycles when its next step has another shape (another stretch of code): the steps are taken
-            // in chunks, one shape per chunk -- the cheapest that holds every row of the chunk.
-            const int chunk = ctx->sgs_phase_chunk > 0 ? ctx->sgs_phase_chunk : 32;
-            std::vector<size_t> cpos(shape_of.size() + 1, 0);
-            for (size_t q = 0; q < shape_of.size(); ++q) cpos[q + 1] = cpos[q] + (size_t)steps[s0 + q].nrows;
-            for (size_t q0 = 0; q0 < shape_of.size(); q0 += (size_t)chunk) {
-              const size_t q1 = std::min(shape_of.size(), q0 + (size_t)chunk);
-              double best = 1e300;
-              Shape bs{-1, 0, 0};
-              const double avg_rows = (double)(cpos[q1] - cpos[q0]) / (double)(q1 - q0);
-              for (int g = 0; g <= 3; ++g)
-                for (int l1 = 4; l1 <= 28; l1 += 4)
-                  for (int l2 = 0; l2 <= 24; l2 += 8) {
-                    if (!ph_shape_ok(g, l1, l2) || (ctx->sgs_phase_nosplit && l2 > 0) || (dep && l1 > kDpMaxL1)) continue;
-                    bool ok = true;
-                    for (size_t u = cpos[q0]; u < cpos[q1] && ok; ++u) ok = fits(cut[u], g, l1, l2, nullptr, nullptr);
-                    if (!ok) continue;
-                    // default: the measured phase costs (sp::shape_cost, shared with the device builder)
-                    // (dep: the dependent wave's step is what counts -- ~20 cycles per T1 slot, ~8 per T2 add; the rest is the prep waves')
-                    // (reg: no copy, no read-back; the record is 2 + 6 g + 0.75 (l1 + l2) load instructions of ~20 cycles)
-                    double cost;
-                    if (dep) {
-                      cost = 20.0 * l1 + 8.0 * l2 + 2.0 * g;
-                    } else if (reg) {
-                      const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, p2 = 100.0 + 11.0 * (8 * g + l2), load = 60.0 + 20.0 * (2.0 + 6.0 * g + 0.75 * (l1 + l2));
-                      cost = std::max(std::max(crit, load), p2) + 0.1 * (crit + load + p2);
-                    } else {
-                      cost = sp::shape_cost(g, l1, l2, avg_rows);
-                    }
-                    if (cost < best) { best = cost; bs = Shape{g, l1, l2}; }
-                  }
-              if (bs.g < 0) return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row, false);
-              for (size_t q = q0; q < q1; ++q) shape_of[q] = bs;
-            }
-          }
-          lap(2);
-          PhRange P{};
-          P.ws_off = R.ws_off; P.n_own = R.n_own; P.n_ws = R.n_ws; P.backward = dir;
-          // the rows updated here as a piece of ycur (sweep-order numbering): first index and direction, if they are one
-          P.own_ci0 = R.n_own > 0 ? ws_ci[(size_t)R.ws_off] : 0;
-          P.own_dir = dir == 0 ? 1 : -1;
-          for (int k = 0; k < R.n_own && P.own_dir; ++k)
-            if (ws_ci[(size_t)R.ws_off + (size_t)k] != P.own_ci0 + P.own_dir * k) P.own_dir = 0;
-          if (sliding) { P.own_dir = 0; P.pad0[0] = 1; P.pad0[1] = slide[dir].n_slots; ++n_self; }
-          P.n_steps = (int32_t)(s1 - s0);
-          const int64_t base = ((int64_t)stream.size() + 1023) / 1024 * 1024;
-          P.stream_off = base;
-          std::vector<int64_t> boff, bbytes;
-          std::vector<uint32_t> step_word;  // shape key | rows << 8 | T1 slots in use << 16
-          int64_t off = 0;
-          size_t tix = 0;
-          for (size_t st = s0; st < s1; ++st) {
-            const Step &S = steps[st];
-            const Shape sh = shape_of[st - s0];
-            const int Gr = sh.g, L1r = sh.l1;
-            // T1 slots the step's own rows need of the chunk's shape (the dependent phase stops there)
-            int t1_used = 0;
-            for (int u = 0; u < S.nrows; ++u) {
-              int h0 = 0, h1 = 0;
-              (void)fits(cut[tix + (size_t)u], Gr, L1r, sh.l2, &h0, &h1);
-              t1_used = std::max(t1_used, h1 - h0);
-            }
-            t1_used = ctx->sgs_phase_nocascade ? L1r : std::min(L1r, std::max(4, (t1_used + 3) / 4 * 4));
-            // (storing the records at the step's OWN width -- head groups, T1 and T2 slots its rows really have -- was measured in
-            // round 3: the stream shrinks by 13 % only, a step's widest row is nearly as wide as its chunk's, and the branches that
-            // make P2 and CRIT stop at the step's counts cost more than the shorter copy saves: 2.52 against 2.48 ms)
-            const int gW = Gr, l1W = L1r;
-            const int Lr = sh.l1 + sh.l2, pstride = ph_stride(gW, Lr);
-            const int64_t raw = 16 + (int64_t)S.nrows * pstride;
-            boff.push_back(off); bbytes.push_back(raw);
-            stream.resize((size_t)(base + off + raw), 0);
-            char *blk = stream.data() + base + off;
-            step_word.push_back((uint32_t)ph::ph_key(Gr, L1r, sh.l2) | ((uint32_t)S.nrows << 8) | ((uint32_t)t1_used << 16));
-            for (int u = 0; u < S.nrows; ++u) {
-              const int i = seq[(size_t)(S.first + u)];
-              const int32_t ci = row_ci[(size_t)(rb + i)];
-              // four-wave sweep: records lane-major (one row's fields together); dep: FIELD-major -- unit k (16 bytes) of row u at
-              // block + 16 + (k * nrows + u) * 16, so that a preparing wave reads a field of all rows with one coalesced load
-              alignas(16) char rec_tmp[32 + 96 * 3 + 12 * kPhMaxEntries + 32];
-              char *rec = fieldmajor ? rec_tmp : blk + 16 + (size_t)u * pstride;
-              const int64_t rec_pos = fieldmajor ? base + off + 16 + (int64_t)u * 16 : base + off + 16 + (int64_t)u * pstride;
-              const int64_t pre_pos = fieldmajor ? base + off + 16 + ((int64_t)S.nrows + u) * 16 : rec_pos + 16;
-              (dir == 0 ? rpos_f : rpos_b)[(size_t)ci] = (int32_t)(rec_pos / 8);
-              if (dir == 1) prefix_pos[(size_t)i] = (int32_t)(pre_pos / 8);
-              double *f = reinterpret_cast<double *>(rec);
-              uint32_t *wv = reinterpret_cast<uint32_t *>(rec);
-              const uint32_t my = (uint32_t)slot_of[(size_t)i] * 8u;
-              f[0] = 0.0; f[1] = invd[(size_t)i]; f[2] = 0.0;
-              wv[6] = my;
-              // aux: forward, where the row's sum goes; backward, self-contained: the level row the result is stored to
-              wv[7] = dir == 0 ? (uint32_t)prefix_pos[(size_t)i] : sliding ? (uint32_t)(rb + i) : 0u;
-              if (dir == 0) max_aux = std::max<uint64_t>(max_aux, wv[7]);
-              else max_yrow = std::max<uint64_t>(max_yrow, wv[7]);
-              if (dir == 1 && sliding) bwd_rows.push_back((int32_t)wv[7]);  // (host copy of what the records carry: gmg_get_ssor_backward_rows)
-              max_lds_addr = std::max<uint64_t>(max_lds_addr, my);
-              double *hv = f + 4, *tv = f + 4 + 8 * gW;
-              uint32_t *ha = reinterpret_cast<uint32_t *>(rec + 32 + 64 * gW + 8 * Lr), *ta = ha + 8 * gW;
-              for (int e = 0; e < 8 * gW; ++e) { hv[e] = 0.0; ha[e] = my; }
-              for (int e = 0; e < Lr; ++e) { tv[e] = 0.0; ta[e] = my; }
-              const RowCut &rc = cut[tix];
-              // head [0, h0), T1 [h0, h1), T2 [h1, ne)
-              int h0 = 0, h1 = rc.ne;
-              (void)fits(rc, Gr, L1r, sh.l2, &h0, &h1);
-              int e = 0;
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1]; ++k) {
-                const int c = pcol[(size_t)k];
-                if (!in_dir(i, c)) continue;
-                const uint32_t ad = (uint32_t)slot_of[(size_t)c] * 8u;
-                max_lds_addr = std::max<uint64_t>(max_lds_addr, ad);
-                if (e < h0) { hv[e] = pval[(size_t)k]; ha[e] = ad; }
-                else if (e < h1) { tv[e - h0] = pval[(size_t)k]; ta[e - h0] = ad; }
-                else { tv[l1W + e - h1] = pval[(size_t)k]; ta[l1W + e - h1] = ad; }
-                ++e;
-              }
-              if (fieldmajor)
-                for (int k = 0; k < (32 + 96 * gW + 12 * Lr) / 16; ++k) std::memcpy(blk + 16 + ((size_t)k * S.nrows + (size_t)u) * 16, rec_tmp + 16 * k, 16);
-              ++tix;
-            }
-            off += (raw + 15) / 16 * 16;
-          }
-          P.blk_tab = (uint32_t)blk_tab.size();
-          for (size_t q = 0; q < boff.size(); ++q) {
-            const Shape sh = shape_of[q];
-            blk_tab.push_back(uint4{(uint32_t)boff[q], (uint32_t)bbytes[q], step_word[q], 0u});
-            uint32_t *h = reinterpret_cast<uint32_t *>(stream.data() + base + boff[q]);
-            if (q + kPhWaves < boff.size()) {  // the block its reader copies next, and that step's shape
-              h[1] = (uint32_t)bbytes[q + kPhWaves]; h[2] = (uint32_t)boff[q + kPhWaves]; h[3] = step_word[q + kPhWaves];
-            }
-            hist_l1[(size_t)std::min(7, sh.l1 / 4)]++; hist_l2[(size_t)(sh.l2 / 8)]++; hist_g[(size_t)sh.g]++;
-          }
-          const int64_t padded = (off + 2048 + 1023) / 1024 * 1024;  // the copies read whole KB: up to 1008 bytes beyond a block
-          if (padded >= ((int64_t)1 << 31) || (base + padded) / 8 >= ((int64_t)1 << 31)) return setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row, false);
-          stream.resize((size_t)(base + padded), 0);
-          P.stream_bytes = (uint32_t)padded;
-          // prefetch wave: pf_step bytes per phase starting pf_lead bytes ahead, never behind block p + 12 at phase p
-          const int64_t nph = P.n_steps + kPhWaves - 1;
-          const int64_t step_b = ((off + nph - 1) / nph + 127) / 128 * 128;
-          int64_t lead = 65536;
-          for (int64_t q = 0; q < (int64_t)boff.size(); ++q) {
-            const int64_t need = boff[(size_t)std::min<int64_t>(q + 12, (int64_t)boff.size() - 1)] + kPhRegion;  // by phase q - 2
-            lead = std::max(lead, need - std::max<int64_t>(q - 2, 0) * step_b);
-          }
-          if (ctx->sgs_pf_lead_kb > 0) lead = std::max<int64_t>(lead, (int64_t)ctx->sgs_pf_lead_kb * 1024);  // (diagnostics: a longer lead / no prefetch at all)
-          P.pf_step = (uint32_t)step_b; P.pf_lead = (uint32_t)((lead + 8191) / 8192 * 8192);
-          // Measured in round 3: the four-wave sweep with LDS copies gains nothing from the touches (2.455 ms without, 2.485 with:
-          // its copies have two phases to land either way), the register variant loses 10 % without them -- so only that one, or
-          // an explicit lead, keeps the fifth wave busy.
-          if (ctx->sgs_pf_lead_kb < 0 || (ctx->sgs_pf_lead_kb == 0 && !fieldmajor)) P.pf_step = P.pf_lead = 0;
-          total_steps += P.n_steps;
-          dir_pranges[dir].push_back(P);
-          lap(3);
-          s0 = s1;
-          continue;
-        }
-        // ---- records in consumption order; a block never straddles the end of the ring
-        const int64_t base = ((int64_t)stream.size() + kSwChunk - 1) / kSwChunk * kSwChunk;
-        R.stream_off = base;
-        int64_t off = 0, prev_hdr = -1;
-        for (size_t st = s0; st < s1; ++st) {
-          const Step &S = steps[st];
-          const int nr = S.nrows;
-          const int n_sub = std::max(1, (S.len + w_dir - 1) / w_dir);
-          const int g = g_dir;
-          for (int sub = 0; sub < n_sub; ++sub) {
-            const int64_t raw = 16 + (int64_t)nr * stride;
-            if (off % kSwRing + raw > kSwRing) off = (off / kSwRing + 1) * kSwRing;
-            stream.resize((size_t)(base + off + raw), 0);
-            char *blk = stream.data() + base + off;
-            SwStepHdr h{};
-            h.nrows = (uint16_t)nr;
-            h.flags = (uint16_t)((sub == 0 ? 1 : 0) | (sub == n_sub - 1 ? 2 : 0));
-            std::memcpy(blk, &h, sizeof h);
-            if (prev_hdr >= 0) {
-              SwStepHdr ph;
-              std::memcpy(&ph, stream.data() + base + prev_hdr, sizeof ph);
-              ph.advance = (uint32_t)(off - prev_hdr); ph.next_raw = (uint32_t)raw; ph.next_nrows = (uint16_t)nr;
-              std::memcpy(stream.data() + base + prev_hdr, &ph, sizeof ph);
-            } else {
-              R.first_raw = (int32_t)raw; R.first_nrows = nr;
-            }
-            prev_hdr = off;
-            for (int u = 0; u < nr; ++u) {
-              const int i = seq[(size_t)(S.first + u)];
-              const int32_t ci = row_ci[(size_t)(rb + i)];
-              char *rec = blk + 16 + (size_t)u * stride;
-              const int64_t rec_pos = base + off + 16 + (int64_t)u * stride;
-              if (sub == n_sub - 1) (dir == 0 ? rpos_f : rpos_b)[(size_t)ci] = (int32_t)(rec_pos / 8);  // the rhs is read when the row is finished
-              if (dir == 1 && sub == 0) prefix_pos[(size_t)i] = (int32_t)(rec_pos / 8 + 2);             // the prefix when it is started
-              double *f = reinterpret_cast<double *>(rec);
-              uint32_t *w = reinterpret_cast<uint32_t *>(rec);
-              const uint32_t my = (uint32_t)slot_of[(size_t)i] * 8u;
-              f[0] = 0.0; f[1] = invd[(size_t)i]; f[2] = 0.0;
-              w[6] = my;
-              w[7] = dir == 0 ? (uint32_t)prefix_pos[(size_t)i] : 0u;
-              max_aux = std::max<uint64_t>(max_aux, w[7]); max_lds_addr = std::max<uint64_t>(max_lds_addr, my);
-              uint32_t *ad = reinterpret_cast<uint32_t *>(rec + 32 + 64 * g);
-              int e = 0, seen = 0;
-              for (int32_t k = prp[(size_t)i]; k < prp[(size_t)i + 1] && e < 8 * g; ++k) {
-                const int c = pcol[(size_t)k];
-                if (!in_dir(i, c)) continue;
-                if (seen++ < sub * w_dir) continue;  // entries of earlier sub-steps
-                f[4 + e] = pval[(size_t)k];
-                max_lds_addr = std::max<uint64_t>(max_lds_addr, (uint64_t)slot_of[(size_t)c] * 8u);
-                ad[e++] = (uint32_t)slot_of[(size_t)c] * 8u;
-              }
-              for (; e < 8 * g; ++e) { f[4 + e] = 0.0; ad[e] = my; }
-            }
-            off += raw;
-            R.n_steps++;
-          }
-        }
-        if (prev_hdr >= 0) {  // last step: advance = its own size, nothing follows
-          SwStepHdr ph;
-          std::memcpy(&ph, stream.data() + base + prev_hdr, sizeof ph);
-          ph.advance = (uint32_t)(off - prev_hdr); ph.next_raw = 0;
-          std::memcpy(stream.data() + base + prev_hdr, &ph, sizeof ph);
-        }
-        const int64_t padded = (off + kSwChunk - 1) / kSwChunk * kSwChunk;
-        if (padded >= ((int64_t)1 << 31) || (base + padded) / 8 >= ((int64_t)1 << 31)) return GMG_OK;  // generic sweep
-        stream.resize((size_t)(base + padded), 0);
-        R.stream_bytes = (int32_t)padded;
-        total_steps += R.n_steps;
-        dir_ranges[dir].push_back(R);
-        s0 = s1;
-      }
-    }
-    for (int dir = 0; dir < 2; ++dir) ranges.insert(ranges.end(), dir_ranges[dir].begin(), dir_ranges[dir].end());
-    for (int dir = 0; dir < 2; ++dir) pranges.insert(pranges.end(), dir_pranges[dir].begin(), dir_pranges[dir].end());
-  }
-  block_rng[(size_t)n_blocks] = (int32_t)(ph ? pranges.size() : ranges.size());
-  blk_steps0[(size_t)n_blocks] = total_steps; blk_bytes0[(size_t)n_blocks] = (int64_t)stream.size();
-  const int y_slots = std::max(2, (max_ws + 1) & ~1);
-  lap(3);
-  // ---- the plan is memory-safe by construction, and checked: every address a record carries lies inside what is allocated
-  if (!stream.empty() && (max_aux * 8 + 8 > stream.size() || max_lds_addr + 8 > (uint64_t)y_slots * 8))
-    return fail(ctx, GMG_ERR_INVALID, "SSOR plan: a record addresses memory outside the stream / the LDS slots (internal error)");
-  if (max_yrow >= (uint64_t)n) return fail(ctx, GMG_ERR_INVALID, "SSOR plan: a backward record stores outside the level vector (internal error)");
-  for (int32_t ci : ws_ci)
-    if (ci < 0 || (size_t)ci >= ci_row.size()) return fail(ctx, GMG_ERR_INVALID, "SSOR plan: working-set entry out of range (internal error)");
-  for (size_t q = 0; q < rpos_f.size(); ++q)
-    if ((uint64_t)rpos_f[q] * 8 + 8 > stream.size() || (uint64_t)rpos_b[q] * 8 + 8 > stream.size())
-      return fail(ctx, GMG_ERR_INVALID, "SSOR plan: rhs position outside the stream (internal error)");
-  HIPC(upload(G.w_ranges, ranges, ctx->stream));
-  HIPC(upload(G.p_ranges, pranges, ctx->stream));
-  HIPC(upload(G.p_blk_tab, blk_tab, ctx->stream));
-  HIPC(upload(G.w_block_rng, block_rng, ctx->stream));
-  HIPC(upload(G.w_ws_ci, ws_ci, ctx->stream));
-  HIPC(upload(G.w_ci_row, ci_row, ctx->stream));
-  HIPC(upload(G.w_row_ci, row_ci, ctx->stream));
-  HIPC(upload(G.w_rpos_f, rpos_f, ctx->stream));
-  HIPC(upload(G.w_rpos_b, rpos_b, ctx->stream));
-  HIPC(upload(G.w_stream, stream, ctx->stream));
-  HIPC(upload(G.w_iso_diag, iso_diag, ctx->stream));
-  HIPC(upload(G.w_iso_invd, iso_invd, ctx->stream));
-  // (every range self-contained: nobody reads or writes ycur -- it is not allocated and the pre-pass gets a null pointer)
-  if (!(ph && n_self == (int)pranges.size())) HIPC(G.w_ycur.alloc(std::max<size_t>(ci_row.size(), 1)));
-  HIPC(hipStreamSynchronize(ctx->stream));
-  lap(4);
-  if (ctx->debug_upload)
-    std::fprintf(stderr, "[gmg] SGS plan laps (host, %lld rows): block graph %.4f s, steps + slots %.4f s, shapes %.4f s, record fill %.4f s, upload %.4f s\n", (long long)n,
-                 laps[0], laps[1], laps[2], laps[3], laps[4]);
-  G.host_bwd_rows = bwd_rows;
-  G.n_self = n_self; G.live_max[0] = live_max[0]; G.live_max[1] = live_max[1];
-  G.host_block_row = block_row;
-  G.host_block_rng = block_rng;
-  G.host_block_steps.assign((size_t)n_blocks, 0);
-  G.host_block_bytes.assign((size_t)n_blocks, 0);
-  for (int b = 0; b < n_blocks; ++b) {
-    G.host_block_steps[(size_t)b] = blk_steps0[(size_t)b + 1] - blk_steps0[(size_t)b];
-    G.host_block_bytes[(size_t)b] = blk_bytes0[(size_t)b + 1] - blk_bytes0[(size_t)b];
-  }
-  {
-    const int n_ranks = ctx->dist ? ctx->comm.n_ranks : 1;
-    if (n_ranks > 1 && n_blocks % n_ranks == 0) {
-      const int nbl = n_blocks / n_ranks;
-      int64_t len = 1;
-      for (int r = 0; r < n_ranks; ++r) len = std::max<int64_t>(len, block_row[(size_t)((r + 1) * nbl)] - block_row[(size_t)(r * nbl)]);
-      G.w_stage_len = len;
-      HIPC(G.w_stage.alloc((size_t)(len * n_ranks)));
-    }
-  }
-  G.w_y_slots = y_slots;
-  G.w_lds_bytes = dep ? y_slots * 8 + kDpSlots * ((kDpSlotBytes + 15) / 16 * 16) + kDpFlagBytes : reg ? y_slots * 8 + kPhJunk : ph ? y_slots * 8 + kPhWaves * kPhRegion + kPhJunk : y_slots * 8 + kSwRing + 32;
-  G.dep = dep;
-  G.reg = reg;
-  G.w_n_ranges = (int)(ph ? pranges.size() : ranges.size());
-  G.phased = ph;
-  G.host_pranges = pranges;
-  G.w_n_coupled = (int64_t)ci_row.size();
-  G.w_stream_bytes = (int64_t)stream.size();
-  G.w_steps = total_steps; G.w_stages = total_stages;
-  CHK(sgs_wave_tail(ctx, G, ph, dep, reg));
-  if (ctx->debug_upload && ph)
+// the options of the context that steer an SSOR plan
+SsorPlanOptions ssor_plan_options(const gmg_context *ctx) {
+  SsorPlanOptions o;
+  o.disable_wave = ctx->sgs_disable_wave; o.disable_phase = ctx->sgs_disable_phase; o.profile = ctx->sgs_profile;
+  o.dep = ctx->sgs_dep; o.reg = ctx->sgs_reg; o.chain = ctx->sgs_chain; o.sliding = ctx->sgs_sliding;
+  o.y_slots = ctx->sgs_y_slots; o.groups = ctx->sgs_groups; o.phase_chunk = ctx->sgs_phase_chunk;
+  o.phase_nosplit = ctx->sgs_phase_nosplit; o.phase_nocascade = ctx->sgs_phase_nocascade; o.pf_lead_kb = ctx->sgs_pf_lead_kb;
+  o.debug = ctx->debug_upload;
+  return o;
+}
+
+static_assert(sizeof(PhBlkEntry) == sizeof(uint4) && alignof(PhBlkEntry) <= alignof(uint4), "the block table is read as uint4 by the sweep kernels");
+
+// The host-side members of a wavefront plan, as both builders leave them.  W: the host builder's plan, or the tallies and the
+// host-side vectors of the device builder's (its tables stay on the device).
+void sgs_set_host_members(SgsPlan &G, const SsorSweepPlan &W, const std::vector<int32_t> &block_row, int64_t n_coupled, int64_t stream_bytes) {
+  G.host_bwd_rows = W.bwd_rows; G.host_pranges = W.pranges;
+  G.host_block_row = block_row; G.host_block_rng = W.block_rng; G.host_block_steps = W.block_steps; G.host_block_bytes = W.block_bytes;
+  G.n_self = W.n_self; G.live_max[0] = W.live_max[0]; G.live_max[1] = W.live_max[1];
+  G.w_y_slots = W.y_slots; G.w_lds_bytes = W.lds_bytes; G.w_n_ranges = W.n_ranges(); G.n_bwd = W.n_bwd;
+  G.phased = W.phased; G.dep = W.dep; G.reg = W.reg;
+  G.w_n_coupled = n_coupled; G.w_stream_bytes = stream_bytes; G.w_steps = W.total_steps; G.w_stages = W.total_stages;
+}
+
+// debug_upload: the shapes of the steps and the plan's totals
+void sgs_plan_log(const SgsPlan &G, const SsorSweepPlan &W, int64_t n) {
+  const std::vector<int64_t> &hist_g = W.hist_g, &hist_l1 = W.hist_l1, &hist_l2 = W.hist_l2;
+  if (W.phased)
     std::fprintf(stderr, "[gmg] SGS step shapes: G %lld %lld %lld %lld | L1/4 %lld %lld %lld %lld %lld %lld %lld %lld | L2/8 %lld %lld %lld %lld\n", (long long)hist_g[0], (long long)hist_g[1],
                  (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
                  (long long)hist_l1[5], (long long)hist_l1[6], (long long)hist_l1[7], (long long)hist_l2[0], (long long)hist_l2[1], (long long)hist_l2[2], (long long)hist_l2[3]);
-  int n_bwd = 0;
-  for (const PhRange &P : pranges) n_bwd += P.backward;
-  for (const SwRange &R : ranges) n_bwd += R.backward;
-  G.n_bwd = n_bwd;
-  if (ctx->debug_upload) {
-    std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
-                 "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
-                 ph ? "four-wave" : "one-wave", (long long)n, (long long)G.w_n_coupled, n_blocks, (long long)total_stages, (long long)total_steps, G.w_n_ranges,
-                 G.w_n_ranges - n_bwd, n_bwd, n_self, y_slots, live_max[0], live_max[1], (double)stream.size() / 1e6);
-  }
-  return GMG_OK;
+  std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
+               "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
+               W.phased ? "four-wave" : "one-wave", (long long)n, (long long)G.w_n_coupled, (int)G.host_block_row.size() - 1, (long long)G.w_stages, (long long)G.w_steps, G.w_n_ranges,
+               G.w_n_ranges - G.n_bwd, G.n_bwd, G.n_self, G.w_y_slots, G.live_max[0], G.live_max[1], (double)G.w_stream_bytes / 1e6);
 }
-
 
 // debug_upload: the partition -- per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
 void sgs_partition_log(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val, const std::vector<int32_t> &block_row,
@@ -2291,73 +1471,67 @@ void sgs_partition_log(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp,
   }
 }
 
-// SGS level schedule on the symmetrised pattern, per block of consecutive rows:
-// stage(i) = 1 + max stage(j) over the coupled j < i of the same block.
-// The boundaries: the caller's (explicit_rows, checked by gmg_set_level_matrix), else the balanced cuts if that mode is on,
-// else equal runs of rows.
+// The SSOR plan of a level from its CSR on the host: gmg_sgs_layout.hpp plans, this copies.  Always the generic level schedule
+// (the sweep of a level whose rows have unsorted columns); the wavefront plan where one can be made.
 int setup_sgs(gmg_context *ctx, Level &L, int64_t n, const int64_t *rp, const int32_t *col, const double *val,
               const std::vector<int64_t> *explicit_rows) {
-  std::vector<int64_t> trp;
-  std::vector<int32_t> tcol;
-  std::vector<double> tval, ones((size_t)rp[n], 1.0);
-  transpose_host(n, n, rp, col, ones.data(), trp, tcol, tval);
-  std::vector<int32_t> block_row;
-  if (explicit_rows) {
-    block_row.assign(explicit_rows->begin(), explicit_rows->end());  // (setup_sgs_device below: the same case and the equal runs)
-  } else if (ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED) {
-    std::vector<int64_t> br;
-    std::vector<double> cost;
-    ssor_balance(SsorPattern(n, rp, col, val), (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64)), br, cost);
-    block_row.assign(br.begin(), br.end());
-  } else {
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64));
-    block_row.resize((size_t)nb + 1);
-    for (int b = 0; b <= nb; ++b) block_row[(size_t)b] = (int32_t)(n * b / nb);
-  }
+  const SsorPlanOptions opt = ssor_plan_options(ctx);
+  const std::vector<int32_t> block_row = ssor_block_rows(n, rp, col, val, explicit_rows, ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED, ctx->ssor_blocks);
   const int n_blocks = (int)block_row.size() - 1;
-  std::vector<int32_t> block_stage((size_t)n_blocks + 1, 0);
-  std::vector<int32_t> stage((size_t)std::max<int64_t>(n, 1), 0), sp, rows((size_t)std::max<int64_t>(n, 1));
-  int n_stages_max = 0;
-  for (int b = 0; b < n_blocks; ++b) {
-    const int64_t rb = block_row[(size_t)b], re = block_row[(size_t)b + 1];
-    int ns = 0;
-    for (int64_t i = rb; i < re; ++i) {
-      int s = 0;
-      for (int64_t k = rp[i]; k < rp[i + 1]; ++k)
-        if (col[k] < i && col[k] >= rb) s = std::max(s, stage[(size_t)col[k]] + 1);
-      for (int64_t k = trp[(size_t)i]; k < trp[(size_t)i + 1]; ++k)
-        if (tcol[(size_t)k] < i && tcol[(size_t)k] >= rb) s = std::max(s, stage[(size_t)tcol[(size_t)k]] + 1);
-      stage[(size_t)i] = s;
-      ns = std::max(ns, s + 1);
-    }
-    if (re == rb) ns = 0;
-    // this block's stage offsets (absolute positions in `rows`), appended to sp
-    std::vector<int32_t> cnt((size_t)ns + 1, 0);
-    for (int64_t i = rb; i < re; ++i) cnt[(size_t)stage[(size_t)i] + 1]++;
-    for (int t = 0; t < ns; ++t) cnt[(size_t)t + 1] += cnt[(size_t)t];
-    std::vector<int32_t> pos(cnt.begin(), cnt.end());
-    for (int64_t i = rb; i < re; ++i) rows[(size_t)(rb + pos[(size_t)stage[(size_t)i]]++)] = (int32_t)i;
-    for (int t = 0; t <= ns; ++t) sp.push_back((int32_t)(rb + cnt[(size_t)t]));
-    block_stage[(size_t)b + 1] = block_stage[(size_t)b] + ns;
-    n_stages_max = std::max(n_stages_max, ns);
-  }
+  const SsorGenericPlan GP = ssor_generic_plan(n, rp, col, block_row);
+  SsorSweepPlan W;
+  ssor_sweep_plan(opt, n, rp, col, val, block_row, true, W);
+  if (W.outcome == kSsorOneWave) ssor_sweep_plan(opt, n, rp, col, val, block_row, false, W);
+  const auto t_planned = std::chrono::steady_clock::now();
+  if (W.outcome == kSsorPlanned)
+    if (const char *bad = check_sweep_plan(W, n)) { W.outcome = kSsorInvalid; W.message = bad; }
+  const bool wave = W.outcome == kSsorPlanned;
   L.sgs = SgsPlan();
-  L.sgs.n_blocks = n_blocks; L.sgs.n_stages_max = n_stages_max;
-  HIPC(L.sgs.stage_ptr.alloc(std::max<size_t>(sp.size(), 1)));
-  HIPC(L.sgs.stage_rows.alloc(rows.size()));
-  HIPC(L.sgs.block_row.alloc(block_row.size()));
-  HIPC(L.sgs.block_stage.alloc(block_stage.size()));
-  HIPC(hipMemcpyAsync(L.sgs.stage_ptr.get(), sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.stage_rows.get(), rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.block_row.get(), block_row.data(), sizeof(int32_t) * block_row.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIPC(hipMemcpyAsync(L.sgs.block_stage.get(), block_stage.data(), sizeof(int32_t) * block_stage.size(), hipMemcpyHostToDevice, ctx->stream));
+  SgsPlan &G = L.sgs;
+  G.n_blocks = n_blocks; G.n_stages_max = GP.n_stages_max;
+  HIPC(upload(G.stage_ptr, GP.stage_ptr, ctx->stream));
+  HIPC(upload(G.stage_rows, GP.stage_rows, ctx->stream));
+  HIPC(upload(G.block_row, block_row, ctx->stream));
+  HIPC(upload(G.block_stage, GP.block_stage, ctx->stream));
+  if (wave) {
+    HIPC(upload(G.w_ranges, W.ranges, ctx->stream));
+    HIPC(upload(G.p_ranges, W.pranges, ctx->stream));
+    HIPC(upload(G.p_blk_tab, reinterpret_cast<const uint4 *>(W.blk_tab.data()), W.blk_tab.size(), ctx->stream));
+    HIPC(upload(G.w_block_rng, W.block_rng, ctx->stream));
+    HIPC(upload(G.w_ws_ci, W.ws_ci, ctx->stream));
+    HIPC(upload(G.w_ci_row, W.ci_row, ctx->stream));
+    HIPC(upload(G.w_row_ci, W.row_ci, ctx->stream));
+    HIPC(upload(G.w_rpos_f, W.rpos_f, ctx->stream));
+    HIPC(upload(G.w_rpos_b, W.rpos_b, ctx->stream));
+    HIPC(upload(G.w_stream, W.stream, ctx->stream));
+    HIPC(upload(G.w_iso_diag, W.iso_diag, ctx->stream));
+    HIPC(upload(G.w_iso_invd, W.iso_invd, ctx->stream));
+    // (every range self-contained: nobody reads or writes ycur -- it is not allocated and the pre-pass gets a null pointer)
+    if (!(W.phased && W.n_self == (int)W.pranges.size())) HIPC(G.w_ycur.alloc(std::max<size_t>(W.ci_row.size(), 1)));
+  }
   HIPC(hipStreamSynchronize(ctx->stream));
   // (the generic sweep: one step per stage and direction; the wavefront plan replaces these with its own counts)
-  L.sgs.host_block_row = block_row;
-  L.sgs.host_block_steps.assign((size_t)n_blocks, 0);
-  for (int b = 0; b < n_blocks; ++b) L.sgs.host_block_steps[(size_t)b] = 2 * (int64_t)(block_stage[(size_t)b + 1] - block_stage[(size_t)b]);
-  L.sgs.host_block_bytes.assign((size_t)n_blocks, 0);
-  CHK(setup_sgs_wave(ctx, L, n, rp, col, val, n_blocks, block_row));
+  G.host_block_row = block_row;
+  G.host_block_steps.assign((size_t)n_blocks, 0);
+  for (int b = 0; b < n_blocks; ++b) G.host_block_steps[(size_t)b] = 2 * (int64_t)(GP.block_stage[(size_t)b + 1] - GP.block_stage[(size_t)b]);
+  G.host_block_bytes.assign((size_t)n_blocks, 0);
+  if (W.outcome == kSsorUnsupported || W.outcome == kSsorInvalid) return fail(ctx, W.outcome == kSsorUnsupported ? GMG_ERR_UNSUPPORTED : GMG_ERR_INVALID, W.message);
+  if (wave) {
+    if (ctx->debug_upload)
+      std::fprintf(stderr, "[gmg] SGS plan laps (host, %lld rows): block graph %.4f s, steps + slots %.4f s, shapes %.4f s, record fill %.4f s, upload %.4f s\n", (long long)n,
+                   W.laps[0], W.laps[1], W.laps[2], W.laps[3], std::chrono::duration<double>(std::chrono::steady_clock::now() - t_planned).count());
+    sgs_set_host_members(G, W, block_row, (int64_t)W.ci_row.size(), (int64_t)W.stream.size());
+    const int n_ranks = ctx->dist ? ctx->comm.n_ranks : 1;
+    if (n_ranks > 1 && n_blocks % n_ranks == 0) {  // staging of the all-gather of the swept pieces
+      const int nbl = n_blocks / n_ranks;
+      int64_t len = 1;
+      for (int r = 0; r < n_ranks; ++r) len = std::max<int64_t>(len, block_row[(size_t)((r + 1) * nbl)] - block_row[(size_t)(r * nbl)]);
+      G.w_stage_len = len;
+      HIPC(G.w_stage.alloc((size_t)(len * n_ranks)));
+    }
+    CHK(sgs_wave_tail(ctx, G, W.phased, W.dep, W.reg));
+    if (ctx->debug_upload) sgs_plan_log(G, W, n);
+  }
   if (ctx->debug_upload) sgs_partition_log(ctx, L, n, rp, col, val, block_row, explicit_rows != nullptr);
   return GMG_OK;
 }
@@ -2398,14 +1572,7 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   *reason = sgs_device_refusal(ctx, explicit_rows != nullptr);
   if (*reason) return GMG_OK;
   if (n <= 0) { *reason = "empty level"; return GMG_OK; }
-  std::vector<int32_t> block_row;
-  if (explicit_rows) {
-    block_row.assign(explicit_rows->begin(), explicit_rows->end());
-  } else {
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->ssor_blocks, (n + 63) / 64));
-    block_row.resize((size_t)nb + 1);
-    for (int b = 0; b <= nb; ++b) block_row[(size_t)b] = (int32_t)(n * b / nb);
-  }
+  const std::vector<int32_t> block_row = ssor_block_rows(n, nullptr, nullptr, nullptr, explicit_rows, false, ctx->ssor_blocks);  // (the caller's or equal runs)
   const int n_blocks = (int)block_row.size() - 1;
   int y_cap = ctx->sgs_y_slots > 0 ? ctx->sgs_y_slots : kPhYSlots;
   y_cap = std::max(64, std::min(y_cap, kPhYSlots)) & ~1;
@@ -2454,7 +1621,10 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   if (flags & sp::kUnsorted) { *reason = "unsorted columns"; return GMG_OK; }
   if (flags & sp::kWide) { *reason = "row too wide"; return GMG_OK; }
   std::vector<sp::Block> blk(NB);
-  std::vector<int32_t> block_rng(NB + 1, 0);
+  SsorSweepPlan W;  // the host-side part of the plan: ranges, tallies, what the logs print (the tables stay on the device)
+  W.phased = true;
+  std::vector<int32_t> &block_rng = W.block_rng;
+  block_rng.assign(NB + 1, 0);
   int64_t nct = 0;
   for (int b = 0; b < n_blocks; ++b) {
     sp::Block &B = blk[(size_t)b];
@@ -2531,14 +1701,17 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   if (flags & sp::kNoFit) { *reason = "block does not fit"; return GMG_OK; }
   if (flags & sp::kNoShape) { *reason = "no shape"; return GMG_OK; }
   // ---- 7. the ranges: inside a block the backward one first in the stream, the forward one first in the table
-  std::vector<PhRange> pranges((size_t)n_ranges);
-  std::vector<int64_t> rbase((size_t)n_ranges + 1, 0), blk_bytes0(NB + 1, 0);
+  std::vector<PhRange> &pranges = W.pranges;
+  pranges.resize((size_t)n_ranges);
+  std::vector<int64_t> rbase((size_t)n_ranges + 1, 0);
   int64_t stream_size = 0;
-  int live_max[2] = {0, 0}, max_ws = 0;
+  int *live_max = W.live_max, max_ws = 0;
+  W.block_steps.assign(NB, 0); W.block_bytes.assign(NB, 0);
   for (int b = 0; b < n_blocks; ++b) {
-    blk_bytes0[(size_t)b] = stream_size;
     const sp::Block &B = blk[(size_t)b];
     if (B.nc == 0) continue;
+    W.block_steps[(size_t)b] = 2 * (int64_t)B.S;
+    const int64_t bytes0 = stream_size;
     for (int dir = 1; dir >= 0; --dir) {
       const int ns = nslots[2 * (size_t)b + dir];
       live_max[dir] = std::max(live_max[dir], ns);
@@ -2556,8 +1729,8 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
       pranges[(size_t)(B.rng + dir)] = P;
       rbase[(size_t)(B.rng + dir)] = base;
     }
+    W.block_bytes[(size_t)b] = stream_size - bytes0;
   }
-  blk_bytes0[NB] = stream_size;
   const int y_slots = std::max(2, (max_ws + 1) & ~1);
   // ---- 8. records
   DevPtr<int64_t> d_rbase;
@@ -2598,7 +1771,7 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
     return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: a record addresses memory outside the stream / the LDS slots (internal error)");
   if (chk[3] >= (uint64_t)n) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: a backward record stores outside the level vector (internal error)");
   if (NC && chk[4] * 8 + 8 > (uint64_t)stream_size) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: rhs position outside the stream (internal error)");
-  // ---- 9. accepted: the plan and its host-side members, as setup_sgs + setup_sgs_wave leave them
+  // ---- 9. accepted: the plan and its host-side members, as setup_sgs leaves them
   L.sgs = SgsPlan();
   SgsPlan &G = L.sgs;
   G.n_blocks = n_blocks;
@@ -2614,25 +1787,12 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   }
   HIPC(hipStreamSynchronize(st));
   for (int b = 0; b < n_blocks; ++b)  // (the aux words of the backward records in stream order: each block's coupled rows, last first)
-    for (int q = blk[(size_t)b].nc - 1; q >= 0; --q) G.host_bwd_rows.push_back(ci_row[(size_t)(blk[(size_t)b].q0 + q)]);
-  G.n_self = n_ranges; G.live_max[0] = live_max[0]; G.live_max[1] = live_max[1];
-  G.host_block_row = block_row;
-  G.host_block_rng = block_rng;
-  G.host_block_steps.assign(NB, 0);
-  G.host_block_bytes.assign(NB, 0);
-  for (int b = 0; b < n_blocks; ++b) {
-    G.host_block_steps[(size_t)b] = blk[(size_t)b].nc > 0 ? 2 * (int64_t)blk[(size_t)b].S : 0;
-    G.host_block_bytes[(size_t)b] = blk_bytes0[(size_t)b + 1] - blk_bytes0[(size_t)b];
-  }
-  G.w_y_slots = y_slots;
-  G.w_lds_bytes = y_slots * 8 + kPhWaves * kPhRegion + kPhJunk;
-  G.w_n_ranges = n_ranges;
-  G.phased = true;
-  G.host_pranges = pranges;
-  G.w_n_coupled = nct;
-  G.w_stream_bytes = stream_size;
-  G.w_steps = n_steps; G.w_stages = total_stages;
-  G.n_bwd = n_ranges / 2;
+    for (int q = blk[(size_t)b].nc - 1; q >= 0; --q) W.bwd_rows.push_back(ci_row[(size_t)(blk[(size_t)b].q0 + q)]);
+  W.n_self = n_ranges; W.n_bwd = n_ranges / 2;
+  W.y_slots = y_slots;
+  W.lds_bytes = y_slots * 8 + kPhWaves * kPhRegion + kPhJunk;
+  W.total_steps = n_steps; W.total_stages = total_stages;
+  sgs_set_host_members(G, W, block_row, nct, stream_size);
   G.on_device = true;
   CHK(sgs_wave_tail(ctx, G, true, false, false));
   if (!G.wave) return fail(ctx, GMG_ERR_INVALID, "SSOR plan on the device: the sweep kernel has static LDS (internal error)");
@@ -2640,19 +1800,12 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   if (ctx->debug_upload) {
     std::fprintf(stderr, "[gmg] SGS plan laps (device, %lld rows): graph %.4f s, stages %.4f s, order + slots + shapes + offsets %.4f s, records + check %.4f s\n", (long long)n,
                  laps[0], laps[1], laps[2], laps[3]);
-    std::vector<int64_t> hist_l1(8, 0), hist_l2(4, 0), hist_g(4, 0);
     for (const uint4 &e : blk_tab_h) {
       int g, l1, l2;
       sp::key_shape((int)(e.z & 255u), &g, &l1, &l2);
-      hist_l1[(size_t)std::min(7, l1 / 4)]++; hist_l2[(size_t)(l2 / 8)]++; hist_g[(size_t)g]++;
+      W.hist_l1[(size_t)std::min(7, l1 / 4)]++; W.hist_l2[(size_t)(l2 / 8)]++; W.hist_g[(size_t)g]++;
     }
-    std::fprintf(stderr, "[gmg] SGS step shapes: G %lld %lld %lld %lld | L1/4 %lld %lld %lld %lld %lld %lld %lld %lld | L2/8 %lld %lld %lld %lld\n", (long long)hist_g[0], (long long)hist_g[1],
-                 (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
-                 (long long)hist_l1[5], (long long)hist_l1[6], (long long)hist_l1[7], (long long)hist_l2[0], (long long)hist_l2[1], (long long)hist_l2[2], (long long)hist_l2[3]);
-    std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
-                 "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
-                 "four-wave", (long long)n, (long long)G.w_n_coupled, n_blocks, (long long)total_stages, (long long)n_steps, G.w_n_ranges,
-                 G.w_n_ranges - G.n_bwd, G.n_bwd, G.n_self, y_slots, live_max[0], live_max[1], (double)stream_size / 1e6);
+    sgs_plan_log(G, W, n);
   }
   return GMG_OK;
 }

@@ -79,6 +79,25 @@ struct CsrView {
   int64_t slice_end(int64_t sl) const { return std::min<int64_t>(n_rows, sl * 64 + 64); }  // one past the last row of slice sl
 };
 
+// stable transpose: row j of A^T lists the entries of column j in ascending source row,
+// i.e. the order in which the sequential scatter of Tvmult / restrict_and_add adds them.
+inline void transpose_host(int64_t n_rows, int64_t n_cols, const int64_t *rp, const int32_t *col, const double *val,
+                    std::vector<int64_t> &trp, std::vector<int32_t> &tcol, std::vector<double> &tval) {
+  const int64_t nnz = rp[n_rows];
+  trp.assign((size_t)n_cols + 1, 0);
+  for (int64_t k = 0; k < nnz; ++k) trp[(size_t)col[k] + 1]++;
+  for (int64_t j = 0; j < n_cols; ++j) trp[(size_t)j + 1] += trp[(size_t)j];
+  tcol.resize((size_t)nnz);
+  tval.resize((size_t)nnz);
+  std::vector<int64_t> pos(trp.begin(), trp.end() - 1);
+  for (int64_t i = 0; i < n_rows; ++i)
+    for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
+      const int64_t p = pos[(size_t)col[k]]++;
+      tcol[(size_t)p] = (int32_t)i;
+      tval[(size_t)p] = val[k];
+    }
+}
+
 // what is wrong with the row pointers or columns of A (nullptr: nothing)
 inline const char *check_csr(const CsrView &A) {
   for (int64_t i = 1; i <= A.n_rows; ++i)

@@ -30,15 +30,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gmg_sgs_layout.hpp"  // the constants and plain structs shared with the host planner: kSw*, SwRange, SwStepHdr, sw_stride
 
 namespace gmg {
 
-constexpr int kSwRing = 32768;     // bytes of the record ring in LDS
-constexpr int kSwChunk = 4096;     // unit the helper waves copy
-constexpr int kSwW = 32;           // most entries per sub-step: a row's sum is formed in groups of 8 products, 1..4 groups per sub-step
-constexpr int kSwMaxBlock = 8192;  // bytes of one step's records: 3 blocks + 1 chunk fit the ring (no deadlock)
-
-constexpr int kSwYSlots = 15744;   // doubles of y in LDS (123 KB) by default
 constexpr uint32_t kSwSpinLimit = 1u << 22;  // polls (> 0.1 s) after which a waiting wave declares the sweep broken
 constexpr int kSwThreads = 256;    // wave 0 computes, waves 1..3 stream
 #ifdef GMG_EXPERIMENTS
@@ -46,19 +41,6 @@ constexpr bool kSwExperiments = true;   // tools/build_experiments.sh: a library
 #else
 constexpr bool kSwExperiments = false;
 #endif
-
-// One range = consecutive steps of one sweep direction whose working set fits the LDS.
-struct SwRange {
-  int64_t stream_off;    // byte offset of the range's records (multiple of kSwChunk)
-  int32_t stream_bytes;  // multiple of kSwChunk
-  int32_t n_steps;       // sub-steps
-  int32_t ws_off;        // first entry of the range in ws_ci
-  int32_t n_own;         // slots [0, n_own): rows updated in this range (written back at its end)
-  int32_t n_ws;          // slots in use: updated rows + rows only read
-  int32_t backward;      // 1: second sweep, its results are final
-  int32_t first_raw, first_nrows, groups, pad1;  // groups: g of every sub-step of the range
-};
-
 
 // A step (<= 64 rows of one stage, lane = row) is cut into SUB-STEPS of exactly 8 g entries per row; g (1..4 groups of
 // 8) is fixed for a whole range of steps, chosen by the host so that nearly every step is one sub-step (a 27-point
@@ -76,13 +58,7 @@ struct SwRange {
 //   +32 double a[8 g]   then uint32 LDS byte address of the column's y slot [8 g]
 // rows are padded with a = +0.0, column = the row itself; the record stride is 32 + 96 g rounded up to an odd
 // multiple of 16 bytes = 96 g + 48 (16-byte LDS reads of consecutive lanes then hit distinct banks).
-struct SwStepHdr {
-  uint16_t nrows, flags;       // flags: 1 = first sub-step of its step, 2 = last one
-  uint16_t next_nrows, pad;
-  uint32_t advance;            // bytes to the next header (>= the raw size: records never straddle the ring end)
-  uint32_t next_raw;           // raw bytes of the next sub-step's records (0: last of the range)
-};
-__host__ __device__ constexpr int sw_stride(int g) { return 96 * g + 48; }
+// (SwStepHdr, the 16-byte header, and sw_stride: gmg_sgs_layout.hpp)
 
 struct SgsWaveArgs {
   const SwRange *ranges;

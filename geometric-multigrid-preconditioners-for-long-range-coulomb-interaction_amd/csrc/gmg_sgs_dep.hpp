@@ -35,22 +35,7 @@
 
 namespace gmg {
 
-constexpr int kDpLate = 3;          // a column updated within the last kDpLate steps is gathered by the dependent wave
-constexpr int kDpPrep = 3;          // preparing waves
-constexpr int kDpSlots = 4;         // ring slots: prep of step t starts when step t - 4 is finished, i.e. when slot t % 4 is free
-constexpr int kDpThreads = 64 * (1 + kDpPrep);
-constexpr int kDpMaxL1 = 28;        // T1 slots of a compact record (the shapes of gmg_sgs_phase.hpp: 8 g + l1 + l2 <= 36)
-constexpr int kDpMaxL2 = 24;
-__host__ __device__ constexpr int dp_cstride(int l1, int l2) {  // bytes of a compact record: odd multiple of 16
-  const int s = 48 + 12 * l1 + 8 * l2;
-  return (s / 16) % 2 ? s : s + 16;
-}
-// the widest compact record the shapes allow (l1 + l2 <= 36): (28, 8)
-constexpr int kDpMaxStride = dp_cstride(28, 8);
-static_assert(dp_cstride(12, 24) <= kDpMaxStride && dp_cstride(20, 16) <= kDpMaxStride && dp_cstride(24, 8) <= kDpMaxStride && dp_cstride(16, 16) <= kDpMaxStride, "slot size");
-constexpr int kDpSlotBytes = 16 + kPhMaxRows * kDpMaxStride;  // 14 864
-constexpr int kDpFlagBytes = 64;   // done, abort, ready[4]
-constexpr int kDpYSlots = ((160 * 1024 - kDpSlots * ((kDpSlotBytes + 15) / 16 * 16) - kDpFlagBytes) / 8) & ~1;
+// (kDp*, dp_cstride: gmg_sgs_layout.hpp, shared with the host planner)
 constexpr uint32_t kDpSpinLimit = 1u << 21;
 
 namespace dp {

@@ -20,7 +20,7 @@
 // L2 adds -> one LDS store -> barrier.  A fifth wave touches the record stream ahead of the copies so that they hit
 // the L2.  Nobody spins: every wave executes exactly n_steps + 3 barriers per range.
 // A range is either one of several per direction, with its working set loaded from and written back to ycur at its ends, or
-// SELF-CONTAINED: the whole direction of its block, y slots recycled, nothing loaded or written back (see PhRange below).
+// SELF-CONTAINED: the whole direction of its block, y slots recycled, nothing loaded or written back (see below; PhRange: gmg_sgs_layout.hpp).
 //
 // Shapes.  The code of a step is straight-line for its shape (G groups of 8 head slots, L1, L2): 51 shapes x 2
 // directions are instantiated, the host picks per CHUNK of 32 steps the cheapest shape that holds every row (measured
@@ -38,38 +38,14 @@
 
 namespace gmg {
 
-constexpr int kPhRegion = 16384;  // bytes of LDS per compute wave for the block it is reading (a block never exceeds it)
-constexpr int kPhMaxRows = 32;    // rows per step
-constexpr int kPhMaxEntries = 36; // 8 G + L of a range
-constexpr int kPhWaves = 4;       // compute waves
-constexpr int kPhThreads = 64 * (kPhWaves + 1);  // waves 0..3 compute, wave 4 prefetches the records into the L2
-constexpr int kPhJunk = 512;      // LDS bytes behind the regions: [0, 256) the prefetch wave's copies land in, [256, 264) the hand-over words of gmg_sgs_chain.hpp
-constexpr int kPhYSlots = (160 * 1024 - kPhWaves * kPhRegion - kPhJunk) / 8 & ~1;  // doubles of y in LDS: 12256
-// a range's shape: 8 g head entries, l1 tail entries gathered in the dependent phase, l2 tail entries whose products are formed ahead
-__host__ __device__ constexpr bool ph_shape_ok(int g, int l1, int l2) {
-  return g >= 0 && g <= 3 && l1 >= 4 && l1 <= 28 && l1 % 4 == 0 && l2 >= 0 && l2 <= 24 && l2 % 8 == 0 && 8 * g + l1 + l2 <= kPhMaxEntries;
-}
-__host__ __device__ constexpr int ph_stride(int g, int l) {
-  const int s = 32 + 96 * g + 12 * l;  // multiple of 16 (l is a multiple of 4)
-  return (s / 16) % 2 ? s : s + 16;    // odd multiple of 16: 16-byte LDS reads of consecutive lanes hit distinct banks
-}
-
-// One range = consecutive steps of one sweep direction whose working set fits the LDS.  A step's block: 16-byte
+// (kPh*, ph_shape_ok, ph_stride, ph_key, PhRange and the block table entry: gmg_sgs_layout.hpp, shared with the host planner)
+// One range (PhRange) = consecutive steps of one sweep direction whose working set fits the LDS.  A step's block: 16-byte
 // header {-, bytes of the block four steps on (0: none), its offset in the range's stream, that step's shape key | rows << 8 |
 // T1 slots in use << 16}, then one record
 // per row:  +0 r  +8 1/a_ii  +16 prefix (backward: the forward sweep's sum)  +24 u32 LDS address of the row's y
 //           +28 u32 aux (forward: index, in doubles, of the prefix field of the row's backward record)
 //           +32 head values [8 G]   tail values [L]   head LDS addresses u32 [8 G]   tail LDS addresses u32 [L]
 // (padding: value +0.0, address = the row's own y).
-struct PhRange {
-  int64_t stream_off;
-  int32_t n_steps, ws_off, n_own, n_ws, backward, G, L;  // L = L1 + L2
-  uint32_t blk_tab, L1;               // first entry of the range in the block table
-  int32_t own_ci0, own_dir, pad0[2];  // own_dir = +1 / -1: slot k of the rows updated here is ycur[own_ci0 + own_dir * k] (ycur is numbered in sweep order); 0: see ws_ci
-                                      // pad0[0] = 1: the range is SELF-CONTAINED (a whole sweep direction of its block, y slots recycled, see below); pad0[1]: its y slots
-  uint32_t pf_lead, pf_step;          // prefetch wave: bytes ahead at phase 0, bytes per phase (multiples of 128)
-  uint32_t stream_bytes, pad;
-};
 
 // A SELF-CONTAINED range is a whole sweep direction of its block with nothing loaded and nothing written back.  The
 // planner hands a y slot to the next row once the last reader of its owner has run (so the live rows, not the touched
@@ -142,7 +118,6 @@ struct Turn {
   int key;                    // its next step: shape | rows << 8 | T1 slots in use << 16 (so that P1 does not wait for the header)
   unsigned long long c_wait, c_p1, c_copy, c_p2, c_crit, c_bar, m0;
 };
-__host__ __device__ constexpr int ph_key(int g, int l1, int l2) { return g * 64 + (l1 / 4) * 8 + l2 / 8; }
 
 // One step of shape (G, L1, L2) by one wave: four phases, four barriers.
 // SC: a backward step of a self-contained range (the forward step is the same code in both kinds of range).

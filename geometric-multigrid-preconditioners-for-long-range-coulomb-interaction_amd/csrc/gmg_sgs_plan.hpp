@@ -1,6 +1,6 @@
 // gmg_sgs_plan.hpp -- the plan of the four-wave SSOR sweep (gmg_sgs_phase.hpp) formed on the device from a level's CSR.
 //
-// What setup_sgs_wave (gmg_coulomb.hip) builds on the host for the default configuration -- four waves, one self-contained
+// What ssor_sweep_plan (gmg_sgs_layout.hpp) builds on the host for the default configuration -- four waves, one self-contained
 // range per direction in every block -- is a pure function of the CSR, the block boundaries and y_cap.  The kernels below
 // form the same plan, byte for byte, from the CSR as it lies on the device; the host text is the definition of every piece.
 // Anything else (another sweep variant, a block whose live rows do not fit, a row without a shape, unsorted columns) is
@@ -23,29 +23,10 @@ namespace gmg {
 namespace sp {
 
 // ---- what the host builder and the kernels share: a row's cut against a shape, and the cost of a shape -------------------
-// head [0, h0), T1 [h0, h1), T2 [h1, ne) of a row with ne entries whose late columns are first .. last (none: first = ne,
-// last = ne - 1): false if the row does not fit the shape (g, l1, l2)
-__host__ __device__ inline bool fits(int ne, int first, int last, int g, int l1, int l2, int *h0o, int *h1o) {
-  const int a = last + 1, b = ne - l2;
-  const int h1 = a < b ? b : a;
-  const int c = first < 8 * g ? first : 8 * g, d = h1 - l1;
-  const int h0 = c < d ? d : c;
-  if (h0 > first || h0 > 8 * g || h0 < 0) return false;
-  if (h0o) { *h0o = h0; *h1o = h1; }
-  return true;
-}
-__host__ __device__ inline double dmax(double a, double b) { return a < b ? b : a; }
-// measured phase costs (cycles) of a step of `rows` rows in shape (g, l1, l2): the four-wave sweep with LDS copies
-__host__ __device__ inline double shape_cost(int g, int l1, int l2, double rows) {
-  const int ent = 8 * g + l1 + l2;
-  const double crit = 330.0 + 15.0 * l1 + 4.0 * l2, copy = 45.0 * (16.0 + rows * ph_stride(g, l1 + l2)) / 1024.0,
-               p1 = 150.0 + 8.0 * (2.0 + 0.75 * ent), p2 = 100.0 + 11.0 * (8 * g + l2);
-  return dmax(dmax(crit, copy), dmax(p1, p2)) + 0.1 * (crit + copy + p1 + p2);
-}
+// (sp::fits, sp::shape_cost: gmg_sgs_layout.hpp)
 // the candidates in loop order (g, then l1, then l2): number c <-> shape
 constexpr int kCand = 4 * 7 * 4;
 __host__ __device__ inline void cand_shape(int c, int *g, int *l1, int *l2) { *g = c / 28; *l1 = 4 + 4 * (c % 28 / 4); *l2 = 8 * (c % 4); }
-__host__ __device__ inline void key_shape(int key, int *g, int *l1, int *l2) { *g = key >> 6; *l1 = 4 * (key >> 3 & 7); *l2 = 8 * (key & 7); }
 
 // ssor_build_steps cuts a step where (rows + 1) * (widest row + 1) exceeds the y slots: with at most kPhMaxRows rows of at
 // most 2 kPhMaxEntries entries that cannot happen for kPhYSlots, so the steps here are plain runs of kPhMaxRows rows

@@ -30,7 +30,7 @@
 
 namespace gmg {
 
-constexpr int kRgYSlots = (160 * 1024 - kPhJunk) / 8 & ~1;  // doubles of y in LDS: 20 416
+// (kRgYSlots: gmg_sgs_layout.hpp)
 
 namespace rg {
 

@@ -85,7 +85,7 @@ def check_block(m, rb, re, backward):
     assert (step[rd_row] > step[rd_col]).all() and (step[rd_col] >= 0).all()
     assert (last >= step).all()
     # every coupled row of the block has a step and a slot, no other row has (what the backward RECORDS carry as the row to
-    # store to is read back from a built plan in tests/test_gpu_ssor_sliding.py: the plan needs a context)
+    # store to: tests/ssor_plan_replay.cc decodes the plan's records on the host)
     coupled = np.flatnonzero(rstep >= 0)
     assert np.array_equal(np.flatnonzero(step >= 0), coupled) and np.array_equal(np.flatnonzero(slot >= 0), coupled)
     # per slot, owners sorted by step: the next owner's step is beyond the previous owner's last reader (so no two
