@@ -18,6 +18,9 @@ JACOBI, SSOR, CHEBYSHEV = 0, 1, 2
 PRECOND_GMG, PRECOND_JACOBI, PRECOND_IDENTITY = 0, 1, 2
 SSOR_PARTITION_ROWS, SSOR_PARTITION_BALANCED = 0, 1
 COARSE_CG, COARSE_DIRECT = 0, 1
+CHEB_FIRST_KIND, CHEB_FOURTH_KIND = 0, 1
+CHEB_LMAX_GERSHGORIN, CHEB_LMAX_LANCZOS = 0, 1
+CHEBYSHEV_KEYS = ("polynomial", "lmax_source", "lanczos_steps", "steps_run", "gershgorin", "ritz", "safety", "lmax")
 LEVEL_A, LEVEL_EDGE, LEVEL_EDGE_T = 0, 1, 2
 UNIQUE_ID_BYTES = 128
 
@@ -37,7 +40,7 @@ SYMBOLS = [
     "gmg_build_face_table_resident", "gmg_get_face_table", "gmg_estimate_error_resident", "gmg_get_marks", "gmg_refine_forest_marked",
     "gmg_energy_norm_error_resident",
     "gmg_build_point_locator_resident", "gmg_get_point_locator", "gmg_atom_forces_resident", "gmg_electrostatic_energy_resident",
-    "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse",
+    "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse", "gmg_set_chebyshev", "gmg_estimate_lmax", "gmg_get_chebyshev",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
     "gmg_vec_alloc", "gmg_vec_free", "gmg_vec_upload", "gmg_vec_download", "gmg_vec_set_zero", "gmg_vec_equ",
     "gmg_vec_add", "gmg_vec_sadd", "gmg_vec_dot", "gmg_vec_norms", "gmg_vec_all_zero",
@@ -416,6 +419,24 @@ class Context:
     def set_smoother(self, kind, omega=0.5, steps=2, cheb_degree=2, cheb_ratio=30.0, cheb_lmax=0.0):
         self._chk(self.L.gmg_set_smoother(self.h, C.c_int(kind), C.c_double(omega), C.c_int(steps), C.c_int(cheb_degree),
                                           C.c_double(cheb_ratio), C.c_double(cheb_lmax)))
+
+    def set_chebyshev(self, polynomial=CHEB_FIRST_KIND, lmax_source=CHEB_LMAX_GERSHGORIN, lanczos_steps=0, safety=0.0):
+        """gmg_set_chebyshev: the polynomial and the source of lambda_max; lanczos_steps = 0 / safety = 0 keep their values"""
+        self._chk(self.L.gmg_set_chebyshev(self.h, C.c_int(polynomial), C.c_int(lmax_source), C.c_int(lanczos_steps), C.c_double(safety)))
+
+    def estimate_lmax(self, level, steps=10, coefficients=True):
+        """gmg_estimate_lmax: dict(ritz, steps_run, alpha [steps], beta [steps]) of the Lanczos estimate on `level`"""
+        ritz, run = C.c_double(0.0), C.c_int(0)
+        alpha, beta = np.zeros(max(int(steps), 1)), np.zeros(max(int(steps), 1))
+        pa, pb = (_p(alpha, C.c_double), _p(beta, C.c_double)) if coefficients else (None, None)
+        self._chk(self.L.gmg_estimate_lmax(self.h, C.c_int(level), C.c_int(steps), C.byref(ritz), pa, pb, C.byref(run)))
+        return {"ritz": ritz.value, "steps_run": run.value, "alpha": alpha, "beta": beta}
+
+    def get_chebyshev(self, level):
+        """gmg_get_chebyshev as a dict over CHEBYSHEV_KEYS"""
+        out = np.zeros(8)
+        self._chk(self.L.gmg_get_chebyshev(self.h, C.c_int(level), _p(out, C.c_double)))
+        return dict(zip(CHEBYSHEV_KEYS, out.tolist()))
 
     def set_coarse(self, abs_tol=1e-10, max_it=1000):
         self._chk(self.L.gmg_set_coarse(self.h, C.c_double(abs_tol), C.c_int(max_it)))

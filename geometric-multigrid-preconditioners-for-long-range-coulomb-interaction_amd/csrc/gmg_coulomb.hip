@@ -25,6 +25,7 @@
 #include "gmg_rhs_cells.hpp"
 #include "gmg_estimate.hpp"
 #include "gmg_fastdiag.hpp"
+#include "gmg_lanczos.hpp"
 #include "gmg_mesh_tables.hpp"
 #include "gmg_close.hpp"
 #include "gmg_refine.hpp"
@@ -157,6 +158,13 @@ struct Level {
   DevPtr<double> sol_full_own, def_full_own;
   DevPtr<double> invd;
   double cheb_lmax = 0.0;
+  // the Lanczos bound of D^-1 A (gmg_lanczos.hpp), formed at the level's first Chebyshev use with lmax_source Lanczos and kept
+  // until the level matrix, the step count or the safety factor changes (drop_cheb_estimate)
+  struct ChebEstimate {
+    bool valid = false;
+    int steps_run = 0;
+    double ritz = 0.0;
+  } cheb_est;
   SgsPlan sgs;
 };
 
@@ -242,6 +250,11 @@ struct gmg_context {
   int steps = 2;
   int cheb_degree = 2;
   double cheb_ratio = 30.0, cheb_lmax_user = 0.0;
+  // gmg_set_chebyshev / options cheb_*: the polynomial, where lmax comes from, the Lanczos steps and the safety factor
+  int cheb_polynomial = GMG_CHEB_FIRST_KIND, cheb_lmax_source = GMG_CHEB_LMAX_GERSHGORIN, cheb_lanczos_steps = 10;
+  double cheb_safety = 1.2;
+  int cheb_degree_opt = 0;      // option "cheb_degree": > 0 overrides the degree gmg_set_smoother was given
+  int lanczos_max_blocks = 0;   // option "lanczos_max_blocks": cap on the grids of the estimator's kernels (0: by size); results do not depend on it
   double coarse_tol = 1e-10;
   int coarse_maxit = 1000;
   int coarse_solver = GMG_COARSE_CG;  // gmg_set_coarse_solver; back to CG with every new level-0 matrix and gmg_reset
@@ -268,6 +281,7 @@ struct gmg_context {
   CGState st_final{};
   Event ev_chunk[2];
   DevPtr<double> part_a, part_b;  // reduction partials (4 * kMaxPartials each)
+  DevPtr<double> lanczos_rec;     // the record of one Lanczos estimate (gmg_lanczos.hpp: record_len(kMaxSteps) doubles)
   DevPtr<double> scal_dev;        // 8 doubles
   HostPtr<double> scal_host;      // pinned, 8 doubles
   // outer CG steps (gmg_cg_direction_step / gmg_cg_update_step): g.h stays on the device between the steps
@@ -871,17 +885,101 @@ int sgs_apply(gmg_context *ctx, Level &L, double *y, const double *r, bool prepa
   return GMG_OK;
 }
 
+// The Lanczos estimate of lambda_max(D^-1 A) of a level (gmg_lanczos.hpp): m steps enqueued without a host wait, then one
+// download of the record.  Scratch: the level's w1 (r), w2 (p), t (A p) and the context's partials and record -- free between two
+// smoother calls.  alpha / beta: m entries each or NULL.
+int lanczos_estimate(gmg_context *ctx, Level &L, int level, int m, double *ritz, double *alpha, double *beta, int *steps_run) {
+  if (!L.A.valid || !L.invd) return fail(ctx, GMG_ERR_INVALID, "Lanczos estimate: the level matrix has not been set");
+  if (L.A.halo.active || (level == 0 && l0_partitioned(ctx)))
+    return fail(ctx, GMG_ERR_UNSUPPORTED, "Lanczos estimate: a row-partitioned operator (the estimate has no communication)");
+  if (m < 1 || m > lanczos::kMaxSteps) return fail(ctx, GMG_ERR_INVALID, "Lanczos estimate: 1 .. 64 steps");
+  std::vector<double> rec(2 * (size_t)m + 2, 0.0);
+  if (L.n > 0) {
+    double *d_rec = ctx->lanczos_rec.get();
+    HIPC(hipMemsetAsync(d_rec, 0, sizeof(double) * lanczos::record_len(m), ctx->stream));
+    lanczos::Args a{};
+    a.r = L.w1.get(); a.p = L.w2.get(); a.q = L.t.get(); a.invd = L.invd.get(); a.n = L.n;
+    a.n_part = grid_for(L.n);
+    a.part_pq = ctx->part_a.get(); a.part_rho = ctx->part_b.get(); a.rec = d_rec; a.m = m;
+    const int g = ctx->lanczos_max_blocks > 0 ? std::min(a.n_part, ctx->lanczos_max_blocks) : a.n_part;
+    hipLaunchKernelGGL(lanczos::lanczos_start_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, a);
+    for (int j = 0; j < m; ++j) {
+      a.j = j;
+      CHK(spmv(ctx, L.A, kStore, L.w2.get(), L.t.get()));
+      hipLaunchKernelGGL(lanczos::lanczos_pq_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, a);
+      hipLaunchKernelGGL(lanczos::lanczos_r_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, a);
+      hipLaunchKernelGGL(lanczos::lanczos_p_kernel, dim3(g), dim3(kThreads), 0, ctx->stream, a);
+    }
+    CHK(launch_status(ctx));
+    HIPC(hipMemcpyAsync(rec.data(), d_rec, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(stream_wait(ctx->stream));  // (the one host wait of the estimate)
+  }
+  const int run = std::min(m, std::max(0, (int)rec[0]));
+  if (steps_run) *steps_run = run;
+  if (ritz) *ritz = lanczos::ritz_value(rec.data() + 2, rec.data() + 2 + m, run);
+  for (int j = 0; j < m; ++j) {
+    if (alpha) alpha[j] = j < run ? rec[2 + (size_t)j] : 0.0;
+    if (beta) beta[j] = j < run ? rec[2 + (size_t)m + (size_t)j] : 0.0;
+  }
+  return GMG_OK;
+}
+
+// the bound the Chebyshev smoother uses on a level: the user's, else min(safety ritz, Gershgorin) where the Lanczos bound is
+// selected and has been formed (cheb_prepare), else Gershgorin
+double cheb_lambda(const gmg_context *ctx, const Level &L) {
+  if (ctx->cheb_lmax_user > 0) return ctx->cheb_lmax_user;
+  if (ctx->cheb_lmax_source == GMG_CHEB_LMAX_LANCZOS && L.cheb_est.valid && L.cheb_est.steps_run > 0) {
+    const double s = ctx->cheb_safety * L.cheb_est.ritz;
+    return L.cheb_lmax > 0 ? std::min(s, L.cheb_lmax) : s;
+  }
+  return L.cheb_lmax;
+}
+
+// before a level's Chebyshev steps: form the Lanczos bound if it is wanted and the level has none yet (one host wait, once
+// per level matrix)
+int cheb_prepare(gmg_context *ctx, Level &L, int level) {
+  if (ctx->cheb_lmax_source != GMG_CHEB_LMAX_LANCZOS || ctx->cheb_lmax_user > 0 || L.cheb_est.valid) return GMG_OK;
+  Level::ChebEstimate e;
+  CHK(lanczos_estimate(ctx, L, level, ctx->cheb_lanczos_steps, &e.ritz, nullptr, nullptr, &e.steps_run));
+  e.valid = true;
+  L.cheb_est = e;
+  if (ctx->debug_upload)
+    std::fprintf(stderr, "[gmg] level %d Chebyshev bound: Gershgorin %.6f, Ritz value %.6f after %d of %d Lanczos steps, lambda in use %.6f\n", level, L.cheb_lmax,
+                 e.ritz, e.steps_run, ctx->cheb_lanczos_steps, cheb_lambda(ctx, L));
+  return GMG_OK;
+}
+
 // y = S r for the Chebyshev "preconditioner" (Ifpack_Chebyshev recurrence, zero start).
 // Result lands in *out (one of L.w1 / L.w3).
 int cheb_apply(gmg_context *ctx, Level &L, const double *r, double **out) {
-  const double lmax = ctx->cheb_lmax_user > 0 ? ctx->cheb_lmax_user : L.cheb_lmax;
+  const double lmax = cheb_lambda(ctx, L);
+  const int degree = ctx->cheb_degree_opt > 0 ? ctx->cheb_degree_opt : ctx->cheb_degree;
+  if (ctx->cheb_polynomial == GMG_CHEB_FOURTH_KIND) {
+    // fourth-kind polynomial (Lottes 2022): d = (4 / (3 lmax)) B r, y = d; then for j = 1 .. k - 1
+    //   d = ((2 j - 1) / (2 j + 3)) d + ((8 j + 4) / ((2 j + 3) lmax)) B (r - A y),  y += d
+    // -- the first-kind recurrence's kernels with other scalars; cheb_ratio is not read
+    double *y = L.w1.get(), *yn = L.w3.get(), *w = L.w2.get();
+    hipLaunchKernelGGL(cheb_first_kernel, dim3(grid_for(L.n)), dim3(kThreads), 0, ctx->stream, y, w, r, (const double *)L.invd.get(),
+                       0.75 * lmax, L.n);
+    for (int j = 1; j < degree; ++j) {
+      CHK(import_ghosts(ctx, L.A, y));
+      SpmvArgs a = base_args(L.A, y, yn);
+      a.b = r; a.invd = L.invd.get(); a.w = w;
+      a.c1 = (2.0 * j - 1.0) / (2.0 * j + 3.0);
+      a.omega = (8.0 * j + 4.0) / ((2.0 * j + 3.0) * lmax);
+      launch_spmv_mode<kCheb>(ctx, L.A, a);
+      std::swap(y, yn);
+    }
+    *out = y;
+    return GMG_OK;
+  }
   const double alpha = lmax / ctx->cheb_ratio, beta = lmax;
   const double delta = 2.0 / (beta - alpha), theta = 0.5 * (beta + alpha), s1 = theta * delta;
   double rhok = 1.0 / s1;
   double *y = L.w1.get(), *yn = L.w3.get(), *w = L.w2.get();
   hipLaunchKernelGGL(cheb_first_kernel, dim3(grid_for(L.n)), dim3(kThreads), 0, ctx->stream, y, w, r, (const double *)L.invd.get(),
                      theta, L.n);
-  for (int deg = 1; deg < ctx->cheb_degree; ++deg) {
+  for (int deg = 1; deg < degree; ++deg) {
     const double rhokp1 = 1.0 / (2.0 * s1 - rhok);
     const double d1 = rhokp1 * rhok, d2 = 2.0 * rhokp1 * delta;
     rhok = rhokp1;
@@ -902,6 +1000,7 @@ int smooth_level(gmg_context *ctx, int l, DevPtr<double> &u_io, const double *rh
   double *u = u_io.get(), *spare = spare_io.get();
   const int g = grid_for(L.n);
   int first = 0;
+  if (ctx->smoother == GMG_SMOOTHER_CHEBYSHEV && ctx->steps > 0) CHK(cheb_prepare(ctx, L, l));
   if (from_zero && ctx->steps > 0) {
     first = 1;
     if (ctx->smoother == GMG_SMOOTHER_JACOBI) {
@@ -2043,6 +2142,7 @@ int gmg_create(gmg_context **out, int device_id, int n_levels) {
     if (e.create(hipEventDisableTiming) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->part_a.alloc(4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->part_b.alloc(4 * kMaxPartials) != hipSuccess) return bail(GMG_ERR_HIP);
+  if (ctx->lanczos_rec.alloc(lanczos::record_len(lanczos::kMaxSteps)) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->scal_dev.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->scal_host.alloc(8) != hipSuccess) return bail(GMG_ERR_HIP);
   if (ctx->ocg_dev.alloc(4) != hipSuccess) return bail(GMG_ERR_HIP);
@@ -2186,6 +2286,7 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
   (void)hipSetDevice(ctx->device);
   Level &L = ctx->lv[(size_t)level];
   if (level == 0) drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
+  L.cheb_est = Level::ChebEstimate();       // (a new matrix: its own bound)
   CHK(upload_csr(ctx, L.A, n_rows, n_cols, rowptr, col, val, level > 0));
   CHK(setup_diag(ctx, n_rows, rowptr, col, val, L.invd, &L.cheb_lmax));
   if (level > 0) {
@@ -2208,6 +2309,7 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
         reset_keep_halo(L.A);
         L.invd.reset();
         L.cheb_lmax = 0.0;
+        L.cheb_est = Level::ChebEstimate();
         L.sgs = SgsPlan();
         return rc_plan;
       }
@@ -2240,6 +2342,7 @@ int gmg_set_level_matrix_lattice(gmg_context *ctx, int level, const int32_t nv[3
   DevCSR &m = L.A;
   drop_coarse_direct(ctx);  // (a new level 0: back to the coarse CG)
   reset_keep_halo(m);
+  L.cheb_est = Level::ChebEstimate();
   for (int d = 0; d < 3; ++d) m.lat_nv[d] = nv[d];
   std::copy(Ke, Ke + 64, m.lat_Ke);
   // ---- class table
@@ -2512,6 +2615,47 @@ int gmg_set_smoother(gmg_context *ctx, int kind, double omega, int steps, int ch
   if (cheb_degree > 0) ctx->cheb_degree = cheb_degree;
   if (cheb_ratio > 0) ctx->cheb_ratio = cheb_ratio;
   ctx->cheb_lmax_user = cheb_lmax;
+  return GMG_OK;
+}
+
+// a bound formed with other steps or another safety factor is not the one asked for: every level estimates again
+static void drop_cheb_estimates(gmg_context *ctx) {
+  for (Level &L : ctx->lv) L.cheb_est = Level::ChebEstimate();
+}
+
+int gmg_set_chebyshev(gmg_context *ctx, int polynomial, int lmax_source, int lanczos_steps, double safety) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (polynomial != GMG_CHEB_FIRST_KIND && polynomial != GMG_CHEB_FOURTH_KIND) return fail(ctx, GMG_ERR_INVALID, "gmg_set_chebyshev: unknown polynomial");
+  if (lmax_source != GMG_CHEB_LMAX_GERSHGORIN && lmax_source != GMG_CHEB_LMAX_LANCZOS) return fail(ctx, GMG_ERR_INVALID, "gmg_set_chebyshev: unknown lmax source");
+  if (lanczos_steps < 0 || lanczos_steps > lanczos::kMaxSteps) return fail(ctx, GMG_ERR_INVALID, "gmg_set_chebyshev: 1 .. 64 Lanczos steps (0 keeps the value)");
+  if (!(safety == 0.0 || (safety >= 1.0 && std::isfinite(safety)))) return fail(ctx, GMG_ERR_INVALID, "gmg_set_chebyshev: a safety factor >= 1 (0 keeps the value)");
+  ctx->cheb_polynomial = polynomial;
+  ctx->cheb_lmax_source = lmax_source;
+  if (lanczos_steps > 0 && lanczos_steps != ctx->cheb_lanczos_steps) { ctx->cheb_lanczos_steps = lanczos_steps; drop_cheb_estimates(ctx); }
+  if (safety > 0.0 && safety != ctx->cheb_safety) { ctx->cheb_safety = safety; drop_cheb_estimates(ctx); }
+  return GMG_OK;
+}
+
+int gmg_estimate_lmax(gmg_context *ctx, int level, int steps, double *ritz, double *alpha, double *beta, int *steps_run) {
+  if (!ctx) return GMG_ERR_INVALID;
+  if (level < 0 || level >= ctx->n_levels) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_lmax: level outside the context");
+  if (!ritz || !steps_run) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_lmax: ritz and steps_run expected");
+  if (steps < 1 || steps > lanczos::kMaxSteps) return fail(ctx, GMG_ERR_INVALID, "gmg_estimate_lmax: 1 .. 64 steps");
+  (void)hipSetDevice(ctx->device);
+  return lanczos_estimate(ctx, ctx->lv[(size_t)level], level, steps, ritz, alpha, beta, steps_run);
+}
+
+int gmg_get_chebyshev(gmg_context *ctx, int level, double out[8]) {
+  if (!ctx || !out || level < 0 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const Level &L = ctx->lv[(size_t)level];
+  const bool lanczos_src = ctx->cheb_lmax_source == GMG_CHEB_LMAX_LANCZOS;
+  out[0] = ctx->cheb_polynomial; out[1] = ctx->cheb_lmax_source; out[2] = ctx->cheb_lanczos_steps;
+  out[3] = L.cheb_est.valid ? L.cheb_est.steps_run : 0;
+  out[4] = L.A.valid ? L.cheb_lmax : 0.0;
+  out[5] = L.cheb_est.valid ? L.cheb_est.ritz : 0.0;
+  out[6] = ctx->cheb_safety;
+  // (the Lanczos bound is formed at the level's first Chebyshev use: 0 until then)
+  out[7] = !L.A.valid ? 0.0 : ctx->cheb_lmax_user > 0 ? ctx->cheb_lmax_user : (lanczos_src && !L.cheb_est.valid) ? 0.0 : cheb_lambda(ctx, L);
   return GMG_OK;
 }
 
@@ -4661,6 +4805,7 @@ static int assemble_level(gmg_context *ctx, const char *who, int level, int dim,
     L.has_I = false;
     L.invd.reset();
     L.cheb_lmax = 0.0;
+    L.cheb_est = Level::ChebEstimate();
     L.sgs = SgsPlan();
   };
   clear();
@@ -5305,6 +5450,30 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "exact_chunk_log2") {
     if (!(value >= 0 && value <= 35) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "exact_chunk_log2: an integer in 0 .. 35");
     ctx->exact_chunk_log2 = (int)value;
+  }
+  else if (k == "cheb_polynomial") {
+    if (value != GMG_CHEB_FIRST_KIND && value != GMG_CHEB_FOURTH_KIND) return fail(ctx, GMG_ERR_INVALID, "cheb_polynomial: 0 (first kind) or 1 (fourth kind)");
+    return gmg_set_chebyshev(ctx, (int)value, ctx->cheb_lmax_source, 0, 0.0);
+  }
+  else if (k == "cheb_lmax_source") {
+    if (value != GMG_CHEB_LMAX_GERSHGORIN && value != GMG_CHEB_LMAX_LANCZOS) return fail(ctx, GMG_ERR_INVALID, "cheb_lmax_source: 0 (Gershgorin) or 1 (Lanczos)");
+    return gmg_set_chebyshev(ctx, ctx->cheb_polynomial, (int)value, 0, 0.0);
+  }
+  else if (k == "cheb_lanczos_steps") {
+    if (!(value >= 1 && value <= lanczos::kMaxSteps) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "cheb_lanczos_steps: an integer in 1 .. 64");
+    return gmg_set_chebyshev(ctx, ctx->cheb_polynomial, ctx->cheb_lmax_source, (int)value, 0.0);
+  }
+  else if (k == "cheb_safety") {
+    if (!(value >= 1.0)) return fail(ctx, GMG_ERR_INVALID, "cheb_safety: a factor >= 1");
+    return gmg_set_chebyshev(ctx, ctx->cheb_polynomial, ctx->cheb_lmax_source, 0, value);
+  }
+  else if (k == "cheb_degree") {
+    if (!(value >= 0 && value <= 64) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "cheb_degree: an integer in 0 .. 64 (0: the degree of gmg_set_smoother)");
+    ctx->cheb_degree_opt = (int)value;
+  }
+  else if (k == "lanczos_max_blocks") {
+    if (!(value >= 0 && value <= 65536) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "lanczos_max_blocks: an integer in 0 .. 65536");
+    ctx->lanczos_max_blocks = (int)value;
   }
   else if (k == "sgs_groups") ctx->sgs_groups = (int)value;
   else if (k == "sgs_lds_bytes_override") ctx->sgs_lds_bytes_override = (int)value;

@@ -217,6 +217,9 @@ void ParameterReader::declare_parameters() {
             {"Polynomial degree", "1"}, {"Preconditioner", "GMG"}, {"Lammps input file", "atom_8.data"},
             // additions of this build (the reference selects the smoother by editing :969-970)
             {"Smoother", "SSOR"}, {"Smoother damping", "0.5"}, {"Smoother steps", "2"}, {"Chebyshev degree", "2"},
+            // the Chebyshev smoother's polynomial and its bound of lambda_max(D^-1 A) (gmg_set_chebyshev)
+            {"Chebyshev polynomial", "first kind"}, {"Chebyshev eigenvalue estimate", "Gershgorin"}, {"Chebyshev Lanczos steps", "10"},
+            {"Chebyshev safety factor", "1.2"},
             {"Device resident outer CG", "false"}, {"SSOR blocks", "1"}, {"SSOR block partition", "equal rows"}, {"Charge densities on device", "true"},
             {"Partition level 0", "auto"},
             // HEAD marks with Kelly + the cell residual (:1040-1089); the cluster logs (January 2018) are reproduced by
@@ -351,6 +354,16 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.smoother_omega = prm.get_double("Smoother damping");
   p.smoother_steps = (int)prm.get_integer("Smoother steps");
   p.chebyshev_degree = (int)prm.get_integer("Chebyshev degree");
+  p.chebyshev_polynomial = prm.get("Chebyshev polynomial");
+  if (p.chebyshev_polynomial != "first kind" && p.chebyshev_polynomial != "fourth kind")
+    throw std::runtime_error("Chebyshev polynomial must be <first kind> or <fourth kind>");
+  p.chebyshev_estimate = prm.get("Chebyshev eigenvalue estimate");
+  if (p.chebyshev_estimate != "Gershgorin" && p.chebyshev_estimate != "Lanczos")
+    throw std::runtime_error("Chebyshev eigenvalue estimate must be <Gershgorin> or <Lanczos>");
+  p.chebyshev_lanczos_steps = (int)prm.get_integer("Chebyshev Lanczos steps");
+  if (p.chebyshev_lanczos_steps < 1 || p.chebyshev_lanczos_steps > 64) throw std::runtime_error("Chebyshev Lanczos steps must be 1 .. 64");
+  p.chebyshev_safety = prm.get_double("Chebyshev safety factor");
+  if (!(p.chebyshev_safety >= 1.0)) throw std::runtime_error("Chebyshev safety factor must be >= 1");
   p.device_resident_outer_cg = prm.get_bool("Device resident outer CG");
   p.ssor_blocks = (int)prm.get_integer("SSOR blocks");
   p.ssor_partition = prm.get("SSOR block partition");
@@ -2076,6 +2089,12 @@ int LaplaceProblem<dim>::upload() {
   }
   const int kind = par.smoother == "Jacobi" ? GMG_SMOOTHER_JACOBI : par.smoother == "Chebyshev" ? GMG_SMOOTHER_CHEBYSHEV : GMG_SMOOTHER_SSOR;
   if (with_levels) GMGC(gmg_set_smoother(gmg, kind, par.smoother_omega, par.smoother_steps, par.chebyshev_degree, 0.0, 0.0));
+  // (all four keys at their defaults: the call is left out, so that the option keys of the context stay in force)
+  if (with_levels && (par.chebyshev_polynomial != "first kind" || par.chebyshev_estimate != "Gershgorin" || par.chebyshev_lanczos_steps != 10 ||
+                      par.chebyshev_safety != 1.2))
+    GMGC(gmg_set_chebyshev(gmg, par.chebyshev_polynomial == "fourth kind" ? GMG_CHEB_FOURTH_KIND : GMG_CHEB_FIRST_KIND,
+                           par.chebyshev_estimate == "Lanczos" ? GMG_CHEB_LMAX_LANCZOS : GMG_CHEB_LMAX_GERSHGORIN, par.chebyshev_lanczos_steps,
+                           par.chebyshev_safety));
   if (with_levels) GMGC(gmg_set_coarse(gmg, 1e-10, 1000));  // :962
   if (with_levels && par.coarse_solver == "direct") {
     const int rc_cs = gmg_set_coarse_solver(gmg, GMG_COARSE_DIRECT);

@@ -63,6 +63,10 @@ struct Parameters {
   std::string smoother = "SSOR";  // Jacobi | SSOR | Chebyshev
   double smoother_omega = 0.5;
   int smoother_steps = 2, chebyshev_degree = 2;
+  std::string chebyshev_polynomial = "first kind";  // first kind | fourth kind
+  std::string chebyshev_estimate = "Gershgorin";    // Gershgorin | Lanczos
+  int chebyshev_lanczos_steps = 10;
+  double chebyshev_safety = 1.2;
   bool densities_on_device = true;  // compute_charge_densities() through gmg_charge_density when a device is in use
   int ssor_blocks = 1;  // 1: exact sequential SGS (mpirun=1); B: rank-local SGS on B blocks (mpirun=B)
   std::string ssor_partition = "equal rows";  // where the B blocks are cut: "equal rows" | "balanced" (modelled sweep time)

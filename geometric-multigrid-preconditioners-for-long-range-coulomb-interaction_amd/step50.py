@@ -76,6 +76,10 @@ def prm_text(**kw) -> str:
         "lammps": ("Lammps data", "Lammps input file"),
         "smoother": ("Solver input data", "Smoother"), "omega": ("Solver input data", "Smoother damping"),
         "steps": ("Solver input data", "Smoother steps"), "cheb_degree": ("Solver input data", "Chebyshev degree"),
+        "cheb_polynomial": ("Solver input data", "Chebyshev polynomial"),
+        "cheb_estimate": ("Solver input data", "Chebyshev eigenvalue estimate"),
+        "cheb_lanczos_steps": ("Solver input data", "Chebyshev Lanczos steps"),
+        "cheb_safety": ("Solver input data", "Chebyshev safety factor"),
         "device_cg": ("Solver input data", "Device resident outer CG"),
         "ssor_blocks": ("Solver input data", "SSOR blocks"),
         "ssor_partition": ("Solver input data", "SSOR block partition"),

@@ -98,6 +98,32 @@ int gmg_set_copy_indices(gmg_context *ctx, int level, int64_t n, const int32_t *
  * cheb_*: Chebyshev degree, eigenvalue ratio and lambda_max of D^-1 A (0 = Gershgorin).    */
 int gmg_set_smoother(gmg_context *ctx, int kind, double omega, int steps, int cheb_degree, double cheb_ratio,
                      double cheb_lmax);
+/* The Chebyshev smoother's polynomial and where its lambda_max of D^-1 A comes from (not in the
+ * reference).  Both choices are independent and both defaults are what the library did before this call existed.
+ *   polynomial   GMG_CHEB_FIRST_KIND: the first-kind polynomial on [lmax / cheb_ratio, lmax] (default);
+ *                GMG_CHEB_FOURTH_KIND: the fourth-kind polynomial of Lottes (2022), which needs lmax only: from a zero start
+ *                  d = (4 / (3 lmax)) D^-1 r, y = d;  d = ((2j-1)/(2j+3)) d + ((8j+4)/((2j+3) lmax)) D^-1 (r - A y), y += d,
+ *                  j = 1 .. degree - 1; cheb_ratio is not read
+ *   lmax_source  GMG_CHEB_LMAX_GERSHGORIN: max_i sum_j |a_ij| / |a_ii| (default);
+ *                GMG_CHEB_LMAX_LANCZOS: min(safety x the largest Ritz value of lanczos_steps steps of Jacobi-preconditioned
+ *                  CG on the level, Gershgorin), formed on the device at the level's first Chebyshev use after its matrix was
+ *                  set and kept until the matrix, lanczos_steps or safety changes
+ *   lanczos_steps  1 .. 64, 0 keeps the current value (default 10);  safety >= 1, 0 keeps the current value (default 1.2)
+ * A cheb_lmax > 0 given to gmg_set_smoother wins over both sources.  Anything else: GMG_ERR_INVALID. */
+#define GMG_CHEB_FIRST_KIND 0
+#define GMG_CHEB_FOURTH_KIND 1
+#define GMG_CHEB_LMAX_GERSHGORIN 0
+#define GMG_CHEB_LMAX_LANCZOS 1
+int gmg_set_chebyshev(gmg_context *ctx, int polynomial, int lmax_source, int lanczos_steps, double safety);
+/* The Lanczos estimate of `level` now (level 0 included), whatever the smoother is; it changes nothing the smoother uses.
+ * steps 1 .. 64.  *ritz: the largest Ritz value; *steps_run: the steps that count (fewer than `steps` after a breakdown:
+ * a level with D^-1 A = I ends after one step with ritz = 1); alpha, beta: `steps` entries each (zeros beyond steps_run) or
+ * NULL.  The same bits from call to call.  GMG_ERR_UNSUPPORTED for a row-partitioned operator, GMG_ERR_INVALID before
+ * the level matrix is set or for bad arguments. */
+int gmg_estimate_lmax(gmg_context *ctx, int level, int steps, double *ritz, double *alpha, double *beta, int *steps_run);
+/* out: polynomial, lmax source, Lanczos steps asked, steps run, Gershgorin bound, Ritz value, safety, lambda in use on
+ * `level`; zeros where a value is not known (yet). */
+int gmg_get_chebyshev(gmg_context *ctx, int level, double out[8]);
 /* SolverControl coarse_solver_control(1000, 1e-10, false, false), :962.                    */
 int gmg_set_coarse(gmg_context *ctx, double abs_tol, int max_it);
 /* Which solver stands behind mg_coarse (:965-967): GMG_COARSE_CG, the reference's unpreconditioned CG (default), or
@@ -879,7 +905,10 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * (0 / 1, default 0: while it is 1, gmg_reset leaves the tables of gmg_build_mesh_tables and the closed lines of
  * gmg_close_constraints in the context instead of dropping them -- for a caller that resets the context between the build and
  * the resident assemblies; the caller must set it back to 0 after that reset, or every later gmg_reset keeps the tables too;
- * the next gmg_build_mesh_tables and gmg_destroy drop them regardless).  Options that shape a device
+ * the next gmg_build_mesh_tables and gmg_destroy drop them regardless), cheb_polynomial, cheb_lmax_source,
+ * cheb_lanczos_steps (1 .. 64), cheb_safety (>= 1): the arguments of gmg_set_chebyshev, one at a time; cheb_degree (0 .. 64,
+ * default 0: a value > 0 overrides the degree given to gmg_set_smoother); lanczos_max_blocks (0 .. 65536, default 0 = by
+ * size: cap on the grids of the Lanczos estimate's kernels; the results do not depend on it).  Options that shape a device
  * layout take effect at the next gmg_set_*_matrix.  The same keys are read once from the environment
  * variable GMG_OPTIONS="key=value,..." at gmg_create (for profiling scripts around bench.py).        */
 int gmg_set_option(gmg_context *ctx, const char *key, double value);
