@@ -16,6 +16,14 @@
 // What the records of a built plan carry could so far only be read back from a context on a GPU (tests/test_gpu_ssor_sliding.py:
 // "the plan needs a context"); tests/test_ssor_slots_cpu.py checks the slot allocator alone.  Every case asserts the path it was
 // written for.  Driven by tests/test_ssor_plan_cpu.py; exit status 0 = every requirement held.
+//
+// Second mode, `ssor_plan_replay FILE [mutate=KEY:stride|t1 ...]` (tests/test_ssor_shapes_cpu.py, tests/test_gpu_ssor_shapes.py): FILE
+// holds one CSR matrix, a block count or the caller's block boundaries, and option sets by the library's option names (the format:
+// read_case below).  Every set is planned and put through the same run(); per set the program prints
+//   plan  SET phased dep reg retried ranges self-contained-ranges steps shape-switches min-rows max-rows live-forward live-backward failures
+//   shape SET g l1 l2 backward self-contained steps        (from blk_tab and pranges: one line per shape key, direction and plan kind)
+// Each mutate= argument is a pass of its own, announced by a line `mutation KEY KIND`; it decodes the records of ONE shape key wrongly -- a stride 32 bytes too long, or the end of T1 four slots late -- as a kernel
+// body with a wrong constant would: the replay must notice it in every plan that holds the shape and in no other.
 #include "gmg_sgs_layout.hpp"
 
 #include <cmath>
@@ -31,6 +39,8 @@ namespace {
 
 int g_failures = 0;
 std::string g_case;
+int g_mut_key = -1;    // file mode: the shape key whose records are decoded wrongly (-1: none)
+char g_mut_kind = 0;   // 's': stride + 32; 't': T1 ends four slots late
 #define REQUIRE(cond)                                                                                    \
   do {                                                                                                   \
     if (!(cond) && ++g_failures <= 30) std::fprintf(stderr, "FAIL [%s] line %d: %s\n", g_case.c_str(), __LINE__, #cond); \
@@ -168,6 +178,12 @@ std::vector<Range> decode(const SsorSweepPlan &P, std::vector<char> &S) {
       REQUIRE(rows >= 1 && rows <= 32 && e.bytes == 16u + (uint32_t)rows * (uint32_t)stride && e.bytes <= 16384u && e.off % 16 == 0 && e.pad == 0);
       REQUIRE((uint64_t)e.off + e.bytes + 1008 <= R.stream_bytes);  // (the copies read whole KB)
       if (q > 0) REQUIRE(e.off >= P.blk_tab[(size_t)R.blk_tab + (size_t)q - 1].off + P.blk_tab[(size_t)R.blk_tab + (size_t)q - 1].bytes);
+      if (key == g_mut_key) REQUIRE(g_mut_kind == 's' || g_mut_kind == 't');
+      if (g_failures) return out;
+      int l1d = l1, l2d = l2, strided = stride;  // what the records are decoded with
+      if (key == g_mut_key && g_mut_kind == 's') strided += 32;
+      if (key == g_mut_key && g_mut_kind == 't') { l1d += 4; l2d = std::max(0, l2 - 4); }
+      REQUIRE(e.bytes == 16u + (uint32_t)rows * (uint32_t)strided);
       if (g_failures) return out;
       uint32_t h[4];
       std::memcpy(h, S.data() + R.stream_off + e.off, 16);
@@ -178,10 +194,10 @@ std::vector<Range> decode(const SsorSweepPlan &P, std::vector<char> &S) {
       D.steps.emplace_back();
       for (int u = 0; u < rows; ++u) {
         Rec r;
-        r.blk = S.data() + R.stream_off + e.off; r.blk_pos = R.stream_off + e.off; r.nrows = rows; r.u = u; r.stride = stride; r.fieldmajor = fm;
-        r.n_head = 8 * g; r.l1 = l1; r.l2 = l2;
+        r.blk = S.data() + R.stream_off + e.off; r.blk_pos = R.stream_off + e.off; r.nrows = rows; r.u = u; r.stride = strided; r.fieldmajor = fm;
+        r.n_head = 8 * g; r.l1 = l1d; r.l2 = l2d;
         // T1 slots beyond those in use are padding (the dependent phase stops there)
-        for (int k = 8 * g + t1; k < 8 * g + l1; ++k) REQUIRE(bits_of(r.value(k)) == 0 && r.addr(k) == r.my());
+        for (int k = 8 * g + t1; k < 8 * g + l1d; ++k) REQUIRE(bits_of(r.value(k)) == 0 && r.addr(k) == r.my());
         D.steps.back().push_back(r);
       }
     }
@@ -219,7 +235,7 @@ std::vector<Range> decode(const SsorSweepPlan &P, std::vector<char> &S) {
   return out;
 }
 
-struct Want { bool planned = true, phased = true, dep = false, reg = false; const char *generic = nullptr; };
+struct Want { bool planned = true, phased = true, dep = false, reg = false; const char *generic = nullptr; bool any_kind = false; };  // any_kind: whichever sweep the planner chose
 
 // Plans A with block boundaries (the caller's, balanced cuts or equal runs), checks the plan and replays it.  Returns the plan.
 SsorSweepPlan run(const std::string &name, const Csr &A, const SsorPlanOptions &opt, const Want &want, const std::vector<int64_t> *explicit_rows = nullptr,
@@ -239,7 +255,7 @@ SsorSweepPlan run(const std::string &name, const Csr &A, const SsorPlanOptions &
   }
   REQUIRE(P.outcome == kSsorPlanned);
   if (P.outcome != kSsorPlanned) return P;
-  REQUIRE(P.phased == want.phased && P.dep == want.dep && P.reg == want.reg);
+  if (!want.any_kind) REQUIRE(P.phased == want.phased && P.dep == want.dep && P.reg == want.reg);
   REQUIRE(check_sweep_plan(P, n) == nullptr);
   REQUIRE((int)P.block_rng.size() == n_blocks + 1 && P.block_rng.back() == P.n_ranges() && (int64_t)P.row_ci.size() == n);
   REQUIRE(P.y_slots % 2 == 0 && P.y_slots * 8 <= P.lds_bytes && P.lds_bytes <= 160 * 1024);
@@ -491,9 +507,106 @@ SsorSweepPlan run(const std::string &name, const Csr &A, const SsorPlanOptions &
 
 int steps_of(const SsorSweepPlan &P) { return (int)P.total_steps; }
 
+// ---- file mode ---------------------------------------------------------------------------------------------------------------
+// FILE (text): "ssor-shape-case" / n nnz blocks n_bounds / rowptr [n + 1] / col [nnz] / val [nnz] as 16 hex digits each (the bits) /
+// bounds [n_bounds] (n_bounds > 0: the caller's block boundaries, else `blocks` equal runs) / n_sets / per set one line: its name,
+// the number of options, then key value pairs with the option names of gmg_set_option.
+struct OptionSet { std::string name; SsorPlanOptions opt; };
+
+bool read_case(const char *path, Csr &A, int &blocks, std::vector<int64_t> &bounds, std::vector<OptionSet> &sets) {
+  std::FILE *f = std::fopen(path, "r");
+  if (!f) return false;
+  char word[128];
+  long long n = 0, nnz = 0, nb = 0, v = 0;
+  bool ok = std::fscanf(f, "%127s", word) == 1 && std::string(word) == "ssor-shape-case" && std::fscanf(f, "%lld %lld %d %lld", &n, &nnz, &blocks, &nb) == 4 &&
+            n >= 1 && n <= 100000 && nnz >= 0 && nnz <= 10000000 && nb >= 0 && nb <= n + 2;
+  if (ok) {
+    A.n = n; A.rp.assign((size_t)n + 1, 0); A.col.assign((size_t)nnz, 0); A.val.assign((size_t)nnz, 0.0);
+    for (int64_t &x : A.rp) { ok = ok && std::fscanf(f, "%lld", &v) == 1; x = v; }
+    for (int32_t &x : A.col) { ok = ok && std::fscanf(f, "%lld", &v) == 1 && v >= 0 && v < n; x = (int32_t)v; }
+    for (double &x : A.val) { unsigned long long b = 0; ok = ok && std::fscanf(f, "%llx", &b) == 1; const uint64_t b64 = b; std::memcpy(&x, &b64, 8); }
+    bounds.assign((size_t)nb, 0);
+    for (int64_t &x : bounds) { ok = ok && std::fscanf(f, "%lld", &v) == 1; x = v; }
+    ok = ok && A.rp.front() == 0 && A.rp.back() == nnz;
+    for (size_t i = 0; ok && i < (size_t)n; ++i) ok = A.rp[i] <= A.rp[i + 1];
+  }
+  int n_sets = 0;
+  ok = ok && std::fscanf(f, "%d", &n_sets) == 1 && n_sets >= 1 && n_sets <= 64;
+  for (int s = 0; ok && s < n_sets; ++s) {
+    OptionSet o;
+    int n_opt = 0;
+    ok = std::fscanf(f, "%127s %d", word, &n_opt) == 2 && n_opt >= 0 && n_opt <= 16;
+    o.name = word;
+    for (int k = 0; ok && k < n_opt; ++k) {
+      double x = 0;
+      ok = std::fscanf(f, "%127s %lf", word, &x) == 2;
+      const std::string key = word;
+      if (key == "sgs_sliding") o.opt.sliding = x != 0;
+      else if (key == "sgs_y_slots") o.opt.y_slots = (int)x;
+      else if (key == "sgs_phase_chunk") o.opt.phase_chunk = (int)x;
+      else if (key == "sgs_phase_nosplit") o.opt.phase_nosplit = x != 0;
+      else if (key == "sgs_phase_nocascade") o.opt.phase_nocascade = x != 0;
+      else if (key == "sgs_dep") o.opt.dep = x != 0;
+      else if (key == "sgs_reg") o.opt.reg = x != 0;
+      else if (key == "sgs_disable_phase") o.opt.disable_phase = x != 0;
+      else if (key == "sgs_groups") o.opt.groups = (int)x;
+      else ok = false;
+    }
+    sets.push_back(o);
+  }
+  std::fclose(f);
+  return ok;
+}
+
+int file_mode(int argc, char **argv) {
+  Csr A;
+  int blocks = 1;
+  std::vector<int64_t> bounds;
+  std::vector<OptionSet> sets;
+  if (!read_case(argv[1], A, blocks, bounds, sets)) { std::fprintf(stderr, "ssor_plan_replay: cannot read %s\n", argv[1]); return 2; }
+  int total = 0;
+  for (int a = 2; a < argc || a == 2; ++a) {  // one pass per mutate= argument (without any: one pass, nothing mutated)
+    if (a < argc) {
+      int key = -1;
+      char kind[16] = "";
+      if (std::sscanf(argv[a], "mutate=%d:%15s", &key, kind) != 2 || key < 0 || key > 255 || (std::string(kind) != "stride" && std::string(kind) != "t1")) {
+        std::fprintf(stderr, "ssor_plan_replay: unknown argument %s\n", argv[a]);
+        return 2;
+      }
+      g_mut_key = key; g_mut_kind = kind[0];
+      std::printf("mutation %d %s\n", key, kind);
+    }
+    for (const OptionSet &o : sets) {
+      g_failures = 0;
+      Want w; w.any_kind = true;
+      bool retried = false;
+      const SsorSweepPlan P = run(o.name, A, o.opt, w, bounds.empty() ? nullptr : &bounds, false, blocks, &retried);
+      std::map<std::vector<int>, int> table;  // (g, l1, l2, backward, self-contained) -> steps
+      int switches = 0, min_rows = 0, max_rows = 0, n_self = 0;
+      for (const PhRange &R : P.pranges) {
+        n_self += R.pad0[0] == 1;
+        for (int q = 0; q < R.n_steps; ++q) {
+          const uint32_t word = P.blk_tab[(size_t)R.blk_tab + (size_t)q].word;
+          const int key = (int)(word & 255u), rows = (int)(word >> 8 & 255u);
+          table[{key >> 6, 4 * (key >> 3 & 7), 8 * (key & 7), R.backward != 0, R.pad0[0] == 1}]++;
+          if (q > 0 && (int)(P.blk_tab[(size_t)R.blk_tab + (size_t)q - 1].word & 255u) != key) ++switches;
+          min_rows = min_rows ? std::min(min_rows, rows) : rows;
+          max_rows = std::max(max_rows, rows);
+        }
+      }
+      std::printf("plan %s %d %d %d %d %d %d %lld %d %d %d %d %d %d\n", o.name.c_str(), (int)P.phased, (int)P.dep, (int)P.reg, (int)retried, P.n_ranges(), n_self,
+                  (long long)P.total_steps, switches, min_rows, max_rows, P.live_max[0], P.live_max[1], g_failures);
+      for (const auto &kv : table) std::printf("shape %s %d %d %d %d %d %d\n", o.name.c_str(), kv.first[0], kv.first[1], kv.first[2], kv.first[3], kv.first[4], kv.second);
+      total += g_failures;
+    }
+  }
+  return total ? 1 : 0;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char **argv) {
+  if (argc > 1) return file_mode(argc, argv);
   const SsorPlanOptions def;
   const Want four;
   Want one; one.phased = false;
