@@ -538,7 +538,9 @@ int upload_csr(gmg_context *ctx, DevCSR &m, int64_t n_rows, int64_t n_cols, cons
   int rc = copy_csr(ctx, m, A, rp, T);
   phase("csr copy");
   if (rc == GMG_OK) {
-    P = plan_streams(A, opt, allow_hybrid && !m.halo.active, phase);
+    // (whether m carries a halo plan says nothing here: the plan of these rows is set after them, what m holds is the one of
+    // the operator before -- none after gmg_reset, so every partitioned system matrix of the host driver has taken the hybrid layout)
+    P = plan_streams(A, opt, allow_hybrid, phase);
     rc = P.sell.built ? copy_sell(ctx, m, P) : P.hyb.built ? copy_hybrid(ctx, m, P.hyb) : GMG_OK;
   }
   const hipError_t waited = hipStreamSynchronize(ctx->stream);  // rp, T and P are read by the copies until here

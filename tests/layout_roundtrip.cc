@@ -427,6 +427,91 @@ void hybrid_cases() {
   }
 }
 
+// tests/partition_reference.py localize(): the rows [begin, end) of a square operator with the columns renumbered [owned |
+// ghosts], the ghosts in ascending global order behind the owned ones.  A row keeps its stored order, so a row that refers
+// to a lower rank has local columns that are not ascending.
+Csr localize(const Csr &g, int64_t begin, int64_t end) {
+  std::vector<int32_t> ghosts;
+  for (int64_t k = g.rp[(size_t)begin]; k < g.rp[(size_t)end]; ++k)
+    if (g.col[(size_t)k] < begin || g.col[(size_t)k] >= end) ghosts.push_back(g.col[(size_t)k]);
+  std::sort(ghosts.begin(), ghosts.end());
+  ghosts.erase(std::unique(ghosts.begin(), ghosts.end()), ghosts.end());
+  Csr m;
+  m.n_cols = end - begin + (int64_t)ghosts.size();
+  for (int64_t r = begin; r < end; ++r) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    for (int64_t k = g.rp[(size_t)r]; k < g.rp[(size_t)r + 1]; ++k) {
+      const int32_t gc = g.col[(size_t)k];
+      const bool owned = gc >= begin && gc < end;
+      c.push_back(owned ? (int32_t)(gc - begin) : (int32_t)(end - begin + (std::lower_bound(ghosts.begin(), ghosts.end(), gc) - ghosts.begin())));
+      v.push_back(g.val[(size_t)k]);
+    }
+    m.add_row(c, v);
+  }
+  return m;
+}
+
+// The operators of tests/rank_cases.py LAYOUT_OPERATORS cut into the row chunks of 2, 3 and 4 ranks (chunk = ceil(n / N)):
+// what every rank's planner makes of its owned rows.  The expectations are the planner's output when the cases were
+// written; a rank that falls back to a simpler layout than listed fails.
+struct RankWant { bool sell, val8, col16, sellp, rowclass, lat, hyb; int K, C; int64_t W; };
+const RankWant kCsr = {false, false, false, false, false, false, false, 0, 0, 0};
+const RankWant kHyb = {false, false, false, false, false, false, true, 0, 0, 0};
+RankWant lat_run(int K, int C, int64_t W) { return {true, true, true, true, true, true, false, K, C, W}; }   // lattice window + pattern-run + row classes
+RankWant lat_only(int K, int C, int64_t W) { return {true, true, true, false, false, true, false, K, C, W}; }  // lattice window on plain SELL streams
+const RankWant kSellDistinct = {true, false, true, false, false, false, false, 0, 0, 0};
+
+void localized_case(const char *name, const Csr &g, int n_ranks, const std::vector<RankWant> &want, bool allow_hybrid = false) {
+  LayoutOptions opt;
+  opt.sellp_cost = 4.0;
+  const int64_t n = g.n_rows, chunk = (n + n_ranks - 1) / n_ranks;
+  REQUIRE((int)want.size() == n_ranks);
+  for (int rank = 0; rank < n_ranks; ++rank) {
+    g_case = std::string("localized ") + name + ": rank " + std::to_string(rank) + " of " + std::to_string(n_ranks);
+    const int64_t begin = std::min(n, rank * chunk), end = std::min(n, (rank + 1) * chunk);
+    const Csr m = localize(g, begin, end);
+    const StreamPlan P = plan_and_check(m, opt, allow_hybrid);
+    const RankWant &w = want[(size_t)rank];
+    std::printf("%s: sell %d val8 %d col16 %d pattern-run %d rowclass %d lattice %d (K %d C %d W %lld R0 %lld, %zu generic slices) hybrid %d; %lld rows, %lld ghosts, %d pattern slices\n",
+                g_case.c_str(), (int)P.sell.built, (int)P.sell.s.val8, (int)P.sell.s.col16, (int)P.sell.use_sellp, (int)P.sellp.rowclass, (int)P.lat.built, P.lat.K, P.lat.C,
+                (long long)P.lat.W, (long long)P.lat.R0, P.lat.gen.size(), (int)P.hyb.built, (long long)m.n_rows, (long long)(m.n_cols - m.n_rows),
+                P.sell.built ? P.sell.pat.n_pattern_slices : P.hyb.built ? P.hyb.pat.n_pattern_slices : 0);
+    REQUIRE(P.sell.built == w.sell && P.hyb.built == w.hyb && P.lat.built == w.lat);
+    if (P.sell.built) REQUIRE(P.sell.s.val8 == w.val8 && P.sell.s.col16 == w.col16 && P.sell.use_sellp == w.sellp && P.sellp.rowclass == w.rowclass);
+    if (P.hyb.built) REQUIRE(P.hyb.n_tiles > 0 && P.hyb.pat.n_pattern_slices > 0);
+    if (!P.lat.built) continue;
+    REQUIRE(P.lat.K == w.K && P.lat.C == w.C && P.lat.W == w.W);
+    // an interior row is served without a look at its stored columns: none of them may be a ghost
+    bool owned_only = true;
+    for (int64_t r = P.lat.R0; r < P.lat.R1; ++r) {
+      if (!((r - P.lat.R0) % P.lat.nxy < P.lat.W && (r - P.lat.R0) / P.lat.nxy < P.lat.K)) continue;
+      for (int64_t k = m.rp[(size_t)r]; k < m.rp[(size_t)r + 1]; ++k) owned_only = owned_only && m.col[(size_t)k] < m.n_rows;
+    }
+    REQUIRE(owned_only);
+  }
+}
+
+void localized_operators() {
+  const Csr big = lattice(37, 23, 19), mixed = lattice(21, 17, 40), thin = lattice(13, 11, 9);
+  const Csr hyb = hybrid_band(4400, {224, 1500, 2900, 4300}, {}, {}, true, true, 0);
+  const Csr few = banded(5037, 27, 11, true, 1, 7), distinct = banded(5037, 27, 12, false);
+  for (int n_ranks = 2; n_ranks <= 4; ++n_ranks) {
+    localized_case("hybrid band 4400", hyb, n_ranks, std::vector<RankWant>((size_t)n_ranks, kHyb), true);
+    localized_case("lattice 13 x 11 x 9", thin, n_ranks, std::vector<RankWant>((size_t)n_ranks, kCsr));
+    localized_case("band 5037 distinct values", distinct, n_ranks, std::vector<RankWant>((size_t)n_ranks, kSellDistinct));
+  }
+  localized_case("lattice 37 x 23 x 19", big, 2, {lat_run(8, 7, 851), lat_run(8, 7, 851)});
+  localized_case("lattice 37 x 23 x 19", big, 3, {lat_run(5, 7, 851), lat_only(5, 7, 851), lat_only(5, 7, 851)});
+  localized_case("lattice 37 x 23 x 19", big, 4, {lat_run(3, 7, 851), lat_only(3, 7, 851), lat_only(3, 7, 851), lat_only(3, 7, 851)});
+  localized_case("lattice 21 x 17 x 40", mixed, 2, {kCsr, kCsr});
+  localized_case("lattice 21 x 17 x 40", mixed, 3, {kCsr, kCsr, kCsr});
+  localized_case("lattice 21 x 17 x 40", mixed, 4, {kCsr, lat_run(8, 3, 357), lat_run(8, 3, 357), kCsr});
+  localized_case("band 5037 few values", few, 2, {lat_run(277, 1, 9), lat_run(277, 1, 9)});
+  localized_case("band 5037 few values", few, 3, {lat_run(184, 1, 9), lat_run(184, 1, 9), lat_run(184, 1, 9)});
+  localized_case("band 5037 few values", few, 4, {lat_run(137, 1, 9), lat_run(137, 1, 9), lat_run(137, 1, 9), lat_run(137, 1, 9)});
+}
+
 void invalid_input() {
   g_case = "invalid input";
   Csr m = banded(100, 3, 16, true);
@@ -464,6 +549,7 @@ int main() {
   sell_variants();
   other_sell_cases();
   hybrid_cases();
+  localized_operators();
   invalid_input();
   threading();
   if (g_failures) std::fprintf(stderr, "%d requirement(s) failed\n", g_failures);

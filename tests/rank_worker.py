@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""One rank of tests/test_gpu_ranks_reference.py: opens a context on the communicator named by the id, runs the steps of one
-group of tests/rank_cases.py and writes everything it computed to one .npz (arrays, iteration counts, residuals, return codes,
-comm_info()).  It judges nothing: the parent compares with the references.  numpy and the library only.
+"""One rank of tests/test_gpu_ranks_reference.py and tests/test_gpu_ranks_layouts.py: opens a context on the communicator named
+by the id, runs the steps of one group of tests/rank_cases.py and writes everything it computed to one .npz (arrays, iteration
+counts, residuals, return codes, the debug_upload lines of an upload, comm_info()).  It judges nothing: the parent compares with the references.  numpy and the library only.
 
 usage: rank_worker.py RANK N_RANKS ID_HEX GROUP OUT_NPZ
 (the smoother groups read their hierarchy and vectors from <directory of OUT_NPZ>/<hierarchy>.npz, written by the parent)"""
@@ -208,6 +208,105 @@ def run_outer(c, rank, N, res):
     res["info"] = np.array(json.dumps(c.comm_info()))
 
 
+def captured(fn, path):
+    """what fn() writes to the process's standard error (the library's debug_upload lines), kept in the rank's log as well"""
+    sys.stderr.flush()
+    saved, fd = os.dup(2), os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o600)
+    os.dup2(fd, 2)
+    try:
+        fn()
+    finally:
+        os.dup2(saved, 2)
+        os.close(saved)
+        os.close(fd)
+    with open(path) as f:
+        text = f.read()
+    os.unlink(path)
+    sys.stderr.write(text)
+    return text
+
+
+def load_layout(c, m, rank, N, system, level0, log_path):
+    """load_partitioned for one operator with debug_upload on: (owned rows, log of the system matrix's upload, log of level 0's)"""
+    c.set_global_sizes(m.n_rows, m.n_rows if level0 else 0)
+    c.set_option("debug_upload", 1)
+    logs, locs = {}, []
+    if system:
+        logs["sys"] = captured(lambda: locs.append(set_local(c, RC.SYSTEM, c.set_system_matrix, m, rank, N)), log_path)
+    if level0:
+        logs["lv"] = captured(lambda: locs.append(set_local(c, 0, lambda l: c.set_level_matrix(0, l), m, rank, N)), log_path)
+    c.set_option("debug_upload", 0)
+    c.comm_barrier()
+    return locs[0], logs
+
+
+def run_layout_spmv(c, rank, N, res, log_path):
+    """every operator of RC.LAYOUT_OPERATORS as system matrix and as partitioned level 0, under each of its option sets"""
+    for name in RC.LAYOUT_OPERATORS:
+        m = RC.operator(name)
+        X = RC.spmv_vectors(name)
+        loc = None
+        for variant, options in RC.LAYOUT_VARIANTS[name]:
+            for key, value in options.items():
+                c.set_option(key, value)
+            if loc is None or any(key in RC.UPLOAD_OPTIONS for key in options):
+                loc, logs = load_layout(c, m, rank, N, True, True, log_path)
+                res[f"{name}_{variant}_syslog"], res[f"{name}_{variant}_lvlog"] = np.array(logs["sys"]), np.array(logs["lv"])
+                res[f"{name}_{variant}_layout"] = np.array([int(c.stats().spmv0_layout)])
+            b, e = loc.row_begin, loc.row_begin + loc.n_rows
+            for i in range(RC.N_SPMV_VECTORS):
+                res[f"{name}_{variant}_sys{i}"] = apply(c, lambda out, v: c.spmv(RC.SYSTEM, out, v), X[i, b:e], n_out=e - b)
+                res[f"{name}_{variant}_lv{i}"] = apply(c, lambda out, v: c.spmv(0, out, v), X[i, b:e], n_out=e - b)
+            for key in options:
+                c.set_option(key, 0)
+        x, y = RC.reduce_vectors(257, rank)
+        vx, vy = vec(c, x), vec(c, y)
+        res[f"{name}_dot"] = np.array([c.dot(vx, vy)])
+        vx.free(); vy.free()
+
+
+def run_layout_coarse(c, rank, N, res, log_path):
+    names = RC.layout_coarse_operators(N)
+    tols = {(name, k): RC.stop_case(name, k)[0] for name in names for k in RC.LAYOUT_COARSE_KS[name]}    # host work first
+    for name in names:
+        m = RC.operator(name)
+        loc, logs = load_layout(c, m, rank, N, False, True, log_path)
+        res[f"{name}_lvlog"], res[f"{name}_layout"] = np.array(logs["lv"]), np.array([int(c.stats().spmv0_layout)])
+        b = RC.rhs(name)[loc.row_begin:loc.row_begin + loc.n_rows]
+        for k in RC.LAYOUT_COARSE_KS[name]:
+            for chunk in RC.COARSE_CHUNKS:
+                res[f"{name}_k{k}_c{chunk}_x"], res[f"{name}_k{k}_c{chunk}_m"] = coarse(c, b, tols[name, k], 1000, chunk)
+        res[f"{name}_variant"] = np.array([int(c.stats().coarse_variant)])
+        res[f"{name}_info"] = np.array(json.dumps(c.comm_info()))
+
+
+def run_layout_outer(c, rank, N, res, log_path):
+    C = capi()
+    name = RC.LAYOUT_OUTER
+    m = RC.operator(name)
+    n = m.n_rows
+    b = RC.rhs(name)
+    norm_b = float(R.cg(m, b, np.inf, 0, tier="ld").res)
+    plan = []
+    for pc, what in RC.LAYOUT_OUTER_CASES:     # host work first
+        if what in ("zero", "random"):
+            plan.append((pc, what, b, RC.x_start(name) if what == "random" else np.zeros(n), RC.outer_case(name, pc, what)[0] / norm_b, 500))
+        elif what == "b0":
+            plan.append((pc, what, np.zeros(n), np.zeros(n), 1e-8, 500))
+        else:
+            plan.append((pc, what, b, np.zeros(n), R.REFUSE_TOL / norm_b, R.OUTER_MAX_IT))
+    loc, logs = load_layout(c, m, rank, N, True, False, log_path)
+    res["syslog"] = np.array(logs["sys"])
+    lo, hi = loc.row_begin, loc.row_begin + loc.n_rows
+    for pc, what, rhs, x0, rel_tol, max_it in plan:
+        vb, vx = vec(c, rhs[lo:hi]), vec(c, x0[lo:hi])
+        r = c.cg_solve(vx, vb, rel_tol=rel_tol, max_it=max_it, precond={"identity": C.PRECOND_IDENTITY, "jacobi": C.PRECOND_JACOBI}[pc])
+        res[f"{pc}_{what}_x"] = vx.download()
+        res[f"{pc}_{what}_m"] = np.array([r["status"], r["iterations"], r["starting_value"], r["convergence_value"]], dtype=np.float64)
+        vb.free(); vx.free()
+    res["info"] = np.array(json.dumps(c.comm_info()))
+
+
 def read_hierarchy(path):
     z = np.load(path)
 
@@ -272,6 +371,8 @@ def main():
         run_coarse(c, rank, N, res)
     elif group == "outer":
         run_outer(c, rank, N, res)
+    elif group.startswith("layout_"):
+        {"layout_spmv": run_layout_spmv, "layout_coarse": run_layout_coarse, "layout_outer": run_layout_outer}[group](c, rank, N, res, out + ".upload.txt")
     else:
         run_mg(c, rank, N, res, name, part == "part", os.path.dirname(out))
     res["comm_info"] = np.array(json.dumps(c.comm_info()))

@@ -128,6 +128,51 @@ def test_every_rank_case_is_targetable_and_sensitive(name, k):
     assert smallest > R.SENSITIVITY * tol_x * scale, (smallest / (tol_x * scale))
 
 
+@pytest.mark.parametrize("pc,what", [c for c in RC.LAYOUT_OUTER_CASES if c[1] != "b0"], ids=lambda v: str(v))
+def test_every_layout_outer_case_is_targetable_and_sensitive(pc, what):
+    """the outer CG cases tests/test_gpu_ranks_layouts.py solves on the partitioned hybrid operator: the same proof"""
+    name = RC.LAYOUT_OUTER
+    tol_x = RC.x_tolerance(name)
+    tol, ref = RC.outer_case(name, pc, what)
+    k = R.OUTER_MAX_IT if what == "max_it" else R.OUTER_K
+    for tier in R.TIERS:
+        r = RC.outer_case(name, pc, what, tier)[1]
+        assert r.iterations == k and r.status == (R.NOCONV if what == "max_it" else R.OK), (tier, r.iterations, r.status)
+        if what != "max_it":
+            assert r.history[k] <= tol / R.MARGIN and r.history[:k].min() >= R.MARGIN * tol
+        assert np.abs(r.history - ref.history).max() <= 1e-9 * ref.history[0]
+        assert np.abs(r.x - ref.x).max() <= tol_x / R.X_TOL_FACTOR * np.abs(ref.x).max()
+    scale = np.abs(ref.x).max()
+    smallest = min(np.abs(s).max() for s in ref.steps)
+    assert smallest > R.SENSITIVITY * tol_x * scale, (smallest / (tol_x * scale))
+
+
+def test_layout_operators_are_symmetric_positive_definite():
+    """the operators the layout groups solve on: the 21 x 17 x 40 lattice and the hybrid operator (strictly diagonally
+    dominant with a positive diagonal, symmetric: SPD, so CG applies)"""
+    for name in ("lat21", RC.LAYOUT_OUTER):
+        m = RC.operator(name)
+        n, length = m.n_rows, np.diff(m.rowptr)
+        row = np.repeat(np.arange(n), length)
+        key = np.sort(row * n + m.col)
+        assert np.array_equal(key, np.sort(m.col.astype(np.int64) * n + row))            # the pattern is symmetric
+        order, order_t = np.argsort(row * n + m.col), np.argsort(m.col.astype(np.int64) * n + row)
+        assert np.array_equal(m.val[order], m.val[order_t])                               # and so are the values
+        assert np.all(np.diff(m.col)[np.delete(np.arange(m.nnz - 1), m.rowptr[1:-1] - 1)] > 0)
+        if name == RC.LAYOUT_OUTER:
+            off = np.zeros(n)
+            np.add.at(off, row[m.col != row], np.abs(m.val[m.col != row]))
+            assert np.all(R.diagonal(m) > off) and length.max() == 84 and np.median(length) == 27
+
+
+def test_spread_of_the_tiers_with_the_layout_cases():
+    """S over the solves the layout groups add: it stays below the S of gpu_cases(), so the tolerance
+    64 S on x is the same for them and nothing is widened"""
+    S, S_new = R.spread(False), RC.layout_spread()
+    print(f"layout cases: S = {S_new:.3e} against {S:.3e} of gpu_cases()")
+    assert 0.0 < S_new <= S
+
+
 def test_rank_sequence_cases_are_those_of_gpu_cases():
     """the sequence and the refused solve the ranks run on "csr" are cases of gpu_cases() already"""
     have = set(R.gpu_cases())

@@ -2,7 +2,8 @@
 small operators -- CSR tiles, SELL-64 with each compression, column patterns, the pattern-run tables, the lattice window,
 the hybrid SELL/CSR streams --, decodes every plan back to (row, column, value) triples by the kernels' addressing rules and
 requires the CSR it started from, entry for entry and bit for bit.  It also requires that every case reaches the layout it
-was written for, that tiles and wave pointers cover rows and slices exactly once, that the lattice window's reads stay inside
+was written for -- among them every rank's rows of operators cut into the row chunks of 2, 3 and 4 ranks, ghost columns
+renumbered behind the owned ones --, that tiles and wave pointers cover rows and slices exactly once, that the lattice window's reads stay inside
 the vectors, that invalid input is reported, and that the plans do not depend on the number of host threads."""
 import os
 import subprocess

@@ -132,13 +132,15 @@ def mutations(locs, x_before):
     return out
 
 
-@pytest.mark.parametrize("name,n_ranks", RC.spmv_cases(), ids=lambda v: str(v))
+@pytest.mark.parametrize("name,n_ranks", RC.spmv_cases() + RC.layout_spmv_cases(), ids=lambda v: str(v))
 def test_every_spmv_case_notices_a_wrong_ghost_tail(name, n_ranks):
     """Per (operator, N, vector, mutation): some row of the mutated product is SENSITIVITY bounds or more away from the true
     row sum, the bound being the one the GPU test checks that row with.  The unmutated emulation is within the bound.
     "blocks" has no ghost tail: no mutation applies to it, and what it is there for -- ranks without neighbours that stay in
     step with the rounds that follow -- is seen by the products and reductions that follow it on the same context.  On two
-    ranks nobody has two neighbours, so nothing can be exchanged there; the exchange is shown on three and four ranks."""
+    ranks nobody has two neighbours, so nothing can be exchanged there; the exchange is shown on three and four ranks.
+    The operators of RC.LAYOUT_OPERATORS (tests/test_gpu_ranks_layouts.py) are held to the same: their GPU test asserts this
+    bound next to bit equality, so every mutation fails both."""
     m = RC.operator(name)
     locs = locs_of(name, n_ranks)
     X = RC.spmv_vectors(name)
@@ -156,3 +158,94 @@ def test_every_spmv_case_notices_a_wrong_ghost_tail(name, n_ranks):
             assert ratio >= SENSITIVITY, (name, n_ranks, i, what, ratio)
     print(f"\n[ranks] SpMV sensitivity {name} on {n_ranks} ranks (|difference| / bound, worst row, min over the vectors): "
           + (", ".join(f"{k} {v:.1e}" for k, v in low.items()) if low else "no ghost tail, no mutation applies"))
+
+
+# ------------------------------------------------------------------------------------------------ device layouts (section 33)
+
+def test_the_layout_table_holds_every_layout():
+    """RC.LAYOUTS by itself: each layout tests/test_gpu_ranks_layouts.py is about is expected of some rank, so equality with the
+    table cannot be met by ranks that fell back to the CSR kernel"""
+    for n in RC.RANKS:
+        lat = RC.LAYOUTS["lattice", n]
+        assert all(e.level0 & 32 and e.window[0] == {2: 8, 3: 5, 4: 3}[n] for e in lat)    # fewer plane steps than XCD slabs for N > 2
+        assert [bool(e.level0 & 8) for e in lat] == [True] + [n == 2] * (n - 1)             # lattice plans without the pattern-run plan
+        assert all(e.system == "hybrid" and e.level0 == RC.CSR for e in RC.LAYOUTS["hybspd", n])
+        assert all(e.level0 == RC.FULL and e.window[0] > 100 for e in RC.LAYOUTS["bandfew", n])
+        assert all(e.level0 == RC.SELL_FP64 for e in RC.LAYOUTS["banddist", n])
+        for name in RC.LAYOUT_OPERATORS:     # every rank owns enough rows for a SELL plan to be tried at all, and has ghosts
+            assert all(l.n_rows >= 1024 and len(l.ghost_global) > 0 for l in locs_of(name, n)), (name, n)
+        # a wide row of the hybrid operator refers to every other rank
+        assert all(len(l.neighbor_rank) == n - 1 for l in locs_of("hybspd", n))
+    assert [e.level0 for e in RC.LAYOUTS["lat21", 4]] == [RC.CSR, RC.FULL, RC.FULL, RC.CSR]
+    assert [e.system for e in RC.LAYOUTS["lat21", 4]] == ["hybrid", "sell", "sell", "hybrid"]
+
+
+LATTICE_STRIDES = {"lattice": (37, 37 * 23), "lat21": (21, 21 * 17), "bandfew": (3, 9)}
+
+
+def lattice_row_sets(loc, nx, nxy):
+    """numpy stand-in of the lattice kernel's two row sets for a lexicographic numbering (the window spans whole planes,
+    W = nxy): `fast` = the longest run [R0, R1) of rows at least reach + 2 from either end whose stored columns are all owned
+    and among the 27 lattice offsets -- the rows the marching waves write --, `generic` = the rows of the 64-row slices that
+    hold any other row -- what lattice_generic_slice walks, writing where its `valid` mask lets it.  Returns (K, R0, R1, fast,
+    generic)."""
+    n, reach = loc.n_rows, nxy + nx + 1
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(loc.rowptr))
+    t = loc.col.astype(np.int64) - row + reach
+    entry_ok = (loc.col < n) & (t >= 0) & (t // nxy <= 2) & ((t % nxy) // nx <= 2) & ((t % nxy) % nx <= 2)
+    bad = np.zeros(n, dtype=np.int64)
+    np.add.at(bad, row, ~entry_ok)
+    r = np.arange(n)
+    ok = (bad == 0) & (r >= reach + 2) & (r + reach < n)
+    edges = np.flatnonzero(np.diff(np.concatenate([[0], ok.astype(np.int8), [0]])))
+    begins, ends = edges[0::2], edges[1::2]
+    longest = int(np.argmax(ends - begins))     # (the first of equal ones, as the planner)
+    R0, R1 = int(begins[longest]), int(ends[longest])
+    fast = (r >= R0) & (r < R1)
+    slice_has_other = np.zeros((n + 63) // 64, dtype=bool)
+    np.logical_or.at(slice_has_other, r // 64, ~fast)
+    return -(-(R1 - R0) // nxy), R0, R1, fast, slice_has_other[r // 64]
+
+
+@pytest.mark.parametrize("name,n_ranks", [(name, n) for n in RC.RANKS for name in LATTICE_STRIDES if any(e.window for e in RC.LAYOUTS[name, n])],
+                         ids=lambda v: str(v))
+def test_a_broken_interior_mask_of_the_generic_slices_is_noticed(name, n_ranks):
+    """The interior rows inside a generic slice written twice, the generic slice's value last (lattice_generic_slice without
+    its `valid` mask).  The two row sets come from the numpy stand-in above, which must give the K, R0 and R1 of RC.LAYOUTS.
+
+    In a product the second write carries the same bits as the first -- the streams of a generic slice hold its interior rows
+    too, and both kernels sum a row in its stored order, which is what their bit equality with the CSR product on one rank
+    says -- so y = A x cannot show this mutation and need not.  What the mask guards is the coarse CG's d.h: a row written
+    twice is summed twice.  Shown on the first iteration of the coarse solves of the layout group (d = b): the mutated
+    alpha = g.g / d.h moves x_1 = alpha d, the solve that stops at iteration 1, by SENSITIVITY tolerances on x or more, with
+    the mask broken on any single rank.  The opposite defect, a mask that is too wide, leaves rows unwritten: y is pre-filled
+    with NaN and the product test requires that none is left."""
+    nx, nxy = LATTICE_STRIDES[name]
+    m = RC.operator(name)
+    locs = locs_of(name, n_ranks)
+    coarse = name in RC.layout_coarse_operators(n_ranks)
+    if coarse:
+        b = RC.rhs(name)
+        h = PR.row_sums(m, b)[0].astype(np.float64)
+        dh, ref = float(b @ h), RC.stop_case(name, 1)[1]
+        tol = RC.x_tolerance(name) * np.abs(ref.x).max()
+        assert ref.iterations == 1 and np.abs(ref.x - (b @ b) / dh * b).max() <= tol
+    low, n_twice = np.inf, []
+    for r, l in enumerate(locs):
+        want = RC.LAYOUTS[name, n_ranks][r].window
+        if want is None:
+            continue
+        K, R0, R1, fast, generic = lattice_row_sets(l, nx, nxy)
+        assert (K, R0, R1) == (want[0], want[2], want[3]), (name, n_ranks, r, (K, R0, R1), want)
+        twice = np.flatnonzero(fast & generic)
+        n_twice.append(len(twice))
+        assert len(twice) > 0 and np.all(l.col[np.concatenate([np.arange(l.rowptr[i], l.rowptr[i + 1]) for i in np.flatnonzero(fast)])] < l.n_rows)
+        if coarse:
+            g = l.row_begin + twice
+            x1 = (b @ b) / (dh + float(b[g] @ h[g])) * b
+            low = min(low, float(np.abs(x1 - ref.x).max() / tol))
+    assert n_twice, (name, n_ranks)
+    if coarse:
+        assert low >= SENSITIVITY, (name, n_ranks, low)
+    print(f"\n[ranks] broken interior mask, {name} on {n_ranks} ranks: rows written twice per rank {n_twice}"
+          + (f", |x_1 - x_ref| / tolerance at least {low:.1e}" if coarse else " (no coarse solve on this operator)"))
