@@ -55,6 +55,7 @@ SYMBOLS = [
     "gmg_gaussian_potential", "gmg_energy_norm_error",
     "gmg_get_ssor_plan", "gmg_get_ssor_backward_rows", "gmg_ssor_slot_plan",
     "gmg_get_ssor_plan_array", "gmg_get_ssor_plan_origin",
+    "gmg_ssor_pack_levels", "gmg_ssor_slot_plan_packed", "gmg_get_ssor_schedule",
 ]
 
 
@@ -1134,6 +1135,12 @@ class Context:
         self._chk(self.L.gmg_get_ssor_plan(self.h, C.c_int(level), _p(out, C.c_int64)))
         return dict(zip(SSOR_PLAN_KEYS, (int(v) for v in out)))
 
+    def get_ssor_schedule(self, level):
+        """gmg_get_ssor_schedule as a dict (SSOR_SCHEDULE_KEYS)."""
+        out = np.zeros(4, dtype=np.int64)
+        self._chk(self.L.gmg_get_ssor_schedule(self.h, C.c_int(level), _p(out, C.c_int64)))
+        return dict(zip(SSOR_SCHEDULE_KEYS, (int(v) for v in out)))
+
     def get_ssor_backward_rows(self, level):
         """gmg_get_ssor_backward_rows: the level rows the self-contained backward records store to, in stream order."""
         cnt = C.c_int64(0)
@@ -1161,22 +1168,40 @@ class Context:
 # gmg_get_ssor_plan_array: the values of GMG_SSOR_PLAN_* in order
 SSOR_PLAN_ARRAYS = ("stream", "ranges", "blk_tab", "block_rng", "row_ci", "ci_row", "rpos_f", "rpos_b", "iso_diag", "iso_invd")
 SSOR_PLAN_KEYS = ("forward_ranges", "backward_ranges", "self_contained_ranges", "y_slots", "max_live_forward", "max_live_backward", "steps", "stream_bytes")
+SSOR_SCHEDULE_KEYS = ("packed", "levels", "steps_per_direction", "stage_steps")
 
 
-def ssor_slot_plan(m, row_begin, row_end, backward):
+def ssor_slot_plan(m, row_begin, row_end, backward, packed=False):
     """gmg_ssor_slot_plan on a host CSR (needs no device): (step, last_reader, slot, n_steps, n_slots) of one block and direction;
-    the three arrays have one entry per row of the block, -1 for a row without couplings inside it."""
+    the three arrays have one entry per row of the block, -1 for a row without couplings inside it.  packed: over the packed
+    levels (gmg_ssor_slot_plan_packed) instead of the stages."""
     rp, col, val = _csr(m)
     n = len(rp) - 1
     k = max(int(row_end) - int(row_begin), 1)
     step, last, slot = (np.full(k, -1, dtype=np.int32) for _ in range(3))
     ns, nl = C.c_int64(0), C.c_int64(0)
-    rc = load().gmg_ssor_slot_plan(C.c_int64(n), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double), C.c_int64(int(row_begin)), C.c_int64(int(row_end)),
-                                   C.c_int(int(bool(backward))), _p(step, C.c_int32), _p(last, C.c_int32), _p(slot, C.c_int32), C.byref(ns), C.byref(nl))
+    name = "gmg_ssor_slot_plan_packed" if packed else "gmg_ssor_slot_plan"
+    rc = getattr(load(), name)(C.c_int64(n), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double), C.c_int64(int(row_begin)), C.c_int64(int(row_end)),
+                               C.c_int(int(bool(backward))), _p(step, C.c_int32), _p(last, C.c_int32), _p(slot, C.c_int32), C.byref(ns), C.byref(nl))
     if rc != OK:
-        raise GMGError(rc, "gmg_ssor_slot_plan")
+        raise GMGError(rc, name)
     k = int(row_end) - int(row_begin)
     return step[:k], last[:k], slot[:k], ns.value, nl.value
+
+
+def ssor_pack_levels(m, row_begin, row_end):
+    """gmg_ssor_pack_levels on a host CSR (needs no device): (level per row of the block, -1 for a row without couplings inside
+    it; number of levels; steps of a direction when the stages are walked 32 rows at a time)."""
+    rp, col, val = _csr(m)
+    n = len(rp) - 1
+    k = int(row_end) - int(row_begin)
+    level = np.full(max(k, 1), -1, dtype=np.int32)
+    nl, ns = C.c_int64(0), C.c_int64(0)
+    rc = load().gmg_ssor_pack_levels(C.c_int64(n), _p(rp, C.c_int64), _p(col, C.c_int32), _p(val, C.c_double), C.c_int64(int(row_begin)), C.c_int64(int(row_end)),
+                                     _p(level, C.c_int32), C.byref(nl), C.byref(ns))
+    if rc != OK:
+        raise GMGError(rc, "gmg_ssor_pack_levels")
+    return level[:k], nl.value, ns.value
 
 
 def ssor_balance_rows(m, n_blocks, use_values=True):

@@ -121,6 +121,8 @@ struct SgsPlan {
   std::vector<int32_t> host_bwd_rows;  // level rows the self-contained backward records store their results to (their aux words, stream order)
   int n_self = 0, live_max[2] = {0, 0};  // self-contained ranges of the four-wave sweep; most y slots live at once per direction, as the allocator found them (0: not run)
   int64_t w_n_coupled = 0, w_stream_bytes = 0, w_steps = 0, w_stages = 0;
+  int n_packed = 0;  // blocks whose rows are scheduled by slack (w_stages counts their levels); gmg_get_ssor_schedule
+  int64_t w_fwd_steps = 0, w_stage_steps = 0;  // steps of a direction: the plan's, and what the stages need
   std::vector<int32_t> host_block_row;  // n_blocks + 1 (several ranks: who sweeps which rows)
   std::vector<int64_t> host_block_steps;  // n_blocks: sub-steps of each block's chain (both directions; gmg_get_ssor_partition)
   std::vector<int64_t> host_block_bytes;  // n_blocks: record-stream bytes of each block (plan log)
@@ -304,6 +306,7 @@ struct gmg_context {
   int sgs_y_slots = 0;      // 0 = kSwYSlots; tests shrink it to force several LDS ranges
   bool ssor_plan_device = false;  // option "ssor_plan_device": the default four-wave plan of a level is formed by kernels (gmg_sgs_plan.hpp) where it applies
   bool sgs_sliding = true;  // four-wave sweep: one self-contained range per direction where a block's live rows fit the y slots
+  int sgs_pack = -1;        // self-contained ranges: rows scheduled by slack (ssor_pack_levels).  0 never, 1 always, -1 (unset) by the level's size
   bool sgs_disable_wave = false, sgs_disable_phase = false, sgs_chain = false, sgs_dep = false, sgs_reg = false, debug_upload = false, sgs_profile = false;
   int sgs_profile_mode = 0;
   int sgs_phase_chunk = 0;         // steps per chunk of one shape (0: default)
@@ -1517,7 +1520,7 @@ SsorPlanOptions ssor_plan_options(const gmg_context *ctx) {
   o.dep = ctx->sgs_dep; o.reg = ctx->sgs_reg; o.chain = ctx->sgs_chain; o.sliding = ctx->sgs_sliding;
   o.y_slots = ctx->sgs_y_slots; o.groups = ctx->sgs_groups; o.phase_chunk = ctx->sgs_phase_chunk;
   o.phase_nosplit = ctx->sgs_phase_nosplit; o.phase_nocascade = ctx->sgs_phase_nocascade; o.pf_lead_kb = ctx->sgs_pf_lead_kb;
-  o.debug = ctx->debug_upload;
+  o.debug = ctx->debug_upload; o.pack = ctx->sgs_pack;
   return o;
 }
 
@@ -1532,6 +1535,7 @@ void sgs_set_host_members(SgsPlan &G, const SsorSweepPlan &W, const std::vector<
   G.w_y_slots = W.y_slots; G.w_lds_bytes = W.lds_bytes; G.w_n_ranges = W.n_ranges(); G.n_bwd = W.n_bwd;
   G.phased = W.phased; G.dep = W.dep; G.reg = W.reg;
   G.w_n_coupled = n_coupled; G.w_stream_bytes = stream_bytes; G.w_steps = W.total_steps; G.w_stages = W.total_stages;
+  G.n_packed = W.n_packed; G.w_fwd_steps = W.fwd_steps; G.w_stage_steps = W.stage_steps;
 }
 
 // debug_upload: the shapes of the steps and the plan's totals
@@ -1542,9 +1546,12 @@ void sgs_plan_log(const SgsPlan &G, const SsorSweepPlan &W, int64_t n) {
                  (long long)hist_g[2], (long long)hist_g[3], (long long)hist_l1[0], (long long)hist_l1[1], (long long)hist_l1[2], (long long)hist_l1[3], (long long)hist_l1[4],
                  (long long)hist_l1[5], (long long)hist_l1[6], (long long)hist_l1[7], (long long)hist_l2[0], (long long)hist_l2[1], (long long)hist_l2[2], (long long)hist_l2[3]);
   std::fprintf(stderr, "[gmg] SGS %s plan: %lld rows, %lld coupled, %d blocks, %lld stages, %lld sub-steps, %d ranges (%d forward + %d backward, %d self-contained), "
-               "y slots %d (most live: forward %d, backward %d), stream %.1f MB\n",
+               "y slots %d (most live: forward %d, backward %d), stream %.1f MB; schedule: packed %d, levels %lld, steps per direction %lld, by stages %lld "
+               "(blocks kept on their stages: %d for the y slots, %d for a step without a shape)\n",
                W.phased ? "four-wave" : "one-wave", (long long)n, (long long)G.w_n_coupled, (int)G.host_block_row.size() - 1, (long long)G.w_stages, (long long)G.w_steps, G.w_n_ranges,
-               G.w_n_ranges - G.n_bwd, G.n_bwd, G.n_self, G.w_y_slots, G.live_max[0], G.live_max[1], (double)G.w_stream_bytes / 1e6);
+               G.w_n_ranges - G.n_bwd, G.n_bwd, G.n_self, G.w_y_slots, G.live_max[0], G.live_max[1], (double)G.w_stream_bytes / 1e6,
+               G.n_packed > 0 ? 1 : 0, (long long)G.w_stages, (long long)G.w_fwd_steps, (long long)G.w_stage_steps,
+               W.n_pack_no_slots, W.n_pack_no_shape);
 }
 
 // debug_upload: the partition -- per block rows, sub-steps and stream of the plan, and the modelled cost (us) the balanced cuts equalise
@@ -1646,7 +1653,7 @@ dim3 asm_blocks(const gmg_context *ctx, int64_t n, int per_block, int most = 1 <
 
 // ---- the same plan formed on the device (option ssor_plan_device; gmg_sgs_plan.hpp) ----------------------------------------
 // Why the device builder does not apply to this context (nullptr: it may); one fixed text per cause.
-const char *sgs_device_refusal(const gmg_context *ctx, bool explicit_rows) {
+const char *sgs_device_refusal(const gmg_context *ctx, bool explicit_rows, int64_t n) {
   if (ctx->dist) return "communicator";
   if (!explicit_rows && ctx->ssor_partition == GMG_SSOR_PARTITION_BALANCED) return "balanced partition";
   if (!ctx->sgs_sliding) return "option sgs_sliding unset";
@@ -1661,6 +1668,8 @@ const char *sgs_device_refusal(const gmg_context *ctx, bool explicit_rows) {
   if (ctx->sgs_phase_nosplit) return "option sgs_phase_nosplit set";
   if (ctx->sgs_phase_nocascade) return "option sgs_phase_nocascade set";
   if (ctx->sgs_pf_lead_kb) return "option sgs_pf_lead_kb set";
+  // (the kernels of gmg_sgs_plan.hpp form the stage-by-stage schedule; a level whose rows are scheduled by slack is the host's)
+  if (ssor_pack_wanted(ssor_plan_options(ctx), n)) return "packed schedule";
   return nullptr;
 }
 
@@ -1670,7 +1679,7 @@ const char *sgs_device_refusal(const gmg_context *ctx, bool explicit_rows) {
 // error (GMG_ERR_INVALID): no sweep runs on it.
 int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, const int32_t *col, const double *val,
                      const std::vector<int64_t> *explicit_rows, const char **reason) {
-  *reason = sgs_device_refusal(ctx, explicit_rows != nullptr);
+  *reason = sgs_device_refusal(ctx, explicit_rows != nullptr, n);
   if (*reason) return GMG_OK;
   if (n <= 0) { *reason = "empty level"; return GMG_OK; }
   const std::vector<int32_t> block_row = ssor_block_rows(n, nullptr, nullptr, nullptr, explicit_rows, false, ctx->ssor_blocks);  // (the caller's or equal runs)
@@ -1893,6 +1902,7 @@ int setup_sgs_device(gmg_context *ctx, Level &L, int64_t n, const int32_t *rp, c
   W.y_slots = y_slots;
   W.lds_bytes = y_slots * 8 + kPhWaves * kPhRegion + kPhJunk;
   W.total_steps = n_steps; W.total_stages = total_stages;
+  W.fwd_steps = W.stage_steps = n_steps / 2;  // (the stages, kPhMaxRows rows at a time: never packed)
   sgs_set_host_members(G, W, block_row, nct, stream_size);
   G.on_device = true;
   CHK(sgs_wave_tail(ctx, G, true, false, false));
@@ -2297,7 +2307,7 @@ int gmg_set_level_matrix(gmg_context *ctx, int level, int64_t n_rows, int64_t n_
       // the device builder reads an int32 CSR: a copy of this call's arrays (upload_csr may have kept another layout)
       DevPtr<int32_t> d_rp, d_col;
       DevPtr<double> d_val;
-      if (!sgs_device_refusal(ctx, explicit_rows != nullptr) && n_rows > 0) {
+      if (!sgs_device_refusal(ctx, explicit_rows != nullptr, n_rows) && n_rows > 0) {
         if (rowptr[n_rows] > INT32_MAX) return fail(ctx, GMG_ERR_INVALID, "gmg_set_level_matrix: more than 2^31 entries");
         const std::vector<int32_t> rp32(rowptr, rowptr + n_rows + 1);
         HIPC(upload(d_rp, rp32, ctx->stream));
@@ -5414,6 +5424,7 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "ssor_balanced") ctx->ssor_partition = on ? GMG_SSOR_PARTITION_BALANCED : GMG_SSOR_PARTITION_ROWS;
   else if (k == "sgs_y_slots") ctx->sgs_y_slots = (int)value;
   else if (k == "sgs_sliding") ctx->sgs_sliding = on;
+  else if (k == "sgs_pack") ctx->sgs_pack = value < 0 ? -1 : on ? 1 : 0;
   else if (k == "ssor_plan_device") ctx->ssor_plan_device = on;
   else if (k == "sgs_disable_wave") ctx->sgs_disable_wave = on;
   else if (k == "sgs_disable_phase") ctx->sgs_disable_phase = on;
@@ -5570,6 +5581,16 @@ int gmg_get_ssor_plan(gmg_context *ctx, int level, int64_t out[8]) {
   return GMG_OK;
 }
 
+int gmg_get_ssor_schedule(gmg_context *ctx, int level, int64_t out[4]) {
+  if (!ctx || !out || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
+  const SgsPlan &G = ctx->lv[(size_t)level].sgs;
+  if (G.host_block_row.empty()) return fail(ctx, GMG_ERR_INVALID, "gmg_get_ssor_schedule: the level matrix has not been set");
+  std::fill(out, out + 4, (int64_t)0);
+  if (!G.wave) return GMG_OK;  // the generic CSR sweep has no plan
+  out[0] = G.n_packed > 0 ? 1 : 0; out[1] = G.w_stages; out[2] = G.w_fwd_steps; out[3] = G.w_stage_steps;
+  return GMG_OK;
+}
+
 int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int32_t *rows) {
   if (!ctx || !count || level < 1 || level >= ctx->n_levels) return GMG_ERR_INVALID;
   const SgsPlan &G = ctx->lv[(size_t)level].sgs;
@@ -5634,6 +5655,57 @@ int gmg_ssor_slot_plan(int64_t n, const int64_t *rowptr, const int32_t *col, con
   if (m > 0) {
     if (!ssor_block_graph(row_begin, row_end, rowptr, col, val, B)) return GMG_ERR_INVALID;  // (ascending columns expected)
     ssor_build_steps(dir, B.n_stages, B.sptr, B.by_stage, B.prp, B.pcol, kPhMaxRows, true, 0, kPhYSlots, seq, steps);
+    ssor_slot_alloc(m, B.prp, B.pcol, dir, seq, steps, S);
+  }
+  if (step) std::copy(S.step.begin(), S.step.end(), step);
+  if (last_reader) std::copy(S.last.begin(), S.last.end(), last_reader);
+  if (slot) std::copy(S.slot.begin(), S.slot.end(), slot);
+  if (n_steps) *n_steps = (int64_t)steps.size();
+  if (n_slots) *n_slots = S.n_slots;
+  return GMG_OK;
+}
+
+// a host CSR and a block of its rows as the two routines below take them: sizes, row pointers, columns in range
+static bool ssor_host_csr_ok(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end) {
+  if (n < 0 || n > INT32_MAX || row_begin < 0 || row_end < row_begin || row_end > n || (n > 0 && (!rowptr || !col || !val)) || (n > 0 && rowptr[0] != 0)) return false;
+  for (int64_t i = 0; i < n; ++i) {
+    if (rowptr[i + 1] < rowptr[i]) return false;
+    for (int64_t k = rowptr[i]; k < rowptr[i + 1]; ++k)
+      if (col[k] < 0 || col[k] >= n) return false;
+  }
+  return true;
+}
+
+int gmg_ssor_pack_levels(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end, int32_t *level,
+                         int64_t *n_levels, int64_t *n_stage_steps) {
+  if (!ssor_host_csr_ok(n, rowptr, col, val, row_begin, row_end)) return GMG_ERR_INVALID;
+  SsorBlockGraph B;
+  SsorLevels Lv;
+  if (row_end > row_begin) {
+    if (!ssor_block_graph(row_begin, row_end, rowptr, col, val, B)) return GMG_ERR_INVALID;  // (ascending columns expected)
+    ssor_pack_levels(B, Lv);
+    for (size_t i = 0; i < Lv.level.size(); ++i)
+      if (!B.coupled[i]) Lv.level[i] = -1;  // a row without couplings has no level
+  }
+  if (level) std::copy(Lv.level.begin(), Lv.level.end(), level);
+  if (n_levels) *n_levels = Lv.n_levels;
+  if (n_stage_steps) *n_stage_steps = Lv.stage_steps;
+  return GMG_OK;
+}
+
+int gmg_ssor_slot_plan_packed(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end, int backward,
+                              int32_t *step, int32_t *last_reader, int32_t *slot, int64_t *n_steps, int64_t *n_slots) {
+  if (!ssor_host_csr_ok(n, rowptr, col, val, row_begin, row_end)) return GMG_ERR_INVALID;
+  const int m = (int)(row_end - row_begin), dir = backward ? 1 : 0;
+  SsorBlockGraph B;
+  SsorLevels Lv;
+  SsorSlotPlan S;
+  std::vector<int32_t> seq;
+  std::vector<SsorStep> steps;
+  if (m > 0) {
+    if (!ssor_block_graph(row_begin, row_end, rowptr, col, val, B)) return GMG_ERR_INVALID;  // (ascending columns expected)
+    ssor_pack_levels(B, Lv);
+    ssor_build_steps(dir, Lv.n_levels, Lv.sptr, Lv.by_level, B.prp, B.pcol, kPhMaxRows, true, 0, kPhYSlots, seq, steps);
     ssor_slot_alloc(m, B.prp, B.pcol, dir, seq, steps, S);
   }
   if (step) std::copy(S.step.begin(), S.step.end(), step);

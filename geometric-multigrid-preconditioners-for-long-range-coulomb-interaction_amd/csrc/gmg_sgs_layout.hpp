@@ -134,12 +134,22 @@ struct SsorPlanOptions {  // the context's options that steer a plan
   bool phase_nosplit = false, phase_nocascade = false;
   int pf_lead_kb = 0;
   bool debug = false;
+  int pack = -1;  // rows scheduled by slack (ssor_pack_levels): 0 never, 1 always, < 0 levels of at least kPhPackMinRows rows
 };
+// Below the gate a sweep direction is a few hundred steps, tens of us: nothing to gain, and every small level keeps the plan
+// the stages give (the device builder of gmg_sgs_plan.hpp forms that one).
+constexpr int64_t kPhPackMinRows = 8192;
+// does the four-wave plan with self-contained ranges of a level of n rows try the packed levels?
+inline bool ssor_pack_wanted(const SsorPlanOptions &opt, int64_t n) {
+  const bool self = !opt.disable_wave && !opt.disable_phase && !opt.profile && !opt.dep && !opt.reg && !opt.chain && opt.sliding;
+  return self && (opt.pack > 0 || (opt.pack < 0 && n >= kPhPackMinRows));
+}
 
 // ---- where the SSOR blocks are cut ("Block boundaries").  Modelled sweep time of a block of consecutive rows:
 //   cost = kSsorStepNs * sub-steps + stream bytes / kSsorBytesPerNs
 // sub-steps: both directions walk the stages of the block's recurrence stage(i) = 1 + max stage(j) over the coupled j in
-// [rb, i), at most kPhMaxRows rows of one stage per step -- the count ssor_sweep_plan makes for the four-wave sweep.  Stream:
+// [rb, i), at most kPhMaxRows rows of one stage per step -- the count ssor_sweep_plan makes for the four-wave sweep that walks the
+// stages, an upper bound where the rows are scheduled by slack (ssor_pack_levels: the model keeps counting stage by stage).  Stream:
 // the records scale with rows x width, kSsorRowBytes per coupled row plus kSsorEntryBytes per in-block entry of it (both
 // directions; 73 MB for the 92 164 coupled rows of the 64 k-atom level 1).  Uncoupled rows (the prepass) cost nothing.
 constexpr double kSsorStepNs = 240.0;     // one dependent step of the four-wave sweep
@@ -273,6 +283,17 @@ struct SsorBlockGraph {
   std::vector<char> coupled;
   int n_stages = 0;
 };
+// sptr / by_stage of the coupled rows crow (ascending) with stages stage[]: rows ascending inside a stage
+inline void ssor_rows_by_stage(const std::vector<int32_t> &crow, const std::vector<int32_t> &stage, int n_stages, std::vector<int32_t> &sptr, std::vector<int32_t> &by_stage) {
+  sptr.assign((size_t)n_stages + 1, 0);
+  by_stage.assign(crow.size(), 0);
+  for (int32_t i : crow) sptr[(size_t)stage[(size_t)i] + 1]++;
+  for (int t = 0; t < n_stages; ++t) sptr[(size_t)t + 1] += sptr[(size_t)t];
+  if (n_stages > 0) {
+    std::vector<int32_t> pos(sptr.begin(), sptr.end() - 1);
+    for (int32_t i : crow) by_stage[(size_t)pos[(size_t)stage[(size_t)i]]++] = i;
+  }
+}
 inline bool ssor_block_graph(int64_t rb, int64_t re, const int64_t *rp, const int32_t *col, const double *val, SsorBlockGraph &B) {
   const int m = (int)(re - rb);
   B.prp.assign((size_t)m + 1, 0); B.pcol.clear(); B.pval.clear();
@@ -308,15 +329,65 @@ inline bool ssor_block_graph(int64_t rb, int64_t re, const int64_t *rp, const in
     B.n_stages = std::max(B.n_stages, st + 1);
     B.crow.push_back(i);
   }
-  B.sptr.assign((size_t)B.n_stages + 1, 0);
-  B.by_stage.assign(B.crow.size(), 0);
-  for (int32_t i : B.crow) B.sptr[(size_t)B.stage[(size_t)i] + 1]++;
-  for (int t = 0; t < B.n_stages; ++t) B.sptr[(size_t)t + 1] += B.sptr[(size_t)t];
-  if (B.n_stages > 0) {
-    std::vector<int32_t> pos(B.sptr.begin(), B.sptr.end() - 1);
-    for (int32_t i : B.crow) B.by_stage[(size_t)pos[(size_t)B.stage[(size_t)i]]++] = i;
-  }
+  ssor_rows_by_stage(B.crow, B.stage, B.n_stages, B.sptr, B.by_stage);
   return true;
+}
+
+// ---- rows scheduled by slack ("Rows scheduled by slack") ------------------------------------------------------
+// A stage of more than kPhMaxRows rows costs the four-wave sweep several dependent steps, although many of its rows have no
+// reader in the next stage and could wait.  The packed LEVELS are a list schedule of the same graph:
+//   height(i) = 0 if row i has no higher coupled neighbour, else 1 + max height(k) over its higher neighbours;
+//   step t = 0, 1, ...: a row is ready when all its lower coupled neighbours lie in steps < t; the step takes at most
+//   kPhMaxRows ready rows, height descending, then row ascending;  level(i) = the row's step.
+// Every coupled lower neighbour lies in a lower level, so the levels stand wherever the stages stood: the forward sweep takes
+// them ascending, the backward sweep descending, and a row's value -- its CSR-ordered sum over values that are final -- does
+// not depend on the step that computes it.  Where no stage has more than kPhMaxRows rows the levels ARE the stages.  Integers
+// only, O(nnz + rows log rows), the same result on every rank.  stage_steps: the steps the stages need (kPhMaxRows rows each).
+struct SsorLevels {
+  std::vector<int32_t> level, sptr, by_level;  // as stage / sptr / by_stage of the block graph
+  int n_levels = 0;
+  int64_t stage_steps = 0;
+};
+inline void ssor_pack_levels(const SsorBlockGraph &B, SsorLevels &Lv) {
+  const size_t m = B.stage.size();
+  Lv.level.assign(m, 0);
+  Lv.n_levels = 0;
+  Lv.stage_steps = 0;
+  for (int t = 0; t < B.n_stages; ++t) Lv.stage_steps += (B.sptr[(size_t)t + 1] - B.sptr[(size_t)t] + kPhMaxRows - 1) / kPhMaxRows;
+  // higher neighbours of every row (an entry stored both ways counts twice, here and in the count of lower ones)
+  std::vector<int32_t> up_ptr(m + 1, 0), n_low(m, 0), height(m, 0);
+  for (size_t i = 0; i < m; ++i)
+    for (int32_t k = B.prp[i]; k < B.prp[i + 1]; ++k)
+      if (B.pcol[(size_t)k] != (int32_t)i) {
+        up_ptr[(size_t)std::min<int32_t>((int32_t)i, B.pcol[(size_t)k]) + 1]++;
+        n_low[(size_t)std::max<int32_t>((int32_t)i, B.pcol[(size_t)k])]++;
+      }
+  for (size_t i = 0; i < m; ++i) up_ptr[i + 1] += up_ptr[i];
+  std::vector<int32_t> up((size_t)up_ptr[m]), fill(up_ptr.begin(), up_ptr.end() - 1);
+  for (size_t i = 0; i < m; ++i)
+    for (int32_t k = B.prp[i]; k < B.prp[i + 1]; ++k)
+      if (B.pcol[(size_t)k] != (int32_t)i) up[(size_t)fill[(size_t)std::min<int32_t>((int32_t)i, B.pcol[(size_t)k])]++] = std::max<int32_t>((int32_t)i, B.pcol[(size_t)k]);
+  for (size_t i = m; i-- > 0;)
+    for (int32_t k = up_ptr[i]; k < up_ptr[i + 1]; ++k) height[i] = std::max(height[i], height[(size_t)up[(size_t)k]] + 1);
+  // the ready rows: greatest height first, then the lowest row (key = height << 32 | ~row, the largest key on top)
+  auto key = [&](int32_t i) { return (uint64_t)(uint32_t)height[(size_t)i] << 32 | (uint32_t)~(uint32_t)i; };
+  std::priority_queue<uint64_t> ready;
+  for (int32_t i : B.crow)
+    if (n_low[(size_t)i] == 0) ready.push(key(i));
+  std::vector<int32_t> taken;
+  for (int t = 0; !ready.empty(); ++t) {
+    taken.clear();
+    while (!ready.empty() && (int)taken.size() < kPhMaxRows) {
+      taken.push_back((int32_t)~(uint32_t)(ready.top() & 0xffffffffu));
+      ready.pop();
+    }
+    for (int32_t i : taken) Lv.level[(size_t)i] = t;
+    for (int32_t i : taken)  // (after the step is complete: a row freed here is ready for the next step, not for this one)
+      for (int32_t k = up_ptr[(size_t)i]; k < up_ptr[(size_t)i + 1]; ++k)
+        if (--n_low[(size_t)up[(size_t)k]] == 0) ready.push(key(up[(size_t)k]));
+    Lv.n_levels = t + 1;
+  }
+  ssor_rows_by_stage(B.crow, Lv.level, Lv.n_levels, Lv.sptr, Lv.by_level);
 }
 
 // ---- steps of one sweep direction of a block, and the y slots of a self-contained range (gmg_sgs_phase.hpp) ----------
@@ -483,6 +554,13 @@ struct SsorSweepPlan {
   std::vector<int64_t> block_steps, block_bytes;  // per block: sub-steps of both directions, bytes of the stream
   int y_slots = 0, lds_bytes = 0, n_self = 0, live_max[2] = {0, 0}, n_bwd = 0;
   int64_t total_steps = 0, total_stages = 0;
+  // the schedule (gmg_get_ssor_schedule): blocks whose rows are scheduled by slack (their levels count as total_stages), steps of
+  // the forward direction, and the steps of a direction if every block walked its stages, the plan's rows per step at a time
+  // (kPhMaxRows; one-wave plan: 64 -- there and in a ranged plan fwd_steps can hold more: a step is also cut by its records'
+  // bytes and by y_cap).  n_pack_no_slots / n_pack_no_shape: blocks that kept their stages because the packed levels did not
+  // fit the y slots / had a step without a shape.
+  int n_packed = 0, n_pack_no_slots = 0, n_pack_no_shape = 0;
+  int64_t fwd_steps = 0, stage_steps = 0;
   std::vector<int64_t> hist_g = std::vector<int64_t>(4, 0), hist_l1 = std::vector<int64_t>(8, 0), hist_l2 = std::vector<int64_t>(4, 0);  // shapes of the steps
   double laps[4] = {0, 0, 0, 0};  // where the host spends the plan's time (seconds): block graph, steps + slots, shapes, record fill
   int n_ranges() const { return (int)(phased ? pranges.size() : ranges.size()); }
@@ -525,7 +603,7 @@ inline SsorShape ssor_choose_shape(const SsorPlanOptions &opt, bool dep, bool re
 struct SsorSweepBuilder {
   const SsorPlanOptions &opt;
   SsorSweepPlan &P;
-  bool ph = false, dep = false, reg = false, fieldmajor = false, slide_ok = false;
+  bool ph = false, dep = false, reg = false, fieldmajor = false, slide_ok = false, pack = false;
   int late_steps = 1, y_max = 0, y_cap = 0, max_ws = 0;
   std::chrono::steady_clock::time_point lap_t = std::chrono::steady_clock::now();
   // the block in work: rows [rb, rb + m) and their graph.  *_stamp[i] == the id of a range: row i is in its working set / has a
@@ -850,6 +928,59 @@ struct SsorSweepBuilder {
     P.rpos_f.resize(P.ci_row.size(), 0);
     P.rpos_b.resize(P.ci_row.size(), 0);
     if (B.crow.empty()) return true;
+    const int step_rows = ph ? kPhMaxRows : 64;  // (the plan's own rows per step, so that the two counts of the schedule compare)
+    for (int t = 0; t < B.n_stages; ++t) P.stage_steps += (B.sptr[(size_t)t + 1] - B.sptr[(size_t)t] + step_rows - 1) / step_rows;
+    // self-contained ranges: both directions of the block must fit; else the ranged plan, unchanged.  The records are built from
+    // the very lists of steps the slots were handed out for.
+    SsorSlotPlan slide[2];
+    std::vector<int32_t> slide_seq[2];
+    std::vector<SsorStep> slide_steps[2];
+    auto self_contained = [&]() {  // steps and slots of both directions as one range each; do they fit?
+      bool fits = true;
+      for (int d = 0; d < 2; ++d) {
+        ssor_build_steps(d, B.n_stages, B.sptr, B.by_stage, B.prp, B.pcol, kPhMaxRows, true, 0, y_max, slide_seq[d], slide_steps[d]);
+        ssor_slot_alloc(m, B.prp, B.pcol, d, slide_seq[d], slide_steps[d], slide[d]);
+        if (((slide[d].n_slots + 1) & ~1) > y_cap) fits = false;
+      }
+      return fits;
+    };
+    // every step of both directions has a shape, chunk by chunk: the row cuts and shapes exactly as phase_range forms them for a
+    // self-contained range (a whole level in the step before its readers can put more than 28 columns between a row's first and
+    // last late column, which no shape holds)
+    auto shapes_exist = [&]() {
+      bool ok = true;
+      for (int d = 0; d < 2 && ok; ++d) {
+        dir = d;
+        seq.swap(slide_seq[d]); steps.swap(slide_steps[d]);
+        ++stamp_id;
+        for_rows(0, steps.size(), [&](int32_t st, int i) { step_of[(size_t)i] = st; upd_stamp[(size_t)i] = stamp_id; });
+        std::vector<SsorShape> shape_of;
+        ok = choose_shapes(0, steps.size(), row_cuts(0, steps.size()), shape_of);
+        seq.swap(slide_seq[d]); steps.swap(slide_steps[d]);
+      }
+      dir = 0;
+      return ok;
+    };
+    // Rows scheduled by slack: the packed levels stand in for the stages if both directions still fit the y slots (the backward
+    // sweep takes the same levels in reverse, which keeps its rows near their readers) and every packed step has a shape; else
+    // the stages, exactly as without them.
+    bool sliding = false, slots_known = false;
+    if (pack) {
+      SsorLevels Lv;
+      ssor_pack_levels(B, Lv);
+      auto exchange = [&]() { B.stage.swap(Lv.level); B.sptr.swap(Lv.sptr); B.by_stage.swap(Lv.by_level); std::swap(B.n_stages, Lv.n_levels); };
+      exchange();
+      for (std::vector<int32_t> *v : {&upd_stamp, &step_of}) v->assign((size_t)m, -1);
+      stamp_id = 0;
+      const bool fits = self_contained();
+      sliding = slots_known = fits && shapes_exist();
+      if (sliding) ++P.n_packed;
+      else { exchange(); ++(fits ? P.n_pack_no_shape : P.n_pack_no_slots); }
+    }
+    if (slide_ok && !slots_known) sliding = self_contained();
+    if (slide_ok)
+      for (int d = 0; d < 2; ++d) P.live_max[d] = std::max(P.live_max[d], slide[d].n_slots);
+    lap(1);
     P.total_stages += B.n_stages;
     // The compact copy ycur is numbered in SWEEP order (stage by stage): the rows a forward range updates are one contiguous
     // piece of it, those of a backward range a run of stage-long pieces -- the working-set loads and write-backs at the range
@@ -862,25 +993,13 @@ struct SsorSweepBuilder {
     slot_of.assign((size_t)m, 0); prefix_pos.assign((size_t)m, 0);
     stamp_id = tmp_id = 0;
     for (int d = 0; d < 2; ++d) { dir_ranges[d].clear(); dir_pranges[d].clear(); }
-    // self-contained ranges: both directions of the block must fit; else the ranged plan, unchanged.  The records are built from
-    // the very lists of steps the slots were handed out for.
-    SsorSlotPlan slide[2];
-    std::vector<int32_t> slide_seq[2];
-    std::vector<SsorStep> slide_steps[2];
-    bool sliding = slide_ok;
-    for (int d = 0; d < 2 && slide_ok; ++d) {
-      ssor_build_steps(d, B.n_stages, B.sptr, B.by_stage, B.prp, B.pcol, kPhMaxRows, true, 0, y_max, slide_seq[d], slide_steps[d]);
-      ssor_slot_alloc(m, B.prp, B.pcol, d, slide_seq[d], slide_steps[d], slide[d]);
-      P.live_max[d] = std::max(P.live_max[d], slide[d].n_slots);
-      if (((slide[d].n_slots + 1) & ~1) > y_cap) sliding = false;
-    }
-    lap(1);
     for (dir = 1; dir >= 0; --dir) {
       const int g_dir = choose_groups();
       // steps: <= 64 rows of one stage, records of a sub-step <= kSwMaxBlock bytes, working set <= y_cap (self-contained: the
       // allocator's own lists -- the LDS bound is the allocator's, not the step's)
       if (sliding) { seq.swap(slide_seq[dir]); steps.swap(slide_steps[dir]); }
       else ssor_build_steps(dir, B.n_stages, B.sptr, B.by_stage, B.prp, B.pcol, ph ? kPhMaxRows : 64, ph, ph ? ph_stride(3, 12) : sw_stride(g_dir), y_cap, seq, steps);
+      if (dir == 0) P.fwd_steps += (int64_t)steps.size();
       for (size_t s0 = 0, s1 = 0; s0 < steps.size(); s0 = s1) {
         ++stamp_id;
         SwRange R{};
@@ -921,6 +1040,7 @@ inline void ssor_sweep_plan(const SsorPlanOptions &opt, int64_t n, const int64_t
   S.fieldmajor = S.dep || S.reg;
   // one self-contained range per direction (gmg_sgs_phase.hpp) where a block's live rows fit: the default four-wave sweep only
   S.slide_ok = ph && !S.dep && !S.reg && !opt.chain && opt.sliding;
+  S.pack = S.slide_ok && ssor_pack_wanted(opt, n);  // rows scheduled by slack: this plan only, the others keep the stages
   S.late_steps = S.dep ? kDpLate : 1;
   S.y_max = S.dep ? kDpYSlots : S.reg ? kRgYSlots : ph ? kPhYSlots : kSwYSlots;
   S.y_cap = std::max(64, std::min(opt.y_slots > 0 ? opt.y_slots : S.y_max, S.y_max)) & ~1;

@@ -893,7 +893,7 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * cg_variant, coarse_chunk, coarse_direct (0 / 1, see gmg_set_coarse_solver), coarse_direct_max_blocks (cap on the grids of the direct
  * coarse solver's passes, 0 = by size; the results do not depend on it), sgs_y_slots (doubles of LDS the SSOR sweep may use for y: small values force
  * several LDS ranges), sgs_sliding (default 1: the four-wave sweep takes a whole sweep direction of a block as one self-contained LDS range, y slots
- * recycled, wherever the block's live rows fit; 0: always the ranged plan; same bits either way, see gmg_get_ssor_plan), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
+ * recycled, wherever the block's live rows fit; 0: always the ranged plan; same bits either way, see gmg_get_ssor_plan), sgs_pack (rows scheduled by slack, see gmg_ssor_pack_levels), sgs_disable_wave (SSOR through the generic CSR sweep), sgs_disable_phase (the one-wave sweep),
  * sgs_phase_profile (cycle counters of the four-wave sweep: same results, one rank only), sgs_profile (instrumented
  * one-wave sweep; its wrong-result timing modes exist only in a -DGMG_EXPERIMENTS build, tools/build_experiments.sh),
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
@@ -972,7 +972,7 @@ int gmg_get_ssor_backward_rows(gmg_context *ctx, int level, int64_t *count, int3
  *   gmg_get_ssor_plan_origin: who built the level's plan (*on_device 1 / 0), how many bytes of col / val came back to the host
  *     for it (0 for a device-built plan from gmg_assemble_level_matrix*, and for gmg_set_level_matrix, whose caller holds
  *     them), and, where the option was set and the host built it anyway, why -- one fixed text per cause: "communicator",
- *     "balanced partition", "option <key> set" ("option sgs_sliding unset"), "unsorted columns", "row too wide", "no shape",
+ *     "balanced partition", "option <key> set" ("option sgs_sliding unset"), "packed schedule", "unsorted columns", "row too wide", "no shape",
  *     "block does not fit", "stream positions beyond 2^31", "empty level"; "" otherwise.  Any pointer may be NULL; the text
  *     is static.                                                                                                          */
 #define GMG_SSOR_PLAN_STREAM 0
@@ -996,6 +996,31 @@ int gmg_get_ssor_plan_origin(gmg_context *ctx, int level, int *on_device, int64_
  * most ever live (the lowest free slot is always taken).                                                                  */
 int gmg_ssor_slot_plan(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end,
                        int backward, int32_t *step, int32_t *last_reader, int32_t *slot, int64_t *n_steps, int64_t *n_slots);
+/* Rows scheduled by slack (option sgs_pack).  The stages of a block are walked at most 32 rows at a time, so a
+ * stage of 40 rows costs two dependent steps although many of its rows have no reader in the next stage.  The packed levels
+ * are a list schedule of the same dependency graph: height(i) = 0 for a row without a higher coupled neighbour, else 1 + the
+ * greatest height of its higher neighbours; step t takes at most 32 of the rows whose lower coupled neighbours all lie in
+ * steps < t, height descending, then row ascending; level(i) = the row's step.  The forward sweep takes the levels
+ * ascending, the backward sweep descending; the results are the same bits as with the stages.
+ *   gmg_ssor_pack_levels: the levels of ONE block [row_begin, row_end) of a level matrix (host CSR, ascending columns,
+ *     values required), without a context or a device: the routine the plan uses.  level: row_end - row_begin entries, -1
+ *     for a row without couplings inside the block (may be NULL); n_levels; n_stage_steps: the steps of a direction when
+ *     the stages are walked 32 rows at a time (gmg_ssor_slot_plan's n_steps).
+ *   gmg_ssor_slot_plan_packed: gmg_ssor_slot_plan over the packed levels.
+ *   gmg_get_ssor_schedule: out = [0] 1 if a block of the level's plan is packed, [1] stages or levels, [2] steps of a sweep
+ *     direction (the forward one), [3] the steps the stages need when walked with the plan's rows per step (32; one-wave
+ *     plan: 64); [1] .. [3] summed over the blocks.  [2] and [3] compare for the four-wave plan with self-contained ranges,
+ *     where [2] < [3] is what packing saved; a ranged or a one-wave plan cuts a step also by the y slots and by the bytes of
+ *     its records, so its [2] may exceed [3].  All 0 for a level on the generic CSR sweep.
+ * Option sgs_pack: 0 never, 1 always, unset (or < 0) for levels of at least 8192 rows.  Only the four-wave plan with
+ * self-contained ranges packs, and only a block whose packed directions both fit the y slots and whose packed steps all have
+ * a record shape; such a block otherwise, and every other plan, keeps the stages, exactly as with sgs_pack = 0.  With option
+ * ssor_plan_device a level that would be tried is planned by the host ("packed schedule"), whatever the trial gives.      */
+int gmg_ssor_pack_levels(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end,
+                         int32_t *level, int64_t *n_levels, int64_t *n_stage_steps);
+int gmg_ssor_slot_plan_packed(int64_t n, const int64_t *rowptr, const int32_t *col, const double *val, int64_t row_begin, int64_t row_end,
+                              int backward, int32_t *step, int32_t *last_reader, int32_t *slot, int64_t *n_steps, int64_t *n_slots);
+int gmg_get_ssor_schedule(gmg_context *ctx, int level, int64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,10 @@ for level in range(1, len(h.level_matrices)):
         step[i] = t; cnt += 1
     n_steps = t + 1
     print(f"  forward: {stage.max() + 1} stages, {n_steps} steps")
+    # rows scheduled by slack: the library's own levels, against the stages walked 32 rows at a time
+    lv, n_levels, stage_steps = pkg.capi.ssor_pack_levels(A, 0, n)
+    per_level = np.bincount(lv[lv >= 0])
+    print(f"  packed:  {n_levels} levels against {stage_steps} steps of <= 32 rows by stages; rows per level: mean {per_level.mean():.1f}, full levels {(per_level == 32).mean():.3f}")
     # entries of the forward sweep: stored nonzero columns j < i (CSR order)
     heads, tails, lens = [], [], []
     for i in order:
