@@ -3,6 +3,8 @@
 // planned from, entry for entry in stored order, values compared as bit patterns.  Explicit +0.0 entries carry no
 // information in a product (x is finite) and are what the layouts pad with: they are dropped on both sides where a layout
 // may have inserted them.  Every case also asserts the layout it was written for: a fall-back to CSR is a failure.
+// Cases: the SELL variants, the other SELL cases, the hybrid layout, operators cut into the row chunks of 2 - 4 ranks, invalid
+// input, host threads, and -- limit_cases() -- a pair of operators on either side of every integer limit of the planner.
 // Driven by tests/test_operator_layout_cpu.py; exit status 0 = every requirement held.
 #include "gmg_layout.hpp"
 
@@ -543,6 +545,328 @@ void threading() {
   REQUIRE(plan_bytes(one) == plan_bytes(seven));
 }
 
+// ---------------------------------------------------------------- operators on the planner's limits
+// The generators of tests/layout_limit_cases.py, restated (no random numbers on either side), and for every limit one operator
+// on either side of it with the flags it must get.  The limits appear here as plain numbers: a planner
+// whose limit moves by one fails the pair of that limit.
+
+// A[i, i + d] = A[i + d, i] = upper(i, d), d = 1 .. 13; the rows of the empty slices store nothing and no row refers to them
+template <class U, class D>
+Csr symmetric_band(int64_t n, U upper, D diag, const std::vector<int64_t> &empty_slices = {}) {
+  auto empty = [&](int64_t r) { return std::find(empty_slices.begin(), empty_slices.end(), r / 64) != empty_slices.end(); };
+  Csr m;
+  m.n_cols = n;
+  for (int64_t i = 0; i < n; ++i) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    for (int d = -13; d <= 13 && !empty(i); ++d) {
+      const int64_t j = i + d;
+      if (j < 0 || j >= n || empty(j)) continue;
+      c.push_back((int32_t)j);
+      v.push_back(d < 0 ? upper(j, -d) : d == 0 ? diag(i) : upper(i, d));
+    }
+    m.add_row(c, v);
+  }
+  return m;
+}
+
+Csr dictionary_operator(int n_nonzero, int64_t n = 5037) {
+  std::vector<double> pool = {-0.0, 5e-324};
+  for (int k = 1; k < 128; ++k) { pool.push_back(k / 128.0); pool.push_back(-k / 128.0); }
+  const int64_t len = n_nonzero - 2;
+  return symmetric_band(n, [&](int64_t i, int d) { return (d == 1 && (i == 40 * 64 + 10 || i == 5000)) ? 255.0 / 256.0 : pool[(size_t)((13 * i + d - 1) % len)]; },
+                        [](int64_t) { return 64.0; });
+}
+
+Csr class_operator(int K, int64_t n, const std::vector<int64_t> &empty_slices = {}) {
+  auto g = [K](int64_t i, int d) {
+    const int64_t c = i % K;
+    if (d == 13) return -(double)(c + 1) / 256.0;
+    const int64_t t = (c * (2 * d + 1) + (c / 16) * d) % 16;
+    return (t % 2 ? -1.0 : 1.0) * (double)(t / 2 + 1) / 64.0;
+  };
+  return symmetric_band(n, g, [K](int64_t i) { return 64.0 + (double)((i % K) % 3); }, empty_slices);
+}
+
+const double kFiveNonzero[5] = {-1.0 / 6, -1.0 / 12, 8.0 / 3, 0.5, 1.25};
+
+Csr spread_operator(int64_t dmax, bool few, int64_t n = 5037, const std::vector<int64_t> &empty_slices = {}) {
+  Csr m;
+  m.n_cols = n + dmax;
+  for (int64_t i = 0; i < n; ++i) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    const int64_t lane = i % 64;
+    const bool empty = std::find(empty_slices.begin(), empty_slices.end(), i / 64) != empty_slices.end();
+    for (int64_t k = 0; k < 11 && !empty; ++k) {
+      int64_t off = k * 6000 + 3 * (lane % 7);
+      if (k == 0) off = lane == 0 ? 0 : lane % 7 + 1;
+      if (k == 10) off = lane == 63 ? dmax : dmax - 1 - lane % 7;
+      const int64_t e = 11 * i + k;
+      c.push_back((int32_t)(i + off));
+      v.push_back(few ? kFiveNonzero[(e * 7 + e / 5) % 5] : 1.0 + (double)e / 65536.0);
+    }
+    m.add_row(c, v);
+  }
+  return m;
+}
+
+Csr padding_operator(int64_t slices, int64_t wide_rows = 0) {
+  Csr m;
+  const int64_t n = 64 * slices;
+  m.n_cols = n + 3 * 29;
+  for (int64_t i = 0; i < n; ++i) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    for (int64_t k = 0; k < ((i >= 64 && i < 64 + wide_rows) ? 29 : 25); ++k) {
+      const int64_t e = 29 * i + k;
+      c.push_back((int32_t)(i + 3 * k));
+      v.push_back(kFiveNonzero[(e * 3 + e / 5) % 5]);
+    }
+    m.add_row(c, v);
+  }
+  return m;
+}
+
+Csr few_valued_band(int64_t n) {
+  Csr m;
+  m.n_cols = n;
+  for (int64_t i = 0; i < n; ++i) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    for (int64_t k = 0; k < 27; ++k) {
+      const int64_t j = i + k - 13, e = 27 * i + k;
+      if (j < 0 || j >= n) continue;
+      c.push_back((int32_t)j);
+      v.push_back(k == 13 ? 64.0 : kFiveNonzero[(e * 3 + e / 5) % 5]);
+    }
+    m.add_row(c, v);
+  }
+  return m;
+}
+
+std::vector<int64_t> window_rows(int64_t first_len, int64_t last_len, int last_align) {
+  std::vector<int64_t> lens = {first_len, 2};
+  int64_t nnz = first_len + 2;
+  auto align = [&](int a) {
+    const int64_t pad = (((int64_t)a - nnz) % 4 + 4) % 4;
+    if (pad) { lens.push_back(pad); nnz += pad; }
+  };
+  const std::vector<std::vector<int64_t>> follows = {{5}, {1, 0, 2}};
+  for (const auto &follow : follows)
+    for (int64_t L = 4092; L <= 4097; ++L)
+      for (int a = 0; a < 4; ++a) {
+        align(a);
+        lens.push_back(L); nnz += L;
+        for (int64_t f : follow) { lens.push_back(f); nnz += f; }
+      }
+  for (int64_t run : {1023, 1024, 1025}) {
+    lens.insert(lens.end(), (size_t)run, 0);
+    lens.push_back(3); nnz += 3;
+  }
+  align(last_align);
+  lens.push_back(last_len);
+  return lens;
+}
+
+Csr window_operator(int64_t first_len, int64_t last_len, int last_align) {
+  Csr m;
+  m.n_cols = 6000;
+  int64_t k = 0, r = 0;
+  for (int64_t len : window_rows(first_len, last_len, last_align)) {
+    std::vector<int32_t> c;
+    std::vector<double> v;
+    for (int64_t j = 0; j < len; ++j, ++k) {
+      c.push_back((int32_t)((17 * r) % 1200 + j + j / 7));
+      v.push_back((k % 2 == 0 ? 1.0 : -1.0) * (0.5 + (double)(k % 8191) / 8192.0));
+    }
+    m.add_row(c, v);
+    ++r;
+  }
+  return m;
+}
+
+// the tile boundaries the planner must give, with the limits as plain numbers
+std::vector<int32_t> window_tiles_restated(const std::vector<int64_t> &rp) {
+  const int64_t n = (int64_t)rp.size() - 1;
+  std::vector<int32_t> tiles(1, 0);
+  for (int64_t r = 0; r < n;) {
+    const int64_t ka = rp[(size_t)r] & ~(int64_t)3;
+    int64_t e = r + 1;
+    while (e < n && rp[(size_t)e + 1] - ka <= 4096 && e - r < 1024) ++e;
+    if (rp[(size_t)e] - ka > 4096) e = r + 1;
+    tiles.push_back((int32_t)e);
+    r = e;
+  }
+  return tiles;
+}
+
+struct LimitWant { bool sell, val8, col16, sellp, rowclass, lat; int sellp_classes, lat_classes; };  // lat_classes < 0: the count at which the planner gave up
+
+StreamPlan limit_case(const char *name, const Csr &m, LayoutOptions opt, const LimitWant &w) {
+  g_case = std::string("limit ") + name;
+  opt.sellp_cost = opt.sellp_cost > 0.0 ? opt.sellp_cost : 4.0;
+  const StreamPlan P = plan_and_check(m, opt);
+  int fullest = 0;
+  for (size_t wv = 0; wv + 1 < P.sellp.wave_ptr.size(); ++wv)
+    fullest = std::max(fullest, (P.sellp.wave_ptr[wv + 1] & (kSellpStrided - 1)) - (P.sellp.wave_ptr[wv] & (kSellpStrided - 1)));
+  std::printf("%s: sell %d val8 %d (%zu values) col16 %d pattern-run %d rowclass %d (%d classes) lattice %d (%d classes); %lld rows, %d pattern slices, %lld of %lld padded entries, fullest wave %d slices\n",
+              g_case.c_str(), (int)P.sell.built, (int)P.sell.s.val8, P.sell.vd.n_values, (int)P.sell.s.col16, (int)P.sell.use_sellp, (int)P.sellp.rowclass, P.sellp.n_classes,
+              (int)P.lat.built, P.lat.classes, (long long)m.n_rows, P.sell.pat.n_pattern_slices, (long long)(P.sell.quads * 256), (long long)m.rp.back(), fullest);
+  REQUIRE(P.sell.built == w.sell && !P.hyb.built);
+  if (!P.sell.built) return P;
+  REQUIRE(P.sell.s.val8 == w.val8 && P.sell.s.col16 == w.col16 && P.sell.use_sellp == w.sellp && P.sellp.rowclass == w.rowclass && P.lat.built == w.lat);
+  REQUIRE(P.sellp.n_classes == w.sellp_classes && P.lat.classes == w.lat_classes);
+  return P;
+}
+
+LayoutOptions with(std::initializer_list<const char *> keys, int sell_grid = 0, double sellp_cost = 0.0) {
+  LayoutOptions o;
+  for (const char *k : keys) {
+    const std::string s = k;
+    if (s == "disable_sellp") o.disable_sellp = true;
+    else if (s == "disable_rowclass") o.disable_rowclass = true;
+    else if (s == "disable_lattice") o.disable_lattice = true;
+    else REQUIRE(!"known option");
+  }
+  o.sell_grid = sell_grid; o.sellp_cost = sellp_cost;
+  return o;
+}
+
+void limit_cases() {
+  const std::vector<int64_t> empty_slices = {0, 20, 38, 39, 77};
+  // ---- 1. value dictionary: 255 nonzero bit patterns + the padding zero = 256 codes | 257 values
+  {
+    const Csr at = dictionary_operator(255), beyond = dictionary_operator(256);
+    StreamPlan P = limit_case("values-255", at, with({}), {true, true, true, true, false, false, 0, -129});
+    REQUIRE(P.sell.vd.n_values == 256);
+    // code 255 belongs to the value placed by hand, in slice 40 and in the last, partial slice: read back from the packed codes
+    if (P.sell.vd.val8) {
+      const uint8_t last = P.sell.vd.lookup(255.0 / 256.0);
+      REQUIRE(last == 255 && P.sell.vd.lookup(-0.0) != 0 && P.sell.vd.lookup(5e-324) != 0 && P.sell.vd.lookup(-0.0) != P.sell.vd.lookup(5e-324));
+      for (int64_t sl : {(int64_t)40, (int64_t)78}) {
+        bool found = false;
+        for (size_t o = (size_t)P.sell.slice_ptr[(size_t)sl] * 256; o < (size_t)P.sell.slice_ptr[(size_t)sl + 1] * 256; ++o) found = found || P.sell.s.v1[o] == 255;
+        REQUIRE(found);
+      }
+    }
+    limit_case("values-255-per-entry-kernel", at, with({"disable_sellp"}), {true, true, true, false, false, false, 0, -129});
+    limit_case("values-255-grid8", at, with({"disable_sellp"}, 8), {true, true, true, false, false, false, 0, -129});
+    P = limit_case("values-256", beyond, with({}), {true, false, true, false, false, false, 0, 0});
+    REQUIRE(P.sell.vd.n_values > 256 || !P.sell.vd.val8);
+    limit_case("values-256-grid8", beyond, with({}, 8), {true, false, true, false, false, false, 0, 0});
+  }
+  // ---- 2. slice span 65535 | 65536 columns, no column patterns
+  for (int grid : {0, 8})
+    for (int few = 1; few >= 0; --few) {
+      const std::string tail = std::string(few ? "-codes" : "-doubles") + (grid ? "-grid8" : "");
+      const Csr at = spread_operator(65472, few), beyond = spread_operator(65473, few);
+      StreamPlan P = limit_case(("span-65535" + tail).c_str(), at, with({}, grid), {true, (bool)few, true, false, false, false, 0, 0});
+      int64_t span = 0;
+      for (int64_t k = at.rp[0]; k < at.rp[64]; ++k) span = std::max<int64_t>(span, at.col[(size_t)k] - P.sell.slice_base[0]);
+      REQUIRE(span == 65535 && P.sell.pat.n_pattern_slices == 0);
+      if (P.sell.s.col16) REQUIRE(*std::max_element(P.sell.s.c2.begin(), P.sell.s.c2.end()) == 65535);
+      P = limit_case(("span-65536" + tail).c_str(), beyond, with({}, grid), {true, (bool)few, false, false, false, false, 0, 0});
+      REQUIRE(P.sell.pat.n_pattern_slices == 0);
+    }
+  // ---- 3. row classes: 96 | 97 for the pattern-run kernel, 128 | 129 for the lattice kernel
+  {
+    const int64_t n = 20037;
+    limit_case("classes-96", class_operator(96, n), with({}), {true, true, true, true, true, true, 96, 96});
+    limit_case("classes-96-no-lattice", class_operator(96, n), with({"disable_lattice"}), {true, true, true, true, true, false, 96, 0});
+    limit_case("classes-97", class_operator(97, n), with({}), {true, true, true, true, false, true, 0, 97});
+    limit_case("classes-97-no-lattice", class_operator(97, n), with({"disable_lattice"}), {true, true, true, true, false, false, 0, 0});
+    limit_case("classes-128", class_operator(128, n), with({}), {true, true, true, true, false, true, 0, 128});
+    limit_case("classes-129", class_operator(129, n), with({}), {true, true, true, true, false, false, 0, -129});
+  }
+  // ---- 4. slices per wave: sell_grid 8 = 32 waves; 64 | 65 slices in the fullest
+  {
+    const Csr keeps = class_operator(7, 2043 * 64), withdrawn = class_operator(7, 2044 * 64);
+    auto fullest = [](const StreamPlan &P) {
+      int f = 0;
+      for (size_t wv = 0; wv + 1 < P.sellp.wave_ptr.size(); ++wv)
+        f = std::max(f, (P.sellp.wave_ptr[wv + 1] & (kSellpStrided - 1)) - (P.sellp.wave_ptr[wv] & (kSellpStrided - 1)));
+      return f;
+    };
+    StreamPlan P = limit_case("wave-64-slices", keeps, with({"disable_lattice"}, 8), {true, true, true, true, true, false, 7, 0});
+    REQUIRE(P.sellp.wave_ptr.size() == 33 && fullest(P) == 64);
+    P = limit_case("wave-64-slices-codes", keeps, with({"disable_lattice", "disable_rowclass"}, 8), {true, true, true, true, false, false, 0, 0});
+    REQUIRE(P.sellp.wave_ptr.size() == 33 && fullest(P) == 64);
+    for (size_t wv = 0; wv + 1 < P.sellp.wave_ptr.size(); ++wv) REQUIRE(!(P.sellp.wave_ptr[wv] & kSellpFastWave));  // every wave needs its metadata lanes
+    P = limit_case("wave-65-slices", withdrawn, with({"disable_lattice"}, 8), {true, true, true, false, false, false, 0, 0});
+    REQUIRE(P.sellp.wave_ptr.empty() && P.sell.sellp_pid >= 0);
+  }
+  // ---- 5. slices without quads: first, where an XCD's eighth begins, two neighbours, the last full slice
+  {
+    const Csr pat = class_operator(7, 5037, empty_slices);
+    auto no_quads = [&](const StreamPlan &P) {
+      bool ok = P.sell.n_slices == 79;
+      for (int64_t sl : empty_slices) ok = ok && P.sell.slice_ptr[(size_t)sl + 1] == P.sell.slice_ptr[(size_t)sl] && P.sell.pat.spat[(size_t)sl] < 0;
+      return ok;
+    };
+    REQUIRE(20 == 2 * ((79 + 7) / 8));  // slice 20 is the first of XCD 2's eighth
+    StreamPlan P = limit_case("empty-slices-lattice", pat, with({}), {true, true, true, true, true, true, 85, 86});
+    REQUIRE(no_quads(P));
+    limit_case("empty-slices-rowclass", pat, with({"disable_lattice"}), {true, true, true, true, true, false, 85, 0});
+    limit_case("empty-slices-codes", pat, with({"disable_lattice", "disable_rowclass"}), {true, true, true, true, false, false, 0, 0});
+    limit_case("empty-slices-per-entry-kernel", pat, with({"disable_lattice", "disable_sellp"}), {true, true, true, false, false, false, 0, 0});
+    const StreamPlan c4 = limit_case("empty-slices-rowclass-grid8", pat, with({"disable_lattice"}, 8), {true, true, true, true, true, false, 85, 0});
+    const StreamPlan c1 = limit_case("empty-slices-rowclass-grid8-cost1", pat, with({"disable_lattice"}, 8, 1.0), {true, true, true, true, true, false, 85, 0});
+    const StreamPlan c16 = limit_case("empty-slices-codes-grid8-cost16", pat, with({"disable_lattice", "disable_rowclass"}, 8, 16.0), {true, true, true, true, false, false, 0, 0});
+    auto bounds = [](const StreamPlan &Q) { std::vector<int32_t> b; for (int32_t e : Q.sellp.wave_ptr) b.push_back(e & (kSellpStrided - 1)); return b; };
+    REQUIRE(bounds(c4) != bounds(c1) && bounds(c4) != bounds(c16) && bounds(c1) != bounds(c16));  // other wave boundaries
+    limit_case("empty-slices-per-entry-kernel-grid8", pat, with({"disable_lattice", "disable_sellp"}, 8), {true, true, true, false, false, false, 0, 0});
+    for (int grid : {0, 8}) {
+      P = limit_case(grid ? "empty-slices-streamed-codes-grid8" : "empty-slices-streamed-codes", spread_operator(65472, true, 5037, empty_slices), with({}, grid),
+                     {true, true, true, false, false, false, 0, 0});
+      REQUIRE(no_quads(P) && P.sell.pat.n_pattern_slices == 0);
+      P = limit_case(grid ? "empty-slices-streamed-doubles-grid8" : "empty-slices-streamed-doubles", spread_operator(65473, false, 5037, empty_slices), with({}, grid),
+                     {true, false, false, false, false, false, 0, 0});
+      REQUIRE(no_quads(P) && P.sell.pat.n_pattern_slices == 0);
+    }
+  }
+  // ---- 6. the row window: 4096 entries from the row's start rounded down to 4, at most 1024 rows in a tile
+  for (int64_t L = 4092; L <= 4097; ++L)
+    for (int a = 0; a < 4; ++a) {
+      g_case = "limit window: first and last row of " + std::to_string(L) + " entries, the last starting at " + std::to_string(a) + " mod 4";
+      const Csr m = window_operator(L, L, a);
+      const StreamPlan P = plan_and_check(m, with({}, 0, 4.0));
+      REQUIRE(!P.sell.built && !P.hyb.built);
+      const TilePlan T = plan_tiles(m.rp.data(), m.n_rows);
+      REQUIRE(T.tile_row == window_tiles_restated(m.rp));
+      REQUIRE(m.rp[(size_t)m.n_rows - 1] % 4 == a && m.rp[(size_t)m.n_rows] - m.rp[(size_t)m.n_rows - 1] == L);
+      if (L != 4092 || a != 0) continue;
+      // what the tiles of this operator must show: rows that end exactly at the window's edge, rows one entry beyond it, and
+      // tiles of exactly 1024 rows
+      int exact = 0, beyond = 0, capped = 0, shared = 0;
+      for (size_t t = 0; t + 1 < T.tile_row.size(); ++t) {
+        const int32_t b = T.tile_row[t], e = T.tile_row[t + 1];
+        const int64_t used = m.rp[(size_t)e] - (m.rp[(size_t)b] & ~(int64_t)3);
+        exact += used == 4096;
+        beyond += used == 4097 && e - b == 1;
+        capped += e - b == 1024;
+        shared += e - b > 1 && m.rp[(size_t)b + 1] - m.rp[(size_t)b] >= 4092;
+      }
+      std::printf("%s: %d tiles, %d filled to the last entry, %d long rows one entry beyond, %d of 1024 rows, %d with a row of >= 4092 entries and others\n", g_case.c_str(),
+                  T.n_tiles, exact, beyond, capped, shared);
+      REQUIRE(exact >= 4 && beyond >= 4 && capped >= 3 && shared >= 4);
+    }
+  // ---- 7. entry conditions: 1024 | 1023 rows; padded entries = floor(1.12 nnz) | one quad more
+  {
+    limit_case("rows-1024", few_valued_band(1024), with({"disable_lattice"}), {true, true, true, true, true, false, 25, 0});
+    limit_case("rows-1023", few_valued_band(1023), with({"disable_lattice"}), {false, false, false, false, false, false, 0, 0});
+    const Csr at = padding_operator(20), beyond = padding_operator(20, 2);
+    const StreamPlan P = limit_case("padding-at-the-bound", at, with({}), {true, true, true, false, false, false, 0, 0});
+    REQUIRE(P.sell.quads * 256 == (int64_t)std::floor(1.12 * (double)at.rp.back()) && P.sell.quads == 20 * 7);
+    limit_case("padding-one-quad-beyond", beyond, with({}), {false, false, false, false, false, false, 0, 0});
+    // the operator beyond the bound is one quad wider and would pass again with the bound at 1.13
+    PhaseLog quiet;
+    SellPlan s;
+    const CsrView B = beyond.view();
+    REQUIRE(!plan_sell(B, analyse_slices(B, true), LayoutOptions(), quiet, s) && s.quads == 20 * 7 + 1 && beyond.rp.back() == at.rp.back() + 8);
+  }
+}
+
 }  // namespace
 
 int main() {
@@ -552,6 +876,7 @@ int main() {
   localized_operators();
   invalid_input();
   threading();
+  limit_cases();
   if (g_failures) std::fprintf(stderr, "%d requirement(s) failed\n", g_failures);
   else std::printf("layout round trip: all cases passed\n");
   return g_failures ? 1 : 0;

@@ -4,7 +4,10 @@ the hybrid SELL/CSR streams --, decodes every plan back to (row, column, value) 
 requires the CSR it started from, entry for entry and bit for bit.  It also requires that every case reaches the layout it
 was written for -- among them every rank's rows of operators cut into the row chunks of 2, 3 and 4 ranks, ghost columns
 renumbered behind the owned ones --, that tiles and wave pointers cover rows and slices exactly once, that the lattice window's reads stay inside
-the vectors, that invalid input is reported, and that the plans do not depend on the number of host threads."""
+the vectors, that invalid input is reported, and that the plans do not depend on the number of host threads.  For every integer
+limit of the planner (256 dictionary values, a slice span of 65535 columns, 96 and 128 row classes, 64 slices in a wave, the
+4096-entry row window and its 1024-row cap, 1024 rows, the 12 % padding bound) a pair of operators, one on either side, must
+get the flags of its side: the generators of tests/layout_limit_cases.py restated."""
 import os
 import subprocess
 
