@@ -50,7 +50,8 @@ def build_host(force=False, verbose=False):
         return None
     srcs = _sources(HOST, (".cc", ".h", ".inc")) + [os.path.join(HERE, "..", "include", "gmg_coulomb.h"),
                                                     os.path.join(CSRC, "gmg_forces.hpp"),  # (the host mirror of the force kernels
-                                                    os.path.join(CSRC, "gmg_exact.hpp")]   # and of the exact-potential kernels)
+                                                    os.path.join(CSRC, "gmg_exact.hpp"),   # of the exact-potential kernels
+                                                    os.path.join(CSRC, "gmg_output.hpp")]  # and of the output's patch kernel)
     lib_srcs = [s for s in _sources(HOST, (".cc",)) if not s.endswith("main.cc")]
     if force or _newer(LIB_HOST, srcs):
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-fopenmp",

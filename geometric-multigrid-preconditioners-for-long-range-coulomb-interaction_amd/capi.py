@@ -39,6 +39,7 @@ SYMBOLS = [
     "gmg_estimate_error",
     "gmg_build_face_table_resident", "gmg_get_face_table", "gmg_estimate_error_resident", "gmg_get_marks", "gmg_refine_forest_marked",
     "gmg_energy_norm_error_resident",
+    "gmg_output_patches", "gmg_output_patches_resident",
     "gmg_build_point_locator_resident", "gmg_get_point_locator", "gmg_atom_forces_resident", "gmg_electrostatic_energy_resident",
     "gmg_set_copy_indices", "gmg_set_smoother", "gmg_set_coarse", "gmg_set_chebyshev", "gmg_estimate_lmax", "gmg_get_chebyshev",
     "gmg_set_coarse_solver", "gmg_coarse_direct_tables", "gmg_coarse_direct_separable", "gmg_coarse_direct_transform", "gmg_coarse_direct_profile",
@@ -1044,6 +1045,46 @@ class Context:
                                                         C.c_int64(len(q)), D(xyz), D(q), C.c_double(r_c), C.c_int(len(w)), D(qp), D(w), D(sg),
                                                         C.byref(err), D(ce)))
         return err.value, ce
+
+    # ---- the patches of the graphical output
+    def _output_patches(self, call, n_cells, nv, n_dofs, u, n_u, fields, want):
+        from types import SimpleNamespace
+        D = C.c_double
+        n_slots = n_cells * nv
+        fs = [None if f is None else np.ascontiguousarray(f, dtype=np.float64) for f in (fields or [])]
+        out = dict(point=np.zeros((n_slots, 3)), solution=np.zeros(n_slots), grad_phi=np.zeros((n_slots, 3)))
+        pf = [np.zeros(n_slots) for _ in fs]
+        want = tuple(out) + ("patch_field",) if want is None else want
+        ptr = lambda a: _p(a, D) if a is not None and a.size else None
+        fin = (C.POINTER(D) * max(len(fs), 1))(*[ptr(f) for f in fs]) if fs else None
+        fout = (C.POINTER(D) * max(len(fs), 1))(*[ptr(f) for f in pf]) if fs and "patch_field" in want else None
+        ms = C.c_double(0)
+        self._chk(call(u.ptr if u is not None else None, C.c_int64(int((u.n if u is not None else 0) if n_u is None else n_u)), C.c_int(len(fs)), fin,
+                       *[ptr(out[k]) if k in want else None for k in ("point", "solution", "grad_phi")], fout, C.byref(ms)))
+        return SimpleNamespace(point=out["point"], solution=out["solution"], grad_phi=out["grad_phi"], patch_field=pf, build_ms=ms.value)
+
+    def output_patches(self, dim, cell_dofs, cell_level, vertex_of_dof, origin, h0, u, fields=None, n_u=None, n_dofs=None, want=None):
+        """One patch per active cell with 2^dim vertices formed on the device (gmg_output_patches): namespace(point [n_slots, 3],
+        solution [n_slots], grad_phi [n_slots, 3], patch_field [one [n_slots] per field], build_ms).  u: a DeviceVector;
+        fields: up to 8 host vectors [n_dofs]; want: the names of the outputs to ask for (the others are passed as NULL and
+        come back 0), None for all."""
+        nv = 1 << int(dim) if dim in (2, 3) else 8
+        cd = None if cell_dofs is None else np.ascontiguousarray(cell_dofs, dtype=np.int32)
+        lv = None if cell_level is None else np.ascontiguousarray(cell_level, dtype=np.uint8)
+        vk = None if vertex_of_dof is None else np.ascontiguousarray(vertex_of_dof, dtype=np.uint64)
+        n_cells = 0 if lv is None else len(lv)
+        n_dofs = (0 if vk is None else len(vk)) if n_dofs is None else int(n_dofs)
+        opt = lambda a, t: _p(a, t) if a is not None and a.size else None
+        call = lambda *rest: self.L.gmg_output_patches(self.h, C.c_int(int(dim)), C.c_int64(n_cells), opt(cd, C.c_int32), opt(lv, C.c_uint8),
+                                                       opt(vk, C.c_uint64), C.c_int64(n_dofs), C.c_double(origin), C.c_double(h0), *rest)
+        return self._output_patches(call, n_cells, nv, n_dofs, u, n_u, fields, want)
+
+    def output_patches_resident(self, origin, h0, u, fields=None, n_u=None, want=None, dim=None):
+        """output_patches on the resident mesh tables (gmg_output_patches_resident): the same namespace"""
+        n_cells, n_dofs = self._mesh_sizes()
+        call = lambda *rest: self.L.gmg_output_patches_resident(self.h, C.c_double(origin), C.c_double(h0), *rest)
+        dim = getattr(self, "mesh_dim", 3) if dim is None else dim  # (without tables the library refuses the call itself)
+        return self._output_patches(call, n_cells, 1 << int(dim), n_dofs, u, n_u, fields, want)
 
     def synchronize(self):
         self._chk(self.L.gmg_synchronize(self.h))

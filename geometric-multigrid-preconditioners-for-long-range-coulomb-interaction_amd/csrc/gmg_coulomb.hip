@@ -24,6 +24,7 @@
 #include "gmg_assemble.hpp"
 #include "gmg_rhs_cells.hpp"
 #include "gmg_estimate.hpp"
+#include "gmg_output.hpp"
 #include "gmg_fastdiag.hpp"
 #include "gmg_lanczos.hpp"
 #include "gmg_mesh_tables.hpp"
@@ -345,6 +346,7 @@ struct gmg_context {
   int64_t loc_max_dof = -1;  // -1: no locator set
   int force_block = 64;      // workgroup size of the force kernels (gmg_set_option "force_block"); results do not depend on it
   int exact_chunk_log2 = 35;  // gmg_exact.hpp: at most 2^this point-atom evaluations per launch (option "exact_chunk_log2")
+  int output_chunk_log2 = 20;  // gmg_output.hpp: at most 2^this cells per launch, the size of the call's device temporaries (option "output_chunk_log2")
   bool reset_keeps_mesh_tables = false;  // option "reset_keeps_mesh_tables": gmg_reset leaves the mesh tables and their closed lines alone
   int assemble_max_blocks = 0;  // gmg_assemble.hpp: cap on the workgroups of every assembly kernel (option "assemble_max_blocks"; 0: by size); results do not depend on it
   MeshTables mesh;              // gmg_build_mesh_tables: the tables of the last build
@@ -5216,6 +5218,116 @@ int gmg_get_marks(gmg_context *ctx, int64_t *n_cells, uint8_t *mark, int64_t *n_
   return GMG_OK;
 }
 
+// ---- the patches of the graphical output (gmg_output.hpp) ----
+
+// What both entries check of the small arguments, before anything is launched; then output_device: the kernel on cell tables
+// that lie on the device, cut into launches of at most 2^output_chunk_log2 cells whose results are copied out one by one.
+static int output_check_args(gmg_context *ctx, const char *who, int dim, int64_t n_cells, int64_t n_dofs, double h0, const double *u, int64_t n_u,
+                             int n_fields, const double *const *dof_field) {
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (dim != 2 && dim != 3) return bad(GMG_ERR_INVALID, "dim must be 2 or 3");
+  if (n_cells < 0 || n_dofs < 0 || n_u < 0) return bad(GMG_ERR_INVALID, "negative size");
+  if (!(h0 > 0.0) || !std::isfinite(h0)) return bad(GMG_ERR_INVALID, "h0 must be positive");
+  if (n_fields < 0 || n_fields > gmg_output::kMaxFields) return bad(GMG_ERR_INVALID, "n_fields must be in 0 .. 8");
+  if (n_u != n_dofs) return bad(GMG_ERR_INVALID, "n_u differs from n_dofs");
+  if (n_u > 0 && !u) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_fields > 0 && !dof_field) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  for (int j = 0; j < n_fields; ++j)
+    if (n_dofs > 0 && !dof_field[j]) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  if (n_cells >= ((int64_t)1 << 31) >> dim || n_dofs >= ((int64_t)1 << 31)) return bad(GMG_ERR_UNSUPPORTED, "more than 2^31 DoFs or slots");
+  return GMG_OK;
+}
+
+static int output_device(gmg_context *ctx, int dim, int64_t n_cells, int64_t n_dofs, const int32_t *d_cell_dofs, const uint8_t *d_cell_level,
+                         const unsigned long long *d_vertex_of_dof, double origin, double h0, const double *u, int n_fields,
+                         const double *const *dof_field, double *point, double *solution, double *grad_phi, double *const *patch_field, double *build_ms) {
+  if (build_ms) *build_ms = 0.0;
+  if (n_cells == 0) return GMG_OK;
+  (void)hipSetDevice(ctx->device);
+  const int nv = 1 << dim;
+  const int64_t chunk = std::min<int64_t>(n_cells, (int64_t)1 << ctx->output_chunk_log2);
+  const size_t cs = (size_t)chunk * (size_t)nv;  // slots of a launch: what the temporaries hold
+  DevPtr<double> d_point, d_sol, d_grad, d_field[gmg_output::kMaxFields], d_out[gmg_output::kMaxFields];
+  Event e0, e1;
+  gmg_output::PatchArgs a{};
+  a.cell_dofs = d_cell_dofs; a.cell_level = d_cell_level; a.vertex_of_dof = d_vertex_of_dof; a.u = u;
+  a.origin = origin; a.h0 = h0; a.hf = h0 / 4096.0; a.n_fields = n_fields;
+  if (point) { HIPC(d_point.alloc(3 * cs)); a.point = d_point.get(); }
+  if (solution) { HIPC(d_sol.alloc(cs)); a.solution = d_sol.get(); }
+  if (grad_phi) { HIPC(d_grad.alloc(3 * cs)); a.grad_phi = d_grad.get(); }
+  for (int j = 0; j < n_fields; ++j) {
+    if (!patch_field || !patch_field[j]) continue;  // (a field nobody asks for is not uploaded either)
+    HIPC(upload(d_field[j], dof_field[j], (size_t)n_dofs, ctx->stream));
+    HIPC(d_out[j].alloc(cs));
+    a.dof_field[j] = d_field[j].get(); a.patch_field[j] = d_out[j].get();
+  }
+  HIPC(e0.create());
+  HIPC(e1.create());
+  double total_ms = 0.0;
+  for (int64_t c0 = 0; c0 < n_cells; c0 += chunk) {
+    const int64_t c1 = std::min(n_cells, c0 + chunk);
+    const size_t ns = (size_t)(c1 - c0) * (size_t)nv, s0 = (size_t)c0 * (size_t)nv;
+    a.c0 = c0; a.c1 = c1;
+    const dim3 grid = asm_blocks(ctx, (int64_t)ns, gmg_output::kPatchThreads);
+    HIPC(hipEventRecord(e0.get(), ctx->stream));
+    if (dim == 2) hipLaunchKernelGGL(gmg_output::patch_kernel<2>, grid, dim3(gmg_output::kPatchThreads), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(gmg_output::patch_kernel<3>, grid, dim3(gmg_output::kPatchThreads), 0, ctx->stream, a);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(e1.get(), ctx->stream));
+    if (point) HIPC(hipMemcpyAsync(point + 3 * s0, d_point.get(), sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (solution) HIPC(hipMemcpyAsync(solution + s0, d_sol.get(), sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    if (grad_phi) HIPC(hipMemcpyAsync(grad_phi + 3 * s0, d_grad.get(), sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, ctx->stream));
+    for (int j = 0; j < n_fields; ++j)
+      if (a.patch_field[j]) HIPC(hipMemcpyAsync(patch_field[j] + s0, d_out[j].get(), sizeof(double) * ns, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));  // (the temporaries are the next launch's)
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e0.get(), e1.get()) == hipSuccess) total_ms += ms;
+  }
+  if (build_ms) *build_ms = total_ms;
+  RETURN_LAUNCHED(ctx);
+}
+
+int gmg_output_patches(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level, const uint64_t *vertex_of_dof,
+                       int64_t n_dofs, double origin, double h0, const double *u, int64_t n_u, int n_fields, const double *const *dof_field, double *point,
+                       double *solution, double *grad_phi, double *const *patch_field, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_output_patches";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  CHK(output_check_args(ctx, who, dim, n_cells, n_dofs, h0, u, n_u, n_fields, dof_field));
+  if (n_cells > 0 && (!cell_dofs || !cell_level || !vertex_of_dof)) return bad(GMG_ERR_INVALID, "an array of nonzero length is NULL");
+  const int nv = 1 << dim;
+  for (int64_t c = 0; c < n_cells; ++c)
+    if (cell_level[c] > gmg_output::kMaxLevel) return bad(GMG_ERR_INVALID, "cell level above 13");
+  for (int64_t s = 0; s < n_cells * nv; ++s)
+    if (cell_dofs[s] < 0 || cell_dofs[s] >= n_dofs) return bad(GMG_ERR_INVALID, "DoF outside [0, n_dofs)");
+  DevPtr<int32_t> d_cd;
+  DevPtr<uint8_t> d_lv;
+  DevPtr<unsigned long long> d_vk;
+  if (n_cells > 0) {
+    (void)hipSetDevice(ctx->device);
+    HIPC(upload(d_cd, cell_dofs, (size_t)n_cells * nv, ctx->stream));
+    HIPC(upload(d_lv, cell_level, (size_t)n_cells, ctx->stream));
+    HIPC(upload(d_vk, (const unsigned long long *)vertex_of_dof, (size_t)n_dofs, ctx->stream));
+  }
+  return output_device(ctx, dim, n_cells, n_dofs, d_cd.get(), d_lv.get(), d_vk.get(), origin, h0, u, n_fields, dof_field, point, solution, grad_phi,
+                       patch_field, build_ms);
+}
+
+// gmg_output_patches on the resident tables: no mesh array crosses the bus
+int gmg_output_patches_resident(gmg_context *ctx, double origin, double h0, const double *u, int64_t n_u, int n_fields, const double *const *dof_field,
+                                double *point, double *solution, double *grad_phi, double *const *patch_field, double *build_ms) {
+  if (!ctx) return GMG_ERR_INVALID;
+  const char *who = "gmg_output_patches_resident";
+  auto bad = [&](int code, const char *msg) { return fail(ctx, code, (std::string(who) + ": " + msg).c_str()); };
+  if (ctx->dist) return bad(GMG_ERR_UNSUPPORTED, "not on a communicator");
+  const MeshTables &m = ctx->mesh;
+  if (!m.valid) return bad(GMG_ERR_INVALID, "the context holds no mesh tables (gmg_build_mesh_tables)");
+  CHK(output_check_args(ctx, who, m.dim, m.n_cells, m.n_dofs, h0, u, n_u, n_fields, dof_field));
+  return output_device(ctx, m.dim, m.n_cells, m.n_dofs, m.cell_dofs.get(), m.cell_level.get(), m.vertex_of_dof.get(), origin, h0, u, n_fields, dof_field,
+                       point, solution, grad_phi, patch_field, build_ms);
+}
+
 // gmg_energy_norm_error on the resident cell_dofs and on the geometry dr_geometry_kernel forms (DESIGN.md sections 23, 24)
 int gmg_energy_norm_error_resident(gmg_context *ctx, double origin, double h0, const double *u, int64_t n_u, int64_t n_atoms, const double *atom_xyz,
                                    const double *atom_q, double r_c, int nq, const double *quadrature_points, const double *weights,
@@ -5463,6 +5575,10 @@ int gmg_set_option(gmg_context *ctx, const char *key, double value) {
   else if (k == "exact_chunk_log2") {
     if (!(value >= 0 && value <= 35) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "exact_chunk_log2: an integer in 0 .. 35");
     ctx->exact_chunk_log2 = (int)value;
+  }
+  else if (k == "output_chunk_log2") {
+    if (!(value >= 0 && value <= 30) || value != (double)(int)value) return fail(ctx, GMG_ERR_INVALID, "output_chunk_log2: an integer in 0 .. 30");
+    ctx->output_chunk_log2 = (int)value;
   }
   else if (k == "cheb_polynomial") {
     if (value != GMG_CHEB_FIRST_KIND && value != GMG_CHEB_FOURTH_KIND) return fail(ctx, GMG_ERR_INVALID, "cheb_polynomial: 0 (first kind) or 1 (fourth kind)");

@@ -598,6 +598,32 @@ int step50_estimator_inputs(step50_problem *h, int32_t *cell_dofs, uint8_t *cell
   });
 }
 
+// ---- graphical output.  step50_output_results writes solution-CCCCC.0000.vtu, .pvtu and .visit of the
+// current solution and estimate into `directory` (NULL: the prm's "Output directory"), whether or not "Output results" is set.
+// step50_output_patches: the patch arrays alone, point [slots][3], solution [slots], grad_phi [slots][3] with slots =
+// step50_n_cells * 2^dim (any may be null); where: 0 the host mirror, 1 the device (the resident tables where the context
+// holds this cycle's and the solution, else host arrays).  step50_output_path: where the last output_results formed them
+// (0 host mirror, 1 gmg_output_patches, 2 gmg_output_patches_resident)
+int step50_output_results(step50_problem *h, int cycle, const char *directory) {
+  return guarded(h, [&] {
+    auto run = [&](auto &P) {
+      if (P.reports.empty()) throw std::runtime_error("step50_output_results: no cycle has run");
+      P.write_output_files((unsigned)cycle, directory ? std::string(directory) : P.par.output_directory);
+    };
+    if (h->dim == 2) run(*h->p2); else run(*h->p3);
+    return 0;
+  });
+}
+int step50_output_patches(step50_problem *h, int where, double *point, double *solution, double *grad_phi) {
+  return guarded(h, [&] {
+    auto run = [&](auto &P) {
+      return P.output_patches(where == 0 ? P.kPatchesMirror : P.patches_on_device(), 0, nullptr, point, solution, grad_phi, nullptr);
+    };
+    return h->dim == 2 ? run(*h->p2) : run(*h->p3);
+  });
+}
+int step50_output_path(step50_problem *h) { return h->dim == 2 ? (int)h->p2->output_path : (int)h->p3->output_path; }
+
 // host threads of the replicated setup (one process per GPU: cores / world size)
 void step50_set_threads(int n) {
 #ifdef _OPENMP

@@ -7,6 +7,7 @@
 #include "partition.h"
 #include "../gmg_forces.hpp"
 #include "../gmg_exact.hpp"
+#include "../gmg_output.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -295,7 +296,12 @@ void ParameterReader::declare_parameters() {
             // the exact free-space potential summed over all atoms in batches (gmg_exact.hpp): the
             // Exact boundary values and the error norm on the device (or by its host mirror), and with it the error norm
             // beyond the reference's 300-atom gate (:1554-1556)
-            {"Analytical solution on device", "false"}, {"Error norm for large systems", "false"}};
+            {"Analytical solution on device", "false"}, {"Error norm for large systems", "false"},
+            // the reference's output_results (:1149-1308) after every cycle's estimate: solution-CCCCC.0000.vtu with the
+            // potential, grad_phi = -grad phi_h, the indicators and, on request of the reference's three output keys, the
+            // analytical solution, the interpolated right-hand side and the atoms' supports; a .pvtu and a .visit record beside
+            // it.  The patches are formed on the device where the cycle ran there (gmg_output_patches)
+            {"Output results", "false"}, {"Output directory", "."}};
 }
 void ParameterReader::parse_input_from_string(const std::string &text) {
   std::istringstream in(text);
@@ -396,6 +402,8 @@ Parameters Parameters::from(const ParameterReader &prm) {  // src/main.cc:25-68
   p.direct_coulomb_check = prm.get_bool("Direct Coulomb check");
   p.analytical_on_device = prm.get_bool("Analytical solution on device");
   p.error_norm_for_large_systems = prm.get_bool("Error norm for large systems");
+  p.output_results = prm.get_bool("Output results");
+  p.output_directory = prm.get("Output directory");
   p.level0_numbering = prm.get("Level 0 numbering");
   if (p.level0_numbering != "lexicographic" && p.level0_numbering != "cell-wise")
     throw std::runtime_error("Level 0 numbering must be <lexicographic> or <cell-wise>");
@@ -2803,6 +2811,7 @@ std::vector<double> LaplaceProblem<dim>::total_charge_density_vector() const {
 template <int dim>
 void LaplaceProblem<dim>::finish_cycle() {
   estimate_error_and_mark_cells();                                               // :1552
+  if (par.output_results) output_results((unsigned)reports.back().cycle);       // :1553
   energy_forces_resident = decide_energy_forces_resident();
   if (lammpsinput && (number_of_atoms < 300 || (par.energy_for_large_systems && par.short_range_cutoff > 0.0))) {
     postprocess_electrostatic_energy();     // :1554-1555
@@ -2837,6 +2846,7 @@ void LaplaceProblem<dim>::run() {
 }  // namespace step50
 
 #include "adaptive.inc"
+#include "output.inc"
 
 namespace step50 {
 template class LaplaceProblem<2>;

@@ -96,6 +96,10 @@ struct Parameters {
   bool estimator_on_device = false;      // gmg_estimate_error instead of the host loops of estimate_error_and_mark_cells (cycle on the device, one rank)
   std::string level0_numbering = "lexicographic";  // lexicographic | cell-wise (deal.II's first-touch order): level 0 carries no smoother
   std::string coarse_solver = "CG";  // CG (the reference, :962-967) | direct (gmg_set_coarse_solver: fast diagonalisation on a lattice level 0)
+  // graphical output (the reference's output_results, :1149-1308).  The three flags above that the
+  // reference reads there -- flag_analytical_solution, flag_rhs_field, flag_atoms_support -- select the optional arrays.
+  bool output_results = false;         // "Output results": write solution-CCCCC.0000.vtu, .pvtu and .visit after every cycle's estimate
+  std::string output_directory = ".";  // "Output directory"
   static Parameters from(const ParameterReader &prm);
 };
 
@@ -225,6 +229,22 @@ class LaplaceProblem {
   bool marks_resident = false;            // the context holds the marks of refine_flags (until the next estimate or mesh)
   bool estimator_resident_fallback_reported = false;
   void face_table(std::vector<uint8_t> &face_kind, std::vector<int32_t> &face_cell) const;  // the forest's faces by kind
+  // Graphical output (csrc/host/output.inc).  output_results: the three files of one cycle in
+  // par.output_directory (rank 0 alone writes, one piece); write_output_files: the same into a given directory.
+  void output_results(unsigned int cycle);                               // :1149-1308
+  void write_output_files(unsigned int cycle, const std::string &directory);
+  // One patch per active cell, 2^dim vertices each: point [slots][3], solution [slots], grad_phi [slots][3] and the gathered
+  // DoF vectors patch_field[j] [slots] (any output may be null).  path: kPatchesMirror the host mirror of gmg_output.hpp,
+  // kPatchesHostArrays gmg_output_patches, kPatchesResident gmg_output_patches_resident.
+  enum PatchPath { kPatchesMirror = 0, kPatchesHostArrays = 1, kPatchesResident = 2 };
+  int output_patches(PatchPath path, int n_fields, const double *const *dof_field, double *point, double *patch_solution, double *grad_phi,
+                     double *const *patch_field, double *build_ms = nullptr);
+  PatchPath patches_on_device() const {  // where an explicit "on the device" forms them
+    return operators_resident && device_solution() != nullptr && !distributed ? kPatchesResident : kPatchesHostArrays;
+  }
+  PatchPath decide_output_patches();     // where this cycle's patches are formed; says so once per fallback
+  bool output_host_arrays_reported = false, output_mirror_reported = false;
+  PatchPath output_path = kPatchesMirror;  // where the last output_results formed its patches
   void refine_grid(unsigned int cycle);                                  // :1095-1121
   // "Refinement on device" 
   bool refinement_applies() const { return par.refinement_on_device && solve_on_device_requested && !distributed; }

@@ -108,6 +108,11 @@ def prm_text(**kw) -> str:
         "direct_coulomb_check": ("Misc", "Direct Coulomb check"),
         "analytical_on_device": ("Misc", "Analytical solution on device"),
         "error_norm_for_large_systems": ("Misc", "Error norm for large systems"),
+        "output_analytical": ("Misc", "Output and calculation of Analytical solution"),
+        "output_rhs_field": ("Misc", "Output of RHS field"),
+        "output_atom_support": ("Misc", "Output of support of each atom"),
+        "output_results": ("Misc", "Output results"),
+        "output_directory": ("Misc", "Output directory"),
     }
     sections = {}
     for k, v in kw.items():
@@ -554,6 +559,28 @@ class Problem:
         out = np.zeros(self.L.step50_n_cells(self.h), dtype=np.float32)
         self.L.step50_error_per_cell(self.h, out.ctypes.data_as(C.POINTER(C.c_float)))
         return out
+
+    def output_results(self, cycle, directory=None):
+        """Write solution-CCCCC.0000.vtu, solution-CCCCC.pvtu and solution-CCCCC.visit of the current solution and estimate
+        into `directory` (None: the prm's "Output directory"), whether or not "Output results" is set (DESIGN.md section
+        35).  Returns the path the patches took: 0 host mirror, 1 gmg_output_patches, 2 gmg_output_patches_resident."""
+        self._chk(self.L.step50_output_results(self.h, C.c_int(int(cycle)), None if directory is None else os.fsencode(directory)), "output_results")
+        return int(self.L.step50_output_path(self.h))
+
+    def output_path(self) -> int:
+        """Where the last output_results (the cycle's or an explicit one) formed its patches: 0, 1 or 2 as above."""
+        return int(self.L.step50_output_path(self.h))
+
+    def output_patches(self, on_device=False):
+        """The patch arrays of the graphical output, one patch per active cell with 2^dim vertices: (point [slots, 3],
+        solution [slots], grad_phi [slots, 3]).  on_device False: the host mirror; True: the device (the resident mesh tables
+        where the context holds them and the solution, else host arrays)."""
+        self.L.step50_n_cells.restype = C.c_int64
+        ns = self.L.step50_n_cells(self.h) << int(self.L.step50_dim(self.h))
+        pt, sol, g = np.zeros((ns, 3)), np.zeros(ns), np.zeros((ns, 3))
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self.L.step50_output_patches(self.h, C.c_int(1 if on_device else 0), P(pt), P(sol), P(g)), "output_patches")
+        return pt, sol, g
 
     def marks(self):
         """The refinement marks of the last estimate per active cell (uint8)."""

@@ -809,6 +809,39 @@ int gmg_energy_norm_error_resident(gmg_context *ctx, double origin, double h0, c
                                    const double *atom_xyz, const double *atom_q, double r_c, int nq, const double *quadrature_points,
                                    const double *weights, const double *shape_grad, double *error, double *cell_err2);
 
+/* The patches of the graphical output (the reference's output_results, src/step-50.cc:1149-1308: what deal.II's
+ * DataOut::build_patches(0) forms) on the device.  One patch per active cell with nv = 2^dim patch
+ * vertices and nothing shared between cells: slot s = a * nv + v, vertex v = bx + 2 by + 4 bz.  cell_dofs [n_cells * nv],
+ * cell_level [n_cells], vertex_of_dof [n_dofs] (21 bits per direction on the level-12 lattice, as gmg_get_mesh_tables returns
+ * them) and up to 8 DoF vectors dof_field[j] [n_dofs] are host arrays; u is a device vector of n_u = n_dofs entries.
+ * Values (fp64, no contraction into fused multiply-adds, this operand order), k = vertex_of_dof[cell_dofs[s]]:
+ *   point[3 s + d]    = origin + (h0 / 4096.0) * (double)((k >> 21 d) & 0x1fffff) for d < dim, +0.0 for d >= dim: the bits of
+ *                       the driver's vertex coordinates, so duplicated vertices of neighbouring cells coincide exactly;
+ *   U[v] = u[cell_dofs[a * nv + v]];   solution[s] = U[v];
+ *   g = (U[v | 1 << d] - U[v & ~(1 << d)]) / h_l,  h_l = h0 / (double)(1 << cell_level[a])  (g_c of gmg_estimate_error);
+ *   grad_phi[3 s + d] = -g for d < dim, +0.0 for d >= dim;
+ *   patch_field[j][s] = dof_field[j][cell_dofs[s]].
+ * The outputs point [n_cells * nv * 3], solution [n_cells * nv], grad_phi [n_cells * nv * 3], patch_field[j] [n_cells * nv]
+ * and build_ms (device time of the kernels) are host memory; any of them, patch_field itself included, may be NULL and is then
+ * skipped.  The work is cut into launches of at most 2^k cells, k = option output_chunk_log2; the device temporaries of the
+ * call hold one launch's results (56 bytes per slot and 8 per gathered field).  Every value has one writer and no sum: the
+ * results depend neither on k nor on the launch shape (option assemble_max_blocks).  Nothing is kept in the context.
+ * GMG_ERR_INVALID -- found on the host, before anything is launched -- for dim other than 2 or 3, a level above 13, a DoF
+ * outside [0, n_dofs), n_u other than n_dofs, n_fields outside 0 .. 8, h0 <= 0, or a NULL input of nonzero length;
+ * GMG_ERR_UNSUPPORTED on a context with a communicator.  Zero cells are valid.                                              */
+int gmg_output_patches(gmg_context *ctx, int dim, int64_t n_cells, const int32_t *cell_dofs, const uint8_t *cell_level,
+                       const uint64_t *vertex_of_dof, int64_t n_dofs, double origin, double h0, const double *u, int64_t n_u,
+                       int n_fields, const double *const *dof_field, double *point, double *solution, double *grad_phi,
+                       double *const *patch_field, double *build_ms);
+/* gmg_output_patches_resident -- gmg_output_patches applied to dim, n_cells, n_dofs, cell_dofs, cell_level and vertex_of_dof
+ * of the tables the last gmg_build_mesh_tables left on the device: the same kernel, the same bits, and no mesh array crosses
+ * the bus.  The sibling's host loops over the mesh arrays are not repeated (the tables are in range by construction).
+ * GMG_ERR_INVALID when the context holds no mesh tables, for n_u other than the tables' n_dofs, and for what the sibling
+ * refuses of the remaining arguments; GMG_ERR_UNSUPPORTED on a context with a communicator.                                 */
+int gmg_output_patches_resident(gmg_context *ctx, double origin, double h0, const double *u, int64_t n_u, int n_fields,
+                                const double *const *dof_field, double *point, double *solution, double *grad_phi,
+                                double *const *patch_field, double *build_ms);
+
 /* Energy and forces at the atoms on the tables the last gmg_build_mesh_tables left on the device.  What
  * the four entries below share: GMG_ERR_UNSUPPORTED on a context with a communicator and for 2D tables; GMG_ERR_INVALID when
  * the context holds no mesh tables; zero cells and zero atoms are valid (without cells phi_h and the field are 0).  The
@@ -899,7 +932,9 @@ int gmg_set_tuning(gmg_context *ctx, int coarse_chunk, int cg_variant);
  * sgs_lds_bytes_override (tests: a value over the CU's 160 KB makes the sweep's launch fail -> GMG_ERR_HIP), force_block (64 | 128 |
  * 256: workgroup size of the force kernels and of the exact-potential kernels; the results do not depend on it),
  * exact_chunk_log2 (0 .. 35, default 35: gmg_gaussian_potential and gmg_energy_norm_error do at most 2^k point-atom
- * evaluations per launch; tests force many launches on small inputs, the results do not depend on it), density_segment
+ * evaluations per launch; tests force many launches on small inputs, the results do not depend on it), output_chunk_log2
+ * (0 .. 30, default 20: gmg_output_patches forms at most 2^k cells per launch, which is also the size of its device
+ * temporaries; the results do not depend on it), density_segment
  * (0 .. 2047, default 0 = by nq: atoms per LDS segment of gmg_charge_density_resident, made odd and fitted to the group size
  * and to 64 KB per workgroup; the results do not depend on it), reset_keeps_mesh_tables
  * (0 / 1, default 0: while it is 1, gmg_reset leaves the tables of gmg_build_mesh_tables and the closed lines of
